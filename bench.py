@@ -65,6 +65,9 @@ def main():
                     help="how the passes in flight are requested: batch = fpt_pt_render_batch(first, n) (default); render = the reference's calling convention, one "
                          "fpt_pt_render(instance) call per pass, with the library deferring and batching them (fpt_pt_set_deferred) -- same kernels, same frame")
     ap.add_argument("--no-extra", action="store_true", help="skip the second, harder scene (extra.testball_room) of the default single-GPU run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame buffer the timed path left after its last step to DIR/framebuffer.npy: its 8 float32 RGBA "
+                         "channels at a fixed, seeded sample of 2^18 pixels (32 MB); one GPU only")
     ap.add_argument("--workload", choices=("bathroom2", "standin", "testball-room", "water-caustic"), default=None,
                     help="default: bathroom2 for --renderer pt / psfpt, water-caustic for --renderer bpt (BASELINE configs[4]: the bidirectional tracer on water_caustic).  "
                          "water-caustic (round 5) = the reference's own models/water_caustic/water_caustic.mtl and water_caustic.fa camera on procedural geometry "
@@ -77,6 +80,8 @@ def main():
     args = ap.parse_args()
     if args.workload is None:
         args.workload = "water-caustic" if args.renderer == "bpt" else "bathroom2"
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs needs --gpus 1 (under N-way sharding no rank holds the whole frame buffer)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)
     if args.renderer != "pt":
@@ -269,6 +274,8 @@ def bench_scene(env, args, s, workload, W, H, full):
     timings = r.collect_timings()
     union = r.union_timings()
     r.set_profiling(0)
+    if full and args.dump_outputs:          # before the instrumented re-run below renders the same passes again
+        dump_outputs(r, args.dump_outputs)
     # the other scaling mode, measured the same way in a second timed region (N > 1 only: at N = 1 the two coincide)
     other = None
     if world > 1 and full:
@@ -452,7 +459,7 @@ def main_widened(args, kind=None, quick_steps=None):
         else:
             dist.init_process_group(backend, rank=rank, world_size=world)
     W, H = CONFIGS[args.config]
-    K = min(args.steps, 128)             # passes of several ms each: 128 steps already average over the launch noise
+    K = args.steps
     if as_extra:
         K = quick_steps
     # BPT and PSFPT keep passes in flight like the PT (fpt_bpt_render_batch, fpt_psfpt_render_batch: the PSFPT's passes are independent until
@@ -550,6 +557,8 @@ def main_widened(args, kind=None, quick_steps=None):
         elapsed = float(te.item())
     timings = r.collect_timings()
     r.set_profiling(0)
+    if not as_extra and args.dump_outputs:
+        dump_outputs(r, args.dump_outputs)
     # instrumented re-run of the same passes from the same starting state (PSFPT's cache and frame carry over between passes)
     r.close()
     r, sp = make()
@@ -612,6 +621,16 @@ def main_widened(args, kind=None, quick_steps=None):
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(r, out_dir):
+    """--dump-outputs: the frame buffer a caller of the timed path reads after its last pass (Renderer.framebuffer(): 8 channels x pixels x RGBA, float32;
+    184 MB at 1600x900), at a fixed, seeded sample of 2^18 pixels, the same for every channel and every run: DIR/framebuffer.npy, (8, 262144, 4), 32 MB"""
+    fb = r.framebuffer()
+    n = fb.shape[1]
+    idx = np.sort(np.random.default_rng(0).choice(n, min(n, 1 << 18), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "framebuffer.npy"), np.ascontiguousarray(fb[:, idx], np.float32))
 
 
 def cap_frac(rf):

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Regenerates tests/golden/ply_cases.npz: what the reference's own PLY parser (rply 1.01, driven like MeshBase::loadFromPly by
-oracle/_ref/ply_dump -- `make -C oracle ref`, needs /root/reference) returns for the files of tests/ply_cases.py.
+oracle/_ref/ply_dump -- `make -C oracle ref`, needs /root/reference) returns for the files of tests/ply_cases.py, and
+tests/golden/ply_models.json: the digests of what it returns for the reference's material-testball models (shipped byte-identical
+under fermat_amd/data/scenes/testball_room).
 Run from the repo root in the build container:  python tests/golden/make_ply_golden.py"""
-import os, subprocess, sys, tempfile
+import hashlib, json, os, subprocess, sys, tempfile
 
 import numpy as np
 
@@ -27,7 +29,23 @@ def ref_dump(path):
     return dict(P=P.copy(), N=N.copy(), T=T.copy(), tri=tri.copy())
 
 
+def digest(a):
+    """[shape, sha256 of the bytes]: tests/test_ply.py computes the same of the loaders' float32 / int32 arrays"""
+    a = np.ascontiguousarray(a)
+    return [list(a.shape), hashlib.sha256(a.tobytes()).hexdigest()]
+
+
 if __name__ == "__main__":
+    models = {}
+    for name in ("Mesh000", "Mesh001", "Mesh002"):
+        path = os.path.join(ROOT, "fermat_amd", "data", "scenes", "testball_room", name + ".ply")
+        r = ref_dump(path)
+        assert r is not None, name
+        models[name] = dict(file_sha256=hashlib.sha256(open(path, "rb").read()).hexdigest(), **{k: digest(v) for k, v in r.items()})
+        print(name, {k: v.shape for k, v in r.items()})
+    with open(os.path.join(ROOT, "tests", "golden", "ply_models.json"), "w") as f:
+        json.dump(models, f, indent=1)
+        f.write("\n")
     with tempfile.TemporaryDirectory() as d:
         files = ply_cases.cases(d)
         out = {}

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -37,8 +38,17 @@ def check_contract(j, steps, warmup):
     assert "traffic_source" in r
 
 
-def test_headline_line_with_cpu_baseline():
-    j = run_bench("--steps", "4", "--warmup", "2", "--no-extra")        # (the default run adds extra.{standin_r1_r3, testball_room, bpt, psfpt})
+def check_dump(d):
+    """--dump-outputs: the frame buffer after the last timed pass, all 8 channels at a seeded sample of 2^18 pixels, float32, within 64 MB"""
+    assert os.listdir(d) == ["framebuffer.npy"]
+    assert os.path.getsize(os.path.join(d, "framebuffer.npy")) <= 64 << 20
+    fb = np.load(os.path.join(d, "framebuffer.npy"))
+    assert fb.shape == (8, 1 << 18, 4) and fb.dtype == np.float32 and np.isfinite(fb).all()
+    assert fb[5, :, :3].max() > 0.0          # COMPOSITED_C: the image is not empty
+
+
+def test_headline_line_with_cpu_baseline(tmp_path):
+    j = run_bench("--steps", "4", "--warmup", "2", "--no-extra", "--dump-outputs", str(tmp_path / "out"))        # (the default run adds extra.{standin_r1_r3, testball_room, bpt, psfpt})
     assert "bathroom2-standin-r4" in j["config"]["workload"] and j["config"]["triangles"] > 1500000
     check_contract(j, 4, 2)
     assert "PT" in j["metric"] and j["config"]["passes_in_flight"] == 4 and j["config"]["max_path_length"] == 9
@@ -50,12 +60,14 @@ def test_headline_line_with_cpu_baseline():
         assert k in c, k
     assert c["kind"] in ("port", "reference") and c["cores"] >= 1 and c["value"] > 0 and c["unit"] == "Msample/s"
     assert j["value"] > 20 * c["value"]                      # sanity only: the ratio says nothing about kernel quality
+    check_dump(tmp_path / "out")
 
 
 @pytest.mark.parametrize("renderer", ["bpt", "psfpt"])
-def test_widened_lines(renderer):
-    j = run_bench("--renderer", renderer, "--steps", "4", "--warmup", "2", "--no-cpu-baseline")
+def test_widened_lines(renderer, tmp_path):
+    j = run_bench("--renderer", renderer, "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "out"))
     check_contract(j, 4, 4 if renderer in ("bpt", "psfpt") else 2)
     assert renderer.upper() in j["metric"] and "cpu_baseline" not in j
     # configs[4] in kind: the bidirectional tracer's line runs on the water_caustic stand-in (the reference's own .mtl and camera), the PSFPT's on the headline scene
     assert ("water_caustic-standin" if renderer == "bpt" else "bathroom2-standin-r4") in j["config"]["workload"]
+    check_dump(tmp_path / "out")

@@ -17,7 +17,7 @@ from fermat_amd import scene
 from oracle import binding as ob
 
 HERE = os.path.join(scene.DATA_DIR, "scenes", "water_caustic_standin")
-REF = "/root/reference/models/water_caustic"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 @pytest.fixture(scope="module")
@@ -48,14 +48,11 @@ def host_threads():
 
 # ---- CPU ---------------------------------------------------------------------------------------------------------------------------------------------------
 def test_the_material_file_and_camera_are_the_references_own():
-    """water_caustic.mtl / camera.txt / readme.txt are byte-for-byte the reference's (sha256 pinned; compared with the checkout where it exists), and the .fa's
-    camera line is water_caustic.fa's"""
-    for name in ("water_caustic.mtl", "camera.txt", "readme.txt"):
-        mine = open(os.path.join(HERE, name), "rb").read()
-        if os.path.isdir(REF):
-            assert mine == open(os.path.join(REF, name), "rb").read(), name
+    """water_caustic.mtl / camera.txt / readme.txt are byte-for-byte the reference's (sha256 pinned), and the .fa's camera line is water_caustic.fa's
+    (tests/golden/water_caustic.fa: the reference's file, verbatim)"""
+    for name, digest in REF_SHA256.items():
+        assert hashlib.sha256(open(os.path.join(HERE, name), "rb").read()).hexdigest() == digest, name
     mtl = open(os.path.join(HERE, "water_caustic.mtl")).read()
-    assert hashlib.sha256(open(os.path.join(HERE, "water_caustic.mtl"), "rb").read()).hexdigest() == MTL_SHA256
     # the facts the stand-in rests on, read off the text: the Water material and the two emitters
     blocks = {b.split()[0]: b for b in mtl.split("newmtl ")[1:]}
     assert set(blocks) == {"Green", "Red", "Silver", "Water", "White", "Light", "Light2"}
@@ -64,11 +61,14 @@ def test_the_material_file_and_camera_are_the_references_own():
     fa_text = open(os.path.join(HERE, "water_caustic_standin.fa")).read()
     cam = "Camera persp eye 2.800000 3.487043 11.134270 aim 2.800000 2.043976 -3.464071 up 0 1 0 fov 0.873"
     assert cam in fa_text
-    if os.path.isdir(REF):
-        assert cam in open(os.path.join(REF, "water_caustic.fa")).read()
+    assert cam in open(os.path.join(GOLDEN, "water_caustic.fa")).read()
 
 
-MTL_SHA256 = "1611a2c27b5f95e2fbea3b4ee170156c6bf37698c1c90f7245c0cb82a3025661"          # of /root/reference/models/water_caustic/water_caustic.mtl
+REF_SHA256 = {          # of the reference's models/water_caustic files
+    "water_caustic.mtl": "1611a2c27b5f95e2fbea3b4ee170156c6bf37698c1c90f7245c0cb82a3025661",
+    "camera.txt": "a2b09ec5563b6a1eef29a68b9fadea1a3573849001db0b5522cd4b4fe8e6c8f2",
+    "readme.txt": "48531c80246d61947a0f4f076b2f5f8ba20b8c968d21a83263bee424b8b629ad",
+}
 
 
 def test_the_loaded_scene_holds_what_the_mtl_says(water):

@@ -77,10 +77,14 @@ def main():
     a = ap.parse_args()
     path = a.listing
     if a.build or not path:
-        path = os.path.join(tempfile.gettempdir(), "fpt_trace_isa_classes.s")
-        subprocess.check_call(["hipcc", "--offload-arch=gfx950"] + STD + ["-S", "--cuda-device-only", os.path.join(ROOT, "fermat_amd", "csrc", "fpt_trace.hip"), "-o", path],
-                              stderr=subprocess.DEVNULL)
-    name, body = kernel_body(open(path).read(), a.kernel)
+        with tempfile.TemporaryDirectory() as d:          # private: a fixed name in the shared temp dir collides with other users' and concurrent runs
+            path = os.path.join(d, "fpt_trace.s")
+            subprocess.check_call(["hipcc", "--offload-arch=gfx950"] + STD + ["-S", "--cuda-device-only", os.path.join(ROOT, "fermat_amd", "csrc", "fpt_trace.hip"), "-o", path],
+                                  stderr=subprocess.DEVNULL)
+            text = open(path).read()
+    else:
+        text = open(path).read()
+    name, body = kernel_body(text, a.kernel)
     node, tri = sections(body)
     cn, ct = census(node), census(tri)
     # the mix a ray executes: node steps and triangle tests weighted by their per-ray counts
