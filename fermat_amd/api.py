@@ -152,7 +152,7 @@ ENTRY_POINTS = ["fpt_create", "fpt_destroy", "fpt_last_error", "fpt_stream", "fp
                 "fpt_rt_trace_shadow", "fpt_rt_trace_shadow_bits", "fpt_rt_trace_counted", "fpt_rt_bvh_info", "fpt_rt_bvh_stats", "fpt_sequence_setup",
                 "fpt_sequence_set_instance", "fpt_sequence_download", "fpt_mesh_lights_init", "fpt_mesh_lights_download", "fpt_pt_init",
                 "fpt_pt_render", "fpt_pt_set_batch", "fpt_pt_render_batch", "fpt_pt_get_stats", "fpt_pt_set_profiling", "fpt_pt_collect_timings", "fpt_pt_set_counting", "fpt_pt_get_trace_counters", "fpt_pt_set_capture", "fpt_pt_get_captured", "fpt_rescale_frame",
-                "fpt_update_variances", "fpt_to_rgba", "fpt_to_rgba_mode", "fpt_filter_variance", "fpt_eaw", "fpt_filter", "fpt_debug_math",
+                "fpt_update_variances", "fpt_to_rgba", "fpt_to_rgba_mode", "fpt_filter_variance", "fpt_eaw", "fpt_filter", "fpt_debug_math", "fpt_debug_bsdf",
                 "fpt_psfpt_init", "fpt_psfpt_render", "fpt_psfpt_download_cells", "fpt_psfpt_set_sharded", "fpt_psfpt_exchange_cells",
                 "fpt_psfpt_export_cells", "fpt_psfpt_import_cells", "fpt_psfpt_finish", "fpt_psfpt_set_batch", "fpt_psfpt_render_batch", "fpt_psfpt_set_deferred",
                 "fpt_bpt_init", "fpt_bpt_render", "fpt_bpt_set_batch", "fpt_bpt_render_batch", "fpt_bpt_set_deferred", "fpt_bpt_get_stats", "fpt_bpt_set_profiling", "fpt_bpt_download_light_vertices",
@@ -756,3 +756,26 @@ class Renderer:
         self._check(self.L.fpt_debug_math(self.ctx, C.c_int(op), C.c_uint32(len(a)), C.c_void_p(da.data_ptr()), C.c_void_p(db.data_ptr()),
                                           C.c_void_p(o0.data_ptr()), C.c_void_p(o1.data_ptr())))
         return o0.cpu().numpy(), o1.cpu().numpy()
+
+    def debug_bsdf(self, op, rec, mats, table, flags=0, vary=None, as_tensor=False):
+        """fpt_debug_bsdf: one function of the device surface model per element (layouts: include/fermat_pt_hip.h).  rec: (n, 32) float32 records, or ONE record
+        (shape (32,)) that every element reads, then with `vary` (n, 3) supplying each element's w_o / z; mats: scene.MATERIAL_DTYPE records.  Returns (n, 16) float32
+        (as_tensor: the device tensor, for reductions that stay on the GPU)."""
+        torch = self.torch
+        rec = np.ascontiguousarray(rec, np.float32); mats = np.ascontiguousarray(mats)
+        broadcast = rec.ndim == 1
+        if broadcast and vary is None:
+            raise ValueError("a broadcast record needs `vary`")
+        n = len(vary) if broadcast else len(rec)
+        assert rec.shape[-1] == 32 and mats.dtype.itemsize == 208 and len(mats) > 0 and (vary is None or np.shape(vary) == (n, 3))
+        dr = torch.from_numpy(rec.reshape(-1)).to(self.dev)
+        dm = torch.from_numpy(mats.view(np.uint8).reshape(-1)).to(self.dev)
+        dt = torch.from_numpy(np.ascontiguousarray(table, np.float32)).to(self.dev)
+        dv = torch.from_numpy(np.ascontiguousarray(vary, np.float32)).to(self.dev) if vary is not None else None
+        out = torch.zeros(max(n, 1) * 16, dtype=torch.float32, device=self.dev)
+        torch.cuda.synchronize(self.dev)
+        self._check(self.L.fpt_debug_bsdf(self.ctx, C.c_int(op), C.c_uint32(flags), C.c_uint32(n), C.c_void_p(dm.data_ptr()), C.c_uint32(len(mats)),
+                                          C.c_void_p(dt.data_ptr()), C.c_void_p(dr.data_ptr()), C.c_uint32(0 if broadcast else 32),
+                                          C.c_void_p(dv.data_ptr() if dv is not None else None), C.c_void_p(out.data_ptr())))
+        out = out[:n * 16].reshape(n, 16)
+        return out if as_tensor else out.cpu().numpy()

@@ -13,6 +13,12 @@
 
 using namespace fpt;
 
+namespace fpt {
+// the BSDF probe's launcher (fpt_pt.hip), declared here rather than in fpt_kernels.h: test infrastructure, not part of the wavefront's launch set
+void launch_debug_bsdf(int op, uint32_t flags, uint32_t n, const fpt_material* mats, uint32_t n_mats, const float* table, const float* rec, uint32_t rec_stride,
+                       const float* vary, float* out, hipStream_t s);
+}
+
 namespace {
 
 thread_local std::string g_create_error;
@@ -1099,5 +1105,17 @@ int fpt_debug_refit_bvh(uint32_t tri_count, const int32_t* h_idx, uint32_t verte
 
 int fpt_debug_math(fpt_context* ctx, int op, uint32_t n, const float* d_in0, const float* d_in1, float* d_out0, float* d_out1)
 { return guarded(ctx, [&] { launch_debug_math(op, n, d_in0, d_in1, d_out0, d_out1, ctx->stream); FPT_HIP_CHECK(hipGetLastError()); FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream)); }); }
+
+int fpt_debug_bsdf(fpt_context* ctx, int op, uint32_t flags, uint32_t n, const fpt_material* d_mats, uint32_t n_mats, const float* d_table,
+                   const float* d_rec, uint32_t rec_stride, const float* d_vary, float* d_out)
+{
+	return guarded(ctx, [&] {
+		if (op < 0 || op > 13) throw std::runtime_error("fpt_debug_bsdf: unknown op");
+		if (n && (!d_mats || !n_mats || !d_table || !d_rec || !d_out)) throw std::runtime_error("fpt_debug_bsdf: null array");
+		if (rec_stride != 0 && rec_stride != 32) throw std::runtime_error("fpt_debug_bsdf: rec_stride must be 0 or 32");
+		launch_debug_bsdf(op, flags, n, d_mats, n_mats, d_table, d_rec, rec_stride, d_vary, d_out, ctx->stream);
+		FPT_HIP_CHECK(hipGetLastError()); FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	});
+}
 
 } // extern "C"

@@ -805,6 +805,84 @@ __global__ void debug_math_kernel(int op, uint32_t n, const float* in0, const fl
 	else if (op == 2) out0[i] = det_pow(in0[i], in1[i]);
 	else if (op == 3) out0[i] = round_through_half(in0[i]);
 	else if (op == 4) { const f3 h = cosine_hemisphere(in0[i], in1[i]); out0[i] = h.x; out1[i] = h.z; }
+	else if (op == 5) out0[i] = det_log2(in0[i]);
+	else if (op == 6) out0[i] = det_exp2(in0[i]);
+}
+
+// BSDF probe: one fpt_bsdf.h entry point per op, on inputs a test chose (tests/test_bsdf_truth.py; the oracle's orc_bsdf_probe_n is its CPU twin).
+// Record (BSDF_PROBE_REC floats): [0] material slot, [1..3] w_i, [4..6] w_o, [7..9] z, [10..21] frame n, ng, t, b, [22..31] op parameters.
+// `vary` (3 floats per element, may be null) replaces w_o of the evaluating ops and z of the sampling ops, so that one broadcast record
+// (rec_stride 0) can drive millions of samples.  Output: BSDF_PROBE_OUT floats per element; layouts in include/fermat_pt_hip.h.
+enum : uint32_t { BSDF_PROBE_REC = 32, BSDF_PROBE_OUT = 16 };
+__global__ void debug_bsdf_kernel(int op, uint32_t flags, uint32_t n, const fpt_material* mats, uint32_t n_mats, const float* table,
+                                  const float* rec, uint32_t rec_stride, const float* vary, float* out)
+{
+	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
+	if (i >= n) return;
+	const float* r = rec + size_t(i) * rec_stride;
+	float* o = out + size_t(i) * BSDF_PROBE_OUT;
+	const bool RR = (flags & 1u) != 0, full = (flags & 2u) != 0, particle = (flags & 4u) != 0;
+	const fpt_material* mat = mats + sel_min(uint32_t(r[0]), n_mats - 1u);
+	const SurfaceModel m = (flags & 8u)
+		? make_surface_model_unpacked(xyz(load4(mat->diffuse)), xyz(load4(mat->specular)), mat->roughness, xyz(load4(mat->diffuse_trans)), mat->opacity, mat->index_of_refraction, table)
+		: make_surface_model(xyz(load4(mat->diffuse)), xyz(load4(mat->diffuse_trans)), xyz(load4(mat->specular)), xyz(load4(mat->reflectivity)),
+		                     mat->roughness, mat->index_of_refraction, mat->opacity, table);
+	ShadingFrame fr;
+	fr.n = mk3(r[10], r[11], r[12]); fr.ng = mk3(r[13], r[14], r[15]); fr.t = mk3(r[16], r[17], r[18]); fr.b = mk3(r[19], r[20], r[21]);
+	const f3 w_i = mk3(r[1], r[2], r[3]);
+	f3 w_o = mk3(r[4], r[5], r[6]);
+	float z[3] = { r[7], r[8], r[9] };
+	if (vary) { const float* v = vary + 3 * size_t(i); w_o = mk3(v[0], v[1], v[2]); z[0] = v[0]; z[1] = v[1]; z[2] = v[2]; }
+	const float* q = r + 22;
+	auto put3 = [&](int k, f3 v) { o[k] = v.x; o[k + 1] = v.y; o[k + 2] = v.z; };
+	auto put_sample = [&](uint32_t comp, f3 d, float p, float pp, f3 g) { o[0] = float(comp); put3(1, d); o[4] = p; o[5] = pp; put3(6, g); };
+	if (op == 0 || op == 1)                // surface_f_and_p, plain / with view terms: f[4] (12), p[4]
+	{
+		f3 f[4]; float p[4];
+		if (op == 0) surface_f_and_p(m, fr, w_i, w_o, f, p);
+		else surface_f_and_p(m, fr, view_terms(m, fr, w_i), w_i, w_o, f, p);
+		for (int k = 0; k < 4; ++k) { put3(3 * k, f[k]); o[12 + k] = p[k]; }
+	}
+	else if (op == 2 || op == 3)           // surface_sample, plain / with view terms: comp, out (3), p, p_proj, g (3)
+	{
+		f3 d, g; float p, pp;
+		const uint32_t c = op == 2 ? surface_sample(m, fr, z[0], z[1], z[2], w_i, d, p, pp, g)
+		                           : surface_sample(m, fr, view_terms(m, fr, w_i), z[0], z[1], z[2], w_i, d, p, pp, g);
+		put_sample(c, d, p, pp, g);
+	}
+	else if (op == 4) { f3 f; float p; surface_f_and_p_sum(m, fr, w_i, w_o, RR, particle, f, p); put3(0, f); o[3] = p; }
+	else if (op == 5) put3(0, surface_f_sum(m, fr, w_i, w_o, particle));
+	else if (op == 6) o[0] = surface_p_sum(m, fr, w_i, w_o, RR);
+	else if (op == 7)
+	{
+		f3 d, g; float p, pp;
+		const uint32_t c = surface_sample_ex(m, fr, z[0], z[1], z[2], w_i, RR, full, particle, d, p, pp, g);
+		put_sample(c, d, p, pp, g);
+	}
+	else if (op == 8 || op == 9)           // one GGX lobe as the lobe stores it: q = alpha, int_ior, ext_ior (-1, -1 = reflective)
+	{
+		GgxLobe l; l.alpha = q[0]; l.inv_alpha = 1.0f / q[0]; l.int_ior = q[1]; l.ext_ior = q[2];
+		if (op == 8) { float f, p; ggx_eval(l, fr, w_i, w_o, f, p); o[0] = f; o[1] = p; }
+		else                               // the microfacet draw of surface_sample, then the lobe's direction: L (3), g, p, p_proj, H (3)
+		{
+			const f3 Vl = to_local(fr, w_i);
+			const float sg = Vl.z >= 0.0f ? 1.0f : -1.0f;
+			f3 Hl = sample_vndf(z[0], z[1], l.alpha, mk3(Vl.x, Vl.y, Vl.z * sg));
+			Hl.z *= sg;
+			const f3 H = from_local(fr, Hl);
+			f3 L = splat3(0.0f); float g, p, pp;
+			ggx_sample_given_h(l, fr, H, w_i, L, g, p, pp);
+			put3(0, L); o[3] = g; o[4] = p; o[5] = pp; put3(6, H);
+		}
+	}
+	else if (op == 10) put3(0, schlick(q[0], q[1], mk3(q[2], q[3], q[4])));          // q = cos_i, eta, base (3)
+	else if (op == 11)                     // coat_interface: ok, cos_i, Fc (3), Tc (3)
+	{
+		float ci = 0.0f; f3 Fc = splat3(0.0f), Tc = splat3(0.0f);
+		o[0] = coat_interface(m, fr, w_i, ci, Fc, Tc) ? 1.0f : 0.0f; o[1] = ci; put3(2, Fc); put3(5, Tc);
+	}
+	else if (op == 12) put3(0, cosine_hemisphere(z[0], z[1]));
+	else if (op == 13) o[0] = directional_albedo(m, q[0]);
 }
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------
@@ -853,5 +931,8 @@ void launch_rgba(const float4* composited, uint32_t n, float exposure, float inv
 { hipLaunchKernelGGL(rgba_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, composited, n, exposure, inv_gamma, rgba); }
 void launch_debug_math(int op, uint32_t n, const float* a, const float* b, float* o0, float* o1, hipStream_t s)
 { hipLaunchKernelGGL(debug_math_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, op, n, a, b, o0, o1); }
+void launch_debug_bsdf(int op, uint32_t flags, uint32_t n, const fpt_material* mats, uint32_t n_mats, const float* table, const float* rec, uint32_t rec_stride,
+                       const float* vary, float* out, hipStream_t s)
+{ hipLaunchKernelGGL(debug_bsdf_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, op, flags, n, mats, n_mats, table, rec, rec_stride, vary, out); }
 
 } // namespace fpt

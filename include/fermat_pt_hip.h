@@ -433,8 +433,20 @@ typedef struct fpt_mesh_lights_view { const float* d_mesh_cdf; const float* d_me
 int fpt_mesh_lights_device_view(fpt_context* ctx, fpt_mesh_lights_view* out);
 
 /* ---- device math probes (parity tests of the "detmath v1" kernels and the BSDF against the oracle) --------------------- */
-/* op: 0 sincos(x)->(s,c)  1 atan2(y,x)  2 pow(x,y)  3 f2h->h2f round trip; inputs/outputs are DEVICE arrays of n (x2 where noted) */
+/* op: 0 sincos(x)->(s,c)  1 atan2(y,x)  2 pow(x,y)  3 f2h->h2f round trip  4 cosine_hemisphere(x,y)->(x,z)  5 log2(x)  6 exp2(x);
+ * inputs/outputs are DEVICE arrays of n (x2 where noted) */
 int fpt_debug_math(fpt_context* ctx, int op, uint32_t n, const float* d_in0, const float* d_in1, float* d_out0, float* d_out1);
+
+/* BSDF probe: runs one function of the device surface model per element.  DEVICE arrays: mats (n_mats records), the 32^4 glossy table, rec (32 floats per
+ * element, rec_stride 32; 0 = every element reads record 0), vary (3 floats per element or NULL: replaces w_o, or z for the sampling ops), out (16 floats per element).
+ * Record: [0] material slot, [1..3] w_i, [4..6] w_o, [7..9] z, [10..21] frame n, ng, t, b, [22..31] op parameters.  flags: 1 RR, 2 full, 4 particle, 8 unpacked material.
+ * op -> out:  0/1 surface_f_and_p plain / view_terms -> f[4][3], p[4]    2/3 surface_sample plain / view_terms -> comp, out[3], p, p_proj, g[3]
+ *             4 surface_f_and_p_sum -> f[3], p    5 surface_f_sum -> f[3]    6 surface_p_sum -> p    7 surface_sample_ex -> as 2
+ *             8 ggx_eval(alpha, int_ior, ext_ior = params) -> f, p    9 sample_vndf + ggx_sample_given_h -> L[3], g, p, p_proj, H[3]
+ *             10 schlick(params: cos_i, eta, base[3]) -> F[3]    11 coat_interface -> ok, cos_i, Fc[3], Tc[3]    12 cosine_hemisphere(z0, z1) -> [3]
+ *             13 directional_albedo(params: cos) -> a */
+int fpt_debug_bsdf(fpt_context* ctx, int op, uint32_t flags, uint32_t n, const fpt_material* d_mats, uint32_t n_mats, const float* d_table,
+                   const float* d_rec, uint32_t rec_stride, const float* d_vary, float* d_out);
 
 /* host-side probe of the acceleration-structure builder behind fpt_rt_create_geometry (no GPU, no context; HOST arrays in, HOST arrays out):
  * *node_words = 32-bit words per node (20: the 80-byte 8-wide compressed node, see fermat_amd/csrc/fpt_bvh.h), records = 48-byte triangle

@@ -151,6 +151,69 @@ void orc_bsdf_f_and_p_n(const Material* m, const float* table, u32 n, const floa
 	#pragma omp parallel for schedule(static)
 	for (i32 i = 0; i < i32(n); ++i) orc_bsdf_f_and_p(m, table, w_i, w_o + 3 * size_t(i), out + 16 * size_t(i));
 }
+// twin of the device BSDF probe fpt_debug_bsdf (include/fermat_pt_hip.h has the record, flag and output layouts): any frame, the BPT variants, the lobes on
+// their own.  The oracle's Bsdf has no view-terms split, so ops 1 and 3 (the device's view_terms overloads) run the same code as ops 0 and 2.
+void orc_bsdf_probe_n(i32 op, u32 flags, u32 n, const Material* mats, u32 n_mats, const float* table, const float* rec, u32 rec_stride, const float* vary, float* out)
+{
+	#pragma omp parallel for schedule(static)
+	for (i32 i = 0; i < i32(n); ++i)
+	{
+		const float* r = rec + size_t(i) * rec_stride;
+		float* o = out + 16 * size_t(i);
+		for (int k = 0; k < 16; ++k) o[k] = 0.0f;
+		const bool RR = (flags & 1u) != 0, full = (flags & 2u) != 0, particle = (flags & 4u) != 0;
+		const Material& m = mats[minu(u32(r[0]), n_mats - 1u)];
+		Bsdf b;
+		if (flags & 8u) b.setup_unpacked(V3(m.diffuse.x, m.diffuse.y, m.diffuse.z), V3(m.specular.x, m.specular.y, m.specular.z), m.roughness,
+		                                 V3(m.diffuse_trans.x, m.diffuse_trans.y, m.diffuse_trans.z), m.opacity, m.index_of_refraction, table, particle);
+		else { b.setup(m, table); b.particle_transport = particle; }
+		Frame g;
+		g.normal_s = V3(r[10], r[11], r[12]); g.normal_g = V3(r[13], r[14], r[15]); g.tangent = V3(r[16], r[17], r[18]); g.binormal = V3(r[19], r[20], r[21]);
+		const V3 w_i(r[1], r[2], r[3]);
+		V3 w_o(r[4], r[5], r[6]);
+		float z[3] = { r[7], r[8], r[9] };
+		if (vary) { const float* v = vary + 3 * size_t(i); w_o = V3(v[0], v[1], v[2]); z[0] = v[0]; z[1] = v[1]; z[2] = v[2]; }
+		const float* q = r + 22;
+		auto put3 = [&](int k, V3 v) { o[k] = v.x; o[k + 1] = v.y; o[k + 2] = v.z; };
+		if (op == 0 || op == 1)
+		{
+			V3 f[4]; float p[4];
+			b.f_and_p(g, w_i, w_o, f, p);
+			for (int k = 0; k < 4; ++k) { put3(3 * k, f[k]); o[12 + k] = p[k]; }
+		}
+		else if (op == 2 || op == 3 || op == 7)
+		{
+			u32 comp = 0; V3 d(0.0f), gg(0.0f); float p = 0, pp = 0;
+			b.sample_ex(g, z, w_i, comp, d, p, pp, gg, op == 7 ? RR : true, op == 7 ? full : false);
+			o[0] = float(comp); put3(1, d); o[4] = p; o[5] = pp; put3(6, gg);
+		}
+		else if (op == 4) { V3 f; float p; b.f_and_p_sum(g, w_i, w_o, f, p, RR); put3(0, f); o[3] = p; }
+		else if (op == 5) put3(0, b.f_sum(g, w_i, w_o));
+		else if (op == 6) o[0] = b.p_sum(g, w_i, w_o, RR);
+		else if (op == 8 || op == 9)
+		{
+			GGXSmith l; l.roughness = q[0]; l.inv_roughness = 1.0f / q[0]; l.int_ior = q[1]; l.ext_ior = q[2];
+			if (op == 8) { V3 f; float p; l.f_and_p(g, w_i, w_o, f, p); o[0] = f.x; o[1] = p; }
+			else
+			{
+				const V3 H = g.from_local(l.sample_h_local(z[0], z[1], g.to_local(w_i)));
+				V3 L(0.0f), gg(0.0f); float p = 0, pp = 0;
+				l.sample_given_h(g, H, w_i, L, gg, p, pp);
+				put3(0, L); o[3] = gg.x; o[4] = p; o[5] = pp; put3(6, H);
+			}
+		}
+		else if (op == 10) put3(0, fresnel_schlick(q[0], q[1], V3(q[2], q[3], q[4])));
+		else if (op == 11)
+		{
+			V3 H, Fc(0.0f), Tc(0.0f); float ci = 0.0f;
+			o[0] = b.clearcoat_transmission(g, w_i, H, ci, Fc, Tc) ? 1.0f : 0.0f; o[1] = ci; put3(2, Fc); put3(5, Tc);
+		}
+		else if (op == 12) put3(0, square_to_cosine_hemisphere(z[0], z[1]));
+		else if (op == 13) o[0] = b.glossy_reflectance(q[0]);
+	}
+}
+float orc_det_log2(float x) { return det_log2(x); }
+float orc_det_exp2(float x) { return det_exp2(x); }
 // glossy reflectance table cells [begin, end) : src/bsdf.cu:36-102
 void orc_glossy_reflectance_cells(u32 begin, u32 end, float* out)
 {
