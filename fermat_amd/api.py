@@ -89,6 +89,7 @@ class EawParams(C.Structure):
 
 
 # ShadingMode (src/renderer_view.h:61-76) and FilterOp (src/filters.h:44-57)
+BUILD_QUALITY, BUILD_FAST, BUILD_TRBVH = 0, 1, 2          # fpt_rt_set_build_mode / Renderer.set_build_mode
 SHADING_SHADED, SHADING_UV, SHADING_ALBEDO, SHADING_DIFFUSE_ALBEDO, SHADING_SPECULAR_ALBEDO = 0, 1, 4, 5, 6
 SHADING_DIFFUSE_COLOR, SHADING_SPECULAR_COLOR, SHADING_DIRECT_LIGHTING, SHADING_FILTERED, SHADING_VARIANCE, SHADING_NORMAL = 7, 8, 9, 10, 11, 12
 FILTER_OP_MODULATE_INPUT, FILTER_OP_DEMODULATE_INPUT, FILTER_OP_MODULATE_OUTPUT, FILTER_OP_DEMODULATE_OUTPUT, FILTER_OP_ADD_MODE, FILTER_OP_REPLACE_MODE = 1, 2, 4, 8, 16, 32
@@ -636,7 +637,9 @@ class Renderer:
                                                  C.c_void_p(self.d_vd.data_ptr())))
 
     def set_build_mode(self, mode):
-        """0 = quality (host SAH builder, the default), 1 = fast (device Morton radix tree + collapse): what the next create_geometry / rebuild uses"""
+        """what the next create_geometry / rebuild uses: BUILD_QUALITY (0, the default: host binned SAH + re-insertion + collapse), BUILD_FAST (1: device Morton radix
+        tree + collapse) or BUILD_TRBVH (2: the device radix tree restructured by 7-leaf treelets before the collapse -- a few ms more than BUILD_FAST on the device,
+        fewer node steps per ray).  FPT_BVH_BUILD=quality|fast|trbvh overrides it."""
         self._check(self.L.fpt_rt_set_build_mode(self.ctx, C.c_uint32(mode)))
 
     def rebuild_geometry(self, vertex_data=None):

@@ -82,15 +82,15 @@ int fpt_rt_create_geometry(fpt_context* ctx, uint32_t tri_count, const int32_t* 
 {
 	return guarded(ctx, [&] { flush_deferred(ctx);
 		const double t0 = wall_seconds();
-		// fast mode (fpt_rt_set_build_mode(ctx, 1) or FPT_BVH_BUILD=fast): the whole build on the device, the mesh stays where it is (fpt_build_lbvh.hip); a tree whose
-		// traversal-stack bound exceeds the kernel's stack -- degenerate inputs -- falls through to the host builder and its ladder of shallower trees
+		// fast and trbvh modes (fpt_rt_set_build_mode(ctx, 1 | 2) or FPT_BVH_BUILD=fast|trbvh): the whole build on the device, the mesh stays where it is (fpt_build_lbvh.hip);
+		// a tree whose traversal-stack bound exceeds the kernel's stack -- degenerate inputs -- falls through to the host builder and its ladder of shallower trees
 		const char* env = std::getenv("FPT_BVH_BUILD");
-		const bool fast = env ? std::strcmp(env, "fast") == 0 : ctx->build_mode == 1;
-		if (fast && tri_count >= 2)
+		const uint32_t mode = env ? (std::strcmp(env, "fast") == 0 ? 1u : std::strcmp(env, "trbvh") == 0 ? 2u : 0u) : ctx->build_mode;
+		if (mode != 0u && tri_count >= 2)
 		{
 			require(d_idx && d_vtx, "fpt_rt_create_geometry: null mesh");
 			FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));          // launches still reading the old tree
-			if (build_acceleration_device(ctx, tri_count, d_idx, vertex_count, d_vtx, trace_stack_entries()))
+			if (build_acceleration_device(ctx, tri_count, d_idx, vertex_count, d_vtx, trace_stack_entries(), mode))
 			{
 				ctx->has_geometry = true; ctx->emitter_generation++;
 				if (std::getenv("FPT_BVH_TIMERS")) std::fprintf(stderr, "fpt_rt_create_geometry: built on the device in %.3f ms\n", (wall_seconds() - t0) * 1e3);
@@ -112,9 +112,10 @@ int fpt_rt_create_geometry(fpt_context* ctx, uint32_t tri_count, const int32_t* 
 		if (std::getenv("FPT_BVH_TIMERS")) std::fprintf(stderr, "fpt_rt_create_geometry: mesh to the host %.3f s, build %.3f, tree to the device %.3f\n", t1 - t0, t2 - t1, wall_seconds() - t2);
 	});
 }
-// 0 = quality (default): the host builder; 1 = fast: the device builder -- what a host that rebuilds every frame (RenderingContext::update_model without refit) wants
+// 0 = quality (default): the host builder; 1 = fast: the device builder -- what a host that rebuilds every frame (RenderingContext::update_model without refit) wants;
+// 2 = trbvh: the device builder with the radix tree restructured by treelets before the collapse
 int fpt_rt_set_build_mode(fpt_context* ctx, uint32_t mode)
-{ return guarded(ctx, [&] { require(mode <= 1, "fpt_rt_set_build_mode: 0 = quality (host), 1 = fast (device)"); ctx->build_mode = mode; }); }
+{ return guarded(ctx, [&] { require(mode <= 2, "fpt_rt_set_build_mode: 0 = quality (host), 1 = fast (device), 2 = trbvh (device, treelet-restructured)"); ctx->build_mode = mode; }); }
 
 int fpt_rt_refit_geometry(fpt_context* ctx, uint32_t tri_count, const int32_t* d_idx, uint32_t vertex_count, const float* d_vtx)
 {

@@ -9,6 +9,7 @@
 //   1 refs      per triangle: validation, the padded box of build_bvh2 (2e-6 (|tri|max + |scene|max)), bounds of the boxes and of their centres     [streaming, HBM]
 //   2 codes     63-bit Morton code of each box centre on the grid of the centre bounds; rocPRIM radix sort of (code, triangle)                      [HBM, 4 passes]
 //   3 tree      Karras (HPG 2012): every inner node of the binary radix tree finds its range and split independently; ties broken by position        [latency]
+//   3b treelets (build mode 2, "trbvh" only) Karras & Aila (HPG 2013): the radix tree restructured in place by 7-leaf treelets, three bottom-up passes  [latency]
 //   4 fit + DP  bottom-up in rounds (a node is done a round after its children; kernel boundaries are the only synchronisation): boxes, and the collapse's cost rows
 //               C(n, 1..7) of Ylitie et al. 2017 (fpt_bvh.cpp Collapse)
 //   5 emission  level by level from the root: a thread per wide node gathers its <= 8 children from the DP's decisions, assigns them to octant slots (the same exact
@@ -178,6 +179,265 @@ __global__ __launch_bounds__(256) void lbvh_tree_kernel(uint32_t n, const unsign
 	const int first = min(i, j), last = max(i, j);
 	const int l_ref = (first == split) ? ~split : split, r_ref = (last == split + 1) ? ~(split + 1) : split + 1;
 	left[i] = l_ref; right[i] = r_ref;
+}
+
+// ---- 3b (mode 2 only): treelet restructuring of the radix tree (Karras & Aila, HPG 2013: "Trbvh") -----------------------------
+// Rewires left / right in place; emission never assumes that a subtree covers a contiguous range of sorted codes.  Per inner node: its box (node_box), its triangle
+// count N (tcount) and its binary SAH cost C (tcost): C(n) = min(C_NODE A(n) + C(l) + C(r), C_PRIM A(n) N(n) when N <= CW8_MAX_LEAF), a triangle costs C_PRIM A;
+// A = half area relative to the root's, in fp64, rounded to float as the fit kernel does.  Every pass is a bottom-up sweep in rounds like lbvh_fit_round_kernel's
+// (a kernel boundary is the only synchronisation): a node whose children finished in earlier rounds and whose N >= gamma roots a treelet; two nodes ready in the
+// same round are never ancestor and descendant, so their treelets are disjoint.
+__device__ __forceinline__ double lbvh_inv_root_area(const int* __restrict__ bounds)
+{
+	LbvhBox root; for (int k = 0; k < 3; ++k) { root.lo[k] = unordered(bounds[k]); root.hi[k] = unordered(bounds[3 + k]); }
+	const double ra = half_area(root);
+	return 1.0 / (ra > 1.0e-300 ? ra : 1.0e-300);
+}
+__device__ __forceinline__ float trbvh_cost(float area, uint32_t count, float split)
+{
+	const float c_inner = area * C_NODE + split;
+	const float c_leaf = count <= CW8_MAX_LEAF ? area * float(count) * C_PRIM : 3.0e38f;
+	return c_leaf < c_inner ? c_leaf : c_inner;
+}
+__device__ __forceinline__ void trbvh_ref(int ref, const LbvhBox* __restrict__ refs, const uint32_t* __restrict__ vals, const LbvhBox* __restrict__ node_box,
+                                          const uint32_t* __restrict__ tcount, const float* __restrict__ tcost, double inv_root_area, LbvhBox& b, uint32_t& count, float& cost)
+{
+	if (ref >= 0) { b = node_box[ref]; count = tcount[ref]; cost = tcost[ref]; return; }
+	b = refs[vals[~ref]]; count = 1u; cost = float(half_area(b) * inv_root_area) * C_PRIM;
+}
+// a node is ready in `round` when both children were stamped in earlier rounds (a stamp equal to the round does not count)
+__device__ __forceinline__ bool trbvh_ready(int l, int r, const uint32_t* __restrict__ stamp, uint32_t round)
+{
+	return !((l >= 0 && (stamp[l] == 0u || stamp[l] >= round)) || (r >= 0 && (stamp[r] == 0u || stamp[r] >= round)));
+}
+// prep: box, N and C of every inner node of the radix tree
+__global__ __launch_bounds__(256) void trbvh_prep_round_kernel(uint32_t n, uint32_t round, const LbvhBox* __restrict__ refs, const uint32_t* __restrict__ vals, const int* __restrict__ left,
+                                                              const int* __restrict__ right, uint32_t* __restrict__ stamp, LbvhBox* __restrict__ node_box, uint32_t* __restrict__ tcount,
+                                                              float* __restrict__ tcost, const int* __restrict__ bounds)
+{
+	const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+	if (p + 1 >= n || stamp[p] != 0u) return;
+	const int l = left[p], r = right[p];
+	if (!trbvh_ready(l, r, stamp, round)) return;
+	const double inv_root_area = lbvh_inv_root_area(bounds);
+	LbvhBox b0, b1; uint32_t n0, n1; float c0, c1;
+	trbvh_ref(l, refs, vals, node_box, tcount, tcost, inv_root_area, b0, n0, c0);
+	trbvh_ref(r, refs, vals, node_box, tcount, tcost, inv_root_area, b1, n1, c1);
+	LbvhBox nb;
+	for (int k = 0; k < 3; ++k) { nb.lo[k] = hmin(b0.lo[k], b1.lo[k]); nb.hi[k] = hmax(b0.hi[k], b1.hi[k]); }
+	node_box[p] = nb;
+	tcount[p] = n0 + n1;
+	tcost[p] = trbvh_cost(float(half_area(nb) * inv_root_area), n0 + n1, c0 + c1);
+	stamp[p] = round;
+}
+// one round of a pass, part 1: stamps the ready nodes and lists those with N >= gamma (wave-aggregated append; the order of the list does not matter)
+__global__ __launch_bounds__(256) void trbvh_ready_round_kernel(uint32_t n, uint32_t round, uint32_t gamma, const int* __restrict__ left, const int* __restrict__ right,
+                                                               uint32_t* __restrict__ stamp, const uint32_t* __restrict__ tcount, int* __restrict__ list, uint32_t* __restrict__ list_count)
+{
+	const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+	if (p + 1 >= n || stamp[p] != 0u) return;
+	if (!trbvh_ready(left[p], right[p], stamp, round)) return;
+	stamp[p] = round;
+	const bool root = tcount[p] >= gamma;
+	const unsigned long long mask = __ballot(root);
+	if (!root) return;
+	const uint32_t lane = threadIdx.x & 63u, leader = uint32_t(__ffsll((long long)mask) - 1);
+	uint32_t base = 0;
+	if (lane == leader) base = atomicAdd(list_count, uint32_t(__popcll(mask)));
+	base = __shfl(base, int(leader));
+	list[base + uint32_t(__popcll(mask & ((1ull << lane) - 1ull)))] = int(p);
+}
+// the subsets of the 7 treelet leaves with 2..7 members, by size, then by mask
+__constant__ uint8_t c_trbvh_subsets[120] = {
+	3, 5, 6, 9, 10, 12, 17, 18, 20, 24, 33, 34, 36, 40, 48, 65, 66, 68, 72, 80, 96,
+	7, 11, 13, 14, 19, 21, 22, 25, 26, 28, 35, 37, 38, 41, 42, 44, 49, 50, 52, 56, 67, 69, 70, 73, 74, 76, 81, 82, 84, 88, 97, 98, 100, 104, 112,
+	15, 23, 27, 29, 30, 39, 43, 45, 46, 51, 53, 54, 57, 58, 60, 71, 75, 77, 78, 83, 85, 86, 89, 90, 92, 99, 101, 102, 105, 106, 108, 113, 114, 116, 120,
+	31, 47, 55, 59, 61, 62, 79, 87, 91, 93, 94, 103, 107, 109, 110, 115, 117, 118, 121, 122, 124,
+	63, 95, 111, 119, 123, 125, 126,
+	127 };
+// the j-th subset of `bits` (bit i of j selects the i-th lowest set bit)
+__device__ __forceinline__ uint32_t trbvh_deposit(uint32_t j, uint32_t bits)
+{
+	uint32_t r = 0;
+	for (uint32_t b = 1u; bits; b <<= 1) { const uint32_t low = bits & (0u - bits); if (j & b) r |= low; bits ^= low; }
+	return r;
+}
+// one round of a pass, part 2: a persistent grid, one wave per listed treelet root R.
+//   formation  R's children are the first two treelet leaves; the inner leaf of largest area (ties: the lower node reference) is replaced, in place, by its two children
+//              until there are 7 (N(R) >= 7 guarantees an inner leaf).  Leaves stay in left-to-right order, so every old inner node covers a run of them.
+//   DP         C(S) for the 127 subsets of the leaves, by size; a subset's partitions {P, S \ P} with P holding S's lowest leaf are split over the lanes of a group,
+//              the minimum of (cost, P) is reduced over the group by butterfly (a fixed order; equal costs: the smaller P).  Areas, costs, best partitions in LDS.
+//   self-check the old topology is one of the candidates: its cost under the same arithmetic is recomputed, and a DP result above it sets status bit 16.
+//   rewrite    only when strictly cheaper: R keeps its index, the treelet's other inner nodes are handed out in ascending order in pre-order of the new topology;
+//              their box, N and C are rewritten.
+__global__ __launch_bounds__(64) void trbvh_treelet_kernel(const int* __restrict__ list, const uint32_t* __restrict__ list_count, const LbvhBox* __restrict__ refs,
+                                                          const uint32_t* __restrict__ vals, int* __restrict__ left, int* __restrict__ right, LbvhBox* __restrict__ node_box,
+                                                          uint32_t* __restrict__ tcount, float* __restrict__ tcost, const int* __restrict__ bounds, uint32_t* __restrict__ status)
+{
+	__shared__ float s_area[128], s_cost[128];
+	__shared__ uint8_t s_part[128];
+	__shared__ LbvhBox s_box[7];
+	__shared__ uint32_t s_n[7];
+	__shared__ int s_ref[7], s_inner[6];
+	__shared__ float s_leaf_area[7];
+	const uint32_t lane = threadIdx.x;
+	const uint32_t total = *list_count;
+	const double inv_root_area = lbvh_inv_root_area(bounds);
+	for (uint32_t t = blockIdx.x; t < total; t += gridDim.x)
+	{
+		const int R = list[t];
+		// formation (lane 0)
+		if (lane == 0u)
+		{
+			s_inner[0] = R;
+			s_ref[0] = left[R]; s_ref[1] = right[R];
+			for (int k = 0; k < 2; ++k) s_leaf_area[k] = s_ref[k] >= 0 ? float(half_area(node_box[s_ref[k]]) * inv_root_area) : -1.0f;
+			int nl = 2;
+			for (; nl < 7; ++nl)
+			{
+				int b = -1;
+				for (int k = 0; k < nl; ++k)
+					if (s_ref[k] >= 0 && (b < 0 || s_leaf_area[k] > s_leaf_area[b] || (s_leaf_area[k] == s_leaf_area[b] && s_ref[k] < s_ref[b]))) b = k;
+				if (b < 0) break;
+				const int x = s_ref[b];
+				s_inner[nl - 1] = x;
+				for (int k = nl; k > b + 1; --k) { s_ref[k] = s_ref[k - 1]; s_leaf_area[k] = s_leaf_area[k - 1]; }
+				s_ref[b] = left[x]; s_ref[b + 1] = right[x];
+				for (int k = b; k < b + 2; ++k) s_leaf_area[k] = s_ref[k] >= 0 ? float(half_area(node_box[s_ref[k]]) * inv_root_area) : -1.0f;
+			}
+			if (nl < 7) { atomicOr(status, 16u); s_ref[0] = 0x7FFFFFFF; }          // N(R) < 7: cannot happen for gamma >= 7
+		}
+		__syncthreads();
+		if (s_ref[0] == 0x7FFFFFFF) { __syncthreads(); continue; }
+		// the leaves
+		if (lane < 7u)
+		{
+			LbvhBox b; uint32_t c; float cost;
+			trbvh_ref(s_ref[lane], refs, vals, node_box, tcount, tcost, inv_root_area, b, c, cost);
+			s_box[lane] = b; s_n[lane] = c; s_cost[1u << lane] = cost; s_area[1u << lane] = float(half_area(b) * inv_root_area);
+		}
+		__syncthreads();
+		// areas of the subsets with >= 2 leaves (box unions in ascending leaf order)
+		for (uint32_t S = lane + 1u; S < 128u; S += 64u)
+		{
+			if (__popc(S) < 2) continue;
+			LbvhBox u; bool first = true;
+			for (uint32_t m = S; m; m &= m - 1u)
+			{
+				const LbvhBox& b = s_box[__ffs(m) - 1];
+				if (first) { u = b; first = false; continue; }
+				for (int k = 0; k < 3; ++k) { u.lo[k] = hmin(u.lo[k], b.lo[k]); u.hi[k] = hmax(u.hi[k], b.hi[k]); }
+			}
+			s_area[S] = float(half_area(u) * inv_root_area);
+		}
+		__syncthreads();
+		// the DP, by subset size k: C(7, k) subsets x 2^(k-1) - 1 partitions; `group` lanes per subset
+		for (uint32_t k = 2; k <= 7; ++k)
+		{
+			const uint32_t first = k == 2 ? 0u : k == 3 ? 21u : k == 4 ? 56u : k == 5 ? 91u : k == 6 ? 112u : 119u;
+			const uint32_t n_sub = k == 2 ? 21u : k == 3 ? 35u : k == 4 ? 35u : k == 5 ? 21u : k == 6 ? 7u : 1u;
+			const uint32_t group = k <= 4 ? 1u : k == 5 ? 2u : k == 6 ? 8u : 64u;
+			const uint32_t sub = lane / group, j0 = lane % group;
+			float best_c = 3.4e38f; uint32_t best_p = 0xFFu;
+			uint32_t S = 0;
+			if (sub < n_sub)
+			{
+				S = c_trbvh_subsets[first + sub];
+				const uint32_t low = S & (0u - S), rest = S ^ low, n_part = (1u << (k - 1u)) - 1u;
+				for (uint32_t j = j0; j < n_part; j += group)
+				{
+					const uint32_t P = low | trbvh_deposit(j, rest);
+					const float c = s_cost[P] + s_cost[S ^ P];
+					if (c < best_c || (c == best_c && P < best_p)) { best_c = c; best_p = P; }
+				}
+			}
+			for (uint32_t off = 1; off < group; off <<= 1)
+			{
+				const float oc = __shfl_xor(best_c, int(off)); const uint32_t op = uint32_t(__shfl_xor(int(best_p), int(off)));
+				if (oc < best_c || (oc == best_c && op < best_p)) { best_c = oc; best_p = op; }
+			}
+			if (sub < n_sub && j0 == 0u)
+			{
+				if (best_p == 0xFFu) { best_p = S & (0u - S); best_c = s_cost[best_p] + s_cost[S ^ best_p]; }          // NaN costs (non-finite vertices: refused later)
+				uint32_t N = 0; for (uint32_t m = S; m; m &= m - 1u) N += s_n[__ffs(m) - 1];
+				s_cost[S] = trbvh_cost(s_area[S], N, best_c); s_part[S] = uint8_t(best_p);
+			}
+			__syncthreads();
+		}
+		if (lane == 0u)
+		{
+			// the old topology's cost under the same arithmetic: inner nodes in reverse order of formation (children before parents)
+			uint32_t o_mask[6]; float o_cost[6];
+			for (int i = 5; i >= 0; --i)
+			{
+				const int x = s_inner[i];
+				uint32_t m2[2]; float c2[2];
+				for (int side = 0; side < 2; ++side)
+				{
+					const int ref = side ? right[x] : left[x];
+					m2[side] = 0u; c2[side] = 0.0f;
+					for (int k = 0; k < 7; ++k) if (s_ref[k] == ref) { m2[side] = 1u << k; c2[side] = s_cost[1u << k]; }
+					for (int j = i + 1; j < 6; ++j) if (s_inner[j] == ref) { m2[side] = o_mask[j]; c2[side] = o_cost[j]; }
+				}
+				o_mask[i] = m2[0] | m2[1];
+				uint32_t N = 0; for (uint32_t m = o_mask[i]; m; m &= m - 1u) N += s_n[__ffs(m) - 1];
+				o_cost[i] = trbvh_cost(s_area[o_mask[i]], N, c2[0] + c2[1]);
+			}
+			const float c_new = s_cost[127], c_old = o_cost[0];
+			if (o_mask[0] != 127u || c_new > c_old) atomicOr(status, 16u);
+			else if (c_new < c_old)
+			{
+				int idx[6]; idx[0] = R;
+				for (int i = 1; i < 6; ++i) { int v = s_inner[i], j = i; while (j > 1 && idx[j - 1] > v) { idx[j] = idx[j - 1]; --j; } idx[j] = v; }
+				// pre-order: the subtree of S at position pos holds positions [pos, pos + |S| - 1); its left child P starts at pos + 1, its right at pos + |P|
+				uint32_t st_s[8], st_pos[8]; int sp = 0;
+				st_s[sp] = 127u; st_pos[sp++] = 0u;
+				while (sp > 0)
+				{
+					--sp; const uint32_t S = st_s[sp], pos = st_pos[sp];
+					const uint32_t P = s_part[S], Q = S ^ P;
+					const int node = idx[pos];
+					left[node] = __popc(P) == 1 ? s_ref[__ffs(P) - 1] : idx[pos + 1u];
+					right[node] = __popc(Q) == 1 ? s_ref[__ffs(Q) - 1] : idx[pos + uint32_t(__popc(P))];
+					LbvhBox u; bool first = true; uint32_t N = 0;
+					for (uint32_t m = S; m; m &= m - 1u)
+					{
+						const int k = __ffs(m) - 1; const LbvhBox& b = s_box[k]; N += s_n[k];
+						if (first) { u = b; first = false; continue; }
+						for (int q = 0; q < 3; ++q) { u.lo[q] = hmin(u.lo[q], b.lo[q]); u.hi[q] = hmax(u.hi[q], b.hi[q]); }
+					}
+					node_box[node] = u; tcount[node] = N; tcost[node] = s_cost[S];
+					if (__popc(Q) > 1) { st_s[sp] = Q; st_pos[sp++] = pos + uint32_t(__popc(P)); }
+					if (__popc(P) > 1) { st_s[sp] = P; st_pos[sp++] = pos + 1u; }
+				}
+			}
+		}
+		__syncthreads();
+	}
+}
+// the inner nodes' summed area and the triangles' summed area, relative to the root's, per block of 256 inner nodes (a fixed-order tree reduction; the host adds the blocks in order)
+__global__ __launch_bounds__(256) void trbvh_area_kernel(uint32_t n, const LbvhBox* __restrict__ refs, const uint32_t* __restrict__ vals, const int* __restrict__ left,
+                                                        const int* __restrict__ right, const LbvhBox* __restrict__ node_box, const int* __restrict__ bounds, double* __restrict__ partials)
+{
+	__shared__ double sh[2][256];
+	const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+	double a_inner = 0.0, a_leaf = 0.0;
+	if (p + 1 < n)
+	{
+		const double inv_root_area = lbvh_inv_root_area(bounds);
+		a_inner = half_area(node_box[p]) * inv_root_area;
+		const int l = left[p], r = right[p];
+		if (l < 0) a_leaf += half_area(refs[vals[~l]]) * inv_root_area;
+		if (r < 0) a_leaf += half_area(refs[vals[~r]]) * inv_root_area;
+	}
+	sh[0][threadIdx.x] = a_inner; sh[1][threadIdx.x] = a_leaf;
+	__syncthreads();
+	for (uint32_t off = 128; off > 0; off >>= 1)
+	{
+		if (threadIdx.x < off) { sh[0][threadIdx.x] += sh[0][threadIdx.x + off]; sh[1][threadIdx.x] += sh[1][threadIdx.x + off]; }
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) { partials[2 * size_t(blockIdx.x)] = sh[0][0]; partials[2 * size_t(blockIdx.x) + 1] = sh[1][0]; }
 }
 
 // ---- 4: boxes and the collapse's cost rows, bottom-up ------------------------------------------------------------------------
@@ -421,7 +681,8 @@ template <class T> static T* carve(uint8_t*& p, size_t n) { T* r = reinterpret_c
 
 // Builds the tree over the DEVICE mesh into ctx->d_nodes / ctx->d_tris; fills the host-side bookkeeping (level ranges, counts, the stack bound).  Returns false -- nothing
 // touched -- when the tree cannot be used (its stack bound exceeds `stack_limit`: a degenerate input) and the caller should fall back to the host builder; throws on bad input.
-bool build_acceleration_device(fpt_context* ctx, uint32_t n, const int32_t* d_idx, uint32_t n_verts, const float* d_vtx, uint32_t stack_limit)
+// mode 1 = fast (the radix tree as it is), 2 = Trbvh (the radix tree restructured by treelets, stage 3b, before the collapse).
+bool build_acceleration_device(fpt_context* ctx, uint32_t n, const int32_t* d_idx, uint32_t n_verts, const float* d_vtx, uint32_t stack_limit, uint32_t mode)
 {
 	hipStream_t s = ctx->stream;
 	const double t0 = wall_seconds();
@@ -441,6 +702,9 @@ bool build_acceleration_device(fpt_context* ctx, uint32_t n, const int32_t* d_id
 	auto sz = [&](size_t bytes) { total += (bytes + 255) & ~size_t(255); };
 	sz(n * sizeof(LbvhBox)); sz(16 * sizeof(int)); sz((size_t((n + 255u) / 256u) * 12 + 12) * sizeof(int)); sz(n * 8); sz(n * 8); sz(n * 4); sz(n * 4); sz(n * 4); sz(n * 4); sz(n * 4); sz(n * 4); sz(n * 4); sz(n * sizeof(LbvhBox)); sz(n * sizeof(LbvhCell));
 	sz(cap * 4); sz(cap * 4); sz(cap * sizeof(LbvhEmitTmp)); sz(cap * 8); sz(cap * 8); sz(64); sz(sort_bytes); sz(scan_bytes); sz(cap * sizeof(BvhNode8)); sz((size_t(n) + 1) * sizeof(BvhTriangle)); sz(cap * 4);
+	// mode 2: N and C per inner node, the treelet list, one list counter per round (a pass launches at most kMaxRounds + 7 rounds before it gives up)
+	static constexpr uint32_t kMaxRounds = 4096;
+	if (mode == 2) { sz(size_t(n) * sizeof(uint32_t)); sz(size_t(n) * sizeof(float)); sz(size_t(n) * sizeof(int)); sz(size_t(kMaxRounds + 16) * sizeof(uint32_t)); }
 	// the scratch stays with the context (a host that rebuilds every frame allocates it once; fpt_destroy or a smaller build's reuse keeps it)
 	if (ctx->d_build_scratch.count < total) ctx->d_build_scratch.alloc(total);
 	uint8_t* p = ctx->d_build_scratch.ptr;
@@ -454,11 +718,13 @@ bool build_acceleration_device(fpt_context* ctx, uint32_t n, const int32_t* d_id
 	uint8_t* sort_tmp = carve<uint8_t>(p, sort_bytes); uint8_t* scan_tmp = carve<uint8_t>(p, scan_bytes);
 	BvhNode8* nodes = carve<BvhNode8>(p, cap); BvhTriangle* records = carve<BvhTriangle>(p, size_t(n) + 1); uint32_t* need = carve<uint32_t>(p, cap);
 	uint2* totals = reinterpret_cast<uint2*>(status + 4);
+	uint32_t* tcount = nullptr; float* tcost = nullptr; int* tlist = nullptr; uint32_t* tlist_count = nullptr;
+	if (mode == 2) { tcount = carve<uint32_t>(p, n); tcost = carve<float>(p, n); tlist = carve<int>(p, n); tlist_count = carve<uint32_t>(p, kMaxRounds + 16); }
 
 	FPT_HIP_CHECK(hipMemsetAsync(status, 0, 64, s));
 	FPT_HIP_CHECK(hipMemsetAsync(flags, 0, size_t(n) * 4, s));
 	const bool timers = std::getenv("FPT_BVH_TIMERS") != nullptr;
-	double t_stage = wall_seconds(); double ms_stage[6] = { 0, 0, 0, 0, 0, 0 };
+	double t_stage = wall_seconds(); double ms_stage[7] = { 0, 0, 0, 0, 0, 0, 0 };
 	auto stage = [&](int k) { if (timers) { FPT_HIP_CHECK(hipStreamSynchronize(s)); const double t = wall_seconds(); ms_stage[k] = (t - t_stage) * 1e3; t_stage = t; } };
 	stage(0);          // |scene|max + scratch
 	const dim3 B(256), G((n + 255u) / 256u);
@@ -472,14 +738,63 @@ bool build_acceleration_device(fpt_context* ctx, uint32_t n, const int32_t* d_id
 	stage(2);          // sort
 	hipLaunchKernelGGL(lbvh_tree_kernel, G, B, 0, s, n, keys, left, right);
 	stage(3);          // radix tree
+	// 3b (mode 2): prep, kTreeletPasses restructuring passes, each bottom-up in rounds with `flags` as its stamps (reset before each and before stage 4)
+	static constexpr uint32_t kTreeletPasses = 3, kGamma0 = 7;          // Karras & Aila's schedule: gamma = 7, 14, 28
+	double area_before = 0.0, area_after = 0.0, area_leaves = 0.0, seconds_opt = 0.0;
+	if (mode == 2)
+	{
+		const double t_opt = wall_seconds();
+		auto bottom_up = [&](auto&& launch_round) {
+			uint32_t r = 0;
+			for (uint32_t root_stamp = 0; root_stamp == 0u;)
+			{
+				for (int k = 0; k < 8; ++k) launch_round(++r);
+				FPT_HIP_CHECK(hipMemcpyAsync(&root_stamp, flags, 4, hipMemcpyDeviceToHost, s));
+				FPT_HIP_CHECK(hipStreamSynchronize(s));
+				require(r <= kMaxRounds, "fpt: internal device-build error (a restructuring pass does not terminate)");
+			}
+		};
+		const uint32_t n_blocks = (n + 255u) / 256u;
+		double* area_partials = reinterpret_cast<double*>(partials);          // stage 1's partials (12 ints per block) are free again: two doubles per block
+		std::vector<double> h_partials(size_t(n_blocks) * 2);
+		auto summed_areas = [&](double& inner, double& leaves) {
+			hipLaunchKernelGGL(trbvh_area_kernel, G, B, 0, s, n, refs, vals, left, right, node_box, bounds, area_partials);
+			FPT_HIP_CHECK(hipMemcpyAsync(h_partials.data(), area_partials, h_partials.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+			FPT_HIP_CHECK(hipStreamSynchronize(s));
+			inner = 0.0; leaves = 0.0;
+			for (uint32_t b = 0; b < n_blocks; ++b) { inner += h_partials[2 * size_t(b)]; leaves += h_partials[2 * size_t(b) + 1]; }
+		};
+		bottom_up([&](uint32_t r) { hipLaunchKernelGGL(trbvh_prep_round_kernel, G, B, 0, s, n, r, refs, vals, left, right, flags, node_box, tcount, tcost, bounds); });
+		summed_areas(area_before, area_leaves);
+		const uint32_t treelet_blocks = 2048;          // persistent: one wave per treelet, 8 per CU
+		for (uint32_t pass = 0, gamma = kGamma0; pass < kTreeletPasses; ++pass, gamma *= 2u)
+		{
+			FPT_HIP_CHECK(hipMemsetAsync(flags, 0, size_t(n) * 4, s));
+			FPT_HIP_CHECK(hipMemsetAsync(tlist_count, 0, size_t(kMaxRounds + 16) * sizeof(uint32_t), s));
+			bottom_up([&](uint32_t r) {
+				hipLaunchKernelGGL(trbvh_ready_round_kernel, G, B, 0, s, n, r, gamma, left, right, flags, tcount, tlist, tlist_count + r);
+				hipLaunchKernelGGL(trbvh_treelet_kernel, dim3(treelet_blocks), dim3(64), 0, s, tlist, tlist_count + r, refs, vals, left, right, node_box, tcount, tcost, bounds, status);
+			});
+		}
+		summed_areas(area_after, area_leaves);
+		FPT_HIP_CHECK(hipMemsetAsync(flags, 0, size_t(n) * 4, s));          // stage 4 starts from fresh stamps
+		uint32_t h_st = 0;
+		FPT_HIP_CHECK(hipMemcpyAsync(&h_st, status, 4, hipMemcpyDeviceToHost, s));
+		FPT_HIP_CHECK(hipStreamSynchronize(s));
+		require(!(h_st & 2u), "fpt: vertex index out of range");
+		require(!(h_st & 16u), "fpt: internal device-build error (restructure)");
+		seconds_opt = wall_seconds() - t_opt;
+		stage(5);          // restructuring
+	}
 	// bottom-up in rounds (lbvh_fit_round_kernel); `flags` holds the stamps.  Eight rounds per read-back of the root's stamp
-	uint32_t rounds = 0;
+	uint32_t rounds = 0, fit_root_stamp = 0;
 	for (uint32_t root_stamp = 0; root_stamp == 0u;)
 	{
 		for (int k = 0; k < 8; ++k) { ++rounds; hipLaunchKernelGGL(lbvh_fit_round_kernel, G, B, 0, s, n, rounds, refs, vals, left, right, flags, node_box, cells, bounds); }
 		FPT_HIP_CHECK(hipMemcpyAsync(&root_stamp, flags, 4, hipMemcpyDeviceToHost, s));
 		FPT_HIP_CHECK(hipStreamSynchronize(s));
 		require(rounds <= 4096, "fpt: internal device-build error (the bottom-up pass does not terminate)");
+		fit_root_stamp = root_stamp;
 	}
 	stage(4);          // boxes + cost rows
 	uint32_t h_status[8] = { 0 };
@@ -521,6 +836,8 @@ bool build_acceleration_device(fpt_context* ctx, uint32_t n, const int32_t* d_id
 	hipLaunchKernelGGL(lbvh_hist_kernel, dim3((n_nodes + 255u) / 256u), B, 0, s, nodes, n_nodes, hist);
 	FPT_HIP_CHECK(hipMemcpyAsync(h_hist, hist, sizeof(h_hist), hipMemcpyDeviceToHost, s));
 	uint32_t h_need = 0, h_scan[2] = { 0, 0 };
+	LbvhCell h_root_cell = {};
+	if (mode == 2) FPT_HIP_CHECK(hipMemcpyAsync(&h_root_cell, cells, sizeof(h_root_cell), hipMemcpyDeviceToHost, s));
 	FPT_HIP_CHECK(hipMemcpyAsync(&h_need, need, 4, hipMemcpyDeviceToHost, s));
 	FPT_HIP_CHECK(hipMemcpyAsync(h_status, status, 4, hipMemcpyDeviceToHost, s));
 	FPT_HIP_CHECK(hipMemcpyAsync(h_scan, ctx->d_refit_scan.ptr, 8, hipMemcpyDeviceToHost, s));
@@ -542,9 +859,19 @@ bool build_acceleration_device(fpt_context* ctx, uint32_t n, const int32_t* d_id
 	H.n_inner_children = h_hist[9]; H.n_leaf_children = h_hist[10];
 	std::memcpy(&H.scene_mag, &h_scan[0], 4);
 	H.seconds_bvh2 = float(t_tree - t0); H.seconds_wide = float(wall_seconds() - t_tree); H.threads = 0;
+	if (mode == 2)
+	{
+		// comparable with the host build's statistics: re-insertion's measure before / after, the binary tree's SAH (all nodes' areas) and depth, the collapse's cost
+		H.opt_cost_before = float(area_before); H.opt_cost_after = float(area_after); H.opt_iterations = kTreeletPasses;
+		H.seconds_opt = float(seconds_opt); H.seconds_bvh2 -= H.seconds_opt;
+		H.sah_cost = float(area_after + area_leaves); H.max_depth = fit_root_stamp;
+		H.wide_cost = h_root_cell.c[1];
+	}
 	if (timers) std::fprintf(stderr, "build_acceleration_device: %u triangles -> %u wide nodes in %zu levels, stack bound %u; to the binary tree %.3f ms (|scene|max + scratch %.3f, references + codes %.3f, "
 	                                 "sort %.3f, radix tree %.3f, boxes + cost rows %.3f), emission + bound + copy %.3f ms\n",
 	                                 n, n_nodes, level_begin.size() - 1, h_need, H.seconds_bvh2 * 1e3, ms_stage[0], ms_stage[1], ms_stage[2], ms_stage[3], ms_stage[4], H.seconds_wide * 1e3);
+	if (timers && mode == 2) std::fprintf(stderr, "build_acceleration_device: restructuring (prep + %u treelet passes) %.3f ms, inner-node area %.4f -> %.4f, binary depth %u\n",
+	                                      kTreeletPasses, ms_stage[5], area_before, area_after, fit_root_stamp);
 	return true;
 }
 

@@ -90,7 +90,8 @@ struct fpt_context
 	fpt::DeviceArray<uint32_t> d_counters;              // ticket dispensers + queue sizes, zeroed per pass
 	fpt::DeviceArray<unsigned long long> d_trace_stats;
 	bool has_geometry = false;
-	uint32_t build_mode = 0;                             // fpt_rt_set_build_mode: 0 = quality (host: binned SAH + re-insertion + collapse), 1 = fast (device: Morton radix tree + collapse)
+	uint32_t build_mode = 0;                             // fpt_rt_set_build_mode: 0 = quality (host: binned SAH + re-insertion + collapse), 1 = fast (device: Morton radix tree + collapse),
+	                                                     // 2 = trbvh (device: Morton radix tree + treelet restructuring + collapse)
 	// device-side refit (fpt_build.hip): per-record and per-node fp32 boxes, {|scene|max bits, error bits}
 	fpt::DeviceArray<float> d_refit_tri_box, d_refit_node_box;
 	fpt::DeviceArray<uint32_t> d_refit_scan;
@@ -281,8 +282,9 @@ inline fpt::FrameBufferDev fb_dev(const fpt_framebuffer_view& v)
 
 inline void require(bool cond, const char* msg) { if (!cond) throw std::runtime_error(msg); }
 inline double wall_seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-// fpt_build_lbvh.hip: the device-side fast build (Morton radix tree -> SAH-optimal 8-wide collapse); false = the tree needs more stack than the kernel has: use the host builder
-namespace fpt { bool build_acceleration_device(fpt_context* ctx, uint32_t tri_count, const int32_t* d_idx, uint32_t vertex_count, const float* d_vtx, uint32_t stack_limit); }
+// fpt_build_lbvh.hip: the device-side builds (Morton radix tree [mode 2: restructured by treelets] -> SAH-optimal 8-wide collapse); mode = fpt_rt_set_build_mode's 1 or 2;
+// false = the tree needs more stack than the kernel has: use the host builder
+namespace fpt { bool build_acceleration_device(fpt_context* ctx, uint32_t tri_count, const int32_t* d_idx, uint32_t vertex_count, const float* d_vtx, uint32_t stack_limit, uint32_t mode); }
 
 // asynchronous launch timing (fpt_pt_set_profiling level 2) for the renderers that have no synchronous profiling mode of their own
 // (BPT, PSFPT): bucket 0 = closest-hit traversal, 2 = any-hit traversal, 3 = shading-side kernels; read with fpt_pt_collect_timings

@@ -105,7 +105,12 @@ void RenderingContext::init(int argc, char** argv, const SceneArrays& scene)
 		else if (std::strcmp(argv[i], "-device") == 0) device = std::atoi(argv[++i]);
 		else if (std::strcmp(argv[i], "-filtered") == 0) m_shading_mode = FPT_SHADING_FILTERED;          // the viewer's 'f' key (src/glut_viewer.cu:298)
 		else if (std::strcmp(argv[i], "-shading-mode") == 0) m_shading_mode = uint32(std::atoi(argv[++i]));
-		else if (std::strcmp(argv[i], "-bvh") == 0 && i + 1 < argc) { m_build_mode = std::strcmp(argv[++i], "fast") == 0 ? 1u : 0u; }      // no counterpart in the reference (OptiX picks its builder): fast = built on the device
+		else if (std::strcmp(argv[i], "-bvh") == 0 && i + 1 < argc)          // no counterpart in the reference (OptiX picks its builder): fast / trbvh = built on the device
+		{
+			const char* v = argv[++i];
+			m_build_mode = std::strcmp(v, "fast") == 0 ? 1u : std::strcmp(v, "trbvh") == 0 ? 2u : 0u;
+			if (m_build_mode == 0u && std::strcmp(v, "quality") != 0) std::fprintf(stderr, "warning: -bvh %s: expected quality, fast or trbvh; using quality\n", v);
+		}
 		else if (argv[i][0] == '-')
 			for (uint32 r = 0; r < m_renderer_names.size(); ++r) if (m_renderer_names[r] == argv[i] + 1) renderer_type = r;
 	}

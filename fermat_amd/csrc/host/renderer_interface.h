@@ -142,7 +142,8 @@ struct RenderingContext
 	std::vector<std::vector<uint32>> m_shards;      // every rank's pixel list (the gather needs all of them on every rank)
 	uint32* m_d_shard = nullptr;
 	uint8_t* m_d_rgba = nullptr;
-	uint32 m_build_mode = 0;          // `-bvh fast|quality`: fpt_rt_set_build_mode (quality = the host SAH builder, the default; fast = Morton radix tree + collapse on the device)
+	uint32 m_build_mode = 0;          // `-bvh quality|fast|trbvh`: fpt_rt_set_build_mode (quality = the host SAH builder, the default; fast = Morton radix tree + collapse on the device;
+	                                  //  trbvh = the same radix tree restructured by treelets on the device before the collapse)
 };
 
 // the MI355X path tracer behind RendererInterface (PathTracer, src/renderers/pathtracer.h:255-305)

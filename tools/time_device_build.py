@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""GPU box: fpt_rt_create_geometry in its two modes on the bench scene -- quality (host: binned SAH + re-insertion + collapse, mesh copied both ways) and fast (device:
-Morton radix tree + the same collapse, fpt_build_lbvh.hip) -- wall time of the call, the trees' shapes, and what each tree costs to traverse (closest-hit launch over
+"""GPU box: fpt_rt_create_geometry in its three modes on the bench scene -- quality (host: binned SAH + re-insertion + collapse, mesh copied both ways), fast (device:
+Morton radix tree + the same collapse, fpt_build_lbvh.hip) and trbvh (device: the radix tree restructured by treelets before the collapse) -- wall time of the call, the trees' shapes, and what each tree costs to traverse (closest-hit launch over
 captured-like random rays: ms and node steps / triangle tests per ray).   python tools/time_device_build.py [bathroom2|standin|testball|water|standin4]"""
 import os, sys, time
 import numpy as np
@@ -22,7 +22,7 @@ d = rng.standard_normal((len(rays), 3)).astype(np.float32); rays["dir"] = d / np
 rays["tmax"] = 1e34
 ref = None
 print("%s: %d triangles" % (which, s.num_triangles), flush=True)
-for mode, name in ((0, "quality (host)"), (1, "fast (device)"), (1, "fast (device)")):
+for mode, name in ((0, "quality (host)"), (1, "fast (device)"), (1, "fast (device)"), (2, "trbvh (device)"), (2, "trbvh (device)")):
     r.set_build_mode(mode)
     t = time.perf_counter(); r.rebuild_geometry(); dt = time.perf_counter() - t
     st = r.bvh_stats()

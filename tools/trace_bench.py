@@ -14,15 +14,18 @@ def main():
     ap.add_argument("--workload", default="standin"); ap.add_argument("--detail", type=float, default=1.0)
     ap.add_argument("--passes", type=int, default=4); ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--bounces", default="0,1,3")
+    ap.add_argument("--build-mode", type=int, default=0, help="fpt_rt_set_build_mode before the rays are captured and traced: 0 quality, 1 fast, 2 trbvh")
     a = ap.parse_args()
     import torch
     import fermat_amd as fa
     from fermat_amd import scene
-    s = scene.testball_room() if a.workload == "testball-room" else scene.bathroom_standin(a.detail)
+    s = scene.testball_room() if a.workload == "testball-room" else scene.bathroom2_standin() if a.workload == "bathroom2" else scene.bathroom_standin(a.detail)
     W, H, L = 1600, 900, 9
     r = fa.Renderer(s, W, H, fa.default_options(L), gbuffer=False)
     r.set_batch(a.passes)
-    out = {"lib": os.path.basename(fa.lib_path()), "workload": a.workload, "triangles": int(s.num_triangles), "bvh": r.bvh_info(), "bounces": {}}
+    if a.build_mode:
+        r.set_build_mode(a.build_mode); r.rebuild_geometry()
+    out = {"lib": os.path.basename(fa.lib_path()), "workload": a.workload, "triangles": int(s.num_triangles), "build_mode": a.build_mode, "bvh": r.bvh_info(), "bounces": {}}
     for b in [int(x) for x in a.bounces.split(",")]:
         r.clear_framebuffer()
         r.set_capture(b)
