@@ -153,7 +153,7 @@ ENTRY_POINTS = ["fpt_create", "fpt_destroy", "fpt_last_error", "fpt_stream", "fp
                 "fpt_rt_trace_shadow", "fpt_rt_trace_shadow_bits", "fpt_rt_trace_counted", "fpt_rt_bvh_info", "fpt_rt_bvh_stats", "fpt_sequence_setup",
                 "fpt_sequence_set_instance", "fpt_sequence_download", "fpt_mesh_lights_init", "fpt_mesh_lights_download", "fpt_pt_init",
                 "fpt_pt_render", "fpt_pt_set_batch", "fpt_pt_render_batch", "fpt_pt_get_stats", "fpt_pt_set_profiling", "fpt_pt_collect_timings", "fpt_pt_set_counting", "fpt_pt_get_trace_counters", "fpt_pt_set_capture", "fpt_pt_get_captured", "fpt_rescale_frame",
-                "fpt_update_variances", "fpt_to_rgba", "fpt_to_rgba_mode", "fpt_filter_variance", "fpt_eaw", "fpt_filter", "fpt_debug_math", "fpt_debug_bsdf",
+                "fpt_update_variances", "fpt_to_rgba", "fpt_to_rgba_mode", "fpt_filter_variance", "fpt_eaw", "fpt_filter", "fpt_debug_math", "fpt_debug_bsdf", "fpt_debug_vertex",
                 "fpt_psfpt_init", "fpt_psfpt_render", "fpt_psfpt_download_cells", "fpt_psfpt_set_sharded", "fpt_psfpt_exchange_cells",
                 "fpt_psfpt_export_cells", "fpt_psfpt_import_cells", "fpt_psfpt_finish", "fpt_psfpt_set_batch", "fpt_psfpt_render_batch", "fpt_psfpt_set_deferred",
                 "fpt_bpt_init", "fpt_bpt_render", "fpt_bpt_set_batch", "fpt_bpt_render_batch", "fpt_bpt_set_deferred", "fpt_bpt_get_stats", "fpt_bpt_set_profiling", "fpt_bpt_download_light_vertices",
@@ -782,3 +782,38 @@ class Renderer:
                                           C.c_void_p(dv.data_ptr() if dv is not None else None), C.c_void_p(out.data_ptr())))
         out = out[:n * 16].reshape(n, 16)
         return out if as_tensor else out.cpu().numpy()
+
+    def debug_vertex(self, op, rec, flags=0, mats=None, textures=None, n=None):
+        """fpt_debug_vertex: one function of the vertex set-up, the emitter sampler or the light-sample weights per element, on this renderer's scene and
+        emitter tables (layouts: include/fermat_pt_hip.h).  rec: (n, 48) float32 records, or ONE record (shape (48,)) read by `n` elements; mats:
+        scene.MATERIAL_DTYPE records (the NEE ops); textures: a list of (H, W, 4) float32 arrays that replace the scene's.  Returns (n, 32) float32."""
+        torch = self.torch
+        rec = np.ascontiguousarray(rec, np.float32)
+        broadcast = rec.ndim == 1
+        n = int(n) if broadcast else len(rec)
+        assert rec.shape[-1] == 48
+        dr = torch.from_numpy(rec.reshape(-1)).to(self.dev)
+        dm, n_mats = None, 0
+        if mats is not None:
+            mats = np.ascontiguousarray(mats)
+            assert mats.dtype.itemsize == 208 and len(mats) > 0
+            dm, n_mats = torch.from_numpy(mats.view(np.uint8).reshape(-1)).to(self.dev), len(mats)
+        dtex, keep = None, []
+        if textures is not None:
+            views = (Texture * max(1, len(textures)))()
+            for i, tx in enumerate(textures):
+                tx = np.ascontiguousarray(tx, np.float32); assert tx.ndim == 3 and tx.shape[2] == 4
+                d = torch.from_numpy(tx.reshape(-1)).to(self.dev); keep.append(d)
+                views[i].texels = d.data_ptr(); views[i].res_x = tx.shape[1]; views[i].res_y = tx.shape[0]
+            dtex = torch.from_numpy(np.frombuffer(bytes(views), np.uint8).copy()).to(self.dev)
+        out = torch.zeros(max(n, 1) * 32, dtype=torch.float32, device=self.dev)
+        torch.cuda.synchronize(self.dev)
+        self._check(self.L.fpt_debug_vertex(self.ctx, C.byref(self.view), C.c_int(op), C.c_uint32(flags), C.c_uint32(n),
+                                            C.c_void_p(dm.data_ptr() if dm is not None else None), C.c_uint32(n_mats),
+                                            C.c_void_p(dtex.data_ptr() if dtex is not None else None), C.c_uint32(len(textures) if textures is not None else 0),
+                                            C.c_void_p(dr.data_ptr()), C.c_uint32(0 if broadcast else 48), C.c_void_p(out.data_ptr())))
+        return out[:n * 32].reshape(n, 32).cpu().numpy()
+
+    def reinit_emitters(self, n_vpls):
+        """fpt_mesh_lights_init again with another VPL count (the probe's emitter tables)"""
+        self._check(self.L.fpt_mesh_lights_init(self.ctx, C.c_uint32(n_vpls), C.byref(self.h_mesh), C.byref(self._h_tex), C.c_uint32(0)))

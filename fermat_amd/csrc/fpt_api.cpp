@@ -17,6 +17,9 @@ namespace fpt {
 // the BSDF probe's launcher (fpt_pt.hip), declared here rather than in fpt_kernels.h: test infrastructure, not part of the wavefront's launch set
 void launch_debug_bsdf(int op, uint32_t flags, uint32_t n, const fpt_material* mats, uint32_t n_mats, const float* table, const float* rec, uint32_t rec_stride,
                        const float* vary, float* out, hipStream_t s);
+// ... and the vertex probe's
+void launch_debug_vertex(int op, uint32_t n, const fpt_rendering_context_view& view, const fpt_material* mats, uint32_t n_mats, const fpt_texture* textures,
+                         uint32_t n_textures, const EmitterView& em, const ShadeRecord* shade_records, const float* rec, uint32_t rec_stride, float* out, hipStream_t s);
 }
 
 namespace {
@@ -1106,6 +1109,32 @@ int fpt_debug_refit_bvh(uint32_t tri_count, const int32_t* h_idx, uint32_t verte
 
 int fpt_debug_math(fpt_context* ctx, int op, uint32_t n, const float* d_in0, const float* d_in1, float* d_out0, float* d_out1)
 { return guarded(ctx, [&] { launch_debug_math(op, n, d_in0, d_in1, d_out0, d_out1, ctx->stream); FPT_HIP_CHECK(hipGetLastError()); FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream)); }); }
+
+int fpt_debug_vertex(fpt_context* ctx, const fpt_rendering_context_view* view, int op, uint32_t flags, uint32_t n, const fpt_material* d_mats, uint32_t n_mats,
+                     const fpt_texture* d_textures, uint32_t n_textures, const float* d_rec, uint32_t rec_stride, float* d_out)
+{
+	return guarded(ctx, [&] {
+		if (op < 0 || op > 9) throw std::runtime_error("fpt_debug_vertex: unknown op");
+		if (!view) throw std::runtime_error("fpt_debug_vertex: null view");
+		if (n && (!d_rec || !d_out)) throw std::runtime_error("fpt_debug_vertex: null array");
+		if (n && (op == 7 || op == 9) && (!d_mats || !n_mats || !view->d_glossy_reflectance)) throw std::runtime_error("fpt_debug_vertex: the NEE ops need materials and the glossy table");
+		if (n && op == 3 && (!d_textures || !n_textures)) throw std::runtime_error("fpt_debug_vertex: the texture op needs textures");
+		if (n && op != 0 && op != 3 && op != 7 && op != 9 && (view->mesh.num_triangles == 0 || !view->mesh.vertex_data || !view->mesh.materials))
+			throw std::runtime_error("fpt_debug_vertex: this op needs the view's mesh");
+		if (n && (op == 4 || op == 5 || op == 6 || op == 8) && !ctx->has_emitters) throw std::runtime_error("fpt_debug_vertex: no emitter tables (fpt_mesh_lights_init)");
+		if (rec_stride != 0 && rec_stride != 48) throw std::runtime_error("fpt_debug_vertex: rec_stride must be 0 or 48");
+		const bool vpl = (flags & 1u) != 0;
+		EmitterView em; std::memset(&em, 0, sizeof(em));
+		em.n_prims = uint32_t(ctx->emitters.mesh_cdf.size()); em.prims_cdf = ctx->d_mesh_cdf.ptr; em.prims_inv_area = ctx->d_mesh_inv_area.ptr;
+		em.n_vpls = vpl ? uint32_t(ctx->emitters.vpls.size()) : 0u; em.vpls = vpl ? ctx->d_vpls.ptr : nullptr; em.norm = ctx->emitters.norm;
+		em.vpl_points = (vpl && (flags & 2u)) ? ensure_vpl_points(ctx, view, ctx->stream) : nullptr;
+		const ShadeRecord* records = op == 2 ? ensure_shade_records(ctx, view, ctx->stream) : nullptr;
+		const fpt_texture* tex = d_textures ? d_textures : view->d_textures;
+		const uint32_t n_tex = d_textures ? n_textures : view->num_textures;
+		launch_debug_vertex(op, n, *view, d_mats, n_mats, tex, n_tex, em, records, d_rec, rec_stride, d_out, ctx->stream);
+		FPT_HIP_CHECK(hipGetLastError()); FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	});
+}
 
 int fpt_debug_bsdf(fpt_context* ctx, int op, uint32_t flags, uint32_t n, const fpt_material* d_mats, uint32_t n_mats, const float* d_table,
                    const float* d_rec, uint32_t rec_stride, const float* d_vary, float* d_out)

@@ -118,12 +118,13 @@ __device__ __forceinline__ float pack_gbuffer_normal(f3 N)
 // (src/pathtracer_core.h:895-988 and :1013-1106; weights per PTVertexProcessor::compute_nee_weights,
 //  src/pathtracer_vertex_processor.h:83-105).  Returns whether a shadow ray is wanted and fills its payload.
 struct ShadowPayload { f3 org, dir, w_d, w_g; };
+struct LightSampleTrace { f3 f_s[4]; float p_s[4], G, mis_w; };        // what light_sample computed on the way (the vertex probe's view; NULL in the kernels)
 // psf_mode: 0 = PTVertexProcessor weights; 1 = PSFPTVertexProcessor, plain; 2 = PSFPTVertexProcessor at a new, valid cache vertex (the diffuse
 // weight is demodulated by the surface albedo `demod`) — compute_nee_weights, src/psfpt_vertex_processor.h:189-248
 __device__ __forceinline__ f3 demodulate(f3 f, f3 c) { return mk3(f.x / sel_max(c.x, 1.0e-4f), f.y / sel_max(c.y, 1.0e-4f), f.z / sel_max(c.z, 1.0e-4f)); }      // src/filters.h:63-67
 __device__ __forceinline__ bool light_sample(const ShadeParams& P, const SurfaceModel& bsdf, const ViewTerms& vt, const SurfacePoint& sp, f3 in, f3 ray_dir, f3 w,
                                              f3 light_pos, f3 light_n, f3 light_radiance, float light_pdf, bool use_mis, float origin_eps, ShadowPayload& out,
-                                             int psf_mode = 0, f3 demod = f3{ 1.0f, 1.0f, 1.0f })
+                                             int psf_mode = 0, f3 demod = f3{ 1.0f, 1.0f, 1.0f }, LightSampleTrace* trace = nullptr)
 {
 	f3 dir_out = light_pos - sp.position;
 	const float d2 = ieee_max(1.0e-8f, dot(dir_out, dir_out));
@@ -141,6 +142,7 @@ __device__ __forceinline__ bool light_sample(const ShadeParams& P, const Surface
 		mis_w = ((P.bounce == 0 && P.opt.direct_lighting_bsdf) || (P.bounce > 0 && P.opt.indirect_lighting_bsdf)) ? mis_power(light_pdf, p_sum * G) : 1.0f;
 	const f3 f_d = ev_d ? f_s[LOBE_DIFF_R] + f_s[LOBE_DIFF_T] : splat3(0.0f);
 	const f3 f_g = ev_g ? f_s[LOBE_GLOSSY_R] + f_s[LOBE_GLOSSY_T] : splat3(0.0f);
+	if (trace) { for (int k = 0; k < 4; ++k) { trace->f_s[k] = f_s[k]; trace->p_s[k] = p_s[k]; } trace->G = G; trace->mis_w = mis_w; }
 	const f3 fl = f_L * G * mis_w;
 	if (psf_mode == 0)
 	{
@@ -166,6 +168,38 @@ __device__ __forceinline__ void write_shadow_entry(const ShadowQueue& q, uint32_
 	q.w_d[slot] = make_float4(pl.w_d.x, pl.w_d.y, pl.w_d.z, as_f32(batched ? pass_k : 0u));
 	q.w_g[slot] = make_float4(pl.w_g.x, pl.w_g.y, pl.w_g.z, 0.0f);
 }
+
+// Two blocks of shade_kernel that the vertex probe (debug_vertex_kernel) runs as they are.  They are macros, expanded in place, because the same bodies as
+// __forceinline__ functions changed shade_kernel's block layout (same operations, other ISA); expanded in place the kernel's instructions are unchanged.
+// The directional-light sample (src/pathtracer_core.h:870-988, src/lights.h:276-294): the light of quantize(z2, n), FAR away against its direction.
+#define FPT_DIRECTIONAL_LIGHT_SAMPLE(want, P, bsdf, vt, sp, in, ray_dir, w, z2, pl, psf_mode, mat_diffuse, trace)                                       \
+	{                                                                                                                                               \
+		const fpt_dir_light L = P.dir_lights[quantize(z2, P.n_dir_lights)];                                                                         \
+		const f3 ldir = mk3(L.dir[0], L.dir[1], L.dir[2]);                                                                                          \
+		const float FAR = 1.0e8f;                                                                                                                   \
+		const f3 lpos = sp.position - ldir * FAR;                                                                                                   \
+		const f3 lrad = FAR * FAR * mk3(L.color[0], L.color[1], L.color[2]);                                                                        \
+		const float lpdf = 1.0f / float(P.n_dir_lights);                                                                                            \
+		want = light_sample(P, bsdf, vt, sp, in, ray_dir, w, lpos, ldir, lrad, lpdf, false, 1.0e-3f, pl, psf_mode, mat_diffuse, trace);             \
+	}
+// The emissive hit's sample, MIS-weighted against NEE at the previous vertex (src/pathtracer_core.h:1109-1154): declares `lpdf`, the light pdf of the hit
+// point (area measure), `mis_w` and `e` = w f_L mis_w; the BSDF's pdf of reaching the point is p1 = |cos| / d^2 * p_prev (p_prev: the SOLID-ANGLE pdf of the
+// scattering that led here, surface_sample's p).
+#define FPT_EMISSIVE_HIT(lpdf, mis_w, e, P, tri, m_emissive, sp, in, hit_t, p_prev, w)                                                                 \
+	f3 lrad; float lpdf;                                                                                                                            \
+	if (P.emitters.n_vpls || P.emitters.n_prims)                                                                                                    \
+	{                                                                                                                                               \
+		if (P.emitters.n_vpls) lpdf = emission_pdf_measure(m_emissive) / P.emitters.norm;                                                           \
+		else                   lpdf = (P.emitters.prims_cdf[tri] - (tri ? P.emitters.prims_cdf[tri - 1] : 0)) * P.emitters.prims_inv_area[tri];    \
+		lrad = xyz(m_emissive);                                                                                                                     \
+	}                                                                                                                                               \
+	else { lpdf = 1.0f; lrad = splat3(0.0f); }                                                                                                      \
+	const f3 f_L = dot(sp.frame.n, in) > 0.0f ? lrad : splat3(0.0f);                                                                                \
+	const float d2 = ieee_max(1.0e-10f, hit_t * hit_t);                                                                                             \
+	const float G_partial = fabsf(dot(in, sp.frame.n)) / d2;                                                                                        \
+	const float p1 = (is_finite(G_partial) && is_finite(p_prev)) ? G_partial * p_prev : inf_f();                                                    \
+	const float mis_w = ((P.bounce == 1 && P.opt.direct_lighting_nee) || (P.bounce > 1 && P.opt.indirect_lighting_nee)) ? mis_power(p1, lpdf) : 1.0f; \
+	const f3 e = w * f_L * mis_w;
 
 // ---- path-space filtering helpers (src/psfpt_vertex_processor.h, src/spatial_hash.h) ------------------------------------------------
 __device__ __forceinline__ float round_half_down(float x) { const int y = x > 0.0f ? to_i32_sat(x) : to_i32_sat(x) - 1; return (x - float(y) > 0.5f) ? float(y) + 1.0f : float(y); }    // cugar::round
@@ -366,16 +400,7 @@ void shade_kernel(const ShadeParams P)
 	if (!(FPT_SHADE_SKIP & 1) && (P.bounce + 2 <= P.opt.max_path_length) && (P.bounce > 0 || P.opt.direct_lighting) && P.n_dir_lights)
 	{
 		ShadowPayload pl; bool want = false;
-		if (active)
-		{
-			const fpt_dir_light L = P.dir_lights[quantize(z[2], P.n_dir_lights)];
-			const f3 ldir = mk3(L.dir[0], L.dir[1], L.dir[2]);
-			const float FAR = 1.0e8f;
-			const f3 lpos = sp.position - ldir * FAR;
-			const f3 lrad = FAR * FAR * mk3(L.color[0], L.color[1], L.color[2]);
-			const float lpdf = 1.0f / float(P.n_dir_lights);
-			want = light_sample(P, bsdf, vt, sp, in, ray_dir, w, lpos, ldir, lrad, lpdf, false, 1.0e-3f, pl, psf_mode, mat_diffuse);
-		}
+		if (active) FPT_DIRECTIONAL_LIGHT_SAMPLE(want, P, bsdf, vt, sp, in, ray_dir, w, z[2], pl, psf_mode, mat_diffuse, nullptr)
 		const uint32_t qslot = block_append_slot(P.shadow_dir.size, want, sc_dir);
 		if (want) { write_shadow_entry(P.shadow_dir, qslot, pl, 0x1u, pixel_info, P.pass.n_passes > 1, slot.k); if (PSF) P.shadow_dir.vinfo[qslot] = vinfo; }
 	}
@@ -396,20 +421,7 @@ void shade_kernel(const ShadeParams P)
 	//  the `max_comp(e) > 0 && all_finite(e)` test that guards every use of it.  Testing the emission first skips the pdf look-ups and the MIS weight for whole waves.)
 	if (!(FPT_SHADE_SKIP & 4) && P.do_emissive && active && (m_emissive.x != 0.0f || m_emissive.y != 0.0f || m_emissive.z != 0.0f))
 	{
-		f3 lrad; float lpdf;
-		if (P.emitters.n_vpls || P.emitters.n_prims)
-		{
-			if (P.emitters.n_vpls) lpdf = emission_pdf_measure(m_emissive) / P.emitters.norm;
-			else                   lpdf = (P.emitters.prims_cdf[tri] - (tri ? P.emitters.prims_cdf[tri - 1] : 0)) * P.emitters.prims_inv_area[tri];
-			lrad = xyz(m_emissive);
-		}
-		else { lpdf = 1.0f; lrad = splat3(0.0f); }
-		const f3 f_L = dot(sp.frame.n, in) > 0.0f ? lrad : splat3(0.0f);
-		const float d2 = ieee_max(1.0e-10f, hit_t * hit_t);
-		const float G_partial = fabsf(dot(in, sp.frame.n)) / d2;
-		const float p1 = (is_finite(G_partial) && is_finite(p_prev)) ? G_partial * p_prev : inf_f();
-		const float mis_w = ((P.bounce == 1 && P.opt.direct_lighting_nee) || (P.bounce > 1 && P.opt.indirect_lighting_nee)) ? mis_power(p1, lpdf) : 1.0f;
-		const f3 e = w * f_L * mis_w;
+		FPT_EMISSIVE_HIT(lpdf, mis_w, e, P, tri, m_emissive, sp, in, hit_t, p_prev, w)
 		if (PSF && max_comp(e) > 0.0f && all_finite(e))
 		{
 			// PSFPTVertexProcessor::accumulate_emissive (src/psfpt_vertex_processor.h:288-343): to the image until a cache vertex exists, to its cell afterwards
@@ -885,6 +897,92 @@ __global__ void debug_bsdf_kernel(int op, uint32_t flags, uint32_t n, const fpt_
 	else if (op == 13) o[0] = directional_albedo(m, q[0]);
 }
 
+// Vertex probe: one function of the vertex set-up, the emitter sampler or the light-sample weights per element, on records a test chose
+// (tests/test_vertex_truth.py; the oracle's orc_vertex_probe_n is its CPU twin).  Records of VERTEX_PROBE_REC floats, outputs of VERTEX_PROBE_OUT floats;
+// integer fields travel as their bits.  Layouts per op in include/fermat_pt_hip.h.  flags: 1 = the VPL instantiation of the emitters (nee_type 1),
+// 2 = with the tabulated VPL light points.  The NEE ops build the vertex's surface model from mats[slot]; everything else reads the view's scene.
+enum : uint32_t { VERTEX_PROBE_REC = 48, VERTEX_PROBE_OUT = 32 };
+__global__ void debug_vertex_kernel(int op, uint32_t n, fpt_rendering_context_view view, const fpt_material* mats, uint32_t n_mats,
+                                    const fpt_texture* textures, uint32_t n_textures, EmitterView em, const ShadeRecord* shade_records,
+                                    const float* rec, uint32_t rec_stride, float* out)
+{
+	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
+	if (i >= n) return;
+	const float* r = rec + size_t(i) * rec_stride;
+	float* o = out + size_t(i) * VERTEX_PROBE_OUT;
+	for (uint32_t k = 0; k < VERTEX_PROBE_OUT; ++k) o[k] = 0.0f;
+	auto put3 = [&](int k, f3 v) { o[k] = v.x; o[k + 1] = v.y; o[k + 2] = v.z; };
+	auto get3 = [&](int k) { return mk3(r[k], r[k + 1], r[k + 2]); };
+	auto put_sp = [&](const SurfacePoint& sp, float area_pdf)
+	{ put3(0, sp.position); put3(3, sp.frame.ng); put3(6, sp.frame.n); put3(9, sp.frame.t); put3(12, sp.frame.b); o[15] = sp.s; o[16] = sp.t; o[17] = area_pdf; };
+	const uint32_t n_tris = view.mesh.num_triangles;
+	const uint32_t tri = n_tris ? sel_min(as_u32(r[0]), n_tris - 1u) : 0u;
+	ShadeParams P = {};
+	P.mesh = view.mesh; P.textures = textures; P.table = view.d_glossy_reflectance; P.dir_lights = view.d_dir_lights; P.n_dir_lights = view.dir_lights_count;
+	P.emitters = em;
+	const uint32_t ob = as_u32(r[38]);
+	P.bounce = as_u32(r[37]);
+	P.opt.diffuse_scattering = ob & 1u; P.opt.glossy_scattering = (ob >> 1) & 1u; P.opt.direct_lighting_bsdf = (ob >> 2) & 1u; P.opt.indirect_lighting_bsdf = (ob >> 3) & 1u;
+	P.opt.direct_lighting_nee = (ob >> 4) & 1u; P.opt.indirect_lighting_nee = (ob >> 5) & 1u;
+	if (op == 0)                          // surface_point_of on three vertex records, three packed texture coordinates
+	{
+		SurfacePoint sp; float pdf = 0.0f;
+		const float ts[2] = { r[16], r[17] }, tb[2] = { r[18], r[19] };
+		surface_point_of(mk4(r[0], r[1], r[2], r[3]), mk4(r[4], r[5], r[6], r[7]), mk4(r[8], r[9], r[10], r[11]), as_u32(r[15]) != 0u,
+		                 int32_t(as_u32(r[12])), int32_t(as_u32(r[13])), int32_t(as_u32(r[14])), ts, tb, r[20], r[21], sp, &pdf);
+		put_sp(sp, pdf);
+	}
+	else if (op == 1 && n_tris) { SurfacePoint sp; float pdf = 0.0f; surface_point(view.mesh, tri, r[20], r[21], sp, &pdf); put_sp(sp, pdf); }
+	else if (op == 2 && n_tris) { SurfacePoint sp; surface_point(shade_records[tri], view.mesh, r[20], r[21], sp); put_sp(sp, 0.0f); }
+	else if (op == 3)                     // sample_texture
+	{
+		fpt_texture_ref ref; ref.texture = as_u32(r[0]); ref._pad = 0; ref.scaling[0] = r[1]; ref.scaling[1] = r[2];
+		if (ref.texture != 0xFFFFFFFFu && ref.texture >= n_textures) ref.texture = 0xFFFFFFFFu;
+		const f4 c = sample_texture(textures, ref, r[3], r[4], mk4(r[5], r[6], r[7], r[8]));
+		o[0] = c.x; o[1] = c.y; o[2] = c.z; o[3] = c.w;
+	}
+	else if (op == 4)                     // emitter_pick + emitter_sample
+	{
+		uint32_t t = 0; float u = 0.0f, v = 0.0f;
+		o[13] = emitter_pick(em, r[0], r[1], r[2], t, u, v) ? 1.0f : 0.0f;
+		SurfacePoint lp; f3 rad; float pdf;
+		emitter_sample(em, view.mesh, textures, r[0], r[1], r[2], lp, rad, pdf);
+		o[0] = as_f32(t); o[1] = u; o[2] = v; put3(3, lp.position); put3(6, lp.frame.n); put3(9, rad); o[12] = pdf;
+	}
+	else if (op == 5) { const LightPoint lp = emitter_light_point(em, view.mesh, textures, r[0], r[1], r[2]); put3(0, lp.position); put3(3, lp.normal); put3(6, lp.radiance); o[9] = lp.pdf; }
+	else if (op == 6 && n_tris) { f3 rad; float pdf; emitter_at(em, view.mesh, textures, tri, r[1], r[2], rad, pdf); put3(0, rad); o[3] = pdf; }
+	else if (op == 7 || op == 9)          // light_sample: a mesh-light point from the record (7), the directional light of quantize(z2, n) (9)
+	{
+		const fpt_material* mat = mats + sel_min(as_u32(r[0]), n_mats - 1u);
+		const SurfaceModel bsdf = make_surface_model(xyz(load4(mat->diffuse)), xyz(load4(mat->diffuse_trans)), xyz(load4(mat->specular)), xyz(load4(mat->reflectivity)),
+		                                             mat->roughness, mat->index_of_refraction, mat->opacity, view.d_glossy_reflectance);
+		SurfacePoint sp;
+		sp.frame.n = get3(1); sp.frame.ng = get3(4); sp.frame.t = get3(7); sp.frame.b = get3(10); sp.position = get3(13); sp.s = sp.t = 0.0f;
+		const f3 in = get3(16);
+		const ViewTerms vt = view_terms(bsdf, sp.frame, in);
+		ShadowPayload pl; pl.org = pl.dir = pl.w_d = pl.w_g = splat3(0.0f);
+		LightSampleTrace tr;
+		const int psf_mode = int(as_u32(r[39]));
+		bool want = false;
+		const f3 ray_dir = get3(19), w = get3(22), demod = get3(40);
+		if (op == 7) want = light_sample(P, bsdf, vt, sp, in, ray_dir, w, get3(25), get3(28), get3(31), r[34], as_u32(r[35]) != 0u, r[36], pl, psf_mode, demod, &tr);
+		else if (view.dir_lights_count) FPT_DIRECTIONAL_LIGHT_SAMPLE(want, P, bsdf, vt, sp, in, ray_dir, w, r[44], pl, psf_mode, demod, &tr)
+		o[0] = want ? 1.0f : 0.0f; put3(1, pl.w_d); put3(4, pl.w_g);
+		if (want) { put3(7, pl.org); put3(10, pl.dir); }
+		if (op == 7 || view.dir_lights_count) { for (int k = 0; k < 4; ++k) { put3(13 + 3 * k, tr.f_s[k]); o[25 + k] = tr.p_s[k]; } o[29] = tr.G; o[30] = tr.mis_w; }
+	}
+	else if (op == 8 && n_tris)           // the emissive hit's weight
+	{
+		SurfacePoint sp; sp.frame.n = get3(1); sp.frame.ng = sp.frame.n; sp.frame.t = sp.frame.b = splat3(0.0f); sp.position = splat3(0.0f); sp.s = sp.t = 0.0f;
+		const int32_t t = int32_t(tri);
+		const f4 emission = mk4(r[4], r[5], r[6], r[7]);
+		const f3 in = get3(8), w = get3(13);
+		const float hit_t = r[11], p_prev = r[12];
+		FPT_EMISSIVE_HIT(lpdf, mis_w, e, P, t, emission, sp, in, hit_t, p_prev, w)
+		o[0] = lpdf; o[1] = mis_w; put3(2, e);
+	}
+}
+
 // ---- launchers ----------------------------------------------------------------------------------------------------------
 static inline uint32_t blocks_for(uint32_t n, uint32_t b) { return n ? (n + b - 1) / b : 1; }
 
@@ -934,5 +1032,8 @@ void launch_debug_math(int op, uint32_t n, const float* a, const float* b, float
 void launch_debug_bsdf(int op, uint32_t flags, uint32_t n, const fpt_material* mats, uint32_t n_mats, const float* table, const float* rec, uint32_t rec_stride,
                        const float* vary, float* out, hipStream_t s)
 { hipLaunchKernelGGL(debug_bsdf_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, op, flags, n, mats, n_mats, table, rec, rec_stride, vary, out); }
+void launch_debug_vertex(int op, uint32_t n, const fpt_rendering_context_view& view, const fpt_material* mats, uint32_t n_mats, const fpt_texture* textures,
+                         uint32_t n_textures, const EmitterView& em, const ShadeRecord* shade_records, const float* rec, uint32_t rec_stride, float* out, hipStream_t s)
+{ hipLaunchKernelGGL(debug_vertex_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, op, n, view, mats, n_mats, textures, n_textures, em, shade_records, rec, rec_stride, out); }
 
 } // namespace fpt

@@ -158,6 +158,28 @@ FPT_HD uint32_t upper_bound(const float* a, uint32_t n, float x)           // co
 // what light_sample needs of an emitter sample: the point, its shading normal, the radiance it emits and the pdf of having drawn it
 struct LightPoint { f3 position, normal, radiance; float pdf; };
 
+// the (triangle, barycentrics) an emitter sample lands on: the VPL at index floor(z2 n_vpls), clamped, or the triangle of the CDF's upper bound at
+// min(z2, 1 - 2^-24) with (z0, z1) folded into it.  False when there are no emitters.  emitter_sample's own first half, stated apart for the vertex probe
+// (fpt_debug_vertex): emitter_sample built on it changed the kernels' block layout.  tests/test_vertex_truth.py holds the two together -- the point
+// emitter_sample returns is, bit for bit, the surface point of this pick.
+FPT_HD bool emitter_pick(const EmitterView& em, float z0, float z1, float z2, uint32_t& tri, float& u, float& v)
+{
+	if (em.n_vpls)
+	{
+		const uint32_t l = sel_min(to_u32_sat(z2 * float(em.n_vpls)), em.n_vpls - 1);
+		const fpt_vpl vp = em.vpls[l];
+		tri = vp.prim_id; u = vp.uv[0]; v = vp.uv[1];
+	}
+	else if (em.n_prims)
+	{
+		tri = upper_bound(em.prims_cdf, em.n_prims, sel_min(z2, as_f32(0x3F7FFFFFu)));
+		u = z0; v = z1;
+		if (u + v > 1.0f) { u = 1.0f - u; v = 1.0f - v; }
+	}
+	else return false;
+	return true;
+}
+
 // draw an emitter point (MeshLight::sample_impl, src/lights.h:309-355)
 FPT_HD void emitter_sample(const EmitterView& em, const fpt_mesh_view& mesh, const fpt_texture* textures, float z0, float z1, float z2,
                            SurfacePoint& lp, f3& radiance, float& pdf)

@@ -451,6 +451,29 @@ int fpt_debug_math(fpt_context* ctx, int op, uint32_t n, const float* d_in0, con
 int fpt_debug_bsdf(fpt_context* ctx, int op, uint32_t flags, uint32_t n, const fpt_material* d_mats, uint32_t n_mats, const float* d_table,
                    const float* d_rec, uint32_t rec_stride, const float* d_vary, float* d_out);
 
+/* Vertex probe: runs one function of the vertex set-up, the emitter sampler or the light-sample weights per element.  `view` is a HOST struct of device
+ * pointers (the scene's mesh, textures, glossy table and directional lights); the emitter tables are the context's (fpt_mesh_lights_init).  DEVICE arrays:
+ * mats (n_mats records: the NEE ops' surface models), textures (n_textures views; NULL = the view's), rec (48 floats per element, rec_stride 48; 0 = every
+ * element reads record 0), out (32 floats per element, zero where an op writes nothing).  Integer fields (marked #) hold their BITS.
+ * flags: 1 the VPL instantiation of the emitters (else the triangle CDF), 2 with the tabulated VPL light points.
+ * Surface point out: [0..2] position, [3..5] ng, [6..8] n, [9..11] t, [12..14] b, [15] s, [16] t, [17] area pdf (0 for op 2).
+ *   0 surface_point_of: rec [0..11] three vertex float4 (.w = packed-normal bits), [12..14] # packed half2 texcoords (< 0 = none), [15] # has texcoords,
+ *     [16..17] tex_scale, [18..19] tex_bias, [20] u, [21] v
+ *   1 surface_point(mesh, tri, u, v) / 2 surface_point(ShadeRecord, ...): rec [0] # tri, [20] u, [21] v
+ *   3 sample_texture: rec [0] # texture (>= n_textures = invalid), [1..2] scaling, [3] s, [4] t, [5..8] fallback -> out [0..3]
+ *   4 emitter_sample(z): rec [0..2] z -> [0] # tri, [1] u, [2] v, [3..5] position, [6..8] n, [9..11] radiance, [12] pdf, [13] picked
+ *   5 emitter_light_point(z): rec [0..2] z -> [0..2] position, [3..5] normal, [6..8] radiance, [9] pdf
+ *   6 emitter_at: rec [0] # tri, [1] s, [2] t -> [0..2] radiance, [3] pdf
+ *   7 light_sample / 9 the directional light of quantize(z2, n): rec [0] # material slot, [1..12] frame n, ng, t, b, [13..15] position, [16..18] in,
+ *     [19..21] ray_dir, [22..24] w, [25..27] light position, [28..30] light normal, [31..33] light radiance, [34] light pdf, [35] # use_mis, [36] origin_eps,
+ *     [37] # bounce, [38] # options (1 diffuse_scattering, 2 glossy_scattering, 4 direct_lighting_bsdf, 8 indirect_lighting_bsdf), [39] # psf_mode,
+ *     [40..42] demod, [44] z2 (op 9) -> [0] want, [1..3] w_d, [4..6] w_g, [7..9] shadow origin, [10..12] shadow dir (when wanted),
+ *     [13..24] f_s[4][3], [25..28] p_s[4] (what surface_f_and_p gave inside), [29] G, [30] mis_w
+ *   8 the emissive hit's weight: rec [0] # tri, [1..3] n, [4..7] emission, [8..10] in, [11] hit t, [12] p_prev, [13..15] w, [37] # bounce,
+ *     [38] # options (16 direct_lighting_nee, 32 indirect_lighting_nee) -> [0] light pdf, [1] mis_w, [2..4] e */
+int fpt_debug_vertex(fpt_context* ctx, const fpt_rendering_context_view* view, int op, uint32_t flags, uint32_t n, const fpt_material* d_mats, uint32_t n_mats,
+                     const fpt_texture* d_textures, uint32_t n_textures, const float* d_rec, uint32_t rec_stride, float* d_out);
+
 /* host-side probe of the acceleration-structure builder behind fpt_rt_create_geometry (no GPU, no context; HOST arrays in, HOST arrays out):
  * *node_words = 32-bit words per node (20: the 80-byte 8-wide compressed node, see fermat_amd/csrc/fpt_bvh.h), records = 48-byte triangle
  * records {v0, e1 = v1 - v0, e2 = v2 - v0, triangle id, shadow mask, delta} -- delta: the constant part of the tolerance of the intersector's box clause for this triangle,

@@ -82,6 +82,8 @@ struct PathEntry      // in_queue / scatter_queue entry : 88 B in the reference 
 	Ray ray; Hit hit; V4 weight; u32 pixel_info; float cone_x, cone_y;
 	u32 vertex_info;    // pixels.y of the reference's uint4: what the vertex processor returned at the previous vertex (0xFFFFFFFF for the plain PT)
 };
+// what nee_sample computed on the way (the vertex probe's view, orc_vertex_probe_n)
+struct NeeTrace { V3 f_s[4]; float p_s[4], G, mis_w; V3 w_d, w_g, org, dir; bool want; };
 struct ShadowEntry    // shadow_queue entry : 112 B
 {
 	Ray ray; Hit hit; V3 w, w_d, w_g; u32 pixel_info;
@@ -243,7 +245,7 @@ struct PathTracer
 
 	// NEE / directional shared tail : src/pathtracer_core.h:1013-1106 (mesh) and :895-988 (directional)
 	void nee_sample(const EyeVertex& ev, const PathEntry& e, const VertexGeometry& lg, float light_pdf, const Edf& edf,
-	                bool use_mis, float origin_eps, u32 mask, std::vector<ShadowEntry>& queue, u32 vertex_info = 0xFFFFFFFFu)
+	                bool use_mis, float origin_eps, u32 mask, std::vector<ShadowEntry>& queue, u32 vertex_info = 0xFFFFFFFFu, NeeTrace* trace = nullptr)
 	{
 		const V3 w = e.weight.xyz();
 		V3 out = lg.position - ev.geom.position;
@@ -271,11 +273,17 @@ struct PathTracer
 		V3 out_w_g = (in_bounce == 0 ? f_g : f_d + f_g) * w * fl;
 		if (psf) psf_nee_weights(ev, vertex_info, f_d, f_g, w, fl, out_w_d, out_w_g);
 		const V3 out_w = out_w_d + out_w_g;
+		if (trace)
+		{
+			for (int k = 0; k < 4; ++k) { trace->f_s[k] = f_s[k]; trace->p_s[k] = p_s[k]; }
+			trace->G = G; trace->mis_w = mis_w; trace->w_d = out_w_d; trace->w_g = out_w_g; trace->want = false;
+		}
 		if (max_comp(out_w) > 0.0f && finite3(out_w))
 		{
 			const V3 rd(e.ray.dx, e.ray.dy, e.ray.dz);
 			const V3 org = ev.geom.position - rd * origin_eps;
 			const V3 dir = lg.position - org;
+			if (trace) { trace->want = true; trace->org = org; trace->dir = dir; }
 			ShadowEntry s;
 			s.ray.ox = org.x; s.ray.oy = org.y; s.ray.oz = org.z; s.ray.mask_or_tmin = mask;
 			s.ray.dx = dir.x; s.ray.dy = dir.y; s.ray.dz = dir.z; s.ray.tmax = 0.9999f;
@@ -288,6 +296,38 @@ struct PathTracer
 				s.vertex_info = (in_bounce < psf->options.psf_depth) ? 0xFFFFFFFFu : cache_info(ci_slot(vertex_info), ci_new(vertex_info) ? 1u : 3u, 0);
 			queue.push_back(s);
 		}
+	}
+
+	// directional lights : :870-988 -- the light of quantize(z2, n), FAR away against its direction (src/lights.h:276-294)
+	void directional_sample(const EyeVertex& ev, const PathEntry& e, float z2, std::vector<ShadowEntry>& queue, u32 vertex_info, NeeTrace* trace = nullptr)
+	{
+		const u32 li = quantize(z2, scene.dir_lights_count);
+		const DirectionalLight& L = scene.dir_lights[li];
+		VertexGeometry lg;
+		const float FAR = 1.0e8f;
+		lg.position = ev.geom.position - L.dir * FAR;
+		lg.normal_s = lg.normal_g = L.dir;
+		lg.tangent = orthogonal(L.dir);
+		lg.binormal = cross(L.dir, lg.tangent);
+		float light_pdf = 1.0f;
+		Edf edf; edf.color = FAR * FAR * L.color;
+		light_pdf /= float(scene.dir_lights_count);
+		nee_sample(ev, e, lg, light_pdf, edf, false, 1.0e-3f, 0x1u, queue, vertex_info, trace);
+	}
+	// emissive hit : :1109-1154 -- the sample w f_L mis_w, MIS-weighted against NEE at the previous vertex; p_prev = the solid-angle pdf of the scattering
+	V3 emissive_weight(const EyeVertex& ev, u32 tri, float hit_t, float p_prev, V3 w, float* out_light_pdf = nullptr, float* out_mis_w = nullptr) const
+	{
+		float light_pdf; Edf edf;
+		light().map_geom(tri, ev.geom, &light_pdf, &edf);
+		const V3 f_L = edf.f(ev.geom, ev.in);
+		const float d2 = fmax_ieee(1.0e-10f, hit_t * hit_t);
+		const float G_partial = fabsf(dot(ev.in, ev.geom.normal_s)) / d2;
+		const float p1 = pdf_product(G_partial, p_prev);
+		const float p2 = light_pdf;
+		const float mis_w = ((in_bounce == 1 && options.direct_lighting_nee) || (in_bounce > 1 && options.indirect_lighting_nee)) ? power_heuristic(p1, p2) : 1.0f;
+		if (out_light_pdf) *out_light_pdf = light_pdf;
+		if (out_mis_w) *out_mis_w = mis_w;
+		return w * f_L * mis_w;
 	}
 
 	// src/pathtracer_core.h:771-1254
@@ -331,20 +371,7 @@ struct PathTracer
 
 		// directional lights : :870-988
 		if ((in_bounce + 2 <= options.max_path_length) && (in_bounce > 0 || options.direct_lighting) && scene.dir_lights_count)
-		{
-			const u32 li = quantize(samples[2], scene.dir_lights_count);
-			const DirectionalLight& L = scene.dir_lights[li];
-			VertexGeometry lg;
-			const float FAR = 1.0e8f;                                   // src/lights.h:276-294
-			lg.position = ev.geom.position - L.dir * FAR;
-			lg.normal_s = lg.normal_g = L.dir;
-			lg.tangent = orthogonal(L.dir);
-			lg.binormal = cross(L.dir, lg.tangent);
-			float light_pdf = 1.0f;
-			Edf edf; edf.color = FAR * FAR * L.color;
-			light_pdf /= float(scene.dir_lights_count);
-			nee_sample(ev, e, lg, light_pdf, edf, false, 1.0e-3f, 0x1u, out_shadow_dir, vertex_info);
-		}
+			directional_sample(ev, e, samples[2], out_shadow_dir, vertex_info);
 		// mesh / VPL next-event estimation : :991-1106
 		if (do_nee)
 		{
@@ -355,15 +382,7 @@ struct PathTracer
 		// emissive hit : :1109-1154
 		if (do_accumulate_emissive)
 		{
-			float light_pdf; Edf edf;
-			light().map_geom(u32(hit.triId), ev.geom, &light_pdf, &edf);
-			const V3 f_L = edf.f(ev.geom, ev.in);
-			const float d2 = fmax_ieee(1.0e-10f, hit.t * hit.t);
-			const float G_partial = fabsf(dot(ev.in, ev.geom.normal_s)) / d2;
-			const float p1 = pdf_product(G_partial, p_prev);
-			const float p2 = light_pdf;
-			const float mis_w = ((in_bounce == 1 && options.direct_lighting_nee) || (in_bounce > 1 && options.indirect_lighting_nee)) ? power_heuristic(p1, p2) : 1.0f;
-			const V3 out_w = w * f_L * mis_w;
+			const V3 out_w = emissive_weight(ev, u32(hit.triId), hit.t, p_prev, w);
 			if (max_comp(out_w) > 0.0f && finite3(out_w))
 			{
 				if (psf) psf_accumulate_emissive(e.pixel_info, prev_vertex_info, out_w);

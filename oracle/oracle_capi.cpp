@@ -212,6 +212,125 @@ void orc_bsdf_probe_n(i32 op, u32 flags, u32 n, const Material* mats, u32 n_mats
 		else if (op == 13) o[0] = b.glossy_reflectance(q[0]);
 	}
 }
+// twin of the device vertex probe fpt_debug_vertex (include/fermat_pt_hip.h has the record and output layouts) on the oracle's scene and emitter tables:
+// setup_differential_geometry, bilinear_texture_lookup, MeshLight::sample / map_geom, nee_sample's weights and the emissive hit's.  The oracle has no
+// ShadeRecord and no tabulated VPL points: ops 2 and 5 run what they stand for (ops 1 and 4).  textures: NULL = the scene's.
+void orc_vertex_probe_n(orc_pt* h, i32 op, u32 flags, u32 n, const Material* mats, u32 n_mats, const Texture* textures, u32 n_textures,
+                        const float* rec, u32 rec_stride, float* out)
+{
+	const PathTracer& base = h->pt;
+	const Mesh& mesh = base.scene.mesh;
+	const Texture* tex = textures ? textures : base.scene.textures;
+	const u32 n_tex = textures ? n_textures : u32(h->textures.size());
+	const MeshLight& ml = (flags & 1u) ? base.scene.mesh_vpls : base.scene.mesh_light;
+	const u32 n_tris = u32(mesh.num_triangles);
+	#pragma omp parallel for schedule(static)
+	for (i32 i = 0; i < i32(n); ++i)
+	{
+		const float* r = rec + size_t(i) * rec_stride;
+		float* o = out + 32 * size_t(i);
+		for (int k = 0; k < 32; ++k) o[k] = 0.0f;
+		auto put3 = [&](int k, V3 v) { o[k] = v.x; o[k + 1] = v.y; o[k + 2] = v.z; };
+		auto get3 = [&](int k) { return V3(r[k], r[k + 1], r[k + 2]); };
+		auto put_geom = [&](const VertexGeometry& g, float pdf)
+		{ put3(0, g.position); put3(3, g.normal_g); put3(6, g.normal_s); put3(9, g.tangent); put3(12, g.binormal); o[15] = g.texture_coords.x; o[16] = g.texture_coords.y; o[17] = pdf; };
+		const u32 tri = n_tris ? minu(f2bits(r[0]), n_tris - 1u) : 0u;
+		PathTracer pt;
+		pt.options = base.options; pt.scene = base.scene; pt.scene.textures = tex;
+		const u32 ob = f2bits(r[38]);
+		pt.in_bounce = f2bits(r[37]);
+		pt.options.diffuse_scattering = ob & 1u; pt.options.glossy_scattering = (ob >> 1) & 1u;
+		pt.options.direct_lighting_bsdf = (ob >> 2) & 1u; pt.options.indirect_lighting_bsdf = (ob >> 3) & 1u;
+		pt.options.direct_lighting_nee = (ob >> 4) & 1u; pt.options.indirect_lighting_nee = (ob >> 5) & 1u;
+		pt.options.nee_type = (flags & 1u) ? 1u : 0u;
+		if (op == 0)
+		{
+			const i32 vi[4] = { 0, 1, 2, 0 };
+			const i32 tc[4] = { i32(f2bits(r[12])), i32(f2bits(r[13])), i32(f2bits(r[14])), 0 };
+			Mesh m; std::memset(&m, 0, sizeof(m));
+			m.num_triangles = 1; m.num_vertices = 3; m.vertex_indices = vi; m.vertex_data = r; m.texture_indices_comp = f2bits(r[15]) ? tc : nullptr;
+			m.tex_scale[0] = r[16]; m.tex_scale[1] = r[17]; m.tex_bias[0] = r[18]; m.tex_bias[1] = r[19];
+			VertexGeometry g; float pdf = 0.0f;
+			setup_differential_geometry(m, 0, r[20], r[21], &g, &pdf);
+			put_geom(g, pdf);
+		}
+		else if ((op == 1 || op == 2) && n_tris)
+		{
+			VertexGeometry g; float pdf = 0.0f;
+			setup_differential_geometry(mesh, tri, r[20], r[21], &g, op == 1 ? &pdf : nullptr);
+			put_geom(g, pdf);
+		}
+		else if (op == 3)
+		{
+			TexRef ref; ref.texture = f2bits(r[0]); ref._pad = 0; ref.sx = r[1]; ref.sy = r[2];
+			if (ref.texture != 0xFFFFFFFFu && ref.texture >= n_tex) ref.texture = 0xFFFFFFFFu;
+			const V4 c = bilinear_texture_lookup(V4(r[3], r[4], 0.0f, 0.0f), ref, tex, V4(r[5], r[6], r[7], r[8]));
+			o[0] = c.x; o[1] = c.y; o[2] = c.z; o[3] = c.w;
+		}
+		else if (op == 4 || op == 5)
+		{
+			MeshLight l = ml; l.textures = tex;
+			u32 prim = 0; float u = 0.0f, v = 0.0f; VertexGeometry g; float pdf; Edf edf;
+			g.position = V3(0.0f); g.normal_s = V3(0, 0, 1);
+			l.sample(r, &prim, &u, &v, &g, &pdf, &edf);
+			if (op == 4) { o[0] = bits2f(prim); o[1] = u; o[2] = v; put3(3, g.position); put3(6, g.normal_s); put3(9, edf.color); o[12] = pdf; o[13] = (l.n_vpls || l.n_prims) ? 1.0f : 0.0f; }
+			else { put3(0, g.position); put3(3, g.normal_s); put3(6, edf.color); o[9] = pdf; }
+		}
+		else if (op == 6 && n_tris)
+		{
+			MeshLight l = ml; l.textures = tex;
+			VertexGeometry g; g.texture_coords = V4(r[1], r[2], 0.0f, 0.0f);
+			float pdf; Edf edf;
+			l.map_geom(tri, g, &pdf, &edf);
+			put3(0, edf.color); o[3] = pdf;
+		}
+		else if (op == 7 || op == 9)
+		{
+			EyeVertex ev;
+			ev.geom.normal_s = get3(1); ev.geom.normal_g = get3(4); ev.geom.tangent = get3(7); ev.geom.binormal = get3(10); ev.geom.position = get3(13);
+			ev.in = get3(16);
+			ev.material = mats[minu(f2bits(r[0]), n_mats - 1u)];
+			ev.material.diffuse = V4(r[40], r[41], r[42], 0.0f);        // what psf_nee_weights demodulates by (the device takes it from the record too)
+			Material bm = mats[minu(f2bits(r[0]), n_mats - 1u)];
+			ev.bsdf.setup(bm, base.scene.glossy_reflectance);
+			PathEntry e{};
+			e.ray.dx = r[19]; e.ray.dy = r[20]; e.ray.dz = r[21];
+			e.weight = V4(r[22], r[23], r[24], 0.0f);
+			PsfState ps; ps.options.psf_depth = 0;
+			const u32 psf_mode = f2bits(r[39]);
+			if (psf_mode) pt.psf = &ps;
+			const u32 vinfo = psf_mode == 2 ? cache_info(0, 0, 1) : 0xFFFFFFFFu;
+			std::vector<ShadowEntry> q;
+			NeeTrace tr{};
+			bool ran = true;
+			if (op == 7)
+			{
+				VertexGeometry lg; lg.position = get3(25); lg.normal_s = lg.normal_g = get3(28);
+				Edf edf; edf.color = get3(31);
+				pt.nee_sample(ev, e, lg, r[34], edf, f2bits(r[35]) != 0u, r[36], 0x2u, q, vinfo, &tr);
+			}
+			else if (base.scene.dir_lights_count) pt.directional_sample(ev, e, r[44], q, vinfo, &tr);
+			else ran = false;
+			o[0] = tr.want ? 1.0f : 0.0f; put3(1, tr.w_d); put3(4, tr.w_g);
+			if (tr.want) { put3(7, tr.org); put3(10, tr.dir); }
+			if (ran) { for (int k = 0; k < 4; ++k) { put3(13 + 3 * k, tr.f_s[k]); o[25 + k] = tr.p_s[k]; } o[29] = tr.G; o[30] = tr.mis_w; }
+		}
+		else if (op == 8 && n_tris)
+		{
+			EyeVertex ev;
+			ev.geom.normal_s = ev.geom.normal_g = get3(1); ev.in = get3(8); ev.geom.texture_coords = V4(0.0f, 0.0f, 0.0f, 0.0f);
+			// map_geom reads the emission from the mesh's material and the texture at the point; the probe passes the emission itself
+			Material em_mat = mesh.materials[mesh.material_indices[tri]];
+			em_mat.emissive = V4(r[4], r[5], r[6], r[7]); em_mat.emissive_map.texture = 0xFFFFFFFFu;
+			std::vector<Material> one_mat(mesh.materials, mesh.materials + mesh.num_materials);
+			one_mat[mesh.material_indices[tri]] = em_mat;
+			pt.scene.mesh.materials = one_mat.data(); pt.scene.mesh_light.mesh = &pt.scene.mesh; pt.scene.mesh_vpls.mesh = &pt.scene.mesh;
+			float lpdf = 0.0f, mis_w = 0.0f;
+			const V3 e = pt.emissive_weight(ev, tri, r[11], r[12], get3(13), &lpdf, &mis_w);
+			o[0] = lpdf; o[1] = mis_w; put3(2, e);
+		}
+	}
+}
 float orc_det_log2(float x) { return det_log2(x); }
 float orc_det_exp2(float x) { return det_exp2(x); }
 // glossy reflectance table cells [begin, end) : src/bsdf.cu:36-102
