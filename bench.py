@@ -11,8 +11,13 @@ variance update.  The passes of the timed region are kept in flight together (fp
 by one -- DESIGN.md 6b; --api render issues one fpt_pt_render call per pass and lets the library batch them).  Scene, BVH, textures and tables are
 resident in HBM before the timed region.  N>1 shards the frame by interleaved scanlines (tile = one row; no data-path collective) and gathers
 COMPOSITED_C to rank 0 over RCCL once, inside the timed region; `value` is then the STRONG-scaling rate (a step = one pass of the frame whatever N), with
-`value_weak` (a step = N passes) measured beside it.  The default single-GPU run adds `extra.testball_room`, the same measurement on a harder scene.
+`value_weak` (a step = N passes) measured beside it under --full.
 Prints ONE JSON line on rank 0.
+
+A plain run does what its headline figure needs and nothing else: set-up, warm-up, the timed steps, --dump-outputs, the line (`value`, `ms_per_step`,
+the configuration and the per-launch timings of the timed steps).  --full adds everything else the benchmark measures: the instrumented re-run behind
+`mray_per_s` and the `roofline` object, the measured copy bandwidth, the other scaling mode and the speed-up over a committed single-GPU line (N>1), the
+single-GPU line's `extra` scenes, jobs and renderers (unless --no-extra) and the CPU baseline (unless --no-cpu-baseline).
 """
 import argparse
 import json
@@ -44,7 +49,11 @@ def main():
     ap.add_argument("--batch", type=int, default=int(os.environ.get("FPT_BENCH_BATCH", "0")),
                     help="passes in flight per launch chain (fpt_pt_render_batch); 1 = the reference's one pass per render(); "
                          "0 = 64 per GPU share (64*N under N-way sharding), capped by --steps; memory: ~0.7 KB per path in flight (fpt_bytes_per_path_in_flight)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need (off by default): the instrumented re-run behind mray_per_s and the roofline "
+                         "object, the measured copy bandwidth, the other scaling mode and speedup_vs_n1 (N>1), the single-GPU line's extra scenes, jobs and "
+                         "renderers, and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--renderer", choices=("pt", "bpt", "psfpt"), default="pt",
                     help="pt = the headline path (default); bpt / psfpt = the widened rows (SURVEY 8f-1, 8f-3) measured the same way, "
                          "one pass per step (--batch passes in flight, default 32)")
@@ -64,7 +73,7 @@ def main():
     ap.add_argument("--api", choices=("batch", "render"), default="batch",
                     help="how the passes in flight are requested: batch = fpt_pt_render_batch(first, n) (default); render = the reference's calling convention, one "
                          "fpt_pt_render(instance) call per pass, with the library deferring and batching them (fpt_pt_set_deferred) -- same kernels, same frame")
-    ap.add_argument("--no-extra", action="store_true", help="skip the second, harder scene (extra.testball_room) of the default single-GPU run")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the extra scenes, jobs and renderers (extra.*) of the single-GPU line")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the frame buffer the timed path left after its last step to DIR/framebuffer.npy: its 8 float32 RGBA "
                          "channels at a fixed, seeded sample of 2^18 pixels (32 MB); one GPU only")
@@ -114,9 +123,9 @@ def main():
     s, workload = load_workload(scene, args, (W, H))
     env = dict(torch=torch, fa=fa, dist=dist, world=world, rank=rank, local_rank=local_rank, gather_framebuffer=gather_framebuffer, comm_init=comm_init,
                gather_framebuffer_capi=gather_framebuffer_capi)
-    out = bench_scene(env, args, s, workload, W, H, full=True)
+    out = bench_scene(env, args, s, workload, W, H, headline=True)
     if rank == 0:
-        if world == 1 and not args.no_extra and args.workload == "bathroom2" and args.config == "c3" and args.detail == 1.0:
+        if args.full and world == 1 and not args.no_extra and args.workload == "bathroom2" and args.config == "c3" and args.detail == 1.0:
             # the same measurement on the two other stand-ins, so that the record shows the scene sensitivity of the headline number: rounds 1-3's headline scene
             # (easy: an open box, 3.3 node steps per ray) and the testball room (4.4 M triangles, ~15 node steps per ray)
             import copy
@@ -124,7 +133,7 @@ def main():
             for key, wl in (("standin_r1_r3", "standin"), ("testball_room", "testball-room")):
                 a2 = copy.copy(args); a2.workload = wl
                 s2, w2 = load_workload(scene, a2, (W, H))
-                o2 = bench_scene(env, a2, s2, w2, W, H, full=False)
+                o2 = bench_scene(env, a2, s2, w2, W, H, headline=False)
                 out["extra"][key] = {"value": o2["value"], "unit": o2["unit"], "ms_per_step": o2["ms_per_step"], "mray_per_s": o2["mray_per_s"],
                                      "nodes_per_ray": o2["roofline"]["nodes_per_ray"], "tris_per_ray": o2["roofline"]["tris_per_ray"],
                                      "roofline_frac": o2["roofline"]["frac"], "kernel_ms_per_step": o2["kernel_ms_per_step"],
@@ -137,7 +146,7 @@ def main():
                 for k, v in over.items():
                     setattr(a2, k, v)
                 o2 = out if (a2.steps, a2.warmup, a2.batch if a2.batch else 64) == (args.steps, args.warmup, args.batch if args.batch else 64) else \
-                    bench_scene(env, a2, s, workload, W, H, full=False)
+                    bench_scene(env, a2, s, workload, W, H, headline=False)
                 out["extra"][key] = {"value": o2["value"], "unit": o2["unit"], "steps": o2["steps"], "warmup": o2["warmup"], "ms_per_step": o2["ms_per_step"],
                                      "passes_in_flight": o2["config"]["passes_in_flight"], "api": o2["config"]["api"], "mray_per_s": o2["mray_per_s"],
                                      "kernel_ms_per_step": o2["kernel_ms_per_step"], "roofline_frac": o2["roofline"]["frac"],
@@ -154,7 +163,7 @@ def main():
                                       "metric": o3["metric"], "passes_in_flight": o3["config"]["passes_in_flight"], "kernel_ms_per_step": o3["kernel_ms_per_step"],
                                       "roofline_frac": o3["roofline"]["frac"], "nodes_per_ray": o3["roofline"]["nodes_per_ray"], "tris_per_ray": o3["roofline"]["tris_per_ray"],
                                       "workload": o3["config"]["workload"]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(s, W, H)
         print(json.dumps(out))
     if dist is not None:
@@ -162,8 +171,8 @@ def main():
         dist.destroy_process_group()
 
 
-def bench_scene(env, args, s, workload, W, H, full):
-    """the timed measurement of one scene: returns the JSON object on rank 0 (None elsewhere)"""
+def bench_scene(env, args, s, workload, W, H, headline):
+    """the timed measurement of one scene: returns the JSON object on rank 0 (None elsewhere); headline = the line's own scene, not one of its extras"""
     torch, fa, dist, world, rank, local_rank = env["torch"], env["fa"], env["dist"], env["world"], env["rank"], env["local_rank"]
     K, Wu = args.steps, args.warmup
     tile = (W, 1)
@@ -274,31 +283,34 @@ def bench_scene(env, args, s, workload, W, H, full):
     timings = r.collect_timings()
     union = r.union_timings()
     r.set_profiling(0)
-    if full and args.dump_outputs:          # before the instrumented re-run below renders the same passes again
+    if headline and args.dump_outputs:          # before the instrumented re-run below renders the same passes again
         dump_outputs(r, args.dump_outputs)
     # the other scaling mode, measured the same way in a second timed region (N > 1 only: at N = 1 the two coincide)
     other = None
-    if world > 1 and full:
+    if world > 1 and headline and args.full:
         pps_o = 1 if pps_primary > 1 else world
         P_o = batch_for(K * pps_o)
         run(Wp + Kp, Wu * pps_o, P_o)
         e_o = timed(Wp + Kp + Wu * pps_o, K * pps_o, P_o)
         other = {"passes_per_step": pps_o, "passes_in_flight": P_o, "value": float(W) * H * K * pps_o / e_o / 1e6, "ms_per_step": e_o / K * 1e3}
 
-    # instrumented re-run of the same K passes: exact rays / nodes popped / triangles tested of the timed launches
-    r.set_counting(True)
-    run(Wp, Kp, P)
-    r.synchronize()
-    closest, shadow = r.trace_counters()
-    r.set_counting(False)
-    counts = torch.tensor([closest.rays, closest.nodes_visited, closest.tris_tested, shadow.rays, shadow.nodes_visited, shadow.tris_tested],
-                          dtype=torch.float64, device=cdev)
     tms = torch.tensor([timings["primary_trace"][0] + timings["path_trace"][0], timings["shadow_trace"][0], timings["shade"][0], union["all_trace"], union["shade"]],
                        dtype=torch.float64, device=cdev)
     if dist is not None:
-        dist.all_reduce(counts, op=dist.ReduceOp.SUM)
         dist.all_reduce(tms, op=dist.ReduceOp.MAX)
-    counts = counts.cpu().numpy(); tms = tms.cpu().numpy()
+    tms = tms.cpu().numpy()
+    if args.full:
+        # instrumented re-run of the same K passes: exact rays / nodes popped / triangles tested of the timed launches
+        r.set_counting(True)
+        run(Wp, Kp, P)
+        r.synchronize()
+        closest, shadow = r.trace_counters()
+        r.set_counting(False)
+        counts = torch.tensor([closest.rays, closest.nodes_visited, closest.tris_tested, shadow.rays, shadow.nodes_visited, shadow.tris_tested],
+                              dtype=torch.float64, device=cdev)
+        if dist is not None:
+            dist.all_reduce(counts, op=dist.ReduceOp.SUM)
+        counts = counts.cpu().numpy()
 
     out = None
     if rank == 0:
@@ -306,24 +318,7 @@ def bench_scene(env, args, s, workload, W, H, full):
         samples = float(W) * H * Kp
         if world == 1 and emulate > 1:
             samples = float(len(pixels)) * K
-        rays_total = counts[0] + counts[3]
-        # roofline of the dominant kernel = the wide-BVH traversal kernel (trace_kernel: closest-hit launch for the primary rays, then
-        # one MIXED launch per bounce = closest-hit rays of bounce b+1 + any-hit shadow rays of bounce b), priced against HBM as SURVEY 8(d) asks:
-        # algorithmic bytes = closest rays*(32+16) + shadow rays*32 + node steps*80 + triangle records tested*48,
-        # over the summed launch time of every traversal launch in the timed region (HIP events on the library's stream)
-        n_trace_launches = timings["primary_trace"][1] + timings["path_trace"][1] + timings["shadow_trace"][1]
-        trace_ms = float(timings["primary_trace"][0] + timings["path_trace"][0] + timings["shadow_trace"][0])      # rank 0's own launches
-        all_rays = counts[0] + counts[3]
-        rank0_share = ((closest.rays + shadow.rays) / all_rays) if all_rays else 1.0
-        alg_bytes = (counts[0] * RAY_BYTES + counts[3] * 32 + (counts[1] + counts[4]) * NODE_BYTES + (counts[2] + counts[5]) * TRI_BYTES) * rank0_share
-        achieved = alg_bytes / (trace_ms * 1e-3) / 1e9 if trace_ms > 0 else 0.0
-        # the same counts priced with SURVEY 8(d)'s record sizes (what the kernel would move with uncompressed records)
-        survey_bytes = (counts[0] * RAY_BYTES + counts[3] * 32 + (counts[1] + counts[4]) * SURVEY_NODE_BYTES + (counts[2] + counts[5]) * SURVEY_TRI_BYTES) * rank0_share
-        n_closest_launches = n_trace_launches; closest_ms = trace_ms
-        avg_launch_ms = closest_ms / max(1, n_closest_launches)
         config_key = pmc_config_key(args.workload, s.num_triangles, P, world, (W, H), n_lanes)
-        pmc, pmc_file, pmc_note = find_pmc_summary(config_key, fa)
-        traffic = pmc.get("hbm_bytes_per_launch") if pmc else None
         bvh = r.bvh_stats()
         value = samples / elapsed / 1e6
         out = {
@@ -346,56 +341,78 @@ def bench_scene(env, args, s, workload, W, H, full):
                                      if pps > 1 else "strong scaling: a step = one pass of the frame")) if world > 1 else "none",
                        "gather": ("fpt_gather_framebuffer (RCCL grouped send/recv inside libfermat_pt_hip.so)" if capi else "torch.distributed gather (%s)" % dist.get_backend()) if world > 1 else "none",
                        "rccl_ranks": rccl_ranks},
-            "mray_per_s": rays_total / elapsed / 1e6,
-            "rays_per_step": rays_total / K,
             # sums of launch durations (HIP events around every launch); with render lanes > 1 launches of different lanes overlap, and the
             # *_busy figures are the time at least one such launch was running
             "kernel_ms_per_step": {"trace_primary+mixed": float(tms[0]) / K, "trace_shadow_only": float(tms[1]) / K, "shade": float(tms[2]) / K,
                                    "trace_busy": float(tms[3]) / K, "shade_busy": float(tms[4]) / K, "render_lanes": n_lanes},
-            # three prices of the same launches, side by side: the algorithmic bytes of THIS layout (80-B node, 48-B
-            # record) -> `achieved`/`frac` as the contract defines them; the same counts priced with SURVEY 8(d)'s 64-B records; and the
-            # bytes that really crossed the HBM interface according to the PMC counters of a rocprofv3 collection over this same
-            # configuration (`traffic`; null when profiles/ holds none for this scene + passes in flight).  A frac >= 1 means the tree is
-            # served from L2 / Infinity Cache: the roof that binds then is the VALU (`valu`, same PMC collection).
-            "roofline": {"bound": "hbm", "kernel": "trace_kernel (8-wide compressed BVH traversal: closest-hit + any-hit/resolve)", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": ("profiles/%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over this same command line "
-                                            "(same scene, %d passes in flight, same kernel sources: %s), bytes per traversal launch of the timed region" % (pmc_file, P, pmc.get("source_hash"))) if pmc else pmc_note,
-                         # the chip-level rate: the same bytes over the time at least one traversal launch was running (= achieved when lanes == 1)
-                         "achieved_chip": (alg_bytes / (union["all_trace"] * 1e-3) / 1e9) if union["all_trace"] > 0 else None,
-                         "frac_chip": (alg_bytes / (union["all_trace"] * 1e-3) / 1e9 / HBM_PEAK_GBS) if union["all_trace"] > 0 else None,
-                         # counter bytes of the timed region's launches over THIS run's live durations of the same launches; beside it the same bytes over the durations
-                         # rocprofv3 itself timed them at (bytes and time of the same launches of one run: VERDICT r4 task 2a)
-                         "counter_gbs": (traffic / (avg_launch_ms * 1e-3) / 1e9) if (traffic and avg_launch_ms > 0) else None,
-                         "counter_frac": (traffic / (avg_launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (traffic and avg_launch_ms > 0) else None,
-                         "counter_gbs_profiled": pmc.get("counter_gbs_profiled") if pmc else None,
-                         "survey_model_gbs": survey_bytes / (trace_ms * 1e-3) / 1e9 if trace_ms > 0 else 0.0,
-                         "survey_model_frac": survey_bytes / (trace_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if trace_ms > 0 else 0.0,
-                         "launches": int(n_closest_launches), "avg_launch_ms": avg_launch_ms,
-                         "alg_bytes_per_launch": alg_bytes / max(1, n_closest_launches),
-                         "record_bytes": {"node": NODE_BYTES, "triangle": TRI_BYTES, "ray+hit": RAY_BYTES},
-                         "bvh_bytes": int(bvh["nodes"]) * NODE_BYTES + int(bvh["records"]) * TRI_BYTES,
-                         "valu": pmc.get("valu") if pmc else None,
-                         "nodes_per_ray": (counts[1] + counts[4]) / max(1.0, all_rays), "tris_per_ray": (counts[2] + counts[5]) / max(1.0, all_rays)},
         }
-        binding_roof(out["roofline"], pmc_file)
-        if other is not None:
-            # both scaling modes in the one line: `value` is the one --scaling names, the other one sits beside it
-            out["value_weak" if pps == 1 else "value_strong"] = other["value"]
-            out["other_scaling"] = other
-        if world > 1:
-            # north_star's tile-parallel speed-up = this run's strong-scaling rate over the committed single-GPU line of the same job
-            strong = value if pps == 1 else (other["value"] if other else None)
-            ref, ref_file = find_single_gpu_line(args, (W, H), K, s.num_triangles)
-            # CROSS-RUN: the denominator is a committed single-GPU line of an earlier run, not a measurement of this session; the driver computes its own
-            # efficiency from its own per-N runs
-            out["speedup_vs_n1"] = (strong / ref["value"]) if (ref and strong) else None
-            out["speedup_vs_n1_source"] = ("cross-run: profiles/%s (value %.1f Msample/s, same workload, resolution and --steps on one GPU, measured in an earlier session)" % (ref_file, ref["value"])) if ref else \
-                "no single-GPU line of this job (workload, resolution, --steps %d) under profiles/" % K
-        if full:
-            out["roofline"]["measured_copy_gbs"] = measured_copy_bandwidth(torch, dev)
+        if args.full:
+            rays_total = counts[0] + counts[3]
+            out["mray_per_s"] = rays_total / elapsed / 1e6
+            out["rays_per_step"] = rays_total / K
+            out["roofline"] = trace_roofline(timings, union, counts, closest.rays + shadow.rays, bvh, config_key, P, fa)
+            if other is not None:
+                # both scaling modes in the one line: `value` is the one --scaling names, the other one sits beside it
+                out["value_weak" if pps == 1 else "value_strong"] = other["value"]
+                out["other_scaling"] = other
+            if world > 1:
+                # north_star's tile-parallel speed-up = this run's strong-scaling rate over the committed single-GPU line of the same job
+                strong = value if pps == 1 else (other["value"] if other else None)
+                ref, ref_file = find_single_gpu_line(args, (W, H), K, s.num_triangles)
+                # CROSS-RUN: the denominator is a committed single-GPU line of an earlier run, not a measurement of this session; the driver computes its own
+                # efficiency from its own per-N runs
+                out["speedup_vs_n1"] = (strong / ref["value"]) if (ref and strong) else None
+                out["speedup_vs_n1_source"] = ("cross-run: profiles/%s (value %.1f Msample/s, same workload, resolution and --steps on one GPU, measured in an earlier session)" % (ref_file, ref["value"])) if ref else \
+                    "no single-GPU line of this job (workload, resolution, --steps %d) under profiles/" % K
+            if headline:
+                out["roofline"]["measured_copy_gbs"] = measured_copy_bandwidth(torch, dev)
     r.close()
     return out
+
+
+def trace_roofline(timings, union, counts, rank0_rays, bvh, config_key, P, fa):
+    """--full: the roofline object of the dominant kernel = the wide-BVH traversal kernel (trace_kernel: closest-hit launch for the primary rays, then
+    one MIXED launch per bounce = closest-hit rays of bounce b+1 + any-hit shadow rays of bounce b), priced against HBM as SURVEY 8(d) asks:
+    algorithmic bytes = closest rays*(32+16) + shadow rays*32 + node steps*80 + triangle records tested*48,
+    over the summed launch time of every traversal launch in the timed region (HIP events on the library's stream).
+    Three prices of the same launches, side by side: the algorithmic bytes of THIS layout (80-B node, 48-B
+    record) -> `achieved`/`frac` as the contract defines them; the same counts priced with SURVEY 8(d)'s 64-B records; and the
+    bytes that really crossed the HBM interface according to the PMC counters of a rocprofv3 collection over this same
+    configuration (`traffic`; null when profiles/ holds none for this scene + passes in flight).  A frac >= 1 means the tree is
+    served from L2 / Infinity Cache: the roof that binds then is the VALU (`valu`, same PMC collection)."""
+    n_trace_launches = timings["primary_trace"][1] + timings["path_trace"][1] + timings["shadow_trace"][1]
+    trace_ms = float(timings["primary_trace"][0] + timings["path_trace"][0] + timings["shadow_trace"][0])      # rank 0's own launches
+    all_rays = counts[0] + counts[3]
+    rank0_share = (rank0_rays / all_rays) if all_rays else 1.0
+    alg_bytes = (counts[0] * RAY_BYTES + counts[3] * 32 + (counts[1] + counts[4]) * NODE_BYTES + (counts[2] + counts[5]) * TRI_BYTES) * rank0_share
+    achieved = alg_bytes / (trace_ms * 1e-3) / 1e9 if trace_ms > 0 else 0.0
+    # the same counts priced with SURVEY 8(d)'s record sizes (what the kernel would move with uncompressed records)
+    survey_bytes = (counts[0] * RAY_BYTES + counts[3] * 32 + (counts[1] + counts[4]) * SURVEY_NODE_BYTES + (counts[2] + counts[5]) * SURVEY_TRI_BYTES) * rank0_share
+    avg_launch_ms = trace_ms / max(1, n_trace_launches)
+    pmc, pmc_file, pmc_note = find_pmc_summary(config_key, fa)
+    traffic = pmc.get("hbm_bytes_per_launch") if pmc else None
+    rf = {"bound": "hbm", "kernel": "trace_kernel (8-wide compressed BVH traversal: closest-hit + any-hit/resolve)", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+          "traffic_source": ("profiles/%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over this same command line "
+                             "(same scene, %d passes in flight, same kernel sources: %s), bytes per traversal launch of the timed region" % (pmc_file, P, pmc.get("source_hash"))) if pmc else pmc_note,
+          # the chip-level rate: the same bytes over the time at least one traversal launch was running (= achieved when lanes == 1)
+          "achieved_chip": (alg_bytes / (union["all_trace"] * 1e-3) / 1e9) if union["all_trace"] > 0 else None,
+          "frac_chip": (alg_bytes / (union["all_trace"] * 1e-3) / 1e9 / HBM_PEAK_GBS) if union["all_trace"] > 0 else None,
+          # counter bytes of the timed region's launches over THIS run's live durations of the same launches; beside it the same bytes over the durations
+          # rocprofv3 itself timed them at (bytes and time of the same launches of one run: VERDICT r4 task 2a)
+          "counter_gbs": (traffic / (avg_launch_ms * 1e-3) / 1e9) if (traffic and avg_launch_ms > 0) else None,
+          "counter_frac": (traffic / (avg_launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (traffic and avg_launch_ms > 0) else None,
+          "counter_gbs_profiled": pmc.get("counter_gbs_profiled") if pmc else None,
+          "survey_model_gbs": survey_bytes / (trace_ms * 1e-3) / 1e9 if trace_ms > 0 else 0.0,
+          "survey_model_frac": survey_bytes / (trace_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if trace_ms > 0 else 0.0,
+          "launches": int(n_trace_launches), "avg_launch_ms": avg_launch_ms,
+          "alg_bytes_per_launch": alg_bytes / max(1, n_trace_launches),
+          "record_bytes": {"node": NODE_BYTES, "triangle": TRI_BYTES, "ray+hit": RAY_BYTES},
+          "bvh_bytes": int(bvh["nodes"]) * NODE_BYTES + int(bvh["records"]) * TRI_BYTES,
+          "valu": pmc.get("valu") if pmc else None,
+          "nodes_per_ray": (counts[1] + counts[4]) / max(1.0, all_rays), "tris_per_ray": (counts[2] + counts[5]) / max(1.0, all_rays)}
+    binding_roof(rf, pmc_file)
+    return rf
 
 
 def load_workload(scene, args, res):
@@ -432,7 +449,7 @@ def self_launch(n):
 
 
 def main_widened(args, kind=None, quick_steps=None):
-    """(kind / quick_steps: the single-GPU default line's `extra.bpt` / `extra.psfpt` -- a short run of the same measurement, returned instead of printed)
+    """(kind / quick_steps: the single-GPU --full line's `extra.bpt` / `extra.psfpt` -- a short run of the same measurement, returned instead of printed)
     BPT (`-bpt`, BASELINE config 5's renderer) and PSFPT on the same frame, scene and JSON contract as the PT line.  A step is one
     pass.  BPT shards light and eye sub-paths by scanline and sums the light-tracing splats with one integer all-reduce per pass
     (fermat_amd.distributed.allreduce_splats); PSFPT's cache is shared by all pixels: its ranks exchange the cells they touched after every pass."""
@@ -559,30 +576,22 @@ def main_widened(args, kind=None, quick_steps=None):
     r.set_profiling(0)
     if not as_extra and args.dump_outputs:
         dump_outputs(r, args.dump_outputs)
-    # instrumented re-run of the same passes from the same starting state (PSFPT's cache and frame carry over between passes)
-    r.close()
-    r, sp = make()
-    run(r, sp, 0, Wu)
-    r.set_counting(True)
-    run(r, sp, Wu, K)
-    r.synchronize()
-    closest, shadow = r.trace_counters()
-    r.set_counting(False)
-    counts = torch.tensor([closest.rays, closest.nodes_visited, closest.tris_tested, shadow.rays, shadow.nodes_visited, shadow.tris_tested], dtype=torch.float64, device=cdev)
-    if dist is not None:
-        dist.all_reduce(counts, op=dist.ReduceOp.SUM)
-    counts = counts.cpu().numpy()
+    if args.full:
+        # instrumented re-run of the same passes from the same starting state (PSFPT's cache and frame carry over between passes)
+        r.close()
+        r, sp = make()
+        run(r, sp, 0, Wu)
+        r.set_counting(True)
+        run(r, sp, Wu, K)
+        r.synchronize()
+        closest, shadow = r.trace_counters()
+        r.set_counting(False)
+        counts = torch.tensor([closest.rays, closest.nodes_visited, closest.tris_tested, shadow.rays, shadow.nodes_visited, shadow.tris_tested], dtype=torch.float64, device=cdev)
+        if dist is not None:
+            dist.all_reduce(counts, op=dist.ReduceOp.SUM)
+        counts = counts.cpu().numpy()
     if rank == 0:
-        trace_ms = float(timings["primary_trace"][0] + timings["shadow_trace"][0])
-        n_launches = int(timings["primary_trace"][1] + timings["shadow_trace"][1])
-        all_rays = counts[0] + counts[3]
-        share = ((closest.rays + shadow.rays) / all_rays) if all_rays else 1.0
-        alg_bytes = (counts[0] * RAY_BYTES + counts[3] * RAY_BYTES + (counts[1] + counts[4]) * NODE_BYTES + (counts[2] + counts[5]) * TRI_BYTES) * share
-        achieved = alg_bytes / (trace_ms * 1e-3) / 1e9 if trace_ms > 0 else 0.0
-        avg_launch_ms = trace_ms / max(1, n_launches)
         config_key = pmc_config_key("%s/%s%s" % (args.workload, kind, "-sc%d" % args.sc if kind == "bpt" else ""), s.num_triangles, P, world)
-        pmc, pmc_file, pmc_note = find_pmc_summary(config_key, fa)
-        traffic = pmc.get("hbm_bytes_per_launch") if pmc else None
         name = {"bpt": "BPT (-bpt -sc %d: %s, light tracing)" % (args.sc, "one connection per eye vertex, the reference's default" if args.sc else "all connections"),
                 "psfpt": "PSFPT (path-space filtering)"}[kind]
         out = {
@@ -594,27 +603,39 @@ def main_widened(args, kind=None, quick_steps=None):
                        "resolution": [W, H], "max_path_length": L, "triangles": int(s.num_triangles), "passes_in_flight": P, "config_key": config_key,
                        "sharding": ("scanlines round-robin over ranks + " + ("one integer all-reduce of the light-tracing splat sums per batch" if kind == "bpt" else
                                                                           "the touched cache cells exchanged and merged by key after every pass")) if world > 1 else "none"},
-            "mray_per_s": all_rays / elapsed / 1e6, "rays_per_step": all_rays / K,
             "kernel_ms_per_step": {("trace_closest+mixed" if kind == "bpt" else "trace_closest"): float(timings["primary_trace"][0]) / K,      # BPT: the eye path's connections ride in the next bounce's closest-hit launch
                                    "trace_any_hit": float(timings["shadow_trace"][0]) / K,
                                    "vertex_kernels": float(timings["shade"][0]) / K},
-            "roofline": {"bound": "hbm", "kernel": "trace_kernel (8-wide compressed BVH traversal: closest-hit and any-hit launches; any-hit results are written, 16 B per ray)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": ("profiles/%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over this same command line (same kernel sources: %s), bytes per "
-                                            "traversal launch of the timed region" % (pmc_file, pmc.get("source_hash"))) if pmc else pmc_note,
-                         "counter_gbs": (traffic / (avg_launch_ms * 1e-3) / 1e9) if (traffic and avg_launch_ms > 0) else None,
-                         "counter_frac": (traffic / (avg_launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (traffic and avg_launch_ms > 0) else None,
-                         "counter_gbs_profiled": pmc.get("counter_gbs_profiled") if pmc else None,
-                         "valu": pmc.get("valu") if pmc else None,
-                         "launches": n_launches, "avg_launch_ms": avg_launch_ms, "alg_bytes_per_launch": alg_bytes / max(1, n_launches),
-                         "record_bytes": {"node": NODE_BYTES, "triangle": TRI_BYTES, "ray+hit": RAY_BYTES},
-                         "nodes_per_ray": (counts[1] + counts[4]) / max(1.0, all_rays), "tris_per_ray": (counts[2] + counts[5]) / max(1.0, all_rays)},
         }
-        binding_roof(out["roofline"], pmc_file)
+        if args.full:
+            trace_ms = float(timings["primary_trace"][0] + timings["shadow_trace"][0])
+            n_launches = int(timings["primary_trace"][1] + timings["shadow_trace"][1])
+            all_rays = counts[0] + counts[3]
+            share = ((closest.rays + shadow.rays) / all_rays) if all_rays else 1.0
+            alg_bytes = (counts[0] * RAY_BYTES + counts[3] * RAY_BYTES + (counts[1] + counts[4]) * NODE_BYTES + (counts[2] + counts[5]) * TRI_BYTES) * share
+            achieved = alg_bytes / (trace_ms * 1e-3) / 1e9 if trace_ms > 0 else 0.0
+            avg_launch_ms = trace_ms / max(1, n_launches)
+            pmc, pmc_file, pmc_note = find_pmc_summary(config_key, fa)
+            traffic = pmc.get("hbm_bytes_per_launch") if pmc else None
+            out["mray_per_s"] = all_rays / elapsed / 1e6
+            out["rays_per_step"] = all_rays / K
+            out["roofline"] = {
+                "bound": "hbm", "kernel": "trace_kernel (8-wide compressed BVH traversal: closest-hit and any-hit launches; any-hit results are written, 16 B per ray)",
+                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                "traffic_source": ("profiles/%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over this same command line (same kernel sources: %s), bytes per "
+                                   "traversal launch of the timed region" % (pmc_file, pmc.get("source_hash"))) if pmc else pmc_note,
+                "counter_gbs": (traffic / (avg_launch_ms * 1e-3) / 1e9) if (traffic and avg_launch_ms > 0) else None,
+                "counter_frac": (traffic / (avg_launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (traffic and avg_launch_ms > 0) else None,
+                "counter_gbs_profiled": pmc.get("counter_gbs_profiled") if pmc else None,
+                "valu": pmc.get("valu") if pmc else None,
+                "launches": n_launches, "avg_launch_ms": avg_launch_ms, "alg_bytes_per_launch": alg_bytes / max(1, n_launches),
+                "record_bytes": {"node": NODE_BYTES, "triangle": TRI_BYTES, "ray+hit": RAY_BYTES},
+                "nodes_per_ray": (counts[1] + counts[4]) / max(1.0, all_rays), "tris_per_ray": (counts[2] + counts[5]) / max(1.0, all_rays)}
+            binding_roof(out["roofline"], pmc_file)
         if as_extra:
             r.close()
             return out
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_widened(kind, s, W, H, args.sc)
         print(json.dumps(out))
     r.close()

@@ -13,7 +13,7 @@ for rep in range(a.repeat):
         env = dict(os.environ)
         if v != "base":
             env["FPT_LIB_PATH"] = os.path.join(ROOT, "fermat_amd", "variants", "libfermat_%s.so" % v)
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-extra", "--no-cpu-baseline"] + a.args.split(), env=env, capture_output=True, text=True)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-extra", "--no-cpu-baseline"] + a.args.split(), env=env, capture_output=True, text=True)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")]
         if not line:
             print("%-12s FAILED rc %d: %s" % (v, p.returncode, p.stderr[-300:])); continue

@@ -3,7 +3,7 @@
 # rocprofv3 --pmc pass per counter set
 R=$PWD; export TMPDIR=/tmp
 D=$R/gpurun_out/pmcs; rm -rf $D; mkdir -p $D
-B="python $R/bench.py --steps 64 --warmup 0 --no-cpu-baseline"
+B="python $R/bench.py --full --steps 64 --warmup 0 --no-cpu-baseline"
 cd /tmp
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU SQ_BUSY_CYCLES -d $D/sq -o p -- $B > $D/sq.log 2>&1
 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum -d $D/tcc -o p -- $B > $D/tcc.log 2>&1

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/run_scale.sh [out_dir]   -- the 1 / 2 / 4 / 8-GPU curve in one command, for the day an 8-GPU MI355X node is at hand (VERDICT r4 task 9; north_star: Msample/s
-# at 1, 2, 4 and 8 GPUs, >= 6x tile-parallel speed-up at 8).  Run from the repo root on the node.  Per N it runs bench.py exactly as the driver does -- one rank per
+# at 1, 2, 4 and 8 GPUs, >= 6x tile-parallel speed-up at 8).  Run from the repo root on the node.  Per N it runs bench.py --full, launched as the driver launches it -- one rank per
 # GPU under torch.distributed.run, RCCL over xGMI -- for
 #   (a) the driver's job           : --steps 20 --warmup 5          (strong scaling: 20 passes of the 1600x900 frame whatever N)
 #   (b) configs[2]'s own job       : --steps 256 --warmup 64        (256 spp)
@@ -14,8 +14,8 @@ PORT=29511
 run() {          # job-name N args...
 	local job=$1 n=$2; shift 2
 	local f=$OUT/scale_${job}_n${n}.json
-	if [ $n -eq 1 ]; then python bench.py --gpus 1 --no-extra --no-cpu-baseline "$@" > $f 2> ${f%.json}.err
-	else python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus $n --no-extra --no-cpu-baseline "$@" > $f 2> ${f%.json}.err; fi
+	if [ $n -eq 1 ]; then python bench.py --full --gpus 1 --no-extra --no-cpu-baseline "$@" > $f 2> ${f%.json}.err
+	else python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $PORT bench.py --full --gpus $n --no-extra --no-cpu-baseline "$@" > $f 2> ${f%.json}.err; fi
 	PORT=$((PORT + 1))
 	python - "$f" "$n" << 'PY'
 import json, sys
