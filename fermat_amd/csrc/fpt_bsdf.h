@@ -550,7 +550,9 @@ FPT_HD uint32_t surface_sample(const SurfaceModel& m, const ShadingFrame& fr, co
 	out = L;
 	f3 w[4];
 	inner_lobe_weights(m, fr, in, out, vt.albedo_v, w);
-	g = g * ((comp & COMP_GLOSSY_R) ? w[LOBE_GLOSSY_R] : (comp & COMP_GLOSSY_T) ? w[LOBE_GLOSSY_T] : (comp & COMP_DIFF_R) ? w[LOBE_DIFF_R] : w[LOBE_DIFF_T]);
+	// the lobe's weight picked by value: a pick among the array's elements became a dynamically indexed stack array (scratch) in shade_kernel
+	const f3 w_gr = w[LOBE_GLOSSY_R], w_gt = w[LOBE_GLOSSY_T], w_dr = w[LOBE_DIFF_R], w_dt = w[LOBE_DIFF_T];
+	g = g * ((comp & COMP_GLOSSY_R) ? w_gr : (comp & COMP_GLOSSY_T) ? w_gt : (comp & COMP_DIFF_R) ? w_dr : w_dt);
 	g = g / p_comp;
 	out_p = p * p_comp;
 	out_p_proj = p_proj * p_comp;

@@ -247,8 +247,13 @@ __device__ __forceinline__ uint32_t psf_insert(const PsfDev& psf, unsigned long 
 	}
 	return 0x1FFFFFFFu;       // table full: the vertex stays uncached
 }
+// waves per SIMD the shading kernels are compiled for: 5 (96 VGPRs) for the path tracer's; path-space filtering's holds the cache look-up's state as well and
+// stays at 4 (128 VGPRs; at 5 it spills)
 #ifndef FPT_SHADE_MIN_WAVES
-#define FPT_SHADE_MIN_WAVES 4
+#define FPT_SHADE_MIN_WAVES 5
+#endif
+#ifndef FPT_SHADE_MIN_WAVES_PSF
+#define FPT_SHADE_MIN_WAVES_PSF 4
 #endif
 // FPT_SHADE_SKIP: a bit mask that compiles sections of shade_kernel OUT -- 1 directional lights, 2 mesh-light NEE, 4 emissive hit, 8 scattering, 16 the albedo /
 // gbuffer writes of bounce 0, 32 the six QMC samples.  Never set in the product build: tools/shade_sections.py counts the instructions of each section by difference
@@ -258,10 +263,14 @@ __device__ __forceinline__ uint32_t psf_insert(const PsfDev& psf, unsigned long 
 // One kernel per vertex: the two-way fission of this kernel (vertex set-up + NEE + emissive | vertex set-up + scatter) was measured and rejected
 // (shading 0.459 vs 0.370 ms per step: the second set-up costs more than the smaller half's occupancy returns).
 template <bool PSF>
-__global__ __launch_bounds__(SHADE_BLOCK, FPT_SHADE_MIN_WAVES)
+__global__ __launch_bounds__(SHADE_BLOCK, PSF ? FPT_SHADE_MIN_WAVES_PSF : FPT_SHADE_MIN_WAVES)
 void shade_kernel(const ShadeParams P)
 {
 	__shared__ AppendScratch sc_dir, sc_nee, sc_scatter, sc_ref;
+	// The vertex state that only the emissive hit and the scattering read -- the emission, hit distance, triangle, previous pdf, cone radius and the
+	// scattering's three QMC samples, the frame weight -- waits out the two NEE sections here rather than in registers: the light sample's BSDF evaluation is the kernel's
+	// register peak, and these fifteen words held across it kept the kernel at 108 VGPRs (4 waves per SIMD).  Each lane reads back only its own words.
+	__shared__ float4 park[3][SHADE_BLOCK];
 	uint32_t prev_vinfo = 0xFFFFFFFFu, vinfo = 0xFFFFFFFFu;
 	int psf_mode = 0; f3 mat_diffuse = splat3(1.0f);
 	// One thread per queue entry.  A miss ends the path (no sky lighting, src/pathtracer_core.h:1249-1252) and its lane idles through the kernel -- a third
@@ -275,8 +284,8 @@ void shade_kernel(const ShadeParams P)
 
 	float4 hit4 = make_float4(-1.0f, as_f32(0xFFFFFFFFu), 0.0f, 0.0f);
 	if (i < n_in) hit4 = P.in.hits[i];
-	const float hit_t = hit4.x;
-	const int32_t tri = int32_t(as_u32(hit4.y));
+	float hit_t = hit4.x;
+	int32_t tri = int32_t(as_u32(hit4.y));
 	// inactive threads still take part in the block-wide queue appends below
 	const bool active = (i < n_in) && (hit_t > 0.0f && tri >= 0);
 
@@ -357,6 +366,9 @@ void shade_kernel(const ShadeParams P)
 		#pragma unroll
 		for (uint32_t k = 0; k < 6; ++k) z[k] = (FPT_SHADE_SKIP & 32) ? float(px + k) * 0.01f : sequence_sample(P.seq, px, py, (P.bounce + 1) * 6 + k, instance);
 	}
+	park[0][threadIdx.x] = make_float4(m_emissive.x, m_emissive.y, m_emissive.z, m_emissive.w);
+	park[1][threadIdx.x] = make_float4(hit_t, as_f32(uint32_t(tri)), p_prev, cone_radius);
+	park[2][threadIdx.x] = make_float4(z[3], z[4], z[5], slot.weight);
 
 	// ---- PSFPTVertexProcessor::preprocess_vertex (src/psfpt_vertex_processor.h:76-187) ----
 	if (PSF)
@@ -415,6 +427,12 @@ void shade_kernel(const ShadeParams P)
 		}
 		const uint32_t qslot = block_append_slot(P.shadow.size, want, sc_nee);
 		if (want) { write_shadow_entry(P.shadow, qslot, pl, 0x2u, pixel_info, P.pass.n_passes > 1, slot.k); if (PSF) P.shadow.vinfo[qslot] = vinfo; }
+	}
+	{
+		const float4 a = park[0][threadIdx.x], b = park[1][threadIdx.x], c = park[2][threadIdx.x];
+		m_emissive = mk4(a.x, a.y, a.z, a.w); hit_t = b.x; tri = int32_t(as_u32(b.y)); p_prev = b.z; cone_radius = b.w; z[3] = c.x; z[4] = c.y; z[5] = c.z; slot.weight = c.w;
+		// the path's cell again (decode_slot); its pixel is read from here on only with one pass in flight, where decode_slot made it the cell
+		slot.slot = slot.pixel = pixel_info & 0x7FFFFFFu;
 	}
 	// ---- emissive surface hit, MIS against NEE at the previous vertex (:1109-1154) ----
 	// (A surface that emits nothing -- nearly every hit -- has nothing to add: with m_emissive = 0 the sample e below is w * 0 * mis_w, i.e. 0 or NaN, and neither passes
