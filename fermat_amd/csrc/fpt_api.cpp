@@ -172,13 +172,12 @@ static void rt_launch(fpt_context* ctx, uint32_t count, const fpt_ray* d_rays, f
 {
 	require(ctx->has_geometry, "fpt_rt_trace*: create_geometry has not been called");
 	if (count == 0) return;
-	TraceParams p = base_trace_params(ctx);
+	PassCounters cnt{ ctx->d_counters.ptr };
+	TraceParams p = trace_params(ctx, cnt);
 	p.rays = reinterpret_cast<const float4*>(d_rays);
 	p.hits = reinterpret_cast<float4*>(d_hits);
 	p.bits = d_bits;
 	p.count = count;
-	p.work_counter = ctx->d_counters.ptr + CNT_TICKETS;
-	p.stats = ctx->d_trace_stats.ptr;
 	FPT_HIP_CHECK(hipMemsetAsync(p.work_counter, 0, TICKET_STRIDE * sizeof(uint32_t), ctx->stream));
 	if (counted) FPT_HIP_CHECK(hipMemsetAsync(p.stats, 0, 8 * sizeof(unsigned long long), ctx->stream));
 	if (d_bits) FPT_HIP_CHECK(hipMemsetAsync(d_bits, 0, size_t((count + 31) / 32) * sizeof(uint32_t), ctx->stream));
@@ -513,10 +512,7 @@ const float4* ensure_vpl_points(fpt_context* ctx, const fpt_rendering_context_vi
 	if (!fresh)
 	{
 		ctx->d_vpl_points.alloc(VPL_POINT_STRIDE * size_t(n));
-		EmitterView em; std::memset(&em, 0, sizeof(em));
-		em.n_prims = uint32_t(ctx->emitters.mesh_cdf.size()); em.prims_cdf = ctx->d_mesh_cdf.ptr; em.prims_inv_area = ctx->d_mesh_inv_area.ptr;
-		em.n_vpls = n; em.vpls = ctx->d_vpls.ptr; em.norm = ctx->emitters.norm;
-		launch_vpl_points(em, view->mesh, view->d_textures, ctx->d_vpl_points.ptr, s);
+		launch_vpl_points(emitter_view(ctx, true), view->mesh, view->d_textures, ctx->d_vpl_points.ptr, s);
 		FPT_HIP_CHECK(hipGetLastError());
 		ctx->vpl_points_generation = ctx->emitter_generation; ctx->vpl_points_mesh = view->mesh; ctx->vpl_points_textures = view->d_textures;
 	}
@@ -534,6 +530,13 @@ ContribLog lane_log(fpt_context* ctx, uint32_t first)
 	g.mask = ctx->log_mask.ptr + size_t(first) * g.mask_words;
 	return g;
 }
+void sample_targets(fpt_context* ctx, const FrameBufferDev& real_fb, bool batched, uint32_t first, FrameBufferDev& fb, ContribLog& log)
+{
+	fb = real_fb; std::memset(&log, 0, sizeof(log));
+	if (!batched) return;
+	fb = plane_view(real_fb, reinterpret_cast<float4*>(ctx->d_acc[FPT_FB_DIFFUSE_A].ptr) + first, reinterpret_cast<float4*>(ctx->d_acc[FPT_FB_SPECULAR_A].ptr) + first);
+	log = lane_log(ctx, first);
+}
 } // namespace fpt
 extern "C" {
 
@@ -546,80 +549,42 @@ static void render_lane(fpt_context* ctx, const LaneRefs& L, uint32_t instance, 
 		const fpt_pt_options& opt = ctx->opt;
 		const FrameBufferDev real_fb = fb_dev(view->fb);
 		PassInfo pass; pass.base_instance = instance; pass.n_passes = n_passes; pass.n_slot = L.n; pass.acc_stride = ctx->n_local; pass.pixels = L.pixels;
-		FrameBufferDev fb = real_fb;
-		ContribLog log; std::memset(&log, 0, sizeof(log));
-		if (batched)
-		{
-			// the two albedo channels keep a plane per pass (one term per pass and pixel); every other sample goes to the path's cell of the log
-			for (int c = 0; c < 6; ++c) fb.ch[c] = nullptr;
-			fb.ch[FPT_FB_DIFFUSE_A] = reinterpret_cast<float4*>(ctx->d_acc[FPT_FB_DIFFUSE_A].ptr) + L.first;
-			fb.ch[FPT_FB_SPECULAR_A] = reinterpret_cast<float4*>(ctx->d_acc[FPT_FB_SPECULAR_A].ptr) + L.first;
-			log = lane_log(ctx, L.first);
-		}
+		FrameBufferDev fb; ContribLog log;
+		sample_targets(ctx, real_fb, batched, L.first, fb, log);
 		const uint32_t n_paths = L.n * n_passes;
 		const size_t q_off = size_t(L.first) * ctx->max_batch;          // the lane's share of the queue arrays
 		// persistent traversal grid: no more blocks than the lane's queues can feed (closest-hit + shadow rays <= 2 per path)
 		const uint32_t trace_grid = std::min(ctx->trace_blocks(), std::max(1u, uint32_t((2ull * n_paths + 255ull) / 256ull)));
-		uint32_t* cnt = L.cnt;
 		const bool sync_mode = ctx->profiling || ctx->capture_bounce >= 0;
 		float t_ms[5] = { 0, 0, 0, 0, 0 };
-		auto timed = [&](int bucket, auto&& launch) {
-			if (ctx->profiling_level == 2 && ctx->ev_cursor + 2 <= ctx->ev_pool.size())
-			{
-				const uint32_t e0 = ctx->ev_cursor, e1 = ctx->ev_cursor + 1; ctx->ev_cursor += 2;
-				FPT_HIP_CHECK(hipEventRecord(ctx->ev_pool[e0], s));
-				launch();
-				FPT_HIP_CHECK(hipEventRecord(ctx->ev_pool[e1], s));
-				ctx->timed_launches.push_back(fpt_context::TimedLaunch{ bucket, e0, e1 });
-				return;
-			}
-			if (ctx->profiling) FPT_HIP_CHECK(hipEventRecord(ctx->ev[0], s));
-			launch();
-			if (ctx->profiling) { FPT_HIP_CHECK(hipEventRecord(ctx->ev[1], s)); FPT_HIP_CHECK(hipEventSynchronize(ctx->ev[1])); float ms = 0; FPT_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1])); t_ms[bucket] += ms; }
-		};
 
 		// PathTracer::render (src/renderers/pathtracer_impl.h:197-324); rescale_frame / update_variances (or the merge of the planes) are the caller's
-		FPT_HIP_CHECK(hipMemsetAsync(cnt, 0, CNT_TOTAL * sizeof(uint32_t), s));
+		FPT_HIP_CHECK(hipMemsetAsync(L.cnt, 0, CNT_TOTAL * sizeof(uint32_t), s));
+		PassCounters cnt{ L.cnt };
 
 		SequenceView seq; seq.shifts = ctx->d_shifts.ptr; seq.n_dims = ctx->seq_dims; seq.tile_size = ctx->seq_tile;
 		// path queue of bounce b counts in group b; shade_b fills the path queue of group b+1 and the shadow queues of group b
-		auto counter = [&](uint32_t bounce, uint32_t which) { return cnt + CNT_QUEUES + CNT_PER_BOUNCE * bounce + which; };
-		PathQueue qin = offset_queue(ctx->q_a.view(counter(0, CNT_PATH)), q_off), qout = offset_queue(ctx->q_b.view(counter(1, CNT_PATH)), q_off);
-		ShadowQueue qsd = offset_queue(ctx->q_shadow_dir.view(counter(0, CNT_SHADOW_DIR)), ctx->q_shadow_dir.entries > 1 ? q_off : 0), qs = offset_queue(ctx->q_shadow.view(counter(0, CNT_SHADOW)), q_off);
+		PathQueue qin = offset_queue(ctx->q_a.view(cnt.queue(0, CNT_PATH)), q_off), qout = offset_queue(ctx->q_b.view(cnt.queue(1, CNT_PATH)), q_off);
+		ShadowQueue qsd = offset_queue(ctx->q_shadow_dir.view(cnt.queue(0, CNT_SHADOW_DIR)), ctx->q_shadow_dir.entries > 1 ? q_off : 0), qs = offset_queue(ctx->q_shadow.view(cnt.queue(0, CNT_SHADOW)), q_off);
 		// The ray-cone plane (PTRayQueue's cone radius + pdf, src/pathtracer_queues.h) is carried for whoever reads it: the path-space filter's hash (fpt_psf_api.cpp)
 		// and fpt_pt_set_capture.  The plain path tracer's vertices do not, and 8 B read + 8 B written per vertex are 4 % of a bandwidth-bound kernel's traffic.
 #ifndef FPT_KEEP_CONES
 		if (ctx->capture_bounce < 0) qin.cones = qout.cones = nullptr;
 #endif
 
-		// generate_primary_rays (src/pathtracer_kernels.h:166-181)
-		{
-			PrimaryParams pp;
-			pp.out = qin; pp.seq = seq; pp.pixels = L.pixels; pp.n_pixels = L.n; pp.res_x = view->res_x; pp.res_y = view->res_y; pp.pass = pass;
-			pp.eye = mk3(view->camera.eye[0], view->camera.eye[1], view->camera.eye[2]);
-			camera_frame(view->camera, view->aspect, pp.U, pp.V, pp.W);
-			pp.W_len = length(pp.W);
-			const float tn = tanf(view->camera.fov / 2);
-			pp.sq_focal = (float(view->res_x * view->res_y) / 4.0f) / (tn * tn);        // Camera::square_pixel_focal_length, src/camera.h:120-128
-			launch_primary_rays(pp, s);
-		}
+		launch_primary_rays(primary_params(view, seq, L.pixels, L.n, pass, qin), s);
 
 		ShadeParams sh; std::memset(&sh, 0, sizeof(sh));
 		sh.shadow_dir = qsd; sh.shadow = qs; sh.seq = seq;
 		sh.mesh = view->mesh; sh.textures = view->d_textures; sh.table = view->d_glossy_reflectance; sh.shade_records = ensure_shade_records(ctx, view, s);
 		sh.dir_lights = view->d_dir_lights; sh.n_dir_lights = view->dir_lights_count;
-		EmitterView em;
-		em.n_prims = uint32_t(ctx->emitters.mesh_cdf.size()); em.prims_cdf = ctx->d_mesh_cdf.ptr; em.prims_inv_area = ctx->d_mesh_inv_area.ptr;
-		em.n_vpls = opt.nee_type == 1 ? uint32_t(ctx->emitters.vpls.size()) : 0u; em.vpls = opt.nee_type == 1 ? ctx->d_vpls.ptr : nullptr; em.norm = ctx->emitters.norm;
-		em.vpl_points = opt.nee_type == 1 ? ensure_vpl_points(ctx, view, s) : nullptr;
-		sh.emitters = em;
+		sh.emitters = emitter_view(ctx, opt.nee_type == 1);
+		sh.emitters.vpl_points = opt.nee_type == 1 ? ensure_vpl_points(ctx, view, s) : nullptr;
 		sh.fb = fb; sh.log = log; sh.gbuffer = real_fb; sh.opt = opt; sh.res_x = view->res_x; sh.res_y = view->res_y;
 		sh.pass = pass;
-		const uint32_t total_vpls = uint32_t(ctx->emitters.vpls.size());
 
 		// what a fused any-hit launch needs to retire an unoccluded sample, one block per (bounce, light kind).  The blocks hold nothing that
-		// changes from pass to pass (the first instance travels as a kernel argument), so they are uploaded -- which synchronises the
-		// stream -- only when a pointer or the batch shape changed, and consecutive render calls stay asynchronous
+		// changes from pass to pass (the first instance travels as a kernel argument), so they are uploaded only when a pointer or the batch shape changed
 		{
 			std::vector<FusedResolve> blocks(2 * size_t(opt.max_path_length));
 			std::memset(blocks.data(), 0, blocks.size() * sizeof(FusedResolve));
@@ -631,36 +596,30 @@ static void render_lane(fpt_context* ctx, const LaneRefs& L, uint32_t instance, 
 					FusedResolve& f = blocks[2 * size_t(b) + kind];
 					f.w_d = q.w_d; f.w_g = q.w_g; f.fb = fb; f.pass = block_pass; f.bounce = b; f.log = log; f.kind = uint32_t(kind);
 				}
-			if (L.h_fused->size() != blocks.size() || std::memcmp(L.h_fused->data(), blocks.data(), blocks.size() * sizeof(FusedResolve)) != 0)
-			{
-				L.d_fused->upload(blocks.data(), blocks.size(), s);
-				*L.h_fused = blocks;
-			}
+			upload_if_changed(*L.d_fused, *L.h_fused, blocks, s);
 		}
-		auto fused_block = [&](const ShadowQueue& q, uint32_t bounce) { return L.d_fused->ptr + 2 * size_t(bounce) + (q.w_d == qs.w_d ? 1 : 0); };
+		// a traversal launch that retires the shadow rays of `q` (bounce `bounce`) through their fused resolve block
+		auto shadow_params = [&](const ShadowQueue& q, uint32_t bounce) {
+			TraceParams p = trace_params(ctx, cnt);
+			p.shadow_rays = q.rays; p.shadow_size = q.size; p.fused = L.d_fused->ptr + 2 * size_t(bounce) + (q.w_d == qs.w_d ? 1 : 0); p.base_instance = instance;
+			return p;
+		};
 
 		fpt_pt_stats& st = ctx->stats;
 		if (sync_mode) { std::memset(&st, 0, sizeof(st)); }
 		ctx->captured_count = 0;
-		uint32_t ticket = 0;
 
 		// closest-hit trace of the primary rays (RTContext::trace); later bounces are traced by the MIXED launch at the end of
 		// the previous iteration, together with that bounce's shadow rays
 		{
-			TraceParams tp = base_trace_params(ctx);
-			tp.rays = qin.rays; tp.hits = qin.hits; tp.count_ptr = qin.size; tp.work_counter = cnt + CNT_TICKETS + TICKET_STRIDE * (ticket++);
-			tp.stats = ctx->d_trace_stats.ptr;
-			timed(0, [&] { launch_trace_closest_queue(tp, true, ctx->counting, trace_grid, s); });
+			TraceParams tp = trace_params(ctx, cnt);
+			tp.rays = qin.rays; tp.hits = qin.hits; tp.count_ptr = qin.size;
+			timed_launch(ctx, 0, s, [&] { launch_trace_closest_queue(tp, true, ctx->counting, trace_grid, s); }, t_ms);
 		}
 		for (uint32_t bounce = 0; bounce < opt.max_path_length; ++bounce)
 		{
-			// compute_per_bounce_options (src/pathtracer_core.h:594-620)
 			sh.bounce = bounce;
-			sh.do_nee = total_vpls && ((bounce + 2 <= opt.max_path_length) &&
-				((bounce == 0 && opt.direct_lighting_nee && opt.direct_lighting) || (bounce > 0 && opt.indirect_lighting_nee)));
-			sh.do_emissive = ((bounce == 0 && opt.visible_lights) || (bounce == 1 && opt.direct_lighting_bsdf && opt.direct_lighting) || (bounce > 1 && opt.indirect_lighting_bsdf));
-			const uint32_t max_vertices = opt.max_path_length + (((opt.max_path_length == 2 && opt.direct_lighting_bsdf) || (opt.max_path_length > 2 && opt.indirect_lighting_bsdf)) ? 1 : 0);
-			sh.do_scatter = (bounce + 2 < max_vertices);
+			per_bounce_options(sh, opt, uint32_t(ctx->emitters.vpls.size()));
 
 			if (sync_mode)
 			{
@@ -692,33 +651,28 @@ static void render_lane(fpt_context* ctx, const LaneRefs& L, uint32_t instance, 
 				}
 			}
 			// this bounce's output counters are fresh words zeroed by the per-pass memset
-			qout.size = counter(bounce + 1, CNT_PATH); qsd.size = counter(bounce, CNT_SHADOW_DIR); qs.size = counter(bounce, CNT_SHADOW);
+			qout.size = cnt.queue(bounce + 1, CNT_PATH); qsd.size = cnt.queue(bounce, CNT_SHADOW_DIR); qs.size = cnt.queue(bounce, CNT_SHADOW);
 			sh.in = qin; sh.scatter = qout; sh.shadow_dir = qsd; sh.shadow = qs;
-			timed(3, [&] { launch_shade(sh, n_paths, s); });
+			timed_launch(ctx, 3, s, [&] { launch_shade(sh, n_paths, s); }, t_ms);
 
 			// directional-light samples are resolved first (their own queue), then the mesh-light samples of the same bounce
 			if (view->dir_lights_count)
 			{
-				TraceParams sp = base_trace_params(ctx);
-				sp.work_counter = cnt + CNT_TICKETS + TICKET_STRIDE * (ticket++);
-				sp.shadow_rays = qsd.rays; sp.shadow_size = qsd.size; sp.fused = fused_block(qsd, bounce); sp.base_instance = instance; sp.stats = ctx->d_trace_stats.ptr;
-				timed(2, [&] { launch_trace_shadow(sp, true, ctx->counting, trace_grid, s); });
+				const TraceParams sp = shadow_params(qsd, bounce);
+				timed_launch(ctx, 2, s, [&] { launch_trace_shadow(sp, true, ctx->counting, trace_grid, s); }, t_ms);
 			}
 			if (bounce + 1 < opt.max_path_length)
 			{
 				// ONE launch: closest-hit trace of the scattered rays (= bounce+1's RTContext::trace) + any-hit trace of this bounce's
 				// shadow rays fused with solve_occlusion (RTContext::trace_shadow + solve_occlusion)
-				TraceParams mp = base_trace_params(ctx);
-				mp.rays = qout.rays; mp.hits = qout.hits; mp.count_ptr = qout.size; mp.work_counter = cnt + CNT_TICKETS + TICKET_STRIDE * (ticket++);
-				mp.shadow_rays = qs.rays; mp.shadow_size = qs.size; mp.fused = fused_block(qs, bounce); mp.base_instance = instance; mp.stats = ctx->d_trace_stats.ptr;
-				timed(1, [&] { launch_trace_mixed(mp, ctx->counting, trace_grid, s); });
+				TraceParams mp = shadow_params(qs, bounce);
+				mp.rays = qout.rays; mp.hits = qout.hits; mp.count_ptr = qout.size;
+				timed_launch(ctx, 1, s, [&] { launch_trace_mixed(mp, ctx->counting, trace_grid, s); }, t_ms);
 			}
 			else if (sh.do_nee)
 			{
-				TraceParams sp = base_trace_params(ctx);
-				sp.work_counter = cnt + CNT_TICKETS + TICKET_STRIDE * (ticket++);
-				sp.shadow_rays = qs.rays; sp.shadow_size = qs.size; sp.fused = fused_block(qs, bounce); sp.base_instance = instance; sp.stats = ctx->d_trace_stats.ptr;
-				timed(2, [&] { launch_trace_shadow(sp, true, ctx->counting, trace_grid, s); });
+				const TraceParams sp = shadow_params(qs, bounce);
+				timed_launch(ctx, 2, s, [&] { launch_trace_shadow(sp, true, ctx->counting, trace_grid, s); }, t_ms);
 			}
 			if (sync_mode)
 			{
@@ -1124,9 +1078,7 @@ int fpt_debug_vertex(fpt_context* ctx, const fpt_rendering_context_view* view, i
 		if (n && (op == 4 || op == 5 || op == 6 || op == 8) && !ctx->has_emitters) throw std::runtime_error("fpt_debug_vertex: no emitter tables (fpt_mesh_lights_init)");
 		if (rec_stride != 0 && rec_stride != 48) throw std::runtime_error("fpt_debug_vertex: rec_stride must be 0 or 48");
 		const bool vpl = (flags & 1u) != 0;
-		EmitterView em; std::memset(&em, 0, sizeof(em));
-		em.n_prims = uint32_t(ctx->emitters.mesh_cdf.size()); em.prims_cdf = ctx->d_mesh_cdf.ptr; em.prims_inv_area = ctx->d_mesh_inv_area.ptr;
-		em.n_vpls = vpl ? uint32_t(ctx->emitters.vpls.size()) : 0u; em.vpls = vpl ? ctx->d_vpls.ptr : nullptr; em.norm = ctx->emitters.norm;
+		EmitterView em = emitter_view(ctx, vpl);
 		em.vpl_points = (vpl && (flags & 2u)) ? ensure_vpl_points(ctx, view, ctx->stream) : nullptr;
 		const ShadeRecord* records = op == 2 ? ensure_shade_records(ctx, view, ctx->stream) : nullptr;
 		const fpt_texture* tex = d_textures ? d_textures : view->d_textures;

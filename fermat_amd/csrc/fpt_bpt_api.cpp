@@ -16,10 +16,6 @@ using namespace fpt;
 
 namespace {
 
-// counters: [0, TICKETS) trace ticket dispensers (one 128-byte-strided group per launch), then one word per queue per bounce
-enum { B_TICKET_STRIDE = 8 * 32, B_MAX_LAUNCHES = 3 * 34, B_QUEUES = B_TICKET_STRIDE * B_MAX_LAUNCHES, B_PER_BOUNCE = 64, B_LIGHT = 0, B_EYE = 32,
-       B_SHADOW_BASE = B_QUEUES + B_PER_BOUNCE * 35, B_TOTAL = B_SHADOW_BASE + 32 * 36 };
-
 BptQueue queue_view(fpt_context::BptState& b, int which, uint32_t* size)
 {
 	BptQueue q; q.rays = b.q_rays[which].ptr; q.hits = b.q_hits[which].ptr; q.weights = b.q_weights[which].ptr; q.path_weights = b.q_pw[which].ptr; q.pixels = b.q_pixels[which].ptr; q.chan = b.q_chan[which].ptr; q.size = size;
@@ -34,14 +30,6 @@ uint32_t read_u32(fpt_context* ctx, const uint32_t* d)
 	return v;
 }
 
-FrameBufferDev plane_view(fpt_context::BptState& b, const FrameBufferDev& real)
-{
-	// passes in flight: only the two albedo channels keep a plane per pass (one term per pass and pixel); every other term goes to the eye path's cell of the log
-	FrameBufferDev fb = real;
-	for (int c = 0; c < 6; ++c) fb.ch[c] = nullptr;
-	fb.ch[FPT_FB_DIFFUSE_A] = b.acc[FPT_FB_DIFFUSE_A].ptr; fb.ch[FPT_FB_SPECULAR_A] = b.acc[FPT_FB_SPECULAR_A].ptr;
-	return fb;
-}
 BptLog log_view(fpt_context::BptState& b)
 {
 	BptLog g; g.val = b.log_val.ptr; g.chan = b.log_chan.ptr; g.mask = b.log_mask.ptr;
@@ -139,7 +127,7 @@ int fpt_bpt_init(fpt_context* ctx, const fpt_bpt_options* opts, const fpt_render
 		const uint32_t L = opts->max_path_length;
 		alloc_storage(ctx, 1);
 		if (ctx->defer_kind == DEFER_BPT) ctx->defer_max = 1;          // storage for one pass: fpt_bpt_set_deferred sizes it again
-		b.counters.alloc(B_TOTAL);
+		b.counters.alloc(CNT_TOTAL);
 		// sampler: (L+1)*2*6 dimensions (src/renderers/bpt.cu:83-87); consumes the context's rand() stream after whatever ran before
 		std::vector<float> shifts;
 		b.seq_dims = (L + 1) * 2 * 6;
@@ -185,23 +173,23 @@ int fpt_bpt_download_light_vertices(fpt_context* ctx, float* h_pos, uint32_t* h_
 // that the ranks can hand each other the vertices of their light paths (fpt_bpt_exchange_light_vertices, or export / import) before fpt_bpt_finish.
 struct BptRun
 {
-	fpt_context* ctx; fpt_context::BptState& b; BptParams P; uint32_t* cnt; hipStream_t s; uint32_t n_launch, L; bool prof;
+	// the queues' slots in a bounce group of the counter block (fpt_host.h)
+	enum : uint32_t { LIGHT = CNT_PATH, EYE = CNT_SHADOW_DIR, SHADOW = CNT_SHADOW };
+	fpt_context* ctx; fpt_context::BptState& b; BptParams P; hipStream_t s; uint32_t n_launch, L; bool prof;
 	BptRun(fpt_context* c, uint32_t instance, uint32_t n_passes, const fpt_rendering_context_view* view) : ctx(c), b(c->bpt)
 	{
 		const bool batched = n_passes > 1;
-		n_launch = b.n_local * n_passes; s = ctx->stream; L = b.opt.max_path_length; cnt = b.counters.ptr; prof = b.profiling;
+		n_launch = b.n_local * n_passes; s = ctx->stream; L = b.opt.max_path_length; prof = b.profiling;
 		std::memset(&P, 0, sizeof(P));
 		P.store.rec = b.v_rec.ptr; P.store.pos = b.v_pos.ptr; P.store.counts = b.v_counts.ptr;
 		P.conn = b.conn.ptr; P.splat = b.splat_ptr();
 		P.flat = b.flat.ptr; P.flat_meta = b.flat_meta.ptr; P.flat_block_sums = b.flat_block_sums.ptr;
 		P.seq.shifts = b.d_shifts.ptr; P.seq.n_dims = b.seq_dims; P.seq.tile_size = 256;
 		P.mesh = view->mesh; P.textures = view->d_textures; P.table = view->d_glossy_reflectance; P.shade_records = ensure_shade_records(ctx, view, s);
-		EmitterView em;
-		em.n_prims = uint32_t(ctx->emitters.mesh_cdf.size()); em.prims_cdf = ctx->d_mesh_cdf.ptr; em.prims_inv_area = ctx->d_mesh_inv_area.ptr;
-		em.n_vpls = b.opt.use_vpls ? uint32_t(ctx->emitters.vpls.size()) : 0u; em.vpls = b.opt.use_vpls ? ctx->d_vpls.ptr : nullptr; em.norm = ctx->emitters.norm; em.vpl_points = nullptr;
-		P.emitters = em;
+		P.emitters = emitter_view(ctx, b.opt.use_vpls);
 		const FrameBufferDev real_fb = fb_dev(view->fb);
-		P.fb = batched ? plane_view(b, real_fb) : real_fb;
+		// passes in flight: the terms of the albedo planes' channels go to the planes, every other term to the eye path's cell of the log
+		P.fb = batched ? plane_view(real_fb, b.acc[FPT_FB_DIFFUSE_A].ptr, b.acc[FPT_FB_SPECULAR_A].ptr) : real_fb;
 		if (batched) P.log = log_view(b);
 		P.opt = b.opt; P.pixels = b.d_pixels; P.n_local = b.n_local; P.n_paths = b.n_paths;
 		P.res_x = view->res_x; P.res_y = view->res_y; P.instance = instance;
@@ -214,30 +202,29 @@ struct BptRun
 	}
 	void trace(const float4* rays, float4* hits, const uint32_t* count_ptr, bool any_hit)
 	{
-		TraceParams tp = base_trace_params(ctx);
-		tp.rays = rays; tp.hits = hits; tp.count_ptr = count_ptr; tp.work_counter = cnt + B_TICKET_STRIDE * (b.ticket++); tp.stats = ctx->d_trace_stats.ptr;
+		TraceParams tp = trace_params(ctx, b.cnt);
+		tp.rays = rays; tp.hits = hits; tp.count_ptr = count_ptr;
 		if (any_hit) timed_launch(ctx, 2, s, [&] { launch_trace_shadow(tp, false, ctx->counting, ctx->trace_blocks(), s); });
 		else         timed_launch(ctx, 0, s, [&] { launch_trace_closest(tp, ctx->counting, ctx->trace_blocks(), s); });
 	}
-	uint32_t* qcount(uint32_t bounce, uint32_t which) { return cnt + B_QUEUES + B_PER_BOUNCE * bounce + which; }
 
 	// ---- sample_light_subpaths (src/bpt_control.h:290-350) ----
 	void light_phase()
 	{
 		fpt_bpt_stats& st = b.stats;
 		if (prof) std::memset(&st, 0, sizeof(st));
-		b.ticket = 0;
-		FPT_HIP_CHECK(hipMemsetAsync(cnt, 0, B_TOTAL * sizeof(uint32_t), s));
+		FPT_HIP_CHECK(hipMemsetAsync(b.counters.ptr, 0, CNT_TOTAL * sizeof(uint32_t), s));
+		b.cnt = PassCounters{ b.counters.ptr };
 		// shared light vertices: the store holds the other ranks' vertices of the previous batch -- forget them
 		if (b.shared_lv) FPT_HIP_CHECK(hipMemsetAsync(b.v_counts.ptr, 0, size_t(P.n_store) * sizeof(uint32_t), s));
 		int cur = 0;
-		P.out = queue_view(b, cur, qcount(0, B_LIGHT));
+		P.out = queue_view(b, cur, b.cnt.queue(0, LIGHT));
 		launch_bpt_light_primary(P, s);
 		for (uint32_t bounce = 0; bounce + 1 < L; ++bounce)
 		{
 			P.bounce = bounce;
-			P.in = queue_view(b, cur, qcount(bounce, B_LIGHT));
-			P.out = queue_view(b, cur ^ 1, qcount(bounce + 1, B_LIGHT));
+			P.in = queue_view(b, cur, b.cnt.queue(bounce, LIGHT));
+			P.out = queue_view(b, cur ^ 1, b.cnt.queue(bounce + 1, LIGHT));
 			trace(P.in.rays, P.in.hits, P.in.size, false);
 			timed_launch(ctx, 3, s, [&] { launch_bpt_light_vertices(P, n_launch, s); });
 			if (prof) { st.light_queue[bounce] = read_u32(ctx, P.in.size); if (st.light_queue[bounce]) st.n_bounces_light = bounce + 1; }
@@ -251,24 +238,24 @@ struct BptRun
 		if (b.opt.single_connection) launch_bpt_build_flat_list(P, s);
 		// ---- sample_eye_subpaths (src/bpt_control.h:384-470) ----
 		int cur = 0;
-		P.out = queue_view(b, cur, qcount(0, B_EYE));
+		P.out = queue_view(b, cur, b.cnt.queue(0, EYE));
 		launch_bpt_eye_primary(P, s);
 		BptParams P_prev = P;
 		for (uint32_t bounce = 0; bounce < L; ++bounce)
 		{
 			P.bounce = bounce;
-			P.in = queue_view(b, cur, qcount(bounce, B_EYE));
-			P.out = queue_view(b, cur ^ 1, qcount(bounce + 1, B_EYE));
+			P.in = queue_view(b, cur, b.cnt.queue(bounce, EYE));
+			P.out = queue_view(b, cur ^ 1, b.cnt.queue(bounce + 1, EYE));
 			P.shadow.rays = b.s_rays.ptr; P.shadow.hits = b.s_hits.ptr; P.shadow.weights = b.s_weights.ptr; P.shadow.pixels = b.s_pixels.ptr; P.shadow.chan = b.s_chan.ptr;
-			P.shadow.size = cnt + B_SHADOW_BASE + 32 * bounce;
+			P.shadow.size = b.cnt.queue(bounce, SHADOW);
 			// the connections of bounce b-1 ride in the launch that finds the hits of bounce b (one traversal launch per bounce instead of two: a
 			// launch cannot end before its longest ray); they are added -- by the previous bounce's parameter block -- before this bounce's
 			// vertices touch the frame or reuse the connection queue, i.e. in the order of the unfused sequence
 			if (bounce == 0) trace(P.in.rays, P.in.hits, P.in.size, false);
 			else
 			{
-				TraceParams tp = base_trace_params(ctx);
-				tp.rays = P.in.rays; tp.hits = P.in.hits; tp.count_ptr = P.in.size; tp.work_counter = cnt + B_TICKET_STRIDE * (b.ticket++); tp.stats = ctx->d_trace_stats.ptr;
+				TraceParams tp = trace_params(ctx, b.cnt);
+				tp.rays = P.in.rays; tp.hits = P.in.hits; tp.count_ptr = P.in.size;
 				tp.shadow_rays = P_prev.shadow.rays; tp.shadow_size = P_prev.shadow.size;
 				timed_launch(ctx, 0, s, [&] { launch_trace_mixed_hits(tp, P_prev.shadow.hits, ctx->counting, ctx->trace_blocks(), s); });
 				timed_launch(ctx, 3, s, [&] { launch_bpt_eye_resolve(P_prev, n_launch, s); });
@@ -290,7 +277,7 @@ struct BptRun
 		// ---- light_tracing (src/bpt_control.h:572-600): this rank's own light paths ----
 		if (b.light_tracing)
 		{
-			P.shadow.size = cnt + B_SHADOW_BASE + 32 * L;
+			P.shadow.size = b.cnt.queue(L, SHADOW);
 			timed_launch(ctx, 3, s, [&] { launch_bpt_connect_camera(P, s); });
 			trace(P.shadow.rays, P.shadow.hits, P.shadow.size, true);
 			launch_bpt_splat(P, uint32_t(std::min<size_t>(size_t(n_launch) * (L > 1 ? L - 1 : 1), 0xFFFFFFFFu)), s);

@@ -11,6 +11,8 @@
 #include <cmath>
 #include <chrono>
 
+inline void require(bool cond, const char* msg) { if (!cond) throw std::runtime_error(msg); }
+
 namespace fpt {
 
 #define FPT_HIP_CHECK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
@@ -74,6 +76,35 @@ struct ShadowStorage
 	void alloc(size_t n) { rays.alloc(2 * n); w_d.alloc(n); w_g.alloc(n); entries = n; }
 };
 
+// The per-pass counter block (uint32 words), one layout for the three renderers and the RT boundary's launches.  [CNT_TICKETS, CNT_QUEUES): one
+// ticket area of TICKET_STRIDE words per traversal launch (8 shard dispensers, 128 B apart); then CNT_GROUPS groups of CNT_PER_BOUNCE words, one per
+// bounce, each with three queue-size slots on their own 128-byte lines: PT / PSFPT path queue, directional and mesh-light shadow queues; BPT light
+// sub-paths, eye sub-paths, connection rays.  Every queue of every bounce counts in a fresh word, so ONE memset per pass replaces the reference's two
+// cudaMemsets per bounce (src/pathtracer_kernels.h:348-350).  Worst cases, L = max_path_length:
+//   PT    (L <= 31): primary trace + per bounce <= 2 (directional shadow, MIXED or mesh-light shadow; none of the latter at the last bounce) <= 2L = 62
+//                    launches; path queues of bounces 0..L: L + 1 = 32 groups
+//   PSFPT (L <= 31): primary trace + per bounce <= 3 (directional shadow, MIXED or shadow + closest; the last bounce traces nothing) <= 1 + 3(L-1) = 91
+//                    launches; L + 1 = 32 groups
+//   BPT   (L <= 15): L - 1 light traces, L eye traces, the last bounce's connections, light tracing = 2L + 1 = 31 launches; bounces 0..L: L + 1 = 16 groups
+enum : uint32_t { TICKET_STRIDE = 8 * 32, CNT_MAX_LAUNCHES = 96, CNT_GROUPS = 34, CNT_PER_BOUNCE = 96,
+                  CNT_TICKETS = 0, CNT_QUEUES = TICKET_STRIDE * CNT_MAX_LAUNCHES, CNT_TOTAL = CNT_QUEUES + CNT_PER_BOUNCE * CNT_GROUPS,
+                  CNT_PATH = 0, CNT_SHADOW_DIR = 32, CNT_SHADOW = 64 };          // the slots of a bounce group
+
+// one pass's view of a counter block: ticket areas handed out in launch order, queue-size words by (bounce, slot)
+struct PassCounters
+{
+	uint32_t* base = nullptr; uint32_t launches = 0;
+	uint32_t* ticket()
+	{
+		require(launches < CNT_MAX_LAUNCHES, "fpt: a pass has more traversal launches than the counter block has ticket areas");
+		return base + CNT_TICKETS + TICKET_STRIDE * launches++;
+	}
+	uint32_t* queue(uint32_t bounce, uint32_t slot) const
+	{
+		require(bounce < CNT_GROUPS, "fpt: a pass has more bounces than the counter block has queue-size groups");
+		return base + CNT_QUEUES + CNT_PER_BOUNCE * bounce + slot;
+	}
+};
 } // namespace fpt
 
 struct fpt_context
@@ -196,8 +227,8 @@ struct fpt_context
 		uint32_t pending_first = 0, pending_n = 0;
 		long long* splat_ptr() { return splat_external ? splat_external : splat.ptr; }
 		fpt::DeviceArray<uint32_t> counters;
+		fpt::PassCounters cnt;                               // the call in progress's view of `counters` (its light and eye phases may be two calls apart)
 		fpt_bpt_stats stats{};
-		uint32_t ticket = 0;                                 // next ticket-dispenser group of the call in progress
 		// shared light vertices (fpt_bpt_set_shared_light_vertices): the call stops after the light sub-paths until fpt_bpt_finish
 		bool shared_lv = false, light_pending = false;
 		uint32_t light_instance = 0, light_passes = 0;
@@ -248,6 +279,9 @@ namespace fpt { const float4* ensure_vpl_points(fpt_context* ctx, const fpt_rend
 namespace fpt { const ShadeRecord* ensure_shade_records(fpt_context* ctx, const fpt_rendering_context_view* view, hipStream_t s); }
 // the view of the contribution log for the pixel range that starts at `first` of the rank's pixel list (fpt_api.cpp)
 namespace fpt { ContribLog lane_log(fpt_context* ctx, uint32_t first); }
+// where the samples of a PT / PSFPT pass go: the frame itself, or (`batched`: passes in flight) the albedo planes and the contribution log of the pixel
+// range that starts at `first` (fpt_api.cpp)
+namespace fpt { void sample_targets(fpt_context* ctx, const FrameBufferDev& real_fb, bool batched, uint32_t first, FrameBufferDev& fb, ContribLog& log); }
 // BPT, shared light vertices (fpt_bpt_api.cpp): this rank's vertices of the batch in flight -> ctx->bpt.lv_send (returns their number); wire records -> the store
 namespace fpt { uint32_t bpt_pack_own_vertices(fpt_context* ctx); void bpt_import_vertices(fpt_context* ctx, const LightVertexWire* d_records, uint32_t count); }
 
@@ -255,13 +289,6 @@ namespace fpt { uint32_t bpt_pack_own_vertices(fpt_context* ctx); void bpt_impor
 extern "C" int fpt_internal_set_batch(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_context_view* view, bool for_psfpt);
 
 // ---- helpers shared by the C-ABI translation units (fpt_api.cpp, fpt_bpt_api.cpp) -------------------------------------------------
-// counters block layout (uint32): trace ticket dispensers (8 shards, 128 B apart, x <= 3 launches per bounce x L <= 31), then queue sizes
-// queue-size counters are per bounce (a fresh, pre-zeroed word for every queue of every bounce), so ONE memset per pass replaces
-// the reference's two cudaMemsets per bounce (src/pathtracer_kernels.h:348-350)
-enum { TICKET_STRIDE = 8 * 32, CNT_MAX_LAUNCHES = 96, CNT_TICKETS = 0, CNT_QUEUES = TICKET_STRIDE * CNT_MAX_LAUNCHES, CNT_PER_BOUNCE = 96,
-       CNT_PATH = 0, CNT_SHADOW_DIR = 32, CNT_SHADOW = 64,            // offsets inside a bounce's group: each on its own 128-byte line
-       CNT_TOTAL = CNT_QUEUES + CNT_PER_BOUNCE * 34 };
-
 template <typename F>
 inline int guarded(fpt_context* ctx, F&& f)
 {
@@ -280,16 +307,17 @@ inline fpt::FrameBufferDev fb_dev(const fpt_framebuffer_view& v)
 	return f;
 }
 
-inline void require(bool cond, const char* msg) { if (!cond) throw std::runtime_error(msg); }
 inline double wall_seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // fpt_build_lbvh.hip: the device-side builds (Morton radix tree [mode 2: restructured by treelets] -> SAH-optimal 8-wide collapse); mode = fpt_rt_set_build_mode's 1 or 2;
 // false = the tree needs more stack than the kernel has: use the host builder
 namespace fpt { bool build_acceleration_device(fpt_context* ctx, uint32_t tri_count, const int32_t* d_idx, uint32_t vertex_count, const float* d_vtx, uint32_t stack_limit, uint32_t mode); }
 
-// asynchronous launch timing (fpt_pt_set_profiling level 2) for the renderers that have no synchronous profiling mode of their own
-// (BPT, PSFPT): bucket 0 = closest-hit traversal, 2 = any-hit traversal, 3 = shading-side kernels; read with fpt_pt_collect_timings
+// launch timing.  Profiling level 2 (fpt_pt_set_profiling): events are recorded around the launch on its stream and read back after the timed region
+// (fpt_pt_collect_timings, fpt_pt_launch_list), so measuring costs no host synchronisation.  Level 1, for a caller that passes `t_ms` (the PT's stats):
+// the launch is timed synchronously and its time added to t_ms[bucket].  Buckets: 0 = closest-hit traversal (the PT: its primary
+// rays), 1 = the PT's MIXED launches, 2 = any-hit traversal, 3 = shading-side kernels
 template <typename F>
-inline void timed_launch(fpt_context* ctx, int bucket, hipStream_t s, F&& launch)
+inline void timed_launch(fpt_context* ctx, int bucket, hipStream_t s, F&& launch, float* t_ms = nullptr)
 {
 	if (ctx->profiling_level == 2 && ctx->ev_cursor + 2 <= ctx->ev_pool.size())
 	{
@@ -298,17 +326,47 @@ inline void timed_launch(fpt_context* ctx, int bucket, hipStream_t s, F&& launch
 		launch();
 		FPT_HIP_CHECK(hipEventRecord(ctx->ev_pool[e1], s));
 		ctx->timed_launches.push_back(fpt_context::TimedLaunch{ bucket, e0, e1 });
+		return;
 	}
-	else launch();
+	const bool sync_timed = t_ms && ctx->profiling;
+	if (sync_timed) FPT_HIP_CHECK(hipEventRecord(ctx->ev[0], s));
+	launch();
+	if (sync_timed)
+	{
+		FPT_HIP_CHECK(hipEventRecord(ctx->ev[1], s)); FPT_HIP_CHECK(hipEventSynchronize(ctx->ev[1]));
+		float ms = 0; FPT_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1])); t_ms[bucket] += ms;
+	}
 }
 
-inline fpt::TraceParams base_trace_params(fpt_context* ctx)
+// the parameters of one traversal launch: the context's tree, the next ticket area of `cnt`, the trace statistics; the caller adds rays and queues
+inline fpt::TraceParams trace_params(fpt_context* ctx, fpt::PassCounters& cnt)
 {
 	fpt::TraceParams p; std::memset(&p, 0, sizeof(p));
 	p.bvh.nodes = reinterpret_cast<const uint4*>(ctx->d_nodes.ptr);
 	p.bvh.tris = reinterpret_cast<const float4*>(ctx->d_tris.ptr);
-	p.n_nodes = uint32_t(ctx->host_bvh.nodes8.size());
+	p.n_nodes = ctx->host_bvh.device_nodes;
+	p.work_counter = cnt.ticket();
+	p.stats = ctx->d_trace_stats.ptr;
 	return p;
+}
+
+// the emitter tables as the kernels see them; `use_vpls` = NEE draws from the VPLs (their tabulated light points, vpl_points, are the caller's to add)
+inline fpt::EmitterView emitter_view(fpt_context* ctx, bool use_vpls)
+{
+	fpt::EmitterView em; std::memset(&em, 0, sizeof(em));
+	em.n_prims = uint32_t(ctx->emitters.mesh_cdf.size()); em.prims_cdf = ctx->d_mesh_cdf.ptr; em.prims_inv_area = ctx->d_mesh_inv_area.ptr;
+	em.n_vpls = use_vpls ? uint32_t(ctx->emitters.vpls.size()) : 0u; em.vpls = use_vpls ? ctx->d_vpls.ptr : nullptr; em.norm = ctx->emitters.norm;
+	return em;
+}
+
+// compute_per_bounce_options (src/pathtracer_core.h:594-620): what the PT / PSFPT vertices of bounce sh.bounce do; `n_vpls` = the VPL set's size
+inline void per_bounce_options(fpt::ShadeParams& sh, const fpt_pt_options& opt, uint32_t n_vpls)
+{
+	const uint32_t bounce = sh.bounce;
+	sh.do_nee = (n_vpls && (bounce + 2 <= opt.max_path_length) && ((bounce == 0 && opt.direct_lighting_nee && opt.direct_lighting) || (bounce > 0 && opt.indirect_lighting_nee))) ? 1u : 0u;
+	sh.do_emissive = ((bounce == 0 && opt.visible_lights) || (bounce == 1 && opt.direct_lighting_bsdf && opt.direct_lighting) || (bounce > 1 && opt.indirect_lighting_bsdf)) ? 1u : 0u;
+	const uint32_t max_path_vertices = opt.max_path_length + (((opt.max_path_length == 2 && opt.direct_lighting_bsdf) || (opt.max_path_length > 2 && opt.indirect_lighting_bsdf)) ? 1u : 0u);
+	sh.do_scatter = (bounce + 2 < max_path_vertices) ? 1u : 0u;
 }
 
 // camera_frame (src/camera.h:141-171) — host code, libm tanf as in the reference's host path
@@ -325,4 +383,36 @@ inline void camera_frame(const fpt_camera& c, float aspect, fpt::f3& U, fpt::f3&
 	V = mk3(V.x * vlen, V.y * vlen, V.z * vlen);
 }
 
+// generate_primary_rays' parameters (src/pathtracer_kernels.h:166-181) for the PT / PSFPT: `n_pixels` pixels of `pixels` (NULL = the identity) into `out`
+inline fpt::PrimaryParams primary_params(const fpt_rendering_context_view* view, const fpt::SequenceView& seq, const uint32_t* pixels, uint32_t n_pixels,
+                                         const fpt::PassInfo& pass, const fpt::PathQueue& out)
+{
+	using namespace fpt;
+	PrimaryParams pp;
+	pp.out = out; pp.seq = seq; pp.pixels = pixels; pp.n_pixels = n_pixels; pp.res_x = view->res_x; pp.res_y = view->res_y; pp.pass = pass;
+	pp.eye = mk3(view->camera.eye[0], view->camera.eye[1], view->camera.eye[2]);
+	camera_frame(view->camera, view->aspect, pp.U, pp.V, pp.W);
+	pp.W_len = length(pp.W);
+	const float tn = tanf(view->camera.fov / 2);
+	pp.sq_focal = (float(view->res_x * view->res_y) / 4.0f) / (tn * tn);        // Camera::square_pixel_focal_length, src/camera.h:120-128
+	return pp;
+}
 
+// passes in flight: the two albedo channels keep a plane per pass (one term per pass and pixel); every other channel is NULL, its samples go to the log
+inline fpt::FrameBufferDev plane_view(const fpt::FrameBufferDev& real, float4* diffuse_a, float4* specular_a)
+{
+	fpt::FrameBufferDev fb = real;
+	for (int c = 0; c < 6; ++c) fb.ch[c] = nullptr;
+	fb.ch[FPT_FB_DIFFUSE_A] = diffuse_a; fb.ch[FPT_FB_SPECULAR_A] = specular_a;
+	return fb;
+}
+
+// the per-bounce blocks a fused resolve reads behind one pointer: uploaded -- which synchronises the stream -- only when they differ from what the device
+// holds (`held`), so that consecutive render calls stay asynchronous
+template <typename T>
+inline void upload_if_changed(fpt::DeviceArray<T>& d, std::vector<T>& held, const std::vector<T>& blocks, hipStream_t s)
+{
+	if (held.size() == blocks.size() && std::memcmp(held.data(), blocks.data(), blocks.size() * sizeof(T)) == 0) return;
+	d.upload(blocks.data(), blocks.size(), s);
+	held = blocks;
+}

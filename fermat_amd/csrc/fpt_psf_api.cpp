@@ -9,11 +9,6 @@
 using namespace fpt;
 
 namespace {
-enum { P_TICKET_STRIDE = 8 * 32, P_MAX_LAUNCHES = 4 * 34, P_QUEUES = P_TICKET_STRIDE * P_MAX_LAUNCHES, P_PER_BOUNCE = 96, P_PATH = 0, P_SHADOW_DIR = 32, P_SHADOW = 64,
-       P_TOTAL = P_QUEUES + P_PER_BOUNCE * 34 };
-}
-
-namespace {
 // the cache as the kernels of a SHARDED context see it: pass table in keys / cells, global table in g_keys / g_cells
 PsfDev sharded_view(fpt_context* ctx)
 {
@@ -25,6 +20,14 @@ PsfDev sharded_view(fpt_context* ctx)
 	psf.depth = ps.opt.psf_depth; psf.width = ps.opt.psf_width; psf.max_prob = ps.opt.psf_max_prob; psf.firefly = ps.opt.firefly_filter;
 	return psf;
 }
+// the cache as the vertices and references of bounce `bounce` see it: that bounce's part of the reference queue (`n` entries per bounce)
+PsfDev at_bounce(const PsfDev& psf, uint32_t bounce, uint32_t n)
+{
+	PsfDev pb = psf;
+	pb.ref_pixels = psf.ref_pixels + size_t(bounce) * n; pb.ref_cache = psf.ref_cache + size_t(bounce) * n; pb.ref_k = psf.ref_k + size_t(bounce) * n;
+	pb.ref_wd = psf.ref_wd + size_t(bounce) * n; pb.ref_wg = psf.ref_wg + size_t(bounce) * n; pb.ref_size = psf.ref_size + bounce;
+	return pb;
+}
 // psf_blending, update_variances, clamp_frame(100): the tail of PSFPT::render (src/renderers/psfpt_impl.h:275-284, 402-420)
 void finish_pass(fpt_context* ctx, const PsfDev& psf, const FrameBufferDev& fb, uint32_t instance, uint32_t bounces_run)
 {
@@ -32,13 +35,7 @@ void finish_pass(fpt_context* ctx, const PsfDev& psf, const FrameBufferDev& fb, 
 	hipStream_t s = ctx->stream;
 	const uint32_t n = ctx->n_local;
 	const float frame_weight = 1.0f / float(instance + 1);
-	for (uint32_t bounce = ps.opt.psf_depth; bounce < bounces_run; ++bounce)
-	{
-		PsfDev pb = psf;
-		pb.ref_pixels = psf.ref_pixels + size_t(bounce) * n; pb.ref_cache = psf.ref_cache + size_t(bounce) * n; pb.ref_k = psf.ref_k + size_t(bounce) * n;
-		pb.ref_wd = psf.ref_wd + size_t(bounce) * n; pb.ref_wg = psf.ref_wg + size_t(bounce) * n; pb.ref_size = psf.ref_size + bounce;
-		launch_psf_blend(pb, fb, frame_weight, n, s);
-	}
+	for (uint32_t bounce = ps.opt.psf_depth; bounce < bounces_run; ++bounce) launch_psf_blend(at_bounce(psf, bounce, n), fb, frame_weight, n, s);
 	launch_variance(fb, ctx->d_pixels, n, instance + 1, s);
 	launch_clamp_frame(fb, ctx->d_pixels, n, 100.0f, s);
 	FPT_HIP_CHECK(hipGetLastError());
@@ -84,7 +81,6 @@ int fpt_psfpt_init(fpt_context* ctx, const fpt_pt_options* opts, const fpt_psf_o
 			lo[c] = lo[c] < v ? lo[c] : v; hi[c] = hi[c] > v ? hi[c] : v;
 		}
 		for (int c = 0; c < 3; ++c) { s.bbox[c] = lo[c]; s.bbox[3 + c] = hi[c]; }
-		ctx->d_counters.alloc(std::max<size_t>(ctx->d_counters.count, size_t(P_TOTAL)));
 		s.ready = true;
 	});
 }
@@ -131,20 +127,12 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 		hipStream_t s = ctx->stream;
 		const fpt_pt_options& opt = ctx->opt;
 		const FrameBufferDev real_fb = fb_dev(view->fb);
-		FrameBufferDev fb = real_fb;
-		ContribLog log; std::memset(&log, 0, sizeof(log));
-		if (batched)
-		{
-			// as in the path tracer (fpt_api.cpp render_lane): the albedo channels keep a plane per pass, every other sample goes to the path's cell of the log
-			for (int c = 0; c < 6; ++c) fb.ch[c] = nullptr;
-			fb.ch[FPT_FB_DIFFUSE_A] = reinterpret_cast<float4*>(ctx->d_acc[FPT_FB_DIFFUSE_A].ptr);
-			fb.ch[FPT_FB_SPECULAR_A] = reinterpret_cast<float4*>(ctx->d_acc[FPT_FB_SPECULAR_A].ptr);
-			log = lane_log(ctx, 0);
-		}
+		FrameBufferDev fb; ContribLog log;
+		sample_targets(ctx, real_fb, batched, 0, fb, log);
 		const uint32_t n = ctx->n_local * n_passes;          // paths of the launch chain
-		uint32_t* cnt = ctx->d_counters.ptr;
 		if (!batched) launch_rescale(fb, ctx->d_pixels, n, float(instance) / float(instance + 1), s);
-		FPT_HIP_CHECK(hipMemsetAsync(cnt, 0, P_TOTAL * sizeof(uint32_t), s));
+		FPT_HIP_CHECK(hipMemsetAsync(ctx->d_counters.ptr, 0, CNT_TOTAL * sizeof(uint32_t), s));
+		PassCounters cnt{ ctx->d_counters.ptr };
 		auto reset_cache = [&] {          // initialize the shading cache (src/renderers/psfpt_impl.h:385-387)
 			FPT_HIP_CHECK(hipMemsetAsync(ps.keys.ptr, 0xFF, (size_t(1) << ps.log2_size) * sizeof(unsigned long long), s));
 			FPT_HIP_CHECK(hipMemsetAsync(ps.cells.ptr, 0, (size_t(1) << ps.log2_size) * 4 * sizeof(long long), s));
@@ -175,37 +163,23 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 			psf.touched = ps.b_touched.ptr; psf.touched_n = ps.b_touched_n.ptr; psf.log2_size = ps.b_log2; psf.pass_stride = 1u << ps.b_log2;
 		}
 
-		auto counter = [&](uint32_t bounce, uint32_t which) { return cnt + P_QUEUES + P_PER_BOUNCE * bounce + which; };
-		uint32_t ticket = 0;
 		// the rays are those of the renderer's own queues (fpt_device.h PathQueue / ShadowQueue): the .w words carry PixelInfo / pass offset, the intervals are the queues'
 		auto trace = [&](const float4* rays, float4* hits, const uint32_t* count_ptr, bool any_hit, bool primary = false)
 		{
-			TraceParams tp = base_trace_params(ctx);
-			tp.rays = rays; tp.hits = hits; tp.count_ptr = count_ptr; tp.work_counter = cnt + P_TICKET_STRIDE * (ticket++); tp.stats = ctx->d_trace_stats.ptr;
+			TraceParams tp = trace_params(ctx, cnt);
+			tp.rays = rays; tp.hits = hits; tp.count_ptr = count_ptr;
 			if (any_hit) timed_launch(ctx, 2, s, [&] { launch_trace_shadow_queue(tp, ctx->counting, ctx->trace_blocks(), s); });
 			else         timed_launch(ctx, 0, s, [&] { launch_trace_closest_queue(tp, primary, ctx->counting, ctx->trace_blocks(), s); });
 		};
 		QueueStorage* qa = &ctx->q_a; QueueStorage* qb = &ctx->q_b;
-		PathQueue qin = qa->view(counter(0, P_PATH)), qout = qb->view(counter(1, P_PATH));
-		{
-			PrimaryParams pp;
-			pp.out = qin; pp.seq = seq; pp.pixels = ctx->d_pixels; pp.n_pixels = ctx->n_local; pp.res_x = view->res_x; pp.res_y = view->res_y; pp.pass = pass;
-			pp.eye = mk3(view->camera.eye[0], view->camera.eye[1], view->camera.eye[2]);
-			camera_frame(view->camera, view->aspect, pp.U, pp.V, pp.W);
-			pp.W_len = length(pp.W);
-			const float tn = tanf(view->camera.fov / 2);
-			pp.sq_focal = (float(view->res_x * view->res_y) / 4.0f) / (tn * tn);
-			launch_primary_rays(pp, s);
-		}
+		PathQueue qin = qa->view(cnt.queue(0, CNT_PATH)), qout = qb->view(cnt.queue(1, CNT_PATH));
+		launch_primary_rays(primary_params(view, seq, ctx->d_pixels, ctx->n_local, pass, qin), s);
 		ShadeParams sh; std::memset(&sh, 0, sizeof(sh));
 		sh.seq = seq; sh.shade_records = ensure_shade_records(ctx, view, s); sh.mesh = view->mesh; sh.textures = view->d_textures; sh.table = view->d_glossy_reflectance;
 		sh.dir_lights = view->d_dir_lights; sh.n_dir_lights = view->dir_lights_count;
-		EmitterView em;
-		em.n_prims = uint32_t(ctx->emitters.mesh_cdf.size()); em.prims_cdf = ctx->d_mesh_cdf.ptr; em.prims_inv_area = ctx->d_mesh_inv_area.ptr;
-		em.n_vpls = opt.nee_type == 1 ? uint32_t(ctx->emitters.vpls.size()) : 0u; em.vpls = opt.nee_type == 1 ? ctx->d_vpls.ptr : nullptr; em.norm = ctx->emitters.norm;
-		em.vpl_points = opt.nee_type == 1 ? ensure_vpl_points(ctx, view, s) : nullptr;
-		sh.emitters = em; sh.fb = fb; sh.log = log; sh.gbuffer = real_fb; sh.opt = opt; sh.res_x = view->res_x; sh.res_y = view->res_y; sh.pass = pass; sh.psf = psf;
-		const uint32_t total_vpls = uint32_t(ctx->emitters.vpls.size());
+		sh.emitters = emitter_view(ctx, opt.nee_type == 1);
+		sh.emitters.vpl_points = opt.nee_type == 1 ? ensure_vpl_points(ctx, view, s) : nullptr;
+		sh.fb = fb; sh.log = log; sh.gbuffer = real_fb; sh.opt = opt; sh.res_x = view->res_x; sh.res_y = view->res_y; sh.pass = pass; sh.psf = psf;
 		const float frame_weight = 1.0f / float(instance + 1);
 
 		// what the fused resolve of a MIXED launch needs, one block per bounce; nothing in it changes from pass to pass (the frame weight
@@ -219,25 +193,17 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 				r.q = ctx->q_shadow.view(nullptr); r.fb = fb; r.bounce = b; r.psf = psf; r.psf.instance = 0; r.log = log; r.kind = 1;
 				r.pass = pass; r.pass.base_instance = 0;          // the launch's first instance travels as a kernel argument
 			}
-			if (ps.h_resolve.size() != blocks.size() || std::memcmp(ps.h_resolve.data(), blocks.data(), blocks.size() * sizeof(ResolveParams)) != 0)
-			{
-				ps.d_resolve.upload(blocks.data(), blocks.size(), s);
-				ps.h_resolve = blocks;
-			}
+			upload_if_changed(ps.d_resolve, ps.h_resolve, blocks, s);
 		}
 		uint32_t bounces_run = 0;
 		trace(qin.rays, qin.hits, qin.size, false, true);
 		for (uint32_t bounce = 0; bounce < opt.max_path_length; ++bounce)
 		{
 			sh.bounce = bounce;
-			sh.do_nee = (total_vpls && (bounce + 2 <= opt.max_path_length) && ((bounce == 0 && opt.direct_lighting_nee && opt.direct_lighting) || (bounce > 0 && opt.indirect_lighting_nee))) ? 1u : 0u;
-			sh.do_emissive = ((bounce == 0 && opt.visible_lights) || (bounce == 1 && opt.direct_lighting_bsdf && opt.direct_lighting) || (bounce > 1 && opt.indirect_lighting_bsdf)) ? 1u : 0u;
-			const uint32_t max_path_vertices = opt.max_path_length + (((opt.max_path_length == 2 && opt.direct_lighting_bsdf) || (opt.max_path_length > 2 && opt.indirect_lighting_bsdf)) ? 1u : 0u);
-			sh.do_scatter = (bounce + 2 < max_path_vertices) ? 1u : 0u;
-			ShadowQueue qsd = ctx->q_shadow_dir.view(counter(bounce, P_SHADOW_DIR)), qs = ctx->q_shadow.view(counter(bounce, P_SHADOW));
+			per_bounce_options(sh, opt, uint32_t(ctx->emitters.vpls.size()));
+			ShadowQueue qsd = ctx->q_shadow_dir.view(cnt.queue(bounce, CNT_SHADOW_DIR)), qs = ctx->q_shadow.view(cnt.queue(bounce, CNT_SHADOW));
 			sh.in = qin; sh.scatter = qout; sh.shadow_dir = qsd; sh.shadow = qs;
-			sh.psf.ref_pixels = psf.ref_pixels + size_t(bounce) * n; sh.psf.ref_cache = psf.ref_cache + size_t(bounce) * n; sh.psf.ref_k = psf.ref_k + size_t(bounce) * n;
-			sh.psf.ref_wd = psf.ref_wd + size_t(bounce) * n; sh.psf.ref_wg = psf.ref_wg + size_t(bounce) * n; sh.psf.ref_size = psf.ref_size + bounce;
+			sh.psf = at_bounce(psf, bounce, n);
 			timed_launch(ctx, 3, s, [&] { launch_shade_psf(sh, n, s); });
 			++bounces_run;
 			ResolveParams rp; std::memset(&rp, 0, sizeof(rp));
@@ -252,8 +218,8 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 			{
 				// MIXED launch as in the path tracer: the closest-hit rays of the next bounce together with this bounce's shadow rays, whose
 				// cache-aware resolve (PSFPTVertexProcessor::accumulate_nee) is fused into the retirement of the any-hit lanes
-				TraceParams mp = base_trace_params(ctx);
-				mp.rays = qout.rays; mp.hits = qout.hits; mp.count_ptr = qout.size; mp.work_counter = cnt + P_TICKET_STRIDE * (ticket++); mp.stats = ctx->d_trace_stats.ptr;
+				TraceParams mp = trace_params(ctx, cnt);
+				mp.rays = qout.rays; mp.hits = qout.hits; mp.count_ptr = qout.size;
 				mp.shadow_rays = qs.rays; mp.shadow_size = qs.size; mp.base_instance = instance;
 				mp.fused = reinterpret_cast<const FusedResolve*>(ps.d_resolve.ptr + bounce);      // MIXED_PSF reads a ResolveParams there
 				timed_launch(ctx, 0, s, [&] { launch_trace_mixed_psf(mp, ctx->counting, ctx->trace_blocks(), s); });
@@ -271,7 +237,7 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 			}
 			if (!sh.do_scatter) break;
 			std::swap(qa, qb);
-			qin = qa->view(counter(bounce + 1, P_PATH)); qout = qb->view(counter(bounce + 2, P_PATH));
+			qin = qa->view(cnt.queue(bounce + 1, CNT_PATH)); qout = qb->view(cnt.queue(bounce + 2, CNT_PATH));
 		}
 		if (ps.sharded)
 		{
@@ -289,13 +255,7 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 				if (((instance + k) % ps.opt.psf_temporal_reuse) == 0) reset_cache();
 				launch_psf_prefix(psf, k, s);
 			}
-			for (uint32_t bounce = ps.opt.psf_depth; bounce < bounces_run; ++bounce)
-			{
-				PsfDev pb = psf;
-				pb.ref_pixels = psf.ref_pixels + size_t(bounce) * n; pb.ref_cache = psf.ref_cache + size_t(bounce) * n; pb.ref_k = psf.ref_k + size_t(bounce) * n;
-				pb.ref_wd = psf.ref_wd + size_t(bounce) * n; pb.ref_wg = psf.ref_wg + size_t(bounce) * n; pb.ref_size = psf.ref_size + bounce;
-				launch_psf_blend_batch(pb, log, bounce, pass, n, s);
-			}
+			for (uint32_t bounce = ps.opt.psf_depth; bounce < bounces_run; ++bounce) launch_psf_blend_batch(at_bounce(psf, bounce, n), log, bounce, pass, n, s);
 			// rescale -> albedos -> the pass's samples in order -> its blends bounce by bounce -> variances -> clamp_frame(100), pass by pass: the sequential frame
 			launch_merge_passes_exact(real_fb, fb.ch[FPT_FB_DIFFUSE_A], fb.ch[FPT_FB_SPECULAR_A], log, ctx->d_pixels, ctx->n_local, pass, s, true, ps.opt.firefly_filter, 100.0f);
 			for (uint32_t k = 0; k < n_passes; ++k)
