@@ -97,6 +97,11 @@ __device__ __forceinline__ void log_mark(const ContribLog& g, uint32_t pidx, uin
 	uint32_t* m = g.mask + size_t(pidx) * g.mask_words + (bit >> 5);      // the word belongs to this path alone, and a path has one writer per launch
 	*m |= 1u << (bit & 31u);
 }
+// One field of a launch-constant parameter block behind a kernel-argument pointer, read through the constant address space: the address is uniform and the block is
+// written by the host before the launch only, so the field arrives by a scalar load in SGPRs -- through the generic pointer a kernel that also stores to memory gets
+// a vector load + v_readfirstlane + a full vmcnt wait per field
+template <typename T>
+__device__ __forceinline__ T load_launch_constant(const T* field) { return *(const __attribute__((address_space(4))) T*)(uintptr_t)field; }
 
 // PTVertexProcessor::accumulate_emissive (src/pathtracer_vertex_processor.h:151-183) on registers / on the frame
 template <typename ADD>
@@ -208,6 +213,34 @@ struct TraceParams
 	uint32_t        base_instance; // first pass of the call: overrides fused->pass.base_instance, so that the blocks behind `fused` do not change from call to call
 };
 struct FusedResolve { const float4* w_d; const float4* w_g; FrameBufferDev fb; PassInfo pass; uint32_t bounce; ContribLog log; uint32_t kind; };      // (PixelInfo and the pass offset ride in the shadow entry: ShadowQueue)
+
+// accumulate_nee for the traversal kernel's fused resolve, on the FusedResolve block itself: the same cells and the same arithmetic, but the block's fields come by
+// scalar loads as they are needed (load_launch_constant; a copy of the block would sit in scratch), so the sample's own three loads -- w_d, w_g, PixelInfo -- are the
+// only round trip, and the mask bit is set by an atomic OR whose result nobody reads: one instruction nothing waits for instead of load - wait - OR - store (the word
+// still has one writer).  The log's cell index stays 64-bit where bounce * cap can pass 2^32; the path index k * acc_stride + slot is bounded by the batch (< 2^32)
+struct FrameAddLaunchConstant      // FrameAdd through the block
+{
+	const FrameBufferDev* fb; uint32_t pixel; float w;
+	__device__ __forceinline__ void operator()(int c, bool variance, f3 f) const
+	{
+		float4* ch = load_launch_constant(&fb->ch[c]);
+		if (variance) fb_add<true>(ch, pixel, f, w); else fb_add<false>(ch, pixel, f, w);
+	}
+};
+__device__ __forceinline__ void accumulate_nee_fused(const FusedResolve* F, uint32_t base_instance, uint32_t pixel_info, float4 wd, float4 wg)
+{
+	const uint32_t n_passes = load_launch_constant(&F->pass.n_passes), bounce = load_launch_constant(&F->bounce);
+	const uint32_t v = pixel_info & 0x7FFFFFFu, comp = (pixel_info >> 27) & 0xFu;
+	const f3 w_d = mk3(wd.x, wd.y, wd.z), w_g = mk3(wg.x, wg.y, wg.z);
+	if (n_passes == 1) { apply_nee(FrameAddLaunchConstant{ &F->fb, v, 1.0f / float(base_instance + 1u) }, bounce, comp, w_d, w_g); return; }      // decode_slot: k = 0, pixel = the field
+	const uint32_t kind = load_launch_constant(&F->kind);
+	const uint32_t pidx = as_u32(wd.w) * load_launch_constant(&F->pass.acc_stride) + v;          // w_d.w = pass offset k
+	float4* cell = load_launch_constant(&F->log.nee[kind]) + (size_t(bounce) * load_launch_constant(&F->log.cap) + pidx) * 2;
+	cell[0] = make_float4(w_d.x, w_d.y, w_d.z, as_f32(comp));
+	cell[1] = make_float4(w_g.x, w_g.y, w_g.z, 0.0f);
+	const uint32_t bit = 3u * bounce + 1u + kind;
+	__hip_atomic_fetch_or(load_launch_constant(&F->log.mask) + size_t(pidx) * load_launch_constant(&F->log.mask_words) + (bit >> 5), 1u << (bit & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 uint32_t trace_blocks_per_cu();
 uint32_t trace_stack_entries();      // capacity of the traversal stack (LDS + scratch levels); fpt_rt_create_geometry checks the tree's bound against it

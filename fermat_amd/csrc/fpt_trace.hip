@@ -24,7 +24,11 @@
 //     (src/kernels/optix_payload.h:75-78); any-hit honours the per-triangle shadow mask (optix_base_shadow_shaders.h:54-59): results
 //     are independent of the tree and of the traversal order, bit for bit;
 //   * MIXED mode: one launch serves the closest-hit rays of bounce b+1 AND the shadow rays of bounce b (fused with
-//     solve_occlusion).  A launch cannot end before its longest ray, so halving the number of launches per pass halves those tails.
+//     solve_occlusion).  A launch cannot end before its longest ray, so halving the number of launches per pass halves those tails;
+//   * the traversal burst holds the node step, the triangle test and the stack only.  A finished ray leaves it with its result in registers, and one retire
+//     block per refill writes the hit records, the any-hit results and the fused resolves of all the lanes that finished since the last one: inside the burst the
+//     whole wave entered those blocks -- 200 VALU + 130 SALU instructions and, for an unoccluded shadow ray, five dependent memory waits -- whenever ONE lane
+//     finished, which is nearly every iteration (round 8: -7 % traversal time; tests/test_trace_retire_isa.py keeps the burst free of other memory traffic).
 // No MFMA: a pointer chase, not a contraction.
 #include "fpt_device.h"
 #include "fpt_bvh.h"
@@ -240,6 +244,53 @@ void trace_kernel(const TraceParams P)
 
 	for (;;)
 	{
+		// ---- retire: write the results of the lanes whose rays finished since the last refill (sp < 0).  The burst leaves its loop when REFILL_MIN lanes are idle (once
+		//      the tickets are dry: when the wave is empty), so this block runs once per refill with 16-64 live lanes -- inside the burst it ran for the one to three
+		//      lanes that finish in an iteration, with the whole wave waiting.  It comes before the refill, which reuses the lane's registers, and before the exit test
+		//      below, so the last rays of a wave are written too.  One writer per cell holds as before: a path has at most one sample of a kind per launch ----
+		if (sp < 0)
+		{
+			if (any)
+			{
+				if (MODE == MODE_MIXED_PSF)
+				{
+					// PSFPTVertexProcessor::accumulate_nee fused: the sample goes to its cache cell and / or the frame
+					if (!occluded) psf_resolve_sample(*reinterpret_cast<const ResolveParams*>(P.fused), P.base_instance, ray_index);
+				}
+				else if (MODE == MODE_MIXED_HITS)
+				{
+					float4* shadow_hits = reinterpret_cast<float4*>(const_cast<FusedResolve*>(P.fused));
+					shadow_hits[ray_index] = occluded ? make_float4(1.0f, as_f32(1u), 0.0f, 0.0f) : make_float4(-1.0f, as_f32(0xFFFFFFFFu), 0.0f, 0.0f);
+				}
+				else if (MODE == MODE_ANY_FUSED || MODE == MODE_MIXED)
+				{
+					// solve_occlusion (src/pathtracer_kernels.h:248-280) fused: accumulate the light sample when unoccluded
+					if (!occluded)
+					{
+						const FusedResolve* F = P.fused;
+						const float4 wd = load_launch_constant(&F->w_d)[ray_index], wg = load_launch_constant(&F->w_g)[ray_index];
+						const uint32_t pixel_info = as_u32(P.shadow_rays[2 * size_t(ray_index) + 1].w);          // ShadowQueue: dir | PixelInfo, w_d.w = pass offset
+						accumulate_nee_fused(F, P.base_instance, pixel_info, wd, wg);
+					}
+				}
+				else
+				{
+					if (P.hits) P.hits[ray_index] = occluded ? make_float4(1.0f, as_f32(1u), 0.0f, 0.0f) : make_float4(-1.0f, as_f32(0xFFFFFFFFu), 0.0f, 0.0f);
+					if (P.bits && occluded) atomicOr(P.bits + (ray_index >> 5), 1u << (ray_index & 31u));
+				}
+			}
+			else
+			{
+				float4 h = make_float4(-1.0f, as_f32(0xFFFFFFFFu), 0.0f, 0.0f);
+				if (best_id >= 0)
+				{
+					const float u = 1.0f - best_bu - best_bv;        // weight of vertex 0 (optix_base_shaders.h:50-57)
+					h = make_float4(best_t, as_f32(uint32_t(best_id)), round_through_half(u), round_through_half(best_bu));
+				}
+				P.hits[ray_index] = h;
+			}
+			sp = 0;
+		}
 		// ---- refill idle lanes from the wave's current chunk ----
 		const unsigned long long idle = __ballot(!have);
 		const int n_idle = __popcll(idle);
@@ -382,51 +433,9 @@ void trace_kernel(const TraceParams P)
 						else if (!(tri_bits & 0xFFFFu)) { tri_base = e.x; tri_bits = e.y; sp--; }
 					}
 				}
-				if (!alive)
-				{
-					// ---- retire the ray ----
-					if (any)
-					{
-						if (MODE == MODE_MIXED_PSF)
-						{
-							// PSFPTVertexProcessor::accumulate_nee fused: the sample goes to its cache cell and / or the frame
-							if (!occluded) psf_resolve_sample(*reinterpret_cast<const ResolveParams*>(P.fused), P.base_instance, ray_index);
-						}
-						else if (MODE == MODE_MIXED_HITS)
-						{
-							float4* shadow_hits = reinterpret_cast<float4*>(const_cast<FusedResolve*>(P.fused));
-							shadow_hits[ray_index] = occluded ? make_float4(1.0f, as_f32(1u), 0.0f, 0.0f) : make_float4(-1.0f, as_f32(0xFFFFFFFFu), 0.0f, 0.0f);
-						}
-						else if (MODE == MODE_ANY_FUSED || MODE == MODE_MIXED)
-						{
-							// solve_occlusion (src/pathtracer_kernels.h:248-280) fused: accumulate the light sample when unoccluded
-							if (!occluded)
-							{
-								const FusedResolve* F = P.fused;
-								const float4 wd = F->w_d[ray_index], wg = F->w_g[ray_index];
-								const uint32_t pixel_info = as_u32(P.shadow_rays[2 * size_t(ray_index) + 1].w);          // ShadowQueue: dir | PixelInfo, w_d.w = pass offset
-								PassInfo ps = F->pass; ps.base_instance = P.base_instance;
-								accumulate_nee(F->fb, ps, F->log, F->kind, pixel_info, ps.n_passes > 1 ? as_u32(wd.w) : 0u, F->bounce, mk3(wd.x, wd.y, wd.z), mk3(wg.x, wg.y, wg.z));
-							}
-						}
-						else
-						{
-							if (P.hits) P.hits[ray_index] = occluded ? make_float4(1.0f, as_f32(1u), 0.0f, 0.0f) : make_float4(-1.0f, as_f32(0xFFFFFFFFu), 0.0f, 0.0f);
-							if (P.bits && occluded) atomicOr(P.bits + (ray_index >> 5), 1u << (ray_index & 31u));
-						}
-					}
-					else
-					{
-						float4 h = make_float4(-1.0f, as_f32(0xFFFFFFFFu), 0.0f, 0.0f);
-						if (best_id >= 0)
-						{
-							const float u = 1.0f - best_bu - best_bv;        // weight of vertex 0 (optix_base_shaders.h:50-57)
-							h = make_float4(best_t, as_f32(uint32_t(best_id)), round_through_half(u), round_through_half(best_bu));
-						}
-						P.hits[ray_index] = h;
-					}
-					have = false;
-				}
+				// a finished ray only leaves the burst: its result stays in the lane's registers (best_*, occluded, ray_index, any, which a lane without a ray no longer
+				// touches) and is written at the head of the next refill for all the lanes that finished since the last one; sp < 0 marks the lane
+				if (!alive) { have = false; sp = -1; }
 			}
 			// every lane of the wave reaches this point: decide (uniformly) whether to keep traversing or go refill
 			const int n_busy = __popcll(__ballot(have));
