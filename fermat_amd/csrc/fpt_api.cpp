@@ -88,14 +88,14 @@ int fpt_rt_create_geometry(fpt_context* ctx, uint32_t tri_count, const int32_t* 
 		// fast and trbvh modes (fpt_rt_set_build_mode(ctx, 1 | 2) or FPT_BVH_BUILD=fast|trbvh): the whole build on the device, the mesh stays where it is (fpt_build_lbvh.hip);
 		// a tree whose traversal-stack bound exceeds the kernel's stack -- degenerate inputs -- falls through to the host builder and its ladder of shallower trees
 		const char* env = std::getenv("FPT_BVH_BUILD");
-		const uint32_t mode = env ? (std::strcmp(env, "fast") == 0 ? 1u : std::strcmp(env, "trbvh") == 0 ? 2u : 0u) : ctx->build_mode;
+		const uint32_t mode = env ? (std::strcmp(env, "fast") == 0 ? 1u : std::strcmp(env, "trbvh") == 0 ? 2u : 0u) : ctx->tree.build_mode;
 		if (mode != 0u && tri_count >= 2)
 		{
 			require(d_idx && d_vtx, "fpt_rt_create_geometry: null mesh");
 			FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));          // launches still reading the old tree
 			if (build_acceleration_device(ctx, tri_count, d_idx, vertex_count, d_vtx, trace_stack_entries(), mode))
 			{
-				ctx->has_geometry = true; ctx->emitter_generation++;
+				ctx->emitter_generation++;
 				if (std::getenv("FPT_BVH_TIMERS")) std::fprintf(stderr, "fpt_rt_create_geometry: built on the device in %.3f ms\n", (wall_seconds() - t0) * 1e3);
 				return;
 			}
@@ -104,62 +104,38 @@ int fpt_rt_create_geometry(fpt_context* ctx, uint32_t tri_count, const int32_t* 
 		if (tri_count) FPT_HIP_CHECK(hipMemcpy(idx.data(), d_idx, idx.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
 		if (vertex_count) FPT_HIP_CHECK(hipMemcpy(vtx.data(), d_vtx, vtx.size() * sizeof(float), hipMemcpyDeviceToHost));
 		const double t1 = wall_seconds();
-		// binned-SAH BVH2, optimised by re-insertion, collapsed into the 8-wide compressed tree the kernels walk; shallower trees for degenerate inputs
-		build_acceleration(tri_count, idx.data(), vertex_count, vtx.data(), ctx->host_bvh, trace_stack_entries());
-		require(ctx->host_bvh.stack_need <= trace_stack_entries(), "fpt_rt_create_geometry: the BVH needs more traversal-stack entries than the kernel has");
+		// binned-SAH BVH2, optimised by re-insertion, collapsed into the 8-wide tree; into the workspace: whatever the builder throws, the context's tree is as it was
+		HostBvh& built = ctx->tree.host_build;
+		build_acceleration(tri_count, idx.data(), vertex_count, vtx.data(), built, trace_stack_entries());
+		require(built.info.stack_need <= trace_stack_entries(), "fpt_rt_create_geometry: the BVH needs more traversal-stack entries than the kernel has");
 		const double t2 = wall_seconds();
-		ctx->d_nodes.upload(ctx->host_bvh.nodes8.data(), ctx->host_bvh.nodes8.size(), ctx->stream);
-		ctx->d_tris.upload(ctx->host_bvh.tris8.data(), ctx->host_bvh.tris8.size(), ctx->stream);
-		ctx->host_bvh.device_nodes = uint32_t(ctx->host_bvh.nodes8.size()); ctx->host_bvh.device_records = uint32_t(ctx->host_bvh.tris8.size()); ctx->host_bvh.built_on_device = false;
-		ctx->has_geometry = true; ctx->emitter_generation++;          // new geometry: the VPLs' tabulated light points are stale
+		ctx->tree.replace(built.info, [&](BvhNode8* d_nodes, BvhTriangle* d_records) {
+			FPT_HIP_CHECK(hipMemcpyAsync(d_nodes, built.nodes8.data(), built.nodes8.size() * sizeof(BvhNode8), hipMemcpyHostToDevice, ctx->stream));
+			FPT_HIP_CHECK(hipMemcpyAsync(d_records, built.tris8.data(), built.tris8.size() * sizeof(BvhTriangle), hipMemcpyHostToDevice, ctx->stream));
+			FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream)); });
+		ctx->emitter_generation++;          // new geometry: the VPLs' tabulated light points are stale
 		if (std::getenv("FPT_BVH_TIMERS")) std::fprintf(stderr, "fpt_rt_create_geometry: mesh to the host %.3f s, build %.3f, tree to the device %.3f\n", t1 - t0, t2 - t1, wall_seconds() - t2);
 	});
 }
 // 0 = quality (default): the host builder; 1 = fast: the device builder -- what a host that rebuilds every frame (RenderingContext::update_model without refit) wants;
-// 2 = trbvh: the device builder with the radix tree restructured by treelets before the collapse
+// 2 = trbvh: the device builder with the radix tree restructured by treelets before the collapse.  Quality mode needs no device scratch: choosing it releases the
+// device builder's (none is in flight: a build returns only after its last read-back)
 int fpt_rt_set_build_mode(fpt_context* ctx, uint32_t mode)
-{ return guarded(ctx, [&] { require(mode <= 2, "fpt_rt_set_build_mode: 0 = quality (host), 1 = fast (device), 2 = trbvh (device, treelet-restructured)"); ctx->build_mode = mode; }); }
+{ return guarded(ctx, [&] { require(mode <= 2, "fpt_rt_set_build_mode: 0 = quality (host), 1 = fast (device), 2 = trbvh (device, treelet-restructured)");
+                            ctx->tree.build_mode = mode; if (mode == 0) ctx->tree.build_scratch.release(); }); }
 
+// Device-side (round 6, fpt_build.hip): the mesh stays where it is, the records and every node's boxes are recomputed on the context's stream -- stream-ordered
+// behind the launches that still read the old tree -- and the host reads back 8 bytes (|scene|max and the error bits).  Byte for byte the tree refit_wide8 gives.
 int fpt_rt_refit_geometry(fpt_context* ctx, uint32_t tri_count, const int32_t* d_idx, uint32_t vertex_count, const float* d_vtx)
-{
-	// Device-side (round 6, fpt_build.hip): the mesh stays where it is, the records and every node's boxes are recomputed on the context's stream -- stream-ordered
-	// behind the launches that still read the old tree -- and the host reads back 8 bytes (|scene|max and the error bits).  Byte for byte the tree refit_wide8 gives.
-	return guarded(ctx, [&] { flush_deferred(ctx);
-		require(ctx->has_geometry, "fpt_rt_refit_geometry: fpt_rt_create_geometry has not been called");
-		HostBvh2& B = ctx->host_bvh;
-		require(tri_count == B.device_records || (tri_count == 0 && B.device_records <= 1), "fpt_rt_refit_geometry: the triangle count differs from the tree's");
-		require(tri_count == 0 || (d_idx && d_vtx), "fpt_rt_refit_geometry: null mesh");
-		const double t0 = wall_seconds();
-		const uint32_t n_records = uint32_t(ctx->d_tris.count), n_nodes = uint32_t(ctx->d_nodes.count);
-		ctx->d_refit_scan.alloc(2); ctx->d_refit_tri_box.alloc(size_t(n_records) * 6); ctx->d_refit_node_box.alloc(size_t(n_nodes) * 6);
-		FPT_HIP_CHECK(hipMemsetAsync(ctx->d_refit_scan.ptr, 0, 2 * sizeof(uint32_t), ctx->stream));
-		launch_refit_scan(tri_count, d_idx, vertex_count, d_vtx, tri_count ? n_records : 0u, ctx->d_tris.ptr, ctx->d_refit_scan.ptr, ctx->stream);
-		uint32_t scan[2] = { 0, 0 };
-		ctx->d_refit_scan.download(scan, 2, ctx->stream);
-		require(!(scan[1] & 1u), "fpt: refit found a triangle record outside the mesh");
-		require(!(scan[1] & 2u), "fpt: vertex index out of range in refit");
-		if (tri_count) launch_refit_records(n_records, ctx->d_tris.ptr, d_idx, d_vtx, ctx->d_refit_scan.ptr, ctx->d_refit_tri_box.ptr, ctx->stream);
-		for (size_t L = B.level_begin.size() > 0 ? B.level_begin.size() - 1 : 0; L-- > 0;)
-			launch_refit_level(ctx->d_nodes.ptr, ctx->d_refit_node_box.ptr, ctx->d_refit_tri_box.ptr, B.level_begin[L], B.level_begin[L + 1] - B.level_begin[L], ctx->d_refit_scan.ptr, ctx->stream);
-		FPT_HIP_CHECK(hipGetLastError());
-		std::memcpy(&B.scene_mag, &scan[0], 4);
-		ctx->emitter_generation++;          // shading records and light points were tabulated from the old vertices
-		// a non-finite vertex makes a box that cannot be quantised (the host refit throws there); the level kernels flag it.  Reading the flag waits for the refit (a
-		// millisecond): the call returns with the tree in place or with the error, like the host refit did
-		ctx->d_refit_scan.download(scan, 2, ctx->stream);
-		if (scan[1] & 4u) { ctx->has_geometry = false; require(false, "fpt: internal wide-BVH quantisation error (refit): non-finite vertices? the geometry is invalid until fpt_rt_create_geometry runs again"); }
-		B.seconds_refit = float(wall_seconds() - t0);
-		if (std::getenv("FPT_BVH_TIMERS")) std::fprintf(stderr, "fpt_rt_refit_geometry: on the device, %.3f ms to completion (%u records, %u nodes, %zu levels)\n", B.seconds_refit * 1e3, n_records, n_nodes, B.level_begin.size() - 1);
-	});
-}
+{ return guarded(ctx, [&] { flush_deferred(ctx); refit_acceleration_device(ctx, tri_count, d_idx, vertex_count, d_vtx); }); }
 
 // test / diagnostic: the DEVICE tree as it stands (after a build or a device-side refit) copied to HOST arrays of n_nodes x 20 words and n_records x 12 words
 int fpt_rt_download_bvh(fpt_context* ctx, uint32_t* h_nodes, float* h_records)
 {
 	return guarded(ctx, [&] { flush_deferred(ctx);
-		require(ctx->has_geometry, "fpt_rt_download_bvh: no geometry");
-		if (h_nodes) ctx->d_nodes.download(reinterpret_cast<BvhNode8*>(h_nodes), ctx->d_nodes.count, ctx->stream);
-		if (h_records) ctx->d_tris.download(reinterpret_cast<BvhTriangle*>(h_records), ctx->d_tris.count, ctx->stream);
+		const AccelTree& T = ctx->tree; require(T.valid, "fpt_rt_download_bvh: no geometry");
+		if (h_nodes) T.nodes.download(reinterpret_cast<BvhNode8*>(h_nodes), T.nodes.count, ctx->stream);
+		if (h_records) T.records.download(reinterpret_cast<BvhTriangle*>(h_records), T.records.count, ctx->stream);
 	});
 }
 
@@ -170,7 +146,7 @@ int fpt_mesh_invalidate(fpt_context* ctx)
 
 static void rt_launch(fpt_context* ctx, uint32_t count, const fpt_ray* d_rays, fpt_hit* d_hits, uint32_t* d_bits, bool shadow, bool counted)
 {
-	require(ctx->has_geometry, "fpt_rt_trace*: create_geometry has not been called");
+	require(ctx->tree.valid, "fpt_rt_trace*: create_geometry has not been called");
 	if (count == 0) return;
 	PassCounters cnt{ ctx->d_counters.ptr };
 	TraceParams p = trace_params(ctx, cnt);
@@ -205,22 +181,21 @@ int fpt_rt_trace_counted(fpt_context* ctx, uint32_t count, const fpt_ray* d_rays
 int fpt_rt_bvh_info(fpt_context* ctx, uint32_t* n_nodes, uint32_t* n_leaf_tris, uint32_t* max_depth)
 {
 	return guarded(ctx, [&] {
-		require(ctx->has_geometry, "fpt_rt_bvh_info: create_geometry has not been called");
-		if (n_nodes) *n_nodes = ctx->host_bvh.device_nodes;
-		if (n_leaf_tris) *n_leaf_tris = ctx->host_bvh.device_records;
-		if (max_depth) *max_depth = ctx->host_bvh.wide_depth;
+		require(ctx->tree.valid, "fpt_rt_bvh_info: create_geometry has not been called");
+		if (n_nodes) *n_nodes = ctx->tree.info.n_nodes;
+		if (n_leaf_tris) *n_leaf_tris = ctx->tree.info.n_records;
+		if (max_depth) *max_depth = ctx->tree.info.wide_depth;
 	});
 }
-static void fill_bvh_stats(const HostBvh2& b, fpt_bvh_stats* s)
+static void fill_bvh_stats(const TreeInfo& b, fpt_bvh_stats* s)
 {
 	std::memset(s, 0, sizeof(*s));
-	s->n_nodes = b.built_on_device ? b.device_nodes : uint32_t(b.nodes8.size()); s->n_records = b.built_on_device ? b.device_records : uint32_t(b.tris8.size());
+	s->n_nodes = b.n_nodes; s->n_records = b.n_records;
 	s->depth = b.wide_depth; s->stack_need = b.stack_need;
 	uint64_t used = 0;
 	for (int k = 0; k < 9; ++k) { s->slot_hist[k] = b.slot_hist[k]; used += uint64_t(k) * b.slot_hist[k]; }
 	s->n_inner_children = b.n_inner_children; s->n_leaf_children = b.n_leaf_children; s->build_threads = b.threads;
-	const uint32_t n_wide = b.built_on_device ? b.device_nodes : uint32_t(b.nodes8.size());
-	s->avg_used_slots = n_wide ? float(double(used) / double(n_wide)) : 0.0f;
+	s->avg_used_slots = b.n_nodes ? float(double(used) / double(b.n_nodes)) : 0.0f;
 	s->sah_cost_binary = b.sah_cost; s->sah_cost_wide = b.wide_cost; s->seconds_binary = b.seconds_bvh2; s->seconds_wide = b.seconds_wide;
 	s->seconds_refit = b.seconds_refit;
 	s->seconds_optimise = b.seconds_opt; s->optimise_iterations = b.opt_iterations; s->inner_area_before = b.opt_cost_before; s->inner_area_after = b.opt_cost_after; s->depth_binary = b.max_depth;
@@ -228,9 +203,9 @@ static void fill_bvh_stats(const HostBvh2& b, fpt_bvh_stats* s)
 int fpt_rt_bvh_stats(fpt_context* ctx, fpt_bvh_stats* out)
 {
 	return guarded(ctx, [&] {
-		require(ctx->has_geometry, "fpt_rt_bvh_stats: create_geometry has not been called");
+		require(ctx->tree.valid, "fpt_rt_bvh_stats: create_geometry has not been called");
 		require(out != nullptr, "fpt_rt_bvh_stats: null output");
-		fill_bvh_stats(ctx->host_bvh, out);
+		fill_bvh_stats(ctx->tree.info, out);
 	});
 }
 
@@ -696,7 +671,7 @@ static void render_passes_impl(fpt_context* ctx, uint32_t instance, uint32_t n_p
 	{
 		require(ctx->pt_ready, "fpt_pt_render: fpt_pt_init has not been called");
 		require(n_passes >= 1 && n_passes <= ctx->max_batch, "fpt_pt_render_batch: n_passes exceeds the batch capacity set by fpt_pt_set_batch");
-		require(ctx->has_geometry, "fpt_pt_render: create_geometry has not been called");
+		require(ctx->tree.valid, "fpt_pt_render: create_geometry has not been called");
 		require(ctx->has_emitters, "fpt_pt_render: fpt_mesh_lights_init has not been called");
 		hipStream_t s = ctx->stream;
 		const FrameBufferDev real_fb = fb_dev(view->fb);
@@ -1000,25 +975,38 @@ int fpt_pt_get_captured(fpt_context* ctx, uint32_t* count, fpt_ray* h_rays, fpt_
 	});
 }
 
-// host-side probe of the acceleration-structure builder (no GPU, no context): builds the structure the traversal kernels walk from HOST
-// arrays and copies it out, so that tests can check the layout, the encodings and the conservativeness of the boxes independently
-int fpt_debug_build_bvh(uint32_t tri_count, const int32_t* h_idx, uint32_t vertex_count, const float* h_vtx, uint32_t* n_nodes, uint32_t* n_records,
-                        uint32_t* depth, uint32_t* node_words, uint32_t* h_nodes, float* h_records, fpt_bvh_stats* stats)
+// host-side probe of the acceleration-structure builder (no GPU, no context): builds the structure the traversal kernels walk from HOST arrays -- and, given
+// h_vtx1, refits it to those vertices -- and copies it out, so that tests can check the layout, the encodings and the conservativeness of the boxes independently
+static int debug_bvh(uint32_t tri_count, const int32_t* h_idx, uint32_t vertex_count, const float* h_vtx0, const float* h_vtx1, uint32_t* n_nodes, uint32_t* n_records,
+                     uint32_t* depth, uint32_t* h_nodes, float* h_records, fpt_bvh_stats* stats)
 {
 	try
 	{
-		HostBvh2 b;
-		build_acceleration(tri_count, h_idx, vertex_count, h_vtx, b, trace_stack_entries());
-		if (stats) fill_bvh_stats(b, stats);
-		if (n_nodes) *n_nodes = uint32_t(b.nodes8.size());
-		if (n_records) *n_records = uint32_t(b.tris8.size());
-		if (depth) *depth = b.wide_depth;
-		if (node_words) *node_words = uint32_t(sizeof(BvhNode8) / 4);
+		HostBvh b;
+		build_acceleration(tri_count, h_idx, vertex_count, h_vtx0, b, trace_stack_entries());
+		if (h_vtx1) refit_wide8(tri_count, h_idx, vertex_count, h_vtx1, b);
+		if (stats) fill_bvh_stats(b.info, stats);
+		if (n_nodes) *n_nodes = b.info.n_nodes;
+		if (n_records) *n_records = b.info.n_records;
+		if (depth) *depth = b.info.wide_depth;
 		if (h_nodes && !b.nodes8.empty()) std::memcpy(h_nodes, b.nodes8.data(), b.nodes8.size() * sizeof(BvhNode8));
 		if (h_records && !b.tris8.empty()) std::memcpy(h_records, b.tris8.data(), b.tris8.size() * sizeof(BvhTriangle));
 		return 0;
 	}
 	catch (const std::exception& e) { g_create_error = e.what(); return 1; }
+}
+int fpt_debug_build_bvh(uint32_t tri_count, const int32_t* h_idx, uint32_t vertex_count, const float* h_vtx, uint32_t* n_nodes, uint32_t* n_records,
+                        uint32_t* depth, uint32_t* node_words, uint32_t* h_nodes, float* h_records, fpt_bvh_stats* stats)
+{
+	if (node_words) *node_words = uint32_t(sizeof(BvhNode8) / 4);
+	return debug_bvh(tri_count, h_idx, vertex_count, h_vtx, nullptr, n_nodes, n_records, depth, h_nodes, h_records, stats);
+}
+// the same probe for the refit: builds over h_vtx0, refits to h_vtx1 (same indices) and copies the refitted structure out
+int fpt_debug_refit_bvh(uint32_t tri_count, const int32_t* h_idx, uint32_t vertex_count, const float* h_vtx0, const float* h_vtx1, uint32_t* n_nodes, uint32_t* n_records,
+                        uint32_t* depth, uint32_t* h_nodes, float* h_records, fpt_bvh_stats* stats)
+{
+	if (!h_vtx1) { g_create_error = "fpt_debug_refit_bvh: null vertices"; return 1; }
+	return debug_bvh(tri_count, h_idx, vertex_count, h_vtx0, h_vtx1, n_nodes, n_records, depth, h_nodes, h_records, stats);
 }
 
 // the emitter-table builder without a context (CPU tests against the oracle, tools/time_emitters.py)
@@ -1036,26 +1024,6 @@ int fpt_debug_build_emitter_tables(uint32_t n_vpls, const fpt_mesh_view* h_mesh,
 		if (h_mesh_cdf && !e.mesh_cdf.empty()) std::memcpy(h_mesh_cdf, e.mesh_cdf.data(), e.mesh_cdf.size() * sizeof(float));
 		if (h_mesh_inv_area && !e.mesh_inv_area.empty()) std::memcpy(h_mesh_inv_area, e.mesh_inv_area.data(), e.mesh_inv_area.size() * sizeof(float));
 		if (norm) *norm = e.norm;
-		return 0;
-	}
-	catch (const std::exception& e) { g_create_error = e.what(); return 1; }
-}
-
-// the same probe for the refit: builds over h_vtx0, refits to h_vtx1 (same indices) and copies the refitted structure out
-int fpt_debug_refit_bvh(uint32_t tri_count, const int32_t* h_idx, uint32_t vertex_count, const float* h_vtx0, const float* h_vtx1, uint32_t* n_nodes, uint32_t* n_records,
-                        uint32_t* depth, uint32_t* h_nodes, float* h_records, fpt_bvh_stats* stats)
-{
-	try
-	{
-		HostBvh2 b;
-		build_acceleration(tri_count, h_idx, vertex_count, h_vtx0, b, trace_stack_entries());
-		refit_wide8(tri_count, h_idx, vertex_count, h_vtx1, b);
-		if (stats) fill_bvh_stats(b, stats);
-		if (n_nodes) *n_nodes = uint32_t(b.nodes8.size());
-		if (n_records) *n_records = uint32_t(b.tris8.size());
-		if (depth) *depth = b.wide_depth;
-		if (h_nodes && !b.nodes8.empty()) std::memcpy(h_nodes, b.nodes8.data(), b.nodes8.size() * sizeof(BvhNode8));
-		if (h_records && !b.tris8.empty()) std::memcpy(h_records, b.tris8.data(), b.tris8.size() * sizeof(BvhTriangle));
 		return 0;
 	}
 	catch (const std::exception& e) { g_create_error = e.what(); return 1; }

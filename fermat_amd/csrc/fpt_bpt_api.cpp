@@ -302,7 +302,7 @@ static void render_impl(fpt_context* ctx, uint32_t instance, uint32_t n_passes, 
 {
 	fpt_context::BptState& b = ctx->bpt;
 	require(b.ready, "fpt_bpt_render: fpt_bpt_init has not been called");
-	require(ctx->has_geometry, "fpt_bpt_render: create_geometry has not been called");
+	require(ctx->tree.valid, "fpt_bpt_render: create_geometry has not been called");
 	require(view->res_x * view->res_y == b.n_paths, "fpt_bpt_render: the view's resolution differs from fpt_bpt_init's");
 	require(n_passes >= 1 && n_passes <= b.max_batch, "fpt_bpt_render_batch: more passes than fpt_bpt_set_batch sized the storage for");
 	require(b.pending_n == 0, "fpt_bpt_render: the previous batch's splats have not been resolved (fpt_bpt_resolve_splats)");

@@ -14,6 +14,7 @@
 // work: 1.82 M records x (48 B written + 16 B indices + 3 x 16 B vertices gathered + 24 B box) + 0.19 M nodes x (80 B read + 80 B written + children's boxes).
 #include "fpt_device.h"
 #include "fpt_bvh.h"
+#include "fpt_host.h"
 
 namespace fpt {
 
@@ -165,15 +166,39 @@ void launch_refit_scan(uint32_t n_tris, const int32_t* d_idx, uint32_t n_verts, 
 	if (n) hipLaunchKernelGGL(refit_scan_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, n_tris, reinterpret_cast<const int4*>(d_idx), n_verts, reinterpret_cast<const float4*>(d_vtx),
 	                          n_records, d_records, d_scan);
 }
-void launch_refit_records(uint32_t n_records, BvhTriangle* d_records, const int32_t* d_idx, const float* d_vtx, const uint32_t* d_scan, void* d_tri_box, hipStream_t s)
+
+// fpt_rt_refit_geometry under AccelTree's contract (fpt_host.h): what can refuse the refit comes before the first write; from there to the read-back of the error bits the tree is not valid
+void refit_acceleration_device(fpt_context* ctx, uint32_t tri_count, const int32_t* d_idx, uint32_t vertex_count, const float* d_vtx)
 {
-	if (n_records) hipLaunchKernelGGL(refit_records_kernel, dim3((n_records + 255u) / 256u), dim3(256), 0, s, n_records, d_records, reinterpret_cast<const int4*>(d_idx),
-	                                  reinterpret_cast<const float4*>(d_vtx), d_scan, static_cast<RefitBox*>(d_tri_box));
-}
-void launch_refit_level(BvhNode8* d_nodes, void* d_node_box, const void* d_tri_box, uint32_t begin, uint32_t count, uint32_t* d_scan, hipStream_t s)
-{
-	if (count) hipLaunchKernelGGL(refit_level_kernel, dim3((count + 127u) / 128u), dim3(128), 0, s, d_nodes, static_cast<RefitBox*>(d_node_box), static_cast<const RefitBox*>(d_tri_box),
-	                              begin, count, d_scan);
+	AccelTree& T = ctx->tree; hipStream_t s = ctx->stream;
+	require(T.valid, "fpt_rt_refit_geometry: fpt_rt_create_geometry has not been called");
+	require(tri_count == T.info.n_records || (tri_count == 0 && T.info.n_records <= 1), "fpt_rt_refit_geometry: the triangle count differs from the tree's");
+	require(tri_count == 0 || (d_idx && d_vtx), "fpt_rt_refit_geometry: null mesh");
+	const double t0 = wall_seconds();
+	const uint32_t n_records = T.info.n_records, n_nodes = T.info.n_nodes;
+	const std::vector<uint32_t>& level_begin = T.info.level_begin;
+	T.refit_scan.alloc(2); T.refit_tri_box.alloc(size_t(n_records) * 6); T.refit_node_box.alloc(size_t(n_nodes) * 6);
+	FPT_HIP_CHECK(hipMemsetAsync(T.refit_scan.ptr, 0, 2 * sizeof(uint32_t), s));
+	launch_refit_scan(tri_count, d_idx, vertex_count, d_vtx, tri_count ? n_records : 0u, T.records.ptr, T.refit_scan.ptr, s);
+	uint32_t scan[2] = { 0, 0 }; T.refit_scan.download(scan, 2, s);
+	require(!(scan[1] & 1u), "fpt: refit found a triangle record outside the mesh");
+	require(!(scan[1] & 2u), "fpt: vertex index out of range in refit");
+	T.valid = false;
+	RefitBox* tri_box = reinterpret_cast<RefitBox*>(T.refit_tri_box.ptr); RefitBox* node_box = reinterpret_cast<RefitBox*>(T.refit_node_box.ptr);
+	if (tri_count && n_records) hipLaunchKernelGGL(refit_records_kernel, dim3((n_records + 255u) / 256u), dim3(256), 0, s, n_records, T.records.ptr, reinterpret_cast<const int4*>(d_idx),
+	                                               reinterpret_cast<const float4*>(d_vtx), T.refit_scan.ptr, tri_box);
+	for (size_t L = level_begin.size() > 0 ? level_begin.size() - 1 : 0; L-- > 0;)          // deepest level first
+		if (const uint32_t count = level_begin[L + 1] - level_begin[L])
+			hipLaunchKernelGGL(refit_level_kernel, dim3((count + 127u) / 128u), dim3(128), 0, s, T.nodes.ptr, node_box, tri_box, level_begin[L], count, T.refit_scan.ptr);
+	FPT_HIP_CHECK(hipGetLastError());
+	std::memcpy(&T.info.scene_mag, &scan[0], 4);
+	ctx->emitter_generation++;          // shading records and light points were tabulated from the old vertices
+	// a non-finite vertex makes a box that cannot be quantised (the host refit throws there); the level kernels flag it.  Reading the flag waits for the refit (a
+	// millisecond): the call returns with the tree in place or with the error, like the host refit did
+	T.refit_scan.download(scan, 2, s);
+	require(!(scan[1] & 4u), "fpt: internal wide-BVH quantisation error (refit): non-finite vertices? the geometry is invalid until fpt_rt_create_geometry runs again");
+	T.valid = true; T.info.seconds_refit = float(wall_seconds() - t0);
+	if (std::getenv("FPT_BVH_TIMERS")) std::fprintf(stderr, "fpt_rt_refit_geometry: on the device, %.3f ms to completion (%u records, %u nodes, %zu levels)\n", T.info.seconds_refit * 1e3, n_records, n_nodes, level_begin.size() - 1);
 }
 
 } // namespace fpt

@@ -677,83 +677,84 @@ __global__ __launch_bounds__(256) void lbvh_hist_kernel(const BvhNode8* __restri
 }
 
 // ---- the driver --------------------------------------------------------------------------------------------------------------
-template <class T> static T* carve(uint8_t*& p, size_t n) { T* r = reinterpret_cast<T*>(p); p += (n * sizeof(T) + 255) & ~size_t(255); return r; }
+static constexpr uint32_t kMaxRounds = 4096;                        // of a bottom-up pass (it launches at most kMaxRounds + 7 before it gives up)
+static constexpr uint32_t kTreeletPasses = 3, kGamma0 = 7;          // Karras & Aila's schedule: gamma = 7, 14, 28
 
-// Builds the tree over the DEVICE mesh into ctx->d_nodes / ctx->d_tris; fills the host-side bookkeeping (level ranges, counts, the stack bound).  Returns false -- nothing
-// touched -- when the tree cannot be used (its stack bound exceeds `stack_limit`: a degenerate input) and the caller should fall back to the host builder; throws on bad input.
-// mode 1 = fast (the radix tree as it is), 2 = Trbvh (the radix tree restructured by treelets, stage 3b, before the collapse).
-bool build_acceleration_device(fpt_context* ctx, uint32_t n, const int32_t* d_idx, uint32_t n_verts, const float* d_vtx, uint32_t stack_limit, uint32_t mode)
+// One build: the inputs, the working set carved from the context's scratch allocation, and what the stages hand to each other.  Every stage launches on the context's stream.
+struct DeviceBuild
 {
-	hipStream_t s = ctx->stream;
-	const double t0 = wall_seconds();
-	// |scene|max (the same kernel the refit uses; no records to validate yet)
-	ctx->d_refit_scan.alloc(2);
-	FPT_HIP_CHECK(hipMemsetAsync(ctx->d_refit_scan.ptr, 0, 2 * sizeof(uint32_t), s));
-	launch_refit_scan(0, d_idx, n_verts, d_vtx, 0, nullptr, ctx->d_refit_scan.ptr, s);
-	// scratch, one allocation
-	size_t sort_bytes = 0, scan_bytes = 0;
+	fpt_context* ctx; hipStream_t s; const uint32_t n; const int4* idx; const uint32_t n_verts; const float4* vtx; const uint32_t mode;
+	const dim3 B{ 256 }, G{ (n + 255u) / 256u };
+	uint32_t* scene_scan; size_t sort_bytes, scan_bytes;          // scene_scan: {|scene|max bits, error bits} (the refit's scan kernel)
+	LbvhBox *refs, *node_box; LbvhCell* cells; LbvhEmitTmp* tmp; BvhNode8* nodes; BvhTriangle* records; unsigned long long *keys0, *keys1; uint2 *counts, *offsets; uint8_t *sort_tmp, *scan_tmp;
+	int *bounds, *partials, *left, *right, *queue0, *queue1, *tlist; uint32_t *vals0, *vals1, *flags, *status, *need, *tcount, *tlist_count; float* tcost;
+	// The ONE list of the working set: a null base only measures, the allocation's base hands the arrays out, each on a 256-byte boundary.  flags: the stamps of the
+	// bottom-up passes; a level of the wide tree holds fewer nodes than there are triangles; mode 2 only: N and C per inner node, the treelet list, a list counter per round
+	size_t layout(uint8_t* base)
 	{
+		size_t at = 0;
+		auto take = [&](auto*& p, size_t count) { p = base ? reinterpret_cast<decltype(+p)>(base + at) : nullptr; at += (count * sizeof(*p) + 255) & ~size_t(255); };
+		const size_t nt = n, cap = nt, nt2 = mode == 2 ? nt : 0;
+		take(refs, nt); take(bounds, 16); take(partials, (nt + 255) / 256 * 12 + 12); take(keys0, nt); take(keys1, nt); take(vals0, nt); take(vals1, nt);
+		take(left, nt); take(right, nt); take(flags, nt); take(node_box, nt); take(cells, nt);
+		take(queue0, cap); take(queue1, cap); take(tmp, cap); take(counts, cap); take(offsets, cap); take(status, 16); take(sort_tmp, sort_bytes); take(scan_tmp, scan_bytes);
+		take(nodes, cap); take(records, nt + 1); take(need, cap);
+		take(tcount, nt2); take(tcost, nt2); take(tlist, nt2); take(tlist_count, mode == 2 ? kMaxRounds + 16 : 0);
+		return at;
+	}
+	const unsigned long long* keys; const uint32_t* vals;          // between the stages: the sorted (code, triangle) pairs, ...
+	double area_before, area_after, area_leaves, seconds_opt; uint32_t fit_root_stamp, tri_total;
+	TreeInfo info;
+	double t0 = wall_seconds(), t_tree = 0.0, t_stage = 0.0, ms_stage[7] = { 0, 0, 0, 0, 0, 0, 0 };
+	const bool timers = std::getenv("FPT_BVH_TIMERS") != nullptr;
+	void stage(int k) { if (timers) { FPT_HIP_CHECK(hipStreamSynchronize(s)); const double t = wall_seconds(); ms_stage[k] = (t - t_stage) * 1e3; t_stage = t; } }
+	template <typename T> T read_back(const T* d) { T h; FPT_HIP_CHECK(hipMemcpyAsync(&h, d, sizeof(T), hipMemcpyDeviceToHost, s)); FPT_HIP_CHECK(hipStreamSynchronize(s)); return h; }
+	// one bottom-up pass in rounds (a node is done a round after its children), `flags` holding the stamps: eight rounds per read-back of the root's stamp, which is returned
+	template <typename F> uint32_t bottom_up(const char* runaway, F&& launch_round)
+	{
+		uint32_t r = 0, root_stamp = 0;
+		while (root_stamp == 0u)
+		{
+			for (int k = 0; k < 8; ++k) launch_round(++r);
+			root_stamp = read_back(flags);
+			require(r <= kMaxRounds, runaway);
+		}
+		return root_stamp;
+	}
+	// |scene|max (the refit's kernel; no records to validate yet) and the scratch: one allocation that stays with the context, reused by every build that fits in it
+	void scene_scan_and_scratch()
+	{
+		AccelTree& T = ctx->tree;
+		T.refit_scan.alloc(2); scene_scan = T.refit_scan.ptr;
+		FPT_HIP_CHECK(hipMemsetAsync(scene_scan, 0, 2 * sizeof(uint32_t), s));
+		launch_refit_scan(0, reinterpret_cast<const int32_t*>(idx), n_verts, reinterpret_cast<const float*>(vtx), 0, nullptr, scene_scan, s);
 		rocprim::double_buffer<unsigned long long> k(nullptr, nullptr); rocprim::double_buffer<uint32_t> v(nullptr, nullptr);
 		FPT_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, k, v, n, 0, 63, s));
 		FPT_HIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, (uint2*)nullptr, (uint2*)nullptr, make_uint2(0, 0), size_t(n), Uint2Plus(), s));
+		const size_t total = layout(nullptr);
+		if (T.build_scratch.count < total) T.build_scratch.alloc(total);
+		layout(T.build_scratch.ptr);
+		FPT_HIP_CHECK(hipMemsetAsync(status, 0, 64, s)); FPT_HIP_CHECK(hipMemsetAsync(flags, 0, size_t(n) * 4, s));
+		t_stage = wall_seconds(); stage(0);
 	}
-	const size_t cap = n;          // a level of the wide tree holds fewer nodes than there are triangles
-	size_t total = 0;
-	auto sz = [&](size_t bytes) { total += (bytes + 255) & ~size_t(255); };
-	sz(n * sizeof(LbvhBox)); sz(16 * sizeof(int)); sz((size_t((n + 255u) / 256u) * 12 + 12) * sizeof(int)); sz(n * 8); sz(n * 8); sz(n * 4); sz(n * 4); sz(n * 4); sz(n * 4); sz(n * 4); sz(n * 4); sz(n * 4); sz(n * sizeof(LbvhBox)); sz(n * sizeof(LbvhCell));
-	sz(cap * 4); sz(cap * 4); sz(cap * sizeof(LbvhEmitTmp)); sz(cap * 8); sz(cap * 8); sz(64); sz(sort_bytes); sz(scan_bytes); sz(cap * sizeof(BvhNode8)); sz((size_t(n) + 1) * sizeof(BvhTriangle)); sz(cap * 4);
-	// mode 2: N and C per inner node, the treelet list, one list counter per round (a pass launches at most kMaxRounds + 7 rounds before it gives up)
-	static constexpr uint32_t kMaxRounds = 4096;
-	if (mode == 2) { sz(size_t(n) * sizeof(uint32_t)); sz(size_t(n) * sizeof(float)); sz(size_t(n) * sizeof(int)); sz(size_t(kMaxRounds + 16) * sizeof(uint32_t)); }
-	// the scratch stays with the context (a host that rebuilds every frame allocates it once; fpt_destroy or a smaller build's reuse keeps it)
-	if (ctx->d_build_scratch.count < total) ctx->d_build_scratch.alloc(total);
-	uint8_t* p = ctx->d_build_scratch.ptr;
-	LbvhBox* refs = carve<LbvhBox>(p, n); int* bounds = carve<int>(p, 16); int* partials = carve<int>(p, size_t((n + 255u) / 256u) * 12 + 12);
-	unsigned long long* keys0 = carve<unsigned long long>(p, n); unsigned long long* keys1 = carve<unsigned long long>(p, n);
-	uint32_t* vals0 = carve<uint32_t>(p, n); uint32_t* vals1 = carve<uint32_t>(p, n);
-	int* left = carve<int>(p, n); int* right = carve<int>(p, n); uint32_t* flags = carve<uint32_t>(p, n);
-	LbvhBox* node_box = carve<LbvhBox>(p, n); LbvhCell* cells = carve<LbvhCell>(p, n);
-	int* queue0 = carve<int>(p, cap); int* queue1 = carve<int>(p, cap); LbvhEmitTmp* tmp = carve<LbvhEmitTmp>(p, cap);
-	uint2* counts = carve<uint2>(p, cap); uint2* offsets = carve<uint2>(p, cap); uint32_t* status = carve<uint32_t>(p, 16);
-	uint8_t* sort_tmp = carve<uint8_t>(p, sort_bytes); uint8_t* scan_tmp = carve<uint8_t>(p, scan_bytes);
-	BvhNode8* nodes = carve<BvhNode8>(p, cap); BvhTriangle* records = carve<BvhTriangle>(p, size_t(n) + 1); uint32_t* need = carve<uint32_t>(p, cap);
-	uint2* totals = reinterpret_cast<uint2*>(status + 4);
-	uint32_t* tcount = nullptr; float* tcost = nullptr; int* tlist = nullptr; uint32_t* tlist_count = nullptr;
-	if (mode == 2) { tcount = carve<uint32_t>(p, n); tcost = carve<float>(p, n); tlist = carve<int>(p, n); tlist_count = carve<uint32_t>(p, kMaxRounds + 16); }
-
-	FPT_HIP_CHECK(hipMemsetAsync(status, 0, 64, s));
-	FPT_HIP_CHECK(hipMemsetAsync(flags, 0, size_t(n) * 4, s));
-	const bool timers = std::getenv("FPT_BVH_TIMERS") != nullptr;
-	double t_stage = wall_seconds(); double ms_stage[7] = { 0, 0, 0, 0, 0, 0, 0 };
-	auto stage = [&](int k) { if (timers) { FPT_HIP_CHECK(hipStreamSynchronize(s)); const double t = wall_seconds(); ms_stage[k] = (t - t_stage) * 1e3; t_stage = t; } };
-	stage(0);          // |scene|max + scratch
-	const dim3 B(256), G((n + 255u) / 256u);
-	hipLaunchKernelGGL(lbvh_refs_kernel, G, B, 0, s, n, reinterpret_cast<const int4*>(d_idx), n_verts, reinterpret_cast<const float4*>(d_vtx), ctx->d_refit_scan.ptr, refs, partials, status);
-	hipLaunchKernelGGL(lbvh_bounds_kernel, dim3(1), B, 0, s, (n + 255u) / 256u, partials, bounds);
-	hipLaunchKernelGGL(lbvh_codes_kernel, G, B, 0, s, n, refs, bounds, keys0, vals0);
-	stage(1);          // references + codes
-	rocprim::double_buffer<unsigned long long> kb(keys0, keys1); rocprim::double_buffer<uint32_t> vb(vals0, vals1);
-	FPT_HIP_CHECK(rocprim::radix_sort_pairs(sort_tmp, sort_bytes, kb, vb, n, 0, 63, s));
-	const unsigned long long* keys = kb.current(); const uint32_t* vals = vb.current();
-	stage(2);          // sort
-	hipLaunchKernelGGL(lbvh_tree_kernel, G, B, 0, s, n, keys, left, right);
-	stage(3);          // radix tree
-	// 3b (mode 2): prep, kTreeletPasses restructuring passes, each bottom-up in rounds with `flags` as its stamps (reset before each and before stage 4)
-	static constexpr uint32_t kTreeletPasses = 3, kGamma0 = 7;          // Karras & Aila's schedule: gamma = 7, 14, 28
-	double area_before = 0.0, area_after = 0.0, area_leaves = 0.0, seconds_opt = 0.0;
-	if (mode == 2)
+	void references_and_codes()
+	{
+		hipLaunchKernelGGL(lbvh_refs_kernel, G, B, 0, s, n, idx, n_verts, vtx, scene_scan, refs, partials, status);
+		hipLaunchKernelGGL(lbvh_bounds_kernel, dim3(1), B, 0, s, (n + 255u) / 256u, partials, bounds);
+		hipLaunchKernelGGL(lbvh_codes_kernel, G, B, 0, s, n, refs, bounds, keys0, vals0);
+		stage(1);
+	}
+	void sort()
+	{
+		rocprim::double_buffer<unsigned long long> kb(keys0, keys1); rocprim::double_buffer<uint32_t> vb(vals0, vals1);
+		FPT_HIP_CHECK(rocprim::radix_sort_pairs(sort_tmp, sort_bytes, kb, vb, n, 0, 63, s));
+		keys = kb.current(); vals = vb.current(); stage(2);
+	}
+	void radix_tree() { hipLaunchKernelGGL(lbvh_tree_kernel, G, B, 0, s, n, keys, left, right); stage(3); }
+	// 3b (mode 2): prep, kTreeletPasses restructuring passes, each bottom-up with fresh stamps (reset before each and before stage 4)
+	void restructure_by_treelets()
 	{
 		const double t_opt = wall_seconds();
-		auto bottom_up = [&](auto&& launch_round) {
-			uint32_t r = 0;
-			for (uint32_t root_stamp = 0; root_stamp == 0u;)
-			{
-				for (int k = 0; k < 8; ++k) launch_round(++r);
-				FPT_HIP_CHECK(hipMemcpyAsync(&root_stamp, flags, 4, hipMemcpyDeviceToHost, s));
-				FPT_HIP_CHECK(hipStreamSynchronize(s));
-				require(r <= kMaxRounds, "fpt: internal device-build error (a restructuring pass does not terminate)");
-			}
-		};
 		const uint32_t n_blocks = (n + 255u) / 256u;
 		double* area_partials = reinterpret_cast<double*>(partials);          // stage 1's partials (12 ints per block) are free again: two doubles per block
 		std::vector<double> h_partials(size_t(n_blocks) * 2);
@@ -764,114 +765,126 @@ bool build_acceleration_device(fpt_context* ctx, uint32_t n, const int32_t* d_id
 			inner = 0.0; leaves = 0.0;
 			for (uint32_t b = 0; b < n_blocks; ++b) { inner += h_partials[2 * size_t(b)]; leaves += h_partials[2 * size_t(b) + 1]; }
 		};
-		bottom_up([&](uint32_t r) { hipLaunchKernelGGL(trbvh_prep_round_kernel, G, B, 0, s, n, r, refs, vals, left, right, flags, node_box, tcount, tcost, bounds); });
+		const char* runaway = "fpt: internal device-build error (a restructuring pass does not terminate)";
+		bottom_up(runaway, [&](uint32_t r) { hipLaunchKernelGGL(trbvh_prep_round_kernel, G, B, 0, s, n, r, refs, vals, left, right, flags, node_box, tcount, tcost, bounds); });
 		summed_areas(area_before, area_leaves);
 		const uint32_t treelet_blocks = 2048;          // persistent: one wave per treelet, 8 per CU
 		for (uint32_t pass = 0, gamma = kGamma0; pass < kTreeletPasses; ++pass, gamma *= 2u)
 		{
 			FPT_HIP_CHECK(hipMemsetAsync(flags, 0, size_t(n) * 4, s));
 			FPT_HIP_CHECK(hipMemsetAsync(tlist_count, 0, size_t(kMaxRounds + 16) * sizeof(uint32_t), s));
-			bottom_up([&](uint32_t r) {
+			bottom_up(runaway, [&](uint32_t r) {
 				hipLaunchKernelGGL(trbvh_ready_round_kernel, G, B, 0, s, n, r, gamma, left, right, flags, tcount, tlist, tlist_count + r);
 				hipLaunchKernelGGL(trbvh_treelet_kernel, dim3(treelet_blocks), dim3(64), 0, s, tlist, tlist_count + r, refs, vals, left, right, node_box, tcount, tcost, bounds, status);
 			});
 		}
 		summed_areas(area_after, area_leaves);
 		FPT_HIP_CHECK(hipMemsetAsync(flags, 0, size_t(n) * 4, s));          // stage 4 starts from fresh stamps
-		uint32_t h_st = 0;
-		FPT_HIP_CHECK(hipMemcpyAsync(&h_st, status, 4, hipMemcpyDeviceToHost, s));
-		FPT_HIP_CHECK(hipStreamSynchronize(s));
+		const uint32_t h_st = read_back(status);
 		require(!(h_st & 2u), "fpt: vertex index out of range");
 		require(!(h_st & 16u), "fpt: internal device-build error (restructure)");
-		seconds_opt = wall_seconds() - t_opt;
-		stage(5);          // restructuring
+		seconds_opt = wall_seconds() - t_opt; stage(5);
 	}
-	// bottom-up in rounds (lbvh_fit_round_kernel); `flags` holds the stamps.  Eight rounds per read-back of the root's stamp
-	uint32_t rounds = 0, fit_root_stamp = 0;
-	for (uint32_t root_stamp = 0; root_stamp == 0u;)
+	// 4: the nodes' boxes and the collapse's cost rows; the root's stamp is the binary tree's depth
+	void boxes_and_cost_rows()
 	{
-		for (int k = 0; k < 8; ++k) { ++rounds; hipLaunchKernelGGL(lbvh_fit_round_kernel, G, B, 0, s, n, rounds, refs, vals, left, right, flags, node_box, cells, bounds); }
-		FPT_HIP_CHECK(hipMemcpyAsync(&root_stamp, flags, 4, hipMemcpyDeviceToHost, s));
-		FPT_HIP_CHECK(hipStreamSynchronize(s));
-		require(rounds <= 4096, "fpt: internal device-build error (the bottom-up pass does not terminate)");
-		fit_root_stamp = root_stamp;
+		fit_root_stamp = bottom_up("fpt: internal device-build error (the bottom-up pass does not terminate)", [&](uint32_t r) {
+			hipLaunchKernelGGL(lbvh_fit_round_kernel, G, B, 0, s, n, r, refs, vals, left, right, flags, node_box, cells, bounds); });
+		stage(4);
+		require(!(read_back(status) & 2u), "fpt: vertex index out of range"); t_tree = wall_seconds();
 	}
-	stage(4);          // boxes + cost rows
-	uint32_t h_status[8] = { 0 };
-	FPT_HIP_CHECK(hipMemcpyAsync(h_status, status, 4, hipMemcpyDeviceToHost, s));
-	FPT_HIP_CHECK(hipStreamSynchronize(s));
-	require(!(h_status[0] & 2u), "fpt: vertex index out of range");
-	const double t_tree = wall_seconds();
-
-	// emission, level by level
-	std::vector<uint32_t> level_begin;
-	const int root_ref = 0;
-	FPT_HIP_CHECK(hipMemcpyAsync(queue0, &root_ref, 4, hipMemcpyHostToDevice, s));
-	int* q_cur = queue0; int* q_next = queue1;
-	uint32_t n_level = 1, level_base = 0, tri_total = 0;
-	while (n_level)
+	// 5: emission, level by level from the root
+	void emit_levels()
 	{
-		require(size_t(level_base) + n_level <= cap, "fpt: internal device-build error (more wide nodes than triangles)");
+		const size_t cap = n; std::vector<uint32_t>& level_begin = info.level_begin;
+		uint2* totals = reinterpret_cast<uint2*>(status + 4);
+		const int root_ref = 0;
+		FPT_HIP_CHECK(hipMemcpyAsync(queue0, &root_ref, 4, hipMemcpyHostToDevice, s));
+		int* q_cur = queue0; int* q_next = queue1;
+		uint32_t n_level = 1, level_base = 0;
+		while (n_level)
+		{
+			require(size_t(level_base) + n_level <= cap, "fpt: internal device-build error (more wide nodes than triangles)");
+			level_begin.push_back(level_base);
+			hipLaunchKernelGGL(lbvh_emit_kernel, dim3((n_level + 63u) / 64u), dim3(64), 0, s, n_level, q_cur, refs, vals, left, right, node_box, cells, nodes + level_base, tmp, counts, status);
+			size_t sb = scan_bytes;
+			FPT_HIP_CHECK(rocprim::exclusive_scan(scan_tmp, sb, counts, offsets, make_uint2(0, 0), size_t(n_level), Uint2Plus(), s));
+			hipLaunchKernelGGL(lbvh_finish_kernel, dim3((n_level + 255u) / 256u), B, 0, s, n_level, nodes + level_base, tmp, counts, offsets, level_base + n_level, tri_total, q_next, records,
+			                   idx, vtx, scene_scan, totals);
+			const uint2 tot = read_back(totals);
+			level_base += n_level; tri_total += tot.y; n_level = tot.x;
+			std::swap(q_cur, q_next);
+			require(level_begin.size() <= 4096, "fpt: internal device-build error (runaway depth)");
+		}
 		level_begin.push_back(level_base);
-		hipLaunchKernelGGL(lbvh_emit_kernel, dim3((n_level + 63u) / 64u), dim3(64), 0, s, n_level, q_cur, refs, vals, left, right, node_box, cells, nodes + level_base, tmp, counts, status);
-		size_t sb = scan_bytes;
-		FPT_HIP_CHECK(rocprim::exclusive_scan(scan_tmp, sb, counts, offsets, make_uint2(0, 0), size_t(n_level), Uint2Plus(), s));
-		hipLaunchKernelGGL(lbvh_finish_kernel, dim3((n_level + 255u) / 256u), B, 0, s, n_level, nodes + level_base, tmp, counts, offsets, level_base + n_level, tri_total, q_next, records,
-		                   reinterpret_cast<const int4*>(d_idx), reinterpret_cast<const float4*>(d_vtx), ctx->d_refit_scan.ptr, totals);
-		uint2 tot;
-		FPT_HIP_CHECK(hipMemcpyAsync(&tot, totals, sizeof(tot), hipMemcpyDeviceToHost, s));
-		FPT_HIP_CHECK(hipStreamSynchronize(s));
-		level_base += n_level; tri_total += tot.y; n_level = tot.x;
-		std::swap(q_cur, q_next);
-		require(level_begin.size() <= 4096, "fpt: internal device-build error (runaway depth)");
+		require(tri_total == n, "fpt: internal device-build error (a triangle was lost or doubled)");
+		info.n_nodes = level_base; info.n_records = tri_total; info.on_device = true; info.wide_depth = uint32_t(level_begin.size() - 1);
 	}
-	const uint32_t n_nodes = level_base;
-	level_begin.push_back(n_nodes);
-	require(tri_total == n, "fpt: internal device-build error (a triangle was lost or doubled)");
-	for (size_t L = level_begin.size() - 1; L-- > 0;)
-		hipLaunchKernelGGL(lbvh_need_kernel, dim3((level_begin[L + 1] - level_begin[L] + 255u) / 256u), B, 0, s, nodes, level_begin[L], level_begin[L + 1] - level_begin[L], need);
-	uint32_t h_hist[11] = { 0 };
-	uint32_t* hist = reinterpret_cast<uint32_t*>(offsets);          // the level scan's offsets are no longer needed: 11 words of them hold the histogram
-	FPT_HIP_CHECK(hipMemsetAsync(hist, 0, sizeof(h_hist), s));
-	hipLaunchKernelGGL(lbvh_hist_kernel, dim3((n_nodes + 255u) / 256u), B, 0, s, nodes, n_nodes, hist);
-	FPT_HIP_CHECK(hipMemcpyAsync(h_hist, hist, sizeof(h_hist), hipMemcpyDeviceToHost, s));
-	uint32_t h_need = 0, h_scan[2] = { 0, 0 };
-	LbvhCell h_root_cell = {};
-	if (mode == 2) FPT_HIP_CHECK(hipMemcpyAsync(&h_root_cell, cells, sizeof(h_root_cell), hipMemcpyDeviceToHost, s));
-	FPT_HIP_CHECK(hipMemcpyAsync(&h_need, need, 4, hipMemcpyDeviceToHost, s));
-	FPT_HIP_CHECK(hipMemcpyAsync(h_status, status, 4, hipMemcpyDeviceToHost, s));
-	FPT_HIP_CHECK(hipMemcpyAsync(h_scan, ctx->d_refit_scan.ptr, 8, hipMemcpyDeviceToHost, s));
-	FPT_HIP_CHECK(hipStreamSynchronize(s));
-	FPT_HIP_CHECK(hipGetLastError());
-	require(!(h_status[0] & 8u), "fpt: internal device-build error (collapse)");
-	require(!(h_status[0] & 4u), "fpt: internal wide-BVH quantisation error: non-finite vertices?");
-	if (h_need > stack_limit) return false;
-	// the tree in exact-size arrays
-	ctx->d_nodes.alloc(n_nodes); ctx->d_tris.alloc(tri_total);
-	FPT_HIP_CHECK(hipMemcpyAsync(ctx->d_nodes.ptr, nodes, size_t(n_nodes) * sizeof(BvhNode8), hipMemcpyDeviceToDevice, s));
-	FPT_HIP_CHECK(hipMemcpyAsync(ctx->d_tris.ptr, records, size_t(tri_total) * sizeof(BvhTriangle), hipMemcpyDeviceToDevice, s));
-	FPT_HIP_CHECK(hipStreamSynchronize(s));
-	HostBvh2& H = ctx->host_bvh;
-	H = HostBvh2();
-	H.level_begin = level_begin; H.wide_depth = uint32_t(level_begin.size() - 1); H.stack_need = h_need;
-	H.device_nodes = n_nodes; H.device_records = tri_total; H.built_on_device = true;
-	for (int k = 0; k < 9; ++k) H.slot_hist[k] = h_hist[k];
-	H.n_inner_children = h_hist[9]; H.n_leaf_children = h_hist[10];
-	std::memcpy(&H.scene_mag, &h_scan[0], 4);
-	H.seconds_bvh2 = float(t_tree - t0); H.seconds_wide = float(wall_seconds() - t_tree); H.threads = 0;
-	if (mode == 2)
+	// 6: the traversal-stack bound, the occupancy histogram, the last look at the error bits: `info` is complete but for the time of the copy
+	void stack_bound_and_histogram()
 	{
-		// comparable with the host build's statistics: re-insertion's measure before / after, the binary tree's SAH (all nodes' areas) and depth, the collapse's cost
-		H.opt_cost_before = float(area_before); H.opt_cost_after = float(area_after); H.opt_iterations = kTreeletPasses;
-		H.seconds_opt = float(seconds_opt); H.seconds_bvh2 -= H.seconds_opt;
-		H.sah_cost = float(area_after + area_leaves); H.max_depth = fit_root_stamp;
-		H.wide_cost = h_root_cell.c[1];
+		const std::vector<uint32_t>& level_begin = info.level_begin;
+		for (size_t L = level_begin.size() - 1; L-- > 0;)
+			hipLaunchKernelGGL(lbvh_need_kernel, dim3((level_begin[L + 1] - level_begin[L] + 255u) / 256u), B, 0, s, nodes, level_begin[L], level_begin[L + 1] - level_begin[L], need);
+		uint32_t h_hist[11] = { 0 };
+		uint32_t* hist = reinterpret_cast<uint32_t*>(offsets);          // the level scan's offsets are no longer needed: 11 words of them hold the histogram
+		FPT_HIP_CHECK(hipMemsetAsync(hist, 0, sizeof(h_hist), s));
+		hipLaunchKernelGGL(lbvh_hist_kernel, dim3((info.n_nodes + 255u) / 256u), B, 0, s, nodes, info.n_nodes, hist);
+		FPT_HIP_CHECK(hipMemcpyAsync(h_hist, hist, sizeof(h_hist), hipMemcpyDeviceToHost, s));
+		uint32_t h_status = 0, h_scan[2] = { 0, 0 }; LbvhCell h_root_cell = {};
+		if (mode == 2) FPT_HIP_CHECK(hipMemcpyAsync(&h_root_cell, cells, sizeof(h_root_cell), hipMemcpyDeviceToHost, s));
+		FPT_HIP_CHECK(hipMemcpyAsync(&info.stack_need, need, 4, hipMemcpyDeviceToHost, s));
+		FPT_HIP_CHECK(hipMemcpyAsync(&h_status, status, 4, hipMemcpyDeviceToHost, s));
+		FPT_HIP_CHECK(hipMemcpyAsync(h_scan, scene_scan, 8, hipMemcpyDeviceToHost, s));
+		FPT_HIP_CHECK(hipStreamSynchronize(s)); FPT_HIP_CHECK(hipGetLastError());
+		require(!(h_status & 8u), "fpt: internal device-build error (collapse)");
+		require(!(h_status & 4u), "fpt: internal wide-BVH quantisation error: non-finite vertices?");
+		for (int k = 0; k < 9; ++k) info.slot_hist[k] = h_hist[k];
+		info.n_inner_children = h_hist[9]; info.n_leaf_children = h_hist[10];
+		std::memcpy(&info.scene_mag, &h_scan[0], 4);
+		info.seconds_bvh2 = float(t_tree - t0); info.threads = 0;
+		if (mode == 2)
+		{
+			// comparable with the host build's statistics: re-insertion's measure before / after, the binary tree's SAH (all nodes' areas) and depth, the collapse's cost
+			info.opt_cost_before = float(area_before); info.opt_cost_after = float(area_after); info.opt_iterations = kTreeletPasses;
+			info.seconds_opt = float(seconds_opt); info.seconds_bvh2 -= info.seconds_opt;
+			info.sah_cost = float(area_after + area_leaves); info.max_depth = fit_root_stamp;
+			info.wide_cost = h_root_cell.c[1];
+		}
 	}
-	if (timers) std::fprintf(stderr, "build_acceleration_device: %u triangles -> %u wide nodes in %zu levels, stack bound %u; to the binary tree %.3f ms (|scene|max + scratch %.3f, references + codes %.3f, "
-	                                 "sort %.3f, radix tree %.3f, boxes + cost rows %.3f), emission + bound + copy %.3f ms\n",
-	                                 n, n_nodes, level_begin.size() - 1, h_need, H.seconds_bvh2 * 1e3, ms_stage[0], ms_stage[1], ms_stage[2], ms_stage[3], ms_stage[4], H.seconds_wide * 1e3);
-	if (timers && mode == 2) std::fprintf(stderr, "build_acceleration_device: restructuring (prep + %u treelet passes) %.3f ms, inner-node area %.4f -> %.4f, binary depth %u\n",
-	                                      kTreeletPasses, ms_stage[5], area_before, area_after, fit_root_stamp);
+	// the tree in exact-size arrays: the guarded section of the owner's contract (AccelTree::replace)
+	void install()
+	{
+		const size_t n_nodes = info.n_nodes, n_records = info.n_records;
+		ctx->tree.replace(std::move(info), [&](BvhNode8* d_nodes, BvhTriangle* d_records) {
+			FPT_HIP_CHECK(hipMemcpyAsync(d_nodes, nodes, n_nodes * sizeof(BvhNode8), hipMemcpyDeviceToDevice, s));
+			FPT_HIP_CHECK(hipMemcpyAsync(d_records, records, n_records * sizeof(BvhTriangle), hipMemcpyDeviceToDevice, s));
+			FPT_HIP_CHECK(hipStreamSynchronize(s)); });
+		TreeInfo& H = ctx->tree.info; H.seconds_wide = float(wall_seconds() - t_tree);
+		if (timers) std::fprintf(stderr, "build_acceleration_device: %u triangles -> %u wide nodes in %zu levels, stack bound %u; to the binary tree %.3f ms (|scene|max + scratch %.3f, references + codes %.3f, "
+		                                 "sort %.3f, radix tree %.3f, boxes + cost rows %.3f), emission + bound + copy %.3f ms\n",
+		                                 n, H.n_nodes, H.level_begin.size() - 1, H.stack_need, H.seconds_bvh2 * 1e3, ms_stage[0], ms_stage[1], ms_stage[2], ms_stage[3], ms_stage[4], H.seconds_wide * 1e3);
+		if (timers && mode == 2) std::fprintf(stderr, "build_acceleration_device: restructuring (prep + %u treelet passes) %.3f ms, inner-node area %.4f -> %.4f, binary depth %u\n",
+		                                      kTreeletPasses, ms_stage[5], area_before, area_after, fit_root_stamp);
+	}
+};
+
+// Builds the tree over the DEVICE mesh and installs it in ctx->tree (AccelTree's contract, fpt_host.h): up to install() everything works in the scratch, so a throw or
+// `return false` -- the stack bound exceeds `stack_limit` (a degenerate input): fall back to the host builder -- leaves ctx->tree exactly as it was.
+// mode 1 = fast (the radix tree as it is), 2 = Trbvh (the radix tree restructured by treelets, stage 3b, before the collapse).
+bool build_acceleration_device(fpt_context* ctx, uint32_t n, const int32_t* d_idx, uint32_t n_verts, const float* d_vtx, uint32_t stack_limit, uint32_t mode)
+{
+	DeviceBuild b{ ctx, ctx->stream, n, reinterpret_cast<const int4*>(d_idx), n_verts, reinterpret_cast<const float4*>(d_vtx), mode };
+	b.scene_scan_and_scratch();
+	b.references_and_codes();
+	b.sort();
+	b.radix_tree();
+	if (mode == 2) b.restructure_by_treelets();
+	b.boxes_and_cost_rows();
+	b.emit_levels();
+	b.stack_bound_and_histogram();
+	if (b.info.stack_need > stack_limit) return false;
+	b.install();
 	return true;
 }
 

@@ -402,30 +402,34 @@ float triangle_vpad(const float* p0, const float* p1, const float* p2, float sce
 	return (m0 + scene_mag) * 5.0e-7f;
 }
 
+// largest |coordinate| of the vertex array (NaNs are skipped, as by every min / max of the builder)
+float scene_magnitude(uint32_t vertex_count, const float* vtx, uint32_t n_threads)
+{
+	float part[64] = { 0.0f }, scene_mag = 0.0f;
+	parallel_slices(vertex_count, vertex_count >= 65536u ? n_threads : 1u, [&](size_t b, size_t e, uint32_t t) {
+		float m = 0.0f;
+		for (size_t v = b; v < e; ++v) for (int k = 0; k < 3; ++k) m = std::max(m, std::fabs(vtx[4 * v + k]));
+		part[t] = m; });
+	for (float m : part) scene_mag = std::max(scene_mag, m);
+	return scene_mag;
+}
+
 double now_seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 } // namespace
 
-void build_bvh2(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, const float* vtx, HostBvh2& out, uint32_t sah_depth)
+void build_bvh2(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, const float* vtx, HostBvh& out, uint32_t sah_depth)
 {
 	PoolScope pool_scope;
 	const double t0 = now_seconds();
-	out.nodes.clear(); out.prims.clear(); out.max_depth = 0; out.sah_cost = 0.0f;
+	out.nodes.clear(); out.prims.clear(); out.info.max_depth = 0; out.info.sah_cost = 0.0f;
 	if (tri_count >= (1u << 28)) throw std::runtime_error("fpt: too many triangles for the leaf reference encoding");
 	const uint32_t n_threads = builder_threads();
-	out.threads = n_threads;
+	out.info.threads = n_threads;
 	const uint32_t wide = tri_count >= 65536u ? n_threads : 1u;
 	// scene magnitude for the conservative padding (rounding in the slab test must never cull a hit that the fpt-MT intersector accepts)
-	float scene_mag = 0.0f;
-	{
-		float part[64] = { 0.0f };
-		parallel_slices(vertex_count, vertex_count >= 65536u ? n_threads : 1u, [&](size_t b, size_t e, uint32_t t) {
-			float m = 0.0f;
-			for (size_t v = b; v < e; ++v) for (int k = 0; k < 3; ++k) m = std::max(m, std::fabs(vtx[4 * v + k]));
-			part[t] = m; });
-		for (float m : part) scene_mag = std::max(scene_mag, m);
-	}
-	out.scene_mag = scene_mag;
+	const float scene_mag = scene_magnitude(vertex_count, vtx, n_threads);
+	out.info.scene_mag = scene_mag;
 	if (tri_count == 0)
 	{
 		// an empty scene still gets one node whose children are empty leaves, so kernels need no special case
@@ -511,9 +515,9 @@ void build_bvh2(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, c
 		out.nodes[0] = n;
 	}
 	else if (root != 0) throw std::runtime_error("fpt: internal BVH builder error (root is not node 0)");
-	out.max_depth = max_depth;
-	out.sah_cost = float(cost);
-	out.seconds_bvh2 = float(now_seconds() - t0);
+	out.info.max_depth = max_depth;
+	out.info.sah_cost = float(cost);
+	out.info.seconds_bvh2 = float(now_seconds() - t0);
 	if (std::getenv("FPT_BVH_TIMERS")) std::fprintf(stderr, "build_bvh2: references %.3f s, top phase %.3f (%zu tasks), tasks %.3f\n", t_refs - t0, t_top - t_refs, top.tasks.size(), now_seconds() - t_top);
 }
 
@@ -686,7 +690,7 @@ struct Optimizer
 
 } // namespace
 
-void optimize_bvh2(HostBvh2& bvh, uint32_t max_iterations, double batch_fraction)
+void optimize_bvh2(HostBvh& bvh, uint32_t max_iterations, double batch_fraction)
 {
 	PoolScope pool_scope;
 	const double t0 = now_seconds();
@@ -746,7 +750,7 @@ void optimize_bvh2(HostBvh2& bvh, uint32_t max_iterations, double batch_fraction
 	std::vector<std::pair<double, int32_t>> order; order.reserve(ni);
 	const size_t per_batch = std::max<size_t>(1, size_t(double(ni) * batch_fraction));
 	double best = O.cost(); uint32_t stale = 0;
-	bvh.opt_cost_before = float(best);
+	bvh.info.opt_cost_before = float(best);
 	uint32_t it = 0;
 	// (nearly all of the gain comes with the first batches -- the few thousand nodes a centroid-binned build gets badly wrong, large triangles filed
 	//  among small ones; pseudo-random batches after the measure-driven ones stall were tried and find nothing more)
@@ -760,7 +764,7 @@ void optimize_bvh2(HostBvh2& bvh, uint32_t max_iterations, double batch_fraction
 		if (c < best * (1.0 - 1.0e-3)) stale = 0; else ++stale;
 		best = std::min(best, c);
 	}
-	bvh.opt_cost_after = float(O.cost()); bvh.opt_iterations = it;
+	bvh.info.opt_cost_after = float(O.cost()); bvh.info.opt_iterations = it;
 	const double t_loop = now_seconds();
 	// back into the array form: pre-order, parents before children (build_wide8's bottom-up pass walks the array backwards), leaves in the order met.
 	// The walk is bound by the latency of 3.6 M scattered 64-byte nodes, so it runs on all threads: the top of the tree (depth <= kCut) is walked once to find
@@ -857,8 +861,8 @@ void optimize_bvh2(HostBvh2& bvh, uint32_t max_iterations, double batch_fraction
 		else               { P.child1 = ref; X.box.store(P.lo1, P.hi1); }
 	}
 	bvh.nodes.swap(out); bvh.prims.swap(prims);
-	bvh.max_depth = max_depth; bvh.sah_cost = float(cost);
-	bvh.seconds_opt = float(now_seconds() - t0);
+	bvh.info.max_depth = max_depth; bvh.info.sah_cost = float(cost);
+	bvh.info.seconds_opt = float(now_seconds() - t0);
 	if (std::getenv("FPT_BVH_TIMERS")) std::fprintf(stderr, "optimize: set-up %.3f s, batches %.3f (select %.3f, apply %.3f, visits %llu), write-back %.3f\n", t_setup - t0, t_loop - t_setup, O.t_select, O.t_apply, (unsigned long long)O.visits, now_seconds() - t_loop);
 }
 
@@ -1004,21 +1008,47 @@ struct Collapse
 struct WideChild { int32_t ref; Box box; uint32_t n_prims; uint32_t prim[3]; };      // ref >= 0: the binary node that roots an inner child; < 0: a leaf of n_prims triangles
 inline float center(const Box& b, int k) { return 0.5f * (b.lo[k] + b.hi[k]); }
 
+// The node-local grid of build_wide8 and refit_wide8.  Exponent of the smallest power-of-two cell that spans the node's extent along axis k in 255 steps ...
+int grid_exponent(const Box& nb, int k, const char* error)
+{
+	const double ext = double(nb.hi[k]) - double(nb.lo[k]);
+	// an infinite vertex: no grid spans this node.  snap_outward would say so too, but only after the search below has walked two billion exponents (most of a minute)
+	if (std::isinf(ext)) throw std::runtime_error(error);
+	int e = -100;
+	if (ext > 0.0)
+	{
+		e = int(std::ceil(std::log2(ext / 255.0)));
+		while (ext / std::ldexp(1.0, e) > 255.0) ++e;
+		while (e > -100 && ext / std::ldexp(1.0, e - 1) <= 255.0) --e;
+	}
+	return std::max(-100, std::min(e, 120));
+}
+// ... and a child's [c_lo, c_hi] along one axis snapped outward onto the grid (origin p, cell size `cell`), checked in double
+void snap_outward(double p, double cell, float c_lo, float c_hi, uint8_t* qlo, uint8_t* qhi, const char* error)
+{
+	double lo = std::floor((double(c_lo) - p) / cell); lo = lo < 0.0 ? 0.0 : (lo > 255.0 ? 255.0 : lo);
+	while (lo > 0.0 && !(p + lo * cell <= double(c_lo))) lo -= 1.0;
+	double hi = std::ceil((double(c_hi) - p) / cell); hi = hi < 0.0 ? 0.0 : (hi > 255.0 ? 255.0 : hi);
+	while (hi < 255.0 && !(p + hi * cell >= double(c_hi))) hi += 1.0;
+	if (!(p + lo * cell <= double(c_lo)) || !(p + hi * cell >= double(c_hi))) throw std::runtime_error(error);
+	*qlo = uint8_t(lo); *qhi = uint8_t(hi);
+}
+
 } // namespace
 
-void build_wide8(uint32_t tri_count, const int32_t* idx, const float* vtx, HostBvh2& bvh)
+void build_wide8(uint32_t tri_count, const int32_t* idx, const float* vtx, HostBvh& bvh)
 {
 	PoolScope pool_scope;
 	const double t0 = now_seconds();
-	bvh.nodes8.clear(); bvh.tris8.clear(); bvh.wide_depth = 0; bvh.stack_need = 0; bvh.wide_cost = 0.0f;
-	bvh.n_inner_children = bvh.n_leaf_children = 0;
-	for (int k = 0; k < 9; ++k) bvh.slot_hist[k] = 0;
+	bvh.nodes8.clear(); bvh.tris8.clear(); bvh.info.wide_depth = 0; bvh.info.stack_need = 0; bvh.info.wide_cost = 0.0f;
+	bvh.info.n_inner_children = bvh.info.n_leaf_children = 0;
+	for (int k = 0; k < 9; ++k) bvh.info.slot_hist[k] = 0;
 	Collapse dp(bvh.nodes);
 	if (const char* e = std::getenv("FPT_BVH_MAX_LEAF")) dp.max_leaf = uint32_t(std::max(1, std::min(int(CW8_MAX_LEAF), std::atoi(e))));
 	if (const char* e = std::getenv("FPT_BVH_C_PRIM")) dp.c_prim = float(std::atof(e));
 	dp.solve(builder_threads());
 	const double t_dp = now_seconds();
-	bvh.wide_cost = dp.cell[0].c[1];
+	bvh.info.wide_cost = dp.cell[0].c[1];
 
 	auto leaf_child = [&](int32_t ref, const Box& b) {
 		WideChild c; c.ref = -1; c.box = b; c.n_prims = 0; c.prim[0] = c.prim[1] = c.prim[2] = 0;
@@ -1027,12 +1057,12 @@ void build_wide8(uint32_t tri_count, const int32_t* idx, const float* vtx, HostB
 		return c;
 	};
 	// the triangles below a binary subtree that the collapse turns into one leaf (<= 3)
-	struct Gather { const HostBvh2& B; WideChild& c; void run(int32_t ref) {
+	struct Gather { const HostBvh& B; WideChild& c; void run(int32_t ref) {
 		if (ref < 0) { const uint32_t leaf = uint32_t(~ref), first = leaf >> 3, count = leaf & 7u;
 		               for (uint32_t t = 0; t < count; ++t) { if (c.n_prims >= 3) throw std::runtime_error("fpt: internal wide-BVH error (leaf size)"); c.prim[c.n_prims++] = B.prims[first + t]; } return; }
 		run(B.nodes[size_t(ref)].child0); run(B.nodes[size_t(ref)].child1); } };
 	// the children that the subtree behind (ref, box) contributes to a wide node when it may use at most `budget` slots
-	struct Collect { const HostBvh2& B; const Collapse& dp; std::vector<WideChild>& out; decltype(leaf_child)& mk_leaf;
+	struct Collect { const HostBvh& B; const Collapse& dp; std::vector<WideChild>& out; decltype(leaf_child)& mk_leaf;
 		void run(int32_t ref, const Box& b, int budget)
 		{
 			if (ref < 0) { if ((uint32_t(~ref) & 7u) != 0u) out.push_back(mk_leaf(ref, b)); return; }      // empty leaves (padding of tiny scenes) carry nothing
@@ -1093,20 +1123,7 @@ void build_wide8(uint32_t tri_count, const int32_t* idx, const float* vtx, HostB
 		std::memcpy(&node.w[0], &nb.lo[0], 4); std::memcpy(&node.w[1], &nb.lo[1], 4); std::memcpy(&node.w[2], &nb.lo[2], 4);
 		// node-local grid: the smallest power-of-two cell that spans the node in 255 steps
 		int ex[3];
-		for (int k = 0; k < 3; ++k)
-		{
-			const double ext = double(nb.hi[k]) - double(nb.lo[k]);
-			int e = -100;
-			if (ext > 0.0)
-			{
-				e = int(std::ceil(std::log2(ext / 255.0)));
-				while (ext / std::ldexp(1.0, e) > 255.0) ++e;
-				while (e > -100 && ext / std::ldexp(1.0, e - 1) <= 255.0) --e;
-			}
-			e = std::max(-100, std::min(e, 120));
-			ex[k] = e;
-			bytes[12 + k] = uint8_t(e + 127);
-		}
+		for (int k = 0; k < 3; ++k) { ex[k] = grid_exponent(nb, k, "fpt: internal wide-BVH quantisation error"); bytes[12 + k] = uint8_t(ex[k] + 127); }
 		const double cell_of[3] = { std::ldexp(1.0, ex[0]), std::ldexp(1.0, ex[1]), std::ldexp(1.0, ex[2]) };
 		uint32_t imask = 0;
 		for (int sl = 0; sl < 8; ++sl)
@@ -1117,13 +1134,7 @@ void build_wide8(uint32_t tri_count, const int32_t* idx, const float* vtx, HostB
 			const WideChild& c = ch[size_t(child_in_slot[sl])];
 			for (int k = 0; k < 3; ++k)
 			{
-				const double p = nb.lo[k], cell = cell_of[k];
-				double lo = std::floor((double(c.box.lo[k]) - p) / cell); lo = lo < 0.0 ? 0.0 : (lo > 255.0 ? 255.0 : lo);
-				while (lo > 0.0 && !(p + lo * cell <= double(c.box.lo[k]))) lo -= 1.0;
-				double hi = std::ceil((double(c.box.hi[k]) - p) / cell); hi = hi < 0.0 ? 0.0 : (hi > 255.0 ? 255.0 : hi);
-				while (hi < 255.0 && !(p + hi * cell >= double(c.box.hi[k]))) hi += 1.0;
-				if (!(p + lo * cell <= double(c.box.lo[k])) || !(p + hi * cell >= double(c.box.hi[k]))) throw std::runtime_error("fpt: internal wide-BVH quantisation error");
-				*qlo[k] = uint8_t(lo); *qhi[k] = uint8_t(hi);
+				snap_outward(nb.lo[k], cell_of[k], c.box.lo[k], c.box.hi[k], qlo[k], qhi[k], "fpt: internal wide-BVH quantisation error");
 			}
 			if (c.ref >= 0)
 			{
@@ -1151,7 +1162,7 @@ void build_wide8(uint32_t tri_count, const int32_t* idx, const float* vtx, HostB
 			const float* p0 = vtx + 4 * size_t(ix[0]); const float* p1 = vtx + 4 * size_t(ix[1]); const float* p2 = vtx + 4 * size_t(ix[2]);
 			BvhTriangle r;
 			for (int k = 0; k < 3; ++k) { r.v0[k] = p0[k]; r.e1[k] = p1[k] - p0[k]; r.e2[k] = p2[k] - p0[k]; }
-			r.tri_id = int32_t(tri); r.mask = uint32_t(ix[3]); r.vpad = triangle_vpad(p0, p1, p2, bvh.scene_mag);
+			r.tri_id = int32_t(tri); r.mask = uint32_t(ix[3]); r.vpad = triangle_vpad(p0, p1, p2, bvh.info.scene_mag);
 			out[t] = r;
 		}
 	};
@@ -1164,12 +1175,12 @@ void build_wide8(uint32_t tri_count, const int32_t* idx, const float* vtx, HostB
 	size_t tri_total = 0;
 	bvh.tris8.clear();
 	NoInitVector<BvhTriangle> records(size_t(tri_count) + 1);          // sized once: every triangle lands in exactly one leaf
-	bvh.level_begin.clear();
+	bvh.info.level_begin.clear();
 	for (size_t lb = 0, depth = 1; lb < queue.size(); ++depth)
 	{
 		const size_t le = queue.size(), n_level = le - lb;
-		bvh.level_begin.push_back(uint32_t(lb));
-		bvh.wide_depth = std::max(bvh.wide_depth, uint32_t(depth));
+		bvh.info.level_begin.push_back(uint32_t(lb));
+		bvh.info.wide_depth = std::max(bvh.info.wide_depth, uint32_t(depth));
 		level.resize(n_level);
 		const uint32_t th = n_level >= 512 ? n_threads : 1u;
 		parallel_slices(n_level, th, [&](size_t b, size_t e, uint32_t) { std::vector<WideChild> ch; for (size_t i = b; i < e; ++i) emit_node(queue[lb + i], level[i], ch); });
@@ -1177,21 +1188,22 @@ void build_wide8(uint32_t tri_count, const int32_t* idx, const float* vtx, HostB
 		for (size_t i = 0; i < n_level; ++i)
 		{
 			Emit& E = level[i];
-			bvh.slot_hist[E.n_children]++;
+			bvh.info.slot_hist[E.n_children]++;
 			E.node.w[4] = uint32_t(queue.size()); E.node.w[5] = uint32_t(tri_total);
 			tri_base_of[i] = tri_total; tri_total += E.n_tris;
 			if (tri_total > records.size()) throw std::runtime_error("fpt: internal wide-BVH error (more leaf triangles than triangles)");
 			for (uint32_t c = 0; c < E.n_inner; ++c) queue.push_back(E.inner_ref[c]);
-			bvh.n_inner_children += E.n_inner; bvh.n_leaf_children += E.n_leaf;
+			bvh.info.n_inner_children += E.n_inner; bvh.info.n_leaf_children += E.n_leaf;
 			bvh.nodes8.push_back(E.node);
 		}
 		parallel_slices(n_level, th, [&](size_t b, size_t e, uint32_t) { for (size_t i = b; i < e; ++i) write_records(level[i], records.data() + tri_base_of[i]); });
 		lb = le;
 	}
-	bvh.level_begin.push_back(uint32_t(bvh.nodes8.size()));
+	bvh.info.level_begin.push_back(uint32_t(bvh.nodes8.size()));
 	records.resize(tri_total);
 	bvh.tris8.swap(records);
 	if (bvh.tris8.empty()) { BvhTriangle z; std::memset(&z, 0, sizeof(z)); bvh.tris8.push_back(z); }
+	bvh.info.n_nodes = uint32_t(bvh.nodes8.size()); bvh.info.n_records = uint32_t(bvh.tris8.size()); bvh.info.on_device = false;
 	// upper bound of the traversal stack a ray can need (fpt_trace.hip pushes, per node step, at most the rest of the node group it came from -- when that
 	// group has more than one inner child -- and at most one parked triangle group -- when the node has leaf children): bottom-up over the BFS order
 	{
@@ -1205,37 +1217,29 @@ void build_wide8(uint32_t tri_count, const int32_t* idx, const float* vtx, HostB
 			for (uint32_t c = 0; c < n_inner; ++c) below = std::max(below, need[size_t(N.w[4]) + c]);
 			need[n] = (has_leaf ? 1u : 0u) + (n_inner ? (n_inner >= 2 ? 1u : 0u) + below : 0u);
 		}
-		bvh.stack_need = need.empty() ? 0u : need[0];
+		bvh.info.stack_need = need.empty() ? 0u : need[0];
 	}
-	bvh.seconds_wide = float(now_seconds() - t0);
+	bvh.info.seconds_wide = float(now_seconds() - t0);
 	if (std::getenv("FPT_BVH_TIMERS")) std::fprintf(stderr, "build_wide8: dp %.3f s, emission + stack bound %.3f s\n", t_dp - t0, now_seconds() - t_dp);
 }
 
 // The whole builder.  The kernel's stack pushes are unchecked, so the bound computed from the tree itself (rest-of-group + parked-triangle entries along
 // the deepest path) must fit `stack_limit`: a degenerate input whose tree is too deep is built again without the optimisation (which may deepen a tree:
 // where every position costs the same -- coincident triangles -- re-insertion strings the subtrees into a chain) and then with shallower SAH limits, down
-// to the balanced object-median tree.  The caller checks out.stack_need.
+// to the balanced object-median tree.  The caller checks out.info.stack_need.
 // Refit (round 5): the vertices moved, the topology stays -- the triangle records are recomputed from the new positions, every wide node's box becomes the union of
 // its children's EXACT boxes (leaves: their triangles' padded boxes, inner children: the box their node was given) bottom-up, and the children are quantised again
 // on the node's new grid, outward, with build_wide8's arithmetic.  Slots, leaves and numbering are untouched, so the traversal-stack bound holds; what degrades with
 // large motion is only the tree's quality (its boxes grow), never a result -- the intersector's answer does not depend on the tree.  Tens of milliseconds where a
 // build takes most of a second: what RenderingContext::update_model uses when asked to (the reference rebuilds: src/renderer.cu:999-1017).
-void refit_wide8(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, const float* vtx, HostBvh2& bvh)
+void refit_wide8(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, const float* vtx, HostBvh& bvh)
 {
 	PoolScope pool_scope;
 	const double t0 = now_seconds();
 	if (bvh.nodes8.empty() || tri_count == 0) return;
 	if (bvh.tris8.size() != size_t(tri_count)) throw std::runtime_error("fpt: refit needs the geometry the tree was built over (triangle count differs)");
 	const uint32_t n_threads = builder_threads();
-	float scene_mag = 0.0f;
-	{
-		float part[64] = { 0.0f };
-		parallel_slices(vertex_count, vertex_count >= 65536u ? n_threads : 1u, [&](size_t b, size_t e, uint32_t t) {
-			float m = 0.0f;
-			for (size_t v = b; v < e; ++v) for (int k = 0; k < 3; ++k) m = std::max(m, std::fabs(vtx[4 * v + k]));
-			part[t] = m; });
-		for (float m : part) scene_mag = std::max(scene_mag, m);
-	}
+	const float scene_mag = scene_magnitude(vertex_count, vtx, n_threads);
 	// nothing is written before every record's triangle id and vertex indices have been checked: a refused refit leaves the tree as it was
 	for (size_t i = 0; i < (tri_count ? bvh.tris8.size() : 0); ++i)
 	{
@@ -1251,12 +1255,10 @@ void refit_wide8(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, 
 		{
 			BvhTriangle& r = bvh.tris8[i];
 			const uint32_t tri = uint32_t(r.tri_id);
-			if (tri >= tri_count) throw std::runtime_error("fpt: refit found a triangle record outside the mesh");
 			const int32_t* ix = idx + 4 * size_t(tri);
 			Box bx; bx.reset(); float m0 = 0.0f;
 			for (int c = 0; c < 3; ++c)
 			{
-				if (ix[c] < 0 || uint32_t(ix[c]) >= vertex_count) throw std::runtime_error("fpt: vertex index out of range in refit");
 				const float* p = vtx + 4 * size_t(ix[c]);
 				bx.grow(p);
 				for (int k = 0; k < 3; ++k) m0 = std::max(m0, std::fabs(p[k]));
@@ -1268,19 +1270,11 @@ void refit_wide8(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, 
 			for (int k = 0; k < 3; ++k) { r.v0[k] = p0[k]; r.e1[k] = p1[k] - p0[k]; r.e2[k] = p2[k] - p0[k]; }
 			r.mask = uint32_t(ix[3]); r.vpad = triangle_vpad(p0, p1, p2, scene_mag);
 		} });
-	bvh.scene_mag = scene_mag;
+	bvh.info.scene_mag = scene_mag;
 	// nodes bottom-up: children have larger indices than their parent (breadth-first numbering: a level is a contiguous range, the next level the children of
-	// its nodes in order), so the levels are found front to back and worked back to front, each on all threads
+	// its nodes in order), so the levels are worked back to front, each on all threads
 	std::vector<Box> node_box(bvh.nodes8.size());
-	std::vector<size_t> level_begin;
-	for (size_t lb = 0, le = 1; lb < le && lb < bvh.nodes8.size();)
-	{
-		level_begin.push_back(lb);
-		size_t children = 0;
-		for (size_t n = lb; n < le; ++n) children += size_t(__builtin_popcount(bvh.nodes8[n].w[3] >> 24));
-		lb = le; le = std::min(bvh.nodes8.size(), le + children);
-	}
-	level_begin.push_back(bvh.nodes8.size());
+	const std::vector<uint32_t>& level_begin = bvh.info.level_begin;
 	auto refit_node = [&](size_t n)
 	{
 		BvhNode8& node = bvh.nodes8[n];
@@ -1307,20 +1301,7 @@ void refit_wide8(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, 
 		node_box[n] = nb;
 		std::memcpy(&node.w[0], &nb.lo[0], 4); std::memcpy(&node.w[1], &nb.lo[1], 4); std::memcpy(&node.w[2], &nb.lo[2], 4);
 		int ex[3];
-		for (int k = 0; k < 3; ++k)
-		{
-			const double ext = double(nb.hi[k]) - double(nb.lo[k]);
-			int e = -100;
-			if (ext > 0.0)
-			{
-				e = int(std::ceil(std::log2(ext / 255.0)));
-				while (ext / std::ldexp(1.0, e) > 255.0) ++e;
-				while (e > -100 && ext / std::ldexp(1.0, e - 1) <= 255.0) --e;
-			}
-			e = std::max(-100, std::min(e, 120));
-			ex[k] = e;
-			bytes[12 + k] = uint8_t(e + 127);
-		}
+		for (int k = 0; k < 3; ++k) { ex[k] = grid_exponent(nb, k, "fpt: internal wide-BVH quantisation error (refit)"); bytes[12 + k] = uint8_t(ex[k] + 127); }
 		for (int sl = 0; sl < 8; ++sl)
 		{
 			uint8_t* qlo[3] = { bytes + 32 + sl, bytes + 40 + sl, bytes + 48 + sl };
@@ -1328,13 +1309,7 @@ void refit_wide8(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, 
 			if (!used[sl]) { for (int k = 0; k < 3; ++k) { *qlo[k] = 255; *qhi[k] = 0; } continue; }
 			for (int k = 0; k < 3; ++k)
 			{
-				const double p = nb.lo[k], cell = std::ldexp(1.0, ex[k]);
-				double lo = std::floor((double(cb[sl].lo[k]) - p) / cell); lo = lo < 0.0 ? 0.0 : (lo > 255.0 ? 255.0 : lo);
-				while (lo > 0.0 && !(p + lo * cell <= double(cb[sl].lo[k]))) lo -= 1.0;
-				double hi = std::ceil((double(cb[sl].hi[k]) - p) / cell); hi = hi < 0.0 ? 0.0 : (hi > 255.0 ? 255.0 : hi);
-				while (hi < 255.0 && !(p + hi * cell >= double(cb[sl].hi[k]))) hi += 1.0;
-				if (!(p + lo * cell <= double(cb[sl].lo[k])) || !(p + hi * cell >= double(cb[sl].hi[k]))) throw std::runtime_error("fpt: internal wide-BVH quantisation error (refit)");
-				*qlo[k] = uint8_t(lo); *qhi[k] = uint8_t(hi);
+				snap_outward(nb.lo[k], std::ldexp(1.0, ex[k]), cb[sl].lo[k], cb[sl].hi[k], qlo[k], qhi[k], "fpt: internal wide-BVH quantisation error (refit)");
 			}
 		}
 	};
@@ -1343,24 +1318,24 @@ void refit_wide8(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, 
 		const size_t lb = level_begin[L], n_level = level_begin[L + 1] - lb;
 		parallel_slices(n_level, n_level >= 512 ? n_threads : 1u, [&](size_t b, size_t e, uint32_t) { for (size_t i = b; i < e; ++i) refit_node(lb + i); });
 	}
-	bvh.seconds_refit = float(now_seconds() - t0);
+	bvh.info.seconds_refit = float(now_seconds() - t0);
 }
 
-void build_acceleration(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, const float* vtx, HostBvh2& out, uint32_t stack_limit)
+void build_acceleration(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, const float* vtx, HostBvh& out, uint32_t stack_limit)
 {
 	PoolScope pool_scope;
 	build_bvh2(tri_count, idx, vertex_count, vtx, out);
 	optimize_bvh2(out);
 	build_wide8(tri_count, idx, vtx, out);
-	for (uint32_t sah_depth = 30; out.stack_need > stack_limit; sah_depth = sah_depth > 12 ? 12 : (sah_depth >= 6 ? sah_depth - 6 : 0))
+	for (uint32_t sah_depth = 30; out.info.stack_need > stack_limit; sah_depth = sah_depth > 12 ? 12 : (sah_depth >= 6 ? sah_depth - 6 : 0))
 	{
-		const float t_opt = out.seconds_opt;
+		const float t_opt = out.info.seconds_opt;
 		build_bvh2(tri_count, idx, vertex_count, vtx, out, sah_depth);
-		out.opt_iterations = 0; out.opt_cost_before = out.opt_cost_after = 0.0f; out.seconds_opt = t_opt;      // (the time was spent; its tree was not kept)
+		out.info.opt_iterations = 0; out.info.opt_cost_before = out.info.opt_cost_after = 0.0f; out.info.seconds_opt = t_opt;      // (the time was spent; its tree was not kept)
 		build_wide8(tri_count, idx, vtx, out);
 		if (sah_depth == 0) break;
 	}
-	// the binary tree has served: a context keeps only what the kernel walks and the refit rewrites (123 MB less per 1.8 M triangles)
+	// the binary tree has served: the caller uploads, copies out or refits only the wide arrays (123 MB less per 1.8 M triangles)
 	NoInitVector<BvhNode>().swap(out.nodes); NoInitVector<uint32_t>().swap(out.prims);
 }
 

@@ -1,5 +1,7 @@
 // fpt_bvh.h — the acceleration structure that replaces OptiX's "Trbvh" + RTX triangles (src/rt.cpp:284-331): an 8-wide compressed BVH
-// ("CW8") built on the host as the SAH-optimal collapse of a binned-SAH binary tree that an insertion-based optimisation pass has improved.
+// ("CW8"), the SAH-optimal collapse of a binary tree.  The binary tree is either built on the host (this header's builder: binned SAH, improved by an
+// insertion-based optimisation pass) or on the device (fpt_build_lbvh.hip: a Morton radix tree, optionally restructured by treelets); a device refit
+// (fpt_build.hip) follows moved vertices in either.  TreeInfo describes the finished tree whichever way it came about.
 //
 // Device layout, chosen for CDNA4:
 //   * one 80-byte node holds EIGHT children's boxes on a node-local 8-bit grid + what is needed to find them (BvhNode8 below): a ray
@@ -70,46 +72,47 @@ inline uint32_t cw8_leaf_count(const BvhNode8& n, int slot) { return ((n.w[6] >>
 inline uint32_t cw8_leaf_first(const BvhNode8& n, int slot) { return n.w[5] + uint32_t(__builtin_popcount(n.w[6] & ((1u << (2 * slot)) - 1u))); }
 inline uint32_t cw8_inner_child(const BvhNode8& n, int slot) { return n.w[4] + uint32_t(__builtin_popcount((n.w[3] >> 24) & ((1u << slot) - 1u))); }
 
-struct HostBvh2
+// What anyone needs to know about a finished wide tree, wherever it was built (host builder, device builder, refitted or not)
+struct TreeInfo
+{
+	uint32_t n_nodes = 0, n_records = 0;     // wide nodes and triangle records
+	bool on_device = false;                  // built by the device builder (fpt_build_lbvh.hip): there is no host copy of the arrays
+	std::vector<uint32_t> level_begin;       // wide nodes are numbered breadth-first: level L = [level_begin[L], level_begin[L + 1]); what a refit walks bottom-up
+	uint32_t wide_depth = 0, stack_need = 0; // stack_need: upper bound of the traversal-stack entries a ray can need in this tree (see build_wide8)
+	float scene_mag = 0.0f;                  // largest |coordinate| of the vertex array the tree was built (or refitted) over
+	uint32_t slot_hist[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, n_inner_children = 0, n_leaf_children = 0;      // wide nodes by number of used child slots
+	float wide_cost = 0.0f;                  // SAH cost of the collapse (c_node = 1 per wide node, c_prim per triangle, areas relative to the root)
+	uint32_t max_depth = 0; float sah_cost = 0.0f;      // of the binary tree the wide one was collapsed from
+	float seconds_bvh2 = 0.0f, seconds_wide = 0.0f, seconds_opt = 0.0f, seconds_refit = 0.0f;
+	float opt_cost_before = 0.0f, opt_cost_after = 0.0f;      // optimize_bvh2: sum of the inner nodes' areas relative to the root's
+	uint32_t opt_iterations = 0, threads = 1;
+};
+// What the host builder produces: its binary intermediate, the wide arrays the traversal kernel walks, and their description
+struct HostBvh
 {
 	NoInitVector<BvhNode> nodes;             // the binary SAH tree (builder intermediate), one triangle per leaf: the collapse forms the leaves
 	NoInitVector<uint32_t> prims;            // triangle ids in leaf order
-	uint32_t max_depth = 0;
-	float sah_cost = 0.0f;
-	// the 8-wide collapse of the same tree (build_wide8): what the traversal kernel walks
-	std::vector<BvhNode8> nodes8;
+	std::vector<BvhNode8> nodes8;            // the 8-wide collapse of the same tree (build_wide8)
 	NoInitVector<BvhTriangle> tris8;         // triangle records grouped per wide node
-	uint32_t wide_depth = 0;
-	std::vector<uint32_t> level_begin;       // wide nodes are numbered breadth-first: level L = [level_begin[L], level_begin[L + 1]); what a refit walks bottom-up
-	uint32_t stack_need = 0;                 // upper bound of the traversal-stack entries a ray can need in this tree (see build_wide8)
-	uint32_t slot_hist[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };      // wide nodes by number of used child slots
-	uint32_t n_inner_children = 0, n_leaf_children = 0;
-	float wide_cost = 0.0f;                  // SAH cost of the collapse (c_node = 1 per wide node, c_prim per triangle, areas relative to the root)
-	float seconds_bvh2 = 0.0f, seconds_wide = 0.0f, seconds_opt = 0.0f, seconds_refit = 0.0f;
-	float opt_cost_before = 0.0f, opt_cost_after = 0.0f;      // optimize_bvh2: sum of the inner nodes' areas relative to the root's
-	uint32_t opt_iterations = 0;
-	uint32_t threads = 1;
-	uint32_t device_nodes = 0, device_records = 0;      // what the device holds (a device-side build keeps no host copy: nodes8 / tris8 stay empty)
-	bool built_on_device = false;
-	float scene_mag = 0.0f;                  // largest |coordinate| of the vertex array the tree was built (or refitted) over
+	TreeInfo info;                           // of nodes8 / tris8
 };
 
 // idx: int4 per triangle (x,y,z vertex ids, w shadow mask); vtx: float4 per vertex.  Multi-threaded (std::thread, one pool per build): the big ranges at the top
 // of the tree are binned and partitioned by all threads, the subtrees below are handed out; references are partitioned in place, nodes come out in pre-order without
 // stitching (a subtree over m triangles has m - 1 nodes); the result does not depend on the number of threads.
 // sah_depth: SAH splits down to that depth, object-median splits below (depth <= sah_depth + log2(n) for any input); 0 = a balanced median tree
-void build_bvh2(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, const float* vtx, HostBvh2& out, uint32_t sah_depth = 30);
+void build_bvh2(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, const float* vtx, HostBvh& out, uint32_t sah_depth = 30);
 // insertion-based optimisation of the binary tree (Bittner et al. 2013): batches of the worst inner nodes are removed and their subtrees re-inserted
 // where they cost least; stops after max_iterations batches or when the cost no longer falls.  Call between build_bvh2 and build_wide8.
-void optimize_bvh2(HostBvh2& bvh, uint32_t max_iterations = 16, double batch_fraction = 0.01);
+void optimize_bvh2(HostBvh& bvh, uint32_t max_iterations = 16, double batch_fraction = 0.01);
 // collapses out.nodes / out.prims into out.nodes8 / out.tris8: the SAH-optimal 8-wide collapse (dynamic programme of Ylitie et al. 2017, section 3:
 // which binary nodes become wide nodes, which subtrees of <= 2 triangles become leaves), octant-ordered slots by an exact 8x8 assignment,
 // outward 8-bit quantisation checked in double
-void build_wide8(uint32_t tri_count, const int32_t* idx, const float* vtx, HostBvh2& bvh);
+void build_wide8(uint32_t tri_count, const int32_t* idx, const float* vtx, HostBvh& bvh);
 // the vertices moved, the topology stays: triangle records and every node's boxes recomputed in place (nodes8 / tris8), bottom-up; nothing else changes
-void refit_wide8(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, const float* vtx, HostBvh2& bvh);
-// build_bvh2 + optimize_bvh2 + build_wide8; a tree whose traversal-stack bound (bvh.stack_need) exceeds stack_limit is built again without the
-// optimisation and then with shallower SAH limits.  The caller checks bvh.stack_need against its kernel.
-void build_acceleration(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, const float* vtx, HostBvh2& bvh, uint32_t stack_limit);
+void refit_wide8(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, const float* vtx, HostBvh& bvh);
+// build_bvh2 + optimize_bvh2 + build_wide8; a tree whose traversal-stack bound (bvh.info.stack_need) exceeds stack_limit is built again without the
+// optimisation and then with shallower SAH limits.  The caller checks bvh.info.stack_need against its kernel.
+void build_acceleration(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, const float* vtx, HostBvh& bvh, uint32_t stack_limit);
 
 } // namespace fpt

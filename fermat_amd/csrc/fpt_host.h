@@ -5,6 +5,7 @@
 #include "fpt_bpt.h"
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 #include <stdexcept>
 #include <cstring>
@@ -105,6 +106,31 @@ struct PassCounters
 		return base + CNT_QUEUES + CNT_PER_BOUNCE * bounce + slot;
 	}
 };
+// The acceleration structure the traversal kernels walk and its one owner.  Whoever builds the tree (the host builder in fpt_api.cpp, the device builder in
+// fpt_build_lbvh.hip) or rewrites it (the refit, fpt_build.hip) keeps this contract, and everything that reads the tree checks `valid` first:
+//   1. A failure that can be detected before the arrays or `info` are modified (a null mesh, an index out of range, a non-finite vertex in the host builder, a stack
+//      bound over the kernel's limit, an internal builder error) leaves both exactly as they were, the old geometry usable: a build works and checks in storage of its own.
+//   2. From the first modification of the arrays or `info` to the last, `valid` is false; it becomes true only when arrays and description agree.  A throw in
+//      between leaves the context with NO geometry: every later trace, render or refit answers "create_geometry has not been called".
+//   3. Replacing adds no second copy of the tree on the device, no allocation when the sizes did not change (DeviceArray::alloc) and no synchronisation.
+struct AccelTree
+{
+	DeviceArray<BvhNode8> nodes; DeviceArray<BvhTriangle> records;      // the 8-wide compressed BVH (fpt_bvh.h)
+	TreeInfo info;                                  // of what `nodes` / `records` hold
+	bool valid = false;
+	uint32_t build_mode = 0;                        // fpt_rt_set_build_mode: 0 = quality (host: binned SAH + re-insertion + collapse), 1 = fast (device: Morton radix tree + collapse),
+	                                                // 2 = trbvh (device: Morton radix tree + treelet restructuring + collapse)
+	DeviceArray<float> refit_tri_box, refit_node_box; DeviceArray<uint32_t> refit_scan;      // device refit (fpt_build.hip): per-record and per-node fp32 boxes, {|scene|max bits, error bits}
+	HostBvh host_build;                             // the quality path's workspace: written by the host builder, read by nothing once its arrays are uploaded
+	DeviceArray<uint8_t> build_scratch;             // the device builder's working set (fpt_build_lbvh.hip), kept between builds; fpt_rt_set_build_mode(0) releases it
+	// part 2 of the contract: exact-size arrays, `fill(nodes.ptr, records.ptr)` writes them and returns once they are written, then the description
+	template <typename F> void replace(TreeInfo built, F&& fill)
+	{
+		valid = false; nodes.alloc(built.n_nodes); records.alloc(built.n_records);
+		fill(nodes.ptr, records.ptr);
+		info = std::move(built); valid = true;
+	}
+};
 } // namespace fpt
 
 struct fpt_context
@@ -115,18 +141,9 @@ struct fpt_context
 	std::string error;
 
 	// RT sub-boundary
-	fpt::HostBvh2 host_bvh;
-	fpt::DeviceArray<fpt::BvhNode8> d_nodes;            // the 8-wide compressed BVH (fpt_bvh.h)
-	fpt::DeviceArray<fpt::BvhTriangle> d_tris;
+	fpt::AccelTree tree;                                // the acceleration structure and everything that describes it
 	fpt::DeviceArray<uint32_t> d_counters;              // ticket dispensers + queue sizes, zeroed per pass
 	fpt::DeviceArray<unsigned long long> d_trace_stats;
-	bool has_geometry = false;
-	uint32_t build_mode = 0;                             // fpt_rt_set_build_mode: 0 = quality (host: binned SAH + re-insertion + collapse), 1 = fast (device: Morton radix tree + collapse),
-	                                                     // 2 = trbvh (device: Morton radix tree + treelet restructuring + collapse)
-	// device-side refit (fpt_build.hip): per-record and per-node fp32 boxes, {|scene|max bits, error bits}
-	fpt::DeviceArray<float> d_refit_tri_box, d_refit_node_box;
-	fpt::DeviceArray<uint32_t> d_refit_scan;
-	fpt::DeviceArray<uint8_t> d_build_scratch;           // the device builder's working set (fpt_build_lbvh.hip), kept between builds
 
 	// sequence
 	fpt::CrtRand crt_rand;
@@ -308,9 +325,10 @@ inline fpt::FrameBufferDev fb_dev(const fpt_framebuffer_view& v)
 }
 
 inline double wall_seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-// fpt_build_lbvh.hip: the device-side builds (Morton radix tree [mode 2: restructured by treelets] -> SAH-optimal 8-wide collapse); mode = fpt_rt_set_build_mode's 1 or 2;
-// false = the tree needs more stack than the kernel has: use the host builder
-namespace fpt { bool build_acceleration_device(fpt_context* ctx, uint32_t tri_count, const int32_t* d_idx, uint32_t vertex_count, const float* d_vtx, uint32_t stack_limit, uint32_t mode); }
+// fpt_build_lbvh.hip: the device-side builds (Morton radix tree [mode 2: restructured by treelets] -> SAH-optimal 8-wide collapse) into ctx->tree; mode =
+// fpt_rt_set_build_mode's 1 or 2; false = the tree needs more stack than the kernel has (ctx->tree is as it was): use the host builder.  fpt_build.hip: the refit of ctx->tree
+namespace fpt { bool build_acceleration_device(fpt_context* ctx, uint32_t tri_count, const int32_t* d_idx, uint32_t vertex_count, const float* d_vtx, uint32_t stack_limit, uint32_t mode);
+                void refit_acceleration_device(fpt_context* ctx, uint32_t tri_count, const int32_t* d_idx, uint32_t vertex_count, const float* d_vtx); }
 
 // launch timing.  Profiling level 2 (fpt_pt_set_profiling): events are recorded around the launch on its stream and read back after the timed region
 // (fpt_pt_collect_timings, fpt_pt_launch_list), so measuring costs no host synchronisation.  Level 1, for a caller that passes `t_ms` (the PT's stats):
@@ -342,9 +360,9 @@ inline void timed_launch(fpt_context* ctx, int bucket, hipStream_t s, F&& launch
 inline fpt::TraceParams trace_params(fpt_context* ctx, fpt::PassCounters& cnt)
 {
 	fpt::TraceParams p; std::memset(&p, 0, sizeof(p));
-	p.bvh.nodes = reinterpret_cast<const uint4*>(ctx->d_nodes.ptr);
-	p.bvh.tris = reinterpret_cast<const float4*>(ctx->d_tris.ptr);
-	p.n_nodes = ctx->host_bvh.device_nodes;
+	p.bvh.nodes = reinterpret_cast<const uint4*>(ctx->tree.nodes.ptr);
+	p.bvh.tris = reinterpret_cast<const float4*>(ctx->tree.records.ptr);
+	p.n_nodes = ctx->tree.info.n_nodes;
 	p.work_counter = cnt.ticket();
 	p.stats = ctx->d_trace_stats.ptr;
 	return p;

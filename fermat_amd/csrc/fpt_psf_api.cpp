@@ -116,7 +116,7 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 {
 		fpt_context::PsfState& ps = ctx->psf;
 		require(ps.ready && ctx->pt_ready, "fpt_psfpt_render: fpt_psfpt_init has not been called");
-		require(ctx->has_geometry && ctx->has_emitters, "fpt_psfpt_render: geometry / mesh lights are not initialised");
+		require(ctx->tree.valid && ctx->has_emitters, "fpt_psfpt_render: geometry / mesh lights are not initialised");
 		const bool batched = n_passes > 1;
 		require(!batched || (n_passes <= ps.max_batch && !ps.sharded), "fpt_psfpt_render_batch: more passes than fpt_psfpt_set_batch sized the storage for (or a sharded context)");
 		// the queues and the log are shared with the plain path tracer: a later fpt_pt_set_batch / fpt_pt_set_deferred may have re-shaped them (no blend cells, fewer

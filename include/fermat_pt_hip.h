@@ -116,7 +116,9 @@ int         fpt_synchronize(fpt_context* ctx);
 /* ---- ray-tracing sub-boundary : struct RTContext (src/rt.h:55-105) ---------------------------------------------------- */
 /* RTContext::create_geometry (src/rt.h:60-69, src/rt.cpp:284-331): builds the acceleration structure over the caller's device mesh -- on the
  * host: binned-SAH binary tree, insertion-based optimisation, SAH-optimal collapse into the 8-wide compressed tree the kernels walk.
- * Unlike OptiX the acceleration structure keeps its own pre-transformed triangle copy; d_idx/d_vtx need not stay alive. */
+ * Unlike OptiX the acceleration structure keeps its own pre-transformed triangle copy; d_idx/d_vtx need not stay alive.
+ * All or nothing: a call that is refused for a reason known before the tree is touched (null mesh, index out of range, infinite vertex, a tree too deep for the
+ * kernel's stack) leaves the previous geometry in place and usable; a failure while the tree is being replaced leaves the context without geometry. */
 int fpt_rt_create_geometry(fpt_context* ctx, uint32_t tri_count, const int32_t* d_idx /*int4*/, uint32_t vertex_count, const float* d_vtx /*float4*/);
 /* Build mode of fpt_rt_create_geometry (round 6).  0 = quality, the default: the mesh is copied to the host, binned-SAH + re-insertion + SAH-optimal 8-wide collapse on the
  * host's threads (0.34 s for 1.8 M triangles).  1 = fast: the whole build on the device -- Morton radix tree (as the reference's own GPU builder,
@@ -124,7 +126,7 @@ int fpt_rt_create_geometry(fpt_context* ctx, uint32_t tri_count, const int32_t* 
  * OptiX builds its Trbvh on the GPU, src/rt.cpp:307-322); the tree traverses slower.  2 = trbvh: the device build of mode 1 with the binary radix tree
  * restructured by treelets before the collapse (Karras & Aila, HPG 2013: three bottom-up passes, 7-leaf treelets, an exact SAH dynamic programme per treelet) -- a few
  * milliseconds more than mode 1 for a tree that needs fewer node steps per ray (DESIGN.md 5 has the measurements).  Results do not depend on the tree.
- * FPT_BVH_BUILD=quality|fast|trbvh overrides. */
+ * FPT_BVH_BUILD=quality|fast|trbvh overrides.  Mode 0 also releases the device builder's scratch (about 400 B per triangle, otherwise kept for the next device build). */
 int fpt_rt_set_build_mode(fpt_context* ctx, uint32_t mode);
 /* Refit (no counterpart in the reference, whose update_model rebuilds: src/renderer.cu:999-1017): the vertices of the mesh the tree was built over have MOVED and nothing
  * else changed (same triangle count, same indices).  Triangle records and every node's boxes are recomputed bottom-up in the existing topology ON THE DEVICE (round 6,

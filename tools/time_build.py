@@ -1,5 +1,5 @@
-import sys, time, numpy as np, ctypes as C, hashlib
-sys.path.insert(0,'/root/repo')
+import os, sys, time, numpy as np, ctypes as C, hashlib
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import fermat_amd as fa
 from fermat_amd import scene
 s = getattr(scene, sys.argv[1] if len(sys.argv)>1 else 'bathroom2_standin')()
