@@ -634,7 +634,7 @@ static void render_lane(fpt_context* ctx, const LaneRefs& L, uint32_t instance, 
 			if (view->dir_lights_count)
 			{
 				const TraceParams sp = shadow_params(qsd, bounce);
-				timed_launch(ctx, 2, s, [&] { launch_trace_shadow(sp, true, ctx->counting, trace_grid, s); }, t_ms);
+				timed_launch(ctx, 2, s, [&] { if (batched) launch_trace_shadow_log(sp, ctx->counting, trace_grid, s); else launch_trace_shadow(sp, true, ctx->counting, trace_grid, s); }, t_ms);
 			}
 			if (bounce + 1 < opt.max_path_length)
 			{
@@ -642,12 +642,12 @@ static void render_lane(fpt_context* ctx, const LaneRefs& L, uint32_t instance, 
 				// shadow rays fused with solve_occlusion (RTContext::trace_shadow + solve_occlusion)
 				TraceParams mp = shadow_params(qs, bounce);
 				mp.rays = qout.rays; mp.hits = qout.hits; mp.count_ptr = qout.size;
-				timed_launch(ctx, 1, s, [&] { launch_trace_mixed(mp, ctx->counting, trace_grid, s); }, t_ms);
+				timed_launch(ctx, 1, s, [&] { if (batched) launch_trace_mixed_log(mp, ctx->counting, trace_grid, s); else launch_trace_mixed(mp, ctx->counting, trace_grid, s); }, t_ms);
 			}
 			else if (sh.do_nee)
 			{
 				const TraceParams sp = shadow_params(qs, bounce);
-				timed_launch(ctx, 2, s, [&] { launch_trace_shadow(sp, true, ctx->counting, trace_grid, s); }, t_ms);
+				timed_launch(ctx, 2, s, [&] { if (batched) launch_trace_shadow_log(sp, ctx->counting, trace_grid, s); else launch_trace_shadow(sp, true, ctx->counting, trace_grid, s); }, t_ms);
 			}
 			if (sync_mode)
 			{

@@ -25,7 +25,7 @@ struct PathQueue
 };
 struct ShadowQueue
 {
-	float4*   rays;        // origin | shadow mask , dir | PixelInfo
+	float4*   rays;        // origin | shadow mask , dir | PixelInfo  (the path tracer's passes in flight: dir | path index pidx of the sample's log cell, and NO w_d / w_g: ContribLog)
 	float4*   w_d;         // diffuse-channel weight, .w = pass offset k
 	float4*   w_g;         // glossy-channel weight
 	uint32_t* size;
@@ -88,6 +88,11 @@ __device__ __forceinline__ void fb_add(float4* channel, uint32_t pixel, f3 f, fl
 //   emissive     [bounce * cap + pidx]               xyz = the sample, w = the PixelInfo comp bits
 //   nee[kind]    [(bounce * cap + pidx) * 2 + {0,1}] w_d (w = comp bits), w_g;  kind 0 = directional light, 1 = mesh light / VPL
 //   mask         [pidx * mask_words + (bit >> 5)]    bit = 3 * bounce + {0 emissive, 1 directional, 2 mesh}
+// Who writes what.  An emissive cell and its bit: the shading kernel (accumulate_emissive).  A nee cell of the path tracer's passes in flight: the SHADING kernel, for every
+// light sample it queues a shadow ray for (fpt_pt.hip write_shadow_entry_logged) -- the cell belongs to (pass, slot, bounce, kind), all known there; its bit: the TRAVERSAL
+// kernel, when the shadow ray retires unoccluded (log_mark_fused below; the ray's dir.w carries pidx).  A cell whose bit is clear -- an occluded sample's, or one left by an
+// earlier batch -- is never read: the merge looks at the bits, clears them, and reads only the cells they name.  The PSFPT writes cell and bit together from its resolve
+// (fpt_psf.h), as the path tracer did until round 9 (accumulate_nee_fused: still the one-pass route's, which has no log and adds the sample to the frame).
 // The PSFPT's passes in flight use the same log with one more kind: the blend of a pixel's cache references, which a pass applies bounce by bounce AFTER
 // all of its bounces' samples:
 //   blend        [(bounce * cap + pidx) * 3 + {0,1,2}] the clamped COMPOSITED term, cell x w_d, cell x w_g (w of the first = comp bits);  bit = 3 * n_bounces + bounce
@@ -242,6 +247,14 @@ __device__ __forceinline__ void accumulate_nee_fused(const FusedResolve* F, uint
 	__hip_atomic_fetch_or(load_launch_constant(&F->log.mask) + size_t(pidx) * load_launch_constant(&F->log.mask_words) + (bit >> 5), 1u << (bit & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The retirement of an unoccluded shadow ray whose sample the shading kernel has already written into its cell (fpt_trace.hip MODE_MIXED_LOG / MODE_ANY_LOG): the cell's
+// bit, by the same atomic OR nothing waits for.  Until this bit is set the cell's contents mean nothing to the merge, so an occluded sample's cell is simply never read
+__device__ __forceinline__ void log_mark_fused(const FusedResolve* F, uint32_t pidx)
+{
+	const uint32_t bit = 3u * load_launch_constant(&F->bounce) + 1u + load_launch_constant(&F->kind);
+	__hip_atomic_fetch_or(load_launch_constant(&F->log.mask) + size_t(pidx) * load_launch_constant(&F->log.mask_words) + (bit >> 5), 1u << (bit & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 uint32_t trace_blocks_per_cu();
 uint32_t trace_stack_entries();      // capacity of the traversal stack (LDS + scratch levels); fpt_rt_create_geometry checks the tree's bound against it
 void launch_trace_closest(const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream);                         // the RT boundary's rays: tmin / tmax in the .w words
@@ -249,6 +262,8 @@ void launch_trace_shadow(const TraceParams& p, bool fused_resolve, bool counted,
 void launch_trace_closest_queue(const TraceParams& p, bool primary, bool counted, uint32_t n_blocks, hipStream_t stream);     // a renderer's path queue (PathQueue): primary or scattered rays
 void launch_trace_shadow_queue(const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream);                    // a renderer's shadow queue (ShadowQueue), results written to p.hits
 void launch_trace_mixed(const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream);
+void launch_trace_mixed_log(const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream);    // launch_trace_mixed / launch_trace_shadow(fused) for the path tracer's passes in flight: the shadow
+void launch_trace_shadow_log(const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream);   // rays' samples are in the log already (dir.w = path index), an unoccluded one sets its bit
 void launch_trace_mixed_psf(const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream);   // p.fused = a ResolveParams block (fpt_kernels.h)
 void launch_trace_mixed_hits(const TraceParams& p, float4* shadow_hits, bool counted, uint32_t n_blocks, hipStream_t stream);   // closest-hit rays -> p.hits, the any-hit rays of p.shadow_rays -> shadow_hits (written, not resolved)
 // fpt_build.hip: the device-side refit of the 8-wide tree (fpt_rt_refit_geometry); d_scan = {bits of |scene|max, error bits}, boxes = 6 floats each

@@ -168,6 +168,23 @@ __device__ __forceinline__ void write_shadow_entry(const ShadowQueue& q, uint32_
 	q.w_d[slot] = make_float4(pl.w_d.x, pl.w_d.y, pl.w_d.z, as_f32(batched ? pass_k : 0u));
 	q.w_g[slot] = make_float4(pl.w_g.x, pl.w_g.y, pl.w_g.z, 0.0f);
 }
+// The path tracer's passes in flight: the sample goes straight to where accumulate_nee would put it once the ray is found unoccluded -- the path's cell of the contribution
+// log (fpt_device.h ContribLog), which belongs to (pass, slot, bounce, kind), all known here -- and the queue entry is the ray alone, 32 B, with the cell's path index in dir.w
+// where PixelInfo rides otherwise.  The traversal kernel then adds the one thing only it knows, the cell's mask bit (fpt_trace.hip MODE_MIXED_LOG / MODE_ANY_LOG): until
+// round 9 it read w_d, w_g and PixelInfo back from the queue and stored the same 32 B into this cell from inside the traversal.  The bit is NOT set here: a cell without its
+// bit is never read, so an occluded sample's cell is dead weight that the path's next sample of this bounce and kind overwrites.
+__device__ __forceinline__ void write_shadow_entry_logged(const PassInfo& ps, const ContribLog& log, uint32_t bounce, uint32_t kind, const ShadowQueue& q, uint32_t slot, const ShadowPayload& pl,
+                                                          uint32_t mask, uint32_t pixel_info, uint32_t pass_k)
+{
+	const uint32_t pidx = pass_k * ps.acc_stride + (pixel_info & 0x7FFFFFFu);
+	float4* cell = log.nee[kind] + (size_t(bounce) * log.cap + pidx) * 2;
+	// non-temporal stores: the cell is read once, by the merge, a whole batch later, and from the second bounce on the lanes' cells lie apart (shading -3 %, EXPERIMENTS B5)
+	typedef float v4f __attribute__((ext_vector_type(4)));
+	__builtin_nontemporal_store(v4f{ pl.w_d.x, pl.w_d.y, pl.w_d.z, as_f32((pixel_info >> 27) & 0xFu) }, reinterpret_cast<v4f*>(cell));
+	__builtin_nontemporal_store(v4f{ pl.w_g.x, pl.w_g.y, pl.w_g.z, 0.0f }, reinterpret_cast<v4f*>(cell) + 1);
+	q.rays[2 * size_t(slot)]     = make_float4(pl.org.x, pl.org.y, pl.org.z, as_f32(mask));
+	q.rays[2 * size_t(slot) + 1] = make_float4(pl.dir.x, pl.dir.y, pl.dir.z, as_f32(pidx));
+}
 
 // Two blocks of shade_kernel that the vertex probe (debug_vertex_kernel) runs as they are.  They are macros, expanded in place, because the same bodies as
 // __forceinline__ functions changed shade_kernel's block layout (same operations, other ISA); expanded in place the kernel's instructions are unchanged.
@@ -414,7 +431,12 @@ void shade_kernel(const ShadeParams P)
 		ShadowPayload pl; bool want = false;
 		if (active) FPT_DIRECTIONAL_LIGHT_SAMPLE(want, P, bsdf, vt, sp, in, ray_dir, w, z[2], pl, psf_mode, mat_diffuse, nullptr)
 		const uint32_t qslot = block_append_slot(P.shadow_dir.size, want, sc_dir);
-		if (want) { write_shadow_entry(P.shadow_dir, qslot, pl, 0x1u, pixel_info, P.pass.n_passes > 1, slot.k); if (PSF) P.shadow_dir.vinfo[qslot] = vinfo; }
+		if (want)
+		{
+			if (!PSF && P.pass.n_passes > 1) write_shadow_entry_logged(P.pass, P.log, P.bounce, 0u, P.shadow_dir, qslot, pl, 0x1u, pixel_info, slot.k);
+			else write_shadow_entry(P.shadow_dir, qslot, pl, 0x1u, pixel_info, P.pass.n_passes > 1, slot.k);
+			if (PSF) P.shadow_dir.vinfo[qslot] = vinfo;
+		}
 	}
 	// ---- next-event estimation on the mesh emitters (:991-1106) ----
 	if (!(FPT_SHADE_SKIP & 2) && P.do_nee)
@@ -426,7 +448,12 @@ void shade_kernel(const ShadeParams P)
 			want = light_sample(P, bsdf, vt, sp, in, ray_dir, w, lp.position, lp.normal, lp.radiance, lp.pdf, true, 1.0e-4f, pl, psf_mode, mat_diffuse);
 		}
 		const uint32_t qslot = block_append_slot(P.shadow.size, want, sc_nee);
-		if (want) { write_shadow_entry(P.shadow, qslot, pl, 0x2u, pixel_info, P.pass.n_passes > 1, slot.k); if (PSF) P.shadow.vinfo[qslot] = vinfo; }
+		if (want)
+		{
+			if (!PSF && P.pass.n_passes > 1) write_shadow_entry_logged(P.pass, P.log, P.bounce, 1u, P.shadow, qslot, pl, 0x2u, pixel_info, slot.k);
+			else write_shadow_entry(P.shadow, qslot, pl, 0x2u, pixel_info, P.pass.n_passes > 1, slot.k);
+			if (PSF) P.shadow.vinfo[qslot] = vinfo;
+		}
 	}
 	{
 		const float4 a = park[0][threadIdx.x], b = park[1][threadIdx.x], c = park[2][threadIdx.x];

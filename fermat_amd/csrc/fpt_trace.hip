@@ -62,14 +62,20 @@ static constexpr int REFILL_MIN  = FPT_REFILL_MIN;       // refill a wave once t
 static constexpr uint32_t TICKET_SHARDS = 8;             // one ticket counter per XCD-sized share of the waves
 static constexpr uint32_t TICKET_PAD    = 32;            // counters sit 128 B apart: atomics on one cache line serialise chip-wide
 
-enum TraceMode { MODE_CLOSEST = 0, MODE_ANY = 1, MODE_ANY_FUSED = 2, MODE_MIXED = 3, MODE_MIXED_PSF = 4, MODE_MIXED_HITS = 5, MODE_CLOSEST_QP = 6, MODE_CLOSEST_QS = 7, MODE_ANY_Q = 8 };
+enum TraceMode { MODE_CLOSEST = 0, MODE_ANY = 1, MODE_ANY_FUSED = 2, MODE_MIXED = 3, MODE_MIXED_PSF = 4, MODE_MIXED_HITS = 5, MODE_CLOSEST_QP = 6, MODE_CLOSEST_QS = 7, MODE_ANY_Q = 8,
+                 MODE_MIXED_LOG = 9, MODE_ANY_LOG = 10 };
 // *_QP / *_QS / ANY_Q (round 5): the rays of a renderer's own queues (fpt_device.h PathQueue / ShadowQueue), whose .w words carry PixelInfo and the pass offset instead of
 // tmin / tmax: primary rays (0, 1e34), scattered rays (1e-3, 1e8), shadow rays (mask, 0.9999).  MIXED, MIXED_PSF and ANY_FUSED read such queues too.
-constexpr bool closest_from_queue(int m) { return m == MODE_MIXED || m == MODE_MIXED_PSF || m == MODE_CLOSEST_QP || m == MODE_CLOSEST_QS; }
-constexpr bool any_from_queue(int m) { return m == MODE_ANY_FUSED || m == MODE_MIXED || m == MODE_MIXED_PSF || m == MODE_ANY_Q; }
+// MIXED_LOG / ANY_LOG: MIXED / ANY_FUSED for the path tracer's passes in flight.  The shading kernel has already written the sample into its cell of the contribution log
+// (fpt_pt.hip write_shadow_entry) and the shadow ray's dir.w carries the path index pidx of that cell instead of PixelInfo: an unoccluded ray retires by setting the cell's
+// mask bit and nothing else -- no load, no cell store, no wait.  The numbers of the older modes stay: tests/test_trace_retire_isa.py names them.
+constexpr bool closest_from_queue(int m) { return m == MODE_MIXED || m == MODE_MIXED_PSF || m == MODE_MIXED_LOG || m == MODE_CLOSEST_QP || m == MODE_CLOSEST_QS; }
+constexpr bool any_from_queue(int m) { return m == MODE_ANY_FUSED || m == MODE_MIXED || m == MODE_MIXED_PSF || m == MODE_ANY_Q || m == MODE_MIXED_LOG || m == MODE_ANY_LOG; }
+constexpr bool any_to_log(int m) { return m == MODE_MIXED_LOG || m == MODE_ANY_LOG; }
+constexpr bool any_only_from_shadow_queue(int m) { return m == MODE_ANY_FUSED || m == MODE_ANY_LOG; }
 // MIXED_PSF: MIXED with the path-space-filtering resolve (`fused` points to a ResolveParams); MIXED_HITS: the any-hit rays' results are WRITTEN
 // (`fused` points to their float4 Hit array) instead of resolved -- the bidirectional path tracer's connections, which its own kernel adds in order
-constexpr bool mode_is_mixed(int m) { return m == MODE_MIXED || m == MODE_MIXED_PSF || m == MODE_MIXED_HITS; }
+constexpr bool mode_is_mixed(int m) { return m == MODE_MIXED || m == MODE_MIXED_PSF || m == MODE_MIXED_HITS || m == MODE_MIXED_LOG; }
 
 struct LaneRay
 {
@@ -211,7 +217,7 @@ void trace_kernel(const TraceParams P)
 	__syncthreads();
 	// index space: [0, n_first) = the primary ray array (closest-hit rays, or the any-hit rays in MODE_ANY*),
 	//              [n_first, n_rays) = the fused shadow queue (MODE_MIXED only)
-	const uint32_t n_first = (MODE == MODE_ANY_FUSED) ? *P.shadow_size : (P.count_ptr ? *P.count_ptr : P.count);
+	const uint32_t n_first = any_only_from_shadow_queue(MODE) ? *P.shadow_size : (P.count_ptr ? *P.count_ptr : P.count);
 	const uint32_t n_rays  = mode_is_mixed(MODE) ? n_first + *P.shadow_size : n_first;
 
 	const uint32_t shard_size = (n_rays + TICKET_SHARDS - 1) / TICKET_SHARDS;
@@ -227,7 +233,7 @@ void trace_kernel(const TraceParams P)
 
 	bool     have = false;          // this lane owns a ray
 	bool     dry  = false;          // wave-uniform: every shard is exhausted
-	bool     any  = (MODE == MODE_ANY || MODE == MODE_ANY_FUSED || MODE == MODE_ANY_Q);     // this lane's ray is an any-hit (shadow) ray
+	bool     any  = (MODE == MODE_ANY || MODE == MODE_ANY_FUSED || MODE == MODE_ANY_Q || MODE == MODE_ANY_LOG);     // this lane's ray is an any-hit (shadow) ray
 	uint32_t ray_index = 0;
 	LaneRay  r;
 	uint32_t ray_mask = 0;
@@ -261,6 +267,11 @@ void trace_kernel(const TraceParams P)
 				{
 					float4* shadow_hits = reinterpret_cast<float4*>(const_cast<FusedResolve*>(P.fused));
 					shadow_hits[ray_index] = occluded ? make_float4(1.0f, as_f32(1u), 0.0f, 0.0f) : make_float4(-1.0f, as_f32(0xFFFFFFFFu), 0.0f, 0.0f);
+				}
+				else if (any_to_log(MODE))
+				{
+					// the sample already sits in its cell: ray_index is the cell's path index (set at the refill from the ray's dir.w)
+					if (!occluded) log_mark_fused(P.fused, ray_index);
 				}
 				else if (MODE == MODE_ANY_FUSED || MODE == MODE_MIXED)
 				{
@@ -326,7 +337,7 @@ void trace_kernel(const TraceParams P)
 				{
 					const uint32_t i = c_next + rank;
 					if (mode_is_mixed(MODE)) any = i >= n_first;
-					const float4* src = (MODE == MODE_ANY_FUSED) ? P.shadow_rays + 2 * size_t(i)
+					const float4* src = any_only_from_shadow_queue(MODE) ? P.shadow_rays + 2 * size_t(i)
 					                  : (mode_is_mixed(MODE) && any) ? P.shadow_rays + 2 * size_t(i - n_first) : P.rays + 2 * size_t(i);
 					const float4 ro = src[0];
 					const float4 rd = src[1];
@@ -342,7 +353,8 @@ void trace_kernel(const TraceParams P)
 					r.tmin = any ? 0.0f : (closest_from_queue(MODE) ? q_tmin : ro.w);
 					r.tmax = any ? (any_from_queue(MODE) ? QUEUE_SHADOW_TMAX : rd.w) : (closest_from_queue(MODE) ? q_tmax : rd.w);
 					best_t = r.tmax; best_id = -1; best_bu = 0.0f; best_bv = 0.0f; occluded = false;
-					ray_index = (mode_is_mixed(MODE) && any) ? i - n_first : i;
+					// (an any-hit lane's ray_index is read by the retire block alone: with the samples in the log it is the path index the shading kernel left in dir.w)
+					ray_index = (any_to_log(MODE) && any) ? as_u32(rd.w) : (mode_is_mixed(MODE) && any) ? i - n_first : i;
 					grp = make_uint2(0u, 0x80000000u);           // the root: "child 0 of base 0", no siblings
 					sp = 0; have = true; tri_bits = 0;
 					if (COUNTED) cnt[any ? 5 : 2]++;
@@ -478,6 +490,8 @@ void launch_trace_closest_queue(const TraceParams& p, bool primary, bool counted
 }
 void launch_trace_shadow_queue(const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream) { launch_mode<MODE_ANY_Q>(p, counted, n_blocks, stream); }
 void launch_trace_mixed(const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream) { launch_mode<MODE_MIXED>(p, counted, n_blocks, stream); }
+void launch_trace_mixed_log(const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream) { launch_mode<MODE_MIXED_LOG>(p, counted, n_blocks, stream); }
+void launch_trace_shadow_log(const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream) { launch_mode<MODE_ANY_LOG>(p, counted, n_blocks, stream); }
 void launch_trace_mixed_psf(const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream) { launch_mode<MODE_MIXED_PSF>(p, counted, n_blocks, stream); }
 void launch_trace_mixed_hits(const TraceParams& p, float4* shadow_hits, bool counted, uint32_t n_blocks, hipStream_t stream)
 { TraceParams q = p; q.fused = reinterpret_cast<const FusedResolve*>(shadow_hits); launch_mode<MODE_MIXED_HITS>(q, counted, n_blocks, stream); }
