@@ -161,7 +161,8 @@ ENTRY_POINTS = ["fpt_create", "fpt_destroy", "fpt_last_error", "fpt_stream", "fp
                 "fpt_comm_unique_id", "fpt_comm_last_error", "fpt_comm_init", "fpt_comm_adopt", "fpt_comm_destroy", "fpt_comm_info", "fpt_gather_framebuffer",
                 "fpt_bpt_allreduce_splats", "fpt_comm_selftest", "fpt_pt_last_union_ms", "fpt_pt_lane_count", "fpt_pt_set_lanes", "fpt_pt_set_deferred", "fpt_pt_flush", "fpt_pt_launch_list", "fpt_set_tile_lists", "fpt_gather_pack", "fpt_gather_unpack", "fpt_device_memory", "fpt_bytes_per_path_in_flight", "fpt_bpt_set_shared_light_vertices", "fpt_bpt_export_light_vertices", "fpt_bpt_import_light_vertices", "fpt_bpt_exchange_light_vertices", "fpt_bpt_finish",
                 "fpt_multiply_frame", "fpt_clamp_frame", "fpt_sequence_device_view", "fpt_mesh_lights_device_view", "fpt_mesh_invalidate", "fpt_rt_refit_geometry", "fpt_debug_refit_bvh",
-                "fpt_debug_build_emitter_tables", "fpt_clear_gbuffer", "fpt_rt_download_bvh", "fpt_mesh_lights_update", "fpt_rt_set_build_mode"]
+                "fpt_debug_build_emitter_tables", "fpt_clear_gbuffer", "fpt_rt_download_bvh", "fpt_mesh_lights_update", "fpt_rt_set_build_mode",
+                "fpt_debug_psf", "fpt_psfpt_debug_set_table_log2"]
 
 
 def kernel_source_hash():
@@ -425,6 +426,10 @@ class Renderer:
         self._check(self.L.fpt_psfpt_finish(self.ctx, C.byref(self.view)))
         if sync:
             self.synchronize()
+
+    def psf_debug_set_table_log2(self, log2_size):
+        """tests of the cache under load: 2^log2_size slots (8..24) instead of 2^24; before the first render, psf_set_batch and psf_set_sharded"""
+        self._check(self.L.fpt_psfpt_debug_set_table_log2(self.ctx, C.c_uint32(log2_size)))
 
     def psf_cells(self):
         """occupied cache cells sorted by key: keys, sample counts, 2^-32 fixed-point sums"""
@@ -814,6 +819,49 @@ class Renderer:
                                             C.c_void_p(dtex.data_ptr() if dtex is not None else None), C.c_uint32(len(textures) if textures is not None else 0),
                                             C.c_void_p(dr.data_ptr()), C.c_uint32(0 if broadcast else 48), C.c_void_p(out.data_ptr())))
         return out[:n * 32].reshape(n, 32).cpu().numpy()
+
+    def debug_psf(self, op, data, size=0, firefly=100.0, touched=False):
+        """fpt_debug_psf (layouts: include/fermat_pt_hip.h).  op 0: (n, 32) float32 records -> uint64 keys.  op 1: uint64 keys, size = log2 of the table ->
+        dict(slots, table[, touched, touched_n]).  op 2: (n, 4) float32 (slot bits, value), size = cells -> dict(cells (size, 4) int64, mean (size, 3) float32).
+        op 3: (n, 4) int64 cells -> (n, 3) float32 means."""
+        torch = self.torch
+        up = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1)).to(self.dev)  # noqa: E731
+        zeros = lambda nbytes: torch.zeros(max(int(nbytes), 8), dtype=torch.uint8, device=self.dev)  # noqa: E731
+        down = lambda t, dt, n: t.cpu().numpy()[:n * np.dtype(dt).itemsize].view(dt).copy()  # noqa: E731
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
+        o0 = o1 = tl = tn = None
+        if op == 0:
+            a = np.ascontiguousarray(data, np.float32).reshape(-1, 32); n = len(a)
+            o0 = zeros(8 * n)
+        elif op == 1:
+            a = np.ascontiguousarray(data, np.uint64).reshape(-1); n = len(a); size = int(size)
+            assert 1 <= size <= 16
+            o0 = zeros(4 * n); o1 = zeros(8 << size)
+            if touched:
+                tl = zeros(4 << size); tn = zeros(4)
+        elif op == 2:
+            a = np.ascontiguousarray(data, np.float32).reshape(-1, 4); n = len(a); size = int(size)
+            assert 1 <= size <= 65536
+            o0 = zeros(32 * size); o1 = zeros(12 * size)
+        elif op == 3:
+            a = np.ascontiguousarray(data, np.int64).reshape(-1, 4); n = size = len(a)
+            o1 = zeros(12 * n)
+        else:
+            raise ValueError("unknown op")
+        d_in = up(a) if n else zeros(8)
+        torch.cuda.synchronize(self.dev)
+        self._check(self.L.fpt_debug_psf(self.ctx, C.c_int(op), C.c_uint32(1 if touched else 0), C.c_uint32(n), ptr(d_in), C.c_uint32(size), C.c_float(firefly),
+                                         ptr(o0), ptr(o1), ptr(tl), ptr(tn)))
+        if op == 0:
+            return down(o0, np.uint64, n)
+        if op == 1:
+            out = dict(slots=down(o0, np.uint32, n), table=down(o1, np.uint64, 1 << size))
+            if touched:
+                out["touched"] = down(tl, np.uint32, 1 << size); out["touched_n"] = int(down(tn, np.uint32, 1)[0])
+            return out
+        if op == 2:
+            return dict(cells=down(o0, np.int64, 4 * size).reshape(size, 4), mean=down(o1, np.float32, 3 * size).reshape(size, 3))
+        return down(o1, np.float32, 3 * n).reshape(n, 3)
 
     def reinit_emitters(self, n_vpls):
         """fpt_mesh_lights_init again with another VPL count (the probe's emitter tables)"""

@@ -20,6 +20,8 @@ void launch_debug_bsdf(int op, uint32_t flags, uint32_t n, const fpt_material* m
 // ... and the vertex probe's
 void launch_debug_vertex(int op, uint32_t n, const fpt_rendering_context_view& view, const fpt_material* mats, uint32_t n_mats, const fpt_texture* textures,
                          uint32_t n_textures, const EmitterView& em, const ShadeRecord* shade_records, const float* rec, uint32_t rec_stride, float* out, hipStream_t s);
+// ... and the path-space-filtering probe's
+void launch_debug_psf(int op, uint32_t n, const PsfDev& psf, uint32_t n_cells, const void* in, void* out0, float* out1, hipStream_t s);
 }
 
 namespace {
@@ -1053,6 +1055,44 @@ int fpt_debug_vertex(fpt_context* ctx, const fpt_rendering_context_view* view, i
 		const uint32_t n_tex = d_textures ? n_textures : view->num_textures;
 		launch_debug_vertex(op, n, *view, d_mats, n_mats, tex, n_tex, em, records, d_rec, rec_stride, d_out, ctx->stream);
 		FPT_HIP_CHECK(hipGetLastError()); FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	});
+}
+
+int fpt_debug_psf(fpt_context* ctx, int op, uint32_t flags, uint32_t n, const void* d_in, uint32_t size, float firefly, void* d_out0, void* d_out1,
+                  uint32_t* d_touched, uint32_t* d_touched_n)
+{
+	return guarded(ctx, [&] {
+		if (op < 0 || op > 3) throw std::runtime_error("fpt_debug_psf: unknown op");
+		if (n && !d_in) throw std::runtime_error("fpt_debug_psf: null input");
+		if ((op == 0 || op == 1) && n && !d_out0) throw std::runtime_error("fpt_debug_psf: null output");
+		if (op == 1 && (size < 1 || size > 16 || !d_out1)) throw std::runtime_error("fpt_debug_psf: the table op takes log2_size 1..16 and a table of that size");
+		if (op == 1 && (flags & 1u) && (!d_touched || !d_touched_n)) throw std::runtime_error("fpt_debug_psf: the touched variant needs the list and its count");
+		if (op == 2 && (size < 1 || size > 65536 || !d_out0)) throw std::runtime_error("fpt_debug_psf: the accumulate op takes 1..65536 cells and their array");
+		if (op == 3 && (size != n || (n && !d_out1))) throw std::runtime_error("fpt_debug_psf: the mean op takes one cell per element and their means");
+		PsfDev psf; std::memset(&psf, 0, sizeof(psf));
+		psf.firefly = firefly;
+		hipStream_t s = ctx->stream;
+		if (op == 1)
+		{
+			const size_t slots = size_t(1) << size;
+			psf.keys = static_cast<unsigned long long*>(d_out1); psf.log2_size = size;
+			FPT_HIP_CHECK(hipMemsetAsync(psf.keys, 0xFF, slots * sizeof(unsigned long long), s));
+			if (flags & 1u)
+			{
+				psf.touched = d_touched; psf.touched_n = d_touched_n;
+				FPT_HIP_CHECK(hipMemsetAsync(d_touched, 0xFF, slots * sizeof(uint32_t), s));
+				FPT_HIP_CHECK(hipMemsetAsync(d_touched_n, 0, sizeof(uint32_t), s));
+			}
+		}
+		if (op == 2)
+		{
+			psf.cells = static_cast<long long*>(d_out0);
+			FPT_HIP_CHECK(hipMemsetAsync(psf.cells, 0, size_t(size) * 4 * sizeof(long long), s));
+		}
+		if (n) launch_debug_psf(op, n, psf, size, d_in, d_out0, static_cast<float*>(d_out1), s);
+		// the accumulate op hands back the means of its cells as well, through the helper the blends use
+		if (op == 2 && d_out1) launch_debug_psf(3, size, psf, size, d_out0, nullptr, static_cast<float*>(d_out1), s);
+		FPT_HIP_CHECK(hipGetLastError()); FPT_HIP_CHECK(hipStreamSynchronize(s));
 	});
 }
 

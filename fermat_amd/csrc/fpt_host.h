@@ -200,7 +200,7 @@ struct fpt_context
 	// path-space filtering (PSFPT): hash table of cache cells + reference queue
 	struct PsfState
 	{
-		bool ready = false;
+		bool ready = false, rendered = false;       // rendered: a pass has run (fpt_psfpt_debug_set_table_log2 re-sizes the table only before)
 		fpt_psf_options opt{};
 		uint32_t log2_size = 0;
 		fpt::DeviceArray<unsigned long long> keys; fpt::DeviceArray<long long> cells;

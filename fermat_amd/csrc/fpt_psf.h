@@ -55,4 +55,11 @@ __device__ __forceinline__ void psf_resolve_sample(const ResolveParams& P, uint3
 	log_mark(P.log, pidx, 3u * P.bounce + 1u + P.kind);
 }
 
+// the estimate a cell holds: each 2^-32 fixed-point sum back in float, over the cell's sample count.  The caller has seen cell[3] != 0 (an empty cell holds no estimate).
+__device__ __forceinline__ f3 psf_cell_mean(const long long* cell)
+{
+	const float cw = float((unsigned long long)cell[3]);
+	return mk3(float(double(cell[0]) * (1.0 / 4294967296.0)) / cw, float(double(cell[1]) * (1.0 / 4294967296.0)) / cw, float(double(cell[2]) * (1.0 / 4294967296.0)) / cw);
+}
+
 } // namespace fpt

@@ -85,6 +85,22 @@ int fpt_psfpt_init(fpt_context* ctx, const fpt_pt_options* opts, const fpt_psf_o
 	});
 }
 
+int fpt_psfpt_debug_set_table_log2(fpt_context* ctx, uint32_t log2_size)
+{
+	return guarded(ctx, [&] {
+		fpt_context::PsfState& s = ctx->psf;
+		require(s.ready, "fpt_psfpt_debug_set_table_log2: fpt_psfpt_init has not been called");
+		require(!s.rendered && !s.sharded && s.max_batch <= 1, "fpt_psfpt_debug_set_table_log2: call it before the first render, fpt_psfpt_set_batch and fpt_psfpt_set_sharded");
+		require(log2_size >= 8 && log2_size <= 24, "fpt_psfpt_debug_set_table_log2: log2_size must be 8..24");
+		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+		s.log2_size = log2_size;
+		s.keys.alloc(size_t(1) << s.log2_size); s.cells.alloc((size_t(1) << s.log2_size) * 4);
+		FPT_HIP_CHECK(hipMemsetAsync(s.keys.ptr, 0xFF, (size_t(1) << s.log2_size) * sizeof(unsigned long long), ctx->stream));
+		FPT_HIP_CHECK(hipMemsetAsync(s.cells.ptr, 0, (size_t(1) << s.log2_size) * 4 * sizeof(long long), ctx->stream));
+		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	});
+}
+
 int fpt_psfpt_download_cells(fpt_context* ctx, uint64_t* h_keys, uint64_t* h_counts, int64_t* h_sums, uint32_t max_cells, uint32_t* n_cells)
 {
 	return guarded(ctx, [&] {
@@ -117,6 +133,7 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 		fpt_context::PsfState& ps = ctx->psf;
 		require(ps.ready && ctx->pt_ready, "fpt_psfpt_render: fpt_psfpt_init has not been called");
 		require(ctx->tree.valid && ctx->has_emitters, "fpt_psfpt_render: geometry / mesh lights are not initialised");
+		ps.rendered = true;
 		const bool batched = n_passes > 1;
 		require(!batched || (n_passes <= ps.max_batch && !ps.sharded), "fpt_psfpt_render_batch: more passes than fpt_psfpt_set_batch sized the storage for (or a sharded context)");
 		// the queues and the log are shared with the plain path tracer: a later fpt_pt_set_batch / fpt_pt_set_deferred may have re-shaped them (no blend cells, fewer

@@ -230,7 +230,7 @@ __device__ __forceinline__ unsigned long long spatial_hash(f3 Ppos, f3 N, f3 T, 
 	const uint32_t ilog = to_u32_sat(flog);
 	const float rlog = flog - float(ilog);
 	const uint32_t log_i = ilog + (s[5] < rlog ? 1u : 0u);
-	const uint32_t grid = 1u << log_i;
+	const uint32_t grid = 1u << (log_i & 31u);       // a level beyond 31 (a cone below 2^-32 of the scene, or 0) wraps: DEFINED here, the reference's shift is undefined there
 	// concentric disk sample (the same map as cosine_hemisphere's first two components)
 	const f3 dsk = cosine_hemisphere(s[0], s[1]);
 	const float rs = filter_radius * cone_radius;
@@ -545,8 +545,7 @@ __global__ void psf_blend_kernel(PsfDev psf, FrameBufferDev fb, float frame_weig
 		if (found) cell = psf.g_cells + 4 * size_t(h);
 	}
 	if (cell[3] == 0) return;                      // an empty cell holds no estimate (0 / 0)
-	const float cw = float((unsigned long long)cell[3]);
-	const f3 cv = mk3(float(double(cell[0]) * (1.0 / 4294967296.0)) / cw, float(double(cell[1]) * (1.0 / 4294967296.0)) / cw, float(double(cell[2]) * (1.0 / 4294967296.0)) / cw);
+	const f3 cv = psf_cell_mean(cell);
 	const uint32_t pixel_info = psf.ref_pixels[i];
 	const uint32_t pixel = pixel_info & 0x7FFFFFFu, comp = (pixel_info >> 27) & 0xFu;
 	const float4 wd4 = psf.ref_wd[i], wg4 = psf.ref_wg[i];
@@ -571,8 +570,7 @@ __global__ void psf_blend_batch_kernel(PsfDev psf, ContribLog log, uint32_t boun
 	const uint32_t comp = (pixel_info >> 27) & 0xFu;
 	const long long* cell = psf_pass_view(psf, sl.k).cells + 4 * size_t(cache & 0x1FFFFFFFu);
 	if (cell[3] == 0) return;                      // an empty cell holds no estimate (0 / 0): no blend cell, as psf_blend_kernel adds nothing
-	const float cw = float((unsigned long long)cell[3]);
-	const f3 cv = mk3(float(double(cell[0]) * (1.0 / 4294967296.0)) / cw, float(double(cell[1]) * (1.0 / 4294967296.0)) / cw, float(double(cell[2]) * (1.0 / 4294967296.0)) / cw);
+	const f3 cv = psf_cell_mean(cell);
 	const float4 wd4 = psf.ref_wd[i], wg4 = psf.ref_wg[i];
 	const f3 w_d = mk3(wd4.x, wd4.y, wd4.z), w_g = mk3(wg4.x, wg4.y, wg4.z);
 	const f3 w = ((comp & COMP_DIFFUSE_MASK) ? w_d : splat3(0.0f)) + ((comp & COMP_GLOSSY_MASK) ? w_g : splat3(0.0f));
@@ -1028,6 +1026,41 @@ __global__ void debug_vertex_kernel(int op, uint32_t n, fpt_rendering_context_vi
 	}
 }
 
+// Path-space-filtering probe (tests/test_psf_truth.py; the oracle's orc_psf_probe_n is its CPU twin): the key function, the table and the cell arithmetic that
+// shade_kernel<true>, the resolve and the blends run, on inputs a test chose.  One element per thread, all in ONE launch: the table's races are real.
+//   0 key:        in = 32 floats per element (P, N, T, B, bbox lo, bbox hi, s[6], cone radius, filter radius) -> out0 = the 64-bit key
+//   1 table:      in = one key per element -> out0 = psf_insert's slot, into the table psf.keys (psf.touched / touched_n: the creators' list, or null)
+//   2 accumulate: in = float4 per element (slot bits, value) -> psf.cells: the slot's count + 1, then psf_add(psf_clamp(value)); slots >= n_cells are skipped
+//   3 mean:       in = 4 x int64 per cell (three sums, count) -> out1 = psf_cell_mean, 3 floats per cell; a cell of count 0 is not divided (its floats stay as they are)
+__global__ void debug_psf_kernel(int op, uint32_t n, PsfDev psf, uint32_t n_cells, const void* __restrict__ in, void* __restrict__ out0, float* __restrict__ out1)
+{
+	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
+	if (i >= n) return;
+	if (op == 0)
+	{
+		const float* r = static_cast<const float*>(in) + size_t(i) * 32;
+		const float s[6] = { r[18], r[19], r[20], r[21], r[22], r[23] };
+		static_cast<unsigned long long*>(out0)[i] = spatial_hash(mk3(r[0], r[1], r[2]), mk3(r[3], r[4], r[5]), mk3(r[6], r[7], r[8]), mk3(r[9], r[10], r[11]),
+		                                                         mk3(r[12], r[13], r[14]), mk3(r[15], r[16], r[17]), s, r[24], r[25]);
+	}
+	else if (op == 1) static_cast<uint32_t*>(out0)[i] = psf_insert(psf, static_cast<const unsigned long long*>(in)[i]);
+	else if (op == 2)
+	{
+		const float4 r = static_cast<const float4*>(in)[i];
+		const uint32_t slot = as_u32(r.x);
+		if (slot >= n_cells) return;
+		atomicAdd(reinterpret_cast<unsigned long long*>(psf.cells + 4 * size_t(slot) + 3), 1ull);          // as shade_kernel counts the vertex it caches
+		psf_add(psf, slot, psf_clamp(psf, mk3(r.y, r.z, r.w)));
+	}
+	else if (op == 3)
+	{
+		const long long* cell = static_cast<const long long*>(in) + 4 * size_t(i);
+		if (cell[3] == 0) return;
+		const f3 m = psf_cell_mean(cell);
+		out1[3 * size_t(i)] = m.x; out1[3 * size_t(i) + 1] = m.y; out1[3 * size_t(i) + 2] = m.z;
+	}
+}
+
 // ---- launchers ----------------------------------------------------------------------------------------------------------
 static inline uint32_t blocks_for(uint32_t n, uint32_t b) { return n ? (n + b - 1) / b : 1; }
 
@@ -1080,5 +1113,7 @@ void launch_debug_bsdf(int op, uint32_t flags, uint32_t n, const fpt_material* m
 void launch_debug_vertex(int op, uint32_t n, const fpt_rendering_context_view& view, const fpt_material* mats, uint32_t n_mats, const fpt_texture* textures,
                          uint32_t n_textures, const EmitterView& em, const ShadeRecord* shade_records, const float* rec, uint32_t rec_stride, float* out, hipStream_t s)
 { hipLaunchKernelGGL(debug_vertex_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, op, n, view, mats, n_mats, textures, n_textures, em, shade_records, rec, rec_stride, out); }
+void launch_debug_psf(int op, uint32_t n, const PsfDev& psf, uint32_t n_cells, const void* in, void* out0, float* out1, hipStream_t s)
+{ hipLaunchKernelGGL(debug_psf_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, op, n, psf, n_cells, in, out0, out1); }
 
 } // namespace fpt

@@ -476,6 +476,23 @@ int fpt_debug_bsdf(fpt_context* ctx, int op, uint32_t flags, uint32_t n, const f
 int fpt_debug_vertex(fpt_context* ctx, const fpt_rendering_context_view* view, int op, uint32_t flags, uint32_t n, const fpt_material* d_mats, uint32_t n_mats,
                      const fpt_texture* d_textures, uint32_t n_textures, const float* d_rec, uint32_t rec_stride, float* d_out);
 
+/* Path-space-filtering probe: the key function, the open-addressing table and the cell arithmetic of `-psfpt` on inputs a test chose, through the functions the
+ * shading, resolve and blend kernels call.  DEVICE arrays; one element per thread, all elements in ONE launch.
+ *   0 key:        d_in 32 floats per element: [0..2] P, [3..5] N, [6..8] T, [9..11] B, [12..14] bbox lo, [15..17] bbox hi, [18..23] s[6], [24] cone radius,
+ *                 [25] filter radius -> d_out0 one uint64 key per element
+ *   1 table:      size = log2 of the table (1..16), d_in one uint64 key per element (duplicates allowed, n may exceed the capacity; ~0 is the empty mark, not a key)
+ *                 -> d_out0 one uint32 slot per element (0x1FFFFFFF = refused: the table was full), d_out1 the table's 2^size uint64 keys, cleared here before the
+ *                 inserts.  flags 1: with the list of created slots, d_touched (2^size uint32) and its count d_touched_n, both cleared here
+ *   2 accumulate: size = number of cells (1..65536), d_in 4 words per element: [0] # slot, [1..3] value; every element adds 1 to its slot's count, clamps its value
+ *                 (non-finite -> 0, min(v, firefly)) and adds it to the slot's sums -> d_out0 4 x int64 per cell (three 2^-32 fixed-point sums, count), cleared
+ *                 here first; d_out1 (may be NULL) 3 floats per cell: the cell's mean as the blends compute it (untouched where the count is 0)
+ *   3 mean:       size = n, d_in 4 x int64 per cell -> d_out1 3 floats per cell (untouched where the count is 0) */
+int fpt_debug_psf(fpt_context* ctx, int op, uint32_t flags, uint32_t n, const void* d_in, uint32_t size, float firefly, void* d_out0, void* d_out1,
+                  uint32_t* d_touched, uint32_t* d_touched_n);
+/* debug entry (tests of the cache under load): the cache of a context after fpt_psfpt_init and before its first render, fpt_psfpt_set_batch or
+ * fpt_psfpt_set_sharded, re-allocated with 2^log2_size slots (8..24) and cleared.  A table that fills up refuses further keys: their vertices stay uncached. */
+int fpt_psfpt_debug_set_table_log2(fpt_context* ctx, uint32_t log2_size);
+
 /* host-side probe of the acceleration-structure builder behind fpt_rt_create_geometry (no GPU, no context; HOST arrays in, HOST arrays out):
  * *node_words = 32-bit words per node (20: the 80-byte 8-wide compressed node, see fermat_amd/csrc/fpt_bvh.h), records = 48-byte triangle
  * records {v0, e1 = v1 - v0, e2 = v2 - v0, triangle id, shadow mask, delta} -- delta: the constant part of the tolerance of the intersector's box clause for this triangle,

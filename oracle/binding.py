@@ -289,6 +289,39 @@ class OraclePT:
         lib().orc_pt_filter(self.h, C.c_uint32(instance))
 
 
+def psf_probe(op, data, size=0, firefly=100.0, touched=False):
+    """orc_psf_probe_n, the twin of fermat_amd's Renderer.debug_psf: the same arguments, the same results"""
+    if op == 0:
+        a = np.ascontiguousarray(data, np.float32).reshape(-1, 32); n = len(a)
+        o0 = np.zeros(n, np.uint64); o1 = tl = None
+    elif op == 1:
+        a = np.ascontiguousarray(data, np.uint64).reshape(-1); n = len(a); size = int(size)
+        assert 1 <= size <= 16
+        o0 = np.zeros(n, np.uint32); o1 = np.zeros(1 << size, np.uint64); tl = np.zeros(1 << size, np.uint32) if touched else None
+    elif op == 2:
+        a = np.ascontiguousarray(data, np.float32).reshape(-1, 4); n = len(a); size = int(size)
+        assert 1 <= size <= 65536
+        o0 = np.zeros((size, 4), np.int64); o1 = np.zeros((size, 3), np.float32); tl = None
+    elif op == 3:
+        a = np.ascontiguousarray(data, np.int64).reshape(-1, 4); n = size = len(a)
+        o0 = None; o1 = np.zeros((n, 3), np.float32); tl = None
+    else:
+        raise ValueError("unknown op")
+    tn = C.c_uint32(0)
+    ptr = lambda x: C.c_void_p(x.ctypes.data if x is not None and x.size else None)  # noqa: E731
+    lib().orc_psf_probe_n(C.c_int32(op), C.c_uint32(1 if touched else 0), C.c_uint32(n), ptr(a), C.c_uint32(size), C.c_float(firefly), ptr(o0), ptr(o1), ptr(tl), C.byref(tn))
+    if op == 0:
+        return o0
+    if op == 1:
+        out = dict(slots=o0, table=o1)
+        if touched:
+            out["touched"] = tl; out["touched_n"] = int(tn.value)
+        return out
+    if op == 2:
+        return dict(cells=o0, mean=o1)
+    return o1
+
+
 def filter_variance(img, fw):
     """filter_variance_kernel (src/renderer.cu:366-399) on an (H, W, 4) float32 image -> (H, W) variance"""
     img = np.ascontiguousarray(img, np.float32); h, w = img.shape[:2]

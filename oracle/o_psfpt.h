@@ -43,7 +43,7 @@ inline u64 spatial_hash(V3 P, V3 N, V3 T, V3 B, V3 bbox_lo, V3 bbox_hi, const fl
 	const u32 log_grid_size = f2u(flog_grid_size);
 	const float rlog_grid_size = flog_grid_size - float(log_grid_size);
 	const u32 log_grid_size_i = log_grid_size + (samples[5] < rlog_grid_size ? 1u : 0u);
-	const u32 grid_size = 1u << log_grid_size_i;
+	const u32 grid_size = 1u << (log_grid_size_i & 31u);      // DEFINED HERE: undefined in the reference once the level passes 31 (a tiny or zero cone); the level bits below are the reference's
 	const V2 disk = square_to_unit_disk(samples[0], samples[1]);
 	const float rs = filter_radius * cone_radius;
 	const float rx = rs * disk.x, ry = rs * disk.y;
@@ -75,7 +75,22 @@ struct PsfState
 	struct Ref { u32 pixel_info, cache; V4 w_d, w_g; };
 	std::vector<Ref> refs;
 
-	static long long fixed(float v) { return (long long)rint(double(v) * 4294967296.0); }
+	// 2^-32 fixed point, round half to even.  DEFINED HERE beyond the range of a 64-bit integer (|v| >= 2^31, which only a firefly_filter above that lets through):
+	// the conversion saturates the way the device's does -- the high word saturates as a signed 32-bit integer, the low word is that of the value, 0 for every
+	// float of that size -- i.e. 2^63 - 2^32 above, -2^63 below (a plain cast is undefined there).
+	static long long fixed(float v)
+	{
+		const double r = rint(double(v) * 4294967296.0);
+		if (!(r < 9223372036854775808.0)) return (long long)0x7FFFFFFF00000000ull;
+		if (r < -9223372036854775808.0) return (long long)0x8000000000000000ull;
+		return (long long)r;
+	}
+	// the estimate a cell holds (count != 0): psf_blending_kernel's float4 / float, src/renderers/psfpt_impl.h:104-106, on the integer sums
+	static V3 mean(const Cell& c)
+	{
+		const float cw = float(c.count);
+		return V3(float(double(c.x) * (1.0 / 4294967296.0)) / cw, float(double(c.y) * (1.0 / 4294967296.0)) / cw, float(double(c.z) * (1.0 / 4294967296.0)) / cw);
+	}
 	void add(u32 slot, V3 v) { Cell& c = cells[slot]; c.x += fixed(v.x); c.y += fixed(v.y); c.z += fixed(v.z); }
 	V3 clamp_sample(V3 v) const { return finite3(v) ? V3(minf(v.x, options.firefly_filter), minf(v.y, options.firefly_filter), minf(v.z, options.firefly_filter)) : V3(0.0f); }
 	void clear() { index.clear(); keys.clear(); cells.clear(); }

@@ -526,8 +526,7 @@ struct PathTracer
 			const PsfState::Ref& r = psf->refs[i];
 			if (!ci_valid(r.cache)) continue;
 			const PsfState::Cell& cell = psf->cells[ci_slot(r.cache)];
-			const float cw = float(cell.count);
-			const V3 cv(float(double(cell.x) * (1.0 / 4294967296.0)) / cw, float(double(cell.y) * (1.0 / 4294967296.0)) / cw, float(double(cell.z) * (1.0 / 4294967296.0)) / cw);
+			const V3 cv = PsfState::mean(cell);
 			const u32 pixel = pi_pixel(r.pixel_info), comp = pi_comp(r.pixel_info);
 			const V3 w = ((comp & kDiffuseMask) ? r.w_d.xyz() : V3(0.0f)) + ((comp & kGlossyMask) ? r.w_g.xyz() : V3(0.0f));
 			const V3 cvw = cv * w;

@@ -471,6 +471,73 @@ u32 orc_psf_get_cells(orc_pt* h, u64* keys, u64* counts, long long* sums, u32 ma
 	return n;
 }
 u32 orc_psf_ref_count(orc_pt* h) { return u32(h->psf.refs.size()); }
+// twin of the device probe fpt_debug_psf (include/fermat_pt_hip.h has the layouts): spatial_hash, the cell sums and the cell mean are the oracle's own.  The
+// oracle keeps its cells in a map and has no table; op 1 restates the device's scheme -- multiplicative hash, linear probing with wrap, refusal when full -- one
+// key after the other, so that the table invariants of tests/psf_truth.py are run on the CPU leg too.
+void orc_psf_probe_n(i32 op, u32 flags, u32 n, const void* in, u32 size, float firefly, void* out0, void* out1, u32* touched, u32* touched_n)
+{
+	if (op == 0)
+	{
+		const float* rec = static_cast<const float*>(in);
+		u64* keys = static_cast<u64*>(out0);
+		for (u32 i = 0; i < n; ++i)
+		{
+			const float* r = rec + 32 * size_t(i);
+			keys[i] = spatial_hash(V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5]), V3(r[6], r[7], r[8]), V3(r[9], r[10], r[11]), V3(r[12], r[13], r[14]), V3(r[15], r[16], r[17]),
+			                       r + 18, r[24], r[25]);
+		}
+	}
+	else if (op == 1)
+	{
+		const u64* keys = static_cast<const u64*>(in);
+		u32* slots = static_cast<u32*>(out0);
+		u64* table = static_cast<u64*>(out1);
+		const u32 mask = (1u << size) - 1u;
+		for (u32 i = 0; i <= mask; ++i) { table[i] = ~u64(0); if (flags & 1u) touched[i] = 0xFFFFFFFFu; }
+		if (flags & 1u) *touched_n = 0;
+		for (u32 i = 0; i < n; ++i)
+		{
+			u32 h = u32((keys[i] * 0x9E3779B97F4A7C15ull) >> (64 - size)) & mask;
+			slots[i] = PSF_INVALID_SLOT;
+			for (u32 probe = 0; probe <= mask; ++probe, h = (h + 1u) & mask)
+			{
+				if (table[h] == ~u64(0)) { table[h] = keys[i]; if (flags & 1u) touched[(*touched_n)++] = h; }
+				if (table[h] == keys[i]) { slots[i] = h; break; }
+			}
+		}
+	}
+	else if (op == 2)
+	{
+		const float* rec = static_cast<const float*>(in);
+		PsfState ps; ps.options.firefly_filter = firefly;
+		ps.cells.assign(size, PsfState::Cell{ 0, 0, 0, 0 });
+		for (u32 i = 0; i < n; ++i)
+		{
+			const u32 slot = f2bits(rec[4 * size_t(i)]);
+			if (slot >= size) continue;
+			ps.cells[slot].count += 1;
+			ps.add(slot, ps.clamp_sample(V3(rec[4 * size_t(i) + 1], rec[4 * size_t(i) + 2], rec[4 * size_t(i) + 3])));
+		}
+		long long* cells = static_cast<long long*>(out0);
+		float* mean = static_cast<float*>(out1);
+		for (u32 c = 0; c < size; ++c)
+		{
+			const PsfState::Cell& k = ps.cells[c];
+			cells[4 * size_t(c)] = k.x; cells[4 * size_t(c) + 1] = k.y; cells[4 * size_t(c) + 2] = k.z; cells[4 * size_t(c) + 3] = (long long)k.count;
+			if (mean && k.count) { const V3 m = PsfState::mean(k); mean[3 * size_t(c)] = m.x; mean[3 * size_t(c) + 1] = m.y; mean[3 * size_t(c) + 2] = m.z; }
+		}
+	}
+	else if (op == 3)
+	{
+		const long long* cells = static_cast<const long long*>(in);
+		float* mean = static_cast<float*>(out1);
+		for (u32 c = 0; c < n; ++c)
+		{
+			const PsfState::Cell k{ cells[4 * size_t(c)], cells[4 * size_t(c) + 1], cells[4 * size_t(c) + 2], u64(cells[4 * size_t(c) + 3]) };
+			if (k.count) { const V3 m = PsfState::mean(k); mean[3 * size_t(c)] = m.x; mean[3 * size_t(c) + 1] = m.y; mean[3 * size_t(c) + 2] = m.z; }
+		}
+	}
+}
 
 // ---- bidirectional path tracer (o_bpt.h) on the same context: scene, BVH, mesh lights and frame buffer are shared -------------------
 void orc_bpt_init(orc_pt* h, const BPTOptions* opts, const char* samples_dir) { h->bpt.init(&h->pt, *opts, samples_dir); }

@@ -93,7 +93,11 @@ def test_cli_psfpt_matches_oracle_image(tmp_path, table):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("scene_name,L,kw", [("CornellBox-JP", 4, {}), ("CornellBox-Glossy", 5, dict(psf_width=2.0, psf_max_prob=8.0)),
-                                               ("CornellBox-JP", 4, dict(psf_temporal_reuse=2, firefly_filter=5.0))])
+                                               ("CornellBox-JP", 4, dict(psf_temporal_reuse=2, firefly_filter=5.0)),
+                                               # deep levels: 8..14; 15..21, where the coordinates pass 2^17 and are masked; and the regime beyond level 31
+                                               # that tests/psf_truth.py defines (masked shift, level bits over the normal digits)
+                                               ("CornellBox-Glossy", 5, dict(psf_width=0.001)), ("CornellBox-Glossy", 5, dict(psf_width=1.0e-5)),
+                                               ("CornellBox-Glossy", 5, dict(psf_width=1.0e-9))])
 def test_gpu_psfpt_parity(table, scene_name, L, kw):
     s = scene.cornell_box(scene_name)
     W, H = 64, 48
@@ -211,3 +215,149 @@ def test_gpu_psfpt_passes_in_flight(table, scene_name, W, H, L, groups, reuse):
         assert np.array_equal(got[c].view(np.uint32), want[c].view(np.uint32)), (c, float(np.sqrt((d * d).sum(1).mean())))
     assert want[5][:, :3].mean() > 1e-3
     seq.close(); bat.close()
+
+
+# ---- the cache under load: a table a test sized (fpt_psfpt_debug_set_table_log2) -------------------------------------------------------------------------------
+CROWD = dict(psf_width=0.001)          # CornellBox-Glossy, 64x48, L = 5, 3 passes: 3905 cells at levels 8..14
+
+
+def _same_cells(got, want, what):
+    assert np.array_equal(got["keys"], want["keys"]) and np.array_equal(got["counts"], want["counts"]) and np.array_equal(got["sums"], want["sums"]), what
+
+
+@pytest.fixture(scope="module")
+def crowd_oracle(table):
+    s = scene.cornell_box("CornellBox-Glossy")
+    return s, _oracle(s, table, 64, 48, 5, 3, **CROWD)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["sequential", "in_flight", "sharded"])
+def test_gpu_psfpt_crowded_table(table, crowd_oracle, mode):
+    """The cache in a table just large enough: the power of two above the oracle's cell count (3905 cells in 2^12 slots: load 0.95, probe chains of hundreds of
+    slots that wrap past the end).  Cells are addressed by key, so cache and frame must still equal the oracle's -- which has no table -- bit for bit: pass by pass,
+    as passes in flight (2 + 1; the pass tables and the fold into the global table probe the same way) and tile-sharded over two rank contexts (pass table,
+    records, merge, look-up by key in the blend)."""
+    s, o = crowd_oracle
+    W, H, L = 64, 48, 5
+    want = o.psf_cells()
+    log2 = max(8, int(len(want["keys"])).bit_length())
+    assert len(want["keys"]) > 0.45 * (1 << log2)
+    mk = lambda **kw: fa.Renderer(s, W, H, fa.default_options(L), table=table, psf_options=fa.default_psf_options(**CROWD), **kw)  # noqa: E731
+    if mode == "sharded":
+        from fermat_amd.distributed import device_bytes, PSF_RECORD_BYTES
+        lists = fa.tile_pixel_lists(W, H, 2, tile=(W, 1))
+        ranks = [mk(pixels=lists[k]) for k in range(2)]
+        for r in ranks:
+            r.psf_debug_set_table_log2(log2); r.psf_set_sharded(True)
+        for i in range(3):
+            for r in ranks:
+                r.psf_render(i)
+            exported = []
+            for r in ranks:
+                ptr, n = r.psf_export_cells()
+                exported.append(device_bytes(ptr, n * PSF_RECORD_BYTES, r.dev).clone() if n else None)
+            for r in ranks:
+                for t in exported:
+                    if t is not None:
+                        r.psf_import_cells(t.data_ptr(), t.numel() // PSF_RECORD_BYTES)
+                r.psf_finish(sync=True)
+        for k, r in enumerate(ranks):
+            _same_cells(r.psf_cells(), want, "rank %d" % k)
+            fb = r.framebuffer()
+            for c in range(8):
+                assert np.array_equal(fb[c][lists[k]].view(np.uint32), o.fb[c][lists[k]].view(np.uint32)), "rank %d channel %d" % (k, c)
+            r.close()
+        return
+    r = mk()
+    r.psf_debug_set_table_log2(log2)
+    if mode == "in_flight":
+        r.psf_set_batch(2)
+        r.psf_render_batch(0, 2, sync=True); r.psf_render(2, sync=True)
+    else:
+        for i in range(3):
+            r.psf_render(i, sync=True)
+    _same_cells(r.psf_cells(), want, mode)
+    fb = r.framebuffer()
+    for c in range(8):
+        assert np.array_equal(fb[c].view(np.uint32), o.fb[c].view(np.uint32)), "channel %d" % c
+    # the setter is refused once the context has rendered, and outside 8..24
+    with pytest.raises(fa.FptError):
+        r.psf_debug_set_table_log2(log2)
+    r.close()
+
+
+def test_psf_energy_brackets_oracle(table):
+    """The two estimators a vertex of a FULL table falls between, on the oracle: path-space filtering with every vertex cached (an unbounded table) and with none
+    (psf_depth beyond the path length).  Mean of COMPOSITED_C over the pixels below 20 (the light source is left out), CornellBox-Glossy 64x48, L = 5, width
+    0.001, 3 passes: 0.4440 cached, 0.4552 uncached; the mean of ONE pass moves by 0.0152 (standard deviation over the passes 0..7, each rendered alone).
+    test_gpu_psfpt_full_table allows three times that, PSF_ENERGY_MARGIN, beyond the bracket."""
+    s = scene.cornell_box("CornellBox-Glossy")
+    a, b, mask = _energy_brackets(s, table)
+    assert 0.3 < min(a, b) and max(a, b) < 0.6 and abs(a - b) < PSF_ENERGY_MARGIN and mask.mean() > 0.9
+    one = []
+    for i in range(8):
+        o = ob.OraclePT(s, 64, 48, ob.default_options(5), table, scene.DATA_DIR)
+        o.psf_enable(ob.default_psf_options(**CROWD))
+        o.render_pass(i)
+        one.append(float(o.fb[5][:, :3][mask].mean()) * (i + 1))              # a first pass rendered as instance i carries the frame weight 1 / (i + 1)
+    sd = float(np.std(one, ddof=1))
+    print("brackets %.5f %.5f, pass-to-pass sd %.5f" % (a, b, sd))
+    assert 3.0 * sd <= 1.25 * PSF_ENERGY_MARGIN and PSF_ENERGY_MARGIN <= 1.25 * 3.0 * sd          # the constant is this measurement
+
+
+PSF_ENERGY_MARGIN = 0.0455
+
+
+def _energy_brackets(s, table):
+    a = _oracle(s, table, 64, 48, 5, 3, **CROWD)
+    b = _oracle(s, table, 64, 48, 5, 3, psf_depth=99, **CROWD)
+    mask = (a.fb[5][:, :3] < 20.0).all(axis=1) & (b.fb[5][:, :3] < 20.0).all(axis=1)
+    return float(a.fb[5][:, :3][mask].mean()), float(b.fb[5][:, :3][mask].mean()), mask
+
+
+@pytest.mark.gpu
+def test_gpu_psfpt_full_table(table, crowd_oracle):
+    """The same run in a table of 2^10 slots, a quarter of what it needs: the table fills up in the first pass and every later key is refused -- its vertex stays
+    uncached.  WHICH vertices those are is a race, so only what must hold is asserted: the run completes, the table holds exactly 1024 distinct keys, the frame
+    is finite and clamped, DIRECT_C (which never touches the cache) equals the unbounded cache's bit for bit -- and the plain path tracer's on every pixel that
+    does not show the emitter, whose emission this renderer clamps --, the energy of the frame lies between the
+    all-cached and the none-cached estimate of the oracle (test_psf_energy_brackets_oracle: margin 3 x 0.0152 = 0.0455, the pass-to-pass deviation of that mean), and a
+    second renderer of the same process still matches the oracle exactly at full size."""
+    s, o = crowd_oracle
+    W, H, L = 64, 48, 5
+    r = fa.Renderer(s, W, H, fa.default_options(L), table=table, psf_options=fa.default_psf_options(**CROWD))
+    with pytest.raises(fa.FptError):
+        r.psf_debug_set_table_log2(7)
+    r.psf_debug_set_table_log2(10)
+    pt = fa.Renderer(s, W, H, fa.default_options(L), table=table)
+    for i in range(3):
+        r.psf_render(i, sync=True); pt.render_pass(i)
+    cells = r.psf_cells()
+    assert len(cells["keys"]) == 1024 and len(np.unique(cells["keys"])) == 1024 and (cells["counts"] >= 1).all()
+    assert np.isin(cells["keys"], o.psf_cells()["keys"]).all()                       # every key is one the unbounded cache holds too
+    fb = r.framebuffer()
+    assert np.isfinite(fb).all()
+    for c in (0, 2, 4, 5):
+        assert fb[c][:, :3].max() <= 100.0, c
+    # DIRECT_C holds the emission seen at bounce 0 and nothing of the cache: the unbounded cache's frame has the same one, all four components, on every pixel;
+    # and so has the plain path tracer wherever it saw no light source (the emitter's 200 is above firefly_filter = 100, which this vertex processor clamps
+    # emission to before clamp_frame cuts the frame at 100: on the emitter's pixels the two renderers differ with ANY table, the oracle's included)
+    want_dc, pt_dc = o.fb[4], pt.framebuffer()[4]
+    assert np.array_equal(fb[4].view(np.uint32), want_dc.view(np.uint32))
+    lit = (pt_dc != 0.0).any(axis=1)
+    assert 0 < lit.sum() < 0.1 * W * H and (pt_dc[lit][:, :3].max(axis=1) > 0.0).all()
+    assert np.array_equal(fb[4][~lit].view(np.uint32), pt_dc[~lit].view(np.uint32))
+    a, b, mask = _energy_brackets(s, table)
+    got = float(fb[5][:, :3][mask].mean())
+    print("energy: %.5f between %.5f and %.5f" % (got, a, b))
+    assert min(a, b) - PSF_ENERGY_MARGIN <= got <= max(a, b) + PSF_ENERGY_MARGIN, (got, a, b)
+    r.close(); pt.close()
+    r2 = fa.Renderer(s, W, H, fa.default_options(L), table=table, psf_options=fa.default_psf_options(**CROWD))
+    for i in range(3):
+        r2.psf_render(i, sync=True)
+    _same_cells(r2.psf_cells(), o.psf_cells(), "full size, afterwards")
+    fb = r2.framebuffer()
+    for c in range(8):
+        assert np.array_equal(fb[c].view(np.uint32), o.fb[c].view(np.uint32)), "channel %d" % c
+    r2.close()
