@@ -162,7 +162,7 @@ ENTRY_POINTS = ["fpt_create", "fpt_destroy", "fpt_last_error", "fpt_stream", "fp
                 "fpt_bpt_allreduce_splats", "fpt_comm_selftest", "fpt_pt_last_union_ms", "fpt_pt_lane_count", "fpt_pt_set_lanes", "fpt_pt_set_deferred", "fpt_pt_flush", "fpt_pt_launch_list", "fpt_set_tile_lists", "fpt_gather_pack", "fpt_gather_unpack", "fpt_device_memory", "fpt_bytes_per_path_in_flight", "fpt_bpt_set_shared_light_vertices", "fpt_bpt_export_light_vertices", "fpt_bpt_import_light_vertices", "fpt_bpt_exchange_light_vertices", "fpt_bpt_finish",
                 "fpt_multiply_frame", "fpt_clamp_frame", "fpt_sequence_device_view", "fpt_mesh_lights_device_view", "fpt_mesh_invalidate", "fpt_rt_refit_geometry", "fpt_debug_refit_bvh",
                 "fpt_debug_build_emitter_tables", "fpt_clear_gbuffer", "fpt_rt_download_bvh", "fpt_mesh_lights_update", "fpt_rt_set_build_mode",
-                "fpt_debug_psf", "fpt_psfpt_debug_set_table_log2"]
+                "fpt_debug_psf", "fpt_psfpt_debug_set_table_log2", "fpt_debug_bpt"]
 
 
 def kernel_source_hash():
@@ -862,6 +862,19 @@ class Renderer:
         if op == 2:
             return dict(cells=down(o0, np.int64, 4 * size).reshape(size, 4), mean=down(o1, np.float32, 3 * size).reshape(size, 3))
         return down(o1, np.float32, 3 * n).reshape(n, 3)
+
+    def debug_bpt(self, op, arrays, params=(), n=None):
+        """fpt_debug_bpt (layouts: include/fermat_pt_hip.h).  arrays: the op's arrays in order, each a numpy array (uploaded; None = a NULL pointer); params: the
+        op's words; n: the element count (default: the rows of the first array).  Returns the arrays as the device left them, in order, with their dtypes and shapes."""
+        torch = self.torch
+        hosts = [None if a is None else np.ascontiguousarray(a) for a in arrays]
+        devs = [None if a is None else torch.from_numpy(a.view(np.uint8).reshape(-1).copy() if a.size else np.zeros(8, np.uint8)).to(self.dev) for a in hosts]
+        n = len(hosts[0]) if n is None else int(n)
+        ptrs = (C.c_void_p * max(1, len(devs)))(*[None if d is None else d.data_ptr() for d in devs])
+        par = (C.c_uint32 * max(1, len(params)))(*[int(p) for p in params])
+        torch.cuda.synchronize(self.dev)
+        self._check(self.L.fpt_debug_bpt(self.ctx, C.c_int(op), C.c_uint32(n), par, C.c_uint32(len(params)), ptrs, C.c_uint32(len(devs))))
+        return [None if a is None else d.cpu().numpy()[:a.nbytes].view(a.dtype).reshape(a.shape) for a, d in zip(hosts, devs)]
 
     def reinit_emitters(self, n_vpls):
         """fpt_mesh_lights_init again with another VPL count (the probe's emitter tables)"""

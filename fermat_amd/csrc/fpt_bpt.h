@@ -76,5 +76,7 @@ void launch_bpt_splat_resolve(const BptParams& p, hipStream_t s);
 // frame n sequential BPT::render calls leave, bit for bit; clears planes, fill bits and splat sums
 void launch_bpt_merge_exact(const FrameBufferDev& fb, float4* albedo_d, float4* albedo_s, const BptLog& log, long long* splat, const uint32_t* pixels, uint32_t n_local,
                             uint32_t n_paths, uint32_t base_instance, uint32_t n_passes, uint32_t max_path_length, hipStream_t s);
+// probe (fpt_debug_bpt): ops 0..5, one element per thread in one launch
+void launch_debug_bpt(int op, uint32_t n, const uint32_t* in, uint32_t* out, uint32_t* counter, const fpt_material* mats, uint32_t n_mats, const float* table, hipStream_t s);
 
 } // namespace fpt

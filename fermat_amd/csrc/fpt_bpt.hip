@@ -107,6 +107,16 @@ __device__ __forceinline__ float camera_pdf(const BptParams& P, f3 out, float* o
 	}
 	return 0.0f;
 }
+// connect_to_camera (src/bpt_kernels.h:919-1032): the unit direction from the lens to a point with the clamped squared distance, and the pixel a
+// screen position (ox, oy) in [-1, 1]^2 lands on
+__device__ __forceinline__ f3 lens_direction(const BptParams& P, f3 position, float& d2)
+{
+	const f3 delta = position - P.eye;
+	d2 = ieee_max(1.0e-8f, dot(delta, delta));
+	const float d = sqrtf(d2);
+	return delta / d;
+}
+__device__ __forceinline__ uint32_t lens_pixel(const BptParams& P, float ox, float oy) { return quantize(ox * 0.5f + 0.5f, P.res_x) + quantize(oy * 0.5f + 0.5f, P.res_y) * P.res_x; }
 // virtual path id -> (pass offset, pixel / light-path index); see BptParams
 struct PathRef { uint32_t k, id; };
 __device__ __forceinline__ PathRef path_ref(const BptParams& P, uint32_t vid)
@@ -186,6 +196,15 @@ __device__ __forceinline__ void write_ray(float4* rays, uint32_t slot, f3 o, flo
 	rays[2 * size_t(slot) + 1] = make_float4(d.x, d.y, d.z, tmax);
 }
 
+// MIS bookkeeping for the next vertex: pw = (pGp_sum, pG, out_p, out_cos_theta) of the edge that led here, t its length in units of the ray direction
+// (an eye vertex divides by t * t as it is, a light vertex by max(t * t, MIN_G_DENOM): src/bpt_utils.h:340-361, 585-642)
+__device__ __forceinline__ void path_weights_step(float4 pw, float t, f3 in, f3 n, bool light, float& G_prime, float& prev_pG, float& pGp_sum)
+{
+	G_prime = light ? fabsf(dot(in, n)) / ieee_max(t * t, kMinGDenom) : fabsf(dot(in, n)) / (t * t);
+	prev_pG = pdf2(pw.z, pw.w * G_prime);
+	pGp_sum = pw.x + (1 / pdf2(pw.y, pw.z));
+}
+
 // ---- a shaded path vertex: EyeVertex / LightVertex::setup(ray, hit, ...) (src/bpt_utils.h:340-361, 585-642) -------------------------
 struct Vertex
 {
@@ -221,10 +240,8 @@ __device__ __forceinline__ void shade_vertex(const BptParams& P, f3 ro, f3 rd, f
 	x.diffuse = xyz(m_diffuse); x.specular = xyz(m_specular); x.diffuse_trans = xyz(m_dtrans);
 	x.roughness = mat->roughness; x.opacity = mat->opacity; x.ior = mat->index_of_refraction;
 	x.bsdf = make_surface_model(x.diffuse, x.diffuse_trans, x.specular, xyz(load4(mat->reflectivity)), mat->roughness, mat->index_of_refraction, mat->opacity, P.table);
-	// MIS bookkeeping for the next vertex: pw = (pGp_sum, pG, out_p, out_cos_theta) of the edge that led here
-	const float G_prime = light ? fabsf(dot(x.in, x.sp.frame.n)) / ieee_max(t * t, kMinGDenom) : fabsf(dot(x.in, x.sp.frame.n)) / (t * t);
-	x.prev_pG = pdf2(pw.z, pw.w * G_prime);
-	x.pGp_sum = pw.x + (1 / pdf2(pw.y, pw.z));
+	float G_prime;
+	path_weights_step(pw, t, x.in, x.sp.frame.n, light, G_prime, x.prev_pG, x.pGp_sum);
 }
 
 // a stored light vertex: LightVertex::setup(pos, packed...) (src/bpt_utils.h:313-337)
@@ -258,8 +275,10 @@ __device__ __forceinline__ void load_stored(const BptParams& P, uint32_t slot, u
 	else s.bsdf = unpack_material(gb, P.table);
 }
 
-// eval_connection (src/bpt_utils.h:911-980); returns the connection weight (0 when nothing is to be traced)
-__device__ __forceinline__ f3 connect(const BptParams& P, const Vertex& ev, uint32_t ev_depth, const StoredVertex& lv)
+// eval_connection (src/bpt_utils.h:911-980); returns the connection weight (0 when nothing is to be traced).  `terms` (the probe's; the kernels pass nullptr)
+// receives the intermediates
+struct ConnectTerms { f3 out; float d2, G; f3 f_s; float p_s; f3 f_L; float p_L, pGp, prev_pGp, next_pGp, mis_w; };
+__device__ __forceinline__ f3 connect(const BptParams& P, const Vertex& ev, uint32_t ev_depth, const StoredVertex& lv, ConnectTerms* terms)
 {
 	const bool RR = P.opt.rr != 0;
 	const f3 delta = lv.position - ev.sp.position;
@@ -270,6 +289,7 @@ __device__ __forceinline__ f3 connect(const BptParams& P, const Vertex& ev, uint
 	f3 f_s; float p_s;
 	surface_f_and_p_sum(ev.bsdf, ev.sp.frame, ev.in, out, RR, false, f_s, p_s);
 	const float prev_pGp = pdf2(ev.prev_pG, p_s);
+	if (terms) { terms->out = out; terms->d2 = d2; terms->G = G; terms->f_s = f_s; terms->p_s = p_s; terms->prev_pGp = prev_pGp; }
 	if (lv.depth == 0)
 	{
 		if (!P.opt.direct_lighting_nee) return splat3(0.0f);
@@ -278,6 +298,7 @@ __device__ __forceinline__ f3 connect(const BptParams& P, const Vertex& ev, uint
 		const float pGp = pdf3(p_s, G, p_L);
 		const float next_pGp = pdf2(p_L, lv.pG);
 		const float mis_w = (ev_depth == 0 && !P.opt.direct_lighting_bsdf) ? 1.0f : mis4(pGp, prev_pGp, next_pGp, ev.pGp_sum + lv.pGp_sum);
+		if (terms) { terms->f_L = f_L; terms->p_L = p_L; terms->pGp = pGp; terms->next_pGp = next_pGp; terms->mis_w = mis_w; }
 		return ev.alpha * lv.alpha * f_L * f_s * G * mis_w;
 	}
 	f3 f_L; float p_L;
@@ -285,6 +306,7 @@ __device__ __forceinline__ f3 connect(const BptParams& P, const Vertex& ev, uint
 	const float pGp = pdf3(p_s, G, p_L);
 	const float next_pGp = pdf2(p_L, lv.pG);
 	const float mis_w = mis4(pGp, prev_pGp, next_pGp, ev.pGp_sum + lv.pGp_sum);
+	if (terms) { terms->f_L = f_L; terms->p_L = p_L; terms->pGp = pGp; terms->next_pGp = next_pGp; terms->mis_w = mis_w; }
 	return ev.alpha * lv.alpha * f_L * f_s * G * mis_w;
 }
 
@@ -540,7 +562,7 @@ __global__ void __launch_bounds__(BPT_BLOCK, FPT_BPT_EYE_WAVES) eye_vertices_ker
 			}
 			StoredVertex lv;
 			load_stored(P, light_slot, light_depth, lv);
-			const f3 w = connect(P, ev, P.bounce, lv) * light_weight;
+			const f3 w = connect(P, ev, P.bounce, lv, nullptr) * light_weight;
 			if (max_comp(w) > 0.0f && finite3(w))
 			{
 				write_ray(P.shadow.rays, base + k, origin, 0.0f, lv.position - origin, 0.9999f);
@@ -603,7 +625,7 @@ __global__ void __launch_bounds__(BPT_BLOCK) flat_count_kernel(const BptParams P
 	(void)block_range_scan(n, sc, block_total);
 	if (threadIdx.x == 0) P.flat_block_sums[blockIdx.x] = block_total;
 }
-__global__ void __launch_bounds__(BPT_BLOCK) flat_scan_kernel(uint32_t* sums, uint32_t n_blocks, uint32_t* total_out)
+__global__ void __launch_bounds__(BPT_BLOCK) flat_scan_kernel(uint32_t* sums, uint32_t n_blocks, uint32_t* total_out, bool single_depth)
 {
 	__shared__ RangeScratch sc;
 	uint32_t carry = 0;
@@ -617,7 +639,8 @@ __global__ void __launch_bounds__(BPT_BLOCK) flat_scan_kernel(uint32_t* sums, ui
 		carry += chunk_total;
 		__syncthreads();
 	}
-	if (threadIdx.x == 0) *total_out = carry;
+	// with L == 1 a pass has no depth-1 vertices: they "begin" where the pass ends, and the last pass ends at the total (flat_fill_kernel writes the others)
+	if (threadIdx.x == 0) { *total_out = carry; if (single_depth) total_out[-1] = carry; }
 }
 __global__ void __launch_bounds__(BPT_BLOCK) flat_fill_kernel(const BptParams P)
 {
@@ -674,6 +697,43 @@ __global__ void __launch_bounds__(BPT_BLOCK) unpack_light_vertices_kernel(const 
 	atomicMax(counts + w.slot % n_store, w.slot / n_store + 1u);
 }
 
+// stage B of connect_camera_kernel for one stored vertex of depth >= 1 (connect_to_camera, src/bpt_kernels.h:919-1032): the sample's weight, the pixel it
+// lands on (without the pass offset) and the origin of its shadow ray; false when nothing is to be traced.  `terms`: as in connect
+struct LensTerms { f3 out; float d2, cos_theta, G, p_s, f_s, ox, oy; f3 f_L; float p_L, pGp, next_pGp, mis_w; };
+__device__ __forceinline__ bool connect_lens(const BptParams& P, const StoredVertex& lv, uint32_t depth, f3& w, float& light_weight, uint32_t& pixel, f3& origin, LensTerms* terms)
+{
+	float d2;
+	const f3 out = lens_direction(P, lv.position, d2);
+	const float cos_theta = dot(out, P.W) / P.W_len;
+	const float G = fabsf(cos_theta * dot(out, lv.fr.n)) / d2;
+	float ox = 0.0f, oy = 0.0f;
+	const float p_s = camera_pdf(P, out, &ox, &oy);
+	const float f_s = p_s * float(P.res_x * P.res_y);
+	const f3 f_L = surface_f_sum(lv.bsdf, lv.fr, lv.in, -out, true);
+	const float p_L = surface_p_sum(lv.bsdf, lv.fr, lv.in, -out, true);
+	const float pGp = pdf3(p_s, G, p_L);
+	const float next_pGp = pdf2(max_comp(f_L), lv.pG);
+	const float mis_w =
+		(depth == 1 && !P.opt.direct_lighting_nee && !P.opt.direct_lighting_bsdf) ? 1.0f :
+		(depth > 1 && !P.opt.indirect_lighting_nee && !P.opt.indirect_lighting_bsdf) ? 1.0f :
+		mis3(pGp / P.light_tracing, next_pGp, lv.pGp_sum);
+	const f3 c = lv.alpha * f_L * f_s * G * mis_w;
+	light_weight = 1.0f / float(P.n_paths);
+	w = mk3(c.x * light_weight, c.y * light_weight, c.z * light_weight);
+	if (terms)
+	{
+		terms->out = out; terms->d2 = d2; terms->cos_theta = cos_theta; terms->G = G; terms->p_s = p_s; terms->f_s = f_s; terms->ox = ox; terms->oy = oy;
+		terms->f_L = f_L; terms->p_L = p_L; terms->pGp = pGp; terms->next_pGp = next_pGp; terms->mis_w = mis_w;
+	}
+	if (max_comp(w) > 0.0f && finite3(w))
+	{
+		origin = lv.position + lv.in * kShadowBias;
+		pixel = lens_pixel(P, ox, oy);
+		return true;
+	}
+	return false;
+}
+
 // pure light tracing: every stored vertex of depth >= 1 is connected to the lens (connect_to_camera).  A workgroup takes 256 light paths in
 // two stages: (A) one thread per path walks its vertices and lists in LDS those inside the view frustum (a position load and the camera pdf:
 // cheap, divergent); (B) the threads share the list, one vertex each per round, for the expensive part (unpack the vertex, both BSDF
@@ -698,10 +758,8 @@ __global__ void __launch_bounds__(BPT_BLOCK) connect_camera_kernel(const BptPara
 		{
 			const uint32_t li = vid + depth * P.n_store;
 			const float4 pos4 = P.store.pos[li];
-			const f3 delta = mk3(pos4.x, pos4.y, pos4.z) - P.eye;
-			const float d2 = ieee_max(1.0e-8f, dot(delta, delta));
-			const float d = sqrtf(d2);
-			const f3 out = delta / d;
+			float d2;
+			const f3 out = lens_direction(P, mk3(pos4.x, pos4.y, pos4.z), d2);
 			float ox = 0.0f, oy = 0.0f;
 			const float p_s = camera_pdf(P, out, &ox, &oy);
 			const float f_s = p_s * float(P.res_x * P.res_y);
@@ -720,32 +778,9 @@ __global__ void __launch_bounds__(BPT_BLOCK) connect_camera_kernel(const BptPara
 			const uint32_t li = list[e].x, depth = list[e].y & 0xFFu, pass_k = list[e].y >> 8;
 			StoredVertex lv;
 			load_stored(P, li, depth, lv);
-			const f3 delta = lv.position - P.eye;
-			const float d2 = ieee_max(1.0e-8f, dot(delta, delta));
-			const float d = sqrtf(d2);
-			const f3 out = delta / d;
-			const float cos_theta = dot(out, P.W) / P.W_len;
-			const float G = fabsf(cos_theta * dot(out, lv.fr.n)) / d2;
-			float ox = 0.0f, oy = 0.0f;
-			const float p_s = camera_pdf(P, out, &ox, &oy);
-			const float f_s = p_s * float(P.res_x * P.res_y);
-			const f3 f_L = surface_f_sum(lv.bsdf, lv.fr, lv.in, -out, true);
-			const float p_L = surface_p_sum(lv.bsdf, lv.fr, lv.in, -out, true);
-			const float pGp = pdf3(p_s, G, p_L);
-			const float next_pGp = pdf2(max_comp(f_L), lv.pG);
-			const float mis_w =
-				(depth == 1 && !P.opt.direct_lighting_nee && !P.opt.direct_lighting_bsdf) ? 1.0f :
-				(depth > 1 && !P.opt.indirect_lighting_nee && !P.opt.indirect_lighting_bsdf) ? 1.0f :
-				mis3(pGp / P.light_tracing, next_pGp, lv.pGp_sum);
-			const f3 c = lv.alpha * f_L * f_s * G * mis_w;
-			light_weight = 1.0f / float(P.n_paths);
-			w = mk3(c.x * light_weight, c.y * light_weight, c.z * light_weight);
-			if (max_comp(w) > 0.0f && finite3(w))
-			{
-				want = true;
-				origin = lv.position + lv.in * kShadowBias;
-				out_pixel = pass_k * P.n_paths + quantize(ox * 0.5f + 0.5f, P.res_x) + quantize(oy * 0.5f + 0.5f, P.res_y) * P.res_x;
-			}
+			uint32_t px = 0;
+			want = connect_lens(P, lv, depth, w, light_weight, px, origin, nullptr);
+			out_pixel = pass_k * P.n_paths + px;
 		}
 		const uint32_t slot = block_range_alloc(P.shadow.size, want ? 1u : 0u, sc);
 		if (want)
@@ -758,6 +793,18 @@ __global__ void __launch_bounds__(BPT_BLOCK) connect_camera_kernel(const BptPara
 	}
 }
 
+// one splat entry in 2^-32 fixed point, by the rule of include/fermat_pt_hip.h ("light-tracing splats"): weight x frame weight in float, x 2^32 in double
+// (exact), rounded half to even; a value outside int64 saturates at its end of the range and a NaN adds nothing (C++ leaves both casts undefined)
+__device__ __forceinline__ long long splat_fixed(float v)
+{
+	const double x = double(v) * 4294967296.0;
+	if (x != x) return 0;
+	if (x >= 9223372036854775808.0) return 0x7FFFFFFFFFFFFFFFll;
+	if (x <= -9223372036854775808.0) return -0x7FFFFFFFFFFFFFFFll - 1;
+	return __double2ll_rn(x);
+}
+__device__ __forceinline__ void splat_fixed3(float4 w, float fw, long long q[3]) { q[0] = splat_fixed(w.x * fw); q[1] = splat_fixed(w.y * fw); q[2] = splat_fixed(w.z * fw); }
+
 // ConnectionsSink<true>: xyz of COMPOSITED_C and DIRECT_C, as order-independent 2^-32 fixed-point sums
 __global__ void __launch_bounds__(BPT_BLOCK) splat_kernel(const BptParams P)
 {
@@ -768,11 +815,12 @@ __global__ void __launch_bounds__(BPT_BLOCK) splat_kernel(const BptParams P)
 	if (!(P.shadow.hits[s].x < 0.0f)) return;
 	const uint32_t pixel = P.shadow.pixels[s];                 // virtual: pass offset * n_paths + pixel
 	const float fw = frame_weight(P, path_ref(P, pixel).k);
-	const float v[3] = { w.x * fw, w.y * fw, w.z * fw };
+	long long q3[3];
+	splat_fixed3(w, fw, q3);
 	#pragma unroll
 	for (int c = 0; c < 3; ++c)
 	{
-		const long long q = __double2ll_rn(double(v[c]) * 4294967296.0);
+		const long long q = q3[c];
 		if (q) atomicAdd(reinterpret_cast<unsigned long long*>(P.splat + size_t(pixel) * 3 + c), (unsigned long long)q);
 	}
 }
@@ -855,6 +903,108 @@ __global__ void __launch_bounds__(BPT_BLOCK) merge_exact_kernel(FrameBufferDev f
 	for (int ch = 0; ch < 6; ++ch) fb.ch[ch][p] = c[ch];
 }
 
+// ---- probe (fpt_debug_bpt; include/fermat_pt_hip.h has the record layouts): the functions above on inputs a test chose, one element per thread --------
+__global__ void __launch_bounds__(BPT_BLOCK) debug_bpt_kernel(int op, uint32_t n, const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t* counter,
+                                                              const fpt_material* __restrict__ mats, uint32_t n_mats, const float* __restrict__ table)
+{
+	__shared__ RangeScratch sc;
+	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
+	if (op == 5)          // every thread of a block takes part in the scan: the threads past n ask for nothing
+	{
+		const uint32_t base = block_range_alloc(counter, i < n ? in[i] : 0u, sc);
+		if (i < n) out[i] = base;
+		return;
+	}
+	if (i >= n) return;
+	if (op == 0)
+	{
+		const uint32_t* r = in + 16 * size_t(i); uint32_t* o = out + 32 * size_t(i);
+		const f3 c = mk3(as_f32(r[0]), as_f32(r[1]), as_f32(r[2])), d = mk3(as_f32(r[3]), as_f32(r[4]), as_f32(r[5]));
+		const f3 spec = mk3(as_f32(r[10]), as_f32(r[11]), as_f32(r[12])), dtr = mk3(as_f32(r[13]), as_f32(r[14]), as_f32(r[15]));
+		const uint32_t e = to_rgbe(c); const f3 back = from_rgbe(e);
+		o[0] = e; o[1] = as_u32(back.x); o[2] = as_u32(back.y); o[3] = as_u32(back.z);
+		const uint32_t pd = pack_direction(d); const f3 ud = unpack_direction(pd);
+		o[4] = pd; o[5] = as_u32(ud.x); o[6] = as_u32(ud.y); o[7] = as_u32(ud.z);
+		o[8] = as_u32(pack_gbuffer_normal(d));
+		const uint4 pm = pack_material(c, spec, dtr, as_f32(r[6]), as_f32(r[7]), as_f32(r[8]));
+		o[9] = pm.x; o[10] = pm.y; o[11] = pm.z; o[12] = pm.w;
+		const SurfaceModel m = unpack_material(pm, nullptr);
+		o[13] = as_u32(m.alpha); o[14] = as_u32(m.opacity); o[15] = as_u32(m.ior);
+		o[16] = as_u32(m.kd.x); o[17] = as_u32(m.kd.y); o[18] = as_u32(m.kd.z);
+		o[19] = as_u32(m.ks.x); o[20] = as_u32(m.ks.y); o[21] = as_u32(m.ks.z);
+		o[22] = as_u32(m.kdt.x); o[23] = as_u32(m.kdt.y); o[24] = as_u32(m.kdt.z);
+		const f3 uc = unpack_direction(r[9]);
+		o[25] = as_u32(uc.x); o[26] = as_u32(uc.y); o[27] = as_u32(uc.z);
+	}
+	else if (op == 1)
+	{
+		const uint32_t* r = in + 24 * size_t(i); uint32_t* o = out + 12 * size_t(i);
+		BptParams P;
+		P.eye = mk3(as_f32(r[0]), as_f32(r[1]), as_f32(r[2])); P.U = mk3(as_f32(r[3]), as_f32(r[4]), as_f32(r[5]));
+		P.V = mk3(as_f32(r[6]), as_f32(r[7]), as_f32(r[8])); P.W = mk3(as_f32(r[9]), as_f32(r[10]), as_f32(r[11]));
+		P.W_len = length(P.W); P.sq_focal = as_f32(r[12]); P.res_x = r[13]; P.res_y = r[14];
+		float d2, ox = 0.0f, oy = 0.0f;
+		const f3 dir = lens_direction(P, mk3(as_f32(r[15]), as_f32(r[16]), as_f32(r[17])), d2);
+		const float p_s = camera_pdf(P, dir, &ox, &oy);
+		const float f_s = p_s * float(P.res_x * P.res_y);
+		o[0] = as_u32(p_s); o[1] = as_u32(ox); o[2] = as_u32(oy); o[3] = lens_pixel(P, ox, oy); o[4] = f_s ? 1u : 0u;
+		o[5] = as_u32(dir.x); o[6] = as_u32(dir.y); o[7] = as_u32(dir.z); o[8] = as_u32(d2);
+	}
+	else if (op == 2)
+	{
+		const uint32_t* r = in + 12 * size_t(i); uint32_t* o = out + 4 * size_t(i);
+		float G_prime, prev_pG, pGp_sum;
+		path_weights_step(make_float4(as_f32(r[0]), as_f32(r[1]), as_f32(r[2]), as_f32(r[3])), as_f32(r[4]), mk3(as_f32(r[5]), as_f32(r[6]), as_f32(r[7])),
+		                  mk3(as_f32(r[8]), as_f32(r[9]), as_f32(r[10])), r[11] != 0u, G_prime, prev_pG, pGp_sum);
+		o[0] = as_u32(G_prime); o[1] = as_u32(prev_pG); o[2] = as_u32(pGp_sum);
+	}
+	else if (op == 3 || op == 4)
+	{
+		// the element's light vertex is the LightVertexRecord in words [32, 48) of its 48-word record: store slot 3 i + 2
+		const uint32_t* r = in + 48 * size_t(i); uint32_t* o = out + 64 * size_t(i);
+		auto f = [&](int k) { return as_f32(r[k]); };
+		auto put3 = [&](int k, f3 v) { o[k] = as_u32(v.x); o[k + 1] = as_u32(v.y); o[k + 2] = as_u32(v.z); };
+		BptParams P;
+		P.store.rec = reinterpret_cast<LightVertexRecord*>(const_cast<uint32_t*>(in)); P.table = table;
+		StoredVertex lv;
+		if (op == 3)
+		{
+			P.opt.rr = r[26] & 1u; P.opt.direct_lighting_nee = (r[26] >> 1) & 1u; P.opt.direct_lighting_bsdf = (r[26] >> 2) & 1u;
+			load_stored(P, 3u * i + 2u, r[25], lv);
+			const fpt_material* mat = mats + sel_min(r[0], n_mats - 1u);
+			Vertex ev;
+			ev.bsdf = make_surface_model(xyz(load4(mat->diffuse)), xyz(load4(mat->diffuse_trans)), xyz(load4(mat->specular)), xyz(load4(mat->reflectivity)),
+			                             mat->roughness, mat->index_of_refraction, mat->opacity, table);
+			ev.sp.frame.n = mk3(f(1), f(2), f(3)); ev.sp.frame.ng = mk3(f(4), f(5), f(6)); ev.sp.frame.t = mk3(f(7), f(8), f(9)); ev.sp.frame.b = mk3(f(10), f(11), f(12));
+			ev.sp.position = mk3(f(13), f(14), f(15)); ev.in = mk3(f(16), f(17), f(18)); ev.alpha = mk3(f(19), f(20), f(21));
+			ev.prev_pG = f(22); ev.pGp_sum = f(23);
+			ConnectTerms t;
+			t.out = splat3(0.0f); t.d2 = t.G = t.p_s = t.p_L = t.pGp = t.prev_pGp = t.next_pGp = t.mis_w = 0.0f; t.f_s = t.f_L = splat3(0.0f);
+			const f3 w = connect(P, ev, r[24], lv, &t);
+			put3(0, w); put3(3, t.out); o[6] = as_u32(t.d2); o[7] = as_u32(t.G); put3(8, t.f_s); o[11] = as_u32(t.p_s); put3(12, t.f_L); o[15] = as_u32(t.p_L);
+			o[16] = as_u32(t.pGp); o[17] = as_u32(t.prev_pGp); o[18] = as_u32(t.next_pGp); o[19] = as_u32(t.mis_w);
+		}
+		else
+		{
+			P.eye = mk3(f(0), f(1), f(2)); P.U = mk3(f(3), f(4), f(5)); P.V = mk3(f(6), f(7), f(8)); P.W = mk3(f(9), f(10), f(11));
+			P.W_len = length(P.W); P.sq_focal = f(12); P.res_x = r[13]; P.res_y = r[14]; P.light_tracing = f(15); P.n_paths = r[16];
+			P.opt.direct_lighting_nee = r[18] & 1u; P.opt.direct_lighting_bsdf = (r[18] >> 1) & 1u;
+			P.opt.indirect_lighting_nee = (r[18] >> 2) & 1u; P.opt.indirect_lighting_bsdf = (r[18] >> 3) & 1u;
+			load_stored(P, 3u * i + 2u, r[17], lv);
+			LensTerms t;
+			f3 w = splat3(0.0f), origin = splat3(0.0f); float light_weight = 0.0f; uint32_t pixel = 0;
+			const bool want = connect_lens(P, lv, r[17], w, light_weight, pixel, origin, &t);
+			put3(0, w); put3(3, t.out); o[6] = as_u32(t.d2); o[7] = as_u32(t.G); o[8] = as_u32(t.f_s); o[9] = as_u32(t.ox); o[10] = as_u32(t.oy); o[11] = as_u32(t.p_s);
+			put3(12, t.f_L); o[15] = as_u32(t.p_L); o[16] = as_u32(t.pGp); o[17] = as_u32(t.cos_theta); o[18] = as_u32(t.next_pGp); o[19] = as_u32(t.mis_w);
+			o[52] = want ? 1u : 0u; o[53] = want ? pixel : 0u; o[54] = as_u32(light_weight);
+			if (want) put3(48, origin);
+		}
+		put3(20, lv.position); put3(23, lv.fr.n); put3(26, lv.in); put3(29, lv.alpha); put3(32, lv.edf); o[35] = as_u32(lv.pGp_sum); o[36] = as_u32(lv.pG);
+		if (r[op == 3 ? 25 : 17] != 0u) { o[37] = as_u32(lv.bsdf.alpha); o[38] = as_u32(lv.bsdf.opacity); o[39] = as_u32(lv.bsdf.ior); }
+		put3(40, lv.fr.t); put3(43, lv.fr.b);
+	}
+}
+
 inline dim3 grid_for(uint32_t n) { return dim3((n + BPT_BLOCK - 1) / BPT_BLOCK); }
 
 } // namespace
@@ -874,7 +1024,7 @@ void launch_bpt_build_flat_list(const BptParams& p, hipStream_t s)
 	const uint64_t total = uint64_t(p.n_passes) * p.opt.max_path_length * p.n_paths;
 	const uint32_t n_blocks = uint32_t((total + uint64_t(BPT_BLOCK) * FLAT_ITEMS - 1) / (uint64_t(BPT_BLOCK) * FLAT_ITEMS));
 	hipLaunchKernelGGL(flat_count_kernel, dim3(n_blocks), dim3(BPT_BLOCK), 0, s, p);
-	hipLaunchKernelGGL(flat_scan_kernel, dim3(1), dim3(BPT_BLOCK), 0, s, p.flat_block_sums, n_blocks, p.flat_meta + 2 * p.n_passes);
+	hipLaunchKernelGGL(flat_scan_kernel, dim3(1), dim3(BPT_BLOCK), 0, s, p.flat_block_sums, n_blocks, p.flat_meta + 2 * p.n_passes, p.opt.max_path_length == 1);
 	hipLaunchKernelGGL(flat_fill_kernel, dim3(n_blocks), dim3(BPT_BLOCK), 0, s, p);
 }
 void launch_bpt_connect_camera(const BptParams& p, hipStream_t s)
@@ -884,5 +1034,8 @@ void launch_bpt_splat_resolve(const BptParams& p, hipStream_t s) { hipLaunchKern
 void launch_bpt_merge_exact(const FrameBufferDev& fb, float4* albedo_d, float4* albedo_s, const BptLog& log, long long* splat, const uint32_t* pixels, uint32_t n_local,
                             uint32_t n_paths, uint32_t base_instance, uint32_t n_passes, uint32_t, hipStream_t s)
 { hipLaunchKernelGGL(merge_exact_kernel, grid_for(n_local), dim3(BPT_BLOCK), 0, s, fb, albedo_d, albedo_s, log, splat, pixels, n_local, n_paths, base_instance, n_passes); }
+
+void launch_debug_bpt(int op, uint32_t n, const uint32_t* in, uint32_t* out, uint32_t* counter, const fpt_material* mats, uint32_t n_mats, const float* table, hipStream_t s)
+{ hipLaunchKernelGGL(debug_bpt_kernel, grid_for(n), dim3(BPT_BLOCK), 0, s, op, n, in, out, counter, mats, n_mats, table); }
 
 } // namespace fpt

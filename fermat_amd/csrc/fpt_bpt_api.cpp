@@ -412,4 +412,84 @@ int fpt_bpt_finish(fpt_context* ctx, const fpt_rendering_context_view* view)
 	});
 }
 
+/* fpt_debug_bpt (include/fermat_pt_hip.h): the probe of the bidirectional kernels.  Ops 0 to 5 are one launch of the probe kernel; ops 6, 7 and 8 launch
+ * the product's own kernels on arrays the caller filled. */
+int fpt_debug_bpt(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_params, uint32_t n_params, void* const* h_arrays, uint32_t n_arrays)
+{
+	return guarded(ctx, [&] {
+		static const uint32_t want_params[9] = { 0, 0, 0, 1, 0, 0, 3, 3, 7 }, want_arrays[9] = { 2, 2, 2, 4, 3, 3, 3, 8, 13 };
+		require(op >= 0 && op <= 8, "fpt_debug_bpt: unknown op");
+		require(n_params == want_params[op] && n_arrays == want_arrays[op] && h_arrays && (h_params || !n_params), "fpt_debug_bpt: wrong number of parameters or arrays for this op");
+		flush_deferred(ctx);
+		hipStream_t s = ctx->stream;
+		auto arr = [&](uint32_t k, bool may_be_null = false) { require(h_arrays[k] || may_be_null || !n, "fpt_debug_bpt: null array"); return h_arrays[k]; };
+		BptParams P; std::memset(&P, 0, sizeof(P));
+		if (op == 0 || op == 1 || op == 2)
+		{
+			if (n) launch_debug_bpt(op, n, static_cast<const uint32_t*>(arr(0)), static_cast<uint32_t*>(arr(1)), nullptr, nullptr, 0u, nullptr, s);
+		}
+		else if (op == 3)
+		{
+			require(!n || h_params[0] >= 1, "fpt_debug_bpt: the connection op needs materials");
+			if (n) launch_debug_bpt(op, n, static_cast<const uint32_t*>(arr(0)), static_cast<uint32_t*>(arr(1)), nullptr, static_cast<const fpt_material*>(arr(2)), h_params[0],
+			                        static_cast<const float*>(arr(3)), s);
+		}
+		else if (op == 4)
+		{
+			if (n) launch_debug_bpt(op, n, static_cast<const uint32_t*>(arr(0)), static_cast<uint32_t*>(arr(1)), nullptr, nullptr, 0u, static_cast<const float*>(arr(2)), s);
+		}
+		else if (op == 5)
+		{
+			require(h_arrays[2], "fpt_debug_bpt: null counter");
+			if (n) launch_debug_bpt(op, n, static_cast<const uint32_t*>(arr(0)), static_cast<uint32_t*>(arr(1)), static_cast<uint32_t*>(arr(2)), nullptr, 0u, nullptr, s);
+		}
+		else if (op == 6)
+		{
+			const uint32_t n_paths = h_params[0], L = h_params[1], n_passes = h_params[2];
+			require(n_paths >= 1 && L >= 1 && L <= 15 && n_passes >= 1 && uint64_t(n_paths) * L * n_passes < (1ull << 31), "fpt_debug_bpt: flat list: n_paths, L (1..15) or n_passes out of range");
+			require(h_arrays[0] && h_arrays[1] && h_arrays[2], "fpt_debug_bpt: null array");
+			const size_t nv = size_t(n_paths) * L * n_passes;
+			DeviceArray<uint32_t> sums; sums.alloc((nv + 4095) / 4096 + 1);
+			P.n_paths = n_paths; P.n_passes = n_passes; P.n_store = n_paths * n_passes; P.opt.max_path_length = L;
+			P.store.counts = static_cast<uint32_t*>(h_arrays[0]); P.flat = static_cast<uint32_t*>(h_arrays[1]); P.flat_meta = static_cast<uint32_t*>(h_arrays[2]);
+			P.flat_block_sums = sums.ptr;
+			launch_bpt_build_flat_list(P, s);
+			FPT_HIP_CHECK(hipGetLastError());
+			FPT_HIP_CHECK(hipStreamSynchronize(s));          // `sums` is released on return
+		}
+		else if (op == 7)
+		{
+			const uint32_t n_paths = h_params[0], n_passes = h_params[1];
+			require(n_paths >= 1 && n_passes >= 1 && uint64_t(n_paths) * n_passes < (1ull << 28), "fpt_debug_bpt: splats: n_paths or n_passes out of range");
+			for (uint32_t k = 3; k < 8; ++k) require(h_arrays[k] != nullptr, "fpt_debug_bpt: null array");
+			const size_t cells = size_t(n_paths) * n_passes * 3;
+			P.shadow.weights = static_cast<float4*>(arr(0)); P.shadow.hits = static_cast<float4*>(arr(1)); P.shadow.pixels = static_cast<uint32_t*>(arr(2));
+			P.shadow.size = static_cast<uint32_t*>(h_arrays[3]);
+			P.splat = static_cast<long long*>(h_arrays[4]);
+			P.fb.ch[FPT_FB_COMPOSITED_C] = static_cast<float4*>(h_arrays[6]); P.fb.ch[FPT_FB_DIRECT_C] = static_cast<float4*>(h_arrays[7]);
+			P.n_paths = n_paths; P.n_passes = n_passes; P.plane_stride = n_passes > 1 ? n_paths : 0u; P.instance = h_params[2];
+			FPT_HIP_CHECK(hipMemcpyAsync(P.shadow.size, &n, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+			FPT_HIP_CHECK(hipMemsetAsync(P.splat, 0, cells * sizeof(long long), s));
+			if (n) launch_bpt_splat(P, n, s);
+			FPT_HIP_CHECK(hipMemcpyAsync(h_arrays[5], P.splat, cells * sizeof(long long), hipMemcpyDeviceToDevice, s));
+			launch_bpt_splat_resolve(P, s);
+		}
+		else
+		{
+			const uint32_t n_local = h_params[0], n_paths = h_params[1], base_instance = h_params[2], n_passes = h_params[3];
+			require(n_local >= 1 && n_local <= n_paths && n_passes >= 1, "fpt_debug_bpt: merge: n_local, n_paths or n_passes out of range");
+			for (uint32_t k = 0; k < 12; ++k) require(h_arrays[k] != nullptr, "fpt_debug_bpt: null array");
+			FrameBufferDev fb; std::memset(&fb, 0, sizeof(fb));
+			for (int c = 0; c < 6; ++c) fb.ch[c] = static_cast<float4*>(h_arrays[c]);
+			BptLog g; g.val = static_cast<float4*>(h_arrays[8]); g.chan = static_cast<uint32_t*>(h_arrays[9]); g.mask = static_cast<uint32_t*>(h_arrays[10]);
+			g.cap = h_params[4]; g.mask_words = h_params[5]; g.conn_cells = h_params[6];
+			require(g.cap >= uint64_t(n_paths) * n_passes, "fpt_debug_bpt: merge: the log's capacity is below n_paths x n_passes");
+			launch_bpt_merge_exact(fb, static_cast<float4*>(h_arrays[6]), static_cast<float4*>(h_arrays[7]), g, static_cast<long long*>(h_arrays[11]),
+			                       static_cast<const uint32_t*>(h_arrays[12]), n_local, n_paths, base_instance, n_passes, 0u, s);
+		}
+		FPT_HIP_CHECK(hipGetLastError());
+		FPT_HIP_CHECK(hipStreamSynchronize(s));
+	});
+}
+
 } // extern "C"

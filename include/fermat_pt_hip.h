@@ -345,6 +345,12 @@ int fpt_bpt_get_stats(fpt_context* ctx, fpt_bpt_stats* out);             /* vali
 int fpt_bpt_set_profiling(fpt_context* ctx, int on);                      /* 1: read the queue sizes back after every launch (tests) */
 /* light-vertex store of the last pass (host arrays sized n_pixels * max_path_length, counts n_pixels) */
 int fpt_bpt_download_light_vertices(fpt_context* ctx, float* h_pos, uint32_t* h_input, uint32_t* h_gbuffer, float* h_weights, uint32_t* h_path_id, uint32_t* h_counts);
+/* Light-tracing splats, the rule of the fixed-point sums.  One queue entry adds, per colour component, the integer
+ *     q = round_half_even(double(float(weight * frame_weight)) * 2^32)      (the product in float, the scaling in double: exact)
+ * with the per-entry value SATURATED at the conversion: q = 2^63 - 1 from weight * frame_weight >= 2^31 on (+infinity included), q = -2^63 at or below -2^31, and a
+ * NaN adds nothing.  The light tracer's finite check lets such weights through (the geometric term reaches 1e8 when the squared distance clamps to 1e-8).  The sums
+ * themselves are 64-bit two's-complement: they wrap modulo 2^64, so a pixel that received one saturated entry holds a sum without meaning -- the rule makes the
+ * device, the oracle and every order of the entries agree on it, nothing more.  The frame receives float(double(sum) * 2^-32) per component. */
 /* the light-tracing splat sums (3 x int64 per pixel, 2^-32 fixed point) BEFORE they are folded into the frame: under tile sharding every
  * rank splats to arbitrary pixels, so ranks sum these buffers (integer all-reduce) and then call fpt_bpt_resolve_splats */
 int64_t* fpt_bpt_splat_buffer(fpt_context* ctx);
@@ -489,6 +495,41 @@ int fpt_debug_vertex(fpt_context* ctx, const fpt_rendering_context_view* view, i
  *   3 mean:       size = n, d_in 4 x int64 per cell -> d_out1 3 floats per cell (untouched where the count is 0) */
 int fpt_debug_psf(fpt_context* ctx, int op, uint32_t flags, uint32_t n, const void* d_in, uint32_t size, float firefly, void* d_out0, void* d_out1,
                   uint32_t* d_touched, uint32_t* d_touched_n);
+/* Bidirectional probe: the packers, the camera terms, the MIS bookkeeping and the integer machinery of `-bpt` on inputs a test chose, through the functions the
+ * kernels call (ops 0 to 5: one element per thread, all elements in ONE launch of the probe kernel) or through the product's kernels themselves (ops 6, 7, 8).
+ * h_params: HOST array of n_params words; h_arrays: HOST array of n_arrays DEVICE pointers.  Records are 32-bit words; integer fields (marked #) hold their BITS.
+ *   0 packers:   arrays {in 16 words per element, out 32 words per element}.  in [0..2] colour, [3..5] direction, [6] roughness, [7] opacity, [8] ior,
+ *                [9] # a direction code, [10..12] specular, [13..15] diffuse transmission.  out [0] # to_rgbe(colour), [1..3] from_rgbe of it, [4] # pack_direction,
+ *                [5..7] unpack_direction of it, [8] # pack_gbuffer_normal(direction), [9..12] # pack_material(colour as diffuse, specular, transmission, ...),
+ *                unpack_material of it: [13] roughness, [14] opacity, [15] ior, [16..18] diffuse / pi, [19..21] specular / pi, [22..24] transmission / pi,
+ *                [25..27] unpack_direction(in [9])
+ *   1 camera:    arrays {in 24 words per element, out 12}.  in [0..2] eye, [3..5] U, [6..8] V, [9..11] W, [12] sq_focal, [13] # res_x, [14] # res_y,
+ *                [15..17] a world point.  out [0] camera_pdf, [1] ox, [2] oy (0 outside the frustum), [3] # the light tracer's pixel of (ox, oy),
+ *                [4] # in-frustum flag (pdf x res_x res_y != 0), [5..7] the unit direction from the eye, [8] the clamped squared distance
+ *   2 weights:   arrays {in 12 words per element, out 4}.  in [0..3] pw = (pGp_sum, pG, out_p, out_cos_theta), [4] t, [5..7] in, [8..10] n, [11] # 1 = light
+ *                vertex.  out [0] G', [1] prev_pG, [2] pGp_sum
+ *   3 connect:   params {n_mats}; arrays {in 48 words per element, out 64, mats (n_mats records), the 32^4 glossy table}.  load_stored, then connect (eval_connection)
+ *                against an eye vertex.  in [0] # material slot of the eye vertex, [1..12] its frame n, ng, t, b, [13..15] position, [16..18] in, [19..21] alpha,
+ *                [22] prev_pG, [23] pGp_sum, [24] # eye depth, [25] # light depth, [26] # options (1 rr, 2 direct_lighting_nee, 4 direct_lighting_bsdf),
+ *                [32..47] the stored light vertex as its 64-byte record: position + # packed normal, # gbuffer x 4, # packed in, # packed alpha, pGp_sum, pG, 4 spare.
+ *                out [0..2] the connection weight, [3..5] out, [6] d2, [7] G, [8..10] f_s, [11] p_s, [12..14] f_L, [15] p_L, [16] pGp, [17] prev_pGp,
+ *                [18] next_pGp, [19] mis_w (from f_L on: 0 where connect returned before them), the unpacked light vertex: [20..22] position, [23..25] n,
+ *                [26..28] in, [29..31] alpha, [32..34] edf, [35] pGp_sum, [36] pG, and at depth > 0 [37] roughness, [38] opacity, [39] ior; [40..42] its tangent, [43..45] its binormal
+ *   4 lens:      arrays {in 48 words per element, out 64, the glossy table}.  load_stored, then stage B of the light tracer (connect_to_camera).  in [0..2] eye,
+ *                [3..5] U, [6..8] V, [9..11] W, [12] sq_focal, [13] # res_x, [14] # res_y, [15] light_tracing, [16] # n_paths, [17] # light depth (>= 1),
+ *                [18] # options (1 direct_lighting_nee, 2 direct_lighting_bsdf, 4 indirect_lighting_nee, 8 indirect_lighting_bsdf), [32..47] as op 3.
+ *                out [0..2] the sample's weight, [3..5] out, [6] d2, [7] G, [8] f_s, [9] ox, [10] oy, [11] p_s, [12..14] f_L, [15] p_L, [16] pGp, [17] cos_theta,
+ *                [18] next_pGp, [19] mis_w, [20..45] as op 3, [48..50] the shadow origin (when wanted), [52] # want, [53] # pixel (when wanted), [54] 1 / n_paths
+ *   5 ranges:    arrays {n counts (0..15), n bases out, the counter: ONE word the caller preset}.  n threads in blocks of 256 call block_range_alloc
+ *   6 flat list: params {n_paths, L, n_passes}; arrays {counts (n_paths x n_passes), flat out (n_paths x L x n_passes), flat_meta out (2 n_passes + 1)}:
+ *                launch_bpt_build_flat_list as `-sc 1` runs it
+ *   7 splats:    n queue entries; params {n_paths, n_passes, instance}; arrays {weights float4 per entry, hits float4 per entry (.x < 0 = unoccluded), # virtual
+ *                pixel per entry, one word of scratch (the queue size), 3 x int64 per virtual pixel of scratch, the same again: the SUMS before the resolve (out),
+ *                COMPOSITED_C and DIRECT_C float4 per virtual pixel (in/out)}: splat_kernel, then splat_resolve_kernel
+ *   8 merge:     params {n_local, n_paths, base_instance, n_passes, log cap, log mask_words, log conn_cells}; arrays {the six accumulation channels (float4 per
+ *                pixel), the DIFFUSE_A and SPECULAR_A planes (float4 per virtual pixel), log values (float4 x cells x cap), log channels (# x cells x cap), log
+ *                mask (# x cap x mask_words), splat sums (3 x int64 per virtual pixel), # pixel list (n_local) or NULL}: merge_exact_kernel, all arrays in place */
+int fpt_debug_bpt(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_params, uint32_t n_params, void* const* h_arrays, uint32_t n_arrays);
 /* debug entry (tests of the cache under load): the cache of a context after fpt_psfpt_init and before its first render, fpt_psfpt_set_batch or
  * fpt_psfpt_set_sharded, re-allocated with 2^log2_size slots (8..24) and cleared.  A table that fills up refuses further keys: their vertices stay uncached. */
 int fpt_psfpt_debug_set_table_log2(fpt_context* ctx, uint32_t log2_size);

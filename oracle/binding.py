@@ -322,6 +322,16 @@ def psf_probe(op, data, size=0, firefly=100.0, touched=False):
     return o1
 
 
+def bpt_probe(op, arrays, params=(), n=None):
+    """orc_bpt_probe_n, the twin of fermat_amd's Renderer.debug_bpt (ops 0 to 4 and 7): the same arguments, the same results"""
+    work = [None if a is None else np.ascontiguousarray(a).copy() for a in arrays]
+    n = len(work[0]) if n is None else int(n)
+    ptrs = (C.c_void_p * max(1, len(work)))(*[None if a is None or not a.size else a.ctypes.data for a in work])
+    par = (C.c_uint32 * max(1, len(params)))(*[int(p) for p in params])
+    lib().orc_bpt_probe_n(C.c_int32(op), C.c_uint32(n), par, ptrs)
+    return work
+
+
 def filter_variance(img, fw):
     """filter_variance_kernel (src/renderer.cu:366-399) on an (H, W, 4) float32 image -> (H, W) variance"""
     img = np.ascontiguousarray(img, np.float32); h, w = img.shape[:2]

@@ -135,6 +135,38 @@ inline float camera_direction_pdf_xy(V3 U, V3 V, V3 W, float W_len, float sq_foc
 	return 0.0f;
 }
 
+// connect_to_camera (src/bpt_kernels.h:919-1032): the unit direction from the lens to a point with the clamped squared distance, and the pixel of a screen position
+inline V3 lens_direction(V3 eye, V3 position, float& d2)
+{
+	const V3 delta = position - eye;
+	d2 = fmax_ieee(1.0e-8f, dot(delta, delta));
+	const float d = sqrtf(d2);
+	return delta / d;
+}
+inline u32 lens_pixel(float out_x, float out_y, u32 res_x, u32 res_y) { return quantize(out_x * 0.5f + 0.5f, res_x) + quantize(out_y * 0.5f + 0.5f, res_y) * res_x; }
+
+// MIS bookkeeping of LightVertex / EyeVertex::setup(ray, hit, ...) (src/bpt_utils.h:340-361, 585-642); len2 = 1 is the reference (see setup_eye)
+inline void path_weights_step(const TempPathWeights& w, float t, V3 in, V3 n, bool light, float len2, float& G_prime, float& prev_pG, float& pGp_sum)
+{
+	G_prime = light ? fabsf(dot(in, n)) / fmax_ieee(t * t, MIN_G_DENOM) : fabsf(dot(in, n)) / (t * t * len2);
+	prev_pG = pdf_product(w.out_p, w.out_cos_theta * G_prime);
+	pGp_sum = w.pGp_sum + (1 / pdf_product(w.pG, w.out_p));
+}
+
+// one light-tracing splat in 2^-32 fixed point (DEFINED HERE, the rule of include/fermat_pt_hip.h): weight x frame weight in float, x 2^32 in double (exact),
+// rounded half to even; a value outside int64 saturates at its end of the range, a NaN adds nothing.  The sums wrap modulo 2^64.
+inline long long splat_fixed(float v)
+{
+	const double x = double(v) * 4294967296.0;
+	if (x != x) return 0;
+	if (x >= 9223372036854775808.0) return 0x7FFFFFFFFFFFFFFFll;
+	if (x <= -9223372036854775808.0) return -0x7FFFFFFFFFFFFFFFll - 1;
+	return (long long)rint(x);
+}
+inline void splat_fixed3(V4 w, float fw, long long q[3]) { q[0] = splat_fixed(w.x * fw); q[1] = splat_fixed(w.y * fw); q[2] = splat_fixed(w.z * fw); }
+inline void splat_add(long long& sum, long long q) { sum = (long long)((unsigned long long)sum + (unsigned long long)q); }
+inline float splat_to_float(long long sum) { return float(double(sum) * (1.0 / 4294967296.0)); }
+
 // Edf sampling : contrib/cugar/bsdf/lambert_edf.h:82-99
 inline void edf_sample(const Edf& e, float u0, float u1, const Frame& g, V3& out, V3& gg, float& p, float& p_proj)
 {
@@ -179,12 +211,10 @@ struct BptVertex            // the fields LightVertex and EyeVertex share
 	{
 		shade(ray, hit, r, true);
 		alpha = _alpha; depth = _depth; weights.pGp_sum = w.pGp_sum; weights.pG = w.pG;
-		prev_G_prime = fabsf(dot(in, geom.normal_s)) / fmax_ieee(hit.t * hit.t, MIN_G_DENOM);
-		prev_pG = pdf_product(w.out_p, w.out_cos_theta * prev_G_prime);
-		pGp_sum = w.pGp_sum + (1 / pdf_product(w.pG, w.out_p));
+		path_weights_step(w, hit.t, in, geom.normal_s, true, 1.0f, prev_G_prime, prev_pG, pGp_sum);
 	}
 	// LightVertex::setup(pos, packed info...) : :313-337
-	void setup_stored(const float* pos, u32 packed_in, u32 packed_alpha, const PackedBsdf& gb, PathWeights w, u32 _depth, const SceneView& r)
+	void setup_stored(const float* pos, u32 packed_in, u32 packed_alpha, const PackedBsdf& gb, PathWeights w, u32 _depth, const float* table)
 	{
 		in = unpack_direction(packed_in);
 		alpha = from_rgbe(packed_alpha);
@@ -195,7 +225,7 @@ struct BptVertex            // the fields LightVertex and EyeVertex share
 		geom.tangent = orthogonal(geom.normal_s);
 		geom.binormal = cross(geom.normal_s, geom.tangent);
 		if (depth == 0) edf.color = from_rgbe(gb.x);
-		else unpack_bsdf(gb, r.glossy_reflectance, bsdf);
+		else unpack_bsdf(gb, table, bsdf);
 	}
 	// EyeVertex::setup(ray, hit, alpha, TempPathWeights, depth) : :585-642
 	// NB hit.t is in units of |ray.dir| and the primary eye rays are not normalised (src/bpt_kernels.h:569-572), so at the first eye vertex the
@@ -206,9 +236,7 @@ struct BptVertex            // the fields LightVertex and EyeVertex share
 		shade(ray, hit, r, false);
 		alpha = _alpha; depth = _depth; tweights = w;
 		const float len2 = true_distance ? (ray.dx * ray.dx + ray.dy * ray.dy) + ray.dz * ray.dz : 1.0f;
-		prev_G_prime = fabsf(dot(in, geom.normal_s)) / (hit.t * hit.t * len2);
-		prev_pG = pdf_product(w.out_p, w.out_cos_theta * prev_G_prime);
-		pGp_sum = w.pGp_sum + (1 / pdf_product(w.pG, w.out_p));
+		path_weights_step(w, hit.t, in, geom.normal_s, false, len2, prev_G_prime, prev_pG, pGp_sum);
 	}
 };
 
@@ -220,8 +248,9 @@ inline bool bpt_scatter(const BptVertex& v, const float z[3], u32& comp, V3& out
 	return s;
 }
 
-// eval_connection : src/bpt_utils.h:911-980 (mis_selector is the identity: DEBUG_S = DEBUG_T = -1)
-inline void eval_connection(const BptVertex& ev, const BptVertex& lv, V3& out, V3& out_w, float& d, bool RR, bool direct_lighting_nee, bool direct_lighting_bsdf)
+// eval_connection : src/bpt_utils.h:911-980 (mis_selector is the identity: DEBUG_S = DEBUG_T = -1); `terms` (the probe's) receives the intermediates
+struct ConnectTerms { V3 out; float d2, G; V3 f_s; float p_s; V3 f_L; float p_L, pGp, prev_pGp, next_pGp, mis_w; };
+inline void eval_connection(const BptVertex& ev, const BptVertex& lv, V3& out, V3& out_w, float& d, bool RR, bool direct_lighting_nee, bool direct_lighting_bsdf, ConnectTerms* terms = nullptr)
 {
 	const V3 delta = lv.geom.position - ev.geom.position;
 	const float d2 = fmax_ieee(MIN_G_DENOM, dot(delta, delta));
@@ -231,6 +260,7 @@ inline void eval_connection(const BptVertex& ev, const BptVertex& lv, V3& out, V
 	V3 f_s; float p_s;
 	ev.bsdf.f_and_p_sum(ev.geom, ev.in, out, f_s, p_s, RR);
 	const float prev_pGp = pdf_product(ev.prev_pG, p_s);
+	if (terms) { terms->out = out; terms->d2 = d2; terms->G = G; terms->f_s = f_s; terms->p_s = p_s; terms->prev_pGp = prev_pGp; }
 	if (lv.depth == 0)
 	{
 		if (direct_lighting_nee == false) { out_w = V3(0.0f); return; }
@@ -239,6 +269,7 @@ inline void eval_connection(const BptVertex& ev, const BptVertex& lv, V3& out, V
 		const float pGp = pdf_product3(p_s, G, p_L);
 		const float next_pGp = pdf_product(p_L, lv.weights.pG);
 		const float mis_w = (ev.depth == 0 && direct_lighting_bsdf == false) ? 1.0f : bpt_mis(pGp, prev_pGp, next_pGp, ev.pGp_sum + lv.weights.pGp_sum);
+		if (terms) { terms->f_L = f_L; terms->p_L = p_L; terms->pGp = pGp; terms->next_pGp = next_pGp; terms->mis_w = mis_w; }
 		out_w = ev.alpha * lv.alpha * f_L * f_s * G * mis_w;
 	}
 	else
@@ -248,6 +279,7 @@ inline void eval_connection(const BptVertex& ev, const BptVertex& lv, V3& out, V
 		const float pGp = pdf_product3(p_s, G, p_L);
 		const float next_pGp = pdf_product(p_L, lv.weights.pG);
 		const float mis_w = bpt_mis(pGp, prev_pGp, next_pGp, ev.pGp_sum + lv.weights.pGp_sum);
+		if (terms) { terms->f_L = f_L; terms->p_L = p_L; terms->pGp = pGp; terms->next_pGp = next_pGp; terms->mis_w = mis_w; }
 		out_w = ev.alpha * lv.alpha * f_L * f_s * G * mis_w;
 	}
 }
@@ -523,7 +555,7 @@ struct BPT
 					const u32 light_depth = light_vertex_id >> 24;
 					BptVertex lv;
 					PathWeights lw; lw.pGp_sum = v_weights[2 * li]; lw.pG = v_weights[2 * li + 1];
-					lv.setup_stored(&v_pos[4 * li], v_input[2 * li], v_input[2 * li + 1], v_gbuffer[li], lw, light_depth, scene());
+					lv.setup_stored(&v_pos[4 * li], v_input[2 * li], v_input[2 * li + 1], v_gbuffer[li], lw, light_depth, scene().glossy_reflectance);
 					V3 out, out_w; float d;
 					eval_connection(ev, lv, out, out_w, d, options.rr != 0, options.direct_lighting_nee != 0, options.direct_lighting_bsdf != 0);
 					out_w = out_w * light_weight;
@@ -549,7 +581,7 @@ struct BPT
 				const u32 li = light_path_id + light_depth * n_light_paths;
 				BptVertex lv;
 				PathWeights lw; lw.pGp_sum = v_weights[2 * li]; lw.pG = v_weights[2 * li + 1];
-				lv.setup_stored(&v_pos[4 * li], v_input[2 * li], v_input[2 * li + 1], v_gbuffer[li], lw, light_depth, scene());
+				lv.setup_stored(&v_pos[4 * li], v_input[2 * li], v_input[2 * li + 1], v_gbuffer[li], lw, light_depth, scene().glossy_reflectance);
 				V3 out, out_w; float d;
 				eval_connection(ev, lv, out, out_w, d, options.rr != 0, options.direct_lighting_nee != 0, options.direct_lighting_bsdf != 0);
 				if (max_comp(out_w) > 0.0f && finite_f(out_w.x) && finite_f(out_w.y) && finite_f(out_w.z))
@@ -598,7 +630,55 @@ struct BPT
 		}
 	}
 
-	// connect_to_camera : src/bpt_kernels.h:919-1032 ; light_tracing src/bpt_control.h:572-600
+	// connect_to_camera for one stored vertex of depth >= 1 : src/bpt_kernels.h:919-1032.  The sample's weight, its pixel and the origin of its shadow ray; false
+	// when nothing is to be traced.  `terms` (the probe's) receives the intermediates
+	struct LensTerms { V3 out; float d2, cos_theta, G, p_s, f_s, ox, oy; V3 f_L; float p_L, pGp, next_pGp, mis_w; };
+	bool lens_sample(const float* pos, u32 packed_in, u32 packed_alpha, const PackedBsdf& gb, float lv_pGp_sum, float lv_pG, u32 light_depth, V3 eye, u32 res_x, u32 res_y,
+	                 const float* table, V4& out_w, u32& pixel, V3& origin, LensTerms* terms) const
+	{
+		const float light_weight = 1.0f / float(n_light_paths);
+		VertexGeometry geom;
+		geom.position = V3(pos[0], pos[1], pos[2]);
+		geom.normal_s = unpack_direction(f2bits(pos[3]));
+		geom.normal_g = geom.normal_s;
+		geom.tangent = orthogonal(geom.normal_s);
+		geom.binormal = cross(geom.normal_s, geom.tangent);
+		const V3 in_dir = unpack_direction(packed_in);
+		const V3 in_alpha = from_rgbe(packed_alpha);
+		float d2;
+		const V3 out = lens_direction(eye, geom.position, d2);
+		const float cos_theta = dot(out, W) / W_len;
+		const float G = fabsf(cos_theta * dot(out, geom.normal_s)) / d2;
+		float out_x = 0, out_y = 0;
+		const float p_s = camera_direction_pdf_xy(U, V, W, W_len, sq_focal, out, &out_x, &out_y, true);
+		const float f_s = p_s * float(res_x * res_y);
+		if (terms) { *terms = LensTerms{}; terms->out = out; terms->d2 = d2; terms->cos_theta = cos_theta; terms->G = G; terms->p_s = p_s; terms->f_s = f_s; terms->ox = out_x; terms->oy = out_y; }
+		if (!f_s && !terms) return false;
+		Bsdf light_bsdf;
+		unpack_bsdf(gb, table, light_bsdf);
+		const V3 f_L = light_bsdf.f_sum(geom, in_dir, -out);
+		const float p_L = light_bsdf.p_sum(geom, in_dir, -out, true);
+		const float pGp = pdf_product3(p_s, G, p_L);
+		// the reference prices the neighbouring strategy with max_comp(f_L) where its own scheme wants the reverse pdf (src/bpt_kernels.h:1009):
+		// the second origin of the light-tracing energy mismatch (it darkens; what-if bit 1 puts the pdf there)
+		const float next_pGp = pdf_product((whatif_consistent_mis & 2u) ? light_bsdf.p_sum(geom, -out, in_dir, true) : max_comp(f_L), lv_pG);
+		const float mis_w =
+			(light_depth == 1 && !options.direct_lighting_nee && !options.direct_lighting_bsdf) ? 1.0f :
+			(light_depth > 1 && !options.indirect_lighting_nee && !options.indirect_lighting_bsdf) ? 1.0f :
+			bpt_mis(pGp / light_tracing, next_pGp, lv_pGp_sum);
+		const V3 c = in_alpha * f_L * f_s * G * mis_w;
+		out_w = V4(c.x, c.y, c.z, 1.0f) * light_weight;
+		if (terms) { terms->f_L = f_L; terms->p_L = p_L; terms->pGp = pGp; terms->next_pGp = next_pGp; terms->mis_w = mis_w; }
+		if (max_comp(out_w.xyz()) > 0.0f && finite_f(out_w.x) && finite_f(out_w.y) && finite_f(out_w.z))
+		{
+			origin = geom.position + in_dir * SHADOW_BIAS;
+			pixel = lens_pixel(out_x, out_y, res_x, res_y);
+			return true;
+		}
+		return false;
+	}
+
+	// light_tracing src/bpt_control.h:572-600
 	void light_tracing_pass()
 	{
 		stats.shadow_light_tracing = 0;
@@ -611,49 +691,15 @@ struct BPT
 				const u32 id = shard_id(ii);
 				const u32 li = id + k * n_light_paths;
 				const u32 light_depth = v_path_id[li] >> 24;
-				const float light_weight = 1.0f / float(n_light_paths);
 				if (light_depth == 0) continue;                     // primary light vertices: "visible lights (a very silly strategy)" is compiled out
-				VertexGeometry geom;
-				geom.position = V3(v_pos[4 * li], v_pos[4 * li + 1], v_pos[4 * li + 2]);
-				geom.normal_s = unpack_direction(f2bits(v_pos[4 * li + 3]));
-				geom.normal_g = geom.normal_s;
-				geom.tangent = orthogonal(geom.normal_s);
-				geom.binormal = cross(geom.normal_s, geom.tangent);
-				const V3 in_dir = unpack_direction(v_input[2 * li]);
-				const V3 in_alpha = from_rgbe(v_input[2 * li + 1]);
-				const V3 delta = geom.position - eye;
-				const float d2 = fmax_ieee(1.0e-8f, dot(delta, delta));
-				const float d = sqrtf(d2);
-				const V3 out = delta / d;
-				const float cos_theta = dot(out, W) / W_len;
-				const float G = fabsf(cos_theta * dot(out, geom.normal_s)) / d2;
-				float out_x = 0, out_y = 0;
-				const float p_s = camera_direction_pdf_xy(U, V, W, W_len, sq_focal, out, &out_x, &out_y, true);
-				const float f_s = p_s * float(scene().res_x * scene().res_y);
-				if (!f_s) continue;
-				Bsdf light_bsdf;
-				unpack_bsdf(v_gbuffer[li], scene().glossy_reflectance, light_bsdf);
-				const V3 f_L = light_bsdf.f_sum(geom, in_dir, -out);
-				const float p_L = light_bsdf.p_sum(geom, in_dir, -out, true);
-				const float pGp = pdf_product3(p_s, G, p_L);
-				// the reference prices the neighbouring strategy with max_comp(f_L) where its own scheme wants the reverse pdf (src/bpt_kernels.h:1009):
-				// the second origin of the light-tracing energy mismatch (it darkens; what-if bit 1 puts the pdf there)
-				const float next_pGp = pdf_product((whatif_consistent_mis & 2u) ? light_bsdf.p_sum(geom, -out, in_dir, true) : max_comp(f_L), v_weights[2 * li + 1]);
-				const float mis_w =
-					(light_depth == 1 && !options.direct_lighting_nee && !options.direct_lighting_bsdf) ? 1.0f :
-					(light_depth > 1 && !options.indirect_lighting_nee && !options.indirect_lighting_bsdf) ? 1.0f :
-					bpt_mis(pGp / light_tracing, next_pGp, v_weights[2 * li]);
-				const V3 c = in_alpha * f_L * f_s * G * mis_w;
-				const V4 out_w = V4(c.x, c.y, c.z, 1.0f) * light_weight;
-				if (max_comp(out_w.xyz()) > 0.0f && finite_f(out_w.x) && finite_f(out_w.y) && finite_f(out_w.z))
-				{
-					Shadow s;
-					const V3 origin = geom.position + in_dir * SHADOW_BIAS;
-					s.ray = make_ray(origin, SHADOW_TMIN, eye - origin, 0.9999f);
-					s.pixel = pixel_info_pack(quantize(out_x * 0.5f + 0.5f, scene().res_x) + quantize(out_y * 0.5f + 0.5f, scene().res_y) * scene().res_x, FB_DIRECT_C, 0);
-					s.w = out_w; s.light_path_id = 0;
-					shadow_queue.push_back(s);
-				}
+				V4 out_w; u32 pixel; V3 origin;
+				if (!lens_sample(&v_pos[4 * li], v_input[2 * li], v_input[2 * li + 1], v_gbuffer[li], v_weights[2 * li], v_weights[2 * li + 1], light_depth, eye,
+				                 scene().res_x, scene().res_y, scene().glossy_reflectance, out_w, pixel, origin, nullptr)) continue;
+				Shadow s;
+				s.ray = make_ray(origin, SHADOW_TMIN, eye - origin, 0.9999f);
+				s.pixel = pixel_info_pack(pixel, FB_DIRECT_C, 0);
+				s.w = out_w; s.light_path_id = 0;
+				shadow_queue.push_back(s);
 			}
 		stats.shadow_light_tracing = u32(shadow_queue.size());
 		host->trace_queue(shadow_queue, false);
@@ -663,12 +709,12 @@ struct BPT
 			const Shadow& s = shadow_queue[i];
 			if (!(s.hit.t < 0.0f)) continue;
 			const u32 pixel = pi_pixel(s.pixel);
-			const float v[3] = { s.w.x * frame_weight, s.w.y * frame_weight, s.w.z * frame_weight };
+			long long q[3];
+			splat_fixed3(s.w, frame_weight, q);
 			for (int c = 0; c < 3; ++c)
 			{
-				const long long q = (long long)rint(double(v[c]) * 4294967296.0);
-				splat[size_t(pixel) * 6 + c] += q;
-				splat[size_t(pixel) * 6 + 3 + c] += q;
+				splat_add(splat[size_t(pixel) * 6 + c], q[c]);
+				splat_add(splat[size_t(pixel) * 6 + 3 + c], q[c]);
 			}
 		}
 		shadow_queue.clear();
@@ -683,8 +729,8 @@ struct BPT
 			long long* q = &splat[size_t(p) * 6];
 			if (!(q[0] | q[1] | q[2])) continue;
 			V4 c = f.get(FB_COMPOSITED_C, p), dch = f.get(FB_DIRECT_C, p);
-			c.x += float(double(q[0]) * (1.0 / 4294967296.0)); c.y += float(double(q[1]) * (1.0 / 4294967296.0)); c.z += float(double(q[2]) * (1.0 / 4294967296.0));
-			dch.x += float(double(q[3]) * (1.0 / 4294967296.0)); dch.y += float(double(q[4]) * (1.0 / 4294967296.0)); dch.z += float(double(q[5]) * (1.0 / 4294967296.0));
+			c.x += splat_to_float(q[0]); c.y += splat_to_float(q[1]); c.z += splat_to_float(q[2]);
+			dch.x += splat_to_float(q[3]); dch.y += splat_to_float(q[4]); dch.z += splat_to_float(q[5]);
 			f.set(FB_COMPOSITED_C, p, c); f.set(FB_DIRECT_C, p, dch);
 			for (int k = 0; k < 6; ++k) q[k] = 0;
 		}

@@ -569,6 +569,144 @@ void orc_from_rgbe(u32 p, float* o) { const V3 v = from_rgbe(p); o[0] = v.x; o[1
 u32 orc_pack_direction(float x, float y, float z) { return pack_direction(V3(x, y, z)); }
 void orc_unpack_direction(u32 p, float* o) { const V3 v = unpack_direction(p); o[0] = v.x; o[1] = v.y; o[2] = v.z; }
 
+// twin of the device probe fpt_debug_bpt (include/fermat_pt_hip.h has the layouts), ops 0 to 4 and 7, through the functions of o_bpt.h the oracle renders with.
+// Ops 5, 6 and 8 have no oracle code of their own: ranges, list order and merge order are defined in the header and tests/bpt_truth.py alone decides them.
+void orc_bpt_probe_n(i32 op, u32 n, const u32* params, void* const* arrays)
+{
+	if (op == 0)
+	{
+		const float* in = static_cast<const float*>(arrays[0]); u32* out = static_cast<u32*>(arrays[1]);
+		for (u32 i = 0; i < n; ++i)
+		{
+			const float* r = in + 16 * size_t(i); u32* o = out + 32 * size_t(i);
+			const V3 c(r[0], r[1], r[2]), d(r[3], r[4], r[5]);
+			const u32 e = to_rgbe(c); const V3 back = from_rgbe(e);
+			o[0] = e; o[1] = f2bits(back.x); o[2] = f2bits(back.y); o[3] = f2bits(back.z);
+			const u32 pd = pack_direction(d); const V3 ud = unpack_direction(pd);
+			o[4] = pd; o[5] = f2bits(ud.x); o[6] = f2bits(ud.y); o[7] = f2bits(ud.z);
+			o[8] = f2bits(pack_geometry_normal(d));
+			Material m{};
+			m.diffuse = V4(c.x, c.y, c.z, 0.0f); m.specular = V4(r[10], r[11], r[12], 0.0f); m.diffuse_trans = V4(r[13], r[14], r[15], 0.0f);
+			m.roughness = r[6]; m.opacity = r[7]; m.index_of_refraction = r[8];
+			const PackedBsdf pm = pack_bsdf(m);
+			o[9] = pm.x; o[10] = pm.y; o[11] = pm.z; o[12] = pm.w;
+			Bsdf b; unpack_bsdf(pm, nullptr, b);
+			o[13] = f2bits(b.glossy.roughness); o[14] = f2bits(b.opacity); o[15] = f2bits(b.ior);
+			o[16] = f2bits(b.diffuse.color.x); o[17] = f2bits(b.diffuse.color.y); o[18] = f2bits(b.diffuse.color.z);
+			o[19] = f2bits(b.fresnel.x); o[20] = f2bits(b.fresnel.y); o[21] = f2bits(b.fresnel.z);
+			o[22] = f2bits(b.diffuse_trans.color.x); o[23] = f2bits(b.diffuse_trans.color.y); o[24] = f2bits(b.diffuse_trans.color.z);
+			const V3 uc = unpack_direction(f2bits(r[9]));
+			o[25] = f2bits(uc.x); o[26] = f2bits(uc.y); o[27] = f2bits(uc.z);
+		}
+	}
+	else if (op == 1)
+	{
+		const float* in = static_cast<const float*>(arrays[0]); u32* out = static_cast<u32*>(arrays[1]);
+		for (u32 i = 0; i < n; ++i)
+		{
+			const float* r = in + 24 * size_t(i); u32* o = out + 12 * size_t(i);
+			const V3 eye(r[0], r[1], r[2]), U(r[3], r[4], r[5]), V(r[6], r[7], r[8]), W(r[9], r[10], r[11]);
+			const u32 res_x = f2bits(r[13]), res_y = f2bits(r[14]);
+			float d2, ox = 0.0f, oy = 0.0f;
+			const V3 dir = lens_direction(eye, V3(r[15], r[16], r[17]), d2);
+			const float p_s = camera_direction_pdf_xy(U, V, W, length(W), r[12], dir, &ox, &oy, true);
+			const float f_s = p_s * float(res_x * res_y);
+			o[0] = f2bits(p_s); o[1] = f2bits(ox); o[2] = f2bits(oy); o[3] = lens_pixel(ox, oy, res_x, res_y); o[4] = f_s ? 1u : 0u;
+			o[5] = f2bits(dir.x); o[6] = f2bits(dir.y); o[7] = f2bits(dir.z); o[8] = f2bits(d2);
+		}
+	}
+	else if (op == 2)
+	{
+		const float* in = static_cast<const float*>(arrays[0]); u32* out = static_cast<u32*>(arrays[1]);
+		for (u32 i = 0; i < n; ++i)
+		{
+			const float* r = in + 12 * size_t(i); u32* o = out + 4 * size_t(i);
+			TempPathWeights w; w.pGp_sum = r[0]; w.pG = r[1]; w.out_p = r[2]; w.out_cos_theta = r[3];
+			float G_prime, prev_pG, pGp_sum;
+			path_weights_step(w, r[4], V3(r[5], r[6], r[7]), V3(r[8], r[9], r[10]), f2bits(r[11]) != 0u, 1.0f, G_prime, prev_pG, pGp_sum);
+			o[0] = f2bits(G_prime); o[1] = f2bits(prev_pG); o[2] = f2bits(pGp_sum);
+		}
+	}
+	else if (op == 3 || op == 4)
+	{
+		const u32* in = static_cast<const u32*>(arrays[0]); u32* out = static_cast<u32*>(arrays[1]);
+		const Material* mats = op == 3 ? static_cast<const Material*>(arrays[2]) : nullptr;
+		const float* table = static_cast<const float*>(arrays[op == 3 ? 3 : 2]);
+		#pragma omp parallel for schedule(static)
+		for (i32 i = 0; i < i32(n); ++i)
+		{
+			const u32* r = in + 48 * size_t(i); u32* o = out + 64 * size_t(i);
+			auto f = [&](int k) { return bits2f(r[k]); };
+			auto put3 = [&](int k, V3 v) { o[k] = f2bits(v.x); o[k + 1] = f2bits(v.y); o[k + 2] = f2bits(v.z); };
+			for (int k = 0; k < 64; ++k) o[k] = 0u;
+			const float* pos = reinterpret_cast<const float*>(r + 32);
+			const PackedBsdf gb{ r[36], r[37], r[38], r[39] };
+			const u32 depth = r[op == 3 ? 25 : 17];
+			BptVertex lv;
+			lv.edf.color = V3(0.0f);
+			PathWeights lw; lw.pGp_sum = f(42); lw.pG = f(43);
+			lv.setup_stored(pos, r[40], r[41], gb, lw, depth, table);
+			if (op == 3)
+			{
+				BptVertex ev;
+				ev.geom.normal_s = V3(f(1), f(2), f(3)); ev.geom.normal_g = V3(f(4), f(5), f(6)); ev.geom.tangent = V3(f(7), f(8), f(9)); ev.geom.binormal = V3(f(10), f(11), f(12));
+				ev.geom.position = V3(f(13), f(14), f(15)); ev.in = V3(f(16), f(17), f(18)); ev.alpha = V3(f(19), f(20), f(21));
+				ev.prev_pG = f(22); ev.pGp_sum = f(23); ev.depth = r[24];
+				ev.bsdf.setup(mats[minu(r[0], params[0] - 1u)], table); ev.bsdf.particle_transport = false;
+				ConnectTerms t{}; t.out = V3(0.0f); t.f_s = V3(0.0f); t.f_L = V3(0.0f);
+				V3 dir, w; float d;
+				eval_connection(ev, lv, dir, w, d, (r[26] & 1u) != 0, (r[26] & 2u) != 0, (r[26] & 4u) != 0, &t);
+				put3(0, w); put3(3, t.out); o[6] = f2bits(t.d2); o[7] = f2bits(t.G); put3(8, t.f_s); o[11] = f2bits(t.p_s); put3(12, t.f_L); o[15] = f2bits(t.p_L);
+				o[16] = f2bits(t.pGp); o[17] = f2bits(t.prev_pGp); o[18] = f2bits(t.next_pGp); o[19] = f2bits(t.mis_w);
+			}
+			else
+			{
+				BPT b;
+				b.U = V3(f(3), f(4), f(5)); b.V = V3(f(6), f(7), f(8)); b.W = V3(f(9), f(10), f(11)); b.W_len = length(b.W); b.sq_focal = f(12);
+				b.light_tracing = f(15); b.n_light_paths = r[16];
+				b.options = BPTOptions{};
+				b.options.direct_lighting_nee = r[18] & 1u; b.options.direct_lighting_bsdf = (r[18] >> 1) & 1u;
+				b.options.indirect_lighting_nee = (r[18] >> 2) & 1u; b.options.indirect_lighting_bsdf = (r[18] >> 3) & 1u;
+				BPT::LensTerms t;
+				V4 w(0, 0, 0, 0); u32 pixel = 0; V3 origin(0.0f);
+				const bool want = b.lens_sample(pos, r[40], r[41], gb, f(42), f(43), depth, V3(f(0), f(1), f(2)), r[13], r[14], table, w, pixel, origin, &t);
+				put3(0, w.xyz()); put3(3, t.out); o[6] = f2bits(t.d2); o[7] = f2bits(t.G); o[8] = f2bits(t.f_s); o[9] = f2bits(t.ox); o[10] = f2bits(t.oy); o[11] = f2bits(t.p_s);
+				put3(12, t.f_L); o[15] = f2bits(t.p_L); o[16] = f2bits(t.pGp); o[17] = f2bits(t.cos_theta); o[18] = f2bits(t.next_pGp); o[19] = f2bits(t.mis_w);
+				o[52] = want ? 1u : 0u; o[53] = want ? pixel : 0u; o[54] = f2bits(1.0f / float(r[16]));
+				if (want) put3(48, origin);
+			}
+			put3(20, lv.geom.position); put3(23, lv.geom.normal_s); put3(26, lv.in); put3(29, lv.alpha); put3(32, lv.edf.color); o[35] = f2bits(lv.weights.pGp_sum); o[36] = f2bits(lv.weights.pG);
+			if (depth != 0u) { o[37] = f2bits(lv.bsdf.glossy.roughness); o[38] = f2bits(lv.bsdf.opacity); o[39] = f2bits(lv.bsdf.ior); }
+			put3(40, lv.geom.tangent); put3(43, lv.geom.binormal);
+		}
+	}
+	else if (op == 7)
+	{
+		const u32 n_paths = params[0], n_passes = params[1], instance = params[2];
+		const float* w = static_cast<const float*>(arrays[0]); const float* hits = static_cast<const float*>(arrays[1]); const u32* pixels = static_cast<const u32*>(arrays[2]);
+		long long* sums = static_cast<long long*>(arrays[5]);
+		float* comp = static_cast<float*>(arrays[6]); float* direct = static_cast<float*>(arrays[7]);
+		const size_t cells = size_t(n_paths) * n_passes * 3;
+		for (size_t c = 0; c < cells; ++c) sums[c] = 0;
+		for (u32 i = 0; i < n; ++i)
+		{
+			const V4 e(w[4 * size_t(i)], w[4 * size_t(i) + 1], w[4 * size_t(i) + 2], w[4 * size_t(i) + 3]);
+			if (!(e.x > 0.0f || e.y > 0.0f || e.z > 0.0f)) continue;          // light_tracing_pass queues only such entries
+			if (!(hits[4 * size_t(i)] < 0.0f)) continue;
+			const u32 k = n_passes == 1 ? 0u : pixels[i] / n_paths;
+			long long q[3];
+			splat_fixed3(e, 1.0f / float(instance + k + 1), q);
+			for (int c = 0; c < 3; ++c) splat_add(sums[size_t(pixels[i]) * 3 + c], q[c]);
+		}
+		for (size_t p = 0; p < size_t(n_paths) * n_passes; ++p)
+		{
+			const long long* q = sums + p * 3;
+			if (!(q[0] | q[1] | q[2])) continue;
+			for (int c = 0; c < 3; ++c) { comp[4 * p + c] += splat_to_float(q[c]); direct[4 * p + c] += splat_to_float(q[c]); }
+		}
+	}
+}
+
 // host threads used for the queue traces inside render_pass, and the wall time spent in them so far
 void orc_debug_set_box_clause(i32 on) { box_clause_enabled() = on != 0; }
 void orc_pt_log_rays(orc_pt* h, i32 on) { h->pt.log_rays = on != 0; if (on) { h->pt.logged_rays.clear(); h->pt.logged_hits.clear(); h->pt.logged_kind.clear(); } }
