@@ -162,7 +162,7 @@ ENTRY_POINTS = ["fpt_create", "fpt_destroy", "fpt_last_error", "fpt_stream", "fp
                 "fpt_bpt_allreduce_splats", "fpt_comm_selftest", "fpt_pt_last_union_ms", "fpt_pt_lane_count", "fpt_pt_set_lanes", "fpt_pt_set_deferred", "fpt_pt_flush", "fpt_pt_launch_list", "fpt_set_tile_lists", "fpt_gather_pack", "fpt_gather_unpack", "fpt_device_memory", "fpt_bytes_per_path_in_flight", "fpt_bpt_set_shared_light_vertices", "fpt_bpt_export_light_vertices", "fpt_bpt_import_light_vertices", "fpt_bpt_exchange_light_vertices", "fpt_bpt_finish",
                 "fpt_multiply_frame", "fpt_clamp_frame", "fpt_sequence_device_view", "fpt_mesh_lights_device_view", "fpt_mesh_invalidate", "fpt_rt_refit_geometry", "fpt_debug_refit_bvh",
                 "fpt_debug_build_emitter_tables", "fpt_clear_gbuffer", "fpt_rt_download_bvh", "fpt_mesh_lights_update", "fpt_rt_set_build_mode",
-                "fpt_debug_psf", "fpt_psfpt_debug_set_table_log2", "fpt_debug_bpt"]
+                "fpt_debug_psf", "fpt_psfpt_debug_set_table_log2", "fpt_debug_bpt", "fpt_debug_frame"]
 
 
 def kernel_source_hash():
@@ -875,6 +875,74 @@ class Renderer:
         torch.cuda.synchronize(self.dev)
         self._check(self.L.fpt_debug_bpt(self.ctx, C.c_int(op), C.c_uint32(n), par, C.c_uint32(len(params)), ptrs, C.c_uint32(len(devs))))
         return [None if a is None else d.cpu().numpy()[:a.nbytes].view(a.dtype).reshape(a.shape) for a, d in zip(hosts, devs)]
+
+    def debug_frame(self, op, frame, log=None, records=None, pixels=None, n=None, **par):
+        """fpt_debug_frame (layouts: include/fermat_pt_hip.h).  frame: (8, n_pixels, 4) float32; log: dict of the op's log arrays -- emissive (n_bounces * cap, 4),
+        nee0 / nee1 (n_bounces * cap * 2, 4), mask (cap * mask_words) uint32 and, for the merge, albedo_d / albedo_s (cap, 4) and blend (n_bounces * cap * 3, 4) or
+        None; records: (n, 16) uint32; pixels: uint32 list or None.  op "bracket": kind, value.  op "write": base_instance, n_passes, acc_stride, cap, mask_words,
+        n_bounces, fused_bounce, firefly[, n_slot].  op "merge": acc_stride, cap, mask_words, n_bounces, base_instance, n_passes, psf, firefly, clamp_max, p0.
+        Returns (frame, log) as the device left them.  Everything the kernels index with is checked against the arrays here, before the launch."""
+        torch = self.torch
+        f32 = lambda v: int(np.float32(v).view(np.uint32))  # noqa: E731
+        frame = np.ascontiguousarray(frame, np.float32)
+        assert frame.ndim == 3 and frame.shape[0] == 8 and frame.shape[2] == 4 and frame.shape[1] >= 1
+        n_pixels = frame.shape[1]
+        if pixels is not None:
+            pixels = np.ascontiguousarray(pixels, np.uint32).reshape(-1)
+            assert len(pixels) and int(pixels.max()) < n_pixels
+        log = dict(log or {})
+        names = {"bracket": (), "write": ("emissive", "nee0", "nee1", "mask"), "merge": ("albedo_d", "albedo_s", "emissive", "nee0", "nee1", "blend", "mask")}[op]
+        g = lambda k: par[k]  # noqa: E731
+        if op == "bracket":
+            n = (len(pixels) if pixels is not None else n_pixels) if n is None else int(n)
+            assert n <= (len(pixels) if pixels is not None else n_pixels) and g("kind") in (0, 1, 2)
+            params = [n_pixels, g("kind"), int(g("value")) if g("kind") == 1 else f32(g("value"))]
+            arrays = list(frame) + [pixels]
+            code = 0
+        else:
+            cap, words, nb, stride, n_passes = g("cap"), g("mask_words"), g("n_bounces"), g("acc_stride"), g("n_passes")
+            batch = n_passes > 1 or op == "merge"
+            want = dict(albedo_d=(cap, 4), albedo_s=(cap, 4), emissive=(nb * cap, 4), nee0=(nb * cap * 2, 4), nee1=(nb * cap * 2, 4), blend=(nb * cap * 3, 4), mask=(cap * words,))
+            for k in names:
+                a = log.get(k)
+                if a is None:
+                    assert (k == "blend" and not g("psf")) if op == "merge" else n_passes == 1
+                    continue
+                log[k] = a = np.ascontiguousarray(a, np.uint32 if k == "mask" else np.float32)
+                assert a.shape == want[k], (k, a.shape, want[k])
+            assert nb >= 1 and (not batch or (stride * n_passes <= cap and 32 * words >= (4 if op == "merge" and g("psf") else 3) * nb))
+            if op == "write":
+                records = np.ascontiguousarray(records, np.uint32).reshape(-1, 16)
+                n = len(records)
+                n_slot = par.get("n_slot", stride if pixels is None else len(pixels))
+                v = records[:, 0] & 0x7FFFFFF
+                assert g("fused_bounce") < nb and (records[:, 2] < nb).all() and (records[:, 3] <= 4).all() and (records[records[:, 3] == 3, 2] == g("fused_bounce")).all()
+                if n_passes == 1:
+                    assert (v < n_pixels).all() and len(np.unique(v)) == n, "one launch carries at most one sample per pixel"
+                else:
+                    assert n_slot <= stride and (v < n_slot).all() and (records[:, 1] < n_passes).all()
+                    assert len(np.unique(records[:, 1].astype(np.int64) * stride + v)) == n, "one launch carries at most one sample per path"
+                params = [n_pixels, g("base_instance"), n_passes, n_slot, stride, cap, words, nb, g("fused_bounce"), f32(g("firefly"))]
+                arrays = list(frame) + [log.get(k) for k in names] + [pixels, records]
+                code = 1
+            else:
+                p0 = g("p0")
+                n = int(n)
+                assert p0 + n <= stride and (pixels is not None or (p0 == 0 and n <= n_pixels)) and (pixels is None or p0 + n <= len(pixels))
+                params = [n_pixels, stride, cap, words, nb, g("base_instance"), n_passes, 1 if g("psf") else 0, f32(g("firefly")), f32(g("clamp_max")), p0]
+                arrays = list(frame) + [log.get(k) for k in names] + [pixels]
+                code = 2
+        devs = [None if a is None else torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy() if a.size else np.zeros(8, np.uint8)).to(self.dev) for a in arrays]
+        ptrs = (C.c_void_p * len(devs))(*[None if d is None else d.data_ptr() for d in devs])
+        prm = (C.c_uint32 * len(params))(*[int(x) for x in params])
+        torch.cuda.synchronize(self.dev)
+        self._check(self.L.fpt_debug_frame(self.ctx, C.c_int(code), C.c_uint32(n), prm, C.c_uint32(len(params)), ptrs, C.c_uint32(len(devs))))
+        down = lambda a, d: d.cpu().numpy()[:a.nbytes].view(a.dtype).reshape(a.shape)  # noqa: E731
+        out = np.stack([down(frame[c], devs[c]) for c in range(8)])
+        for i, k in enumerate(names):
+            if log.get(k) is not None:
+                log[k] = down(log[k], devs[8 + i])
+        return out, log
 
     def reinit_emitters(self, n_vpls):
         """fpt_mesh_lights_init again with another VPL count (the probe's emitter tables)"""

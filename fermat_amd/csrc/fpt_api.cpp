@@ -495,17 +495,22 @@ const float4* ensure_vpl_points(fpt_context* ctx, const fpt_rendering_context_vi
 	}
 	return ctx->d_vpl_points.ptr;
 }
-// the lane's view of the contribution log: every index is linear in the path index, so a lane's range is a pointer offset
+// a lane's view of a contribution log: every index is linear in the path index, so the range that starts at path `first` is a pointer offset (an absent array stays absent)
+static ContribLog log_from(ContribLog g, uint32_t first)
+{
+	if (g.emissive) g.emissive += first;
+	for (int kind = 0; kind < 2; ++kind) if (g.nee[kind]) g.nee[kind] += 2 * size_t(first);
+	if (g.blend) g.blend += 3 * size_t(first);
+	if (g.mask) g.mask += size_t(first) * g.mask_words;
+	return g;
+}
+// the lane's view of the context's log
 ContribLog lane_log(fpt_context* ctx, uint32_t first)
 {
 	ContribLog g;
 	g.cap = uint32_t(size_t(ctx->n_local) * ctx->max_batch); g.mask_words = ctx->log_mask_words; g.n_bounces = ctx->opt.max_path_length;
-	g.emissive = ctx->log_emissive.ptr + first;
-	g.nee[0] = ctx->log_nee[0].ptr ? ctx->log_nee[0].ptr + 2 * size_t(first) : nullptr;
-	g.nee[1] = ctx->log_nee[1].ptr + 2 * size_t(first);
-	g.blend = ctx->log_blend.ptr ? ctx->log_blend.ptr + 3 * size_t(first) : nullptr;
-	g.mask = ctx->log_mask.ptr + size_t(first) * g.mask_words;
-	return g;
+	g.emissive = ctx->log_emissive.ptr; g.nee[0] = ctx->log_nee[0].ptr; g.nee[1] = ctx->log_nee[1].ptr; g.blend = ctx->log_blend.ptr; g.mask = ctx->log_mask.ptr;
+	return log_from(g, first);
 }
 void sample_targets(fpt_context* ctx, const FrameBufferDev& real_fb, bool batched, uint32_t first, FrameBufferDev& fb, ContribLog& log)
 {
@@ -1093,6 +1098,79 @@ int fpt_debug_psf(fpt_context* ctx, int op, uint32_t flags, uint32_t n, const vo
 		// the accumulate op hands back the means of its cells as well, through the helper the blends use
 		if (op == 2 && d_out1) launch_debug_psf(3, size, psf, size, d_out0, nullptr, static_cast<float*>(d_out1), s);
 		FPT_HIP_CHECK(hipGetLastError()); FPT_HIP_CHECK(hipStreamSynchronize(s));
+	});
+}
+
+/* fpt_debug_frame (include/fermat_pt_hip.h): the probe of the frame path.  Every op goes through the launchers the renderers call; the lane offset of the merge is
+ * applied as render_passes_impl / lane_log apply it. */
+int fpt_debug_frame(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_params, uint32_t n_params, void* const* h_arrays, uint32_t n_arrays)
+{
+	return guarded(ctx, [&] {
+		static const uint32_t want_params[3] = { 3, 10, 11 }, want_arrays[3] = { 9, 14, 16 };
+		require(op >= 0 && op <= 2, "fpt_debug_frame: unknown op");
+		require(n_params == want_params[op] && n_arrays == want_arrays[op] && h_arrays && h_params, "fpt_debug_frame: wrong number of parameters or arrays for this op");
+		flush_deferred(ctx);
+		hipStream_t s = ctx->stream;
+		auto f32 = [&](uint32_t k) { float v; std::memcpy(&v, h_params + k, sizeof(v)); return v; };
+		FrameBufferDev fb; std::memset(&fb, 0, sizeof(fb));
+		for (int c = 0; c < FPT_FB_NUM_CHANNELS; ++c) { require(h_arrays[c] != nullptr, "fpt_debug_frame: null channel"); fb.ch[c] = static_cast<float4*>(h_arrays[c]); }
+		const uint32_t n_pixels = h_params[0];
+		require(n_pixels >= 1, "fpt_debug_frame: an empty frame");
+		if (op == 0)
+		{
+			const uint32_t* pixels = static_cast<const uint32_t*>(h_arrays[8]);
+			require(pixels ? true : n <= n_pixels, "fpt_debug_frame: bracket: more entries than pixels");
+			require(h_params[1] <= 2, "fpt_debug_frame: bracket: unknown kind");
+			if (n && h_params[1] == 0) launch_rescale(fb, pixels, n, f32(2), s);
+			if (n && h_params[1] == 1) launch_variance(fb, pixels, n, h_params[2], s);
+			if (n && h_params[1] == 2) launch_clamp_frame(fb, pixels, n, f32(2), s);
+		}
+		else if (op == 1)
+		{
+			FrameProbe W; std::memset(&W, 0, sizeof(W));
+			W.fb = fb; W.n_pixels = n_pixels; W.firefly = f32(9);
+			W.pass.base_instance = h_params[1]; W.pass.n_passes = h_params[2]; W.pass.n_slot = h_params[3]; W.pass.acc_stride = h_params[4];
+			W.pass.pixels = static_cast<const uint32_t*>(h_arrays[12]);
+			W.log.cap = h_params[5]; W.log.mask_words = h_params[6]; W.log.n_bounces = h_params[7];
+			W.log.emissive = static_cast<float4*>(h_arrays[8]); W.log.nee[0] = static_cast<float4*>(h_arrays[9]); W.log.nee[1] = static_cast<float4*>(h_arrays[10]);
+			W.log.mask = static_cast<uint32_t*>(h_arrays[11]);
+			require(W.pass.n_passes >= 1 && W.log.n_bounces >= 1 && h_params[8] < W.log.n_bounces, "fpt_debug_frame: write: n_passes, n_bounces or the block's bounce out of range");
+			if (W.pass.n_passes > 1)
+			{
+				for (uint32_t k = 8; k < 12; ++k) require(h_arrays[k] != nullptr, "fpt_debug_frame: write: null log array");
+				require(W.pass.n_slot <= W.pass.acc_stride && uint64_t(W.pass.acc_stride) * W.pass.n_passes <= W.log.cap && 32ull * W.log.mask_words >= 3ull * W.log.n_bounces,
+				        "fpt_debug_frame: write: the log is too small for the passes");
+			}
+			require(!n || h_arrays[13], "fpt_debug_frame: write: null records");
+			// the block the traversal kernel's retirement reads its targets from (FusedResolve): this launch's bounce, the mesh lights' kind
+			FusedResolve F; std::memset(&F, 0, sizeof(F));
+			F.fb = fb; F.pass = W.pass; F.bounce = h_params[8]; F.log = W.log; F.kind = 1u;
+			DeviceArray<FusedResolve> d_fused; d_fused.upload(&F, 1, s);
+			DeviceArray<float4> scratch; scratch.alloc(2 * size_t(n ? n : 1));
+			W.fused = d_fused.ptr; W.scratch_rays = scratch.ptr;
+			if (n) launch_debug_frame(n, static_cast<const uint32_t*>(h_arrays[13]), W, s);
+			FPT_HIP_CHECK(hipGetLastError());
+			FPT_HIP_CHECK(hipStreamSynchronize(s));          // the block and the scratch queue are released on return
+		}
+		else
+		{
+			const uint32_t acc_stride = h_params[1], n_passes = h_params[6], p0 = h_params[10];
+			const bool psf = h_params[7] != 0;
+			ContribLog g; std::memset(&g, 0, sizeof(g));
+			g.cap = h_params[2]; g.mask_words = h_params[3]; g.n_bounces = h_params[4];
+			for (uint32_t k = 8; k < 15; ++k) require(h_arrays[k] != nullptr || (k == 13 && !psf), "fpt_debug_frame: merge: null array");
+			const uint32_t* list = static_cast<const uint32_t*>(h_arrays[15]);
+			require(n_passes >= 1 && uint64_t(p0) + n <= acc_stride && uint64_t(acc_stride) * n_passes <= g.cap && (list || (p0 == 0 && n <= n_pixels)),
+			        "fpt_debug_frame: merge: the lane, the passes or the list do not fit the log and the frame");
+			require(32ull * g.mask_words >= (psf ? 4ull : 3ull) * g.n_bounces, "fpt_debug_frame: merge: too few mask words for the bounces");
+			g.emissive = static_cast<float4*>(h_arrays[10]); g.nee[0] = static_cast<float4*>(h_arrays[11]); g.nee[1] = static_cast<float4*>(h_arrays[12]);
+			g.blend = static_cast<float4*>(h_arrays[13]); g.mask = static_cast<uint32_t*>(h_arrays[14]);
+			g = log_from(g, p0);          // the offsets lane_log applies, by the function it applies them with
+			PassInfo pass; pass.base_instance = h_params[5]; pass.n_passes = n_passes; pass.n_slot = n; pass.acc_stride = acc_stride; pass.pixels = list ? list + p0 : nullptr;
+			if (n) launch_merge_passes_exact(fb, static_cast<float4*>(h_arrays[8]) + p0, static_cast<float4*>(h_arrays[9]) + p0, g, pass.pixels, n, pass, s, psf, f32(8), f32(9));
+		}
+		FPT_HIP_CHECK(hipGetLastError());
+		FPT_HIP_CHECK(hipStreamSynchronize(s));
 	});
 }
 

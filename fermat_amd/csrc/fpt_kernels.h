@@ -118,6 +118,9 @@ void launch_eaw(float4* dst, int op, const float4* w_img, float w_min, const flo
 void launch_unpack_normals(const float4* geo, float4* nrm, uint32_t n, hipStream_t s);
 void launch_filter_variance(const float4* img, float* var, uint32_t FW, uint32_t res_x, uint32_t res_y, hipStream_t s);
 void launch_rgba_mode(const FrameBufferDev& fb, uint32_t mode, uint32_t n, float exposure, float inv_gamma, uint32_t* rgba, hipStream_t s);
+// the frame probe's targets (fpt_debug_frame): what the writers of fpt_device.h / fpt_psf.h take, plus the bounds of the arrays behind them
+struct FrameProbe { FrameBufferDev fb; PassInfo pass; ContribLog log; const FusedResolve* fused; float4* scratch_rays; uint32_t n_pixels; float firefly; };
+void launch_debug_frame(uint32_t n, const uint32_t* rec, const FrameProbe& w, hipStream_t s);
 void launch_debug_math(int op, uint32_t n, const float* a, const float* b, float* o0, float* o1, hipStream_t s);
 
 } // namespace fpt

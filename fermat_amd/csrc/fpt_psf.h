@@ -31,6 +31,21 @@ __device__ __forceinline__ void psf_add(const PsfDev& psf, uint32_t slot, f3 v)
 __device__ __forceinline__ f3 psf_clamp(const PsfDev& psf, f3 v) { return all_finite(v) ? mk3(sel_min(v.x, psf.firefly), sel_min(v.y, psf.firefly), sel_min(v.z, psf.firefly)) : splat3(0.0f); }
 
 
+// The part of PSFPTVertexProcessor::accumulate_nee that reaches the FRAME, after the cache cell has had its share (src/psfpt_vertex_processor.h:434-467): nothing
+// when the whole sample went to the cell; otherwise straight to the frame (one pass per render()), or to the path's cell of the batch's log, which the
+// merge applies in order.  Shared by psf_resolve_sample and the frame probe (fpt_pt.hip debug_frame_kernel), which has no cache.
+__device__ __forceinline__ void psf_frame_share(const FrameBufferDev& fb, const PassInfo& ps, const ContribLog& log, uint32_t kind, uint32_t bounce, const PathSlot& sl, uint32_t comp,
+                                                bool cached, bool diffuse_only, f3 w_d, f3 w_g, float firefly)
+{
+	if (cached && !diffuse_only) return;
+	if (ps.n_passes == 1) { apply_psf_nee(FrameAdd{ fb, sl.pixel, sl.weight }, bounce, comp, cached, diffuse_only, w_d, w_g, firefly); return; }
+	const uint32_t pidx = sl.k * ps.acc_stride + sl.slot;
+	float4* cell = log.nee[kind] + (size_t(bounce) * log.cap + pidx) * 2;
+	cell[0] = make_float4(w_d.x, w_d.y, w_d.z, as_f32(comp | (cached ? 0x100u : 0u) | (diffuse_only ? 0x200u : 0u)));
+	cell[1] = make_float4(w_g.x, w_g.y, w_g.z, 0.0f);
+	log_mark(log, pidx, 3u * bounce + 1u + kind);
+}
+
 // PSFPTVertexProcessor::accumulate_nee for ONE unoccluded light sample (src/psfpt_vertex_processor.h:345-441): to the sample's cache
 // cell, to the frame, or to both
 // `base_instance` = the first pass of the launch (the blocks behind a fused launch do not change from call to call, so it travels separately)
@@ -45,14 +60,8 @@ __device__ __forceinline__ void psf_resolve_sample(const ResolveParams& P, uint3
 	const bool cached = ci_valid(vinfo), diffuse_only = ((vinfo >> 29) & 3u) == 1u;
 	// the cell's share: integer sums, order-independent
 	if (cached) psf_add(psf_pass_view(P.psf, sl.k), vinfo & 0x1FFFFFFFu, diffuse_only ? w_d : w_d + w_g);
-	if (cached && !diffuse_only) return;
-	// the frame's share: straight to the frame (one pass per render()), or to the path's cell of the batch's log, applied in order by the merge
-	if (ps.n_passes == 1) { apply_psf_nee(FrameAdd{ P.fb, sl.pixel, sl.weight }, P.bounce, comp, cached, diffuse_only, w_d, w_g, P.psf.firefly); return; }
-	const uint32_t pidx = sl.k * ps.acc_stride + sl.slot;
-	float4* cell = P.log.nee[P.kind] + (size_t(P.bounce) * P.log.cap + pidx) * 2;
-	cell[0] = make_float4(w_d.x, w_d.y, w_d.z, as_f32(comp | (cached ? 0x100u : 0u) | (diffuse_only ? 0x200u : 0u)));
-	cell[1] = make_float4(w_g.x, w_g.y, w_g.z, 0.0f);
-	log_mark(P.log, pidx, 3u * P.bounce + 1u + P.kind);
+	// the frame's share
+	psf_frame_share(P.fb, ps, P.log, P.kind, P.bounce, sl, comp, cached, diffuse_only, w_d, w_g, P.psf.firefly);
 }
 
 // the estimate a cell holds: each 2^-32 fixed-point sum back in float, over the cell's sample count.  The caller has seen cell[3] != 0 (an empty cell holds no estimate).

@@ -1061,6 +1061,43 @@ __global__ void debug_psf_kernel(int op, uint32_t n, PsfDev psf, uint32_t n_cell
 	}
 }
 
+// Frame probe (tests/test_frame_truth.py, judged by tests/frame_truth.py): the writers that bring a sample to the frame or to the contribution log, on records a test
+// chose.  One record of 16 words per thread: [0] PixelInfo (slot / pixel : 27 | comp : 4), [1] pass offset k, [2] bounce, [3] what, [4..6] w_d (what 0: the emission),
+// [7] flags (what 4: 1 cached, 2 diffuse_only, 4 mesh light instead of directional), [8..10] w_g.  what: 0 accumulate_emissive, 1 / 2 accumulate_nee of a directional /
+// mesh light, 3 the mesh light through the FusedResolve block as the traversal kernel's retirement does it -- accumulate_nee_fused with one pass, and with passes in
+// flight the cell by write_shadow_entry_logged and its bit by log_mark_fused, from the path index the queue entry carries -- 4 psf_frame_share.  The frame adds are plain
+// read-modify-write: a launch carries at most one sample per pixel, as a renderer's does.  A record that points outside the arrays -- the frame, the log's planes or the
+// pixel list of n_slot entries -- is skipped.
+__global__ void debug_frame_kernel(uint32_t n, const uint32_t* __restrict__ rec, FrameProbe W)
+{
+	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
+	if (i >= n) return;
+	const uint32_t* r = rec + 16 * size_t(i);
+	const uint32_t pixel_info = r[0], pass_k = r[1], bounce = r[2], what = r[3], flags = r[7];
+	const f3 a = mk3(as_f32(r[4]), as_f32(r[5]), as_f32(r[6])), b = mk3(as_f32(r[8]), as_f32(r[9]), as_f32(r[10]));
+	const uint32_t v = pixel_info & 0x7FFFFFFu;
+	if (bounce >= W.log.n_bounces) return;
+	if (W.pass.n_passes == 1) { if (v >= W.n_pixels) return; }
+	else if (pass_k >= W.pass.n_passes || v >= W.pass.acc_stride || (W.pass.pixels && v >= W.pass.n_slot) || uint64_t(pass_k) * W.pass.acc_stride + v >= W.log.cap) return;
+	const uint32_t k = W.pass.n_passes > 1 ? pass_k : 0u;
+	if (what == 0) accumulate_emissive(W.fb, W.pass, W.log, decode_slot(W.pass, pixel_info, k), pixel_info, bounce, a);
+	else if (what == 1 || what == 2) accumulate_nee(W.fb, W.pass, W.log, what - 1u, pixel_info, k, bounce, a, b);
+	else if (what == 3)
+	{
+		if (bounce != load_launch_constant(&W.fused->bounce)) return;
+		if (W.pass.n_passes == 1) accumulate_nee_fused(W.fused, W.pass.base_instance, pixel_info, make_float4(a.x, a.y, a.z, as_f32(0u)), make_float4(b.x, b.y, b.z, 0.0f));
+		else
+		{
+			ShadowQueue q; q.rays = W.scratch_rays; q.w_d = nullptr; q.w_g = nullptr; q.size = nullptr; q.vinfo = nullptr;
+			ShadowPayload pl; pl.org = splat3(0.0f); pl.dir = splat3(0.0f); pl.w_d = a; pl.w_g = b;
+			write_shadow_entry_logged(W.pass, W.log, bounce, 1u, q, i, pl, 0x2u, pixel_info, k);
+			log_mark_fused(W.fused, as_u32(q.rays[2 * size_t(i) + 1].w));
+		}
+	}
+	else if (what == 4)
+		psf_frame_share(W.fb, W.pass, W.log, (flags >> 2) & 1u, bounce, decode_slot(W.pass, pixel_info, k), (pixel_info >> 27) & 0xFu, (flags & 1u) != 0u, (flags & 2u) != 0u, a, b, W.firefly);
+}
+
 // ---- launchers ----------------------------------------------------------------------------------------------------------
 static inline uint32_t blocks_for(uint32_t n, uint32_t b) { return n ? (n + b - 1) / b : 1; }
 
@@ -1115,5 +1152,8 @@ void launch_debug_vertex(int op, uint32_t n, const fpt_rendering_context_view& v
 { hipLaunchKernelGGL(debug_vertex_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, op, n, view, mats, n_mats, textures, n_textures, em, shade_records, rec, rec_stride, out); }
 void launch_debug_psf(int op, uint32_t n, const PsfDev& psf, uint32_t n_cells, const void* in, void* out0, float* out1, hipStream_t s)
 { hipLaunchKernelGGL(debug_psf_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, op, n, psf, n_cells, in, out0, out1); }
+
+void launch_debug_frame(uint32_t n, const uint32_t* rec, const FrameProbe& w, hipStream_t s)
+{ hipLaunchKernelGGL(debug_frame_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, n, rec, w); }
 
 } // namespace fpt

@@ -530,6 +530,24 @@ int fpt_debug_psf(fpt_context* ctx, int op, uint32_t flags, uint32_t n, const vo
  *                pixel), the DIFFUSE_A and SPECULAR_A planes (float4 per virtual pixel), log values (float4 x cells x cap), log channels (# x cells x cap), log
  *                mask (# x cap x mask_words), splat sums (3 x int64 per virtual pixel), # pixel list (n_local) or NULL}: merge_exact_kernel, all arrays in place */
 int fpt_debug_bpt(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_params, uint32_t n_params, void* const* h_arrays, uint32_t n_arrays);
+/* Frame probe: the kernels and inline writers that bring the samples of `-pt` and `-psfpt` to the image -- the one-pass bracket and the contribution log of the
+ * passes in flight with its merge -- on arrays a test built, through the launchers and functions the renderers call.  h_params: HOST array of n_params words
+ * (floats hold their BITS); h_arrays: HOST array of n_arrays DEVICE pointers, all updated in place.  A frame is its eight channels in enum order, float4 per pixel.
+ *   0 bracket: n = entries (the pixel list's length, or n_pixels); params {n_pixels, kind, value}: kind 0 rescale_kernel (value = the scale), 1 variance_kernel
+ *              (value = n, the 1-based pass count), 2 clamp_frame_kernel (value = the maximum); arrays {the frame [0..7], # pixel list or NULL}
+ *   1 write:   n = records; params {n_pixels, base_instance, n_passes, n_slot, acc_stride, log cap, log mask_words, n_bounces, the bounce of the FusedResolve block,
+ *              firefly}; arrays {the frame [0..7], log emissive (float4 x n_bounces x cap), log nee of the directional lights and of the mesh lights (2 float4 x
+ *              n_bounces x cap each), log mask (# x cap x mask_words), # pixel list (n_slot) or NULL, the records}.  n_passes == 1: the samples are added to the frame
+ *              (read-modify-write: at most ONE record per pixel in a call); n_passes > 1: they fill their cells of the log, path index = k x acc_stride + slot.
+ *              A record is 16 words: [0] # PixelInfo (pixel, or slot with passes in flight : 27 | comp : 4), [1] # pass offset k, [2] # bounce, [3] # what, [4..6] w_d
+ *              (what 0: the emission), [7] # flags, [8..10] w_g.  what 0 accumulate_emissive, 1 accumulate_nee of a directional light, 2 of a mesh light, 3 the mesh
+ *              light through a FusedResolve block in device memory, as the traversal kernel retires it (accumulate_nee_fused; with passes in flight the shading
+ *              kernel's cell write and log_mark_fused), 4 the frame's share of PSFPTVertexProcessor::accumulate_nee (flags: 1 cached, 2 diffuse_only, 4 mesh light)
+ *   2 merge:   n = the lane's pixels; params {n_pixels, acc_stride, log cap, log mask_words, n_bounces, base_instance, n_passes, psf (0 / 1), firefly, clamp_max,
+ *              p0}; arrays {the frame [0..7], the DIFFUSE_A and SPECULAR_A planes (float4 x cap), log emissive, log nee x 2, log blend (3 float4 x n_bounces x cap;
+ *              may be NULL without psf), log mask, # pixel list or NULL}: merge_passes_exact_kernel<psf> over the lane that starts at path p0 -- planes, log and
+ *              list offset by p0 as a renderer's lanes are; p0 > 0 needs the list */
+int fpt_debug_frame(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_params, uint32_t n_params, void* const* h_arrays, uint32_t n_arrays);
 /* debug entry (tests of the cache under load): the cache of a context after fpt_psfpt_init and before its first render, fpt_psfpt_set_batch or
  * fpt_psfpt_set_sharded, re-allocated with 2^log2_size slots (8..24) and cleared.  A table that fills up refuses further keys: their vertices stay uncached. */
 int fpt_psfpt_debug_set_table_log2(fpt_context* ctx, uint32_t log2_size);
