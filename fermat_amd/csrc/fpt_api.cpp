@@ -303,16 +303,14 @@ int fpt_pt_init(fpt_context* ctx, const fpt_pt_options* opts, const fpt_renderin
 		ctx->d_pixels = d_pixels;
 		require(ctx->n_local > 0, "fpt_pt_init: empty pixel set");
 		// queue arena (alloc_queues, src/pathtracer_kernels.h:90-126): two path queues, one shadow queue per light kind
-		ctx->q_a.alloc(ctx->n_local); ctx->q_b.alloc(ctx->n_local);
-		ctx->q_shadow.alloc(ctx->n_local);
-		ctx->q_shadow_dir.alloc(view->dir_lights_count ? ctx->n_local : 1);
+		resize_wavefront(ctx, 1, view, false);
 		// sampler (PathTracer::init, src/renderers/pathtracer_impl.h:148-150)
 		build_shift_table(256, 6 * (opts->max_path_length + 1), h_samples_dir, ctx->crt_rand, ctx->h_shifts);
 		ctx->seq_dims = 6 * (opts->max_path_length + 1); ctx->seq_tile = 256;
 		ctx->d_shifts.upload(ctx->h_shifts.data(), ctx->h_shifts.size(), ctx->stream);
 		ctx->d_samples.alloc(ctx->h_shifts.size());
 		if (ctx->has_emitters && ctx->emitters.vpls.empty()) ctx->opt.nee_type = 0;     // :165-166
-		ctx->max_batch = 1; ctx->defer_max = 1;
+		ctx->defer_max = 1;
 		ctx->pt_ready = true;
 	});
 }
@@ -504,19 +502,26 @@ static ContribLog log_from(ContribLog g, uint32_t first)
 	if (g.mask) g.mask += size_t(first) * g.mask_words;
 	return g;
 }
+// ctx->store.resize for this context; the held blocks of the fused resolves, which name its buffers, are forgotten
+void resize_wavefront(fpt_context* ctx, uint32_t passes, const fpt_rendering_context_view* view, bool for_psfpt)
+{
+	ctx->store.resize(WavefrontStore::Shape{ ctx->n_local, passes, ctx->opt.max_path_length, view->dir_lights_count != 0, for_psfpt }, ctx->stream);
+	ctx->h_fused.clear(); ctx->psf.h_resolve.clear();
+	for (auto& X : ctx->extra_lanes) X->h_fused.clear();
+}
 // the lane's view of the context's log
 ContribLog lane_log(fpt_context* ctx, uint32_t first)
 {
-	ContribLog g;
-	g.cap = uint32_t(size_t(ctx->n_local) * ctx->max_batch); g.mask_words = ctx->log_mask_words; g.n_bounces = ctx->opt.max_path_length;
-	g.emissive = ctx->log_emissive.ptr; g.nee[0] = ctx->log_nee[0].ptr; g.nee[1] = ctx->log_nee[1].ptr; g.blend = ctx->log_blend.ptr; g.mask = ctx->log_mask.ptr;
+	ContribLog g; const WavefrontStore& w = ctx->store;
+	g.cap = uint32_t(w.shape.paths()); g.mask_words = w.shape.mask_words(); g.n_bounces = ctx->opt.max_path_length;
+	g.emissive = w.log_emissive.ptr; g.nee[0] = w.log_nee[0].ptr; g.nee[1] = w.log_nee[1].ptr; g.blend = w.log_blend.ptr; g.mask = w.log_mask.ptr;
 	return log_from(g, first);
 }
 void sample_targets(fpt_context* ctx, const FrameBufferDev& real_fb, bool batched, uint32_t first, FrameBufferDev& fb, ContribLog& log)
 {
 	fb = real_fb; std::memset(&log, 0, sizeof(log));
 	if (!batched) return;
-	fb = plane_view(real_fb, reinterpret_cast<float4*>(ctx->d_acc[FPT_FB_DIFFUSE_A].ptr) + first, reinterpret_cast<float4*>(ctx->d_acc[FPT_FB_SPECULAR_A].ptr) + first);
+	fb = plane_view(real_fb, ctx->store.albedo[0].ptr + first, ctx->store.albedo[1].ptr + first);
 	log = lane_log(ctx, first);
 }
 } // namespace fpt
@@ -534,7 +539,7 @@ static void render_lane(fpt_context* ctx, const LaneRefs& L, uint32_t instance, 
 		FrameBufferDev fb; ContribLog log;
 		sample_targets(ctx, real_fb, batched, L.first, fb, log);
 		const uint32_t n_paths = L.n * n_passes;
-		const size_t q_off = size_t(L.first) * ctx->max_batch;          // the lane's share of the queue arrays
+		const size_t q_off = size_t(L.first) * ctx->store.shape.passes;          // the lane's share of the queue arrays
 		// persistent traversal grid: no more blocks than the lane's queues can feed (closest-hit + shadow rays <= 2 per path)
 		const uint32_t trace_grid = std::min(ctx->trace_blocks(), std::max(1u, uint32_t((2ull * n_paths + 255ull) / 256ull)));
 		const bool sync_mode = ctx->profiling || ctx->capture_bounce >= 0;
@@ -546,8 +551,9 @@ static void render_lane(fpt_context* ctx, const LaneRefs& L, uint32_t instance, 
 
 		SequenceView seq; seq.shifts = ctx->d_shifts.ptr; seq.n_dims = ctx->seq_dims; seq.tile_size = ctx->seq_tile;
 		// path queue of bounce b counts in group b; shade_b fills the path queue of group b+1 and the shadow queues of group b
-		PathQueue qin = offset_queue(ctx->q_a.view(cnt.queue(0, CNT_PATH)), q_off), qout = offset_queue(ctx->q_b.view(cnt.queue(1, CNT_PATH)), q_off);
-		ShadowQueue qsd = offset_queue(ctx->q_shadow_dir.view(cnt.queue(0, CNT_SHADOW_DIR)), ctx->q_shadow_dir.entries > 1 ? q_off : 0), qs = offset_queue(ctx->q_shadow.view(cnt.queue(0, CNT_SHADOW)), q_off);
+		WavefrontStore& w = ctx->store;
+		PathQueue qin = offset_queue(w.q_a.view(cnt.queue(0, CNT_PATH)), q_off), qout = offset_queue(w.q_b.view(cnt.queue(1, CNT_PATH)), q_off);
+		ShadowQueue qsd = offset_queue(w.q_shadow_dir.view(cnt.queue(0, CNT_SHADOW_DIR)), w.shape.dir ? q_off : 0), qs = offset_queue(w.q_shadow.view(cnt.queue(0, CNT_SHADOW)), q_off);
 		// The ray-cone plane (PTRayQueue's cone radius + pdf, src/pathtracer_queues.h) is carried for whoever reads it: the path-space filter's hash (fpt_psf_api.cpp)
 		// and fpt_pt_set_capture.  The plain path tracer's vertices do not, and 8 B read + 8 B written per vertex are 4 % of a bandwidth-bound kernel's traffic.
 #ifndef FPT_KEEP_CONES
@@ -677,7 +683,8 @@ static void render_passes_impl(fpt_context* ctx, uint32_t instance, uint32_t n_p
 {
 	{
 		require(ctx->pt_ready, "fpt_pt_render: fpt_pt_init has not been called");
-		require(n_passes >= 1 && n_passes <= ctx->max_batch, "fpt_pt_render_batch: n_passes exceeds the batch capacity set by fpt_pt_set_batch");
+		require(ctx->store.serves(n_passes, false, view->dir_lights_count != 0),
+		        "fpt_pt_render_batch: n_passes exceeds the batch capacity set by fpt_pt_set_batch (or the view has directional lights and the storage was sized without them): call fpt_pt_set_batch with this view");
 		require(ctx->tree.valid, "fpt_pt_render: create_geometry has not been called");
 		require(ctx->has_emitters, "fpt_pt_render: fpt_mesh_lights_init has not been called");
 		hipStream_t s = ctx->stream;
@@ -714,7 +721,7 @@ static void render_passes_impl(fpt_context* ctx, uint32_t instance, uint32_t n_p
 			else
 			{
 				render_lane(ctx, L, instance, n_passes, true, view);
-				launch_merge_passes_exact(real_fb, reinterpret_cast<float4*>(ctx->d_acc[FPT_FB_DIFFUSE_A].ptr) + p0, reinterpret_cast<float4*>(ctx->d_acc[FPT_FB_SPECULAR_A].ptr) + p0,
+				launch_merge_passes_exact(real_fb, ctx->store.albedo[0].ptr + p0, ctx->store.albedo[1].ptr + p0,
 				                          lane_log(ctx, p0), L.pixels, L.n, pass, L.s);
 			}
 			if (j > 0) FPT_HIP_CHECK(hipEventRecord(ctx->extra_lanes[j - 1]->done, L.s));
@@ -760,6 +767,19 @@ void defer_pass(fpt_context* ctx, uint32_t kind, uint32_t instance, const fpt_re
 	ctx->defer_n++;
 	if (ctx->defer_n >= ctx->defer_max) flush_deferred(ctx);
 }
+// sizes the store for max_passes passes in flight (the PSFPT's has its extras and a fourth kind of log cell: its blends)
+void set_batch(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_context_view* view, bool for_psfpt)
+{
+	flush_deferred(ctx);
+	require(ctx->pt_ready, "fpt_pt_set_batch: fpt_pt_init has not been called");
+	require(max_passes >= 1, "fpt_pt_set_batch: max_passes must be >= 1");
+	require(uint64_t(ctx->n_local) * max_passes < (1ull << 32), "fpt_pt_set_batch: passes x (pixels rendered here) must stay below 2^32 paths in flight");
+	FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	for (auto& X : ctx->extra_lanes) FPT_HIP_CHECK(hipStreamSynchronize(X->stream));
+	resize_wavefront(ctx, max_passes, view, for_psfpt);
+	FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	if (ctx->defer_kind != DEFER_BPT && ctx->defer_max > max_passes) ctx->defer_max = max_passes;      // a smaller batch than the deferral was sized for
+}
 } // namespace fpt
 extern "C" {
 
@@ -778,7 +798,7 @@ int fpt_pt_set_deferred(fpt_context* ctx, uint32_t max_passes, const fpt_renderi
 	return guarded(ctx, [&] {
 		flush_deferred(ctx);
 		require(max_passes >= 1, "fpt_pt_set_deferred: max_passes must be >= 1");
-		if (max_passes > ctx->max_batch) require(fpt_internal_set_batch(ctx, max_passes, view, false) == 0, ctx->error.c_str());
+		if (max_passes > ctx->store.shape.passes) set_batch(ctx, max_passes, view, false);
 		ctx->defer_max = max_passes; ctx->defer_kind = DEFER_PT;
 	});
 }
@@ -786,42 +806,7 @@ int fpt_pt_flush(fpt_context* ctx) { return guarded(ctx, [&] { flush_deferred(ct
 int fpt_clear_gbuffer(fpt_context* ctx, const fpt_rendering_context_view* view)
 { return guarded(ctx, [&] { require(view != nullptr, "fpt_clear_gbuffer: null view"); clear_gbuffer(ctx, view); }); }
 
-// sizes the queues, the two albedo planes and the contribution log for max_passes passes in flight (the PSFPT's log has a fourth kind of cell: its blends)
-int fpt_internal_set_batch(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_context_view* view, bool for_psfpt)
-{
-	return guarded(ctx, [&] { flush_deferred(ctx);
-		require(ctx->pt_ready, "fpt_pt_set_batch: fpt_pt_init has not been called");
-		require(max_passes >= 1, "fpt_pt_set_batch: max_passes must be >= 1");
-		require(uint64_t(ctx->n_local) * max_passes < (1ull << 32), "fpt_pt_set_batch: passes x (pixels rendered here) must stay below 2^32 paths in flight");
-		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		for (auto& X : ctx->extra_lanes) FPT_HIP_CHECK(hipStreamSynchronize(X->stream));
-		const size_t n = size_t(ctx->n_local) * max_passes;
-		ctx->q_a.alloc(n); ctx->q_b.alloc(n); ctx->q_shadow.alloc(n);
-		ctx->q_shadow_dir.alloc(view->dir_lights_count ? n : 1);
-		const bool planes = max_passes > 1;
-		for (int c = 0; c < 6; ++c)
-		{
-			const bool want = planes && (c == FPT_FB_DIFFUSE_A || c == FPT_FB_SPECULAR_A);
-			ctx->d_acc[c].alloc(want ? n * 4 : 0);
-			if (ctx->d_acc[c].ptr) FPT_HIP_CHECK(hipMemsetAsync(ctx->d_acc[c].ptr, 0, ctx->d_acc[c].count * sizeof(float), ctx->stream));
-		}
-		// the contribution log: emission / directional / mesh cells per bounce (+ the PSFPT's blend cells), one fill bit per cell
-		const size_t L = ctx->opt.max_path_length;
-		ctx->log_mask_words = uint32_t(((for_psfpt ? 4 : 3) * L + 31) / 32);
-		ctx->log_emissive.alloc(planes ? n * L : 0);
-		ctx->log_nee[0].alloc(planes && view->dir_lights_count ? n * L * 2 : 0);
-		ctx->log_nee[1].alloc(planes ? n * L * 2 : 0);
-		ctx->log_blend.alloc(planes && for_psfpt ? n * L * 3 : 0);
-		ctx->log_mask.alloc(planes ? n * ctx->log_mask_words : 0);
-		if (ctx->log_mask.ptr) FPT_HIP_CHECK(hipMemsetAsync(ctx->log_mask.ptr, 0, ctx->log_mask.count * sizeof(uint32_t), ctx->stream));
-		ctx->h_fused.clear();                    // the resolve blocks name these buffers
-		for (auto& X : ctx->extra_lanes) X->h_fused.clear();
-		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		ctx->max_batch = max_passes;
-		if (ctx->defer_kind != DEFER_BPT && ctx->defer_max > max_passes) ctx->defer_max = max_passes;      // a smaller batch than the deferral was sized for
-	});
-}
-int fpt_pt_set_batch(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_context_view* view) { return fpt_internal_set_batch(ctx, max_passes, view, false); }
+int fpt_pt_set_batch(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_context_view* view) { return guarded(ctx, [&] { set_batch(ctx, max_passes, view, false); }); }
 int fpt_device_memory(fpt_context* ctx, uint64_t* free_bytes, uint64_t* total_bytes)
 {
 	return guarded(ctx, [&] {
@@ -835,20 +820,9 @@ int fpt_bytes_per_path_in_flight(fpt_context* ctx, uint32_t renderer, const fpt_
 {
 	return guarded(ctx, [&] {
 		require(view && bytes, "fpt_bytes_per_path_in_flight: null argument");
-		const uint64_t dir = view->dir_lights_count ? 1 : 0;
-		if (renderer == 2)
-		{
-			// fpt_bpt_set_batch: four ray/weight queues, the light-vertex store (64-B record + position per vertex), connection queue, albedo planes, 20-byte log cells
-			const uint64_t L = ctx->bpt.opt.max_path_length ? ctx->bpt.opt.max_path_length : 9, cells = ctx->bpt.opt.single_connection ? 2 : L + 1;
-			*bytes = 2 * 84 + 84 + 8 + L * 80 + 32 + L * cells * 20 + 8 * L + 16;
-			return;
-		}
-		const uint64_t L = ctx->opt.max_path_length ? ctx->opt.max_path_length : 9;
-		// two path queues (rays 32 incl. PixelInfo and pass offset, hit 16, weight 16, cone 8), the shadow queue(s) (ray 32 incl. PixelInfo, two weights 32 incl. pass offset),
-		// two albedo planes, the log: emission 16 + mesh-light 32 (+ directional 32) bytes per bounce, fill bits
-		uint64_t b = 2 * 72 + 64 * (1 + dir) + 32 + L * (48 + 32 * dir) + 4 * ((3 * L + 31) / 32);
-		if (renderer == 1) b += 2 * 4 + 2 * 4 + L * 48 + (L + 1) * 44 + 4;      // PSFPT: cache-info words, blend cells, the reference queue, (its pass tables are sized per pass, not per path)
-		*bytes = b;
+		// per path of a batch (two passes stand for any number in flight: the planes and the log exist from two on), before the renderer's init with the default path length
+		if (renderer == 2) { *bytes = bpt_bytes_per_path(ctx); return; }
+		*bytes = ctx->store.bytes_per_path(WavefrontStore::Shape{ 1, 2, ctx->opt.max_path_length ? ctx->opt.max_path_length : 9u, view->dir_lights_count != 0, renderer == 1 });
 	});
 }
 

@@ -47,7 +47,7 @@ void resolve_splats(fpt_context* ctx, const fpt_rendering_context_view* view)
 	const FrameBufferDev real = fb_dev(view->fb);
 	if (n_passes > 1)
 	{
-		launch_bpt_merge_exact(real, b.acc[FPT_FB_DIFFUSE_A].ptr, b.acc[FPT_FB_SPECULAR_A].ptr, log_view(b), b.splat_ptr(), b.d_pixels, b.n_local, b.n_paths, b.pending_first, n_passes,
+		launch_bpt_merge_exact(real, b.albedo[0].ptr, b.albedo[1].ptr, log_view(b), b.splat_ptr(), b.d_pixels, b.n_local, b.n_paths, b.pending_first, n_passes,
 		                       b.opt.max_path_length, ctx->stream);
 		// the sums of every pixel of the batch, this rank's or not (all-reduced sums cover the whole frame)
 		FPT_HIP_CHECK(hipMemsetAsync(b.splat_ptr(), 0, size_t(b.n_paths) * n_passes * 3 * sizeof(long long), ctx->stream));
@@ -63,40 +63,32 @@ void resolve_splats(fpt_context* ctx, const fpt_rendering_context_view* view)
 	FPT_HIP_CHECK(hipGetLastError());
 }
 
-// device storage for `passes` passes in flight
+// The list of the arrays sized by paths in flight: v(array, elements per eye / connection path rendered HERE, elements per light path or pixel of the FRAME); the
+// two differ under tile sharding.  `L`, `sc`: max_path_length, -sc 1; `batched`: the planes and the log exist for passes in flight only
+template <typename V> void each_array(fpt_context::BptState& b, size_t L, size_t sc, size_t batched, V&& v)
+{
+	for (int k = 0; k < 2; ++k) { v(b.q_rays[k], 2, 0); v(b.q_hits[k], 1, 0); v(b.q_weights[k], 1, 0); v(b.q_pw[k], 1, 0); v(b.q_pixels[k], 1, 0); v(b.q_chan[k], 1, 0); }
+	// an eye vertex connects to at most L light vertices; a light path splats at most L-1
+	v(b.s_rays, 2 * L, 0); v(b.s_hits, L, 0); v(b.s_weights, L, 0); v(b.s_pixels, L, 0); v(b.s_chan, L, 0); v(b.conn, 1, 0);
+	v(b.v_pos, 0, L); v(b.v_rec, 0, L); v(b.v_counts, 0, 1);
+	v(b.flat, 0, sc * L);                     // -sc 1: the flat vertex list, at most one entry per store slot
+	v(b.splat, 0, 3);
+	v(b.albedo[0], 0, batched); v(b.albedo[1], 0, batched);
+	// the eye paths' contribution log (BptLog, fpt_bpt.h): per bounce an emission cell + 1 (-sc 1) or L (-sc 0) connection cells, a fill bit per cell
+	const size_t cells = L * (1 + (sc ? 1 : L));
+	v(b.log_val, 0, batched * cells); v(b.log_chan, 0, batched * cells); v(b.log_mask, 0, batched * ((cells + 31) / 32));
+}
+
+// device storage for `passes` passes in flight; clears what the kernels expect zeroed
 void alloc_storage(fpt_context* ctx, uint32_t passes)
 {
 	fpt_context::BptState& b = ctx->bpt;
-	const uint32_t L = b.opt.max_path_length;
-	const size_t nl = size_t(b.n_local) * passes, np = size_t(b.n_paths) * passes;
-	for (int k = 0; k < 2; ++k)
-	{
-		b.q_rays[k].alloc(nl * 2); b.q_hits[k].alloc(nl); b.q_weights[k].alloc(nl); b.q_pw[k].alloc(nl); b.q_pixels[k].alloc(nl); b.q_chan[k].alloc(nl);
-	}
-	const size_t n_shadow = nl * L;           // an eye vertex connects to at most L light vertices; a light path splats at most L-1
-	b.s_rays.alloc(n_shadow * 2); b.s_hits.alloc(n_shadow); b.s_weights.alloc(n_shadow); b.s_pixels.alloc(n_shadow); b.s_chan.alloc(n_shadow); b.conn.alloc(nl);
-	const size_t nv = np * L;
-	b.v_pos.alloc(nv); b.v_rec.alloc(nv); b.v_counts.alloc(np);
-	if (b.opt.single_connection)
-	{
-		// the flat vertex list: at most one entry per store slot; per-block counts of the scan (4096 elements per block); per-pass bounds
-		b.flat.alloc(nv); b.flat_block_sums.alloc((nv + 4095) / 4096 + 1); b.flat_meta.alloc(2 * size_t(passes) + 2);
-	}
-	FPT_HIP_CHECK(hipMemsetAsync(b.v_counts.ptr, 0, np * sizeof(uint32_t), ctx->stream));
-	b.splat.alloc(np * 3);
-	FPT_HIP_CHECK(hipMemsetAsync(b.splat.ptr, 0, np * 3 * sizeof(long long), ctx->stream));
-	for (int c = 0; c < 6; ++c)
-	{
-		const bool want = passes > 1 && (c == FPT_FB_DIFFUSE_A || c == FPT_FB_SPECULAR_A);
-		b.acc[c].alloc(want ? np : 0);
-		if (want) FPT_HIP_CHECK(hipMemsetAsync(b.acc[c].ptr, 0, np * sizeof(float4), ctx->stream));
-	}
-	// the eye paths' contribution log (BptLog, fpt_bpt.h): per bounce an emission cell + 1 (-sc 1) or L (-sc 0) connection cells
-	{
-		const size_t cells = size_t(L) * (1u + (b.opt.single_connection ? 1u : L)), words = (cells + 31) / 32;
-		b.log_val.alloc(passes > 1 ? np * cells : 0); b.log_chan.alloc(passes > 1 ? np * cells : 0); b.log_mask.alloc(passes > 1 ? np * words : 0);
-		if (passes > 1) FPT_HIP_CHECK(hipMemsetAsync(b.log_mask.ptr, 0, np * words * sizeof(uint32_t), ctx->stream));
-	}
+	const size_t nl = size_t(b.n_local) * passes, np = size_t(b.n_paths) * passes, L = b.opt.max_path_length;
+	each_array(b, L, b.opt.single_connection ? 1 : 0, passes > 1, [&](auto& a, size_t per_local, size_t per_path) { a.alloc(per_local * nl + per_path * np); });
+	// -sc 1, not per path: per-block counts of the list's scan (4096 elements per block); per-pass bounds
+	if (b.opt.single_connection) { b.flat_block_sums.alloc((np * L + 4095) / 4096 + 1); b.flat_meta.alloc(2 * size_t(passes) + 2); }
+	auto zero = [&](auto& a) { if (a.ptr) FPT_HIP_CHECK(hipMemsetAsync(a.ptr, 0, a.count * sizeof(*a.ptr), ctx->stream)); };
+	zero(b.v_counts); zero(b.splat); zero(b.albedo[0]); zero(b.albedo[1]); zero(b.log_mask);
 	b.max_batch = passes;
 }
 
@@ -189,7 +181,7 @@ struct BptRun
 		P.emitters = emitter_view(ctx, b.opt.use_vpls);
 		const FrameBufferDev real_fb = fb_dev(view->fb);
 		// passes in flight: the terms of the albedo planes' channels go to the planes, every other term to the eye path's cell of the log
-		P.fb = batched ? plane_view(real_fb, b.acc[FPT_FB_DIFFUSE_A].ptr, b.acc[FPT_FB_SPECULAR_A].ptr) : real_fb;
+		P.fb = batched ? plane_view(real_fb, b.albedo[0].ptr, b.albedo[1].ptr) : real_fb;
 		if (batched) P.log = log_view(b);
 		P.opt = b.opt; P.pixels = b.d_pixels; P.n_local = b.n_local; P.n_paths = b.n_paths;
 		P.res_x = view->res_x; P.res_y = view->res_y; P.instance = instance;
@@ -369,6 +361,13 @@ int fpt_bpt_set_shared_light_vertices(fpt_context* ctx, int on)
 }
 } // extern "C"
 namespace fpt {
+uint64_t bpt_bytes_per_path(fpt_context* ctx)
+{
+	fpt_context::BptState& b = ctx->bpt;
+	uint64_t bytes = 0;          // before fpt_bpt_init: the default path length, -sc 0
+	each_array(b, b.opt.max_path_length ? b.opt.max_path_length : 9, b.opt.single_connection ? 1 : 0, 1, [&](auto& a, size_t per_local, size_t per_path) { bytes += (per_local + per_path) * sizeof(*a.ptr); });
+	return bytes;
+}
 uint32_t bpt_pack_own_vertices(fpt_context* ctx)
 {
 	fpt_context::BptState& b = ctx->bpt;

@@ -281,7 +281,7 @@ int fpt_psfpt_exchange_cells(fpt_context* ctx)
 		hipStream_t s = ctx->stream;
 		ps.ex_counts.alloc(std::max<size_t>(ps.ex_counts.count, size_t(W)));
 		FPT_HIP_CHECK(hipMemsetAsync(ps.ex_counts.ptr, 0, size_t(W) * sizeof(uint32_t), s));
-		FPT_HIP_CHECK(hipMemcpyAsync(ps.ex_counts.ptr + me, ps.touched_n.ptr, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+		FPT_HIP_CHECK(hipMemcpyAsync(ps.ex_counts.ptr + me, ps.shard.touched_n.ptr, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
 		if (W > 1) nccl_check(rccl().AllReduce(ps.ex_counts.ptr, ps.ex_counts.ptr, size_t(W), ncclUint32, ncclSum, comm, s), "ncclAllReduce");
 		std::vector<uint32_t> counts(size_t(W), 0u);
 		ps.ex_counts.download(counts.data(), size_t(W), s);

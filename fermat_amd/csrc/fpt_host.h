@@ -65,16 +65,12 @@ uint64_t emitter_fingerprint(const fpt_mesh_view& h_mesh, const fpt_texture* h_t
 struct QueueStorage
 {
 	DeviceArray<float4> rays, hits, weights; DeviceArray<uint32_t> vinfo; DeviceArray<float2> cones;
-	size_t entries = 0;
 	PathQueue view(uint32_t* size) { PathQueue q; q.rays = rays.ptr; q.hits = hits.ptr; q.weights = weights.ptr; q.cones = cones.ptr; q.size = size; q.vinfo = vinfo.count ? vinfo.ptr : nullptr; return q; }
-	void alloc(size_t n) { rays.alloc(2 * n); hits.alloc(n); weights.alloc(n); cones.alloc(n); entries = n; }
 };
 struct ShadowStorage
 {
 	DeviceArray<float4> rays, w_d, w_g, hits; DeviceArray<uint32_t> vinfo;
-	size_t entries = 0;
 	ShadowQueue view(uint32_t* size) { ShadowQueue q; q.rays = rays.ptr; q.w_d = w_d.ptr; q.w_g = w_g.ptr; q.size = size; q.vinfo = vinfo.count ? vinfo.ptr : nullptr; return q; }
-	void alloc(size_t n) { rays.alloc(2 * n); w_d.alloc(n); w_g.alloc(n); entries = n; }
 };
 
 // The per-pass counter block (uint32 words), one layout for the three renderers and the RT boundary's launches.  [CNT_TICKETS, CNT_QUEUES): one
@@ -131,6 +127,79 @@ struct AccelTree
 		info = std::move(built); valid = true;
 	}
 };
+
+// The device memory behind the PT's and the PSFPT's passes in flight -- the largest allocation of the library -- and its one owner:
+//   1. `shape` says what every array below is sized for, and resize() is the only code that allocates or clears them.  It re-allocates nothing whose size did not
+//      change (DeviceArray::alloc), zeroes the albedo planes and the log's fill bits on the given stream and does not synchronise: that is the caller's (resize_wavefront).
+//   2. Each array stands ONCE in each_array() with its elements per path in flight as a function of the shape (its element size is its type's).  resize() and
+//      bytes_per_path() both walk that list, so what fpt_bytes_per_path_in_flight reports is what is allocated.
+//   3. Whoever renders asks serves() first: the PT and the PSFPT share these arrays, and the last set-up call of either decides their shape.
+struct WavefrontStore
+{
+	struct Shape
+	{
+		uint32_t pixels = 0, passes = 0, max_path_length = 0;      // pixels rendered here, passes in flight, bounces a path can log
+		bool dir = false, psf = false;                           // the directional lights' queue and cells exist; the PSFPT's extras exist (cache-info words, shadow hit records, blend cells, reference queue)
+		size_t paths() const { return size_t(pixels) * passes; }
+		uint32_t mask_words() const { return uint32_t(((psf ? 4u : 3u) * max_path_length + 31u) / 32u); }      // one fill bit per cell: emission, two light kinds (+ the PSFPT's blend)
+	};
+	Shape shape;
+	QueueStorage q_a, q_b;
+	ShadowStorage q_shadow_dir, q_shadow;
+	DeviceArray<float4> albedo[2];                               // passes in flight: a plane per pass of the diffuse and the specular albedo
+	// the contribution log (fpt_device.h ContribLog): one cell per (pass in flight, pixel slot, bounce, kind) + the fill bits
+	DeviceArray<float4> log_emissive, log_nee[2], log_blend; DeviceArray<uint32_t> log_mask;
+	DeviceArray<uint32_t> ref_pixels, ref_cache, ref_k; DeviceArray<float4> ref_wd, ref_wg;      // the PSFPT's reference queue: <= 1 entry per path and bounce 0..L
+
+	// the list: v(array, elements per path in flight, elements it keeps when that is zero).  Planes and log exist for passes IN FLIGHT only (passes > 1); a
+	// view without directional lights keeps one entry of their queue, so that the kernels' parameters hold valid pointers
+	template <typename V> void each_array(const Shape& s, V&& v)
+	{
+		const size_t L = s.max_path_length, d = s.dir, x = s.psf, g = s.passes > 1;
+		for (QueueStorage* q : { &q_a, &q_b }) { v(q->rays, 2, 0); v(q->hits, 1, 0); v(q->weights, 1, 0); v(q->cones, 1, 0); v(q->vinfo, x, 0); }
+		v(q_shadow.rays, 2, 0); v(q_shadow.w_d, 1, 0); v(q_shadow.w_g, 1, 0); v(q_shadow.vinfo, x, 0); v(q_shadow.hits, x, 0);
+		v(q_shadow_dir.rays, 2 * d, 2); v(q_shadow_dir.w_d, d, 1); v(q_shadow_dir.w_g, d, 1); v(q_shadow_dir.vinfo, x * d, x); v(q_shadow_dir.hits, x * d, x);
+		v(albedo[0], g, 0); v(albedo[1], g, 0);
+		v(log_emissive, g * L, 0); v(log_nee[0], g * d * 2 * L, 0); v(log_nee[1], g * 2 * L, 0); v(log_blend, g * x * 3 * L, 0); v(log_mask, g * s.mask_words(), 0);
+		v(ref_pixels, x * (L + 1), 0); v(ref_cache, x * (L + 1), 0); v(ref_k, x * (L + 1), 0); v(ref_wd, x * (L + 1), 0); v(ref_wg, x * (L + 1), 0);
+	}
+	void resize(const Shape& s, hipStream_t stream)
+	{
+		shape = Shape{};                                         // a throw on the way (out of memory) leaves a store that serves nobody
+		each_array(s, [&](auto& a, size_t per_path, size_t floor) { a.alloc(per_path ? per_path * s.paths() : floor); });
+		for (DeviceArray<float4>& a : albedo) if (a.ptr) FPT_HIP_CHECK(hipMemsetAsync(a.ptr, 0, a.count * sizeof(float4), stream));
+		if (log_mask.ptr) FPT_HIP_CHECK(hipMemsetAsync(log_mask.ptr, 0, log_mask.count * sizeof(uint32_t), stream));
+		shape = s;
+	}
+	uint64_t bytes_per_path(const Shape& s)
+	{
+		uint64_t b = 0;
+		each_array(s, [&](auto& a, size_t per_path, size_t) { b += per_path * sizeof(*a.ptr); });
+		return b;
+	}
+	// is a render of `passes` passes, by the PSFPT or the PT, of a view with or without directional lights covered by what the arrays are sized for?
+	bool serves(uint32_t passes, bool psf, bool dir) const { return passes >= 1 && passes <= shape.passes && (shape.psf || !psf) && (shape.dir || !dir); }
+};
+
+// a table of the path-space filter's cache (fpt_kernels.h PsfDev): `tables` tables of 2^log2 slots each, side by side.  `listed`: pass tables, whose
+// live slots are listed in `touched` (as long as the tables) and counted in `touched_n` (one word per table)
+struct PsfTable
+{
+	DeviceArray<unsigned long long> keys; DeviceArray<long long> cells; uint32_t log2 = 0;
+	DeviceArray<uint32_t> touched, touched_n;
+	void alloc(uint32_t log2_size, size_t tables = 1, bool listed = false)
+	{
+		const size_t slots = (size_t(1) << log2_size) * tables;
+		log2 = log2_size; keys.alloc(slots); cells.alloc(slots * 4);
+		touched.alloc(listed ? slots : 0); touched_n.alloc(listed ? (tables > 32 ? tables : 32) : 0);
+	}
+	void clear(hipStream_t s)
+	{
+		FPT_HIP_CHECK(hipMemsetAsync(keys.ptr, 0xFF, keys.count * sizeof(unsigned long long), s));
+		FPT_HIP_CHECK(hipMemsetAsync(cells.ptr, 0, cells.count * sizeof(long long), s));
+		if (touched_n.ptr) FPT_HIP_CHECK(hipMemsetAsync(touched_n.ptr, 0, touched_n.count * sizeof(uint32_t), s));
+	}
+};
 } // namespace fpt
 
 struct fpt_context
@@ -169,9 +238,7 @@ struct fpt_context
 	const uint32_t* d_pixels = nullptr;
 	fpt::DeviceArray<fpt::FusedResolve> d_fused;        // per-(bounce, light kind) blocks read by the fused any-hit launches
 	std::vector<fpt::FusedResolve> h_fused;             // what d_fused holds (re-uploaded only when it changes)
-	fpt::QueueStorage q_a, q_b;
-	fpt::ShadowStorage q_shadow_dir, q_shadow;
-	uint32_t max_batch = 1;                              // passes in flight per fpt_pt_render_batch call
+	fpt::WavefrontStore store;                           // queues, albedo planes, contribution log, reference queue: everything sized by paths in flight
 	// deferred fpt_pt_render (fpt_pt_set_deferred): consecutive render(instance) calls are collected and rendered as one batch -- bit-identical to
 	// rendering them one by one -- when defer_max of them are pending or when anything is about to look at the frame (fpt_pt_flush, fpt_synchronize, ...)
 	uint32_t defer_max = 1, defer_first = 0, defer_n = 0;
@@ -193,33 +260,24 @@ struct fpt_context
 	fpt::DeviceArray<uint32_t> d_identity;               // 0 .. n-1: the pixel list the lanes index when the caller passed none
 	hipEvent_t lane_start = nullptr;
 	fpt::DeviceArray<float4> filter_tmp[2], filter_nrm; fpt::DeviceArray<float> filter_var;     // fpt_filter scratch (ping-pong images, variance)
-	fpt::DeviceArray<float> d_acc[6];                    // passes in flight: per-pass accumulation planes, float4 x n_local x max_batch per channel (the two albedo channels)
-	// the path tracer's contribution log (fpt_device.h ContribLog): one cell per (pass in flight, pixel slot, bounce, kind) + the fill bits
-	fpt::DeviceArray<float4> log_emissive, log_nee[2], log_blend; fpt::DeviceArray<uint32_t> log_mask;      // log_blend: the PSFPT's fourth kind
-	uint32_t log_mask_words = 1;
-	// path-space filtering (PSFPT): hash table of cache cells + reference queue
+	// path-space filtering (PSFPT): hash table of cache cells (its reference queue is the store's)
 	struct PsfState
 	{
 		bool ready = false, rendered = false;       // rendered: a pass has run (fpt_psfpt_debug_set_table_log2 re-sizes the table only before)
 		fpt_psf_options opt{};
-		uint32_t log2_size = 0;
-		fpt::DeviceArray<unsigned long long> keys; fpt::DeviceArray<long long> cells;
-		fpt::DeviceArray<uint32_t> ref_pixels, ref_cache, ref_size, ref_k; fpt::DeviceArray<float4> ref_wd, ref_wg;
+		fpt::PsfTable table;                        // the global table
+		fpt::DeviceArray<uint32_t> ref_size;        // the reference queue's fill, one word per bounce
 		float bbox[6] = { 0, 0, 0, 0, 0, 0 };
 		fpt::DeviceArray<fpt::ResolveParams> d_resolve;     // per-bounce blocks read by the MIXED launches with the fused cache-aware resolve
 		std::vector<fpt::ResolveParams> h_resolve;
-		// tile sharding (fpt_psfpt_set_sharded): the pass table, the list of its live slots, this rank's records of the pass in flight and the
+		// tile sharding (fpt_psfpt_set_sharded): the pass table with the list of its live slots, this rank's records of the pass in flight and the
 		// receive buffer of the exchange; `pending` = a pass has been rendered and waits for fpt_psfpt_finish
 		bool sharded = false, pending = false;
 		uint32_t pending_instance = 0, pending_bounces = 0;
-		fpt::DeviceArray<unsigned long long> p_keys; fpt::DeviceArray<long long> p_cells;
-		fpt::DeviceArray<uint32_t> touched, touched_n;
+		fpt::PsfTable shard;
 		fpt::DeviceArray<fpt::PsfRecord> records, recv;
 		fpt::DeviceArray<uint32_t> ex_counts;
-		// passes in flight (fpt_psfpt_set_batch): one pass table of 2^b_log2 slots per pass of the batch and the lists of their live slots
-		uint32_t max_batch = 1, b_log2 = 0;
-		fpt::DeviceArray<unsigned long long> b_keys; fpt::DeviceArray<long long> b_cells;
-		fpt::DeviceArray<uint32_t> b_touched, b_touched_n;
+		fpt::PsfTable batch;                        // passes in flight (fpt_psfpt_set_batch): one pass table per pass of the batch, with the lists of their live slots
 	} psf;
 	// bidirectional path tracer
 	struct BptState
@@ -236,10 +294,10 @@ struct fpt_context
 		fpt::DeviceArray<uint32_t> v_counts;
 		fpt::DeviceArray<uint32_t> flat, flat_meta, flat_block_sums;      // -sc 1: the flat light-vertex list (fpt_bpt.h)
 		fpt::DeviceArray<long long> splat; long long* splat_external = nullptr;
-		// passes in flight (fpt_bpt_set_batch / fpt_bpt_render_batch): everything above is sized for max_batch passes; acc = the per-pass
+		// passes in flight (fpt_bpt_set_batch / fpt_bpt_render_batch): everything above is sized for max_batch passes; albedo = the per-pass
 		// accumulation planes; pending_* = a batch whose light-tracing splats still wait for fpt_bpt_resolve_splats (deferred mode)
 		uint32_t max_batch = 1;
-		fpt::DeviceArray<float4> acc[6];                     // the albedo channels' per-pass planes
+		fpt::DeviceArray<float4> albedo[2];                  // the diffuse and the specular albedo's per-pass planes
 		fpt::DeviceArray<float4> log_val; fpt::DeviceArray<uint32_t> log_chan, log_mask;      // the eye paths' contribution log (fpt_bpt.h BptLog)
 		uint32_t pending_first = 0, pending_n = 0;
 		long long* splat_ptr() { return splat_external ? splat_external : splat.ptr; }
@@ -302,8 +360,12 @@ namespace fpt { void sample_targets(fpt_context* ctx, const FrameBufferDev& real
 // BPT, shared light vertices (fpt_bpt_api.cpp): this rank's vertices of the batch in flight -> ctx->bpt.lv_send (returns their number); wire records -> the store
 namespace fpt { uint32_t bpt_pack_own_vertices(fpt_context* ctx); void bpt_import_vertices(fpt_context* ctx, const LightVertexWire* d_records, uint32_t count); }
 
-// shared by fpt_pt_set_batch and fpt_psfpt_set_batch (fpt_api.cpp): not part of the public boundary
-extern "C" int fpt_internal_set_batch(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_context_view* view, bool for_psfpt);
+// fpt_api.cpp, called inside the caller's `guarded`.  resize_wavefront: ctx->store.resize, and the held blocks of the fused resolves, which name its buffers, are
+// forgotten.  set_batch: fpt_pt_set_batch's body, the shared part of fpt_psfpt_set_batch's
+namespace fpt { void resize_wavefront(fpt_context* ctx, uint32_t passes, const fpt_rendering_context_view* view, bool for_psfpt);
+                void set_batch(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_context_view* view, bool for_psfpt); }
+// fpt_bpt_api.cpp: what fpt_bpt_set_batch allocates per path in flight, with every pixel rendered here
+namespace fpt { uint64_t bpt_bytes_per_path(fpt_context* ctx); }
 
 // ---- helpers shared by the C-ABI translation units (fpt_api.cpp, fpt_bpt_api.cpp) -------------------------------------------------
 template <typename F>

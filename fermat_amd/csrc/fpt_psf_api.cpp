@@ -9,14 +9,18 @@
 using namespace fpt;
 
 namespace {
-// the cache as the kernels of a SHARDED context see it: pass table in keys / cells, global table in g_keys / g_cells
-PsfDev sharded_view(fpt_context* ctx)
+// the cache as the kernels see it.  PLAIN: the one table in keys / cells.  SHARDED: the pass table there, the global table in g_keys / g_cells.  BATCHED: one
+// pass table per pass of the batch there (pass_stride apart), the global table in g_keys / g_cells.  bbox_* and instance are the render's to add
+enum PsfMode { PSF_PLAIN, PSF_SHARDED, PSF_BATCHED };
+PsfDev psf_dev(fpt_context* ctx, PsfMode mode)
 {
-	fpt_context::PsfState& ps = ctx->psf;
+	fpt_context::PsfState& ps = ctx->psf; WavefrontStore& w = ctx->store;
 	PsfDev psf; std::memset(&psf, 0, sizeof(psf));
-	psf.keys = ps.p_keys.ptr; psf.cells = ps.p_cells.ptr; psf.log2_size = ps.log2_size;
-	psf.g_keys = ps.keys.ptr; psf.g_cells = ps.cells.ptr; psf.touched = ps.touched.ptr; psf.touched_n = ps.touched_n.ptr; psf.g_log2_size = ps.log2_size;
-	psf.ref_pixels = ps.ref_pixels.ptr; psf.ref_cache = ps.ref_cache.ptr; psf.ref_wd = ps.ref_wd.ptr; psf.ref_wg = ps.ref_wg.ptr; psf.ref_size = ps.ref_size.ptr; psf.ref_k = ps.ref_k.ptr;
+	const PsfTable& t = mode == PSF_BATCHED ? ps.batch : mode == PSF_SHARDED ? ps.shard : ps.table;
+	psf.keys = t.keys.ptr; psf.cells = t.cells.ptr; psf.log2_size = mode == PSF_BATCHED ? t.log2 : ps.table.log2; psf.g_log2_size = ps.table.log2;
+	if (mode != PSF_PLAIN) { psf.g_keys = ps.table.keys.ptr; psf.g_cells = ps.table.cells.ptr; psf.touched = t.touched.ptr; psf.touched_n = t.touched_n.ptr; }
+	if (mode == PSF_BATCHED) psf.pass_stride = 1u << t.log2;
+	psf.ref_pixels = w.ref_pixels.ptr; psf.ref_cache = w.ref_cache.ptr; psf.ref_wd = w.ref_wd.ptr; psf.ref_wg = w.ref_wg.ptr; psf.ref_size = ps.ref_size.ptr; psf.ref_k = w.ref_k.ptr;
 	psf.depth = ps.opt.psf_depth; psf.width = ps.opt.psf_width; psf.max_prob = ps.opt.psf_max_prob; psf.firefly = ps.opt.firefly_filter;
 	return psf;
 }
@@ -54,22 +58,14 @@ int fpt_psfpt_init(fpt_context* ctx, const fpt_pt_options* opts, const fpt_psf_o
 		require(psf->psf_temporal_reuse >= 1, "fpt_psfpt_init: psf_temporal_reuse must be >= 1");
 		fpt_context::PsfState& s = ctx->psf;
 		s.opt = *psf;
-		const uint32_t n = ctx->n_local;
-		// per-path vertex info and per-shadow-sample hit records
-		ctx->q_a.vinfo.alloc(n); ctx->q_b.vinfo.alloc(n);
-		ctx->q_shadow.vinfo.alloc(n); ctx->q_shadow.hits.alloc(n);
-		ctx->q_shadow_dir.vinfo.alloc(view->dir_lights_count ? n : 1); ctx->q_shadow_dir.hits.alloc(view->dir_lights_count ? n : 1);
+		// the store's extras: per-path vertex info, per-shadow-sample hit records and the reference queue.  PSFRefQueue: n_pixels * (L + 1) entries as in the
+		// reference (:176-181).  A path can open a new cache vertex after every glossy bounce, i.e. own several references; they are kept per bounce (<= 1 per
+		// path and bounce) and blended bounce by bounce, which makes the per-pixel order of the blend the order of creation without any atomics
+		resize_wavefront(ctx, 1, view, true);
 		// cache: the reference allocates 64M cells (HASH_SIZE, src/renderers/psfpt_impl.h:46); a cell is addressed by key, so the table size only
 		// has to exceed the number of live cells: 2^26 for frames beyond a megapixel, 2^24 below
-		s.log2_size = uint64_t(view->res_x) * view->res_y > (1u << 20) ? 26u : 24u;
-		s.keys.alloc(size_t(1) << s.log2_size); s.cells.alloc((size_t(1) << s.log2_size) * 4);
-		FPT_HIP_CHECK(hipMemsetAsync(s.keys.ptr, 0xFF, (size_t(1) << s.log2_size) * sizeof(unsigned long long), ctx->stream));
-		FPT_HIP_CHECK(hipMemsetAsync(s.cells.ptr, 0, (size_t(1) << s.log2_size) * 4 * sizeof(long long), ctx->stream));
-		// PSFRefQueue: n_pixels * (L + 1) entries as in the reference (:176-181).  A path can open a new cache vertex after every glossy bounce,
-		// i.e. own several references; they are kept per bounce (<= 1 per path and bounce) and blended bounce by bounce, which makes the
-		// per-pixel order of the blend the order of creation without any atomics
-		const size_t nr = size_t(n) * (opts->max_path_length + 1);
-		s.ref_pixels.alloc(nr); s.ref_k.alloc(nr); s.ref_cache.alloc(nr); s.ref_wd.alloc(nr); s.ref_wg.alloc(nr); s.ref_size.alloc(32);
+		s.table.alloc(uint64_t(view->res_x) * view->res_y > (1u << 20) ? 26u : 24u); s.table.clear(ctx->stream);
+		s.ref_size.alloc(32);
 		// m_bbox = renderer.compute_bbox(): over the mesh vertices (src/renderer.cu:1086-1097)
 		std::vector<float> vtx(size_t(view->mesh.num_vertices) * 4);
 		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -90,13 +86,10 @@ int fpt_psfpt_debug_set_table_log2(fpt_context* ctx, uint32_t log2_size)
 	return guarded(ctx, [&] {
 		fpt_context::PsfState& s = ctx->psf;
 		require(s.ready, "fpt_psfpt_debug_set_table_log2: fpt_psfpt_init has not been called");
-		require(!s.rendered && !s.sharded && s.max_batch <= 1, "fpt_psfpt_debug_set_table_log2: call it before the first render, fpt_psfpt_set_batch and fpt_psfpt_set_sharded");
+		require(!s.rendered && !s.sharded && ctx->store.shape.passes <= 1, "fpt_psfpt_debug_set_table_log2: call it before the first render, fpt_psfpt_set_batch and fpt_psfpt_set_sharded");
 		require(log2_size >= 8 && log2_size <= 24, "fpt_psfpt_debug_set_table_log2: log2_size must be 8..24");
 		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		s.log2_size = log2_size;
-		s.keys.alloc(size_t(1) << s.log2_size); s.cells.alloc((size_t(1) << s.log2_size) * 4);
-		FPT_HIP_CHECK(hipMemsetAsync(s.keys.ptr, 0xFF, (size_t(1) << s.log2_size) * sizeof(unsigned long long), ctx->stream));
-		FPT_HIP_CHECK(hipMemsetAsync(s.cells.ptr, 0, (size_t(1) << s.log2_size) * 4 * sizeof(long long), ctx->stream));
+		s.table.alloc(log2_size); s.table.clear(ctx->stream);
 		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 	});
 }
@@ -107,11 +100,11 @@ int fpt_psfpt_download_cells(fpt_context* ctx, uint64_t* h_keys, uint64_t* h_cou
 		flush_deferred(ctx);
 		fpt_context::PsfState& s = ctx->psf;
 		require(s.ready, "fpt_psfpt_download_cells: fpt_psfpt_init has not been called");
-		const size_t n = size_t(1) << s.log2_size;
+		const size_t n = size_t(1) << s.table.log2;
 		std::vector<unsigned long long> keys(n); std::vector<long long> cells(n * 4);
 		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		FPT_HIP_CHECK(hipMemcpy(keys.data(), s.keys.ptr, n * 8, hipMemcpyDeviceToHost));
-		FPT_HIP_CHECK(hipMemcpy(cells.data(), s.cells.ptr, n * 32, hipMemcpyDeviceToHost));
+		FPT_HIP_CHECK(hipMemcpy(keys.data(), s.table.keys.ptr, n * 8, hipMemcpyDeviceToHost));
+		FPT_HIP_CHECK(hipMemcpy(cells.data(), s.table.cells.ptr, n * 32, hipMemcpyDeviceToHost));
 		uint32_t k = 0;
 		for (size_t i = 0; i < n; ++i)
 		{
@@ -135,12 +128,13 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 		require(ctx->tree.valid && ctx->has_emitters, "fpt_psfpt_render: geometry / mesh lights are not initialised");
 		ps.rendered = true;
 		const bool batched = n_passes > 1;
-		require(!batched || (n_passes <= ps.max_batch && !ps.sharded), "fpt_psfpt_render_batch: more passes than fpt_psfpt_set_batch sized the storage for (or a sharded context)");
-		// the queues and the log are shared with the plain path tracer: a later fpt_pt_set_batch / fpt_pt_set_deferred may have re-shaped them (no blend cells, fewer
-		// mask bits, smaller queues), and a view with directional lights needs their log cells
-		require(!batched || (n_passes <= ctx->max_batch && ctx->log_blend.ptr != nullptr && ctx->log_mask_words == uint32_t((4 * size_t(ctx->opt.max_path_length) + 31) / 32)),
-		        "fpt_psfpt_render_batch: the shared queues / contribution log were re-sized by fpt_pt_set_batch since fpt_psfpt_set_batch: call fpt_psfpt_set_batch again");
-		require(!batched || !view->dir_lights_count || ctx->log_nee[0].ptr != nullptr, "fpt_psfpt_render_batch: the view has directional lights but the log was sized without them: call fpt_psfpt_set_batch with this view");
+		require(!batched || !ps.sharded, "fpt_psfpt_render_batch: a sharded context renders one pass at a time");
+		// the store is shared with the plain path tracer: a later fpt_pt_init / fpt_pt_set_batch / fpt_pt_set_deferred re-shapes it without the PSFPT's extras, and a
+		// view with directional lights needs their queue and log cells
+		WavefrontStore& w = ctx->store;
+		require(w.serves(n_passes, true, view->dir_lights_count != 0),
+		        "fpt_psfpt_render_batch: more passes than fpt_psfpt_set_batch sized the storage for, the storage was re-shaped by fpt_pt_set_batch since, or the view has "
+		        "directional lights and it was sized without them: call fpt_psfpt_set_batch with this view");
 		hipStream_t s = ctx->stream;
 		const fpt_pt_options& opt = ctx->opt;
 		const FrameBufferDev real_fb = fb_dev(view->fb);
@@ -150,10 +144,7 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 		if (!batched) launch_rescale(fb, ctx->d_pixels, n, float(instance) / float(instance + 1), s);
 		FPT_HIP_CHECK(hipMemsetAsync(ctx->d_counters.ptr, 0, CNT_TOTAL * sizeof(uint32_t), s));
 		PassCounters cnt{ ctx->d_counters.ptr };
-		auto reset_cache = [&] {          // initialize the shading cache (src/renderers/psfpt_impl.h:385-387)
-			FPT_HIP_CHECK(hipMemsetAsync(ps.keys.ptr, 0xFF, (size_t(1) << ps.log2_size) * sizeof(unsigned long long), s));
-			FPT_HIP_CHECK(hipMemsetAsync(ps.cells.ptr, 0, (size_t(1) << ps.log2_size) * 4 * sizeof(long long), s));
-		};
+		auto reset_cache = [&] { ps.table.clear(s); };          // initialize the shading cache (src/renderers/psfpt_impl.h:385-387)
 		if (!batched && (instance % ps.opt.psf_temporal_reuse) == 0) reset_cache();
 		FPT_HIP_CHECK(hipMemsetAsync(ps.ref_size.ptr, 0, 32 * sizeof(uint32_t), s));
 
@@ -161,24 +152,10 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 		if (batched) { pass.n_slot = ctx->n_local; pass.acc_stride = ctx->n_local; pass.pixels = ctx->d_pixels; }
 		else         { pass.n_slot = view->res_x * view->res_y; pass.acc_stride = pass.n_slot; pass.pixels = nullptr; }
 		SequenceView seq; seq.shifts = ctx->d_shifts.ptr; seq.n_dims = ctx->seq_dims; seq.tile_size = ctx->seq_tile;
-		PsfDev psf;
-		psf.keys = ps.keys.ptr; psf.cells = ps.cells.ptr; psf.log2_size = ps.log2_size;
-		psf.ref_pixels = ps.ref_pixels.ptr; psf.ref_cache = ps.ref_cache.ptr; psf.ref_wd = ps.ref_wd.ptr; psf.ref_wg = ps.ref_wg.ptr; psf.ref_size = ps.ref_size.ptr; psf.ref_k = ps.ref_k.ptr;
-		psf.bbox_lo = mk3(ps.bbox[0], ps.bbox[1], ps.bbox[2]); psf.bbox_hi = mk3(ps.bbox[3], ps.bbox[4], ps.bbox[5]);
-		psf.depth = ps.opt.psf_depth; psf.width = ps.opt.psf_width; psf.max_prob = ps.opt.psf_max_prob; psf.firefly = ps.opt.firefly_filter; psf.instance = instance;
-		psf.g_keys = nullptr; psf.g_cells = nullptr; psf.touched = nullptr; psf.touched_n = nullptr; psf.pass_stride = 0; psf.g_log2_size = ps.log2_size;
-		if (ps.sharded)
-		{
-			require(!ps.pending, "fpt_psfpt_render: the previous pass has not been finished (fpt_psfpt_exchange_cells / fpt_psfpt_import_cells, then fpt_psfpt_finish)");
-			psf.g_keys = ps.keys.ptr; psf.g_cells = ps.cells.ptr; psf.keys = ps.p_keys.ptr; psf.cells = ps.p_cells.ptr;
-			psf.touched = ps.touched.ptr; psf.touched_n = ps.touched_n.ptr;
-		}
-		if (batched)
-		{
-			// one pass table per pass of the batch (2^b_log2 slots each, enough for every cell a pass can create), their slot lists, the global table
-			psf.g_keys = ps.keys.ptr; psf.g_cells = ps.cells.ptr; psf.keys = ps.b_keys.ptr; psf.cells = ps.b_cells.ptr;
-			psf.touched = ps.b_touched.ptr; psf.touched_n = ps.b_touched_n.ptr; psf.log2_size = ps.b_log2; psf.pass_stride = 1u << ps.b_log2;
-		}
+		require(!ps.sharded || !ps.pending, "fpt_psfpt_render: the previous pass has not been finished (fpt_psfpt_exchange_cells / fpt_psfpt_import_cells, then fpt_psfpt_finish)");
+		// batched: one pass table per pass of the batch (2^log2 slots each, enough for every cell a pass can create), their slot lists, the global table
+		PsfDev psf = psf_dev(ctx, batched ? PSF_BATCHED : ps.sharded ? PSF_SHARDED : PSF_PLAIN);
+		psf.bbox_lo = mk3(ps.bbox[0], ps.bbox[1], ps.bbox[2]); psf.bbox_hi = mk3(ps.bbox[3], ps.bbox[4], ps.bbox[5]); psf.instance = instance;
 
 		// the rays are those of the renderer's own queues (fpt_device.h PathQueue / ShadowQueue): the .w words carry PixelInfo / pass offset, the intervals are the queues'
 		auto trace = [&](const float4* rays, float4* hits, const uint32_t* count_ptr, bool any_hit, bool primary = false)
@@ -188,7 +165,7 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 			if (any_hit) timed_launch(ctx, 2, s, [&] { launch_trace_shadow_queue(tp, ctx->counting, ctx->trace_blocks(), s); });
 			else         timed_launch(ctx, 0, s, [&] { launch_trace_closest_queue(tp, primary, ctx->counting, ctx->trace_blocks(), s); });
 		};
-		QueueStorage* qa = &ctx->q_a; QueueStorage* qb = &ctx->q_b;
+		QueueStorage* qa = &w.q_a; QueueStorage* qb = &w.q_b;
 		PathQueue qin = qa->view(cnt.queue(0, CNT_PATH)), qout = qb->view(cnt.queue(1, CNT_PATH));
 		launch_primary_rays(primary_params(view, seq, ctx->d_pixels, ctx->n_local, pass, qin), s);
 		ShadeParams sh; std::memset(&sh, 0, sizeof(sh));
@@ -207,7 +184,7 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 			for (uint32_t b = 0; b < opt.max_path_length; ++b)
 			{
 				ResolveParams& r = blocks[b];
-				r.q = ctx->q_shadow.view(nullptr); r.fb = fb; r.bounce = b; r.psf = psf; r.psf.instance = 0; r.log = log; r.kind = 1;
+				r.q = w.q_shadow.view(nullptr); r.fb = fb; r.bounce = b; r.psf = psf; r.psf.instance = 0; r.log = log; r.kind = 1;
 				r.pass = pass; r.pass.base_instance = 0;          // the launch's first instance travels as a kernel argument
 			}
 			upload_if_changed(ps.d_resolve, ps.h_resolve, blocks, s);
@@ -218,7 +195,7 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 		{
 			sh.bounce = bounce;
 			per_bounce_options(sh, opt, uint32_t(ctx->emitters.vpls.size()));
-			ShadowQueue qsd = ctx->q_shadow_dir.view(cnt.queue(bounce, CNT_SHADOW_DIR)), qs = ctx->q_shadow.view(cnt.queue(bounce, CNT_SHADOW));
+			ShadowQueue qsd = w.q_shadow_dir.view(cnt.queue(bounce, CNT_SHADOW_DIR)), qs = w.q_shadow.view(cnt.queue(bounce, CNT_SHADOW));
 			sh.in = qin; sh.scatter = qout; sh.shadow_dir = qsd; sh.shadow = qs;
 			sh.psf = at_bounce(psf, bounce, n);
 			timed_launch(ctx, 3, s, [&] { launch_shade_psf(sh, n, s); });
@@ -227,8 +204,8 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 			rp.fb = fb; rp.bounce = bounce; rp.pass = pass; rp.psf = psf; rp.frame_weight = frame_weight; rp.log = log;
 			if (view->dir_lights_count && (bounce + 2 <= opt.max_path_length) && (bounce > 0 || opt.direct_lighting))
 			{
-				trace(qsd.rays, ctx->q_shadow_dir.hits.ptr, qsd.size, true);
-				rp.q = qsd; rp.hits = ctx->q_shadow_dir.hits.ptr; rp.kind = 0;
+				trace(qsd.rays, w.q_shadow_dir.hits.ptr, qsd.size, true);
+				rp.q = qsd; rp.hits = w.q_shadow_dir.hits.ptr; rp.kind = 0;
 				launch_psf_resolve(rp, n, s);
 			}
 			if (sh.do_nee && sh.do_scatter)
@@ -245,8 +222,8 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 			{
 				if (sh.do_nee)
 				{
-					trace(qs.rays, ctx->q_shadow.hits.ptr, qs.size, true);
-					rp.q = qs; rp.hits = ctx->q_shadow.hits.ptr; rp.kind = 1;
+					trace(qs.rays, w.q_shadow.hits.ptr, qs.size, true);
+					rp.q = qs; rp.hits = w.q_shadow.hits.ptr; rp.kind = 1;
 					launch_psf_resolve(rp, n, s);
 				}
 				if (!sh.do_scatter) break;
@@ -282,7 +259,7 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 				t.touched = psf.touched + size_t(k) * psf.pass_stride; t.touched_n = psf.touched_n + k;
 				launch_psf_clear_pass(t, s);
 			}
-			FPT_HIP_CHECK(hipMemsetAsync(ps.b_touched_n.ptr, 0, ps.b_touched_n.count * sizeof(uint32_t), s));
+			FPT_HIP_CHECK(hipMemsetAsync(ps.batch.touched_n.ptr, 0, ps.batch.touched_n.count * sizeof(uint32_t), s));
 			FPT_HIP_CHECK(hipGetLastError());
 			return;
 		}
@@ -307,39 +284,24 @@ int fpt_psfpt_render_batch(fpt_context* ctx, uint32_t first_instance, uint32_t n
 int fpt_psfpt_set_deferred(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_context_view* view)
 {
 	{ const int st = guarded(ctx, [&] { flush_deferred(ctx); require(max_passes >= 1, "fpt_psfpt_set_deferred: max_passes must be >= 1"); }); if (st != 0) return st; }
-	if (max_passes > ctx->psf.max_batch) { const int st = fpt_psfpt_set_batch(ctx, max_passes, view); if (st != 0) return st; }
+	if (!ctx->store.serves(max_passes, true, view && view->dir_lights_count)) { const int st = fpt_psfpt_set_batch(ctx, max_passes, view); if (st != 0) return st; }
 	return guarded(ctx, [&] { ctx->defer_max = max_passes; ctx->defer_kind = DEFER_PSFPT; });
 }
 
-// storage for `max_passes` passes in flight: the path tracer's queues and planes (fpt_pt_set_batch), the PSFPT's per-path words and reference
-// queue, and one pass table per pass of 2^b slots, 2^b >= (pixels rendered here) x (max_path_length + 1) >= the cells a pass can create, so a pass
+// storage for `max_passes` passes in flight: the store with the PSFPT's extras, and one pass table per pass of 2^b slots, 2^b >= (pixels rendered here) x (max_path_length + 1) >= the cells a pass can create, so a pass
 // table fills up only if the global table (2^24 or 2^26 slots) would
 int fpt_psfpt_set_batch(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_context_view* view)
 {
-	const int st = fpt_internal_set_batch(ctx, max_passes, view, true);       // queues + albedo planes + the contribution log with blend cells
-	if (st != 0) return st;
 	return guarded(ctx, [&] {
 		fpt_context::PsfState& ps = ctx->psf;
 		require(ps.ready, "fpt_psfpt_set_batch: fpt_psfpt_init has not been called");
 		require(!ps.sharded || max_passes == 1, "fpt_psfpt_set_batch: a sharded context renders one pass at a time");
-		const size_t n = size_t(ctx->n_local) * max_passes;
-		ctx->q_a.vinfo.alloc(n); ctx->q_b.vinfo.alloc(n);
-		ctx->q_shadow.vinfo.alloc(n); ctx->q_shadow.hits.alloc(n);
-		ctx->q_shadow_dir.vinfo.alloc(view->dir_lights_count ? n : 1); ctx->q_shadow_dir.hits.alloc(view->dir_lights_count ? n : 1);
-		const size_t nr = n * (ctx->opt.max_path_length + 1);
-		ps.ref_pixels.alloc(nr); ps.ref_k.alloc(nr); ps.ref_cache.alloc(nr); ps.ref_wd.alloc(nr); ps.ref_wg.alloc(nr);
-		ps.max_batch = max_passes;
-		ps.h_resolve.clear();          // the blocks of the fused resolve name these buffers
+		set_batch(ctx, max_passes, view, true);
 		if (max_passes > 1)
 		{
 			uint32_t b = 10;
-			while ((size_t(1) << b) < size_t(ctx->n_local) * (ctx->opt.max_path_length + 1) && b < ps.log2_size) ++b;
-			ps.b_log2 = b;
-			const size_t slots = (size_t(1) << b) * max_passes;
-			ps.b_keys.alloc(slots); ps.b_cells.alloc(slots * 4); ps.b_touched.alloc(slots); ps.b_touched_n.alloc(std::max<size_t>(max_passes, 32));
-			FPT_HIP_CHECK(hipMemsetAsync(ps.b_keys.ptr, 0xFF, slots * sizeof(unsigned long long), ctx->stream));
-			FPT_HIP_CHECK(hipMemsetAsync(ps.b_cells.ptr, 0, slots * 4 * sizeof(long long), ctx->stream));
-			FPT_HIP_CHECK(hipMemsetAsync(ps.b_touched_n.ptr, 0, ps.b_touched_n.count * sizeof(uint32_t), ctx->stream));
+			while ((size_t(1) << b) < size_t(ctx->n_local) * (ctx->opt.max_path_length + 1) && b < ps.table.log2) ++b;
+			ps.batch.alloc(b, max_passes, true); ps.batch.clear(ctx->stream);
 		}
 		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 	});
@@ -354,11 +316,8 @@ int fpt_psfpt_set_sharded(fpt_context* ctx, int on)
 		require(!ps.pending, "fpt_psfpt_set_sharded: a pass is pending");
 		ps.sharded = on != 0;
 		if (!ps.sharded) return;
-		const size_t n = size_t(1) << ps.log2_size;
-		ps.p_keys.alloc(n); ps.p_cells.alloc(n * 4); ps.touched.alloc(n); ps.touched_n.alloc(32); ps.records.alloc(n);
-		FPT_HIP_CHECK(hipMemsetAsync(ps.p_keys.ptr, 0xFF, n * sizeof(unsigned long long), ctx->stream));
-		FPT_HIP_CHECK(hipMemsetAsync(ps.p_cells.ptr, 0, n * 4 * sizeof(long long), ctx->stream));
-		FPT_HIP_CHECK(hipMemsetAsync(ps.touched_n.ptr, 0, 32 * sizeof(uint32_t), ctx->stream));
+		ps.shard.alloc(ps.table.log2, 1, true); ps.shard.clear(ctx->stream);
+		ps.records.alloc(size_t(1) << ps.table.log2);
 	});
 }
 
@@ -369,7 +328,7 @@ int fpt_psfpt_export_cells(fpt_context* ctx, const void** d_records, uint32_t* n
 		require(ps.sharded && ps.pending, "fpt_psfpt_export_cells: no sharded pass is pending");
 		require(d_records && n_records, "fpt_psfpt_export_cells: null argument");
 		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		FPT_HIP_CHECK(hipMemcpy(n_records, ps.touched_n.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost));
+		FPT_HIP_CHECK(hipMemcpy(n_records, ps.shard.touched_n.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost));
 		*d_records = ps.records.ptr;
 	});
 }
@@ -381,7 +340,7 @@ int fpt_psfpt_import_cells(fpt_context* ctx, const void* d_records, uint32_t n_r
 		require(ps.sharded && ps.pending, "fpt_psfpt_import_cells: no sharded pass is pending");
 		require(d_records || n_records == 0, "fpt_psfpt_import_cells: null records");
 		if (!n_records) return;
-		launch_psf_merge(sharded_view(ctx), static_cast<const PsfRecord*>(d_records), nullptr, n_records, ctx->stream);
+		launch_psf_merge(psf_dev(ctx, PSF_SHARDED), static_cast<const PsfRecord*>(d_records), nullptr, n_records, ctx->stream);
 		FPT_HIP_CHECK(hipGetLastError());
 	});
 }
@@ -391,11 +350,11 @@ int fpt_psfpt_finish(fpt_context* ctx, const fpt_rendering_context_view* view)
 	return guarded(ctx, [&] {
 		fpt_context::PsfState& ps = ctx->psf;
 		require(ps.sharded && ps.pending, "fpt_psfpt_finish: no sharded pass is pending");
-		PsfDev psf = sharded_view(ctx);
+		PsfDev psf = psf_dev(ctx, PSF_SHARDED);
 		psf.instance = ps.pending_instance;
 		finish_pass(ctx, psf, fb_dev(view->fb), ps.pending_instance, ps.pending_bounces);
 		launch_psf_clear_pass(psf, ctx->stream);
-		FPT_HIP_CHECK(hipMemsetAsync(ps.touched_n.ptr, 0, sizeof(uint32_t), ctx->stream));
+		FPT_HIP_CHECK(hipMemsetAsync(ps.shard.touched_n.ptr, 0, sizeof(uint32_t), ctx->stream));
 		ps.pending = false;
 		FPT_HIP_CHECK(hipGetLastError());
 	});

@@ -212,6 +212,11 @@ int fpt_pt_set_batch(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_
 /* What passes in flight cost, so that a host can size them to the device it runs on (VERDICT r3 weak #9 / ADVICE r3): free and total bytes of the context's
  * device (hipMemGetInfo), and the bytes ONE path in flight takes in the queues, the albedo planes and the contribution log of `renderer`
  * (0 = -pt, 1 = -psfpt, 2 = -bpt with the options of the last fpt_*_init).  Memory for n passes = n x (pixels rendered here) x that figure.
+ * The figure is the sum over the arrays the set-up calls allocate, read off the same list they allocate from: without directional lights 436 B for -pt at
+ * max_path_length 4 and 676 B at 9, 1016 B for -psfpt at 5 (its pass tables are per pass, not per path), 3391 B for -bpt at 9 with -sc 0 (there with every
+ * pixel rendered here: under tile sharding its light-vertex store, splat sums, planes and log stay whole-frame).
+ * -pt and -psfpt share that storage, and the last set-up call of either decides its shape: after fpt_pt_init / fpt_pt_set_batch / fpt_pt_set_deferred a -psfpt
+ * render is refused until fpt_psfpt_set_batch is called again, and a view with directional lights is refused by storage that was sized for a view without.
  * Since round 4 PixelInfo no longer bounds the passes in flight of -pt / -psfpt (the pass offset travels beside it): memory does. */
 int fpt_device_memory(fpt_context* ctx, uint64_t* free_bytes, uint64_t* total_bytes);
 int fpt_bytes_per_path_in_flight(fpt_context* ctx, uint32_t renderer, const fpt_rendering_context_view* view, uint64_t* bytes);
