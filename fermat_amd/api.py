@@ -162,6 +162,7 @@ ENTRY_POINTS = ["fpt_create", "fpt_destroy", "fpt_last_error", "fpt_stream", "fp
                 "fpt_bpt_allreduce_splats", "fpt_comm_selftest", "fpt_pt_last_union_ms", "fpt_pt_lane_count", "fpt_pt_set_lanes", "fpt_pt_set_deferred", "fpt_pt_flush", "fpt_pt_launch_list", "fpt_set_tile_lists", "fpt_gather_pack", "fpt_gather_unpack", "fpt_device_memory", "fpt_bytes_per_path_in_flight", "fpt_bpt_set_shared_light_vertices", "fpt_bpt_export_light_vertices", "fpt_bpt_import_light_vertices", "fpt_bpt_exchange_light_vertices", "fpt_bpt_finish",
                 "fpt_multiply_frame", "fpt_clamp_frame", "fpt_sequence_device_view", "fpt_mesh_lights_device_view", "fpt_mesh_invalidate", "fpt_rt_refit_geometry", "fpt_debug_refit_bvh",
                 "fpt_debug_build_emitter_tables", "fpt_clear_gbuffer", "fpt_rt_download_bvh", "fpt_mesh_lights_update", "fpt_rt_set_build_mode",
+                "fpt_mesh_lights_init_device", "fpt_mesh_lights_update_device",
                 "fpt_debug_psf", "fpt_psfpt_debug_set_table_log2", "fpt_debug_bpt", "fpt_debug_frame"]
 
 
@@ -943,6 +944,17 @@ class Renderer:
             if log.get(k) is not None:
                 log[k] = down(log[k], devs[8 + i])
         return out, log
+
+    def init_emitters_device(self, n_vpls=None, instance=0):
+        """fpt_mesh_lights_init_device: the emitter tables built ON THE DEVICE from the device mesh (self.view.mesh, self.d_tex_views), bit for bit the tables
+        fpt_mesh_lights_init builds from a host mesh with the same vertices; the host views give the static part only (materials, texture coordinates, texels)"""
+        n = self.res[0] * self.res[1] if n_vpls is None else int(n_vpls)
+        self._check(self.L.fpt_mesh_lights_init_device(self.ctx, C.c_uint32(n), C.byref(self.h_mesh), C.byref(self._h_tex), C.byref(self.view.mesh),
+                                                       C.c_void_p(self.d_tex_views.data_ptr()), C.c_uint32(instance)))
+
+    def update_emitters_device(self):
+        """fpt_mesh_lights_update_device: the device mesh's vertices moved (refit_geometry / rebuild_geometry): all four tables are rebuilt on the device"""
+        self._check(self.L.fpt_mesh_lights_update_device(self.ctx, C.byref(self.view.mesh)))
 
     def reinit_emitters(self, n_vpls):
         """fpt_mesh_lights_init again with another VPL count (the probe's emitter tables)"""

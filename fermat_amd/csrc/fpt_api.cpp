@@ -275,16 +275,33 @@ int fpt_mesh_lights_update(fpt_context* ctx, uint32_t n_vpls, const fpt_mesh_vie
 	}
 	return fpt_mesh_lights_init(ctx, n_vpls, h_mesh, h_textures, instance);
 }
+// the same tables built on the device from the device mesh view (fpt_lights_device.hip): bit for bit what fpt_mesh_lights_init builds from a host mesh with these vertices
+int fpt_mesh_lights_init_device(fpt_context* ctx, uint32_t n_vpls, const fpt_mesh_view* h_mesh, const fpt_texture* h_textures, const fpt_mesh_view* d_mesh,
+                                const fpt_texture* d_textures, uint32_t instance)
+{
+	return guarded(ctx, [&] { flush_deferred(ctx);
+		require(h_mesh != nullptr && d_mesh != nullptr, "fpt_mesh_lights_init_device: null mesh");
+		emitters_init_device(ctx, n_vpls, *h_mesh, h_textures, *d_mesh, d_textures, instance);
+	});
+}
+int fpt_mesh_lights_update_device(fpt_context* ctx, const fpt_mesh_view* d_mesh)
+{
+	return guarded(ctx, [&] { flush_deferred(ctx);
+		require(ctx->emitter_builder.ready, "fpt_mesh_lights_update_device: fpt_mesh_lights_init_device has not been called");
+		require(d_mesh != nullptr, "fpt_mesh_lights_update_device: null mesh");
+		emitters_update_device(ctx, *d_mesh);
+	});
+}
 int fpt_mesh_lights_download(fpt_context* ctx, uint32_t* n_vpls, fpt_vpl* h_vpls, float* h_vpl_cdf, float* h_mesh_cdf, float* h_mesh_inv_area, float* norm)
 {
 	return guarded(ctx, [&] {
 		require(ctx->has_emitters, "fpt_mesh_lights_download: mesh lights not initialised");
 		const EmitterTables& e = ctx->emitters;
-		if (n_vpls) *n_vpls = uint32_t(e.vpls.size());
-		if (h_vpls) ctx->d_vpls.download(h_vpls, e.vpls.size(), ctx->stream);
-		if (h_vpl_cdf) ctx->d_vpl_cdf.download(h_vpl_cdf, e.vpl_cdf.size(), ctx->stream);
-		if (h_mesh_cdf) ctx->d_mesh_cdf.download(h_mesh_cdf, e.mesh_cdf.size(), ctx->stream);
-		if (h_mesh_inv_area) ctx->d_mesh_inv_area.download(h_mesh_inv_area, e.mesh_inv_area.size(), ctx->stream);
+		if (n_vpls) *n_vpls = e.n_vpls;
+		if (h_vpls) ctx->d_vpls.download(h_vpls, e.n_vpls, ctx->stream);
+		if (h_vpl_cdf) ctx->d_vpl_cdf.download(h_vpl_cdf, e.n_vpls, ctx->stream);
+		if (h_mesh_cdf) ctx->d_mesh_cdf.download(h_mesh_cdf, e.n_prims, ctx->stream);
+		if (h_mesh_inv_area) ctx->d_mesh_inv_area.download(h_mesh_inv_area, e.n_prims, ctx->stream);
 		if (norm) *norm = e.norm;
 	});
 }
@@ -309,7 +326,7 @@ int fpt_pt_init(fpt_context* ctx, const fpt_pt_options* opts, const fpt_renderin
 		ctx->seq_dims = 6 * (opts->max_path_length + 1); ctx->seq_tile = 256;
 		ctx->d_shifts.upload(ctx->h_shifts.data(), ctx->h_shifts.size(), ctx->stream);
 		ctx->d_samples.alloc(ctx->h_shifts.size());
-		if (ctx->has_emitters && ctx->emitters.vpls.empty()) ctx->opt.nee_type = 0;     // :165-166
+		if (ctx->has_emitters && ctx->emitters.n_vpls == 0) ctx->opt.nee_type = 0;     // :165-166
 		ctx->defer_max = 1;
 		ctx->pt_ready = true;
 	});
@@ -358,8 +375,8 @@ int fpt_mesh_lights_device_view(fpt_context* ctx, fpt_mesh_lights_view* out)
 {
 	return guarded(ctx, [&] {
 		require(ctx->has_emitters && out, "fpt_mesh_lights_device_view: fpt_mesh_lights_init has not been called");
-		out->d_mesh_cdf = ctx->d_mesh_cdf.ptr; out->d_mesh_inv_area = ctx->d_mesh_inv_area.ptr; out->n_prims = uint32_t(ctx->emitters.mesh_cdf.size());
-		out->d_vpls = ctx->d_vpls.ptr; out->d_vpl_cdf = ctx->d_vpl_cdf.ptr; out->n_vpls = uint32_t(ctx->emitters.vpls.size()); out->norm = ctx->emitters.norm;
+		out->d_mesh_cdf = ctx->d_mesh_cdf.ptr; out->d_mesh_inv_area = ctx->d_mesh_inv_area.ptr; out->n_prims = ctx->emitters.n_prims;
+		out->d_vpls = ctx->d_vpls.ptr; out->d_vpl_cdf = ctx->d_vpl_cdf.ptr; out->n_vpls = ctx->emitters.n_vpls; out->norm = ctx->emitters.norm;
 	});
 }
 int fpt_to_rgba(fpt_context* ctx, const fpt_rendering_context_view* view, uint8_t* d_rgba)
@@ -480,7 +497,7 @@ const ShadeRecord* ensure_shade_records(fpt_context* ctx, const fpt_rendering_co
 }
 const float4* ensure_vpl_points(fpt_context* ctx, const fpt_rendering_context_view* view, hipStream_t s)
 {
-	const uint32_t n = uint32_t(ctx->emitters.vpls.size());
+	const uint32_t n = ctx->emitters.n_vpls;
 	if (n == 0) return nullptr;
 	const bool fresh = ctx->vpl_points_generation == ctx->emitter_generation && ctx->d_vpl_points.count == VPL_POINT_STRIDE * size_t(n) &&
 	                   same_mesh(ctx->vpl_points_mesh, view->mesh) && ctx->vpl_points_textures == view->d_textures;
@@ -607,7 +624,7 @@ static void render_lane(fpt_context* ctx, const LaneRefs& L, uint32_t instance, 
 		for (uint32_t bounce = 0; bounce < opt.max_path_length; ++bounce)
 		{
 			sh.bounce = bounce;
-			per_bounce_options(sh, opt, uint32_t(ctx->emitters.vpls.size()));
+			per_bounce_options(sh, opt, ctx->emitters.n_vpls);
 
 			if (sync_mode)
 			{

@@ -58,9 +58,30 @@ struct EmitterTables
 	std::vector<float> mesh_cdf, mesh_inv_area, vpl_cdf;
 	std::vector<fpt_vpl> vpls;
 	float norm = 0.0f;
+	uint32_t n_prims = 0, n_vpls = 0;          // the tables' sizes, set by whoever built them: the device builder (fpt_lights_device.hip) leaves the host vectors empty
 };
 void build_emitter_tables(uint32_t n_vpls, const fpt_mesh_view& h_mesh, const fpt_texture* h_textures, uint32_t instance, EmitterTables& out);
+// what the tables take from materials, texture coordinates and texels alone (fpt_lights.cpp): the per-triangle factor of the area and the random stream behind it
+struct EmitterStatic { std::vector<float> e; uint32_t state = 0, scramble = 0; };
+void emitter_static_part(const fpt_mesh_view& h_mesh, const fpt_texture* h_textures, uint32_t instance, EmitterStatic& out);
+enum : uint32_t { LFSR_JUMPS = 41 };
+void lfsr_jump_matrices(uint32_t* out);          // LFSR_JUMPS x 32 words
 uint64_t emitter_fingerprint(const fpt_mesh_view& h_mesh, const fpt_texture* h_textures);          // of the emitting triangles' positions
+
+// The device builder of the emitter tables (fpt_lights_device.hip) and what it keeps between rebuilds: the static part of the last fpt_mesh_lights_init_device, the
+// stream's jump matrices, the tables under construction (swapped with the context's when a build succeeded, so a rebuild of the same sizes allocates nothing) and scratch.
+struct DeviceEmitterBuilder
+{
+	bool ready = false;                                 // fpt_mesh_lights_init_device succeeded: fpt_mesh_lights_update_device may follow
+	uint32_t n_vpls = 0, n_prims = 0, state = 0, scramble = 0;
+	const fpt_texture* d_textures = nullptr;
+	DeviceArray<float> e; DeviceArray<uint32_t> jumps;
+	DeviceArray<float> next_mesh_cdf, next_mesh_inv_area, next_vpl_cdf; DeviceArray<fpt_vpl> next_vpls;
+	DeviceArray<uint8_t> scratch;
+	float* h_stage = nullptr; size_t h_stage_count = 0;   // pinned host staging of the sums that stay in index order
+	~DeviceEmitterBuilder() { if (h_stage) (void)hipHostFree(h_stage); }
+	DeviceEmitterBuilder() = default; DeviceEmitterBuilder(const DeviceEmitterBuilder&) = delete; DeviceEmitterBuilder& operator=(const DeviceEmitterBuilder&) = delete;
+};
 
 struct QueueStorage
 {
@@ -225,6 +246,7 @@ struct fpt_context
 	fpt::DeviceArray<float> d_mesh_cdf, d_mesh_inv_area, d_vpl_cdf;
 	fpt::DeviceArray<fpt_vpl> d_vpls;
 	bool has_emitters = false;
+	fpt::DeviceEmitterBuilder emitter_builder;
 	uint64_t emitters_fingerprint = 0; uint32_t emitters_n_vpls = 0, emitters_instance = 0; const void* emitters_mesh_identity[4] = { nullptr, nullptr, nullptr, nullptr };
 	// the VPLs' tabulated light points (EmitterView::vpl_points): built from the view's mesh / materials / textures, so rebuilt when fpt_mesh_lights_init or
 	// fpt_rt_create_geometry ran (emitter_generation) or a view names other buffers
@@ -389,6 +411,10 @@ inline fpt::FrameBufferDev fb_dev(const fpt_framebuffer_view& v)
 inline double wall_seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // fpt_build_lbvh.hip: the device-side builds (Morton radix tree [mode 2: restructured by treelets] -> SAH-optimal 8-wide collapse) into ctx->tree; mode =
 // fpt_rt_set_build_mode's 1 or 2; false = the tree needs more stack than the kernel has (ctx->tree is as it was): use the host builder.  fpt_build.hip: the refit of ctx->tree
+// fpt_lights_device.hip: the emitter tables built on the device from the device mesh view (fpt_mesh_lights_init_device / fpt_mesh_lights_update_device)
+namespace fpt { void emitters_init_device(fpt_context* ctx, uint32_t n_vpls, const fpt_mesh_view& h_mesh, const fpt_texture* h_textures, const fpt_mesh_view& d_mesh,
+                                          const fpt_texture* d_textures, uint32_t instance);
+                void emitters_update_device(fpt_context* ctx, const fpt_mesh_view& d_mesh); }
 namespace fpt { bool build_acceleration_device(fpt_context* ctx, uint32_t tri_count, const int32_t* d_idx, uint32_t vertex_count, const float* d_vtx, uint32_t stack_limit, uint32_t mode);
                 void refit_acceleration_device(fpt_context* ctx, uint32_t tri_count, const int32_t* d_idx, uint32_t vertex_count, const float* d_vtx); }
 
@@ -434,8 +460,8 @@ inline fpt::TraceParams trace_params(fpt_context* ctx, fpt::PassCounters& cnt)
 inline fpt::EmitterView emitter_view(fpt_context* ctx, bool use_vpls)
 {
 	fpt::EmitterView em; std::memset(&em, 0, sizeof(em));
-	em.n_prims = uint32_t(ctx->emitters.mesh_cdf.size()); em.prims_cdf = ctx->d_mesh_cdf.ptr; em.prims_inv_area = ctx->d_mesh_inv_area.ptr;
-	em.n_vpls = use_vpls ? uint32_t(ctx->emitters.vpls.size()) : 0u; em.vpls = use_vpls ? ctx->d_vpls.ptr : nullptr; em.norm = ctx->emitters.norm;
+	em.n_prims = ctx->emitters.n_prims; em.prims_cdf = ctx->d_mesh_cdf.ptr; em.prims_inv_area = ctx->d_mesh_inv_area.ptr;
+	em.n_vpls = use_vpls ? ctx->emitters.n_vpls : 0u; em.vpls = use_vpls ? ctx->d_vpls.ptr : nullptr; em.norm = ctx->emitters.norm;
 	return em;
 }
 

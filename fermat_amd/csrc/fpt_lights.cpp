@@ -172,32 +172,35 @@ uint64_t emitter_fingerprint(const fpt_mesh_view& mesh, const fpt_texture* textu
 	return h ^ (uint64_t(th) << 56);          // (the slicing depends on the thread count, which is fixed for a process)
 }
 
-void build_emitter_tables(uint32_t n_vpls, const fpt_mesh_view& mesh, const fpt_texture* textures, uint32_t instance, EmitterTables& out)
+namespace { const Lfsr32& lfsr_generator() { static const Lfsr32 generator; return generator; } }
+
+// the column matrices of the stream's transition raised to 2^k, k < LFSR_JUMPS (32 words each): what the device builder's threads apply to jump to their place in the stream
+// (LfsrStream::skipped's squarings, tabulated)
+void lfsr_jump_matrices(uint32_t* out)
 {
-	const auto clock = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-	const double t_start = clock();
+	auto apply = [](const uint32_t* M, uint32_t v) { uint32_t r = 0; for (uint32_t i = 0; v; ++i, v >>= 1) if (v & 1u) r ^= M[i]; return r; };
+	for (uint32_t i = 0; i < 32; ++i) out[i] = lfsr_generator().col[i];
+	for (uint32_t k = 1; k < LFSR_JUMPS; ++k) for (uint32_t i = 0; i < 32; ++i) out[32 * k + i] = apply(out + 32 * (k - 1), out[32 * (k - 1) + i]);
+}
+
+// The part of the tables that does not depend on vertex positions, shared by the host builder below and the device builder (fpt_lights_device.hip): per triangle the
+// factor e[t] = emission_pdf_measure(emission) that multiplies its area -- for a triangle with a texel-backed emissive map the 10-sample mip estimate -- and the random
+// stream as those estimates leave it (20 draws per mapped triangle, in triangle order, with or without texture coordinates).
+void emitter_static_part(const fpt_mesh_view& mesh, const fpt_texture* textures, uint32_t instance, EmitterStatic& out)
+{
 	const uint32_t nt = uint32_t(mesh.num_triangles);
 	const uint32_t th = table_threads();
-	out.mesh_cdf.assign(nt, 0.0f); out.mesh_inv_area.assign(nt, 0.0f);
-	out.vpl_cdf.clear(); out.vpls.clear(); out.norm = 0.0f;
-	static const Lfsr32 generator;
-	LfsrStream random{ generator, 1u, hash32(1351u + instance) };
-
-	// emission-weighted triangle CDF, accumulated in double (src/mesh_lights.cu:169-277)
-	std::vector<float> weight(nt);          // emission_pdf_measure(emission) * area
+	out.e.assign(nt, 0.0f);
+	LfsrStream random{ lfsr_generator(), 1u, hash32(1351u + instance) };
 	std::vector<uint32_t> mapped;           // triangles whose material has an emissive map with texels: they draw from the stream, in triangle order
 	{
 		std::vector<std::vector<uint32_t>> part(th);
 		slices(nt, th, [&](size_t tb, size_t te, uint32_t sl) {
 			for (size_t t = tb; t < te; ++t)
 			{
-				const int32_t* ix = mesh.vertex_indices + 4 * t;
-				const f3 p0 = mesh_position(mesh, ix[0]), p1 = mesh_position(mesh, ix[1]), p2 = mesh_position(mesh, ix[2]);
-				const float area = 0.5f * length(cross(p0 - p2, p1 - p2));
 				const fpt_material& mat = mesh.materials[mesh.material_indices[t]];
-				out.mesh_inv_area[t] = 1.0f / area;
-				if (mat.emissive_map.texture != 0xFFFFFFFFu && textures && textures[mat.emissive_map.texture].texels) { part[sl].push_back(uint32_t(t)); weight[t] = area; }
-				else weight[t] = emission_pdf_measure(load4(mat.emissive)) * area;
+				if (mat.emissive_map.texture != 0xFFFFFFFFu && textures && textures[mat.emissive_map.texture].texels) part[sl].push_back(uint32_t(t));
+				else out.e[t] = emission_pdf_measure(load4(mat.emissive));
 			} });
 		for (const std::vector<uint32_t>& p : part) mapped.insert(mapped.end(), p.begin(), p.end());
 	}
@@ -205,7 +208,6 @@ void build_emitter_tables(uint32_t n_vpls, const fpt_mesh_view& mesh, const fpt_
 	for (const uint32_t t : mapped)
 	{
 		const int32_t* ix = mesh.vertex_indices + 4 * size_t(t);
-		const float area = weight[t];
 		const fpt_material& mat = mesh.materials[mesh.material_indices[t]];
 		f4 emission = load4(mat.emissive);
 		const uint32_t n_samples = 10;
@@ -237,8 +239,35 @@ void build_emitter_tables(uint32_t n_vpls, const fpt_mesh_view& mesh, const fpt_
 			const float inv = float(n_samples);
 			emission = emission * mk4(avg.x / inv, avg.y / inv, avg.z / inv, avg.w / inv);
 		}
-		weight[t] = emission_pdf_measure(emission) * area;
+		out.e[t] = emission_pdf_measure(emission);
 	}
+	out.state = random.state; out.scramble = random.scramble;
+}
+
+void build_emitter_tables(uint32_t n_vpls, const fpt_mesh_view& mesh, const fpt_texture* textures, uint32_t instance, EmitterTables& out)
+{
+	const auto clock = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+	const double t_start = clock();
+	const uint32_t nt = uint32_t(mesh.num_triangles);
+	const uint32_t th = table_threads();
+	out.mesh_cdf.assign(nt, 0.0f); out.mesh_inv_area.assign(nt, 0.0f);
+	out.vpl_cdf.clear(); out.vpls.clear(); out.norm = 0.0f;
+	out.n_prims = nt; out.n_vpls = 0;
+	EmitterStatic fixed;
+	emitter_static_part(mesh, textures, instance, fixed);
+	LfsrStream random{ lfsr_generator(), fixed.state, fixed.scramble };
+
+	// emission-weighted triangle CDF, accumulated in double (src/mesh_lights.cu:169-277)
+	std::vector<float> weight(nt);          // emission_pdf_measure(emission) * area
+	slices(nt, th, [&](size_t tb, size_t te, uint32_t) {
+		for (size_t t = tb; t < te; ++t)
+		{
+			const int32_t* ix = mesh.vertex_indices + 4 * t;
+			const f3 p0 = mesh_position(mesh, ix[0]), p1 = mesh_position(mesh, ix[1]), p2 = mesh_position(mesh, ix[2]);
+			const float area = 0.5f * length(cross(p0 - p2, p1 - p2));
+			out.mesh_inv_area[t] = 1.0f / area;
+			weight[t] = fixed.e[t] * area;
+		} });
 	double total = 0.0;
 	for (uint32_t t = 0; t < nt; ++t) { total += double(weight[t]); out.mesh_cdf[t] = float(total); }
 	if (total == 0.0)
@@ -366,7 +395,7 @@ void build_emitter_tables(uint32_t n_vpls, const fpt_mesh_view& mesh, const fpt_
 			std::swap(src, dst);
 		}
 	}
-	out.vpls.resize(n_vpls);
+	out.vpls.resize(n_vpls); out.n_vpls = n_vpls;
 	slices(n_vpls, th, [&](size_t ib, size_t ie, uint32_t) { for (size_t i = ib; i < ie; ++i) out.vpls[i] = picked[(*src)[i].second]; });
 	if (std::getenv("FPT_BVH_TIMERS"))
 		std::fprintf(stderr, "build_emitter_tables: triangle CDF %.3f s, first draw %.3f, resampling %.3f, Morton order %.3f (%u threads)\n", t_cdf - t_start, t_first - t_cdf, t_second - t_first, clock() - t_second, th);

@@ -194,7 +194,7 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 		for (uint32_t bounce = 0; bounce < opt.max_path_length; ++bounce)
 		{
 			sh.bounce = bounce;
-			per_bounce_options(sh, opt, uint32_t(ctx->emitters.vpls.size()));
+			per_bounce_options(sh, opt, ctx->emitters.n_vpls);
 			ShadowQueue qsd = w.q_shadow_dir.view(cnt.queue(bounce, CNT_SHADOW_DIR)), qs = w.q_shadow.view(cnt.queue(bounce, CNT_SHADOW));
 			sh.in = qin; sh.scatter = qout; sh.shadow_dir = qsd; sh.shadow = qs;
 			sh.psf = at_bounce(psf, bounce, n);

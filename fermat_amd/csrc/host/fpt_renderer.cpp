@@ -111,10 +111,21 @@ void RenderingContext::init(int argc, char** argv, const SceneArrays& scene)
 			m_build_mode = std::strcmp(v, "fast") == 0 ? 1u : std::strcmp(v, "trbvh") == 0 ? 2u : 0u;
 			if (m_build_mode == 0u && std::strcmp(v, "quality") != 0) std::fprintf(stderr, "warning: -bvh %s: expected quality, fast or trbvh; using quality\n", v);
 		}
+		else if (std::strcmp(argv[i], "-lights") == 0 && i + 1 < argc)       // no counterpart in the reference, which always builds from device pointers (src/mesh_lights.cu:164)
+		{
+			const char* v = argv[++i];
+			m_lights_device = std::strcmp(v, "device") == 0;
+			if (!m_lights_device && std::strcmp(v, "host") != 0) std::fprintf(stderr, "warning: -lights %s: expected host or device; using host\n", v);
+		}
 		else if (argv[i][0] == '-')
 			for (uint32 r = 0; r < m_renderer_names.size(); ++r) if (m_renderer_names[r] == argv[i] + 1) renderer_type = r;
 	}
 	if (m_aspect == 0.0f) m_aspect = float(m_res_x) / float(m_res_y);
+	if (const char* env = std::getenv("FPT_LIGHTS_BUILD"))
+	{
+		if (std::strcmp(env, "device") == 0) m_lights_device = true;
+		else if (std::strcmp(env, "host") == 0) m_lights_device = false;
+	}
 	m_scene = scene;
 
 	if (m_world > 1) device = m_rank;                      // one process per GPU: rank r drives device r of the node
@@ -227,12 +238,13 @@ void RenderingContext::update_model(const float* h_vertex_data, bool refit)
 		hip_check(hipMemcpy(const_cast<float*>(m_view.mesh.vertex_data), h_vertex_data, n * sizeof(float), hipMemcpyHostToDevice), "update_model: vertex upload");
 		if (m_scene.mesh.vertex_data != h_vertex_data)
 		{
-			// the host view the emitter builder reads must show the same vertices: from now on the context's own copy (the caller's original array is not written to)
+			// the host view must show the same vertices -- the host emitter builder (-lights host) and compute_bbox read it: from now on the context's own copy (the
+			// caller's original array is not written to)
 			m_host_vertices.assign(h_vertex_data, h_vertex_data + n);
 			m_scene.mesh.vertex_data = m_host_vertices.data();
 		}
 	}
-	else if (n)
+	else if (n && !m_lights_device)
 	{
 		// the documented route for a mesh edited in place on the device (get_device_mesh()): the emitter builder reads the HOST view, so it has to follow -- areas, the
 		// triangle CDF and the VPL selection would otherwise come from the old vertices while shading records and VPL points are derived from the new ones
@@ -240,10 +252,18 @@ void RenderingContext::update_model(const float* h_vertex_data, bool refit)
 		hip_check(hipMemcpy(m_host_vertices.data(), m_view.mesh.vertex_data, n * sizeof(float), hipMemcpyDeviceToHost), "update_model: vertex download");
 		m_scene.mesh.vertex_data = m_host_vertices.data();
 	}
+	// (-lights device: the emitter tables follow the DEVICE mesh, nothing is copied back for them; the host view's vertices then lag behind an in-place edit)
 	if (refit) check(m_ctx, fpt_rt_refit_geometry(m_ctx, uint32(m_scene.mesh.num_triangles), m_view.mesh.vertex_indices, uint32(m_scene.mesh.num_vertices), m_view.mesh.vertex_data), "update_model: refit");
 	else m_rt_context->create_geometry(uint32(m_scene.mesh.num_triangles), m_view.mesh.vertex_indices, uint32(m_scene.mesh.num_vertices), m_view.mesh.vertex_data, 0, 0, 0, 0,
 	                                   m_view.mesh.material_indices);
 	m_renderer->update_scene(*this);
+}
+
+void RenderingContext::init_mesh_lights(const char* who)
+{
+	const fpt_rendering_context_view& v = m_view;
+	if (m_lights_device) check(m_ctx, fpt_mesh_lights_init_device(m_ctx, v.res_x * v.res_y, &m_scene.mesh, m_scene.textures, &v.mesh, v.d_textures, 0), who);
+	else check(m_ctx, fpt_mesh_lights_init(m_ctx, v.res_x * v.res_y, &m_scene.mesh, m_scene.textures, 0), who);
 }
 
 void RenderingContext::render(const uint32 instance)
@@ -311,7 +331,7 @@ void HipPathTracer::init(int argc, char** argv, RenderingContext& renderer)
 	// PathTracer::init (src/renderers/pathtracer_impl.h:99-178) sets up queues + sampler, then the mesh lights with
 	// n_vpls = n_pixels; the two use independent generators (rand() vs LFSR), so the emitters are built first here to let
 	// fpt_pt_init apply the "no emitters -> mesh NEE" rule (:165-166) in one call.
-	check(ctx, fpt_mesh_lights_init(ctx, v.res_x * v.res_y, &h.mesh, h.textures, 0), "mesh_lights.init");
+	renderer.init_mesh_lights("mesh_lights.init");
 	check(ctx, fpt_pt_init(ctx, &o, &v, h.samples_dir, renderer.shard_pixels(), renderer.shard_count()), "PathTracer::init");
 	// Passes in flight behind the unchanged render(instance) calls: the library collects consecutive instances and renders them as one wavefront when
 	// `-batch N` of them are pending or when anything reads the frame (fpt_synchronize, fpt_to_rgba, fpt_filter, the gather ...).  The frame is
@@ -337,6 +357,7 @@ static void rebuild_emitters(RenderingContext& renderer, const char* who)
 	const fpt_rendering_context_view v = renderer.view(0);
 	const SceneArrays& h = renderer.get_host_scene();
 	check(ctx, fpt_synchronize(ctx), who);
+	if (renderer.lights_on_device()) { check(ctx, fpt_mesh_lights_update_device(ctx, &v.mesh), who); return; }          // all four tables, from the device mesh
 	check(ctx, fpt_mesh_lights_update(ctx, v.res_x * v.res_y, &h.mesh, h.textures, 0, nullptr), who);          // rebuilt only when an emitting triangle moved
 }
 void HipPathTracer::update_scene(RenderingContext& renderer) { rebuild_emitters(renderer, "PathTracer::update_scene"); }
@@ -408,7 +429,7 @@ void HipPSFPT::init(int argc, char** argv, RenderingContext& renderer)
 	fpt_context* ctx = renderer.get_hip_context();
 	const fpt_rendering_context_view v = renderer.view(0);
 	const SceneArrays& h = renderer.get_host_scene();
-	check(ctx, fpt_mesh_lights_init(ctx, v.res_x * v.res_y, &h.mesh, h.textures, 0), "mesh_lights.init");
+	renderer.init_mesh_lights("mesh_lights.init");
 	check(ctx, fpt_psfpt_init(ctx, &o, &p, &v, h.samples_dir, renderer.shard_pixels(), renderer.shard_count()), "PSFPT::init");
 	// tile sharding: the cache is shared by every pixel, so the ranks exchange the cells they touched after every pass (integer sums merged by key)
 	m_sharded = renderer.world_size() > 1;
@@ -467,7 +488,7 @@ void HipBPT::init(int argc, char** argv, RenderingContext& renderer)
 	fpt_context* ctx = renderer.get_hip_context();
 	const fpt_rendering_context_view v = renderer.view(0);
 	const SceneArrays& h = renderer.get_host_scene();
-	check(ctx, fpt_mesh_lights_init(ctx, v.res_x * v.res_y, &h.mesh, h.textures, 0), "mesh_lights.init");     // src/renderers/bpt.cu:53
+	renderer.init_mesh_lights("mesh_lights.init");     // src/renderers/bpt.cu:53
 	check(ctx, fpt_bpt_init(ctx, &o, &v, h.samples_dir, renderer.shard_pixels(), renderer.shard_count()), "BPT::init");
 	const bool several = renderer.world_size() > 1;
 	{

@@ -4,6 +4,7 @@
 //              [-benchmark file] [-save-intermediate] [PT flags: -pl/-bounces/-nee/-bsdf/-nee-alg mesh|vpl ...]
 //              [-data dir] [-device id] [-filtered | -shading-mode N]   (kFiltered = EAW-denoised output; the reference toggles it in the viewer)
 //              [-bvh quality|fast|trbvh]   the acceleration structure's build mode (fpt_rt_set_build_mode): host SAH, device radix tree, device Trbvh
+//              [-lights host|device]       who builds the emitter tables: the host from the host mesh (default), or the device from the device mesh (the same tables)
 //              [-gpus N]   one process per GPU of this node (forked here), image rows interleaved over the ranks, frame gathered to rank 0
 //                          over RCCL (fpt_gather_framebuffer); -pt and -bpt
 //   fermat_hip -diff a.tga b.tga
@@ -114,7 +115,8 @@ int main(int argc, char** argv)
 		std::fprintf(stderr, "options:\n  -i scene.obj|scene.fa  specify the input scene\n  -r int int             specify the resolution\n"
 		                     "  -a float               specify the aspect ratio\n  -c camera.txt          specify a camera file\n"
 		                     "  -pt                    use the PT renderer\n  -passes int            number of passes - 1\n  -o name                output image name\n"
-		                     "  -bvh quality|fast|trbvh  build mode of the acceleration structure (host SAH, device radix tree, device Trbvh)\n");
+		                     "  -bvh quality|fast|trbvh  build mode of the acceleration structure (host SAH, device radix tree, device Trbvh)\n"
+		                     "  -lights host|device      builder of the emitter tables (host mesh on host threads, device mesh on the device; FPT_LIGHTS_BUILD overrides)\n");
 		return 0;
 	}
 	// -gpus N: fork the other ranks BEFORE anything touches HIP or RCCL; rank 0 creates the RCCL id and hands it down one pipe per child

@@ -144,6 +144,10 @@ struct RenderingContext
 	uint8_t* m_d_rgba = nullptr;
 	uint32 m_build_mode = 0;          // `-bvh quality|fast|trbvh`: fpt_rt_set_build_mode (quality = the host SAH builder, the default; fast = Morton radix tree + collapse on the device;
 	                                  //  trbvh = the same radix tree restructured by treelets on the device before the collapse)
+	bool m_lights_device = false;     // `-lights host|device` (FPT_LIGHTS_BUILD overrides): who builds the emitter tables -- fpt_mesh_lights_init / _update from the host mesh (the default), or
+	                                  //  fpt_mesh_lights_init_device / _update_device from the device mesh, the same tables bit for bit
+	bool lights_on_device() const { return m_lights_device; }
+	void init_mesh_lights(const char* who);            // the renderers' init: the emitter tables with one VPL per pixel, by the builder chosen
 };
 
 // the MI355X path tracer behind RendererInterface (PathTracer, src/renderers/pathtracer.h:255-305)

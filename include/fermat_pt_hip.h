@@ -183,6 +183,13 @@ int fpt_mesh_lights_init(fpt_context* ctx, uint32_t n_vpls, const fpt_mesh_view*
  * arrays with MOVED vertices.  Rebuilds the tables -- as fpt_mesh_lights_init would -- when an emitting triangle moved, keeps them when only non-emitting geometry did
  * (the tables depend on nothing else of the vertex array); *rebuilt (may be NULL) says which. */
 int fpt_mesh_lights_update(fpt_context* ctx, uint32_t n_vpls, const fpt_mesh_view* h_mesh, const fpt_texture* h_textures, uint32_t instance, int* rebuilt);
+/* the tables of fpt_mesh_lights_init, built on the device from the DEVICE mesh view, bit for bit; h_mesh / h_textures are read for the static part only
+ * (materials, material indices, texture coordinates, texels) -- never their vertex_data.  A failure leaves the previous tables in place. */
+int fpt_mesh_lights_init_device(fpt_context* ctx, uint32_t n_vpls, const fpt_mesh_view* h_mesh, const fpt_texture* h_textures,
+                                const fpt_mesh_view* d_mesh, const fpt_texture* d_textures, uint32_t instance);
+/* vertices behind d_mesh moved: rebuild everything that follows them (all four tables, always -- no fingerprint, no stale inverse areas).  Needs a successful
+ * fpt_mesh_lights_init_device before it, whose n_vpls, instance, static part and d_textures it keeps. */
+int fpt_mesh_lights_update_device(fpt_context* ctx, const fpt_mesh_view* d_mesh);
 int fpt_mesh_lights_download(fpt_context* ctx, uint32_t* n_vpls, fpt_vpl* h_vpls, float* h_vpl_cdf, float* h_mesh_cdf, float* h_mesh_inv_area, float* norm);
 
 /* ---- renderer : PathTracer (src/renderers/pathtracer.h:255-305, pathtracer_impl.h:99-350) behind RendererInterface
