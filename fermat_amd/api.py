@@ -956,6 +956,14 @@ class Renderer:
         """fpt_mesh_lights_update_device: the device mesh's vertices moved (refit_geometry / rebuild_geometry): all four tables are rebuilt on the device"""
         self._check(self.L.fpt_mesh_lights_update_device(self.ctx, C.byref(self.view.mesh)))
 
+    def update_emitters(self, n_vpls=None):
+        """fpt_mesh_lights_update: the host mesh's vertices moved in place.  The tables are rebuilt (returns 1) unless the live ones were built on the host from this
+        mesh with this VPL count and no emitting triangle moved since (returns 0)"""
+        n = self.res[0] * self.res[1] if n_vpls is None else int(n_vpls)
+        rebuilt = C.c_int(-1)
+        self._check(self.L.fpt_mesh_lights_update(self.ctx, C.c_uint32(n), C.byref(self.h_mesh), C.byref(self._h_tex), C.c_uint32(0), C.byref(rebuilt)))
+        return rebuilt.value
+
     def reinit_emitters(self, n_vpls):
         """fpt_mesh_lights_init again with another VPL count (the probe's emitter tables)"""
         self._check(self.L.fpt_mesh_lights_init(self.ctx, C.c_uint32(n_vpls), C.byref(self.h_mesh), C.byref(self._h_tex), C.c_uint32(0)))

@@ -97,7 +97,7 @@ int fpt_rt_create_geometry(fpt_context* ctx, uint32_t tri_count, const int32_t* 
 			FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));          // launches still reading the old tree
 			if (build_acceleration_device(ctx, tri_count, d_idx, vertex_count, d_vtx, trace_stack_entries(), mode))
 			{
-				ctx->emitter_generation++;
+				ctx->scene.changed();
 				if (std::getenv("FPT_BVH_TIMERS")) std::fprintf(stderr, "fpt_rt_create_geometry: built on the device in %.3f ms\n", (wall_seconds() - t0) * 1e3);
 				return;
 			}
@@ -115,7 +115,7 @@ int fpt_rt_create_geometry(fpt_context* ctx, uint32_t tri_count, const int32_t* 
 			FPT_HIP_CHECK(hipMemcpyAsync(d_nodes, built.nodes8.data(), built.nodes8.size() * sizeof(BvhNode8), hipMemcpyHostToDevice, ctx->stream));
 			FPT_HIP_CHECK(hipMemcpyAsync(d_records, built.tris8.data(), built.tris8.size() * sizeof(BvhTriangle), hipMemcpyHostToDevice, ctx->stream));
 			FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream)); });
-		ctx->emitter_generation++;          // new geometry: the VPLs' tabulated light points are stale
+		ctx->scene.changed();          // new geometry: the VPLs' tabulated light points are stale
 		if (std::getenv("FPT_BVH_TIMERS")) std::fprintf(stderr, "fpt_rt_create_geometry: mesh to the host %.3f s, build %.3f, tree to the device %.3f\n", t1 - t0, t2 - t1, wall_seconds() - t2);
 	});
 }
@@ -144,7 +144,7 @@ int fpt_rt_download_bvh(fpt_context* ctx, uint32_t* h_nodes, float* h_records)
 // the buffers behind a view's mesh / textures were edited IN PLACE (a material colour, a texture coordinate, texels): the derived device tables -- shading
 // records, the VPLs' light points -- are rebuilt at the next render call.  (The VPL distribution itself follows only fpt_mesh_lights_init, as in the reference.)
 int fpt_mesh_invalidate(fpt_context* ctx)
-{ return guarded(ctx, [&] { flush_deferred(ctx); ctx->emitter_generation++; }); }
+{ return guarded(ctx, [&] { flush_deferred(ctx); ctx->scene.changed(); }); }
 
 static void rt_launch(fpt_context* ctx, uint32_t count, const fpt_ray* d_rays, fpt_hit* d_hits, uint32_t* d_bits, bool shadow, bool counted)
 {
@@ -245,31 +245,33 @@ int fpt_mesh_lights_init(fpt_context* ctx, uint32_t n_vpls, const fpt_mesh_view*
 {
 	return guarded(ctx, [&] { flush_deferred(ctx);
 		require(h_mesh != nullptr, "fpt_mesh_lights_init: null mesh");
+		require(h_mesh->num_triangles == 0 || (h_mesh->material_indices && h_mesh->materials && h_mesh->vertex_indices && h_mesh->vertex_data), "fpt_mesh_lights_init: the host mesh view has null arrays");
 		const double t0 = wall_seconds();
-		build_emitter_tables(n_vpls, *h_mesh, h_textures, instance, ctx->emitters);
+		// EmitterSet's contract (fpt_host.h): into the workspace -- whatever the builder throws, the live tables are as they were -- then not valid from the first upload to the commit
+		EmitterSet& E = ctx->emitters; EmitterTables& built = E.host_build;
+		build_emitter_tables(n_vpls, *h_mesh, h_textures, instance, built);
+		const EmitterSet::Built how{ n_vpls, instance, true, { h_mesh->vertex_indices, h_mesh->materials, h_mesh->material_indices, h_textures }, emitter_fingerprint(*h_mesh, h_textures) };
 		const double t1 = wall_seconds();
-		const EmitterTables& e = ctx->emitters;
-		ctx->d_mesh_cdf.upload(e.mesh_cdf.data(), e.mesh_cdf.size(), ctx->stream);
-		ctx->d_mesh_inv_area.upload(e.mesh_inv_area.data(), e.mesh_inv_area.size(), ctx->stream);
-		ctx->d_vpl_cdf.upload(e.vpl_cdf.data(), e.vpl_cdf.size(), ctx->stream);
-		ctx->d_vpls.upload(e.vpls.data(), e.vpls.size(), ctx->stream);
-		ctx->has_emitters = true; ctx->emitter_generation++;
-		ctx->emitters_fingerprint = emitter_fingerprint(*h_mesh, h_textures); ctx->emitters_n_vpls = n_vpls; ctx->emitters_instance = instance;
-		ctx->emitters_mesh_identity[0] = h_mesh->vertex_indices; ctx->emitters_mesh_identity[1] = h_mesh->materials; ctx->emitters_mesh_identity[2] = h_mesh->material_indices; ctx->emitters_mesh_identity[3] = h_textures;
+		E.valid = false;
+		E.mesh_cdf.upload(built.mesh_cdf.data(), built.mesh_cdf.size(), ctx->stream);
+		E.mesh_inv_area.upload(built.mesh_inv_area.data(), built.mesh_inv_area.size(), ctx->stream);
+		E.vpl_cdf.upload(built.vpl_cdf.data(), built.vpl_cdf.size(), ctx->stream);
+		E.vpls.upload(built.vpls.data(), built.vpls.size(), ctx->stream);
+		E.commit(built.n_prims, built.n_vpls, built.norm, how, ctx->scene);
 		if (std::getenv("FPT_BVH_TIMERS")) std::fprintf(stderr, "fpt_mesh_lights_init: tables %.3f s, to the device %.3f\n", t1 - t0, wall_seconds() - t1);
 	});
 }
 // update_scene's form of fpt_mesh_lights_init: VERTICES of the same mesh moved (same index / material arrays, same textures, same n_vpls and instance).  The tables are a
 // function of the emitting triangles' positions only, so they are rebuilt when one of those moved (*rebuilt = 1) and left alone otherwise (*rebuilt = 0; the derived
-// device tables -- shading records, light points -- still follow the geometry through fpt_rt_refit_geometry / fpt_rt_create_geometry).
+// device tables -- shading records, light points -- still follow the geometry through fpt_rt_refit_geometry / fpt_rt_create_geometry).  Only a set the host built has a
+// fingerprint to compare with: after fpt_mesh_lights_init_device the first call rebuilds.
 int fpt_mesh_lights_update(fpt_context* ctx, uint32_t n_vpls, const fpt_mesh_view* h_mesh, const fpt_texture* h_textures, uint32_t instance, int* rebuilt)
 {
 	if (rebuilt) *rebuilt = 1;
-	if (ctx && h_mesh && ctx->has_emitters && n_vpls == ctx->emitters_n_vpls && instance == ctx->emitters_instance && ctx->emitters_mesh_identity[0] == h_mesh->vertex_indices &&
-	    ctx->emitters_mesh_identity[1] == h_mesh->materials && ctx->emitters_mesh_identity[2] == h_mesh->material_indices && ctx->emitters_mesh_identity[3] == h_textures)
+	if (ctx && h_mesh && ctx->emitters.valid && ctx->emitters.built.is_host_build_of(n_vpls, instance, *h_mesh, h_textures))
 	{
 		bool same = false;
-		const int st = guarded(ctx, [&] { same = emitter_fingerprint(*h_mesh, h_textures) == ctx->emitters_fingerprint; });
+		const int st = guarded(ctx, [&] { same = emitter_fingerprint(*h_mesh, h_textures) == ctx->emitters.built.fingerprint; });
 		if (st != 0) return st;
 		if (same) { if (rebuilt) *rebuilt = 0; return 0; }
 	}
@@ -295,13 +297,13 @@ int fpt_mesh_lights_update_device(fpt_context* ctx, const fpt_mesh_view* d_mesh)
 int fpt_mesh_lights_download(fpt_context* ctx, uint32_t* n_vpls, fpt_vpl* h_vpls, float* h_vpl_cdf, float* h_mesh_cdf, float* h_mesh_inv_area, float* norm)
 {
 	return guarded(ctx, [&] {
-		require(ctx->has_emitters, "fpt_mesh_lights_download: mesh lights not initialised");
-		const EmitterTables& e = ctx->emitters;
+		const EmitterSet& e = ctx->emitters;
+		require(e.valid, "fpt_mesh_lights_download: mesh lights not initialised");
 		if (n_vpls) *n_vpls = e.n_vpls;
-		if (h_vpls) ctx->d_vpls.download(h_vpls, e.n_vpls, ctx->stream);
-		if (h_vpl_cdf) ctx->d_vpl_cdf.download(h_vpl_cdf, e.n_vpls, ctx->stream);
-		if (h_mesh_cdf) ctx->d_mesh_cdf.download(h_mesh_cdf, e.n_prims, ctx->stream);
-		if (h_mesh_inv_area) ctx->d_mesh_inv_area.download(h_mesh_inv_area, e.n_prims, ctx->stream);
+		if (h_vpls) e.vpls.download(h_vpls, e.n_vpls, ctx->stream);
+		if (h_vpl_cdf) e.vpl_cdf.download(h_vpl_cdf, e.n_vpls, ctx->stream);
+		if (h_mesh_cdf) e.mesh_cdf.download(h_mesh_cdf, e.n_prims, ctx->stream);
+		if (h_mesh_inv_area) e.mesh_inv_area.download(h_mesh_inv_area, e.n_prims, ctx->stream);
 		if (norm) *norm = e.norm;
 	});
 }
@@ -326,7 +328,7 @@ int fpt_pt_init(fpt_context* ctx, const fpt_pt_options* opts, const fpt_renderin
 		ctx->seq_dims = 6 * (opts->max_path_length + 1); ctx->seq_tile = 256;
 		ctx->d_shifts.upload(ctx->h_shifts.data(), ctx->h_shifts.size(), ctx->stream);
 		ctx->d_samples.alloc(ctx->h_shifts.size());
-		if (ctx->has_emitters && ctx->emitters.n_vpls == 0) ctx->opt.nee_type = 0;     // :165-166
+		if (ctx->emitters.valid && ctx->emitters.n_vpls == 0) ctx->opt.nee_type = 0;     // :165-166
 		ctx->defer_max = 1;
 		ctx->pt_ready = true;
 	});
@@ -374,9 +376,10 @@ int fpt_sequence_device_view(fpt_context* ctx, const float** d_shifts, uint32_t*
 int fpt_mesh_lights_device_view(fpt_context* ctx, fpt_mesh_lights_view* out)
 {
 	return guarded(ctx, [&] {
-		require(ctx->has_emitters && out, "fpt_mesh_lights_device_view: fpt_mesh_lights_init has not been called");
-		out->d_mesh_cdf = ctx->d_mesh_cdf.ptr; out->d_mesh_inv_area = ctx->d_mesh_inv_area.ptr; out->n_prims = ctx->emitters.n_prims;
-		out->d_vpls = ctx->d_vpls.ptr; out->d_vpl_cdf = ctx->d_vpl_cdf.ptr; out->n_vpls = ctx->emitters.n_vpls; out->norm = ctx->emitters.norm;
+		const EmitterSet& e = ctx->emitters;
+		require(e.valid && out, "fpt_mesh_lights_device_view: fpt_mesh_lights_init has not been called");
+		out->d_mesh_cdf = e.mesh_cdf.ptr; out->d_mesh_inv_area = e.mesh_inv_area.ptr; out->n_prims = e.n_prims;
+		out->d_vpls = e.vpls.ptr; out->d_vpl_cdf = e.vpl_cdf.ptr; out->n_vpls = e.n_vpls; out->norm = e.norm;
 	});
 }
 int fpt_to_rgba(fpt_context* ctx, const fpt_rendering_context_view* view, uint8_t* d_rgba)
@@ -484,14 +487,14 @@ const ShadeRecord* ensure_shade_records(fpt_context* ctx, const fpt_rendering_co
 {
 	const uint32_t n = view->mesh.num_triangles;
 	if (n == 0) return nullptr;
-	const bool fresh = ctx->shade_records_generation == ctx->emitter_generation && ctx->d_shade_records.count == size_t(n) &&
+	const bool fresh = ctx->shade_records_generation == ctx->scene.value && ctx->d_shade_records.count == size_t(n) &&
 	                   same_mesh(ctx->shade_records_mesh, view->mesh);
 	if (!fresh)
 	{
 		ctx->d_shade_records.alloc(n);
 		launch_shade_records(view->mesh, ctx->d_shade_records.ptr, s);
 		FPT_HIP_CHECK(hipGetLastError());
-		ctx->shade_records_generation = ctx->emitter_generation; ctx->shade_records_mesh = view->mesh;
+		ctx->shade_records_generation = ctx->scene.value; ctx->shade_records_mesh = view->mesh;
 	}
 	return ctx->d_shade_records.ptr;
 }
@@ -499,14 +502,14 @@ const float4* ensure_vpl_points(fpt_context* ctx, const fpt_rendering_context_vi
 {
 	const uint32_t n = ctx->emitters.n_vpls;
 	if (n == 0) return nullptr;
-	const bool fresh = ctx->vpl_points_generation == ctx->emitter_generation && ctx->d_vpl_points.count == VPL_POINT_STRIDE * size_t(n) &&
+	const bool fresh = ctx->vpl_points_generation == ctx->scene.value && ctx->d_vpl_points.count == VPL_POINT_STRIDE * size_t(n) &&
 	                   same_mesh(ctx->vpl_points_mesh, view->mesh) && ctx->vpl_points_textures == view->d_textures;
 	if (!fresh)
 	{
 		ctx->d_vpl_points.alloc(VPL_POINT_STRIDE * size_t(n));
 		launch_vpl_points(emitter_view(ctx, true), view->mesh, view->d_textures, ctx->d_vpl_points.ptr, s);
 		FPT_HIP_CHECK(hipGetLastError());
-		ctx->vpl_points_generation = ctx->emitter_generation; ctx->vpl_points_mesh = view->mesh; ctx->vpl_points_textures = view->d_textures;
+		ctx->vpl_points_generation = ctx->scene.value; ctx->vpl_points_mesh = view->mesh; ctx->vpl_points_textures = view->d_textures;
 	}
 	return ctx->d_vpl_points.ptr;
 }
@@ -703,7 +706,7 @@ static void render_passes_impl(fpt_context* ctx, uint32_t instance, uint32_t n_p
 		require(ctx->store.serves(n_passes, false, view->dir_lights_count != 0),
 		        "fpt_pt_render_batch: n_passes exceeds the batch capacity set by fpt_pt_set_batch (or the view has directional lights and the storage was sized without them): call fpt_pt_set_batch with this view");
 		require(ctx->tree.valid, "fpt_pt_render: create_geometry has not been called");
-		require(ctx->has_emitters, "fpt_pt_render: fpt_mesh_lights_init has not been called");
+		require(ctx->emitters.valid, "fpt_pt_render: fpt_mesh_lights_init has not been called");
 		hipStream_t s = ctx->stream;
 		const FrameBufferDev real_fb = fb_dev(view->fb);
 		const bool batched = n_passes > 1;       // batched mode accumulates into per-pass planes and merges them in order at the end
@@ -1041,7 +1044,7 @@ int fpt_debug_vertex(fpt_context* ctx, const fpt_rendering_context_view* view, i
 		if (n && op == 3 && (!d_textures || !n_textures)) throw std::runtime_error("fpt_debug_vertex: the texture op needs textures");
 		if (n && op != 0 && op != 3 && op != 7 && op != 9 && (view->mesh.num_triangles == 0 || !view->mesh.vertex_data || !view->mesh.materials))
 			throw std::runtime_error("fpt_debug_vertex: this op needs the view's mesh");
-		if (n && (op == 4 || op == 5 || op == 6 || op == 8) && !ctx->has_emitters) throw std::runtime_error("fpt_debug_vertex: no emitter tables (fpt_mesh_lights_init)");
+		if (n && (op == 4 || op == 5 || op == 6 || op == 8) && !ctx->emitters.valid) throw std::runtime_error("fpt_debug_vertex: no emitter tables (fpt_mesh_lights_init)");
 		if (rec_stride != 0 && rec_stride != 48) throw std::runtime_error("fpt_debug_vertex: rec_stride must be 0 or 48");
 		const bool vpl = (flags & 1u) != 0;
 		EmitterView em = emitter_view(ctx, vpl);

@@ -104,7 +104,7 @@ int fpt_bpt_init(fpt_context* ctx, const fpt_bpt_options* opts, const fpt_render
 		require(opts && view, "fpt_bpt_init: null argument");
 		require(opts->max_path_length >= 1 && opts->max_path_length <= 15, "fpt_bpt_init: max_path_length out of range [1,15] (the s,t technique ids are 4-bit)");
 		require(uint64_t(view->res_x) * view->res_y < (1ull << 24), "fpt_bpt_init: light-vertex ids hold 24-bit path indices");
-		require(ctx->has_emitters, "fpt_bpt_init: fpt_mesh_lights_init has not been called");
+		require(ctx->emitters.valid, "fpt_bpt_init: fpt_mesh_lights_init has not been called");
 		require(!opts->use_vpls || ctx->emitters.n_vpls != 0, "fpt_bpt_init: -use-vpls needs a VPL set");
 		// light_primary_kernel reads vpls[pixel index]: the reference allocates one VPL per light path by construction (src/renderers/bpt.cu:53)
 		require(!opts->use_vpls || size_t(ctx->emitters.n_vpls) >= size_t(view->res_x) * view->res_y, "fpt_bpt_init: -use-vpls needs one VPL per pixel (fpt_mesh_lights_init with n_vpls >= res_x * res_y)");
@@ -295,6 +295,7 @@ static void render_impl(fpt_context* ctx, uint32_t instance, uint32_t n_passes, 
 	fpt_context::BptState& b = ctx->bpt;
 	require(b.ready, "fpt_bpt_render: fpt_bpt_init has not been called");
 	require(ctx->tree.valid, "fpt_bpt_render: create_geometry has not been called");
+	require(ctx->emitters.valid, "fpt_bpt_render: fpt_mesh_lights_init has not been called");
 	require(view->res_x * view->res_y == b.n_paths, "fpt_bpt_render: the view's resolution differs from fpt_bpt_init's");
 	require(n_passes >= 1 && n_passes <= b.max_batch, "fpt_bpt_render_batch: more passes than fpt_bpt_set_batch sized the storage for");
 	require(b.pending_n == 0, "fpt_bpt_render: the previous batch's splats have not been resolved (fpt_bpt_resolve_splats)");

@@ -192,7 +192,7 @@ void refit_acceleration_device(fpt_context* ctx, uint32_t tri_count, const int32
 			hipLaunchKernelGGL(refit_level_kernel, dim3((count + 127u) / 128u), dim3(128), 0, s, T.nodes.ptr, node_box, tri_box, level_begin[L], count, T.refit_scan.ptr);
 	FPT_HIP_CHECK(hipGetLastError());
 	std::memcpy(&T.info.scene_mag, &scan[0], 4);
-	ctx->emitter_generation++;          // shading records and light points were tabulated from the old vertices
+	ctx->scene.changed();          // shading records and light points were tabulated from the old vertices
 	// a non-finite vertex makes a box that cannot be quantised (the host refit throws there); the level kernels flag it.  Reading the flag waits for the refit (a
 	// millisecond): the call returns with the tree in place or with the error, like the host refit did
 	T.refit_scan.download(scan, 2, s);

@@ -38,6 +38,7 @@ struct DeviceArray
 		count = n;
 	}
 	void upload(const T* h, size_t n, hipStream_t s) { alloc(n); if (n) { FPT_HIP_CHECK(hipMemcpyAsync(ptr, h, n * sizeof(T), hipMemcpyHostToDevice, s)); FPT_HIP_CHECK(hipStreamSynchronize(s)); } }
+	void swap(DeviceArray& o) { std::swap(ptr, o.ptr); std::swap(count, o.count); }
 	void download(T* h, size_t n, hipStream_t s) const { if (n) { FPT_HIP_CHECK(hipMemcpyAsync(h, ptr, n * sizeof(T), hipMemcpyDeviceToHost, s)); FPT_HIP_CHECK(hipStreamSynchronize(s)); } }
 	DeviceArray() = default; DeviceArray(const DeviceArray&) = delete; DeviceArray& operator=(const DeviceArray&) = delete;
 };
@@ -58,7 +59,7 @@ struct EmitterTables
 	std::vector<float> mesh_cdf, mesh_inv_area, vpl_cdf;
 	std::vector<fpt_vpl> vpls;
 	float norm = 0.0f;
-	uint32_t n_prims = 0, n_vpls = 0;          // the tables' sizes, set by whoever built them: the device builder (fpt_lights_device.hip) leaves the host vectors empty
+	uint32_t n_prims = 0, n_vpls = 0;          // the tables' sizes: n_vpls = 0 for a scene without emitters, whatever was asked for
 };
 void build_emitter_tables(uint32_t n_vpls, const fpt_mesh_view& h_mesh, const fpt_texture* h_textures, uint32_t instance, EmitterTables& out);
 // what the tables take from materials, texture coordinates and texels alone (fpt_lights.cpp): the per-triangle factor of the area and the random stream behind it
@@ -68,12 +69,54 @@ enum : uint32_t { LFSR_JUMPS = 41 };
 void lfsr_jump_matrices(uint32_t* out);          // LFSR_JUMPS x 32 words
 uint64_t emitter_fingerprint(const fpt_mesh_view& h_mesh, const fpt_texture* h_textures);          // of the emitting triangles' positions
 
-// The device builder of the emitter tables (fpt_lights_device.hip) and what it keeps between rebuilds: the static part of the last fpt_mesh_lights_init_device, the
-// stream's jump matrices, the tables under construction (swapped with the context's when a build succeeded, so a rebuild of the same sizes allocates nothing) and scratch.
+// What stamps the tables derived from the scene (the triangles' shading records, the VPLs' light points: ensure_shade_records, ensure_vpl_points): changed() when geometry,
+// emitters or the buffers behind the mesh changed -- EmitterSet::commit, whoever builds or refits the AccelTree (fpt_api.cpp, fpt_build.hip), fpt_mesh_invalidate
+struct SceneGeneration { uint64_t value = 1; void changed() { ++value; } };
+
+// The emitter tables the kernels sample (EmitterView) and their one owner.  Whoever builds them (the host builder through fpt_mesh_lights_init, the device builder in
+// fpt_lights_device.hip) keeps this contract:
+//   1. Arrays, counts and `norm` agree whenever `valid` is true, and everything that reads the tables checks `valid` first: emitter_view (an empty view otherwise),
+//      fpt_mesh_lights_download, fpt_mesh_lights_device_view, the render entry points of the three renderers, fpt_bpt_init and fpt_debug_vertex.
+//   2. A failure detected before the live arrays are touched (a null mesh, null arrays, a host builder that throws, any throw of the device builder before its last
+//      synchronise) leaves the set exactly as it was, the old tables usable: a build works in storage of its own (`host_build`, the device builder's `next` arrays).
+//   3. From the first write to the live arrays to the commit, `valid` is false.  A throw in between leaves the context with NO emitters: every later render answers
+//      "fpt_mesh_lights_init has not been called".
+//   4. commit() ends every successful build on either route: nothing else writes the counts, `norm` or `built`, sets `valid`, or stales the tables derived from the set.
+//   5. Replacing adds no synchronisation, no allocation when the sizes did not change (DeviceArray::alloc, DeviceArray::swap) and, on the host route, no second copy of
+//      the tables on the device.
+struct EmitterSet
+{
+	DeviceArray<float> mesh_cdf, mesh_inv_area, vpl_cdf; DeviceArray<fpt_vpl> vpls;
+	uint32_t n_prims = 0, n_vpls = 0; float norm = 0.0f;      // n_vpls: the VPL set's actual size, 0 for a scene without emitters
+	bool valid = false;
+	// how the live tables were built: what fpt_mesh_lights_update compares a request with.  `source` (index, material and material-index arrays, textures) and
+	// `fingerprint` (of the emitting triangles' positions) describe the host mesh a host-built set was made from; a device-built set has neither
+	struct Built
+	{
+		uint32_t requested_vpls = 0, instance = 0; bool on_host = false;
+		const void* source[4] = { nullptr, nullptr, nullptr, nullptr }; uint64_t fingerprint = 0;
+		bool is_host_build_of(uint32_t n, uint32_t inst, const fpt_mesh_view& m, const fpt_texture* t) const
+		{ return on_host && requested_vpls == n && instance == inst && source[0] == m.vertex_indices && source[1] == m.materials && source[2] == m.material_indices && source[3] == t; }
+	} built;
+	EmitterTables host_build;                       // the host route's workspace: written by the host builder, read by nothing once its arrays are uploaded
+	// the device route's part 3: the builder's finished tables become the live ones, the old ones its next workspace; a set without VPLs keeps no VPL arrays
+	void adopt(DeviceArray<float>& next_mesh_cdf, DeviceArray<float>& next_mesh_inv_area, DeviceArray<float>& next_vpl_cdf, DeviceArray<fpt_vpl>& next_vpls, bool with_vpls)
+	{
+		valid = false;
+		mesh_cdf.swap(next_mesh_cdf); mesh_inv_area.swap(next_mesh_inv_area);
+		if (with_vpls) { vpl_cdf.swap(next_vpl_cdf); vpls.swap(next_vpls); } else { vpl_cdf.release(); vpls.release(); }
+	}
+	void commit(uint32_t prims, uint32_t vpl_count, float vpl_norm, const Built& how, SceneGeneration& scene)
+	{ n_prims = prims; n_vpls = vpl_count; norm = vpl_norm; built = how; valid = true; scene.changed(); }
+};
+
+// The device builder of the emitter tables (fpt_lights_device.hip) and what it keeps between rebuilds: the parameters of the last successful fpt_mesh_lights_init_device
+// (static part `e`, one entry per triangle; VPL count; stream start; textures), with which fpt_mesh_lights_update_device builds again whatever fpt_mesh_lights_init made of
+// the live set in between; the jump matrices; the tables under construction (EmitterSet::adopt swaps them with the live ones: a rebuild of the same sizes allocates nothing); scratch.
 struct DeviceEmitterBuilder
 {
 	bool ready = false;                                 // fpt_mesh_lights_init_device succeeded: fpt_mesh_lights_update_device may follow
-	uint32_t n_vpls = 0, n_prims = 0, state = 0, scramble = 0;
+	uint32_t n_vpls = 0, instance = 0, state = 0, scramble = 0;
 	const fpt_texture* d_textures = nullptr;
 	DeviceArray<float> e; DeviceArray<uint32_t> jumps;
 	DeviceArray<float> next_mesh_cdf, next_mesh_inv_area, next_vpl_cdf; DeviceArray<fpt_vpl> next_vpls;
@@ -242,16 +285,13 @@ struct fpt_context
 	fpt::DeviceArray<float> d_shifts, d_samples;
 
 	// emitters
-	fpt::EmitterTables emitters;
-	fpt::DeviceArray<float> d_mesh_cdf, d_mesh_inv_area, d_vpl_cdf;
-	fpt::DeviceArray<fpt_vpl> d_vpls;
-	bool has_emitters = false;
+	fpt::EmitterSet emitters;                           // the tables the kernels sample and everything that describes them
 	fpt::DeviceEmitterBuilder emitter_builder;
-	uint64_t emitters_fingerprint = 0; uint32_t emitters_n_vpls = 0, emitters_instance = 0; const void* emitters_mesh_identity[4] = { nullptr, nullptr, nullptr, nullptr };
-	// the VPLs' tabulated light points (EmitterView::vpl_points): built from the view's mesh / materials / textures, so rebuilt when fpt_mesh_lights_init or
-	// fpt_rt_create_geometry ran (emitter_generation) or a view names other buffers
+	// the tables derived from the view's mesh / materials / textures and the emitter set -- the triangles' shading records, the VPLs' tabulated light points
+	// (EmitterView::vpl_points) -- are rebuilt when the scene changed under them or a view names other buffers
+	fpt::SceneGeneration scene;
 	fpt::DeviceArray<fpt::ShadeRecord> d_shade_records; uint64_t shade_records_generation = 0; fpt_mesh_view shade_records_mesh{};      // ShadeRecord (fpt_shading.h): one per triangle of the view's mesh
-	fpt::DeviceArray<float4> d_vpl_points; uint64_t emitter_generation = 1, vpl_points_generation = 0; fpt_mesh_view vpl_points_mesh{}; const fpt_texture* vpl_points_textures = nullptr;
+	fpt::DeviceArray<float4> d_vpl_points; uint64_t vpl_points_generation = 0; fpt_mesh_view vpl_points_mesh{}; const fpt_texture* vpl_points_textures = nullptr;
 
 	// renderer
 	fpt_pt_options opt{};
@@ -460,8 +500,10 @@ inline fpt::TraceParams trace_params(fpt_context* ctx, fpt::PassCounters& cnt)
 inline fpt::EmitterView emitter_view(fpt_context* ctx, bool use_vpls)
 {
 	fpt::EmitterView em; std::memset(&em, 0, sizeof(em));
-	em.n_prims = ctx->emitters.n_prims; em.prims_cdf = ctx->d_mesh_cdf.ptr; em.prims_inv_area = ctx->d_mesh_inv_area.ptr;
-	em.n_vpls = use_vpls ? ctx->emitters.n_vpls : 0u; em.vpls = use_vpls ? ctx->d_vpls.ptr : nullptr; em.norm = ctx->emitters.norm;
+	const fpt::EmitterSet& E = ctx->emitters;
+	if (!E.valid) return em;                            // no tables: the render entry points refuse before they get here, fpt_debug_vertex's other ops sample nothing
+	em.n_prims = E.n_prims; em.prims_cdf = E.mesh_cdf.ptr; em.prims_inv_area = E.mesh_inv_area.ptr;
+	em.n_vpls = use_vpls ? E.n_vpls : 0u; em.vpls = use_vpls ? E.vpls.ptr : nullptr; em.norm = E.norm;
 	return em;
 }
 

@@ -204,7 +204,6 @@ __global__ void __launch_bounds__(kBlock) gather_kernel(const fpt_vpl* __restric
 }
 
 inline uint32_t blocks_for(uint32_t n) { return uint32_t((uint64_t(n) + kBlock - 1) / kBlock); }
-template <typename T> void swap_arrays(DeviceArray<T>& a, DeviceArray<T>& b) { std::swap(a.ptr, b.ptr); std::swap(a.count, b.count); }
 
 // carves the scratch block: sizes in size_t, every array on a 256-byte boundary
 struct Carver
@@ -222,7 +221,7 @@ void build_on_device(fpt_context* ctx, const fpt_mesh_view& mesh)
 {
 	DeviceEmitterBuilder& B = ctx->emitter_builder;
 	hipStream_t s = ctx->stream;
-	const uint32_t nt = B.n_prims, n = B.n_vpls;
+	const uint32_t nt = uint32_t(B.e.count), n = B.n_vpls;
 	require(uint32_t(mesh.num_triangles) == nt, "fpt_mesh_lights_*_device: the device mesh has another number of triangles than the static part was built for");
 	require(nt == 0 || (mesh.vertex_indices && mesh.vertex_data && mesh.material_indices && mesh.materials), "fpt_mesh_lights_*_device: the device mesh view has null arrays");
 	const bool timers = std::getenv("FPT_BVH_TIMERS") != nullptr;
@@ -338,14 +337,8 @@ void build_on_device(fpt_context* ctx, const fpt_mesh_view& mesh)
 	}
 	FPT_HIP_CHECK(hipStreamSynchronize(s));          // the last step succeeded: from here on nothing throws
 	if (timers) t_phase[4] = wall_seconds() - t_mark;
-	swap_arrays(ctx->d_mesh_cdf, B.next_mesh_cdf); swap_arrays(ctx->d_mesh_inv_area, B.next_mesh_inv_area);
-	if (n_out) { swap_arrays(ctx->d_vpl_cdf, B.next_vpl_cdf); swap_arrays(ctx->d_vpls, B.next_vpls); }
-	else { ctx->d_vpl_cdf.release(); ctx->d_vpls.release(); }          // no emitters: the VPL set is empty, as the host builder's
-	EmitterTables& e = ctx->emitters;
-	e.mesh_cdf.clear(); e.mesh_inv_area.clear(); e.vpl_cdf.clear(); e.vpls.clear();
-	e.n_prims = nt; e.n_vpls = n_out; e.norm = lit ? norm : 0.0f;
-	ctx->has_emitters = true; ctx->emitter_generation++;
-	ctx->emitters_mesh_identity[0] = nullptr;          // fpt_mesh_lights_update's fingerprint is not of these tables: it rebuilds
+	ctx->emitters.adopt(B.next_mesh_cdf, B.next_mesh_inv_area, B.next_vpl_cdf, B.next_vpls, n_out != 0);          // no emitters: the VPL set is empty, as the host builder's
+	ctx->emitters.commit(nt, n_out, lit ? norm : 0.0f, EmitterSet::Built{ n, B.instance, false }, ctx->scene);
 	if (timers)
 		std::fprintf(stderr, "build_emitter_tables (device): triangle CDF %.3f ms, first draw %.3f, norm + VPL CDF %.3f, resampling %.3f, Morton order %.3f (%u triangles, %u emitters, %u VPLs)\n",
 		             1e3 * t_phase[0], 1e3 * t_phase[1], 1e3 * t_phase[2], 1e3 * t_phase[3], 1e3 * t_phase[4], nt, n_emitters, n_out);
@@ -370,7 +363,7 @@ void emitters_init_device(fpt_context* ctx, uint32_t n_vpls, const fpt_mesh_view
 		lfsr_jump_matrices(J.data());
 		B.jumps.upload(J.data(), J.size(), ctx->stream);
 	}
-	B.n_vpls = n_vpls; B.n_prims = uint32_t(h_mesh.num_triangles); B.state = fixed.state; B.scramble = fixed.scramble; B.d_textures = d_textures;
+	B.n_vpls = n_vpls; B.instance = instance; B.state = fixed.state; B.scramble = fixed.scramble; B.d_textures = d_textures;
 	if (std::getenv("FPT_BVH_TIMERS")) std::fprintf(stderr, "fpt_mesh_lights_init_device: static part %.3f ms\n", 1e3 * (wall_seconds() - t0));
 	build_on_device(ctx, d_mesh);
 	B.ready = true;

@@ -125,7 +125,8 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 {
 		fpt_context::PsfState& ps = ctx->psf;
 		require(ps.ready && ctx->pt_ready, "fpt_psfpt_render: fpt_psfpt_init has not been called");
-		require(ctx->tree.valid && ctx->has_emitters, "fpt_psfpt_render: geometry / mesh lights are not initialised");
+		require(ctx->tree.valid, "fpt_psfpt_render: create_geometry has not been called");
+		require(ctx->emitters.valid, "fpt_psfpt_render: fpt_mesh_lights_init has not been called");
 		ps.rendered = true;
 		const bool batched = n_passes > 1;
 		require(!batched || !ps.sharded, "fpt_psfpt_render_batch: a sharded context renders one pass at a time");

@@ -181,7 +181,8 @@ int fpt_mesh_invalidate(fpt_context* ctx);
 int fpt_mesh_lights_init(fpt_context* ctx, uint32_t n_vpls, const fpt_mesh_view* h_mesh, const fpt_texture* h_textures, uint32_t instance);
 /* the renderer's update_scene after RenderingContext::update_model (the reference leaves it as "TODO: update m_mesh_lights if needed", src/renderer.cu:1011): the same mesh
  * arrays with MOVED vertices.  Rebuilds the tables -- as fpt_mesh_lights_init would -- when an emitting triangle moved, keeps them when only non-emitting geometry did
- * (the tables depend on nothing else of the vertex array); *rebuilt (may be NULL) says which. */
+ * (the tables depend on nothing else of the vertex array); *rebuilt (may be NULL) says which.  Tables that fpt_mesh_lights_init_device built are always rebuilt.
+ * Both calls refuse a NULL mesh or a view with NULL arrays and then leave the previous tables in place; a failure while the new tables are uploaded leaves none. */
 int fpt_mesh_lights_update(fpt_context* ctx, uint32_t n_vpls, const fpt_mesh_view* h_mesh, const fpt_texture* h_textures, uint32_t instance, int* rebuilt);
 /* the tables of fpt_mesh_lights_init, built on the device from the DEVICE mesh view, bit for bit; h_mesh / h_textures are read for the static part only
  * (materials, material indices, texture coordinates, texels) -- never their vertex_data.  A failure leaves the previous tables in place. */
