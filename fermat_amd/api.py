@@ -90,6 +90,7 @@ class EawParams(C.Structure):
 
 # ShadingMode (src/renderer_view.h:61-76) and FilterOp (src/filters.h:44-57)
 BUILD_QUALITY, BUILD_FAST, BUILD_TRBVH = 0, 1, 2          # fpt_rt_set_build_mode / Renderer.set_build_mode
+INTERSECTOR_MT, INTERSECTOR_WATERTIGHT = 0, 1             # fpt_rt_set_intersector / Renderer.set_intersector
 SHADING_SHADED, SHADING_UV, SHADING_ALBEDO, SHADING_DIFFUSE_ALBEDO, SHADING_SPECULAR_ALBEDO = 0, 1, 4, 5, 6
 SHADING_DIFFUSE_COLOR, SHADING_SPECULAR_COLOR, SHADING_DIRECT_LIGHTING, SHADING_FILTERED, SHADING_VARIANCE, SHADING_NORMAL = 7, 8, 9, 10, 11, 12
 FILTER_OP_MODULATE_INPUT, FILTER_OP_DEMODULATE_INPUT, FILTER_OP_MODULATE_OUTPUT, FILTER_OP_DEMODULATE_OUTPUT, FILTER_OP_ADD_MODE, FILTER_OP_REPLACE_MODE = 1, 2, 4, 8, 16, 32
@@ -162,7 +163,7 @@ ENTRY_POINTS = ["fpt_create", "fpt_destroy", "fpt_last_error", "fpt_stream", "fp
                 "fpt_bpt_allreduce_splats", "fpt_comm_selftest", "fpt_pt_last_union_ms", "fpt_pt_lane_count", "fpt_pt_set_lanes", "fpt_pt_set_deferred", "fpt_pt_flush", "fpt_pt_launch_list", "fpt_set_tile_lists", "fpt_gather_pack", "fpt_gather_unpack", "fpt_device_memory", "fpt_bytes_per_path_in_flight", "fpt_bpt_set_shared_light_vertices", "fpt_bpt_export_light_vertices", "fpt_bpt_import_light_vertices", "fpt_bpt_exchange_light_vertices", "fpt_bpt_finish",
                 "fpt_multiply_frame", "fpt_clamp_frame", "fpt_sequence_device_view", "fpt_mesh_lights_device_view", "fpt_mesh_invalidate", "fpt_rt_refit_geometry", "fpt_debug_refit_bvh",
                 "fpt_debug_build_emitter_tables", "fpt_clear_gbuffer", "fpt_rt_download_bvh", "fpt_mesh_lights_update", "fpt_rt_set_build_mode",
-                "fpt_mesh_lights_init_device", "fpt_mesh_lights_update_device",
+                "fpt_mesh_lights_init_device", "fpt_mesh_lights_update_device", "fpt_rt_set_intersector", "fpt_rt_intersector",
                 "fpt_debug_psf", "fpt_psfpt_debug_set_table_log2", "fpt_debug_bpt", "fpt_debug_frame"]
 
 
@@ -172,7 +173,7 @@ def kernel_source_hash():
     import hashlib
     d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
     h = hashlib.sha256()
-    for name in ("fpt_trace.hip", "fpt_device.h", "fpt_kernels.h", "fpt_math.h", "fpt_shading.h", "fpt_psf.h", "fpt_bvh.h", "fpt_bvh.cpp", "fpt_build.hip", "fpt_build_lbvh.hip",
+    for name in ("fpt_trace.hip", "fpt_trace_kernel.inc", "fpt_trace_wt.hip", "fpt_device.h", "fpt_kernels.h", "fpt_math.h", "fpt_shading.h", "fpt_psf.h", "fpt_bvh.h", "fpt_bvh.cpp", "fpt_build.hip", "fpt_build_lbvh.hip",
                  "fpt_cw8_slots.h", "Makefile"):
         with open(os.path.join(d, name), "rb") as f:
             h.update(name.encode()); h.update(f.read())
@@ -649,6 +650,18 @@ class Renderer:
         fewer node steps per ray).  FPT_BVH_BUILD=quality|fast|trbvh overrides it."""
         self._check(self.L.fpt_rt_set_build_mode(self.ctx, C.c_uint32(mode)))
 
+    def set_intersector(self, intersector):
+        """what the next create_geometry / rebuild writes its triangle records for: INTERSECTOR_MT (0, the default: fpt-MT, bit for bit the oracle's) or
+        INTERSECTOR_WATERTIGHT (1: fpt-WT, Woop-Benthin-Wald on the exact vertices -- no ray passes between two triangles that share an edge or a vertex).
+        The live tree keeps its own until it is rebuilt.  FPT_INTERSECTOR=mt|watertight overrides it."""
+        self._check(self.L.fpt_rt_set_intersector(self.ctx, C.c_uint32(intersector)))
+
+    def intersector(self):
+        """(requested, of_tree): what the next build will use, and what the live tree's records were written for"""
+        req, live = C.c_uint32(), C.c_uint32()
+        self._check(self.L.fpt_rt_intersector(self.ctx, C.byref(req), C.byref(live)))
+        return req.value, live.value
+
     def rebuild_geometry(self, vertex_data=None):
         """fpt_rt_create_geometry over the device mesh again (after set_build_mode, or with new vertices)"""
         if vertex_data is not None:
@@ -658,7 +671,7 @@ class Renderer:
                                                   C.c_void_p(self.d_vd.data_ptr())))
 
     def download_bvh(self):
-        """the device tree as it stands: (nodes [n, 20] uint32, records [m, 12] float32)"""
+        """the device tree as it stands: (nodes [n, 20] uint32, records [m, 12] float32: {v0, e1, e2, id, mask, delta}, or {v0, v1, v2, id, mask, delta} in a watertight tree)"""
         nn, nt, dp = C.c_uint32(), C.c_uint32(), C.c_uint32()
         self._check(self.L.fpt_rt_bvh_info(self.ctx, C.byref(nn), C.byref(nt), C.byref(dp)))
         nodes = np.zeros((nn.value, 20), np.uint32); recs = np.zeros((max(nt.value, 1), 12), np.float32)

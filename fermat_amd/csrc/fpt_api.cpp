@@ -91,11 +91,15 @@ int fpt_rt_create_geometry(fpt_context* ctx, uint32_t tri_count, const int32_t* 
 		// a tree whose traversal-stack bound exceeds the kernel's stack -- degenerate inputs -- falls through to the host builder and its ladder of shallower trees
 		const char* env = std::getenv("FPT_BVH_BUILD");
 		const uint32_t mode = env ? (std::strcmp(env, "fast") == 0 ? 1u : std::strcmp(env, "trbvh") == 0 ? 2u : 0u) : ctx->tree.build_mode;
+		// the intersector the new tree's records are written for (fpt_rt_set_intersector or FPT_INTERSECTOR=mt|watertight): it reaches the tree with the records, in
+		// TreeInfo, through the same all-or-nothing replace -- a refused build leaves the old tree with its own
+		const char* env_isect = std::getenv("FPT_INTERSECTOR");
+		const uint32_t intersector = env_isect ? (std::strcmp(env_isect, "watertight") == 0 ? INTERSECTOR_WATERTIGHT : INTERSECTOR_MT) : ctx->tree.requested_intersector;
 		if (mode != 0u && tri_count >= 2)
 		{
 			require(d_idx && d_vtx, "fpt_rt_create_geometry: null mesh");
 			FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));          // launches still reading the old tree
-			if (build_acceleration_device(ctx, tri_count, d_idx, vertex_count, d_vtx, trace_stack_entries(), mode))
+			if (build_acceleration_device(ctx, tri_count, d_idx, vertex_count, d_vtx, trace_stack_entries(), mode, intersector))
 			{
 				ctx->scene.changed();
 				if (std::getenv("FPT_BVH_TIMERS")) std::fprintf(stderr, "fpt_rt_create_geometry: built on the device in %.3f ms\n", (wall_seconds() - t0) * 1e3);
@@ -108,7 +112,7 @@ int fpt_rt_create_geometry(fpt_context* ctx, uint32_t tri_count, const int32_t* 
 		const double t1 = wall_seconds();
 		// binned-SAH BVH2, optimised by re-insertion, collapsed into the 8-wide tree; into the workspace: whatever the builder throws, the context's tree is as it was
 		HostBvh& built = ctx->tree.host_build;
-		build_acceleration(tri_count, idx.data(), vertex_count, vtx.data(), built, trace_stack_entries());
+		build_acceleration(tri_count, idx.data(), vertex_count, vtx.data(), built, trace_stack_entries(), intersector);
 		require(built.info.stack_need <= trace_stack_entries(), "fpt_rt_create_geometry: the BVH needs more traversal-stack entries than the kernel has");
 		const double t2 = wall_seconds();
 		ctx->tree.replace(built.info, [&](BvhNode8* d_nodes, BvhTriangle* d_records) {
@@ -126,12 +130,26 @@ int fpt_rt_set_build_mode(fpt_context* ctx, uint32_t mode)
 { return guarded(ctx, [&] { require(mode <= 2, "fpt_rt_set_build_mode: 0 = quality (host), 1 = fast (device), 2 = trbvh (device, treelet-restructured)");
                             ctx->tree.build_mode = mode; if (mode == 0) ctx->tree.build_scratch.release(); }); }
 
+// Which intersector the NEXT fpt_rt_create_geometry writes its records for, in any build mode: 0 = fpt-MT (default), 1 = fpt-WT, watertight.  The live tree
+// is not touched: it keeps the intersector it was built for (AccelTree::info), through refits too, until a build replaces it
+int fpt_rt_set_intersector(fpt_context* ctx, uint32_t intersector)
+{ return guarded(ctx, [&] { require(intersector <= INTERSECTOR_WATERTIGHT, "fpt_rt_set_intersector: 0 = mt (default), 1 = watertight");
+                            ctx->tree.requested_intersector = intersector; }); }
+int fpt_rt_intersector(fpt_context* ctx, uint32_t* requested, uint32_t* of_tree)
+{
+	return guarded(ctx, [&] {
+		if (requested) *requested = ctx->tree.requested_intersector;
+		if (of_tree) { require(ctx->tree.valid, "fpt_rt_intersector: create_geometry has not been called"); *of_tree = ctx->tree.info.intersector; }
+	});
+}
+
 // Device-side (round 6, fpt_build.hip): the mesh stays where it is, the records and every node's boxes are recomputed on the context's stream -- stream-ordered
 // behind the launches that still read the old tree -- and the host reads back 8 bytes (|scene|max and the error bits).  Byte for byte the tree refit_wide8 gives.
 int fpt_rt_refit_geometry(fpt_context* ctx, uint32_t tri_count, const int32_t* d_idx, uint32_t vertex_count, const float* d_vtx)
 { return guarded(ctx, [&] { flush_deferred(ctx); refit_acceleration_device(ctx, tri_count, d_idx, vertex_count, d_vtx); }); }
 
-// test / diagnostic: the DEVICE tree as it stands (after a build or a device-side refit) copied to HOST arrays of n_nodes x 20 words and n_records x 12 words
+// test / diagnostic: the DEVICE tree as it stands (after a build or a device-side refit) copied to HOST arrays of n_nodes x 20 words and n_records x 12 words.  A record is
+// {v0, e1 = v1 - v0, e2 = v2 - v0, id, mask, delta} in a tree built for fpt-MT and {v0, v1, v2, id, mask, delta} in one built for fpt-WT (fpt_rt_intersector tells which)
 int fpt_rt_download_bvh(fpt_context* ctx, uint32_t* h_nodes, float* h_records)
 {
 	return guarded(ctx, [&] { flush_deferred(ctx);
@@ -160,8 +178,8 @@ static void rt_launch(fpt_context* ctx, uint32_t count, const fpt_ray* d_rays, f
 	if (counted) FPT_HIP_CHECK(hipMemsetAsync(p.stats, 0, 8 * sizeof(unsigned long long), ctx->stream));
 	if (d_bits) FPT_HIP_CHECK(hipMemsetAsync(d_bits, 0, size_t((count + 31) / 32) * sizeof(uint32_t), ctx->stream));
 	const uint32_t blocks = std::min(ctx->trace_blocks(), (count + 255u) / 256u);
-	if (shadow) launch_trace_shadow(p, false, counted, blocks, ctx->stream);
-	else        launch_trace_closest(p, counted, blocks, ctx->stream);
+	if (shadow) launch_trace_shadow(p, ctx->tree.info.intersector, false, counted, blocks, ctx->stream);
+	else        launch_trace_closest(p, ctx->tree.info.intersector, counted, blocks, ctx->stream);
 	FPT_HIP_CHECK(hipGetLastError());
 }
 
@@ -622,7 +640,7 @@ static void render_lane(fpt_context* ctx, const LaneRefs& L, uint32_t instance, 
 		{
 			TraceParams tp = trace_params(ctx, cnt);
 			tp.rays = qin.rays; tp.hits = qin.hits; tp.count_ptr = qin.size;
-			timed_launch(ctx, 0, s, [&] { launch_trace_closest_queue(tp, true, ctx->counting, trace_grid, s); }, t_ms);
+			timed_launch(ctx, 0, s, [&] { launch_trace_closest_queue(tp, ctx->tree.info.intersector, true, ctx->counting, trace_grid, s); }, t_ms);
 		}
 		for (uint32_t bounce = 0; bounce < opt.max_path_length; ++bounce)
 		{
@@ -667,7 +685,7 @@ static void render_lane(fpt_context* ctx, const LaneRefs& L, uint32_t instance, 
 			if (view->dir_lights_count)
 			{
 				const TraceParams sp = shadow_params(qsd, bounce);
-				timed_launch(ctx, 2, s, [&] { if (batched) launch_trace_shadow_log(sp, ctx->counting, trace_grid, s); else launch_trace_shadow(sp, true, ctx->counting, trace_grid, s); }, t_ms);
+				timed_launch(ctx, 2, s, [&] { if (batched) launch_trace_shadow_log(sp, ctx->tree.info.intersector, ctx->counting, trace_grid, s); else launch_trace_shadow(sp, ctx->tree.info.intersector, true, ctx->counting, trace_grid, s); }, t_ms);
 			}
 			if (bounce + 1 < opt.max_path_length)
 			{
@@ -675,12 +693,12 @@ static void render_lane(fpt_context* ctx, const LaneRefs& L, uint32_t instance, 
 				// shadow rays fused with solve_occlusion (RTContext::trace_shadow + solve_occlusion)
 				TraceParams mp = shadow_params(qs, bounce);
 				mp.rays = qout.rays; mp.hits = qout.hits; mp.count_ptr = qout.size;
-				timed_launch(ctx, 1, s, [&] { if (batched) launch_trace_mixed_log(mp, ctx->counting, trace_grid, s); else launch_trace_mixed(mp, ctx->counting, trace_grid, s); }, t_ms);
+				timed_launch(ctx, 1, s, [&] { if (batched) launch_trace_mixed_log(mp, ctx->tree.info.intersector, ctx->counting, trace_grid, s); else launch_trace_mixed(mp, ctx->tree.info.intersector, ctx->counting, trace_grid, s); }, t_ms);
 			}
 			else if (sh.do_nee)
 			{
 				const TraceParams sp = shadow_params(qs, bounce);
-				timed_launch(ctx, 2, s, [&] { if (batched) launch_trace_shadow_log(sp, ctx->counting, trace_grid, s); else launch_trace_shadow(sp, true, ctx->counting, trace_grid, s); }, t_ms);
+				timed_launch(ctx, 2, s, [&] { if (batched) launch_trace_shadow_log(sp, ctx->tree.info.intersector, ctx->counting, trace_grid, s); else launch_trace_shadow(sp, ctx->tree.info.intersector, true, ctx->counting, trace_grid, s); }, t_ms);
 			}
 			if (sync_mode)
 			{

@@ -196,8 +196,8 @@ struct BptRun
 	{
 		TraceParams tp = trace_params(ctx, b.cnt);
 		tp.rays = rays; tp.hits = hits; tp.count_ptr = count_ptr;
-		if (any_hit) timed_launch(ctx, 2, s, [&] { launch_trace_shadow(tp, false, ctx->counting, ctx->trace_blocks(), s); });
-		else         timed_launch(ctx, 0, s, [&] { launch_trace_closest(tp, ctx->counting, ctx->trace_blocks(), s); });
+		if (any_hit) timed_launch(ctx, 2, s, [&] { launch_trace_shadow(tp, ctx->tree.info.intersector, false, ctx->counting, ctx->trace_blocks(), s); });
+		else         timed_launch(ctx, 0, s, [&] { launch_trace_closest(tp, ctx->tree.info.intersector, ctx->counting, ctx->trace_blocks(), s); });
 	}
 
 	// ---- sample_light_subpaths (src/bpt_control.h:290-350) ----
@@ -249,7 +249,7 @@ struct BptRun
 				TraceParams tp = trace_params(ctx, b.cnt);
 				tp.rays = P.in.rays; tp.hits = P.in.hits; tp.count_ptr = P.in.size;
 				tp.shadow_rays = P_prev.shadow.rays; tp.shadow_size = P_prev.shadow.size;
-				timed_launch(ctx, 0, s, [&] { launch_trace_mixed_hits(tp, P_prev.shadow.hits, ctx->counting, ctx->trace_blocks(), s); });
+				timed_launch(ctx, 0, s, [&] { launch_trace_mixed_hits(tp, ctx->tree.info.intersector, P_prev.shadow.hits, ctx->counting, ctx->trace_blocks(), s); });
 				timed_launch(ctx, 3, s, [&] { launch_bpt_eye_resolve(P_prev, n_launch, s); });
 			}
 			timed_launch(ctx, 3, s, [&] { launch_bpt_eye_vertices(P, n_launch, s); });

@@ -5,7 +5,7 @@
 // Three kernels, all on the context's stream, no host memory touched but one 8-byte read-back of {|scene|max, error bits}:
 //   refit_scan_kernel     |scene|max over the vertices (the tolerance of the intersector's box clause and the leaf padding scale with it) and validation of every
 //                         record's triangle id and vertex indices BEFORE anything is written (a refused refit leaves the tree as it was);
-//   refit_records_kernel  the 48-byte triangle records {v0, e1, e2, id, mask, delta} and each triangle's padded box, one thread per record;
+//   refit_records_kernel  the 48-byte triangle records {v0, e1, e2, id, mask, delta} (a watertight tree's: {v0, v1, v2, id, mask, delta}) and each triangle's padded box, one thread per record;
 //   refit_level_kernel    one launch per level of the tree, deepest first (wide nodes are numbered breadth-first: a level is a contiguous range and a node's children
 //                         come behind it): a node's box = union of its children's exact boxes, then origin, per-axis power-of-two cell and the eight children's boxes
 //                         snapped outward onto the 8-bit grid, one thread per node.
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void refit_scan_kernel(uint32_t n_tris, const 
 }
 
 __global__ __launch_bounds__(256) void refit_records_kernel(uint32_t n_records, BvhTriangle* __restrict__ records, const int4* __restrict__ idx, const float4* __restrict__ vtx,
-                                                           const uint32_t* __restrict__ scan, RefitBox* __restrict__ tri_box)
+                                                           const uint32_t* __restrict__ scan, RefitBox* __restrict__ tri_box, uint32_t watertight)
 {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n_records) return;
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void refit_records_kernel(uint32_t n_records, 
 	for (int k = 0; k < 3; ++k) { bx.lo[k] -= pad; bx.hi[k] += pad; }
 	tri_box[i] = bx;
 	#pragma unroll
-	for (int k = 0; k < 3; ++k) { r.v0[k] = p[0][k]; r.e1[k] = p[1][k] - p[0][k]; r.e2[k] = p[2][k] - p[0][k]; }
+	for (int k = 0; k < 3; ++k) { r.v0[k] = p[0][k]; r.e1[k] = watertight ? p[1][k] : p[1][k] - p[0][k]; r.e2[k] = watertight ? p[2][k] : p[2][k] - p[0][k]; }          // the tree's own layout (TreeInfo::intersector)
 	r.mask = uint32_t(ix.w);
 	// triangle_vpad (fpt_bvh.cpp): max over the components of max(|p0|, max(|p1|, |p2|)), then 5e-7 (that + |scene|max)
 	float mv = 0.0f;
@@ -186,7 +186,7 @@ void refit_acceleration_device(fpt_context* ctx, uint32_t tri_count, const int32
 	T.valid = false;
 	RefitBox* tri_box = reinterpret_cast<RefitBox*>(T.refit_tri_box.ptr); RefitBox* node_box = reinterpret_cast<RefitBox*>(T.refit_node_box.ptr);
 	if (tri_count && n_records) hipLaunchKernelGGL(refit_records_kernel, dim3((n_records + 255u) / 256u), dim3(256), 0, s, n_records, T.records.ptr, reinterpret_cast<const int4*>(d_idx),
-	                                               reinterpret_cast<const float4*>(d_vtx), T.refit_scan.ptr, tri_box);
+	                                               reinterpret_cast<const float4*>(d_vtx), T.refit_scan.ptr, tri_box, T.info.intersector);
 	for (size_t L = level_begin.size() > 0 ? level_begin.size() - 1 : 0; L-- > 0;)          // deepest level first
 		if (const uint32_t count = level_begin[L + 1] - level_begin[L])
 			hipLaunchKernelGGL(refit_level_kernel, dim3((count + 127u) / 128u), dim3(128), 0, s, T.nodes.ptr, node_box, tri_box, level_begin[L], count, T.refit_scan.ptr);

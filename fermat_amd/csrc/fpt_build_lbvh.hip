@@ -619,7 +619,7 @@ struct Uint2Plus { __host__ __device__ uint2 operator()(const uint2& a, const ui
 __global__ __launch_bounds__(256) void lbvh_finish_kernel(uint32_t n_level, BvhNode8* __restrict__ nodes, const LbvhEmitTmp* __restrict__ tmp, const uint2* __restrict__ counts,
                                                          const uint2* __restrict__ offsets, uint32_t next_base, uint32_t tri_base, int* __restrict__ next_queue,
                                                          BvhTriangle* __restrict__ records, const int4* __restrict__ idx, const float4* __restrict__ vtx, const uint32_t* __restrict__ scan,
-                                                         uint2* __restrict__ totals)
+                                                         uint2* __restrict__ totals, uint32_t watertight)
 {
 	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
 	if (t >= n_level) return;
@@ -638,7 +638,7 @@ __global__ __launch_bounds__(256) void lbvh_finish_kernel(uint32_t n_level, BvhN
 		float mv = 0.0f;
 		for (int k = 0; k < 3; ++k)
 		{
-			r.v0[k] = p[0][k]; r.e1[k] = p[1][k] - p[0][k]; r.e2[k] = p[2][k] - p[0][k];
+			r.v0[k] = p[0][k]; r.e1[k] = watertight ? p[1][k] : p[1][k] - p[0][k]; r.e2[k] = watertight ? p[2][k] : p[2][k] - p[0][k];          // fpt-WT's records hold the vertices (fpt_bvh.h)
 			mv = hmax(mv, hmax(fabsf(p[0][k]), hmax(fabsf(p[1][k]), fabsf(p[2][k]))));
 		}
 		r.tri_id = int32_t(tri); r.mask = uint32_t(ix.w); r.vpad = (mv + scene_mag) * 5.0e-7f;
@@ -683,7 +683,7 @@ static constexpr uint32_t kTreeletPasses = 3, kGamma0 = 7;          // Karras & 
 // One build: the inputs, the working set carved from the context's scratch allocation, and what the stages hand to each other.  Every stage launches on the context's stream.
 struct DeviceBuild
 {
-	fpt_context* ctx; hipStream_t s; const uint32_t n; const int4* idx; const uint32_t n_verts; const float4* vtx; const uint32_t mode;
+	fpt_context* ctx; hipStream_t s; const uint32_t n; const int4* idx; const uint32_t n_verts; const float4* vtx; const uint32_t mode; const uint32_t intersector;
 	const dim3 B{ 256 }, G{ (n + 255u) / 256u };
 	uint32_t* scene_scan; size_t sort_bytes, scan_bytes;          // scene_scan: {|scene|max bits, error bits} (the refit's scan kernel)
 	LbvhBox *refs, *node_box; LbvhCell* cells; LbvhEmitTmp* tmp; BvhNode8* nodes; BvhTriangle* records; unsigned long long *keys0, *keys1; uint2 *counts, *offsets; uint8_t *sort_tmp, *scan_tmp;
@@ -810,7 +810,7 @@ struct DeviceBuild
 			size_t sb = scan_bytes;
 			FPT_HIP_CHECK(rocprim::exclusive_scan(scan_tmp, sb, counts, offsets, make_uint2(0, 0), size_t(n_level), Uint2Plus(), s));
 			hipLaunchKernelGGL(lbvh_finish_kernel, dim3((n_level + 255u) / 256u), B, 0, s, n_level, nodes + level_base, tmp, counts, offsets, level_base + n_level, tri_total, q_next, records,
-			                   idx, vtx, scene_scan, totals);
+			                   idx, vtx, scene_scan, totals, intersector);
 			const uint2 tot = read_back(totals);
 			level_base += n_level; tri_total += tot.y; n_level = tot.x;
 			std::swap(q_cur, q_next);
@@ -818,7 +818,7 @@ struct DeviceBuild
 		}
 		level_begin.push_back(level_base);
 		require(tri_total == n, "fpt: internal device-build error (a triangle was lost or doubled)");
-		info.n_nodes = level_base; info.n_records = tri_total; info.on_device = true; info.wide_depth = uint32_t(level_begin.size() - 1);
+		info.n_nodes = level_base; info.n_records = tri_total; info.intersector = intersector; info.on_device = true; info.wide_depth = uint32_t(level_begin.size() - 1);
 	}
 	// 6: the traversal-stack bound, the occupancy histogram, the last look at the error bits: `info` is complete but for the time of the copy
 	void stack_bound_and_histogram()
@@ -871,10 +871,10 @@ struct DeviceBuild
 
 // Builds the tree over the DEVICE mesh and installs it in ctx->tree (AccelTree's contract, fpt_host.h): up to install() everything works in the scratch, so a throw or
 // `return false` -- the stack bound exceeds `stack_limit` (a degenerate input): fall back to the host builder -- leaves ctx->tree exactly as it was.
-// mode 1 = fast (the radix tree as it is), 2 = Trbvh (the radix tree restructured by treelets, stage 3b, before the collapse).
-bool build_acceleration_device(fpt_context* ctx, uint32_t n, const int32_t* d_idx, uint32_t n_verts, const float* d_vtx, uint32_t stack_limit, uint32_t mode)
+// mode 1 = fast (the radix tree as it is), 2 = Trbvh (the radix tree restructured by treelets, stage 3b, before the collapse).  intersector: the layout of the records (TreeInfo::intersector).
+bool build_acceleration_device(fpt_context* ctx, uint32_t n, const int32_t* d_idx, uint32_t n_verts, const float* d_vtx, uint32_t stack_limit, uint32_t mode, uint32_t intersector)
 {
-	DeviceBuild b{ ctx, ctx->stream, n, reinterpret_cast<const int4*>(d_idx), n_verts, reinterpret_cast<const float4*>(d_vtx), mode };
+	DeviceBuild b{ ctx, ctx->stream, n, reinterpret_cast<const int4*>(d_idx), n_verts, reinterpret_cast<const float4*>(d_vtx), mode, intersector };
 	b.scene_scan_and_scratch();
 	b.references_and_codes();
 	b.sort();

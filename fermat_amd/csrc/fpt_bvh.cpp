@@ -1036,7 +1036,7 @@ void snap_outward(double p, double cell, float c_lo, float c_hi, uint8_t* qlo, u
 
 } // namespace
 
-void build_wide8(uint32_t tri_count, const int32_t* idx, const float* vtx, HostBvh& bvh)
+void build_wide8(uint32_t tri_count, const int32_t* idx, const float* vtx, HostBvh& bvh, uint32_t intersector)
 {
 	PoolScope pool_scope;
 	const double t0 = now_seconds();
@@ -1153,6 +1153,8 @@ void build_wide8(uint32_t tri_count, const int32_t* idx, const float* vtx, HostB
 		}
 		bytes[15] = uint8_t(imask);
 	};
+	bvh.info.intersector = intersector;
+	const bool watertight = intersector != 0u;          // fpt-WT's records hold the vertices (fpt_bvh.h BvhTriangle)
 	auto write_records = [&](const Emit& E, BvhTriangle* out)
 	{
 		for (uint32_t t = 0; t < E.n_tris; ++t)
@@ -1161,7 +1163,7 @@ void build_wide8(uint32_t tri_count, const int32_t* idx, const float* vtx, HostB
 			const int32_t* ix = idx + 4 * size_t(tri);
 			const float* p0 = vtx + 4 * size_t(ix[0]); const float* p1 = vtx + 4 * size_t(ix[1]); const float* p2 = vtx + 4 * size_t(ix[2]);
 			BvhTriangle r;
-			for (int k = 0; k < 3; ++k) { r.v0[k] = p0[k]; r.e1[k] = p1[k] - p0[k]; r.e2[k] = p2[k] - p0[k]; }
+			for (int k = 0; k < 3; ++k) { r.v0[k] = p0[k]; r.e1[k] = watertight ? p1[k] : p1[k] - p0[k]; r.e2[k] = watertight ? p2[k] : p2[k] - p0[k]; }
 			r.tri_id = int32_t(tri); r.mask = uint32_t(ix[3]); r.vpad = triangle_vpad(p0, p1, p2, bvh.info.scene_mag);
 			out[t] = r;
 		}
@@ -1240,6 +1242,7 @@ void refit_wide8(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, 
 	if (bvh.tris8.size() != size_t(tri_count)) throw std::runtime_error("fpt: refit needs the geometry the tree was built over (triangle count differs)");
 	const uint32_t n_threads = builder_threads();
 	const float scene_mag = scene_magnitude(vertex_count, vtx, n_threads);
+	const bool watertight = bvh.info.intersector != 0u;          // the records keep the tree's own layout
 	// nothing is written before every record's triangle id and vertex indices have been checked: a refused refit leaves the tree as it was
 	for (size_t i = 0; i < (tri_count ? bvh.tris8.size() : 0); ++i)
 	{
@@ -1267,7 +1270,7 @@ void refit_wide8(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, 
 			for (int k = 0; k < 3; ++k) { bx.lo[k] -= pad; bx.hi[k] += pad; }
 			tri_box[i] = bx;
 			const float* p0 = vtx + 4 * size_t(ix[0]); const float* p1 = vtx + 4 * size_t(ix[1]); const float* p2 = vtx + 4 * size_t(ix[2]);
-			for (int k = 0; k < 3; ++k) { r.v0[k] = p0[k]; r.e1[k] = p1[k] - p0[k]; r.e2[k] = p2[k] - p0[k]; }
+			for (int k = 0; k < 3; ++k) { r.v0[k] = p0[k]; r.e1[k] = watertight ? p1[k] : p1[k] - p0[k]; r.e2[k] = watertight ? p2[k] : p2[k] - p0[k]; }
 			r.mask = uint32_t(ix[3]); r.vpad = triangle_vpad(p0, p1, p2, scene_mag);
 		} });
 	bvh.info.scene_mag = scene_mag;
@@ -1321,18 +1324,18 @@ void refit_wide8(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, 
 	bvh.info.seconds_refit = float(now_seconds() - t0);
 }
 
-void build_acceleration(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, const float* vtx, HostBvh& out, uint32_t stack_limit)
+void build_acceleration(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, const float* vtx, HostBvh& out, uint32_t stack_limit, uint32_t intersector)
 {
 	PoolScope pool_scope;
 	build_bvh2(tri_count, idx, vertex_count, vtx, out);
 	optimize_bvh2(out);
-	build_wide8(tri_count, idx, vtx, out);
+	build_wide8(tri_count, idx, vtx, out, intersector);
 	for (uint32_t sah_depth = 30; out.info.stack_need > stack_limit; sah_depth = sah_depth > 12 ? 12 : (sah_depth >= 6 ? sah_depth - 6 : 0))
 	{
 		const float t_opt = out.info.seconds_opt;
 		build_bvh2(tri_count, idx, vertex_count, vtx, out, sah_depth);
 		out.info.opt_iterations = 0; out.info.opt_cost_before = out.info.opt_cost_after = 0.0f; out.info.seconds_opt = t_opt;      // (the time was spent; its tree was not kept)
-		build_wide8(tri_count, idx, vtx, out);
+		build_wide8(tri_count, idx, vtx, out, intersector);
 		if (sah_depth == 0) break;
 	}
 	// the binary tree has served: the caller uploads, copies out or refits only the wide arrays (123 MB less per 1.8 M triangles)

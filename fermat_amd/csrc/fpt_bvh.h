@@ -7,7 +7,9 @@
 //   * one 80-byte node holds EIGHT children's boxes on a node-local 8-bit grid + what is needed to find them (BvhNode8 below): a ray
 //     needs a third of the dependent fetches of a binary tree, and the tree is a quarter of the size;
 //   * leaves reference runs of 1..2 pre-transformed 48-byte triangle records {v0, e1 = v1-v0, e2 = v2-v0, id, mask}; the edges are
-//     computed on the host in fp32 exactly as the intersector would, so results are unchanged.
+//     computed on the host in fp32 exactly as the intersector would, so results are unchanged.  A tree built for the watertight intersector
+//     (TreeInfo::intersector == 1) holds the VERTICES instead, {v0, v1, v2, id, mask, delta}: both triangles of a shared edge must see the same
+//     vertex bits, and v0 + e1 is not v1.  Same size, same words for id, mask and delta; nodes, padded boxes and the stack bound do not differ.
 // BvhNode (fp32, two children) is the builder's intermediate: child reference >= 0 inner node index; < 0 leaf, ~ref = (first_prim << 3) | count.
 #pragma once
 #include <stdint.h>
@@ -39,7 +41,7 @@ static_assert(sizeof(BvhNode) == 64, "BVH2 node must be one 64-byte record");
 
 struct alignas(16) BvhTriangle
 {
-	float v0[3], e1[3], e2[3];
+	float v0[3], e1[3], e2[3];      // fpt-MT: the edges v1 - v0, v2 - v0; fpt-WT (TreeInfo::intersector == 1): the vertices v1, v2 themselves
 	int32_t tri_id;
 	uint32_t mask;
 	float vpad;          // constant part of the tolerance of the intersector's box clause for this triangle: 5e-7 (|triangle|max + |scene|max)
@@ -76,6 +78,8 @@ inline uint32_t cw8_inner_child(const BvhNode8& n, int slot) { return n.w[4] + u
 struct TreeInfo
 {
 	uint32_t n_nodes = 0, n_records = 0;     // wide nodes and triangle records
+	uint32_t intersector = 0;                // which intersector the records were written for: 0 = fpt-MT {v0, e1, e2}, 1 = fpt-WT (watertight) {v0, v1, v2}.  Set by whoever
+	                                         // writes the records of a build; a refit rewrites them in the tree's own layout; the traversal launches pick their kernel from it
 	bool on_device = false;                  // built by the device builder (fpt_build_lbvh.hip): there is no host copy of the arrays
 	std::vector<uint32_t> level_begin;       // wide nodes are numbered breadth-first: level L = [level_begin[L], level_begin[L + 1]); what a refit walks bottom-up
 	uint32_t wide_depth = 0, stack_need = 0; // stack_need: upper bound of the traversal-stack entries a ray can need in this tree (see build_wide8)
@@ -108,11 +112,12 @@ void optimize_bvh2(HostBvh& bvh, uint32_t max_iterations = 16, double batch_frac
 // collapses out.nodes / out.prims into out.nodes8 / out.tris8: the SAH-optimal 8-wide collapse (dynamic programme of Ylitie et al. 2017, section 3:
 // which binary nodes become wide nodes, which subtrees of <= 2 triangles become leaves), octant-ordered slots by an exact 8x8 assignment,
 // outward 8-bit quantisation checked in double
-void build_wide8(uint32_t tri_count, const int32_t* idx, const float* vtx, HostBvh& bvh);
-// the vertices moved, the topology stays: triangle records and every node's boxes recomputed in place (nodes8 / tris8), bottom-up; nothing else changes
+// intersector: the layout of the records (TreeInfo::intersector), recorded in bvh.info
+void build_wide8(uint32_t tri_count, const int32_t* idx, const float* vtx, HostBvh& bvh, uint32_t intersector = 0);
+// the vertices moved, the topology stays: triangle records (in the layout of bvh.info.intersector) and every node's boxes recomputed in place (nodes8 / tris8), bottom-up; nothing else changes
 void refit_wide8(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, const float* vtx, HostBvh& bvh);
 // build_bvh2 + optimize_bvh2 + build_wide8; a tree whose traversal-stack bound (bvh.info.stack_need) exceeds stack_limit is built again without the
 // optimisation and then with shallower SAH limits.  The caller checks bvh.info.stack_need against its kernel.
-void build_acceleration(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, const float* vtx, HostBvh& bvh, uint32_t stack_limit);
+void build_acceleration(uint32_t tri_count, const int32_t* idx, uint32_t vertex_count, const float* vtx, HostBvh& bvh, uint32_t stack_limit, uint32_t intersector = 0);
 
 } // namespace fpt

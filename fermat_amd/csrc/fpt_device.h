@@ -256,16 +256,20 @@ __device__ __forceinline__ void log_mark_fused(const FusedResolve* F, uint32_t p
 }
 
 uint32_t trace_blocks_per_cu();
+// Every traversal launch names the intersector the tree's records were written for (TreeInfo::intersector, fpt_bvh.h): fpt-MT's kernels are fpt_trace.hip's,
+// fpt-WT's fpt_trace_wt.hip's (launch_trace_watertight: `mode` is fpt_trace_kernel.inc's TraceMode)
+enum : uint32_t { INTERSECTOR_MT = 0, INTERSECTOR_WATERTIGHT = 1 };
+void launch_trace_watertight(int mode, const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream);
 uint32_t trace_stack_entries();      // capacity of the traversal stack (LDS + scratch levels); fpt_rt_create_geometry checks the tree's bound against it
-void launch_trace_closest(const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream);                         // the RT boundary's rays: tmin / tmax in the .w words
-void launch_trace_shadow(const TraceParams& p, bool fused_resolve, bool counted, uint32_t n_blocks, hipStream_t stream);      // fused: a renderer's shadow queue, resolved as the rays retire
-void launch_trace_closest_queue(const TraceParams& p, bool primary, bool counted, uint32_t n_blocks, hipStream_t stream);     // a renderer's path queue (PathQueue): primary or scattered rays
-void launch_trace_shadow_queue(const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream);                    // a renderer's shadow queue (ShadowQueue), results written to p.hits
-void launch_trace_mixed(const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream);
-void launch_trace_mixed_log(const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream);    // launch_trace_mixed / launch_trace_shadow(fused) for the path tracer's passes in flight: the shadow
-void launch_trace_shadow_log(const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream);   // rays' samples are in the log already (dir.w = path index), an unoccluded one sets its bit
-void launch_trace_mixed_psf(const TraceParams& p, bool counted, uint32_t n_blocks, hipStream_t stream);   // p.fused = a ResolveParams block (fpt_kernels.h)
-void launch_trace_mixed_hits(const TraceParams& p, float4* shadow_hits, bool counted, uint32_t n_blocks, hipStream_t stream);   // closest-hit rays -> p.hits, the any-hit rays of p.shadow_rays -> shadow_hits (written, not resolved)
+void launch_trace_closest(const TraceParams& p, uint32_t intersector, bool counted, uint32_t n_blocks, hipStream_t stream);                         // the RT boundary's rays: tmin / tmax in the .w words
+void launch_trace_shadow(const TraceParams& p, uint32_t intersector, bool fused_resolve, bool counted, uint32_t n_blocks, hipStream_t stream);      // fused: a renderer's shadow queue, resolved as the rays retire
+void launch_trace_closest_queue(const TraceParams& p, uint32_t intersector, bool primary, bool counted, uint32_t n_blocks, hipStream_t stream);     // a renderer's path queue (PathQueue): primary or scattered rays
+void launch_trace_shadow_queue(const TraceParams& p, uint32_t intersector, bool counted, uint32_t n_blocks, hipStream_t stream);                    // a renderer's shadow queue (ShadowQueue), results written to p.hits
+void launch_trace_mixed(const TraceParams& p, uint32_t intersector, bool counted, uint32_t n_blocks, hipStream_t stream);
+void launch_trace_mixed_log(const TraceParams& p, uint32_t intersector, bool counted, uint32_t n_blocks, hipStream_t stream);    // launch_trace_mixed / launch_trace_shadow(fused) for the path tracer's passes in flight: the shadow
+void launch_trace_shadow_log(const TraceParams& p, uint32_t intersector, bool counted, uint32_t n_blocks, hipStream_t stream);   // rays' samples are in the log already (dir.w = path index), an unoccluded one sets its bit
+void launch_trace_mixed_psf(const TraceParams& p, uint32_t intersector, bool counted, uint32_t n_blocks, hipStream_t stream);   // p.fused = a ResolveParams block (fpt_kernels.h)
+void launch_trace_mixed_hits(const TraceParams& p, uint32_t intersector, float4* shadow_hits, bool counted, uint32_t n_blocks, hipStream_t stream);   // closest-hit rays -> p.hits, the any-hit rays of p.shadow_rays -> shadow_hits (written, not resolved)
 // fpt_build.hip: the device-side refit of the 8-wide tree (fpt_rt_refit_geometry); d_scan = {bits of |scene|max, error bits}, boxes = 6 floats each
 struct BvhNode8; struct BvhTriangle;
 void launch_refit_scan(uint32_t n_tris, const int32_t* d_idx, uint32_t n_verts, const float* d_vtx, uint32_t n_records, const BvhTriangle* d_records, uint32_t* d_scan, hipStream_t s);

@@ -180,6 +180,9 @@ struct AccelTree
 	bool valid = false;
 	uint32_t build_mode = 0;                        // fpt_rt_set_build_mode: 0 = quality (host: binned SAH + re-insertion + collapse), 1 = fast (device: Morton radix tree + collapse),
 	                                                // 2 = trbvh (device: Morton radix tree + treelet restructuring + collapse)
+	uint32_t requested_intersector = 0;             // fpt_rt_set_intersector: what the NEXT build writes its records for (0 = fpt-MT, 1 = fpt-WT, watertight).  What the LIVE records
+	                                                // were written for is info.intersector, set by the builder with the records and replaced with them, all or nothing: the
+	                                                // launches read it from there (trace_params' callers), so a kernel of one kind never meets records of the other
 	DeviceArray<float> refit_tri_box, refit_node_box; DeviceArray<uint32_t> refit_scan;      // device refit (fpt_build.hip): per-record and per-node fp32 boxes, {|scene|max bits, error bits}
 	HostBvh host_build;                             // the quality path's workspace: written by the host builder, read by nothing once its arrays are uploaded
 	DeviceArray<uint8_t> build_scratch;             // the device builder's working set (fpt_build_lbvh.hip), kept between builds; fpt_rt_set_build_mode(0) releases it
@@ -455,7 +458,7 @@ inline double wall_seconds() { return std::chrono::duration<double>(std::chrono:
 namespace fpt { void emitters_init_device(fpt_context* ctx, uint32_t n_vpls, const fpt_mesh_view& h_mesh, const fpt_texture* h_textures, const fpt_mesh_view& d_mesh,
                                           const fpt_texture* d_textures, uint32_t instance);
                 void emitters_update_device(fpt_context* ctx, const fpt_mesh_view& d_mesh); }
-namespace fpt { bool build_acceleration_device(fpt_context* ctx, uint32_t tri_count, const int32_t* d_idx, uint32_t vertex_count, const float* d_vtx, uint32_t stack_limit, uint32_t mode);
+namespace fpt { bool build_acceleration_device(fpt_context* ctx, uint32_t tri_count, const int32_t* d_idx, uint32_t vertex_count, const float* d_vtx, uint32_t stack_limit, uint32_t mode, uint32_t intersector);
                 void refit_acceleration_device(fpt_context* ctx, uint32_t tri_count, const int32_t* d_idx, uint32_t vertex_count, const float* d_vtx); }
 
 // launch timing.  Profiling level 2 (fpt_pt_set_profiling): events are recorded around the launch on its stream and read back after the timed region

@@ -163,8 +163,8 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 		{
 			TraceParams tp = trace_params(ctx, cnt);
 			tp.rays = rays; tp.hits = hits; tp.count_ptr = count_ptr;
-			if (any_hit) timed_launch(ctx, 2, s, [&] { launch_trace_shadow_queue(tp, ctx->counting, ctx->trace_blocks(), s); });
-			else         timed_launch(ctx, 0, s, [&] { launch_trace_closest_queue(tp, primary, ctx->counting, ctx->trace_blocks(), s); });
+			if (any_hit) timed_launch(ctx, 2, s, [&] { launch_trace_shadow_queue(tp, ctx->tree.info.intersector, ctx->counting, ctx->trace_blocks(), s); });
+			else         timed_launch(ctx, 0, s, [&] { launch_trace_closest_queue(tp, ctx->tree.info.intersector, primary, ctx->counting, ctx->trace_blocks(), s); });
 		};
 		QueueStorage* qa = &w.q_a; QueueStorage* qb = &w.q_b;
 		PathQueue qin = qa->view(cnt.queue(0, CNT_PATH)), qout = qb->view(cnt.queue(1, CNT_PATH));
@@ -217,7 +217,7 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 				mp.rays = qout.rays; mp.hits = qout.hits; mp.count_ptr = qout.size;
 				mp.shadow_rays = qs.rays; mp.shadow_size = qs.size; mp.base_instance = instance;
 				mp.fused = reinterpret_cast<const FusedResolve*>(ps.d_resolve.ptr + bounce);      // MIXED_PSF reads a ResolveParams there
-				timed_launch(ctx, 0, s, [&] { launch_trace_mixed_psf(mp, ctx->counting, ctx->trace_blocks(), s); });
+				timed_launch(ctx, 0, s, [&] { launch_trace_mixed_psf(mp, ctx->tree.info.intersector, ctx->counting, ctx->trace_blocks(), s); });
 			}
 			else
 			{

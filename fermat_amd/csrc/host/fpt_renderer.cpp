@@ -111,6 +111,12 @@ void RenderingContext::init(int argc, char** argv, const SceneArrays& scene)
 			m_build_mode = std::strcmp(v, "fast") == 0 ? 1u : std::strcmp(v, "trbvh") == 0 ? 2u : 0u;
 			if (m_build_mode == 0u && std::strcmp(v, "quality") != 0) std::fprintf(stderr, "warning: -bvh %s: expected quality, fast or trbvh; using quality\n", v);
 		}
+		else if (std::strcmp(argv[i], "-intersector") == 0 && i + 1 < argc)  // no counterpart in the reference (OptiX's triangles are watertight): mt = fpt-MT, the default; watertight = fpt-WT
+		{
+			const char* v = argv[++i];
+			m_intersector = std::strcmp(v, "watertight") == 0 ? 1u : 0u;
+			if (m_intersector == 0u && std::strcmp(v, "mt") != 0) std::fprintf(stderr, "warning: -intersector %s: expected mt or watertight; using mt\n", v);
+		}
 		else if (std::strcmp(argv[i], "-lights") == 0 && i + 1 < argc)       // no counterpart in the reference, which always builds from device pointers (src/mesh_lights.cu:164)
 		{
 			const char* v = argv[++i];
@@ -179,7 +185,14 @@ void RenderingContext::init(int argc, char** argv, const SceneArrays& scene)
 	// ray-tracing context over the device mesh (src/renderer.cu:920-933)
 	m_rt_context.reset(new RTContext(m_ctx));
 	check(m_ctx, fpt_rt_set_build_mode(m_ctx, m_build_mode), "fpt_rt_set_build_mode");
+	check(m_ctx, fpt_rt_set_intersector(m_ctx, m_intersector), "fpt_rt_set_intersector");
 	m_rt_context->create_geometry(uint32(scene.mesh.num_triangles), v.mesh.vertex_indices, uint32(scene.mesh.num_vertices), v.mesh.vertex_data, 0, 0, 0, 0, v.mesh.material_indices);
+	{
+		// what the tree was built for (FPT_INTERSECTOR overrides the flag): said once, so that a log tells which guarantee its image has
+		uint32_t requested = 0, of_tree = 0;
+		check(m_ctx, fpt_rt_intersector(m_ctx, &requested, &of_tree), "fpt_rt_intersector");
+		if (requested != 0u || of_tree != 0u) std::fprintf(stderr, "intersector: requested %u, tree %u (%s)\n", requested, of_tree, of_tree ? "fpt-WT, watertight" : "fpt-MT");
+	}
 	// the context's own 72-dimensional sequence: unused by the PT but it advances rand() (src/renderer.cu:949-953)
 	check(m_ctx, fpt_sequence_setup(m_ctx, 72, 256, scene.samples_dir), "m_sequence.setup");
 	m_renderer = m_renderer_factories[renderer_type]();

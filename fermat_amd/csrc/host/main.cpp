@@ -4,6 +4,7 @@
 //              [-benchmark file] [-save-intermediate] [PT flags: -pl/-bounces/-nee/-bsdf/-nee-alg mesh|vpl ...]
 //              [-data dir] [-device id] [-filtered | -shading-mode N]   (kFiltered = EAW-denoised output; the reference toggles it in the viewer)
 //              [-bvh quality|fast|trbvh]   the acceleration structure's build mode (fpt_rt_set_build_mode): host SAH, device radix tree, device Trbvh
+//              [-intersector mt|watertight]  the triangle intersector the tree is built for (fpt_rt_set_intersector): fpt-MT (default) or the watertight fpt-WT
 //              [-lights host|device]       who builds the emitter tables: the host from the host mesh (default), or the device from the device mesh (the same tables)
 //              [-gpus N]   one process per GPU of this node (forked here), image rows interleaved over the ranks, frame gathered to rank 0
 //                          over RCCL (fpt_gather_framebuffer); -pt and -bpt
@@ -116,6 +117,7 @@ int main(int argc, char** argv)
 		                     "  -a float               specify the aspect ratio\n  -c camera.txt          specify a camera file\n"
 		                     "  -pt                    use the PT renderer\n  -passes int            number of passes - 1\n  -o name                output image name\n"
 		                     "  -bvh quality|fast|trbvh  build mode of the acceleration structure (host SAH, device radix tree, device Trbvh)\n"
+		                     "  -intersector mt|watertight  triangle intersector the acceleration structure is built for (default mt; watertight: no ray slips between adjacent triangles)\n"
 		                     "  -lights host|device      builder of the emitter tables (host mesh on host threads, device mesh on the device; FPT_LIGHTS_BUILD overrides)\n");
 		return 0;
 	}

@@ -144,6 +144,8 @@ struct RenderingContext
 	uint8_t* m_d_rgba = nullptr;
 	uint32 m_build_mode = 0;          // `-bvh quality|fast|trbvh`: fpt_rt_set_build_mode (quality = the host SAH builder, the default; fast = Morton radix tree + collapse on the device;
 	                                  //  trbvh = the same radix tree restructured by treelets on the device before the collapse)
+	uint32 m_intersector = 0;         // `-intersector mt|watertight`: fpt_rt_set_intersector before the geometry is created (mt = fpt-MT, the default; watertight = fpt-WT: no ray slips between
+	                                  //  triangles that share an edge or a vertex); FPT_INTERSECTOR overrides it inside the library
 	bool m_lights_device = false;     // `-lights host|device` (FPT_LIGHTS_BUILD overrides): who builds the emitter tables -- fpt_mesh_lights_init / _update from the host mesh (the default), or
 	                                  //  fpt_mesh_lights_init_device / _update_device from the device mesh, the same tables bit for bit
 	bool lights_on_device() const { return m_lights_device; }

@@ -128,6 +128,17 @@ int fpt_rt_create_geometry(fpt_context* ctx, uint32_t tri_count, const int32_t* 
  * milliseconds more than mode 1 for a tree that needs fewer node steps per ray (DESIGN.md 5 has the measurements).  Results do not depend on the tree.
  * FPT_BVH_BUILD=quality|fast|trbvh overrides.  Mode 0 also releases the device builder's scratch (about 400 B per triangle, otherwise kept for the next device build). */
 int fpt_rt_set_build_mode(fpt_context* ctx, uint32_t mode);
+/* The triangle intersector, a property of the acceleration structure.  0 = fpt-MT, the default: fixed-order Moeller-Trumbore on pre-transformed records {v0, v1 - v0, v2 - v0},
+ * bit for bit the CPU oracle's; not watertight.  1 = fpt-WT, watertight: Woop, Benthin and Wald's test (JCGT 2013) in a fixed fp32 order with an fp64 fallback
+ * for edge functions that are exactly zero, on records that hold the exact vertices {v0, v1, v2} -- no ray passes between two triangles that share an edge or a vertex,
+ * and a ray that starts inside a closed mesh always reports a hit.  Interval, closest-hit ties, u / v through binary16, the shadow mask and the box clause are fpt-MT's;
+ * what it does not promise is the float64 answer at a silhouette.
+ * fpt_rt_set_intersector sets what the NEXT fpt_rt_create_geometry builds, in any build mode; the live tree is not touched and keeps its own intersector through
+ * fpt_rt_refit_geometry.  The tree records which intersector its records were written for and every traversal launch (the three renderers, fpt_rt_trace*) picks its
+ * kernel from the tree; a refused build leaves the old tree with its old intersector.  FPT_INTERSECTOR=mt|watertight overrides the request.
+ * fpt_rt_intersector reads both back (either pointer may be NULL; of_tree needs geometry). */
+int fpt_rt_set_intersector(fpt_context* ctx, uint32_t intersector);
+int fpt_rt_intersector(fpt_context* ctx, uint32_t* requested, uint32_t* of_tree);
 /* Refit (no counterpart in the reference, whose update_model rebuilds: src/renderer.cu:999-1017): the vertices of the mesh the tree was built over have MOVED and nothing
  * else changed (same triangle count, same indices).  Triangle records and every node's boxes are recomputed bottom-up in the existing topology ON THE DEVICE (round 6,
  * fpt_build.hip: the mesh is not copied anywhere; 0.55 ms for 1.8 M triangles, byte for byte the tree the host refit gave) where fpt_rt_create_geometry's quality mode takes 0.4 s.
@@ -160,7 +171,8 @@ typedef struct fpt_bvh_stats
 } fpt_bvh_stats;
 int fpt_rt_bvh_stats(fpt_context* ctx, fpt_bvh_stats* out);
 /* test / diagnostic: the DEVICE tree as it stands -- after fpt_rt_create_geometry or a device-side fpt_rt_refit_geometry -- copied to HOST arrays of n_nodes x 20 words
- * and n_leaf_tris x 12 words (fpt_rt_bvh_info gives the sizes; either pointer may be NULL) */
+ * and n_leaf_tris x 12 words (fpt_rt_bvh_info gives the sizes; either pointer may be NULL).  A record is {v0, e1 = v1 - v0, e2 = v2 - v0, id, mask, delta} in a tree built
+ * for fpt-MT and {v0, v1, v2, id, mask, delta} in a tree built for fpt-WT: the same 48 bytes, id, mask and delta in the same words (fpt_rt_intersector tells which) */
 int fpt_rt_download_bvh(fpt_context* ctx, uint32_t* h_nodes, float* h_records);
 
 /* ---- QMC sequence : struct TiledSequence (src/tiled_sequence.h:109-157, src/tiled_sequence.cu:62-110) ------------------ */
