@@ -83,6 +83,27 @@ def default_bpt_options(max_path_length=6, **kw):
     return o
 
 
+class PssmltOptions(C.Structure):
+    """fpt_pssmlt_options: PSSMLTOptions (src/renderers/pssmlt.h) over the bidirectional base options"""
+    _fields_ = [("bpt", BptOptions), ("n_chains", C.c_uint32), ("spp", C.c_uint32), ("light_perturbations", C.c_uint32), ("eye_perturbations", C.c_uint32),
+                ("independent_samples", C.c_float), ("radius", C.c_float)]
+
+
+class PssmltStats(C.Structure):
+    _fields_ = [("image_brightness", C.c_float), ("pdf_norm", C.c_float), ("chain_length", C.c_uint32), ("n_chains", C.c_uint32),
+                ("accepted", C.c_uint64), ("rejected", C.c_uint64)]
+
+
+def default_pssmlt_options(max_path_length=6, **kw):
+    """the reference's defaults: 64 K chains, 4 spp, both perturbations on, no independent samples, Cauchy radius 0.01.  Keywords name fields of the
+    structure or of its bidirectional base options (light_tracing and single_connection are forced to 0 at init)"""
+    o = PssmltOptions(default_bpt_options(max_path_length, light_tracing=0.0), 64 * 1024, 4, 1, 1, 0.0, 0.01)
+    own = {f[0] for f in PssmltOptions._fields_}
+    for k, v in kw.items():
+        setattr(o if k in own else o.bpt, k, v)
+    return o
+
+
 class EawParams(C.Structure):
     _fields_ = [("phi_normal", C.c_float), ("phi_position", C.c_float), ("phi_color", C.c_float),
                 ("E", C.c_float * 3), ("U", C.c_float * 3), ("V", C.c_float * 3), ("W", C.c_float * 3)]
@@ -164,7 +185,8 @@ ENTRY_POINTS = ["fpt_create", "fpt_destroy", "fpt_last_error", "fpt_stream", "fp
                 "fpt_multiply_frame", "fpt_clamp_frame", "fpt_sequence_device_view", "fpt_mesh_lights_device_view", "fpt_mesh_invalidate", "fpt_rt_refit_geometry", "fpt_debug_refit_bvh",
                 "fpt_debug_build_emitter_tables", "fpt_clear_gbuffer", "fpt_rt_download_bvh", "fpt_mesh_lights_update", "fpt_rt_set_build_mode",
                 "fpt_mesh_lights_init_device", "fpt_mesh_lights_update_device", "fpt_rt_set_intersector", "fpt_rt_intersector",
-                "fpt_debug_psf", "fpt_psfpt_debug_set_table_log2", "fpt_debug_bpt", "fpt_debug_frame"]
+                "fpt_debug_psf", "fpt_psfpt_debug_set_table_log2", "fpt_debug_bpt", "fpt_debug_frame",
+                "fpt_pssmlt_init", "fpt_pssmlt_render", "fpt_pssmlt_get_stats", "fpt_pssmlt_download", "fpt_pssmlt_debug_eval", "fpt_debug_mlt"]
 
 
 def kernel_source_hash():
@@ -174,7 +196,7 @@ def kernel_source_hash():
     d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
     h = hashlib.sha256()
     for name in ("fpt_trace.hip", "fpt_trace_kernel.inc", "fpt_trace_wt.hip", "fpt_device.h", "fpt_kernels.h", "fpt_math.h", "fpt_shading.h", "fpt_psf.h", "fpt_bvh.h", "fpt_bvh.cpp", "fpt_build.hip", "fpt_build_lbvh.hip",
-                 "fpt_cw8_slots.h", "Makefile"):
+                 "fpt_cw8_slots.h", "Makefile", "fpt_bpt.h", "fpt_bpt_device.h", "fpt_bpt.hip", "fpt_mlt.h", "fpt_mlt.hip", "fpt_mlt_host.h", "fpt_mlt_api.cpp"):
         with open(os.path.join(d, name), "rb") as f:
             h.update(name.encode()); h.update(f.read())
     return h.hexdigest()[:16]
@@ -251,7 +273,7 @@ class Renderer:
     """RenderingContext + PathTracer for one GPU: owns torch device tensors, calls the C-ABI with their pointers."""
 
     def __init__(self, scn: "_scene.Scene", res_x, res_y, options=None, device=0, table=None, samples_dir=None, pixels=None,
-                 exposure=1.0, gamma=2.2, gbuffer=True, replay_context_sequence=True, bpt_options=None, psf_options=None):
+                 exposure=1.0, gamma=2.2, gbuffer=True, replay_context_sequence=True, bpt_options=None, psf_options=None, pssmlt_options=None):
         import torch
         if not torch.cuda.is_available():
             raise FptError("no HIP device visible: fermat_amd has no CPU fallback")
@@ -315,7 +337,11 @@ class Renderer:
         px = C.c_void_p(self.d_pixels.data_ptr()) if self.d_pixels is not None else None
         self.bpt_options = bpt_options
         self.psf_options = psf_options
-        if psf_options is not None:
+        self.pssmlt_options = pssmlt_options
+        if pssmlt_options is not None:
+            # `-pssmlt`: Metropolis chains over the bidirectional kernels; initialises the bidirectional state itself
+            self._check(self.L.fpt_pssmlt_init(self.ctx, C.byref(pssmlt_options), C.byref(self.view), sd, px, C.c_uint32(self.n_local)))
+        elif psf_options is not None:
             # `-psfpt`: the path tracer's loop with the path-space-filtering vertex processor
             self._check(self.L.fpt_psfpt_init(self.ctx, C.byref(self.options), C.byref(psf_options), C.byref(self.view), sd, px, C.c_uint32(self.n_local)))
         elif bpt_options is None:
@@ -515,6 +541,51 @@ class Renderer:
         w = np.zeros((nv, 2), np.float32); pid = np.zeros(nv, np.uint32); cnt = np.zeros(n, np.uint32)
         self._check(self.L.fpt_bpt_download_light_vertices(self.ctx, *[C.c_void_p(x.ctypes.data) for x in (pos, inp, gb, w, pid, cnt)]))
         return dict(pos=pos, input=inp, gbuffer=gb, weights=w, path_id=pid, counts=cnt)
+
+    # -- primary-sample-space Metropolis renderer (Renderer(..., pssmlt_options=default_pssmlt_options(L)))
+    def pssmlt_render(self, instance, sync=False):
+        self._check(self.L.fpt_pssmlt_render(self.ctx, C.c_uint32(instance), C.byref(self.view)))
+        if sync:
+            self.synchronize()
+
+    def pssmlt_stats(self):
+        st = PssmltStats()
+        self._check(self.L.fpt_pssmlt_get_stats(self.ctx, C.byref(st)))
+        return dict(image_brightness=np.float32(st.image_brightness), pdf_norm=np.float32(st.pdf_norm), chain_length=int(st.chain_length), n_chains=int(st.n_chains),
+                    accepted=int(st.accepted), rejected=int(st.rejected))
+
+    def _pssmlt_dims(self):
+        return (self.pssmlt_options.bpt.max_path_length + 1) * 3
+
+    def pssmlt_state(self):
+        """what the last pssmlt_render left: light_u / eye_u (dims, n_chains), path_value (n_chains, 4), path_pdf, rejections, seeds (n_chains), presample (n_pixels, 4)"""
+        n = int(self.pssmlt_options.n_chains); d = self._pssmlt_dims(); npx = self.res[0] * self.res[1]
+        out = dict(light_u=np.zeros((d, n), np.float32), eye_u=np.zeros((d, n), np.float32), path_value=np.zeros((n, 4), np.float32), path_pdf=np.zeros(n, np.float32),
+                   rejections=np.zeros(n, np.uint32), seeds=np.zeros(n, np.uint32), presample=np.zeros((npx, 4), np.float32))
+        self._check(self.L.fpt_pssmlt_download(self.ctx, *[C.c_void_p(out[k].ctypes.data) for k in ("light_u", "eye_u", "path_value", "path_pdf", "rejections", "seeds", "presample")]))
+        return out
+
+    def pssmlt_eval(self, light_u, eye_u):
+        """the value (n, 4) of n coordinate sets, light_u / eye_u of shape (dims, n), through the chain-mode kernels with mutation Null"""
+        light_u = np.ascontiguousarray(light_u, np.float32); eye_u = np.ascontiguousarray(eye_u, np.float32)
+        d = self._pssmlt_dims()
+        assert light_u.shape == eye_u.shape and light_u.shape[0] == d
+        n = light_u.shape[1]
+        out = np.zeros((n, 4), np.float32)
+        self._check(self.L.fpt_pssmlt_debug_eval(self.ctx, C.byref(self.view), C.c_uint32(n), C.c_void_p(light_u.ctypes.data), C.c_void_p(eye_u.ctypes.data), C.c_void_p(out.ctypes.data)))
+        return out
+
+    def debug_mlt(self, op, arrays, params=(), n=None):
+        """fpt_debug_mlt (layouts: include/fermat_pt_hip.h); arguments and result as debug_bpt's"""
+        torch = self.torch
+        hosts = [None if a is None else np.ascontiguousarray(a) for a in arrays]
+        devs = [None if a is None else torch.from_numpy(a.view(np.uint8).reshape(-1).copy() if a.size else np.zeros(8, np.uint8)).to(self.dev) for a in hosts]
+        n = len(hosts[0]) if n is None else int(n)
+        ptrs = (C.c_void_p * max(1, len(devs)))(*[None if d is None else d.data_ptr() for d in devs])
+        par = (C.c_uint32 * max(1, len(params)))(*[int(p) for p in params])
+        torch.cuda.synchronize(self.dev)
+        self._check(self.L.fpt_debug_mlt(self.ctx, C.c_int(op), C.c_uint32(n), par, C.c_uint32(len(params)), ptrs, C.c_uint32(len(devs))))
+        return [None if a is None else d.cpu().numpy()[:a.nbytes].view(a.dtype).reshape(a.shape) for a, d in zip(hosts, devs)]
 
     def device_memory(self):
         """(free, total) bytes of the context's device"""

@@ -26,6 +26,15 @@ static_assert(sizeof(LightVertexWire) == 80, "light-vertex wire record must be 8
 //   cell = bounce * (1 + conn_cells) + {0 emission, 1 + k: the k-th connection of the eye vertex (light-depth order)};  index [cell * cap + virtual path id]
 struct BptLog { float4* val; uint32_t* chan; uint32_t* mask; uint32_t cap, mask_words, conn_cells; };
 
+// Chain mode (the Metropolis renderer, fpt_mlt.h): the primary sample coordinates of light and eye sub-path `chain` come from two arrays instead of the tiled
+// sequence, PerturbedPrimaryCoords (src/bpt_samplers.h:90-155).  light_u / eye_u: (L+1)*3 dimensions each, laid out dim * n_chains + chain (src/bpt_samplers.h:100-103);
+// mutation: 0 Null, 1 Cauchy, 2 Independent, applied where a coordinate is read (fpt_bpt_device.h); a side whose *_perturbations flag is 0 is read as it
+// is.  Set = light_u != NULL.  The path id is the chain; the eye path's screen position is (coordinate 3, coordinate 4) and the lens sample is ignored (pssmlt.cu:391-397)
+struct ChainCoords { const float* light_u; const float* eye_u; uint32_t n_chains, step, mutation, light_perturbations, eye_perturbations; float radius; };
+// Value sink: every frame contribution of eye path `id` is added to value[id] (all four components) and nothing else is written: no frame cell, no albedo
+// plane, no gbuffer, no log (the sinks of pssmlt.cu:257-304).  Set = value != NULL
+struct ValueSink { float4* value; };
+
 struct BptParams
 {
 	BptQueue in, out;
@@ -57,6 +66,10 @@ struct BptParams
 	BptLog log;                  // passes in flight only
 	f3 eye, U, V, W;
 	float W_len, sq_focal;
+	// the Metropolis renderer's two switches, both off (NULL) for `-bpt`.  A parameter block with either set is served by a second instantiation of the five
+	// kernels that read coordinates or sink samples (fpt_bpt.hip): the launchers below choose
+	ChainCoords chain;
+	ValueSink value;
 };
 
 void launch_bpt_light_primary(const BptParams& p, hipStream_t s);

@@ -17,7 +17,10 @@
 //    racy read-modify-write);
 //  * light-tracing splats land on arbitrary pixels: they are accumulated as 2^-32 fixed-point 64-bit integer atomics
 //    (order-independent) and added to the frame once per pass.
-#include "fpt_bpt.h"
+//  * the Metropolis renderer (fpt_mlt.hip, `-pssmlt`) runs these kernels with two optional views of BptParams set: ChainCoords (coordinates from per-chain arrays,
+//    mutated where they are read) and ValueSink (every sample into the eye path's value, nothing else written).  The five kernels that read coordinates or sink
+//    samples are templates on one bool; `-bpt` launches the `false` instantiation, whose code does not know the other exists.
+#include "fpt_bpt_device.h"
 
 namespace fpt {
 
@@ -117,39 +120,8 @@ __device__ __forceinline__ f3 lens_direction(const BptParams& P, f3 position, fl
 	return delta / d;
 }
 __device__ __forceinline__ uint32_t lens_pixel(const BptParams& P, float ox, float oy) { return quantize(ox * 0.5f + 0.5f, P.res_x) + quantize(oy * 0.5f + 0.5f, P.res_y) * P.res_x; }
-// virtual path id -> (pass offset, pixel / light-path index); see BptParams
-struct PathRef { uint32_t k, id; };
-__device__ __forceinline__ PathRef path_ref(const BptParams& P, uint32_t vid)
-{
-	PathRef r;
-	r.k = P.n_passes == 1 ? 0u : vid / P.n_paths;
-	r.id = vid - r.k * P.n_paths;
-	return r;
-}
 __device__ __forceinline__ float frame_weight(const BptParams& P, uint32_t k) { return 1.0f / float(P.instance + k + 1); }
 __device__ __forceinline__ float4* fb_cell(const BptParams& P, uint32_t channel, PathRef r) { return P.fb.ch[channel] + size_t(r.k) * P.plane_stride + r.id; }
-
-// primary sample coordinates (src/bpt_samplers.h:43-88) with the per-frame table folded in
-__device__ __forceinline__ float light_coord(const BptParams& P, PathRef r, uint32_t vertex, uint32_t dim)
-{
-	const uint32_t T2 = P.seq.tile_size * P.seq.tile_size, d = vertex * 3 + dim;
-	return frac_pos(randfloat(d, P.instance + r.k + 1) + P.seq.shifts[size_t(d) * T2 + (r.id & (T2 - 1u))]);
-}
-__device__ __forceinline__ float tiled_coord(const BptParams& P, uint32_t k, uint32_t px, uint32_t py, uint32_t dim)
-{
-	const uint32_t T = P.seq.tile_size;
-	const uint32_t shift = (px & (T - 1)) + (py & (T - 1)) * T;
-	const uint32_t tile  = ((px / T) & (T - 1)) + ((py / T) & (T - 1)) * T;
-	const size_t base = size_t(dim) * T * T;
-	const float sample = frac_pos(randfloat(dim, P.instance + k + 1) + P.seq.shifts[base + shift]);
-	return frac_pos(sample + P.seq.shifts[base + tile]);
-}
-__device__ __forceinline__ float eye_coord(const BptParams& P, uint32_t k, uint32_t px, uint32_t py, uint32_t vertex, uint32_t dim)
-{
-	if (vertex == 1 && dim < 2)
-		return dim == 0 ? (float(px) + tiled_coord(P, k, px, py, dim)) / float(P.res_x) : (float(py) + tiled_coord(P, k, px, py, dim)) / float(P.res_y);
-	return tiled_coord(P, k, px, py, (vertex - 1) * 6 + dim);
-}
 
 // ---- queue-slot allocation -----------------------------------------------------------------------------------------------------
 // every thread asks for `n` CONTIGUOUS slots; one atomic per workgroup
@@ -312,8 +284,20 @@ __device__ __forceinline__ f3 connect(const BptParams& P, const Vertex& ev, uint
 
 // ConnectionsSink<false>::sink (src/renderers/bpt_impl.h:131-163): all four components, COMPOSITED_C and the path's channel.  One pass per render():
 // straight into the frame; passes in flight: into the eye path's cell `cell` of the batch's log (BptLog), applied in order by merge_exact_kernel
+// MLT, value sink set (fpt_bpt.h ValueSink): the sample joins the eye path's value and nothing else is touched.  The plain read-modify-write is free of races:
+// eye_vertices_kernel and eye_resolve_kernel run one thread per queue entry, a path owns at most one entry of a queue, and the launches of a pass are
+// ordered on one stream -- at any time one thread at most holds a given path
+template <bool MLT>
 __device__ __forceinline__ void sink(const BptParams& P, uint32_t channel, f3 v, float w, uint32_t vid, uint32_t cell)
 {
+	if (MLT && P.value.value)
+	{
+		float4* c = P.value.value + path_ref(P, vid).id;
+		float4 a = *c;
+		a.x += v.x; a.y += v.y; a.z += v.z; a.w += w;
+		*c = a;
+		return;
+	}
 	if (P.n_passes > 1)
 	{
 		P.log.val[size_t(cell) * P.log.cap + vid] = make_float4(v.x, v.y, v.z, w);
@@ -338,6 +322,7 @@ __device__ __forceinline__ void sink(const BptParams& P, uint32_t channel, f3 v,
 }
 
 // ---- kernels -------------------------------------------------------------------------------------------------------------------
+template <bool MLT>
 __global__ void __launch_bounds__(BPT_BLOCK) light_primary_kernel(const BptParams P)
 {
 	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
@@ -356,13 +341,13 @@ __global__ void __launch_bounds__(BPT_BLOCK) light_primary_kernel(const BptParam
 		emitter_at(P.emitters, P.mesh, P.textures, vp.prim_id, lp.s, lp.t, radiance, pdf);
 	}
 	else
-		emitter_sample(P.emitters, P.mesh, P.textures, light_coord(P, r, 0, 0), light_coord(P, r, 0, 1), light_coord(P, r, 0, 2), lp, radiance, pdf);
+		emitter_sample(P.emitters, P.mesh, P.textures, light_coord<MLT>(P, r, 0, 0), light_coord<MLT>(P, r, 0, 1), light_coord<MLT>(P, r, 0, 2), lp, radiance, pdf);
 	store_vertex(P, vid, make_float4(lp.position.x, lp.position.y, lp.position.z, as_f32(pack_direction(lp.frame.n))), make_uint4(to_rgbe(radiance), 0, 0, 0),
 	             make_uint2(0u, to_rgbe(splat3(1.0f) / pdf)), make_float2(0.0f, 1.0f * pdf), id);
 	P.store.counts[vid] = 1;
 	if (1 >= L + 1) return;
 	// Edf::sample: cosine-distributed emission (contrib/cugar/bsdf/lambert_edf.h:82-99)
-	const f3 l = cosine_hemisphere(light_coord(P, r, 1, 0), light_coord(P, r, 1, 1));
+	const f3 l = cosine_hemisphere(light_coord<MLT>(P, r, 1, 0), light_coord<MLT>(P, r, 1, 1));
 	const f3 out = l.x * lp.frame.t + l.y * lp.frame.b + l.z * lp.frame.n;
 	const f3 g = (radiance * kPi) / pdf;
 	const float p_proj = 1.0f / kPi;
@@ -373,6 +358,7 @@ __global__ void __launch_bounds__(BPT_BLOCK) light_primary_kernel(const BptParam
 	if (i == 0) *P.out.size = P.n_local * P.n_passes;
 }
 
+template <bool MLT>
 __global__ void __launch_bounds__(BPT_BLOCK) light_vertices_kernel(const BptParams P)
 {
 	__shared__ RangeScratch sc;
@@ -396,7 +382,7 @@ __global__ void __launch_bounds__(BPT_BLOCK) light_vertices_kernel(const BptPara
 			if (P.bounce + 2 < P.opt.max_path_length + 1)
 			{
 				f3 out, g; float p, p_proj;
-				const uint32_t comp = surface_sample_ex(lv.bsdf, lv.sp.frame, light_coord(P, r, P.bounce + 2, 0), light_coord(P, r, P.bounce + 2, 1), light_coord(P, r, P.bounce + 2, 2),
+				const uint32_t comp = surface_sample_ex(lv.bsdf, lv.sp.frame, light_coord<MLT>(P, r, P.bounce + 2, 0), light_coord<MLT>(P, r, P.bounce + 2, 1), light_coord<MLT>(P, r, P.bounce + 2, 2),
 				                                        lv.in, P.opt.rr != 0, true, true, out, p, p_proj, g);
 				(void)comp;
 				const f3 out_w = g * lv.alpha;
@@ -422,6 +408,7 @@ __global__ void __launch_bounds__(BPT_BLOCK) light_vertices_kernel(const BptPara
 	}
 }
 
+template <bool MLT>
 __global__ void __launch_bounds__(BPT_BLOCK) eye_primary_kernel(const BptParams P)
 {
 	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
@@ -429,7 +416,8 @@ __global__ void __launch_bounds__(BPT_BLOCK) eye_primary_kernel(const BptParams 
 	const uint32_t k = i / P.n_local, li = i - k * P.n_local;
 	const uint32_t idx = P.pixels ? P.pixels[li] : li;
 	const uint32_t px = idx % P.res_x, py = idx / P.res_x;
-	const float ux = eye_coord(P, k, px, py, 1, 0), uy = eye_coord(P, k, px, py, 1, 1);
+	// chain mode: eye path idx is the chain, its screen position the chain's coordinates 3 and 4 (eye vertex 1); (px, py) is not read
+	const float ux = eye_coord<MLT>(P, k, idx, px, py, 1, 0), uy = eye_coord<MLT>(P, k, idx, px, py, 1, 1);
 	const float dx = ux * 2.f - 1.f, dy = uy * 2.f - 1.f;
 	const f3 dir = dx * P.U + dy * P.V + P.W;
 	write_ray(P.out.rays, i, P.eye, 0.0f, dir, 1e34f);
@@ -444,6 +432,7 @@ __global__ void __launch_bounds__(BPT_BLOCK) eye_primary_kernel(const BptParams 
 #ifndef FPT_BPT_EYE_WAVES
 #define FPT_BPT_EYE_WAVES 3      // 168 VGPRs instead of 176: 3 waves per SIMD, measured +5 % on the BPT pass (4 waves spill too much: -11 %)
 #endif
+template <bool MLT>
 __global__ void __launch_bounds__(BPT_BLOCK, FPT_BPT_EYE_WAVES) eye_vertices_kernel(const BptParams P)
 {
 	__shared__ RangeScratch sc, sc2;
@@ -481,7 +470,7 @@ __global__ void __launch_bounds__(BPT_BLOCK, FPT_BPT_EYE_WAVES) eye_vertices_ker
 			if (P.bounce + 2 < L + 1)
 			{
 				f3 out, g; float p, p_proj;
-				const uint32_t comp = surface_sample_ex(ev.bsdf, ev.sp.frame, eye_coord(P, pr.k, px, py, P.bounce + 2, 0), eye_coord(P, pr.k, px, py, P.bounce + 2, 1), eye_coord(P, pr.k, px, py, P.bounce + 2, 2),
+				const uint32_t comp = surface_sample_ex(ev.bsdf, ev.sp.frame, eye_coord<MLT>(P, pr.k, pixel, px, py, P.bounce + 2, 0), eye_coord<MLT>(P, pr.k, pixel, px, py, P.bounce + 2, 1), eye_coord<MLT>(P, pr.k, pixel, px, py, P.bounce + 2, 2),
 				                                        ev.in, P.opt.rr != 0, true, false, out, p, p_proj, g);
 				const f3 out_w = g * ev.alpha;
 				if (max_comp(out_w) > 0.0f)
@@ -489,7 +478,7 @@ __global__ void __launch_bounds__(BPT_BLOCK, FPT_BPT_EYE_WAVES) eye_vertices_ker
 					if (P.bounce + 2 == 2)          // sink_eye_scattering_event: albedo of the visible surface (src/renderers/bpt_impl.h:167-186)
 					{
 						const int ch = comp == COMP_DIFF_R ? FPT_FB_DIFFUSE_A : (comp == COMP_GLOSSY_R ? FPT_FB_SPECULAR_A : -1);
-						if (ch >= 0)
+						if (ch >= 0 && !(MLT && P.value.value))          // a value sink keeps no albedo planes
 						{
 							float4* cell = fb_cell(P, uint32_t(ch), pr);
 							const float fw = frame_weight(P, pr.k);
@@ -517,7 +506,7 @@ __global__ void __launch_bounds__(BPT_BLOCK, FPT_BPT_EYE_WAVES) eye_vertices_ker
 				const float prev_pGp = pdf2(ev.prev_pG, p_L);
 				const float mis_w = (P.bounce == 0 || pGp == 0.0f || (P.bounce == 1 && !P.opt.direct_lighting_nee) || (P.bounce > 1 && !P.opt.indirect_lighting_nee)) ? 1.0f : mis3(pGp, prev_pGp, ev.pGp_sum);
 				const f3 e = ev.alpha * f_L * mis_w;
-				if (max_comp(e) > 0.0f && finite3(e)) sink(P, chan & 0xFu, e, w_alpha, vid, P.bounce * (1u + P.log.conn_cells));
+				if (max_comp(e) > 0.0f && finite3(e)) sink<MLT>(P, chan & 0xFu, e, w_alpha, vid, P.bounce * (1u + P.log.conn_cells));
 			}
 			// how many light vertices this eye vertex may connect to
 			const int32_t max_light_depth = int32_t(L + 1) - int32_t(P.bounce) - 2 - 1;
@@ -556,7 +545,7 @@ __global__ void __launch_bounds__(BPT_BLOCK, FPT_BPT_EYE_WAVES) eye_vertices_ker
 				// a light vertex drawn uniformly from ALL stored vertices of this pass, weighted #vertices / #light paths (src/bpt_kernels.h:714-760)
 				const uint32_t first = P.flat_meta[2 * pr.k], n_vertices = P.flat_meta[2 * (pr.k + 1)] - first, n_primary = P.flat_meta[2 * pr.k + 1] - first;
 				const uint32_t px = pixel % P.res_x, py = pixel / P.res_x;
-				light_slot = P.flat[first + quantize(eye_coord(P, pr.k, px, py, P.bounce + 2, 5), n_vertices)];
+				light_slot = P.flat[first + quantize(eye_coord<MLT>(P, pr.k, pixel, px, py, P.bounce + 2, 5), n_vertices)];
 				light_depth = P.store.rec[light_slot].path_id >> 24;
 				light_weight = float(n_vertices) / float(n_primary);
 			}
@@ -582,6 +571,7 @@ __global__ void __launch_bounds__(BPT_BLOCK, FPT_BPT_EYE_WAVES) eye_vertices_ker
 }
 
 // one thread per eye vertex: its visible connections are added in light-depth order
+template <bool MLT>
 __global__ void __launch_bounds__(BPT_BLOCK) eye_resolve_kernel(const BptParams P)
 {
 	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
@@ -596,7 +586,7 @@ __global__ void __launch_bounds__(BPT_BLOCK) eye_resolve_kernel(const BptParams 
 		// an occluded connection adds zeros: no cell.  (One pass per render() adds w * 0 instead, which differs only for a non-finite weight -- NaN there, nothing
 		// here: the bit-identity of batched and sequential passes is for finite samples, as include/fermat_pt_hip.h says)
 		if (P.n_passes > 1 && vis == 0.0f) continue;
-		sink(P, ch & 0xFu, mk3(w.x * vis, w.y * vis, w.z * vis), w.w * vis, pi, P.bounce * (1u + P.log.conn_cells) + 1u + k);
+		sink<MLT>(P, ch & 0xFu, mk3(w.x * vis, w.y * vis, w.z * vis), w.w * vis, pi, P.bounce * (1u + P.log.conn_cells) + 1u + k);
 	}
 }
 
@@ -793,16 +783,6 @@ __global__ void __launch_bounds__(BPT_BLOCK) connect_camera_kernel(const BptPara
 	}
 }
 
-// one splat entry in 2^-32 fixed point, by the rule of include/fermat_pt_hip.h ("light-tracing splats"): weight x frame weight in float, x 2^32 in double
-// (exact), rounded half to even; a value outside int64 saturates at its end of the range and a NaN adds nothing (C++ leaves both casts undefined)
-__device__ __forceinline__ long long splat_fixed(float v)
-{
-	const double x = double(v) * 4294967296.0;
-	if (x != x) return 0;
-	if (x >= 9223372036854775808.0) return 0x7FFFFFFFFFFFFFFFll;
-	if (x <= -9223372036854775808.0) return -0x7FFFFFFFFFFFFFFFll - 1;
-	return __double2ll_rn(x);
-}
 __device__ __forceinline__ void splat_fixed3(float4 w, float fw, long long q[3]) { q[0] = splat_fixed(w.x * fw); q[1] = splat_fixed(w.y * fw); q[2] = splat_fixed(w.z * fw); }
 
 // ConnectionsSink<true>: xyz of COMPOSITED_C and DIRECT_C, as order-independent 2^-32 fixed-point sums
@@ -1009,11 +989,15 @@ inline dim3 grid_for(uint32_t n) { return dim3((n + BPT_BLOCK - 1) / BPT_BLOCK);
 
 } // namespace
 
-void launch_bpt_light_primary(const BptParams& p, hipStream_t s) { hipLaunchKernelGGL(light_primary_kernel, grid_for(p.n_local * p.n_passes), dim3(BPT_BLOCK), 0, s, p); }
-void launch_bpt_light_vertices(const BptParams& p, uint32_t max_entries, hipStream_t s) { hipLaunchKernelGGL(light_vertices_kernel, grid_for(max_entries), dim3(BPT_BLOCK), 0, s, p); }
-void launch_bpt_eye_primary(const BptParams& p, hipStream_t s) { hipLaunchKernelGGL(eye_primary_kernel, grid_for(p.n_local * p.n_passes), dim3(BPT_BLOCK), 0, s, p); }
-void launch_bpt_eye_vertices(const BptParams& p, uint32_t max_entries, hipStream_t s) { hipLaunchKernelGGL(eye_vertices_kernel, grid_for(max_entries), dim3(BPT_BLOCK), 0, s, p); }
-void launch_bpt_eye_resolve(const BptParams& p, uint32_t max_entries, hipStream_t s) { hipLaunchKernelGGL(eye_resolve_kernel, grid_for(max_entries), dim3(BPT_BLOCK), 0, s, p); }
+// the Metropolis renderer's parameter blocks (a chain or a value sink set) run the MLT instantiation, `-bpt`'s the other
+static bool mlt_block(const BptParams& p) { return p.chain.light_u != nullptr || p.value.value != nullptr; }
+#define FPT_BPT_LAUNCH(kernel, n) do { if (mlt_block(p)) hipLaunchKernelGGL(kernel<true>, grid_for(n), dim3(BPT_BLOCK), 0, s, p); \
+                                       else hipLaunchKernelGGL(kernel<false>, grid_for(n), dim3(BPT_BLOCK), 0, s, p); } while (0)
+void launch_bpt_light_primary(const BptParams& p, hipStream_t s) { FPT_BPT_LAUNCH(light_primary_kernel, p.n_local * p.n_passes); }
+void launch_bpt_light_vertices(const BptParams& p, uint32_t max_entries, hipStream_t s) { FPT_BPT_LAUNCH(light_vertices_kernel, max_entries); }
+void launch_bpt_eye_primary(const BptParams& p, hipStream_t s) { FPT_BPT_LAUNCH(eye_primary_kernel, p.n_local * p.n_passes); }
+void launch_bpt_eye_vertices(const BptParams& p, uint32_t max_entries, hipStream_t s) { FPT_BPT_LAUNCH(eye_vertices_kernel, max_entries); }
+void launch_bpt_eye_resolve(const BptParams& p, uint32_t max_entries, hipStream_t s) { FPT_BPT_LAUNCH(eye_resolve_kernel, max_entries); }
 void launch_bpt_pack_light_vertices(const LightVertexRecord* rec, const uint32_t* counts, const uint32_t* pixels, uint32_t n_local, uint32_t n_paths, uint32_t n_passes,
                                     LightVertexWire* out, uint32_t* out_count, hipStream_t s)
 { hipLaunchKernelGGL(pack_light_vertices_kernel, grid_for(n_local * n_passes), dim3(BPT_BLOCK), 0, s, rec, counts, pixels, n_local, n_paths, n_passes, out, out_count); }

@@ -83,7 +83,7 @@ template <typename V> void each_array(fpt_context::BptState& b, size_t L, size_t
 void alloc_storage(fpt_context* ctx, uint32_t passes)
 {
 	fpt_context::BptState& b = ctx->bpt;
-	const size_t nl = size_t(b.n_local) * passes, np = size_t(b.n_paths) * passes, L = b.opt.max_path_length;
+	const size_t nl = size_t(std::max(b.n_local, b.min_paths)) * passes, np = size_t(std::max(b.n_paths, b.min_paths)) * passes, L = b.opt.max_path_length;
 	each_array(b, L, b.opt.single_connection ? 1 : 0, passes > 1, [&](auto& a, size_t per_local, size_t per_path) { a.alloc(per_local * nl + per_path * np); });
 	// -sc 1, not per path: per-block counts of the list's scan (4096 elements per block); per-pass bounds
 	if (b.opt.single_connection) { b.flat_block_sums.alloc((np * L + 4095) / 4096 + 1); b.flat_meta.alloc(2 * size_t(passes) + 2); }
@@ -94,12 +94,10 @@ void alloc_storage(fpt_context* ctx, uint32_t passes)
 
 } // namespace
 
-extern "C" {
-
-int fpt_bpt_init(fpt_context* ctx, const fpt_bpt_options* opts, const fpt_rendering_context_view* view, const char* h_samples_dir,
-                 const uint32_t* d_pixels, uint32_t n_local_pixels)
+namespace fpt {
+void bpt_init(fpt_context* ctx, const fpt_bpt_options* opts, const fpt_rendering_context_view* view, const char* h_samples_dir, const uint32_t* d_pixels, uint32_t n_local_pixels,
+              uint32_t min_paths)
 {
-	return guarded(ctx, [&] {
 		flush_deferred(ctx);
 		require(opts && view, "fpt_bpt_init: null argument");
 		require(opts->max_path_length >= 1 && opts->max_path_length <= 15, "fpt_bpt_init: max_path_length out of range [1,15] (the s,t technique ids are 4-bit)");
@@ -110,6 +108,7 @@ int fpt_bpt_init(fpt_context* ctx, const fpt_bpt_options* opts, const fpt_render
 		require(!opts->use_vpls || size_t(ctx->emitters.n_vpls) >= size_t(view->res_x) * view->res_y, "fpt_bpt_init: -use-vpls needs one VPL per pixel (fpt_mesh_lights_init with n_vpls >= res_x * res_y)");
 		fpt_context::BptState& b = ctx->bpt;
 		b.opt = *opts;
+		b.min_paths = min_paths;
 		b.n_paths = view->res_x * view->res_y;
 		b.n_local = d_pixels ? n_local_pixels : b.n_paths;
 		b.d_pixels = d_pixels;
@@ -126,7 +125,15 @@ int fpt_bpt_init(fpt_context* ctx, const fpt_bpt_options* opts, const fpt_render
 		build_shift_table(256, b.seq_dims, h_samples_dir, ctx->crt_rand, shifts);
 		b.d_shifts.upload(shifts.data(), shifts.size(), ctx->stream);
 		b.ready = true;
-	});
+}
+} // namespace fpt
+
+extern "C" {
+
+int fpt_bpt_init(fpt_context* ctx, const fpt_bpt_options* opts, const fpt_rendering_context_view* view, const char* h_samples_dir,
+                 const uint32_t* d_pixels, uint32_t n_local_pixels)
+{
+	return guarded(ctx, [&] { ctx->mlt.ready = false; bpt_init(ctx, opts, view, h_samples_dir, d_pixels, n_local_pixels, 0u); });
 }
 
 int fpt_bpt_set_profiling(fpt_context* ctx, int on) { return guarded(ctx, [&] { flush_deferred(ctx); ctx->bpt.profiling = on != 0; }); }
@@ -191,6 +198,16 @@ struct BptRun
 		camera_frame(view->camera, view->aspect, P.U, P.V, P.W);
 		P.W_len = length(P.W);
 		{ const float tn = tanf(view->camera.fov / 2); P.sq_focal = (1.0f / 4.0f) / (tn * tn); }           // Camera::square_screen_focal_length, src/camera.h:132-136
+	}
+	// the Metropolis renderer's wavefront: n light and eye sub-paths (path id = chain, or pixel when the coordinates are the tiled ones) into a value sink; no frame
+	// cells, albedo planes, gbuffer or log, and the splat sums are left to the caller
+	void for_value_sink(uint32_t n, const ChainCoords* chain, float4* value)
+	{
+		n_launch = n; prof = false;
+		P.n_local = P.n_paths = P.n_store = n; P.pixels = nullptr;
+		std::memset(&P.fb, 0, sizeof(P.fb));
+		if (chain) P.chain = *chain;
+		P.value.value = value;
 	}
 	void trace(const float4* rays, float4* hits, const uint32_t* count_ptr, bool any_hit)
 	{
@@ -283,6 +300,7 @@ struct BptRun
 			uint64_t total = 0; for (uint32_t c : counts) total += c;
 			st.n_light_vertices = uint32_t(total);
 		}
+		if (P.value.value) { FPT_HIP_CHECK(hipGetLastError()); return; }          // a value sink: the frame and the splat sums are the caller's
 		// the frame: light-tracing splats, then (batch) the planes in pass order.  Deferred mode leaves both to fpt_bpt_resolve_splats
 		b.pending_first = P.instance; b.pending_n = P.n_passes;
 		if (!b.deferred_splats || !b.light_tracing) resolve_splats(ctx, view);
@@ -310,6 +328,19 @@ static void render_impl(fpt_context* ctx, uint32_t instance, uint32_t n_passes, 
 
 } // extern "C"
 namespace fpt { void bpt_render_passes(fpt_context* ctx, uint32_t first, uint32_t n, const fpt_rendering_context_view* view) { render_impl(ctx, first, n, view); } }
+namespace fpt {
+void bpt_sample_paths(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view, uint32_t n, const ChainCoords* chain, float4* value, BptParams* tiled)
+{
+	fpt_context::BptState& b = ctx->bpt;
+	require(b.ready && b.max_batch == 1 && !b.d_pixels && !b.light_pending && b.pending_n == 0, "fpt_pssmlt: the bidirectional state is not the one fpt_pssmlt_init made");
+	require(value != nullptr && (n ? n : b.n_paths) <= std::max(b.n_paths, b.min_paths), "fpt_pssmlt: more paths than the storage holds");
+	BptRun run(ctx, instance, 1, view);
+	if (tiled) *tiled = run.P;
+	run.for_value_sink(n ? n : b.n_paths, chain, value);
+	run.light_phase();
+	run.rest(view);
+}
+}
 extern "C" {
 
 int fpt_bpt_render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view)

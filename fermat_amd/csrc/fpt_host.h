@@ -350,6 +350,7 @@ struct fpt_context
 		bool ready = false, profiling = false, deferred_splats = false;
 		fpt_bpt_options opt{};
 		uint32_t n_local = 0, n_paths = 0;
+		uint32_t min_paths = 0;                              // the arrays hold at least this many paths per pass (the Metropolis renderer's chains may outnumber the pixels)
 		const uint32_t* d_pixels = nullptr;
 		float light_tracing = 0.0f;
 		fpt::DeviceArray<float> d_shifts; uint32_t seq_dims = 0;
@@ -374,6 +375,19 @@ struct fpt_context
 		uint32_t light_instance = 0, light_passes = 0;
 		fpt::DeviceArray<fpt::LightVertexWire> lv_send, lv_recv; fpt::DeviceArray<uint32_t> lv_count;
 	} bpt;
+	// primary-sample-space Metropolis renderer (fpt_mlt_api.cpp) on the bidirectional state above
+	struct MltState
+	{
+		bool ready = false;
+		fpt_pssmlt_options opt{};
+		uint32_t n_pixels = 0, n_chains = 0, chain_length = 0;
+		fpt::DeviceArray<float4> presample, new_value, path_value;       // per pixel; per chain (new_value: max(n_pixels, n_chains), fpt_pssmlt_debug_eval)
+		fpt::DeviceArray<float> light_u, eye_u, path_pdf;                  // (L+1)*3 x max(n_pixels, n_chains); n_chains
+		fpt::DeviceArray<uint32_t> rejections, seeds;
+		fpt::DeviceArray<unsigned long long> q, cdf, counts;               // the seed CDF and its terms (n_pixels); accepted, rejected, + the CDF's total read back
+		fpt::DeviceArray<uint8_t> scan_scratch;
+		fpt_pssmlt_stats stats{};
+	} mlt;
 	bool profiling = false;
 	int capture_bounce = -1;
 	uint32_t captured_count = 0;
@@ -431,6 +445,13 @@ namespace fpt { void resize_wavefront(fpt_context* ctx, uint32_t passes, const f
                 void set_batch(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_context_view* view, bool for_psfpt); }
 // fpt_bpt_api.cpp: what fpt_bpt_set_batch allocates per path in flight, with every pixel rendered here
 namespace fpt { uint64_t bpt_bytes_per_path(fpt_context* ctx); }
+// fpt_bpt_api.cpp, for the Metropolis renderer (inside the caller's `guarded`).  bpt_init: fpt_bpt_init's body, storage for at least `min_paths` paths.
+// bpt_sample_paths: one bidirectional wavefront (BptRun: light_phase, rest) of `n` light and eye sub-paths -- n = 0: the frame's pixels -- whose samples go to
+// `value` (ValueSink) and whose coordinates come from `chain` (ChainCoords) or, chain == NULL, from the tiled sequence; the frame is not touched.  `tiled`, when
+// given, receives the parameter block of the tiled pass (what launch_mlt_recover_coordinates reads)
+namespace fpt { void bpt_init(fpt_context* ctx, const fpt_bpt_options* opts, const fpt_rendering_context_view* view, const char* h_samples_dir, const uint32_t* d_pixels,
+                              uint32_t n_local_pixels, uint32_t min_paths);
+                void bpt_sample_paths(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view, uint32_t n, const ChainCoords* chain, float4* value, BptParams* tiled); }
 
 // ---- helpers shared by the C-ABI translation units (fpt_api.cpp, fpt_bpt_api.cpp) -------------------------------------------------
 template <typename F>

@@ -96,6 +96,7 @@ void RenderingContext::init(int argc, char** argv, const SceneArrays& scene)
 	register_renderer("pt", &HipPathTracer::factory);
 	register_renderer("bpt", &HipBPT::factory);
 	register_renderer("psfpt", &HipPSFPT::factory);
+	register_renderer("pssmlt", &HipPSSMLT::factory);
 	int device = 0;
 	uint32 renderer_type = 0;
 	for (int i = 0; i < argc; ++i)                           // flag loop, src/renderer.cu:493-539 (unknown flags are ignored)
@@ -376,6 +377,7 @@ static void rebuild_emitters(RenderingContext& renderer, const char* who)
 void HipPathTracer::update_scene(RenderingContext& renderer) { rebuild_emitters(renderer, "PathTracer::update_scene"); }
 void HipPSFPT::update_scene(RenderingContext& renderer) { rebuild_emitters(renderer, "PSFPT::update_scene"); }
 void HipBPT::update_scene(RenderingContext& renderer) { rebuild_emitters(renderer, "BPT::update_scene"); }
+void HipPSSMLT::update_scene(RenderingContext& renderer) { rebuild_emitters(renderer, "PSSMLT::update_scene"); }
 
 void HipPathTracer::render(const uint32 instance, RenderingContext& renderer)
 {
@@ -521,6 +523,47 @@ void HipBPT::init(int argc, char** argv, RenderingContext& renderer)
 	// does not depend on the number of GPUs
 	m_shared_lv = renderer.world_size() > 1 && o.single_connection;
 	if (m_shared_lv) check(ctx, fpt_bpt_set_shared_light_vertices(ctx, 1), "BPT::init (shared light vertices)");
+}
+
+// ---- HipPSSMLT ---------------------------------------------------------------------------------------------------------------
+void HipPSSMLT::init(int argc, char** argv, RenderingContext& renderer)
+{
+	// BPTOptionsBase + PSSMLTOptions defaults and parse (src/bpt_options.h:42-92, src/renderers/pssmlt.h:54-99)
+	fpt_pssmlt_options& p = m_options;
+	fpt_bpt_options& o = p.bpt;
+	o.max_path_length = 6; o.direct_lighting_nee = 1; o.direct_lighting_bsdf = 1; o.indirect_lighting_nee = 1; o.indirect_lighting_bsdf = 1;
+	o.visible_lights = 1; o.use_vpls = 0; o.rr = 1; o.light_tracing = 0.0f; o.single_connection = 0;
+	p.n_chains = 64 * 1024; p.spp = 4; p.light_perturbations = 1; p.eye_perturbations = 1; p.independent_samples = 0.0f; p.radius = 0.01f;
+	for (int i = 0; i < argc; ++i)
+	{
+		auto is = [&](const char* f) { return std::strcmp(argv[i], f) == 0 && i + 1 < argc; };
+		if (is("-pl") || is("-path-length") || is("-max-path-length")) o.max_path_length = uint32(std::atoi(argv[++i]));
+		else if (is("-bounces")) o.max_path_length = uint32(std::atoi(argv[++i]) + 1);
+		else if (is("-nee")) o.direct_lighting_nee = o.indirect_lighting_nee = std::atoi(argv[++i]) > 0;
+		else if (is("-direct-nee")) o.direct_lighting_nee = std::atoi(argv[++i]) > 0;
+		else if (is("-direct-bsdf")) o.direct_lighting_bsdf = std::atoi(argv[++i]) > 0;
+		else if (is("-indirect-nee")) o.indirect_lighting_nee = std::atoi(argv[++i]) > 0;
+		else if (is("-indirect-bsdf")) o.indirect_lighting_bsdf = std::atoi(argv[++i]) > 0;
+		else if (is("-visible-lights")) o.visible_lights = std::atoi(argv[++i]) > 0;
+		else if (is("-use-vpls")) o.use_vpls = std::atoi(argv[++i]) > 0;
+		else if (is("-chains")) p.n_chains = uint32(std::atoi(argv[++i])) * 1024u;
+		else if (is("-spp")) p.spp = uint32(std::atoi(argv[++i]));
+		else if (is("-rr") || is("-RR")) o.rr = std::atoi(argv[++i]) > 0;
+		else if (is("-light-perturbations")) p.light_perturbations = std::atoi(argv[++i]) > 0;
+		else if (is("-eye-perturbations")) p.eye_perturbations = std::atoi(argv[++i]) > 0;
+		else if (is("-perturbations")) p.light_perturbations = p.eye_perturbations = std::atoi(argv[++i]) > 0;
+		else if (is("-independent-samples") || is("-independent") || is("-is")) p.independent_samples = float(std::atof(argv[++i]));
+	}
+	fpt_context* ctx = renderer.get_hip_context();
+	const fpt_rendering_context_view v = renderer.view(0);
+	const SceneArrays& h = renderer.get_host_scene();
+	renderer.init_mesh_lights("mesh_lights.init");     // src/renderers/pssmlt.cu:465
+	check(ctx, fpt_pssmlt_init(ctx, &p, &v, h.samples_dir, renderer.shard_pixels(), renderer.shard_count()), "PSSMLT::init");
+}
+void HipPSSMLT::render(const uint32 instance, RenderingContext& renderer)
+{
+	const fpt_rendering_context_view v = renderer.view(instance);
+	check(renderer.get_hip_context(), fpt_pssmlt_render(renderer.get_hip_context(), instance, &v), "PSSMLT::render");
 }
 
 // the integer all-reduce of the light-tracing splat sums (3 x int64 per pixel per pass in flight), then the fold into the frame

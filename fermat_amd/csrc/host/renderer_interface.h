@@ -209,6 +209,19 @@ struct HipBPT final : RendererInterface
 	void finish_sharded_pass(fpt_context* ctx, const fpt_rendering_context_view& v, uint32 passes_in_flight);
 };
 
+// the primary-sample-space Metropolis renderer behind RendererInterface (PSSMLT, src/renderers/pssmlt.h:101-130); `-pssmlt` on the command line.  One GPU, one
+// render call per pass (no passes in flight): include/fermat_pt_hip.h says what is and is not built
+struct HipPSSMLT final : RendererInterface
+{
+	void init(int argc, char** argv, RenderingContext& renderer) override;
+	void update_scene(RenderingContext& renderer) override;      // as HipPathTracer's
+	void render(const uint32 instance, RenderingContext& renderer) override;
+	void destroy() override { delete this; }
+	static RendererInterface* factory() { return new HipPSSMLT(); }
+
+	fpt_pssmlt_options m_options;
+};
+
 } // namespace fermat
 
 // plugin entry point with the reference's name and meaning (src/renderers/hellopt_plugin.cpp:35-39)

@@ -383,6 +383,56 @@ int fpt_bpt_use_splat_buffer(fpt_context* ctx, int64_t* d_splats);       /* call
 int fpt_bpt_set_deferred_splats(fpt_context* ctx, int deferred);
 int fpt_bpt_resolve_splats(fpt_context* ctx, const fpt_rendering_context_view* view);
 
+/* ---- primary-sample-space Metropolis light transport (`-pssmlt`, src/renderers/pssmlt.{h,cu}) on the bidirectional kernels ----------------------
+ * One render call = PSSMLT::render (pssmlt.cu:541-700): the frame is rescaled by instance / (instance + 1); a presampling BPT pass over the pixels keeps every
+ * eye path's summed value; an integer CDF over those values draws n_chains seed paths; their primary sample coordinates are recovered; every chain then takes
+ * chain_length = spp * n_pixels / n_chains Metropolis steps (step 0 re-evaluates the seed, later steps propose an Independent sample with probability
+ * independent_samples, a Cauchy perturbation of radius `radius` otherwise), each step one bidirectional wavefront of n_chains light and eye sub-paths followed by
+ * the acceptance test, which splats the weighted old and new values to their pixels; the sums are folded into COMPOSITED_C (xyz only, the one channel the
+ * reference writes) at the end of the call.  Forced as in the reference: light_tracing = 0, single_connection = 0 (all connections, kPathOrdering).
+ * Deviations from the reference, each so that the frame is bit-reproducible:
+ *   1. mutation numbers are a counter-based function of (instance, step, chain, dimension) -- randfloat(chain, hash32(hash32(hash32(instance) + step) + dim)) --
+ *      computed where they are read, not a stored cuRAND stream; the accept/reject number is dimension (L + 1) * 6.  The step's mutation type is the host function
+ *      randfloat(step, hash32(instance + 0x9e3779b9)) < independent_samples
+ *   2. the seed CDF is the inclusive scan of floor(min(max_comp(value), 2^31) * 2^32) as uint64 (0 for a negative or non-finite value; sums wrap modulo 2^64);
+ *      image_brightness = float(double(total) * 2^-32 / n_pixels)
+ *   3. the chains' splats are the 2^-32 fixed-point integer sums of the light-tracing splats (above), not float atomics.
+ * Not built: the per-(s,t) statistics the reference prints (st_norms), passes in flight, deferral, tile sharding / multi-GPU, use_vpls.
+ * fpt_pssmlt_init replaces fpt_bpt_init (it initialises the bidirectional state itself, sized for max(n_pixels, n_chains) paths) and refuses, with a message that
+ * names the option: bpt.use_vpls = 1, a tile-sharded context (d_pixels != NULL), n_chains = 0, spp * n_pixels < n_chains. */
+typedef struct fpt_pssmlt_options
+{
+	fpt_bpt_options bpt;
+	uint32_t n_chains, spp, light_perturbations, eye_perturbations;
+	float independent_samples, radius;
+} fpt_pssmlt_options;
+typedef struct fpt_pssmlt_stats
+{
+	float image_brightness, pdf_norm;      /* of the last render call */
+	uint32_t chain_length, n_chains;
+	uint64_t accepted, rejected;           /* proposals of the last render call, step 0 included */
+} fpt_pssmlt_stats;
+int fpt_pssmlt_init(fpt_context* ctx, const fpt_pssmlt_options* opts, const fpt_rendering_context_view* view, const char* h_samples_dir,
+                    const uint32_t* d_pixels, uint32_t n_local_pixels);      /* d_pixels: as fpt_bpt_init's, and must be NULL */
+int fpt_pssmlt_render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view);
+int fpt_pssmlt_get_stats(fpt_context* ctx, fpt_pssmlt_stats* out);
+/* the state the last render call left (any pointer may be NULL): the chains' coordinates ((L+1)*3 dims each, dim * n_chains + chain), values, pdfs, rejection counters
+ * and seeds (n_chains each), and the presampling pass's value per pixel */
+int fpt_pssmlt_download(fpt_context* ctx, float* h_light_u, float* h_eye_u, float* h_path_value /*float4*/,
+                        float* h_path_pdf, uint32_t* h_rejections, uint32_t* h_seeds,
+                        float* h_presample /*float4 per pixel*/);
+/* evaluate n caller-given coordinate sets (host arrays laid out dim * n + set, n <= max(n_pixels, n_chains)) through the chain-mode pipeline, mutation Null (tests);
+ * the chains' own state is not touched */
+int fpt_pssmlt_debug_eval(fpt_context* ctx, const fpt_rendering_context_view* view, uint32_t n, const float* h_light_u, const float* h_eye_u, float* h_value /*float4*/);
+/* probe of the Metropolis kernels; h_arrays holds DEVICE pointers.
+ *   op 0  perturbed_u: params {mutation, instance, step, radius bits}; arrays {u, m_in or NULL, chain, dim, out, m_out}: out[i] = perturbed_u(u[i], m), m = m_in[i] or the
+ *         mutation number of (instance, step, chain[i], dim[i]); m_out[i] = m
+ *   op 1  seed_cdf + sample_seeds: n values; params {n_seeds}; arrays {value float4 n, cdf uint64 n, seeds uint32 n_seeds}
+ *   op 2  accept_reject + resolve on hand-made chains: n chains; params {max_path_length, instance, step, mutation, light_perturbations, eye_perturbations, radius bits,
+ *         pdf_norm bits, res_x, res_y}; arrays {light_u, eye_u, new_value float4, path_value float4, path_pdf, rejections, splat int64 3 per pixel (zeroed by the caller),
+ *         splat_out (copy of the sums before the resolve), composited float4 per pixel, counts uint64[2]} */
+int fpt_debug_mlt(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_params, uint32_t n_params, void* const* h_arrays, uint32_t n_arrays);
+
 /* ---- multi-GPU: image tiles sharded over one process per GPU; replaces the single-GPU reference's cudaSetDevice(0) + whole-frame
  *      ownership (src/renderer.cu:600-603).  No data-path collective: each rank renders the pixels handed to fpt_pt_init / fpt_bpt_init
  *      with ABSOLUTE coordinates; once per output image the owned pixels travel to the root over RCCL (xGMI).  RCCL is dlopen'ed on first
