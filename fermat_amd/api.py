@@ -186,7 +186,13 @@ ENTRY_POINTS = ["fpt_create", "fpt_destroy", "fpt_last_error", "fpt_stream", "fp
                 "fpt_debug_build_emitter_tables", "fpt_clear_gbuffer", "fpt_rt_download_bvh", "fpt_mesh_lights_update", "fpt_rt_set_build_mode",
                 "fpt_mesh_lights_init_device", "fpt_mesh_lights_update_device", "fpt_rt_set_intersector", "fpt_rt_intersector",
                 "fpt_debug_psf", "fpt_psfpt_debug_set_table_log2", "fpt_debug_bpt", "fpt_debug_frame",
-                "fpt_pssmlt_init", "fpt_pssmlt_render", "fpt_pssmlt_get_stats", "fpt_pssmlt_download", "fpt_pssmlt_debug_eval", "fpt_debug_mlt"]
+                "fpt_pssmlt_init", "fpt_pssmlt_render", "fpt_pssmlt_get_stats", "fpt_pssmlt_download", "fpt_pssmlt_debug_eval", "fpt_debug_mlt", "fpt_debug_device_build"]
+
+# fpt_debug_device_build: the arrays of the last device build, by their `which` (name -> (which, dtype, columns)); rows: n triangles, n - 1 binary nodes or the wide nodes
+LBVH_CELL_DTYPE = np.dtype([("c", "<f4", 7), ("k", "u1", 7), ("k8", "u1"), ("leaf", "u1"), ("count", "u1"), ("spare", "u1", 2)])
+DEVICE_BUILD_ARRAYS = {"refs": (1, np.float32, 6), "bounds": (2, np.int32, 12), "keys": (3, np.uint64, 1), "vals": (4, np.uint32, 1), "left": (5, np.int32, 1),
+                       "right": (6, np.int32, 1), "node_box": (7, np.float32, 6), "cells": (8, LBVH_CELL_DTYPE, 1), "need": (9, np.uint32, 1), "tcount": (10, np.uint32, 1),
+                       "tcost": (11, np.float32, 1)}
 
 
 def kernel_source_hash():
@@ -748,6 +754,28 @@ class Renderer:
         nodes = np.zeros((nn.value, 20), np.uint32); recs = np.zeros((max(nt.value, 1), 12), np.float32)
         self._check(self.L.fpt_rt_download_bvh(self.ctx, C.c_void_p(nodes.ctypes.data), C.c_void_p(recs.ctypes.data)))
         return nodes, recs
+
+    def debug_build_arrays(self):
+        """the working arrays of the last DEVICE build of this context (fpt_debug_device_build; build modes 1 and 2), as the stages left them in the builder's scratch:
+        a dict of numpy arrays -- refs, bounds, keys, vals, left, right, node_box, cells (LBVH_CELL_DTYPE), need, in mode 2 also tcount and tcost -- and the description
+        words n, mode, nodes, passes, sort_buffer, depth_binary.  Raises FptError when the context holds no such build."""
+        d = np.zeros(16, np.uint32)
+        self._check(self.L.fpt_debug_device_build(self.ctx, C.c_uint32(0), C.c_void_p(d.ctypes.data), C.c_uint64(64)))
+        n, mode, n_nodes, cell_bytes = (int(x) for x in d[:4])
+        assert cell_bytes == LBVH_CELL_DTYPE.itemsize
+        out = dict(n=n, mode=mode, nodes=n_nodes, passes=int(d[4]), sort_buffer=int(d[5]), depth_binary=int(d[6]))
+        for name, (which, dt, cols) in DEVICE_BUILD_ARRAYS.items():
+            if which >= 10 and mode != 2:
+                continue
+            rows = 1 if name == "bounds" else n if which in (1, 3, 4) else n_nodes if name == "need" else n - 1
+            a = np.zeros((rows, cols) if cols > 1 else rows, dt)
+            self._check(self.L.fpt_debug_device_build(self.ctx, C.c_uint32(which), C.c_void_p(a.ctypes.data), C.c_uint64(a.nbytes)))
+            out[name] = a[0] if name == "bounds" else a
+        return out
+
+    def debug_set_treelet_passes(self, passes):
+        """the NEXT device build of this context runs `passes` (0..3) treelet passes instead of 3 (mode 2 only; consumed by that build)"""
+        self._check(self.L.fpt_debug_device_build(self.ctx, C.c_uint32(100 + int(passes)), None, C.c_uint64(0)))
 
     def clear_gbuffer_async(self):
         """the same clear as RenderingContextImpl::render issues it before every renderer->render (src/renderer.cu:1039): on the library's stream, no host synchronisation,

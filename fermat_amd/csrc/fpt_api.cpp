@@ -128,7 +128,7 @@ int fpt_rt_create_geometry(fpt_context* ctx, uint32_t tri_count, const int32_t* 
 // device builder's (none is in flight: a build returns only after its last read-back)
 int fpt_rt_set_build_mode(fpt_context* ctx, uint32_t mode)
 { return guarded(ctx, [&] { require(mode <= 2, "fpt_rt_set_build_mode: 0 = quality (host), 1 = fast (device), 2 = trbvh (device, treelet-restructured)");
-                            ctx->tree.build_mode = mode; if (mode == 0) ctx->tree.build_scratch.release(); }); }
+                            ctx->tree.build_mode = mode; if (mode == 0) ctx->tree.release_build_scratch(); }); }
 
 // Which intersector the NEXT fpt_rt_create_geometry writes its records for, in any build mode: 0 = fpt-MT (default), 1 = fpt-WT, watertight.  The live tree
 // is not touched: it keeps the intersector it was built for (AccelTree::info), through refits too, until a build replaces it
@@ -1026,6 +1026,38 @@ int fpt_debug_refit_bvh(uint32_t tri_count, const int32_t* h_idx, uint32_t verte
 {
 	if (!h_vtx1) { g_create_error = "fpt_debug_refit_bvh: null vertices"; return 1; }
 	return debug_bvh(tri_count, h_idx, vertex_count, h_vtx0, h_vtx1, n_nodes, n_records, depth, h_nodes, h_records, stats);
+}
+
+// read-only probe of the last device build's working arrays (tests/build_truth.py replays the builder stage by stage against them): copies, nothing else
+int fpt_debug_device_build(fpt_context* ctx, uint32_t which, void* h_out, uint64_t bytes)
+{
+	return guarded(ctx, [&] { flush_deferred(ctx);
+		AccelTree& T = ctx->tree;
+		if (which >= 100u)
+		{
+			require(which <= 103u && h_out == nullptr && bytes == 0, "fpt_debug_device_build: 100 + p sets p = 0..3 treelet passes for the next build and copies nothing");
+			T.debug_treelet_passes = which - 100u;
+			return;
+		}
+		const AccelTree::LastDeviceBuild& B = T.last_device_build;
+		require(B.valid && T.build_scratch.ptr != nullptr, "fpt_debug_device_build: the context holds no device build (fpt_rt_set_build_mode 1 or 2, then create_geometry)");
+		require(h_out != nullptr, "fpt_debug_device_build: null output");
+		if (which == 0u)
+		{
+			require(bytes == 64, "fpt_debug_device_build: the description is 16 words");
+			const uint32_t d[16] = { B.n, B.mode, B.n_nodes, B.cell_bytes, B.passes, B.sort_buffer, B.binary_depth, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+			std::memcpy(h_out, d, sizeof(d));
+			return;
+		}
+		require(which <= AccelTree::LastDeviceBuild::N_ARRAYS, "fpt_debug_device_build: unknown array");
+		const uint32_t a = which - 1u;
+		require(B.ptr[a] != nullptr && B.bytes[a] != 0, "fpt_debug_device_build: the last build has no such array (tcount and tcost exist in mode 2 only)");
+		require(bytes == B.bytes[a], "fpt_debug_device_build: `bytes` is not the array's size");
+		const uint8_t* lo = T.build_scratch.ptr; const uint8_t* p = static_cast<const uint8_t*>(B.ptr[a]);
+		require(p >= lo && p + B.bytes[a] <= lo + T.build_scratch.count, "fpt_debug_device_build: internal error (an array outside the scratch)");
+		FPT_HIP_CHECK(hipMemcpyAsync(h_out, p, B.bytes[a], hipMemcpyDeviceToHost, ctx->stream));
+		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	});
 }
 
 // the emitter-table builder without a context (CPU tests against the oracle, tools/time_emitters.py)

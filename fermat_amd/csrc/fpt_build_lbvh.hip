@@ -704,6 +704,7 @@ struct DeviceBuild
 	}
 	const unsigned long long* keys; const uint32_t* vals;          // between the stages: the sorted (code, triangle) pairs, ...
 	double area_before, area_after, area_leaves, seconds_opt; uint32_t fit_root_stamp, tri_total;
+	uint32_t passes;          // treelet passes of this build: kTreeletPasses, unless fpt_debug_device_build asked for fewer (tests pin a failure to a pass)
 	TreeInfo info;
 	double t0 = wall_seconds(), t_tree = 0.0, t_stage = 0.0, ms_stage[7] = { 0, 0, 0, 0, 0, 0, 0 };
 	const bool timers = std::getenv("FPT_BVH_TIMERS") != nullptr;
@@ -732,6 +733,8 @@ struct DeviceBuild
 		FPT_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, k, v, n, 0, 63, s));
 		FPT_HIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, (uint2*)nullptr, (uint2*)nullptr, make_uint2(0, 0), size_t(n), Uint2Plus(), s));
 		const size_t total = layout(nullptr);
+		T.last_device_build = AccelTree::LastDeviceBuild();          // this build overwrites the scratch: the probe's view of the last one ends here
+		passes = mode == 2 ? (T.debug_treelet_passes < kTreeletPasses ? T.debug_treelet_passes : kTreeletPasses) : 0u; T.debug_treelet_passes = kTreeletPasses;
 		if (T.build_scratch.count < total) T.build_scratch.alloc(total);
 		layout(T.build_scratch.ptr);
 		FPT_HIP_CHECK(hipMemsetAsync(status, 0, 64, s)); FPT_HIP_CHECK(hipMemsetAsync(flags, 0, size_t(n) * 4, s));
@@ -751,7 +754,7 @@ struct DeviceBuild
 		keys = kb.current(); vals = vb.current(); stage(2);
 	}
 	void radix_tree() { hipLaunchKernelGGL(lbvh_tree_kernel, G, B, 0, s, n, keys, left, right); stage(3); }
-	// 3b (mode 2): prep, kTreeletPasses restructuring passes, each bottom-up with fresh stamps (reset before each and before stage 4)
+	// 3b (mode 2): prep, `passes` (kTreeletPasses) restructuring passes, each bottom-up with fresh stamps (reset before each and before stage 4)
 	void restructure_by_treelets()
 	{
 		const double t_opt = wall_seconds();
@@ -769,7 +772,7 @@ struct DeviceBuild
 		bottom_up(runaway, [&](uint32_t r) { hipLaunchKernelGGL(trbvh_prep_round_kernel, G, B, 0, s, n, r, refs, vals, left, right, flags, node_box, tcount, tcost, bounds); });
 		summed_areas(area_before, area_leaves);
 		const uint32_t treelet_blocks = 2048;          // persistent: one wave per treelet, 8 per CU
-		for (uint32_t pass = 0, gamma = kGamma0; pass < kTreeletPasses; ++pass, gamma *= 2u)
+		for (uint32_t pass = 0, gamma = kGamma0; pass < passes; ++pass, gamma *= 2u)
 		{
 			FPT_HIP_CHECK(hipMemsetAsync(flags, 0, size_t(n) * 4, s));
 			FPT_HIP_CHECK(hipMemsetAsync(tlist_count, 0, size_t(kMaxRounds + 16) * sizeof(uint32_t), s));
@@ -846,10 +849,22 @@ struct DeviceBuild
 		if (mode == 2)
 		{
 			// comparable with the host build's statistics: re-insertion's measure before / after, the binary tree's SAH (all nodes' areas) and depth, the collapse's cost
-			info.opt_cost_before = float(area_before); info.opt_cost_after = float(area_after); info.opt_iterations = kTreeletPasses;
+			info.opt_cost_before = float(area_before); info.opt_cost_after = float(area_after); info.opt_iterations = passes;
 			info.seconds_opt = float(seconds_opt); info.seconds_bvh2 -= info.seconds_opt;
 			info.sah_cost = float(area_after + area_leaves); info.max_depth = fit_root_stamp;
 			info.wide_cost = h_root_cell.c[1];
+		}
+		// the build is complete in the scratch: where fpt_debug_device_build finds its arrays
+		{
+			typedef AccelTree::LastDeviceBuild V; V& v = ctx->tree.last_device_build;
+			const size_t nt = n, ni = nt - 1;
+			auto set = [&](uint32_t a, const void* p, size_t bytes) { v.ptr[a] = p; v.bytes[a] = bytes; };
+			set(V::REFS, refs, nt * sizeof(LbvhBox)); set(V::BOUNDS, bounds, 12 * sizeof(int)); set(V::KEYS, keys, nt * 8); set(V::VALS, vals, nt * 4);
+			set(V::LEFT, left, ni * 4); set(V::RIGHT, right, ni * 4); set(V::NODE_BOX, node_box, ni * sizeof(LbvhBox)); set(V::CELLS, cells, ni * sizeof(LbvhCell));
+			set(V::NEED, need, size_t(info.n_nodes) * 4);
+			if (mode == 2) { set(V::TCOUNT, tcount, ni * 4); set(V::TCOST, tcost, ni * 4); }
+			v.n = n; v.mode = mode; v.n_nodes = info.n_nodes; v.cell_bytes = uint32_t(sizeof(LbvhCell)); v.passes = passes; v.sort_buffer = keys == keys1 ? 1u : 0u;
+			v.binary_depth = fit_root_stamp; v.valid = true;
 		}
 	}
 	// the tree in exact-size arrays: the guarded section of the owner's contract (AccelTree::replace)
@@ -865,7 +880,7 @@ struct DeviceBuild
 		                                 "sort %.3f, radix tree %.3f, boxes + cost rows %.3f), emission + bound + copy %.3f ms\n",
 		                                 n, H.n_nodes, H.level_begin.size() - 1, H.stack_need, H.seconds_bvh2 * 1e3, ms_stage[0], ms_stage[1], ms_stage[2], ms_stage[3], ms_stage[4], H.seconds_wide * 1e3);
 		if (timers && mode == 2) std::fprintf(stderr, "build_acceleration_device: restructuring (prep + %u treelet passes) %.3f ms, inner-node area %.4f -> %.4f, binary depth %u\n",
-		                                      kTreeletPasses, ms_stage[5], area_before, area_after, fit_root_stamp);
+		                                      passes, ms_stage[5], area_before, area_after, fit_root_stamp);
 	}
 };
 

@@ -186,6 +186,16 @@ struct AccelTree
 	DeviceArray<float> refit_tri_box, refit_node_box; DeviceArray<uint32_t> refit_scan;      // device refit (fpt_build.hip): per-record and per-node fp32 boxes, {|scene|max bits, error bits}
 	HostBvh host_build;                             // the quality path's workspace: written by the host builder, read by nothing once its arrays are uploaded
 	DeviceArray<uint8_t> build_scratch;             // the device builder's working set (fpt_build_lbvh.hip), kept between builds; fpt_rt_set_build_mode(0) releases it
+	// where the last device build left its arrays in build_scratch (fpt_debug_device_build reads them; nothing else does).  Invalid from the moment a build starts to
+	// write the scratch until its last stage has passed, and wherever the scratch is released or reallocated: the probe then answers with an error, never stale memory
+	struct LastDeviceBuild
+	{
+		enum : uint32_t { REFS, BOUNDS, KEYS, VALS, LEFT, RIGHT, NODE_BOX, CELLS, NEED, TCOUNT, TCOST, N_ARRAYS };
+		bool valid = false; uint32_t n = 0, mode = 0, n_nodes = 0, cell_bytes = 0, passes = 0, sort_buffer = 0, binary_depth = 0;
+		const void* ptr[N_ARRAYS] = {}; size_t bytes[N_ARRAYS] = {};
+	} last_device_build;
+	uint32_t debug_treelet_passes = 3;              // fpt_debug_device_build(100 + p): the treelet passes of the NEXT mode-2 build, which puts the 3 back
+	void release_build_scratch() { last_device_build = LastDeviceBuild(); build_scratch.release(); }
 	// part 2 of the contract: exact-size arrays, `fill(nodes.ptr, records.ptr)` writes them and returns once they are written, then the description
 	template <typename F> void replace(TreeInfo built, F&& fill)
 	{

@@ -636,6 +636,18 @@ int fpt_debug_build_bvh(uint32_t tri_count, const int32_t* h_idx, uint32_t verte
 /* the same probe for fpt_rt_refit_geometry: the structure built over h_vtx0 and refitted to h_vtx1 (same indices, same vertex count) */
 int fpt_debug_refit_bvh(uint32_t tri_count, const int32_t* h_idx, uint32_t vertex_count, const float* h_vtx0, const float* h_vtx1, uint32_t* n_nodes, uint32_t* n_records,
                         uint32_t* depth, uint32_t* h_nodes, float* h_records, fpt_bvh_stats* stats /* may be NULL */);
+/* read-only probe of the LAST device build of this context (fpt_rt_set_build_mode 1 or 2; fermat_amd/csrc/fpt_build_lbvh.hip): the builder's working arrays, which stay
+ * in the context's build scratch until the next device build overwrites them or fpt_rt_set_build_mode(ctx, 0) releases them, copied to a HOST array.  `which`:
+ *   0        16 words of description: {n triangles, mode, wide nodes, bytes per `cells` row (40), treelet passes run, sort buffer the sorted pairs ended in (0 / 1),
+ *            binary depth (the root's stamp of the fit pass), 0 ...}; bytes = 64
+ *   1 refs      n x 6 float   the padded triangle boxes {lo.xyz, hi.xyz}, by triangle          2 bounds    12 int     ordered-int min / max of the boxes [0..5], of their centres [6..11]
+ *   3 keys      n x uint64    the sorted 63-bit Morton keys                                    4 vals      n x uint32 the triangle of each sorted position
+ *   5 left      (n-1) x int32                                                                  6 right     (n-1) x int32     the binary tree as stages 3 / 3b left it (>= 0 inner node, < 0 ~sorted position)
+ *   7 node_box  (n-1) x 6 float                                                                8 cells     (n-1) x 40 bytes  {float c[7]; uint8 k[7], k8, leaf, count; 2 spare}
+ *   9 need      wide nodes x uint32   the stack bound per wide node                           10 tcount    (n-1) x uint32   and   11 tcost (n-1) x float: mode 2 only
+ * `bytes` must be the array's exact size.  100 + p (p = 0..3; h_out NULL, bytes 0): the NEXT device build of this context runs p treelet passes instead of 3 (mode 2 only; the
+ * override is consumed by that build).  An error -- never stale memory -- when the context holds no such build. */
+int fpt_debug_device_build(fpt_context* ctx, uint32_t which, void* h_out, uint64_t bytes);
 /* host-side probe of the emitter-table builder behind fpt_mesh_lights_init (no GPU, no context; HOST arrays in -- the mesh view and the textures as
  * fpt_mesh_lights_init takes them -- HOST arrays out: n_vpls VPLs and their CDF, one mesh-CDF / inverse-area entry per triangle).  *n_out = number of VPLs
  * built (0 for a scene without emitters).  Any output may be NULL. */
