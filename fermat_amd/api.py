@@ -104,6 +104,27 @@ def default_pssmlt_options(max_path_length=6, **kw):
     return o
 
 
+class MmltOptions(C.Structure):
+    """fpt_mmlt_options: the PSSMLT options plus the swap frequency (CMLTOptions::mmlt_frequency, src/renderers/cmlt.h)"""
+    _fields_ = [("mlt", PssmltOptions), ("mmlt_frequency", C.c_uint32)]
+
+
+class MmltStats(C.Structure):
+    _fields_ = [("image_brightness", C.c_float), ("pdf_norm", C.c_float), ("chain_length", C.c_uint32), ("n_chains", C.c_uint32),
+                ("accepted", C.c_uint64), ("rejected", C.c_uint64), ("swaps_proposed", C.c_uint64), ("swaps_accepted", C.c_uint64), ("rays", C.c_uint64)]
+
+
+def default_mmlt_options(max_path_length=6, mmlt_frequency=0, **kw):
+    """the multiplexed Metropolis renderer (the reference's `-cmlt -charted-swaps 0`): default_pssmlt_options' keywords, and mmlt_frequency = F > 0 for a technique
+    swap at every F-th chain step"""
+    return MmltOptions(default_pssmlt_options(max_path_length, **kw), mmlt_frequency)
+
+
+def tech_word(s, t):
+    """a chain's technique (s light vertices, t eye vertices) as the library keeps it: s | t << 8"""
+    return np.asarray(s, np.uint32) | (np.asarray(t, np.uint32) << np.uint32(8))
+
+
 class EawParams(C.Structure):
     _fields_ = [("phi_normal", C.c_float), ("phi_position", C.c_float), ("phi_color", C.c_float),
                 ("E", C.c_float * 3), ("U", C.c_float * 3), ("V", C.c_float * 3), ("W", C.c_float * 3)]
@@ -186,7 +207,8 @@ ENTRY_POINTS = ["fpt_create", "fpt_destroy", "fpt_last_error", "fpt_stream", "fp
                 "fpt_debug_build_emitter_tables", "fpt_clear_gbuffer", "fpt_rt_download_bvh", "fpt_mesh_lights_update", "fpt_rt_set_build_mode",
                 "fpt_mesh_lights_init_device", "fpt_mesh_lights_update_device", "fpt_rt_set_intersector", "fpt_rt_intersector",
                 "fpt_debug_psf", "fpt_psfpt_debug_set_table_log2", "fpt_debug_bpt", "fpt_debug_frame",
-                "fpt_pssmlt_init", "fpt_pssmlt_render", "fpt_pssmlt_get_stats", "fpt_pssmlt_download", "fpt_pssmlt_debug_eval", "fpt_debug_mlt", "fpt_debug_device_build"]
+                "fpt_pssmlt_init", "fpt_pssmlt_render", "fpt_pssmlt_get_stats", "fpt_pssmlt_download", "fpt_pssmlt_debug_eval", "fpt_debug_mlt", "fpt_debug_device_build",
+                "fpt_mmlt_init", "fpt_mmlt_render", "fpt_mmlt_get_stats", "fpt_mmlt_get_st_norms", "fpt_mmlt_download", "fpt_mmlt_debug_eval"]
 
 # fpt_debug_device_build: the arrays of the last device build, by their `which` (name -> (which, dtype, columns)); rows: n triangles, n - 1 binary nodes or the wide nodes
 LBVH_CELL_DTYPE = np.dtype([("c", "<f4", 7), ("k", "u1", 7), ("k8", "u1"), ("leaf", "u1"), ("count", "u1"), ("spare", "u1", 2)])
@@ -279,7 +301,7 @@ class Renderer:
     """RenderingContext + PathTracer for one GPU: owns torch device tensors, calls the C-ABI with their pointers."""
 
     def __init__(self, scn: "_scene.Scene", res_x, res_y, options=None, device=0, table=None, samples_dir=None, pixels=None,
-                 exposure=1.0, gamma=2.2, gbuffer=True, replay_context_sequence=True, bpt_options=None, psf_options=None, pssmlt_options=None):
+                 exposure=1.0, gamma=2.2, gbuffer=True, replay_context_sequence=True, bpt_options=None, psf_options=None, pssmlt_options=None, mmlt_options=None):
         import torch
         if not torch.cuda.is_available():
             raise FptError("no HIP device visible: fermat_amd has no CPU fallback")
@@ -344,7 +366,11 @@ class Renderer:
         self.bpt_options = bpt_options
         self.psf_options = psf_options
         self.pssmlt_options = pssmlt_options
-        if pssmlt_options is not None:
+        self.mmlt_options = mmlt_options
+        if mmlt_options is not None:
+            # `-mmlt`: one bidirectional technique per Metropolis chain; initialises the bidirectional state itself
+            self._check(self.L.fpt_mmlt_init(self.ctx, C.byref(mmlt_options), C.byref(self.view), sd, px, C.c_uint32(self.n_local)))
+        elif pssmlt_options is not None:
             # `-pssmlt`: Metropolis chains over the bidirectional kernels; initialises the bidirectional state itself
             self._check(self.L.fpt_pssmlt_init(self.ctx, C.byref(pssmlt_options), C.byref(self.view), sd, px, C.c_uint32(self.n_local)))
         elif psf_options is not None:
@@ -580,6 +606,50 @@ class Renderer:
         out = np.zeros((n, 4), np.float32)
         self._check(self.L.fpt_pssmlt_debug_eval(self.ctx, C.byref(self.view), C.c_uint32(n), C.c_void_p(light_u.ctypes.data), C.c_void_p(eye_u.ctypes.data), C.c_void_p(out.ctypes.data)))
         return out
+
+    # -- multiplexed Metropolis renderer (Renderer(..., mmlt_options=default_mmlt_options(L)))
+    def mmlt_render(self, instance, sync=False):
+        self._check(self.L.fpt_mmlt_render(self.ctx, C.c_uint32(instance), C.byref(self.view)))
+        if sync:
+            self.synchronize()
+
+    def mmlt_stats(self):
+        st = MmltStats()
+        self._check(self.L.fpt_mmlt_get_stats(self.ctx, C.byref(st)))
+        return dict(image_brightness=np.float32(st.image_brightness), pdf_norm=np.float32(st.pdf_norm), chain_length=int(st.chain_length), n_chains=int(st.n_chains),
+                    accepted=int(st.accepted), rejected=int(st.rejected), swaps_proposed=int(st.swaps_proposed), swaps_accepted=int(st.swaps_accepted), rays=int(st.rays))
+
+    def _mmlt_L(self):
+        return int(self.mmlt_options.mlt.bpt.max_path_length)
+
+    def mmlt_st_norms(self):
+        """(st_norms, chains) of the last mmlt_render, both (L + 2, L + 2) arrays indexed [t, s] (the reference's s + t * (L + 2))"""
+        w = self._mmlt_L() + 2
+        norms = np.zeros((w, w), np.float32); chains = np.zeros((w, w), np.uint32)
+        self._check(self.L.fpt_mmlt_get_st_norms(self.ctx, C.c_void_p(norms.ctypes.data), C.c_void_p(chains.ctypes.data)))
+        return norms, chains
+
+    def mmlt_state(self):
+        """what the last mmlt_render left: light_u / eye_u (dims, n_chains), path_value (n_chains, 4), path_pdf, rejections, seeds (cells of the table), st (s | t << 8) per
+        chain, and the technique table (n_techniques, n_pixels, 4)"""
+        L = self._mmlt_L()
+        n = int(self.mmlt_options.mlt.n_chains); d = (L + 1) * 3; npx = self.res[0] * self.res[1]
+        out = dict(light_u=np.zeros((d, n), np.float32), eye_u=np.zeros((d, n), np.float32), path_value=np.zeros((n, 4), np.float32), path_pdf=np.zeros(n, np.float32),
+                   rejections=np.zeros(n, np.uint32), seeds=np.zeros(n, np.uint32), st=np.zeros(n, np.uint32), table=np.zeros((L * (L + 1) // 2, npx, 4), np.float32))
+        self._check(self.L.fpt_mmlt_download(self.ctx, *[C.c_void_p(out[k].ctypes.data) for k in ("light_u", "eye_u", "path_value", "path_pdf", "rejections", "seeds", "st", "table")]))
+        return out
+
+    def mmlt_eval(self, light_u, eye_u, st, with_rays=False):
+        """the value (n, 4) of n coordinate sets (light_u / eye_u of shape (dims, n)), set i through technique st[i] = s | t << 8 alone, mutation Null; with_rays: also the
+        number of rays the evaluation queued"""
+        light_u = np.ascontiguousarray(light_u, np.float32); eye_u = np.ascontiguousarray(eye_u, np.float32); st = np.ascontiguousarray(st, np.uint32)
+        d = (self._mmlt_L() + 1) * 3
+        assert light_u.shape == eye_u.shape and light_u.shape[0] == d and st.shape == (light_u.shape[1],)
+        n = light_u.shape[1]
+        out = np.zeros((n, 4), np.float32); rays = C.c_uint64(0)
+        self._check(self.L.fpt_mmlt_debug_eval(self.ctx, C.byref(self.view), C.c_uint32(n), C.c_void_p(light_u.ctypes.data), C.c_void_p(eye_u.ctypes.data), C.c_void_p(st.ctypes.data),
+                                               C.c_void_p(out.ctypes.data), C.byref(rays)))
+        return (out, int(rays.value)) if with_rays else out
 
     def debug_mlt(self, op, arrays, params=(), n=None):
         """fpt_debug_mlt (layouts: include/fermat_pt_hip.h); arguments and result as debug_bpt's"""

@@ -34,6 +34,17 @@ struct ChainCoords { const float* light_u; const float* eye_u; uint32_t n_chains
 // Value sink: every frame contribution of eye path `id` is added to value[id] (all four components) and nothing else is written: no frame cell, no albedo
 // plane, no gbuffer, no log (the sinks of pssmlt.cu:257-304).  Set = value != NULL
 struct ValueSink { float4* value; };
+// The multiplexed Metropolis renderer (`-mmlt`, fpt_mlt.h) names a sample by its technique (s light vertices, t eye vertices): an emission sample of eye vertex
+// `bounce + 2` is (0, bounce + 2), a connection of that vertex to stored light depth d is (d + 1, bounce + 2).  With light tracing off the techniques are
+// t in [2, L + 1], s in [0, L + 1 - t]: L (L + 1) / 2 of them, numbered t-major by mlt_tech_index (fpt_mlt_host.h)
+// Technique table sink (the presampling pass of `-mmlt`): the sample of eye path `id` with technique (s, t) is stored in cell[mlt_tech_index(s, t) * n_paths + id]
+// and nothing else is written.  With single_connection = 0 a path has one sample per technique at most: a plain store, free of races for the reason given above
+// sink<MLT> (fpt_bpt.hip).  Set = cell != NULL
+struct TechTable { float4* cell; };
+// Technique-fixed evaluation (the chain steps of `-mmlt`): chain c evaluates technique st[c] = s | t << 8 alone -- its light sub-path stops at vertex s - 1 (none
+// for s = 0), its eye sub-path at vertex t, one connection or the emission is sampled -- and the one sample goes to the ValueSink.  rays, when set, counts the
+// rays queued (sub-path and connection rays; null rays are not counted).  Set = st != NULL; needs ChainCoords and ValueSink
+struct ChainTech { const uint32_t* st; unsigned long long* rays; };
 
 struct BptParams
 {
@@ -70,6 +81,9 @@ struct BptParams
 	// kernels that read coordinates or sink samples (fpt_bpt.hip): the launchers below choose
 	ChainCoords chain;
 	ValueSink value;
+	// the multiplexed Metropolis renderer's two, read by the same second instantiation only; with both unset its code path is `-pssmlt`'s
+	TechTable tech;
+	ChainTech fixed;
 };
 
 void launch_bpt_light_primary(const BptParams& p, hipStream_t s);

@@ -20,6 +20,8 @@
 //  * the Metropolis renderer (fpt_mlt.hip, `-pssmlt`) runs these kernels with two optional views of BptParams set: ChainCoords (coordinates from per-chain arrays,
 //    mutated where they are read) and ValueSink (every sample into the eye path's value, nothing else written).  The five kernels that read coordinates or sink
 //    samples are templates on one bool; `-bpt` launches the `false` instantiation, whose code does not know the other exists.
+//  * the multiplexed Metropolis renderer (`-mmlt`) adds two more views, read by the `true` instantiation alone: TechTable (the presampling pass keeps every sample in
+//    the cell of its (s, t) technique) and ChainTech (a chain evaluates one technique: its sub-paths stop at vertex s - 1 and t, one connection or the emission).
 #include "fpt_bpt_device.h"
 
 namespace fpt {
@@ -321,6 +323,18 @@ __device__ __forceinline__ void sink(const BptParams& P, uint32_t channel, f3 v,
 	}
 }
 
+// the technique table sink (fpt_bpt.h TechTable): the sample of technique (s, t) into its own cell, a plain store.  (s, t) is valid by construction -- an eye vertex
+// `bounce + 2 <= L + 1` connects to light depths <= L - bounce - 2 -- and checked all the same: an index outside the table is dropped, not written
+__device__ __forceinline__ void sink_tech(const BptParams& P, uint32_t s, uint32_t t, f3 v, float w, uint32_t vid)
+{
+	const uint32_t L = P.opt.max_path_length;
+	if (!mlt_tech_valid(s, t, L)) return;
+	P.tech.cell[size_t(mlt_tech_index(s, t, L)) * P.n_paths + path_ref(P, vid).id] = make_float4(v.x, v.y, v.z, w);
+}
+// technique-fixed evaluation (fpt_bpt.h ChainTech): the chain's s and t, and the count of the rays it queues
+__device__ __forceinline__ void fixed_tech(const BptParams& P, uint32_t chain, uint32_t& s, uint32_t& t) { const uint32_t w = P.fixed.st[chain]; s = w & 0xFFu; t = w >> 8; }
+__device__ __forceinline__ void count_rays(const BptParams& P, uint32_t n) { if (P.fixed.rays && n) atomicAdd(P.fixed.rays, (unsigned long long)n); }
+
 // ---- kernels -------------------------------------------------------------------------------------------------------------------
 template <bool MLT>
 __global__ void __launch_bounds__(BPT_BLOCK) light_primary_kernel(const BptParams P)
@@ -333,6 +347,16 @@ __global__ void __launch_bounds__(BPT_BLOCK) light_primary_kernel(const BptParam
 	const uint32_t id = r.id, vid = r.k * P.n_paths + r.id;
 	P.store.counts[vid] = 0; P.store.rec[vid].path_id = 0xFFFFFFFFu;
 	const uint32_t L = P.opt.max_path_length;
+	// technique-fixed: the light sub-path holds vertices 0 .. s - 1.  s = 0: it is not started; s <= 1: no ray leaves vertex 0.  Its queue slot gets a null ray
+	uint32_t fs = 2u, ft = 0u;
+	if (MLT && P.fixed.st) fixed_tech(P, id, fs, ft);
+	if (MLT && fs < 2u && L >= 1u)
+	{
+		write_ray(P.out.rays, i, splat3(0.0f), 0.0f, splat3(0.0f), -1.0f);
+		P.out.weights[i] = make_float4(0, 0, 0, 0); P.out.pixels[i] = vid; P.out.path_weights[i] = make_float4(0, 0, 0, 0);
+		if (i == 0) *P.out.size = P.n_local * P.n_passes;
+		if (fs == 0u) return;
+	}
 	SurfacePoint lp; f3 radiance; float pdf;
 	if (P.opt.use_vpls)
 	{
@@ -346,6 +370,8 @@ __global__ void __launch_bounds__(BPT_BLOCK) light_primary_kernel(const BptParam
 	             make_uint2(0u, to_rgbe(splat3(1.0f) / pdf)), make_float2(0.0f, 1.0f * pdf), id);
 	P.store.counts[vid] = 1;
 	if (1 >= L + 1) return;
+	if (MLT && fs < 2u) return;
+	if (MLT && P.fixed.st) count_rays(P, 1u);
 	// Edf::sample: cosine-distributed emission (contrib/cugar/bsdf/lambert_edf.h:82-99)
 	const f3 l = cosine_hemisphere(light_coord<MLT>(P, r, 1, 0), light_coord<MLT>(P, r, 1, 1));
 	const f3 out = l.x * lp.frame.t + l.y * lp.frame.b + l.z * lp.frame.n;
@@ -379,7 +405,9 @@ __global__ void __launch_bounds__(BPT_BLOCK) light_vertices_kernel(const BptPara
 			const PathRef r = path_ref(P, vid);
 			Vertex lv;
 			shade_vertex(P, mk3(ro.x, ro.y, ro.z), mk3(rd4.x, rd4.y, rd4.z), hit4.x, uint32_t(tri), hit4.z, hit4.w, mk3(w4.x, w4.y, w4.z), P.in.path_weights[i], true, lv);
-			if (P.bounce + 2 < P.opt.max_path_length + 1)
+			bool scatter = P.bounce + 2 < P.opt.max_path_length + 1;
+			if (MLT && P.fixed.st) { uint32_t fs, ft; fixed_tech(P, r.id, fs, ft); scatter = scatter && P.bounce + 2 < fs; }          // vertex s - 1 is the last one stored
+			if (scatter)
 			{
 				f3 out, g; float p, p_proj;
 				const uint32_t comp = surface_sample_ex(lv.bsdf, lv.sp.frame, light_coord<MLT>(P, r, P.bounce + 2, 0), light_coord<MLT>(P, r, P.bounce + 2, 1), light_coord<MLT>(P, r, P.bounce + 2, 2),
@@ -405,6 +433,7 @@ __global__ void __launch_bounds__(BPT_BLOCK) light_vertices_kernel(const BptPara
 	{
 		write_ray(P.out.rays, slot, o, 1.0e-4f, dir, 1.0e8f);
 		P.out.weights[slot] = w_out; P.out.pixels[slot] = pixel_info; P.out.path_weights[slot] = pw_out;
+		if (MLT && P.fixed.st) count_rays(P, 1u);
 	}
 }
 
@@ -427,6 +456,7 @@ __global__ void __launch_bounds__(BPT_BLOCK) eye_primary_kernel(const BptParams 
 	const float cos_theta = dot(normalize(dir), P.W) / P.W_len;
 	P.out.path_weights[i] = make_float4(0.0f, 1.0e8f, P.light_tracing ? p_e / P.light_tracing : 1.0f, P.light_tracing ? cos_theta : 1.0e8f);
 	if (i == 0) *P.out.size = P.n_local * P.n_passes;
+	if (MLT && P.fixed.st) count_rays(P, 1u);
 }
 
 #ifndef FPT_BPT_EYE_WAVES
@@ -467,7 +497,11 @@ __global__ void __launch_bounds__(BPT_BLOCK, FPT_BPT_EYE_WAVES) eye_vertices_ker
 				P.fb.gb_uv[pixel] = make_float4(hit4.z, hit4.w, ev.sp.s, ev.sp.t);
 				P.fb.gb_tri[pixel] = uint32_t(tri);
 			}
-			if (P.bounce + 2 < L + 1)
+			// technique-fixed: the eye sub-path ends at vertex ft, where it samples the emission (fs = 0) or the connection to light depth fs - 1, and nothing before
+			const bool fixed = MLT && P.fixed.st != nullptr;
+			uint32_t fs = 0u, ft = 0u;
+			if (fixed) fixed_tech(P, pixel, fs, ft);
+			if (P.bounce + 2 < L + 1 && !(fixed && P.bounce + 2 >= ft))
 			{
 				f3 out, g; float p, p_proj;
 				const uint32_t comp = surface_sample_ex(ev.bsdf, ev.sp.frame, eye_coord<MLT>(P, pr.k, pixel, px, py, P.bounce + 2, 0), eye_coord<MLT>(P, pr.k, pixel, px, py, P.bounce + 2, 1), eye_coord<MLT>(P, pr.k, pixel, px, py, P.bounce + 2, 2),
@@ -478,7 +512,7 @@ __global__ void __launch_bounds__(BPT_BLOCK, FPT_BPT_EYE_WAVES) eye_vertices_ker
 					if (P.bounce + 2 == 2)          // sink_eye_scattering_event: albedo of the visible surface (src/renderers/bpt_impl.h:167-186)
 					{
 						const int ch = comp == COMP_DIFF_R ? FPT_FB_DIFFUSE_A : (comp == COMP_GLOSSY_R ? FPT_FB_SPECULAR_A : -1);
-						if (ch >= 0 && !(MLT && P.value.value))          // a value sink keeps no albedo planes
+						if (ch >= 0 && !(MLT && (P.value.value || P.tech.cell)))          // a value sink or a technique table keeps no albedo planes
 						{
 							float4* cell = fb_cell(P, uint32_t(ch), pr);
 							const float fw = frame_weight(P, pr.k);
@@ -496,7 +530,7 @@ __global__ void __launch_bounds__(BPT_BLOCK, FPT_BPT_EYE_WAVES) eye_vertices_ker
 			}
 			// emission seen along the incoming direction (eval_incoming_emission, src/bpt_utils.h:1031-1066)
 			const uint32_t t = P.bounce + 2;
-			if ((t == 2 && P.opt.visible_lights) || (t == 3 && P.opt.direct_lighting_bsdf) || (t > 3 && P.opt.indirect_lighting_bsdf))
+			if (((t == 2 && P.opt.visible_lights) || (t == 3 && P.opt.direct_lighting_bsdf) || (t > 3 && P.opt.indirect_lighting_bsdf)) && !(fixed && !(t == ft && fs == 0u)))
 			{
 				f3 radiance; float light_pdf;
 				emitter_at(P.emitters, P.mesh, P.textures, uint32_t(tri), ev.sp.s, ev.sp.t, radiance, light_pdf);
@@ -506,7 +540,11 @@ __global__ void __launch_bounds__(BPT_BLOCK, FPT_BPT_EYE_WAVES) eye_vertices_ker
 				const float prev_pGp = pdf2(ev.prev_pG, p_L);
 				const float mis_w = (P.bounce == 0 || pGp == 0.0f || (P.bounce == 1 && !P.opt.direct_lighting_nee) || (P.bounce > 1 && !P.opt.indirect_lighting_nee)) ? 1.0f : mis3(pGp, prev_pGp, ev.pGp_sum);
 				const f3 e = ev.alpha * f_L * mis_w;
-				if (max_comp(e) > 0.0f && finite3(e)) sink<MLT>(P, chan & 0xFu, e, w_alpha, vid, P.bounce * (1u + P.log.conn_cells));
+				if (max_comp(e) > 0.0f && finite3(e))
+				{
+					if (MLT && P.tech.cell) sink_tech(P, 0u, t, e, w_alpha, vid);
+					else sink<MLT>(P, chan & 0xFu, e, w_alpha, vid, P.bounce * (1u + P.log.conn_cells));
+				}
 			}
 			// how many light vertices this eye vertex may connect to
 			const int32_t max_light_depth = int32_t(L + 1) - int32_t(P.bounce) - 2 - 1;
@@ -519,6 +557,11 @@ __global__ void __launch_bounds__(BPT_BLOCK, FPT_BPT_EYE_WAVES) eye_vertices_ker
 				const int32_t end = nlv < max_light_depth + 1 ? nlv : max_light_depth + 1;
 				first_depth = P.opt.direct_lighting_nee ? 0u : 1u;
 				n_conn = end > int32_t(first_depth) ? uint32_t(end) - first_depth : 0u;
+				if (fixed)          // the one connection to depth fs - 1, when the full evaluation makes it
+				{
+					n_conn = (t == ft && fs >= 1u && fs - 1u >= first_depth && int32_t(fs - 1u) < end) ? 1u : 0u;
+					first_depth = fs - 1u;
+				}
 			}
 		}
 	}
@@ -527,6 +570,7 @@ __global__ void __launch_bounds__(BPT_BLOCK, FPT_BPT_EYE_WAVES) eye_vertices_ker
 	{
 		write_ray(P.out.rays, slot, o, 1.0e-4f, dir, 1.0e8f);
 		P.out.weights[slot] = w_out; P.out.pixels[slot] = vid; P.out.chan[slot] = uint8_t(out_chan); P.out.path_weights[slot] = pw_out;
+		if (MLT && P.fixed.st) count_rays(P, 1u);
 	}
 	// connections: a contiguous range of the shadow queue per eye vertex, filled in light-depth order (unused tail = null rays)
 	const uint32_t base = block_range_alloc(P.shadow.size, n_conn, sc2);
@@ -556,11 +600,13 @@ __global__ void __launch_bounds__(BPT_BLOCK, FPT_BPT_EYE_WAVES) eye_vertices_ker
 			{
 				write_ray(P.shadow.rays, base + k, origin, 0.0f, lv.position - origin, 0.9999f);
 				P.shadow.weights[base + k] = make_float4(w.x, w.y, w.z, w_alpha);
-				P.shadow.pixels[base + k] = vid; P.shadow.chan[base + k] = uint8_t(sh_chan);
+				// the MLT instantiation carries the technique's s = light depth + 1 (<= 15) in the byte's free high nibble: eye_resolve_kernel names the sample by it
+				P.shadow.pixels[base + k] = vid; P.shadow.chan[base + k] = uint8_t(MLT ? (sh_chan | ((light_depth + 1u) << 4)) : sh_chan);
 				++k;
 			}
 		}
 		P.conn[i] = make_uint2(base, k);
+		if (MLT && P.fixed.st) count_rays(P, k);
 		for (uint32_t d = k; d < n_conn; ++d)
 		{
 			write_ray(P.shadow.rays, base + d, splat3(0.0f), 0.0f, splat3(0.0f), -1.0f);
@@ -586,6 +632,7 @@ __global__ void __launch_bounds__(BPT_BLOCK) eye_resolve_kernel(const BptParams 
 		// an occluded connection adds zeros: no cell.  (One pass per render() adds w * 0 instead, which differs only for a non-finite weight -- NaN there, nothing
 		// here: the bit-identity of batched and sequential passes is for finite samples, as include/fermat_pt_hip.h says)
 		if (P.n_passes > 1 && vis == 0.0f) continue;
+		if (MLT && P.tech.cell) { sink_tech(P, ch >> 4, P.bounce + 2u, mk3(w.x * vis, w.y * vis, w.z * vis), w.w * vis, pi); continue; }
 		sink<MLT>(P, ch & 0xFu, mk3(w.x * vis, w.y * vis, w.z * vis), w.w * vis, pi, P.bounce * (1u + P.log.conn_cells) + 1u + k);
 	}
 }
@@ -990,7 +1037,7 @@ inline dim3 grid_for(uint32_t n) { return dim3((n + BPT_BLOCK - 1) / BPT_BLOCK);
 } // namespace
 
 // the Metropolis renderer's parameter blocks (a chain or a value sink set) run the MLT instantiation, `-bpt`'s the other
-static bool mlt_block(const BptParams& p) { return p.chain.light_u != nullptr || p.value.value != nullptr; }
+static bool mlt_block(const BptParams& p) { return p.chain.light_u != nullptr || p.value.value != nullptr || p.tech.cell != nullptr; }
 #define FPT_BPT_LAUNCH(kernel, n) do { if (mlt_block(p)) hipLaunchKernelGGL(kernel<true>, grid_for(n), dim3(BPT_BLOCK), 0, s, p); \
                                        else hipLaunchKernelGGL(kernel<false>, grid_for(n), dim3(BPT_BLOCK), 0, s, p); } while (0)
 void launch_bpt_light_primary(const BptParams& p, hipStream_t s) { FPT_BPT_LAUNCH(light_primary_kernel, p.n_local * p.n_passes); }

@@ -199,15 +199,18 @@ struct BptRun
 		P.W_len = length(P.W);
 		{ const float tn = tanf(view->camera.fov / 2); P.sq_focal = (1.0f / 4.0f) / (tn * tn); }           // Camera::square_screen_focal_length, src/camera.h:132-136
 	}
-	// the Metropolis renderer's wavefront: n light and eye sub-paths (path id = chain, or pixel when the coordinates are the tiled ones) into a value sink; no frame
-	// cells, albedo planes, gbuffer or log, and the splat sums are left to the caller
-	void for_value_sink(uint32_t n, const ChainCoords* chain, float4* value)
+	// the Metropolis renderers' wavefront: n light and eye sub-paths (path id = chain, or pixel when the coordinates are the tiled ones) into a value sink; no frame
+	// cells, albedo planes, gbuffer or log, and the splat sums are left to the caller.  `tech`: the samples go to the technique table instead of `value`;
+	// `fixed`: every chain evaluates its one technique (fpt_bpt.h)
+	void for_value_sink(uint32_t n, const ChainCoords* chain, float4* value, const TechTable* tech, const ChainTech* fixed)
 	{
 		n_launch = n; prof = false;
 		P.n_local = P.n_paths = P.n_store = n; P.pixels = nullptr;
 		std::memset(&P.fb, 0, sizeof(P.fb));
 		if (chain) P.chain = *chain;
 		P.value.value = value;
+		if (tech) P.tech = *tech;
+		if (fixed) P.fixed = *fixed;
 	}
 	void trace(const float4* rays, float4* hits, const uint32_t* count_ptr, bool any_hit)
 	{
@@ -300,7 +303,7 @@ struct BptRun
 			uint64_t total = 0; for (uint32_t c : counts) total += c;
 			st.n_light_vertices = uint32_t(total);
 		}
-		if (P.value.value) { FPT_HIP_CHECK(hipGetLastError()); return; }          // a value sink: the frame and the splat sums are the caller's
+		if (P.value.value || P.tech.cell) { FPT_HIP_CHECK(hipGetLastError()); return; }          // a value sink or a technique table: the frame and the splat sums are the caller's
 		// the frame: light-tracing splats, then (batch) the planes in pass order.  Deferred mode leaves both to fpt_bpt_resolve_splats
 		b.pending_first = P.instance; b.pending_n = P.n_passes;
 		if (!b.deferred_splats || !b.light_tracing) resolve_splats(ctx, view);
@@ -329,14 +332,16 @@ static void render_impl(fpt_context* ctx, uint32_t instance, uint32_t n_passes, 
 } // extern "C"
 namespace fpt { void bpt_render_passes(fpt_context* ctx, uint32_t first, uint32_t n, const fpt_rendering_context_view* view) { render_impl(ctx, first, n, view); } }
 namespace fpt {
-void bpt_sample_paths(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view, uint32_t n, const ChainCoords* chain, float4* value, BptParams* tiled)
+void bpt_sample_paths(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view, uint32_t n, const ChainCoords* chain, float4* value, BptParams* tiled,
+                      const TechTable* tech, const ChainTech* fixed)
 {
 	fpt_context::BptState& b = ctx->bpt;
 	require(b.ready && b.max_batch == 1 && !b.d_pixels && !b.light_pending && b.pending_n == 0, "fpt_pssmlt: the bidirectional state is not the one fpt_pssmlt_init made");
-	require(value != nullptr && (n ? n : b.n_paths) <= std::max(b.n_paths, b.min_paths), "fpt_pssmlt: more paths than the storage holds");
+	require(((value != nullptr) != (tech != nullptr && tech->cell != nullptr)) && (n ? n : b.n_paths) <= std::max(b.n_paths, b.min_paths), "fpt_pssmlt: more paths than the storage holds");
+	require(!fixed || (chain && value && !b.opt.single_connection), "fpt_mmlt: a technique-fixed evaluation needs chain coordinates, a value sink and single_connection = 0");
 	BptRun run(ctx, instance, 1, view);
 	if (tiled) *tiled = run.P;
-	run.for_value_sink(n ? n : b.n_paths, chain, value);
+	run.for_value_sink(n ? n : b.n_paths, chain, value, tech, fixed);
 	run.light_phase();
 	run.rest(view);
 }

@@ -3,6 +3,7 @@
 // re-evaluated from recovered coordinates (fpt_mlt.hip) must read exactly what the pass that found it read.
 #pragma once
 #include "fpt_bpt.h"
+#include "fpt_mlt_host.h"
 
 namespace fpt {
 

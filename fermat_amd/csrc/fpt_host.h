@@ -397,6 +397,14 @@ struct fpt_context
 		fpt::DeviceArray<unsigned long long> q, cdf, counts;               // the seed CDF and its terms (n_pixels); accepted, rejected, + the CDF's total read back
 		fpt::DeviceArray<uint8_t> scan_scratch;
 		fpt_pssmlt_stats stats{};
+		// the multiplexed renderer (`-mmlt`, fpt_mmlt_init): one (s, t) technique per chain
+		bool multiplexed = false;
+		uint32_t mmlt_frequency = 0, n_tech = 0;
+		fpt::DeviceArray<float4> table;                                    // the presampling pass's technique table: n_tech x n_pixels cells
+		fpt::DeviceArray<uint32_t> st, st_new, path_seeds, tech_chains;    // per chain: s | t << 8, the swap step's proposal, the seed's eye path; chains seeded per technique
+		fpt::DeviceArray<unsigned long long> mcounts, ends;                // swaps proposed, swaps accepted, rays queued by the chain steps; the CDF at the techniques' block ends
+		std::vector<float> st_norms; std::vector<uint32_t> st_chains;      // (L+2)^2 each, s + t * (L+2)
+		fpt_mmlt_stats mstats{};
 	} mlt;
 	bool profiling = false;
 	int capture_bounce = -1;
@@ -458,10 +466,12 @@ namespace fpt { uint64_t bpt_bytes_per_path(fpt_context* ctx); }
 // fpt_bpt_api.cpp, for the Metropolis renderer (inside the caller's `guarded`).  bpt_init: fpt_bpt_init's body, storage for at least `min_paths` paths.
 // bpt_sample_paths: one bidirectional wavefront (BptRun: light_phase, rest) of `n` light and eye sub-paths -- n = 0: the frame's pixels -- whose samples go to
 // `value` (ValueSink) and whose coordinates come from `chain` (ChainCoords) or, chain == NULL, from the tiled sequence; the frame is not touched.  `tiled`, when
-// given, receives the parameter block of the tiled pass (what launch_mlt_recover_coordinates reads)
+// given, receives the parameter block of the tiled pass (what launch_mlt_recover_coordinates reads).  `tech` (with value == NULL): the samples go to the technique
+// table; `fixed` (with chain and value): every chain evaluates its one technique -- the multiplexed renderer's two views (fpt_bpt.h)
 namespace fpt { void bpt_init(fpt_context* ctx, const fpt_bpt_options* opts, const fpt_rendering_context_view* view, const char* h_samples_dir, const uint32_t* d_pixels,
                               uint32_t n_local_pixels, uint32_t min_paths);
-                void bpt_sample_paths(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view, uint32_t n, const ChainCoords* chain, float4* value, BptParams* tiled); }
+                void bpt_sample_paths(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view, uint32_t n, const ChainCoords* chain, float4* value, BptParams* tiled,
+                                      const TechTable* tech = nullptr, const ChainTech* fixed = nullptr); }
 
 // ---- helpers shared by the C-ABI translation units (fpt_api.cpp, fpt_bpt_api.cpp) -------------------------------------------------
 template <typename F>

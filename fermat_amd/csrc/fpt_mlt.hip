@@ -8,7 +8,11 @@
 //
 // Deviations, each for a frame that does not depend on the order in which threads run: the seed CDF is an integer scan (2^-32 fixed point), the chains' splats
 // are 2^-32 fixed-point integer atomics folded into the frame once per render call (the BPT's splat sums), and the mutation numbers are a counter-based function
-// (fpt_bpt_device.h) instead of a stored cuRAND stream.  The per-(s,t) statistics (st_norms), which the reference only prints, are not kept.
+// (fpt_bpt_device.h) instead of a stored cuRAND stream.  `-pssmlt` keeps no per-(s,t) statistics; the multiplexed renderer (`-mmlt`, one technique per chain:
+// src/renderers/cmlt.cu without its charted swaps) does, and adds three small kernels:
+//   mmlt_start_chains_kernel            a seed cell of the technique table -> the chain's technique and eye path
+//   mmlt_block_ends_kernel              the seed CDF at the end of every technique's block (st_norms)
+//   mmlt_swap_kernel                    mmlt_swap_kernel                     src/renderers/cmlt.cu:496-544
 #include "fpt_mlt.h"
 #include "fpt_bpt_device.h"
 #include <cstring>
@@ -32,7 +36,8 @@ __global__ void __launch_bounds__(MLT_BLOCK) seed_values_kernel(const float4* __
 	q[i] = r;
 }
 
-__global__ void __launch_bounds__(MLT_BLOCK) sample_seeds_kernel(const unsigned long long* __restrict__ cdf, uint32_t n, uint32_t n_seeds, uint32_t* __restrict__ seeds)
+// common_offset < 0: PSSMLT's rule, one jitter per stratum in float; >= 0 (the multiplexed renderer): the exact integer targets of mlt_seed_target with that offset
+__global__ void __launch_bounds__(MLT_BLOCK) sample_seeds_kernel(const unsigned long long* __restrict__ cdf, uint32_t n, uint32_t n_seeds, uint32_t* __restrict__ seeds, int common_offset)
 {
 	const uint32_t seed_id = threadIdx.x + blockIdx.x * blockDim.x;
 	if (seed_id >= n_seeds) return;
@@ -41,7 +46,7 @@ __global__ void __launch_bounds__(MLT_BLOCK) sample_seeds_kernel(const unsigned 
 	// pick a stratified sample
 	const float r = (float(seed_id) + randfloat(seed_id, 0)) / float(n_seeds);
 	const double x = double(r) * double(total);
-	const unsigned long long target = x >= 18446744073709551616.0 ? ~0ull : (unsigned long long)x;
+	const unsigned long long target = common_offset >= 0 ? mlt_seed_target(total, seed_id, n_seeds, uint32_t(common_offset)) : x >= 18446744073709551616.0 ? ~0ull : (unsigned long long)x;
 	// upper bound: the first entry with cdf > target
 	uint32_t lo = 0, hi = n;
 	while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (cdf[mid] > target) hi = mid; else lo = mid + 1; }
@@ -103,6 +108,8 @@ __global__ void __launch_bounds__(MLT_BLOCK) accept_reject_kernel(const MltChain
 		{
 			C.path_value[chain] = w;
 			C.path_pdf[chain] = new_pdf;
+			// write out the successful st
+			if (C.st && C.swap) C.st[chain] = C.st_new[chain];
 			// copy the successful mutation coordinates
 			if (light_mut) for (uint32_t d = 0; d < dims; ++d) C.light_u[size_t(d) * n + chain] = new_light(d);
 			if (eye_mut) for (uint32_t d = 0; d < dims; ++d) C.eye_u[size_t(d) * n + chain] = new_eye(d);
@@ -123,6 +130,11 @@ __global__ void __launch_bounds__(MLT_BLOCK) accept_reject_kernel(const MltChain
 	{
 		if (acc) atomicAdd(C.counts, (unsigned long long)__popcll(acc));
 		if (rej) atomicAdd(C.counts + 1, (unsigned long long)__popcll(rej));
+		if (C.mcounts && C.swap)
+		{
+			atomicAdd(C.mcounts, (unsigned long long)__popcll(acc | rej));
+			if (acc) atomicAdd(C.mcounts + 1, (unsigned long long)__popcll(acc));
+		}
 	}
 }
 
@@ -137,6 +149,54 @@ __global__ void __launch_bounds__(MLT_BLOCK) mlt_resolve_kernel(float4* __restri
 	v.x += float(double(a) * (1.0 / 4294967296.0)); v.y += float(double(b) * (1.0 / 4294967296.0)); v.z += float(double(c) * (1.0 / 4294967296.0));
 	composited[p] = v;
 	q[0] = q[1] = q[2] = 0;
+}
+
+__global__ void __launch_bounds__(MLT_BLOCK) mmlt_start_chains_kernel(const uint32_t* __restrict__ seeds, uint32_t n_chains, uint32_t n_paths, uint32_t L, uint32_t* __restrict__ st,
+                                                                      uint32_t* __restrict__ path_seeds, uint32_t* __restrict__ tech_chains)
+{
+	const uint32_t c = threadIdx.x + blockIdx.x * blockDim.x;
+	if (c >= n_chains) return;
+	const uint32_t e = seeds[c];
+	uint32_t tech = e / n_paths;
+	if (tech >= mlt_tech_count(L)) tech = mlt_tech_count(L) - 1u;          // (a seed is a cell of the table: never taken)
+	st[c] = mlt_tech_st(tech, L);
+	path_seeds[c] = e - (e / n_paths) * n_paths;
+	atomicAdd(tech_chains + tech, 1u);
+}
+
+__global__ void __launch_bounds__(MLT_BLOCK) mmlt_block_ends_kernel(const unsigned long long* __restrict__ cdf, uint32_t n_tech, uint32_t n_paths, unsigned long long* __restrict__ ends)
+{
+	const uint32_t k = threadIdx.x + blockIdx.x * blockDim.x;
+	if (k < n_tech) ends[k] = cdf[size_t(k + 1u) * n_paths - 1u];
+}
+
+__global__ void __launch_bounds__(MLT_BLOCK) mmlt_swap_kernel(const uint32_t* __restrict__ st, uint32_t* __restrict__ st_new, uint32_t n_chains, uint32_t L, uint32_t instance, uint32_t step)
+{
+	const uint32_t c = threadIdx.x + blockIdx.x * blockDim.x;
+	if (c >= n_chains) return;
+	const uint32_t w = st[c];
+	// generate a candidate (s_new,t_new) pair with s_new + t_new = s + t: perform a random walk on s
+	st_new[c] = mlt_swap_proposal(w & 0xFFu, w >> 8, mlt_mutation_number(instance, step, c, mlt_swap_dim(L)));
+}
+
+__global__ void __launch_bounds__(MLT_BLOCK) debug_mmlt_tech_kernel(uint32_t n, uint32_t L, const uint32_t* __restrict__ st, uint32_t* __restrict__ index, uint32_t* __restrict__ back)
+{
+	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
+	if (i >= n) return;
+	const uint32_t s = st[i] & 0xFFu, t = st[i] >> 8;
+	const bool ok = mlt_tech_valid(s, t, L);
+	index[i] = ok ? mlt_tech_index(s, t, L) : 0xFFFFFFFFu;
+	back[i] = ok ? mlt_tech_st(index[i], L) : 0xFFFFFFFFu;
+}
+
+__global__ void __launch_bounds__(MLT_BLOCK) debug_mmlt_swap_kernel(uint32_t n, uint32_t L, uint32_t instance, uint32_t step, const uint32_t* __restrict__ st, const uint32_t* __restrict__ chain,
+                                                                    uint32_t* __restrict__ st_new, float* __restrict__ m_out)
+{
+	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
+	if (i >= n) return;
+	const float m = mlt_mutation_number(instance, step, chain[i], mlt_swap_dim(L));
+	st_new[i] = mlt_swap_proposal(st[i] & 0xFFu, st[i] >> 8, m);
+	m_out[i] = m;
 }
 
 __global__ void __launch_bounds__(MLT_BLOCK) debug_perturb_kernel(uint32_t n, const float* __restrict__ u, const float* __restrict__ m_in, const uint32_t* __restrict__ chain, const uint32_t* __restrict__ dim,
@@ -162,13 +222,23 @@ void launch_mlt_seed_cdf(const float4* value, uint32_t n, unsigned long long* q,
 	hipLaunchKernelGGL(seed_values_kernel, grid_for(n), dim3(MLT_BLOCK), 0, s, value, n, q);
 	(void)rocprim::inclusive_scan(scratch, scratch_bytes, static_cast<const unsigned long long*>(q), cdf, size_t(n), rocprim::plus<unsigned long long>(), s);
 }
-void launch_mlt_sample_seeds(const unsigned long long* cdf, uint32_t n, uint32_t n_seeds, uint32_t* seeds, hipStream_t s)
-{ hipLaunchKernelGGL(sample_seeds_kernel, grid_for(n_seeds), dim3(MLT_BLOCK), 0, s, cdf, n, n_seeds, seeds); }
+void launch_mlt_sample_seeds(const unsigned long long* cdf, uint32_t n, uint32_t n_seeds, uint32_t* seeds, hipStream_t s, int common_offset)
+{ hipLaunchKernelGGL(sample_seeds_kernel, grid_for(n_seeds), dim3(MLT_BLOCK), 0, s, cdf, n, n_seeds, seeds, common_offset); }
 void launch_mlt_recover_coordinates(const BptParams& tiled, const uint32_t* seeds, uint32_t n_chains, float* light_u, float* eye_u, hipStream_t s)
 { hipLaunchKernelGGL(recover_coordinates_kernel, grid_for(n_chains), dim3(MLT_BLOCK), 0, s, tiled, seeds, n_chains, light_u, eye_u); }
 void launch_mlt_accept_reject(const MltChains& c, hipStream_t s) { hipLaunchKernelGGL(accept_reject_kernel, grid_for(c.n_chains), dim3(MLT_BLOCK), 0, s, c); }
 void launch_mlt_resolve(float4* composited, long long* splat, uint32_t n_pixels, hipStream_t s)
 { hipLaunchKernelGGL(mlt_resolve_kernel, grid_for(n_pixels), dim3(MLT_BLOCK), 0, s, composited, splat, n_pixels); }
+void launch_mmlt_start_chains(const uint32_t* seeds, uint32_t n_chains, uint32_t n_paths, uint32_t L, uint32_t* st, uint32_t* path_seeds, uint32_t* tech_chains, hipStream_t s)
+{ hipLaunchKernelGGL(mmlt_start_chains_kernel, grid_for(n_chains), dim3(MLT_BLOCK), 0, s, seeds, n_chains, n_paths, L, st, path_seeds, tech_chains); }
+void launch_mmlt_block_ends(const unsigned long long* cdf, uint32_t n_tech, uint32_t n_paths, unsigned long long* ends, hipStream_t s)
+{ hipLaunchKernelGGL(mmlt_block_ends_kernel, grid_for(n_tech), dim3(MLT_BLOCK), 0, s, cdf, n_tech, n_paths, ends); }
+void launch_mmlt_swap(const uint32_t* st, uint32_t* st_new, uint32_t n_chains, uint32_t L, uint32_t instance, uint32_t step, hipStream_t s)
+{ hipLaunchKernelGGL(mmlt_swap_kernel, grid_for(n_chains), dim3(MLT_BLOCK), 0, s, st, st_new, n_chains, L, instance, step); }
+void launch_debug_mmlt_tech(uint32_t n, uint32_t L, const uint32_t* st, uint32_t* index, uint32_t* back, hipStream_t s)
+{ hipLaunchKernelGGL(debug_mmlt_tech_kernel, grid_for(n), dim3(MLT_BLOCK), 0, s, n, L, st, index, back); }
+void launch_debug_mmlt_swap(uint32_t n, uint32_t L, uint32_t instance, uint32_t step, const uint32_t* st, const uint32_t* chain, uint32_t* st_new, float* m_out, hipStream_t s)
+{ hipLaunchKernelGGL(debug_mmlt_swap_kernel, grid_for(n), dim3(MLT_BLOCK), 0, s, n, L, instance, step, st, chain, st_new, m_out); }
 void launch_debug_mlt_perturb(uint32_t n, const float* u, const float* m_in, const uint32_t* chain, const uint32_t* dim, uint32_t instance, uint32_t step, uint32_t mutation, float radius,
                               float* out, float* m_out, hipStream_t s)
 { hipLaunchKernelGGL(debug_perturb_kernel, grid_for(n), dim3(MLT_BLOCK), 0, s, n, u, m_in, chain, dim, instance, step, mutation, radius, out, m_out); }

@@ -4,6 +4,10 @@
 // presampling pass), then once per chain step over the chains with their perturbed coordinates.  One read-back per render call: the seed CDF's total, which the
 // normalisation needs on the host (the reference synchronises there as well, pssmlt.cu:531).
 // Out of scope: passes in flight, deferral, tile sharding / multi-GPU, use_vpls, the per-(s,t) statistics the reference prints.
+//
+// And of the multiplexed renderer (`-mmlt`, fpt_mmlt_*: the reference's `-cmlt -charted-swaps 0`, src/renderers/cmlt.cu): the same wavefront, with the presampling pass
+// sinking into a technique table (TechTable) and every chain step evaluating the chain's one (s, t) technique (ChainTech).  Read-backs per call: the CDF at the
+// techniques' block ends (st_norms and the total), and at the end the counters and the chains seeded per technique.  Every call reseeds; charted swaps are not built.
 #include "fpt_host.h"
 #include "fpt_mlt.h"
 #include "fpt_mlt_host.h"
@@ -27,7 +31,7 @@ void render_impl(fpt_context* ctx, uint32_t instance, const fpt_rendering_contex
 {
 	fpt_context::MltState& m = ctx->mlt;
 	fpt_context::BptState& b = ctx->bpt;
-	require(m.ready && b.ready, "fpt_pssmlt_render: fpt_pssmlt_init has not been called");
+	require(m.ready && b.ready && !m.multiplexed, "fpt_pssmlt_render: fpt_pssmlt_init has not been called");
 	require(ctx->tree.valid, "fpt_pssmlt_render: create_geometry has not been called");
 	require(ctx->emitters.valid, "fpt_pssmlt_render: fpt_mesh_lights_init has not been called");
 	require(view->res_x * view->res_y == m.n_pixels, "fpt_pssmlt_render: the view's resolution differs from fpt_pssmlt_init's");
@@ -84,6 +88,88 @@ void render_impl(fpt_context* ctx, uint32_t instance, const fpt_rendering_contex
 	st.accepted = counts[0]; st.rejected = counts[1];
 }
 
+// ---- the multiplexed renderer: CMLT::render (src/renderers/cmlt.cu:983-1190) without charted swaps; every call reseeds ----
+void mmlt_render_impl(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view)
+{
+	fpt_context::MltState& m = ctx->mlt;
+	fpt_context::BptState& b = ctx->bpt;
+	require(m.ready && b.ready && m.multiplexed, "fpt_mmlt_render: fpt_mmlt_init has not been called");
+	require(ctx->tree.valid, "fpt_mmlt_render: create_geometry has not been called");
+	require(ctx->emitters.valid, "fpt_mmlt_render: fpt_mesh_lights_init has not been called");
+	require(view->res_x * view->res_y == m.n_pixels, "fpt_mmlt_render: the view's resolution differs from fpt_mmlt_init's");
+	hipStream_t s = ctx->stream;
+	const uint32_t n_pixels = m.n_pixels, n_chains = m.n_chains, L = m.opt.bpt.max_path_length, n_tech = m.n_tech, n_cells = n_tech * n_pixels, W = L + 2u;
+	const FrameBufferDev fb = fb_dev(view->fb);
+	// pre-multiply the previous frame for blending
+	launch_rescale(fb, nullptr, n_pixels, float(instance) / float(instance + 1), s);
+	// the BPT presampling pass: the tiled coordinates, every sample into the cell of its technique
+	zero(m.table, n_cells, s);
+	BptParams tiled;
+	const TechTable table = { m.table.ptr };
+	bpt_sample_paths(ctx, instance, view, 0u, nullptr, nullptr, &tiled, &table, nullptr);
+	// one CDF over all cells: the seeds are single connections, drawn in proportion to their value whatever their technique
+	launch_mlt_seed_cdf(m.table.ptr, n_cells, m.q.ptr, m.cdf.ptr, m.scan_scratch.ptr, m.scan_scratch.count, s);
+	launch_mlt_sample_seeds(m.cdf.ptr, n_cells, n_chains, m.seeds.ptr, s, int(mlt_seed_offset(instance)));
+	launch_mmlt_block_ends(m.cdf.ptr, n_tech, n_pixels, m.ends.ptr, s);
+	FPT_HIP_CHECK(hipGetLastError());
+	std::vector<unsigned long long> ends(n_tech, 0ull);
+	FPT_HIP_CHECK(hipMemcpyAsync(ends.data(), m.ends.ptr, n_tech * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+	FPT_HIP_CHECK(hipStreamSynchronize(s));
+	const unsigned long long total = ends[n_tech - 1];
+	fpt_mmlt_stats& st = m.mstats;
+	std::memset(&st, 0, sizeof(st));
+	st.n_chains = n_chains; st.chain_length = m.chain_length;
+	st.image_brightness = mlt_image_brightness(total, n_pixels);
+	st.pdf_norm = mlt_pdf_norm(st.image_brightness, n_pixels, m.chain_length, n_chains);
+	// the st_norms: exact, as the CDF is an integer
+	m.st_norms.assign(size_t(W) * W, 0.0f); m.st_chains.assign(size_t(W) * W, 0u);
+	for (uint32_t k = 0; k < n_tech; ++k)
+	{
+		const uint32_t w = mlt_tech_st(k, L);
+		m.st_norms[(w & 0xFFu) + (w >> 8) * W] = mlt_image_brightness(ends[k] - (k ? ends[k - 1] : 0ull), n_pixels);
+	}
+	if (total == 0) return;          // a black frame: no sample to start a chain from, the frame is only rescaled
+	zero(m.tech_chains, n_tech, s);
+	launch_mmlt_start_chains(m.seeds.ptr, n_chains, n_pixels, L, m.st.ptr, m.path_seeds.ptr, m.tech_chains.ptr, s);
+	// recover the primary coordinates of the selected seed paths
+	launch_mlt_recover_coordinates(tiled, m.path_seeds.ptr, n_chains, m.light_u.ptr, m.eye_u.ptr, s);
+	// initialize the initial path pdfs and the rejection counters to zero
+	zero(m.path_pdf, n_chains, s); zero(m.rejections, n_chains, s); zero(m.counts, 2, s); zero(m.mcounts, 3, s);
+	MltChains C; std::memset(&C, 0, sizeof(C));
+	C.light_u = m.light_u.ptr; C.eye_u = m.eye_u.ptr; C.new_value = m.new_value.ptr; C.path_value = m.path_value.ptr; C.path_pdf = m.path_pdf.ptr; C.rejections = m.rejections.ptr;
+	C.splat = b.splat_ptr(); C.counts = m.counts.ptr;
+	C.n_chains = n_chains; C.max_path_length = L; C.instance = instance;
+	C.light_perturbations = m.opt.light_perturbations; C.eye_perturbations = m.opt.eye_perturbations; C.radius = m.opt.radius; C.pdf_norm = st.pdf_norm;
+	C.res_x = view->res_x; C.res_y = view->res_y;
+	C.st = m.st.ptr; C.st_new = m.st_new.ptr; C.mcounts = m.mcounts.ptr;
+	// start the chains
+	for (uint32_t l = 0; l < m.chain_length; ++l)
+	{
+		// a swap step keeps the coordinates and proposes another technique of the same path length; any other step is PSSMLT's on the chain's own technique
+		const bool swap = mlt_is_swap_step(m.mmlt_frequency, l);
+		const uint32_t mutation = swap ? 0u : mlt_mutation_type(m.opt.independent_samples, instance, l);
+		if (swap) launch_mmlt_swap(m.st.ptr, m.st_new.ptr, n_chains, L, instance, l, s);
+		// reset the new path values
+		zero(m.new_value, n_chains, s);
+		const ChainCoords chain = chain_view(m, n_chains, l, mutation);
+		const ChainTech fixed = { swap ? m.st_new.ptr : m.st.ptr, m.mcounts.ptr + 2 };
+		bpt_sample_paths(ctx, instance, view, n_chains, &chain, m.new_value.ptr, nullptr, nullptr, &fixed);
+		// and perform the usual acceptance-rejection step
+		C.step = l; C.mutation = mutation; C.swap = swap ? 1u : 0u;
+		launch_mlt_accept_reject(C, s);
+	}
+	launch_mlt_resolve(fb.ch[FPT_FB_COMPOSITED_C], b.splat_ptr(), n_pixels, s);
+	FPT_HIP_CHECK(hipGetLastError());
+	unsigned long long counts[2] = { 0, 0 }, mcounts[3] = { 0, 0, 0 };
+	std::vector<uint32_t> tech_chains(n_tech, 0u);
+	FPT_HIP_CHECK(hipMemcpyAsync(counts, m.counts.ptr, sizeof(counts), hipMemcpyDeviceToHost, s));
+	FPT_HIP_CHECK(hipMemcpyAsync(mcounts, m.mcounts.ptr, sizeof(mcounts), hipMemcpyDeviceToHost, s));
+	FPT_HIP_CHECK(hipMemcpyAsync(tech_chains.data(), m.tech_chains.ptr, n_tech * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+	FPT_HIP_CHECK(hipStreamSynchronize(s));
+	st.accepted = counts[0]; st.rejected = counts[1]; st.swaps_proposed = mcounts[0]; st.swaps_accepted = mcounts[1]; st.rays = mcounts[2];
+	for (uint32_t k = 0; k < n_tech; ++k) { const uint32_t w = mlt_tech_st(k, L); m.st_chains[(w & 0xFFu) + (w >> 8) * W] = tech_chains[k]; }
+}
+
 } // namespace
 
 extern "C" {
@@ -95,7 +181,7 @@ int fpt_pssmlt_init(fpt_context* ctx, const fpt_pssmlt_options* opts, const fpt_
 		flush_deferred(ctx);
 		require(opts && view, "fpt_pssmlt_init: null argument");
 		fpt_context::MltState& m = ctx->mlt;
-		m.ready = false; (void)n_local_pixels;
+		m.ready = false; m.multiplexed = false; (void)n_local_pixels;
 		const uint32_t n_pixels = view->res_x * view->res_y;
 		require(n_pixels > 0, "fpt_pssmlt_init: empty frame");
 		if (const char* why = mlt_refusal(*opts, n_pixels, d_pixels != nullptr)) require(false, why);
@@ -125,13 +211,13 @@ int fpt_pssmlt_render(fpt_context* ctx, uint32_t instance, const fpt_rendering_c
 { return guarded(ctx, [&] { flush_deferred(ctx); require(view != nullptr, "fpt_pssmlt_render: null view"); render_impl(ctx, instance, view); }); }
 
 int fpt_pssmlt_get_stats(fpt_context* ctx, fpt_pssmlt_stats* out)
-{ return guarded(ctx, [&] { require(out != nullptr, "fpt_pssmlt_get_stats: null"); require(ctx->mlt.ready, "fpt_pssmlt_get_stats: fpt_pssmlt_init has not been called"); *out = ctx->mlt.stats; }); }
+{ return guarded(ctx, [&] { require(out != nullptr, "fpt_pssmlt_get_stats: null"); require(ctx->mlt.ready && !ctx->mlt.multiplexed, "fpt_pssmlt_get_stats: fpt_pssmlt_init has not been called"); *out = ctx->mlt.stats; }); }
 
 int fpt_pssmlt_download(fpt_context* ctx, float* h_light_u, float* h_eye_u, float* h_path_value, float* h_path_pdf, uint32_t* h_rejections, uint32_t* h_seeds, float* h_presample)
 {
 	return guarded(ctx, [&] {
 		fpt_context::MltState& m = ctx->mlt;
-		require(m.ready, "fpt_pssmlt_download: fpt_pssmlt_init has not been called");
+		require(m.ready && !m.multiplexed, "fpt_pssmlt_download: fpt_pssmlt_init has not been called");
 		hipStream_t s = ctx->stream;
 		const size_t n = m.n_chains, nu = size_t(coord_dims(m)) * n;
 		if (h_light_u) m.light_u.download(h_light_u, nu, s);
@@ -149,7 +235,7 @@ int fpt_pssmlt_debug_eval(fpt_context* ctx, const fpt_rendering_context_view* vi
 {
 	return guarded(ctx, [&] {
 		fpt_context::MltState& m = ctx->mlt;
-		require(m.ready, "fpt_pssmlt_debug_eval: fpt_pssmlt_init has not been called");
+		require(m.ready && !m.multiplexed, "fpt_pssmlt_debug_eval: fpt_pssmlt_init has not been called");
 		require(view && h_light_u && h_eye_u && h_value, "fpt_pssmlt_debug_eval: null argument");
 		require(n >= 1 && n <= std::max(m.n_pixels, m.n_chains), "fpt_pssmlt_debug_eval: n out of range [1, max(n_pixels, n_chains)]");
 		hipStream_t s = ctx->stream;
@@ -168,8 +254,8 @@ int fpt_pssmlt_debug_eval(fpt_context* ctx, const fpt_rendering_context_view* vi
 int fpt_debug_mlt(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_params, uint32_t n_params, void* const* h_arrays, uint32_t n_arrays)
 {
 	return guarded(ctx, [&] {
-		static const uint32_t want_params[3] = { 4, 1, 10 }, want_arrays[3] = { 6, 3, 10 };
-		require(op >= 0 && op <= 2, "fpt_debug_mlt: unknown op");
+		static const uint32_t want_params[5] = { 4, 1, 10, 1, 3 }, want_arrays[5] = { 6, 3, 10, 3, 4 };
+		require(op >= 0 && op <= 4, "fpt_debug_mlt: unknown op");
 		require(n_params == want_params[op] && n_arrays == want_arrays[op] && h_arrays && h_params, "fpt_debug_mlt: wrong number of parameters or arrays for this op");
 		flush_deferred(ctx);
 		hipStream_t s = ctx->stream;
@@ -193,6 +279,13 @@ int fpt_debug_mlt(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_params
 			FPT_HIP_CHECK(hipGetLastError());
 			FPT_HIP_CHECK(hipStreamSynchronize(s));          // `q` and `scratch` are released on return
 		}
+		else if (op == 3 || op == 4)
+		{
+			require(h_params[0] >= 1 && h_params[0] <= 15, "fpt_debug_mlt: max_path_length out of range [1,15]");
+			if (n && op == 3) launch_debug_mmlt_tech(n, h_params[0], static_cast<const uint32_t*>(arr(0)), static_cast<uint32_t*>(arr(1)), static_cast<uint32_t*>(arr(2)), s);
+			if (n && op == 4) launch_debug_mmlt_swap(n, h_params[0], h_params[1], h_params[2], static_cast<const uint32_t*>(arr(0)), static_cast<const uint32_t*>(arr(1)),
+			                                         static_cast<uint32_t*>(arr(2)), static_cast<float*>(arr(3)), s);
+		}
 		else
 		{
 			MltChains C; std::memset(&C, 0, sizeof(C));
@@ -210,6 +303,113 @@ int fpt_debug_mlt(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_params
 		}
 		FPT_HIP_CHECK(hipGetLastError());
 		FPT_HIP_CHECK(hipStreamSynchronize(s));
+	});
+}
+
+int fpt_mmlt_init(fpt_context* ctx, const fpt_mmlt_options* opts, const fpt_rendering_context_view* view, const char* h_samples_dir,
+                  const uint32_t* d_pixels, uint32_t n_local_pixels)
+{
+	return guarded(ctx, [&] {
+		flush_deferred(ctx);
+		require(opts && view, "fpt_mmlt_init: null argument");
+		fpt_context::MltState& m = ctx->mlt;
+		m.ready = false; m.multiplexed = false; (void)n_local_pixels;
+		const uint32_t n_pixels = view->res_x * view->res_y;
+		require(n_pixels > 0, "fpt_mmlt_init: empty frame");
+		if (const char* why = mmlt_refusal(*opts, n_pixels, d_pixels != nullptr)) require(false, why);
+		m.opt = opts->mlt; m.mmlt_frequency = opts->mmlt_frequency;
+		// forced as in PSSMLT: no light tracing (no technique with t <= 1), every connection of the path's own light sub-path: one sample per technique
+		m.opt.bpt.light_tracing = 0.0f; m.opt.bpt.single_connection = 0u;
+		const uint32_t n_chains = m.opt.n_chains, cap = std::max(n_pixels, n_chains), L = m.opt.bpt.max_path_length;
+		bpt_init(ctx, &m.opt.bpt, view, h_samples_dir, nullptr, 0u, n_chains);
+		m.n_pixels = n_pixels; m.n_chains = n_chains; m.chain_length = mlt_chain_length(m.opt.spp, n_pixels, n_chains);
+		m.n_tech = mlt_tech_count(L);
+		const uint32_t n_cells = m.n_tech * n_pixels;          // below 2^32: mmlt_refusal
+		const size_t dims = coord_dims(m);
+		m.table.alloc(n_cells); m.new_value.alloc(cap); m.path_value.alloc(n_chains);
+		m.light_u.alloc(dims * cap); m.eye_u.alloc(dims * cap); m.path_pdf.alloc(n_chains); m.rejections.alloc(n_chains); m.seeds.alloc(n_chains);
+		m.st.alloc(n_chains); m.st_new.alloc(n_chains); m.path_seeds.alloc(n_chains); m.tech_chains.alloc(m.n_tech); m.ends.alloc(m.n_tech);
+		m.q.alloc(n_cells); m.cdf.alloc(n_cells); m.counts.alloc(2); m.mcounts.alloc(3);
+		const size_t scratch = mlt_seed_cdf_scratch_bytes(n_cells);
+		require(scratch != 0, "fpt_mmlt_init: the scan's scratch size could not be determined");
+		m.scan_scratch.alloc(scratch);
+		hipStream_t s = ctx->stream;
+		zero(m.table, n_cells, s); zero(m.new_value, cap, s); zero(m.path_value, n_chains, s); zero(m.light_u, dims * cap, s); zero(m.eye_u, dims * cap, s);
+		zero(m.path_pdf, n_chains, s); zero(m.rejections, n_chains, s); zero(m.seeds, n_chains, s); zero(m.counts, 2, s); zero(m.mcounts, 3, s);
+		zero(m.st, n_chains, s); zero(m.st_new, n_chains, s); zero(m.path_seeds, n_chains, s); zero(m.tech_chains, m.n_tech, s); zero(m.ends, m.n_tech, s);
+		m.st_norms.assign(size_t(L + 2) * (L + 2), 0.0f); m.st_chains.assign(size_t(L + 2) * (L + 2), 0u);
+		std::memset(&m.mstats, 0, sizeof(m.mstats));
+		m.mstats.n_chains = n_chains; m.mstats.chain_length = m.chain_length;
+		m.ready = true; m.multiplexed = true;
+	});
+}
+
+int fpt_mmlt_render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view)
+{ return guarded(ctx, [&] { flush_deferred(ctx); require(view != nullptr, "fpt_mmlt_render: null view"); mmlt_render_impl(ctx, instance, view); }); }
+
+int fpt_mmlt_get_stats(fpt_context* ctx, fpt_mmlt_stats* out)
+{
+	return guarded(ctx, [&] {
+		require(out != nullptr, "fpt_mmlt_get_stats: null");
+		require(ctx->mlt.ready && ctx->mlt.multiplexed, "fpt_mmlt_get_stats: fpt_mmlt_init has not been called");
+		*out = ctx->mlt.mstats;
+	});
+}
+
+int fpt_mmlt_get_st_norms(fpt_context* ctx, float* h_st_norms, uint32_t* h_chains)
+{
+	return guarded(ctx, [&] {
+		fpt_context::MltState& m = ctx->mlt;
+		require(m.ready && m.multiplexed, "fpt_mmlt_get_st_norms: fpt_mmlt_init has not been called");
+		if (h_st_norms) std::memcpy(h_st_norms, m.st_norms.data(), m.st_norms.size() * sizeof(float));
+		if (h_chains) std::memcpy(h_chains, m.st_chains.data(), m.st_chains.size() * sizeof(uint32_t));
+	});
+}
+
+int fpt_mmlt_download(fpt_context* ctx, float* h_light_u, float* h_eye_u, float* h_path_value, float* h_path_pdf, uint32_t* h_rejections, uint32_t* h_seeds, uint32_t* h_st, float* h_table)
+{
+	return guarded(ctx, [&] {
+		fpt_context::MltState& m = ctx->mlt;
+		require(m.ready && m.multiplexed, "fpt_mmlt_download: fpt_mmlt_init has not been called");
+		hipStream_t s = ctx->stream;
+		const size_t n = m.n_chains, nu = size_t(coord_dims(m)) * n;
+		if (h_light_u) m.light_u.download(h_light_u, nu, s);
+		if (h_eye_u) m.eye_u.download(h_eye_u, nu, s);
+		if (h_path_value) m.path_value.download(reinterpret_cast<float4*>(h_path_value), n, s);
+		if (h_path_pdf) m.path_pdf.download(h_path_pdf, n, s);
+		if (h_rejections) m.rejections.download(h_rejections, n, s);
+		if (h_seeds) m.seeds.download(h_seeds, n, s);
+		if (h_st) m.st.download(h_st, n, s);
+		if (h_table) m.table.download(reinterpret_cast<float4*>(h_table), size_t(m.n_tech) * m.n_pixels, s);
+		FPT_HIP_CHECK(hipStreamSynchronize(s));
+	});
+}
+
+int fpt_mmlt_debug_eval(fpt_context* ctx, const fpt_rendering_context_view* view, uint32_t n, const float* h_light_u, const float* h_eye_u, const uint32_t* h_st, float* h_value, uint64_t* h_rays)
+{
+	return guarded(ctx, [&] {
+		fpt_context::MltState& m = ctx->mlt;
+		require(m.ready && m.multiplexed, "fpt_mmlt_debug_eval: fpt_mmlt_init has not been called");
+		require(view && h_light_u && h_eye_u && h_st && h_value, "fpt_mmlt_debug_eval: null argument");
+		require(n >= 1 && n <= std::max(m.n_pixels, m.n_chains), "fpt_mmlt_debug_eval: n out of range [1, max(n_pixels, n_chains)]");
+		const uint32_t L = m.opt.bpt.max_path_length;
+		for (uint32_t i = 0; i < n; ++i) require(mlt_tech_valid(h_st[i] & 0xFFu, h_st[i] >> 8, L), "fpt_mmlt_debug_eval: a technique outside t in [2, L + 1], s in [0, L + 1 - t]");
+		hipStream_t s = ctx->stream;
+		const size_t nu = size_t(coord_dims(m)) * n;
+		// the chains' own coordinates and techniques are kept: the caller's sets are evaluated from scratch arrays
+		DeviceArray<float> lu, eu; DeviceArray<uint32_t> st; DeviceArray<unsigned long long> rays;
+		lu.upload(h_light_u, nu, s); eu.upload(h_eye_u, nu, s); st.upload(h_st, n, s); rays.alloc(1);
+		zero(rays, 1, s);
+		zero(m.new_value, n, s);
+		ChainCoords c = chain_view(m, n, 0u, 0u);
+		c.light_u = lu.ptr; c.eye_u = eu.ptr;
+		const ChainTech fixed = { st.ptr, rays.ptr };
+		bpt_sample_paths(ctx, 0u, view, n, &c, m.new_value.ptr, nullptr, nullptr, &fixed);          // (with mutation Null nothing reads the instance)
+		m.new_value.download(reinterpret_cast<float4*>(h_value), n, s);
+		unsigned long long r = 0;
+		FPT_HIP_CHECK(hipMemcpyAsync(&r, rays.ptr, sizeof(r), hipMemcpyDeviceToHost, s));
+		FPT_HIP_CHECK(hipStreamSynchronize(s));
+		if (h_rays) *h_rays = r;
 	});
 }
 

@@ -1,5 +1,6 @@
-// fpt_mlt_host.h — the host-only arithmetic of the Metropolis renderer (fpt_mlt_api.cpp): option checks, chain length, normalisation, the choice of a step's
-// mutation.  Pure functions of their arguments, so that a stand-alone program can run them under a sanitizer (tools/mlt_host_check.cpp).
+// fpt_mlt_host.h — the host-only arithmetic of the Metropolis renderers (fpt_mlt_api.cpp): option checks, chain length, normalisation, the choice of a step's
+// mutation; for the multiplexed renderer the technique count and index, the swap proposal (shared with the kernels) and its refusals.  Pure functions of their
+// arguments, so that a stand-alone program can run them under a sanitizer (tools/mlt_host_check.cpp).
 #pragma once
 #include "fpt_math.h"
 #include "../../include/fermat_pt_hip.h"
@@ -30,6 +31,74 @@ inline uint32_t mlt_mutation_type(float independent_samples, uint32_t instance, 
 {
 	if (step == 0) return 0u;
 	return randfloat(step, hash32(instance + 0x9e3779b9u)) < independent_samples ? 2u : 1u;
+}
+
+// ---- the multiplexed renderer (`-mmlt`): one bidirectional technique (s light vertices, t eye vertices) per chain ------------------------------------------
+// With light tracing off the techniques are t in [2, L + 1], s in [0, L + 1 - t]: L (L + 1) / 2 of them, numbered t-major (all techniques of t = 2, s rising, then
+// t = 3, ...): index = sum_{j = 2}^{t - 1} (L + 2 - j) + s.  Shared by the kernels (fpt_bpt.hip, fpt_mlt.hip) and the host
+FPT_HD uint32_t mlt_tech_count(uint32_t L) { return L * (L + 1u) / 2u; }
+FPT_HD bool mlt_tech_valid(uint32_t s, uint32_t t, uint32_t L) { return t >= 2u && t <= L + 1u && s <= L + 1u - t; }
+FPT_HD uint32_t mlt_tech_index(uint32_t s, uint32_t t, uint32_t L) { return (t - 2u) * (L + 2u) - (t * (t - 1u) / 2u - 1u) + s; }
+// the inverse: technique `index` < mlt_tech_count(L) as s | t << 8 (the word a chain keeps)
+FPT_HD uint32_t mlt_tech_st(uint32_t index, uint32_t L)
+{
+	uint32_t t = 2u;
+	while (t < L + 1u && index >= L + 2u - t) { index -= L + 2u - t; ++t; }
+	return index | (t << 8);
+}
+// the swap proposal (mmlt_swap_kernel, cmlt.cu:496-544): the cyclic walk on s in [0, k - 1], k = s + t - 1 the path length, which s + t keeps: u > 1/2 proposes
+// s + 1 (0 from t = 2), otherwise s - 1 (s + t - 2 from s = 0).  k = 1 proposes the chain's own technique.  Returns s_new | t_new << 8; needs t >= 2
+FPT_HD uint32_t mlt_swap_proposal(uint32_t s, uint32_t t, float u)
+{
+	const uint32_t s_new = u > 0.5f ? (t > 2u ? s + 1u : 0u) : (s > 0u ? s - 1u : s + t - 2u);
+	return s_new | ((s + t - s_new) << 8);
+}
+// the dimension of mlt_mutation_number that picks the swap's direction: one past the accept/reject number
+FPT_HD uint32_t mlt_swap_dim(uint32_t L) { return (L + 1u) * 6u + 1u; }
+// is chain step `step` a swap step?  (mmlt_frequency = F > 0, at step l > 0 with l % F == 0; cmlt.cu:1118)
+FPT_HD bool mlt_is_swap_step(uint32_t frequency, uint32_t step) { return frequency != 0u && step != 0u && step % frequency == 0u; }
+// the most rays one proposal of technique (s, t) queues: s - 1 light sub-path rays, t - 1 eye sub-path rays, one connection for s > 0
+FPT_HD uint32_t mlt_tech_max_rays(uint32_t s, uint32_t t) { return (s > 0u ? s - 1u : 0u) + (t - 1u) + (s > 0u ? 1u : 0u); }
+// The seeds of the multiplexed renderer: stratified targets with ONE offset common to all strata (systematic sampling), in exact integers.  With m = the offset in
+// units of 2^-24, target_i = floor(total * (i * 2^24 + m) / (n * 2^24)), i < n.  A block [A, B) of the integer CDF receives the strata with A <= target_i < B, i.e.
+// with i + m 2^-24 in [n A / total, n B / total): their number differs from n (B - A) / total by LESS than 1 -- the chains per technique are within 1 of their
+// share, which per-stratum jitter (PSSMLT's sample_seeds) cannot promise (it bounds the cumulative counts by 1, a block's own by 2).  The offset is uniform over the
+// render calls, so a cell is still drawn in proportion to its value
+// floor(a * b / d) for a, b < d < 2^63: the 128-bit product, then a bitwise long division (no 128-bit division on the device)
+FPT_HD unsigned long long mlt_muldiv(unsigned long long a, unsigned long long b, unsigned long long d)
+{
+	const unsigned __int128 p = (unsigned __int128)a * b;
+	const unsigned long long lo = (unsigned long long)p;
+	unsigned long long r = (unsigned long long)(p >> 64), q = 0;          // r < d because a, b < d
+	for (int i = 63; i >= 0; --i)
+	{
+		r = (r << 1) | ((lo >> i) & 1ull); q <<= 1;
+		if (r >= d) { r -= d; q |= 1ull; }
+	}
+	return q;
+}
+// the common offset of render call `instance`, in units of 2^-24: a counter-based number, as the mutation numbers are
+FPT_HD uint32_t mlt_seed_offset(uint32_t instance) { return uint32_t(randfloat(instance, hash32(0x5eed5eedu)) * 16777216.0f) & 0xFFFFFFu; }
+// target_i (above); n_seeds < 2^24 (mmlt_refusal), so the divisor is below 2^48
+FPT_HD unsigned long long mlt_seed_target(unsigned long long total, uint32_t i, uint32_t n_seeds, uint32_t offset)
+{
+	const unsigned long long d = (unsigned long long)n_seeds << 24, num = ((unsigned long long)i << 24) | offset;
+	return (total / d) * num + mlt_muldiv(total % d, num, d);
+}
+// (st_norm of a technique is mlt_image_brightness on the seed CDF's difference across the technique's block of the table)
+// why fpt_mmlt_init refuses these options (the message names the option), or NULL: fpt_pssmlt_init's reasons and a technique table whose cells do not fit 32 bits
+inline const char* mmlt_refusal(const fpt_mmlt_options& o, uint32_t n_pixels, bool sharded)
+{
+	if (o.mlt.bpt.use_vpls) return "fpt_mmlt_init: use_vpls = 1 is not supported (a chain's first light coordinate would have to select a VPL)";
+	if (sharded) return "fpt_mmlt_init: a tile-sharded context (pixels != NULL) is not supported: a chain splats to any pixel";
+	if (o.mlt.n_chains == 0) return "fpt_mmlt_init: n_chains must be at least 1";
+	if (o.mlt.n_chains >= (1u << 24)) return "fpt_mmlt_init: n_chains must stay below 2^24 (light-vertex ids hold 24-bit path indices)";
+	if (uint64_t(o.mlt.spp) * n_pixels < o.mlt.n_chains) return "fpt_mmlt_init: spp * n_pixels < n_chains: the chains would have no steps (raise spp or lower n_chains)";
+	if (uint64_t(o.mlt.spp) * n_pixels / o.mlt.n_chains > 0xFFFFFFFFull) return "fpt_mmlt_init: spp * n_pixels / n_chains does not fit 32 bits";
+	if (o.mlt.bpt.max_path_length < 1 || o.mlt.bpt.max_path_length > 15) return "fpt_mmlt_init: max_path_length out of range [1,15]";
+	if (uint64_t(mlt_tech_count(o.mlt.bpt.max_path_length)) * n_pixels > 0xFFFFFFFFull)
+		return "fpt_mmlt_init: the technique table (max_path_length (max_path_length + 1) / 2 cells per pixel) does not fit 32 bits: lower the resolution or max_path_length";
+	return nullptr;
 }
 
 } // namespace fpt

@@ -97,6 +97,7 @@ void RenderingContext::init(int argc, char** argv, const SceneArrays& scene)
 	register_renderer("bpt", &HipBPT::factory);
 	register_renderer("psfpt", &HipPSFPT::factory);
 	register_renderer("pssmlt", &HipPSSMLT::factory);
+	register_renderer("mmlt", &HipMMLT::factory);
 	int device = 0;
 	uint32 renderer_type = 0;
 	for (int i = 0; i < argc; ++i)                           // flag loop, src/renderer.cu:493-539 (unknown flags are ignored)
@@ -378,6 +379,7 @@ void HipPathTracer::update_scene(RenderingContext& renderer) { rebuild_emitters(
 void HipPSFPT::update_scene(RenderingContext& renderer) { rebuild_emitters(renderer, "PSFPT::update_scene"); }
 void HipBPT::update_scene(RenderingContext& renderer) { rebuild_emitters(renderer, "BPT::update_scene"); }
 void HipPSSMLT::update_scene(RenderingContext& renderer) { rebuild_emitters(renderer, "PSSMLT::update_scene"); }
+void HipMMLT::update_scene(RenderingContext& renderer) { rebuild_emitters(renderer, "MMLT::update_scene"); }
 
 void HipPathTracer::render(const uint32 instance, RenderingContext& renderer)
 {
@@ -526,10 +528,9 @@ void HipBPT::init(int argc, char** argv, RenderingContext& renderer)
 }
 
 // ---- HipPSSMLT ---------------------------------------------------------------------------------------------------------------
-void HipPSSMLT::init(int argc, char** argv, RenderingContext& renderer)
+// BPTOptionsBase + PSSMLTOptions defaults and parse (src/bpt_options.h:42-92, src/renderers/pssmlt.h:54-99); shared with HipMMLT
+static void parse_pssmlt_options(int argc, char** argv, fpt_pssmlt_options& p)
 {
-	// BPTOptionsBase + PSSMLTOptions defaults and parse (src/bpt_options.h:42-92, src/renderers/pssmlt.h:54-99)
-	fpt_pssmlt_options& p = m_options;
 	fpt_bpt_options& o = p.bpt;
 	o.max_path_length = 6; o.direct_lighting_nee = 1; o.direct_lighting_bsdf = 1; o.indirect_lighting_nee = 1; o.indirect_lighting_bsdf = 1;
 	o.visible_lights = 1; o.use_vpls = 0; o.rr = 1; o.light_tracing = 0.0f; o.single_connection = 0;
@@ -554,6 +555,11 @@ void HipPSSMLT::init(int argc, char** argv, RenderingContext& renderer)
 		else if (is("-perturbations")) p.light_perturbations = p.eye_perturbations = std::atoi(argv[++i]) > 0;
 		else if (is("-independent-samples") || is("-independent") || is("-is")) p.independent_samples = float(std::atof(argv[++i]));
 	}
+}
+void HipPSSMLT::init(int argc, char** argv, RenderingContext& renderer)
+{
+	fpt_pssmlt_options& p = m_options;
+	parse_pssmlt_options(argc, argv, p);
 	fpt_context* ctx = renderer.get_hip_context();
 	const fpt_rendering_context_view v = renderer.view(0);
 	const SceneArrays& h = renderer.get_host_scene();
@@ -564,6 +570,41 @@ void HipPSSMLT::render(const uint32 instance, RenderingContext& renderer)
 {
 	const fpt_rendering_context_view v = renderer.view(instance);
 	check(renderer.get_hip_context(), fpt_pssmlt_render(renderer.get_hip_context(), instance, &v), "PSSMLT::render");
+}
+
+// ---- HipMMLT: the reference's `-cmlt -charted-swaps 0` (CMLTOptions, src/renderers/cmlt.h) --------------------------------------------------
+void HipMMLT::init(int argc, char** argv, RenderingContext& renderer)
+{
+	fpt_mmlt_options& p = m_options;
+	parse_pssmlt_options(argc, argv, p.mlt);
+	p.mmlt_frequency = 0;
+	for (int i = 0; i + 1 < argc; ++i)
+		if (std::strcmp(argv[i], "-mmlt-swaps") == 0 || std::strcmp(argv[i], "-mmlt-frequency") == 0) p.mmlt_frequency = uint32(std::atoi(argv[++i]));
+	fpt_context* ctx = renderer.get_hip_context();
+	const fpt_rendering_context_view v = renderer.view(0);
+	const SceneArrays& h = renderer.get_host_scene();
+	renderer.init_mesh_lights("mesh_lights.init");     // src/renderers/cmlt.cu:847-852
+	check(ctx, fpt_mmlt_init(ctx, &p, &v, h.samples_dir, renderer.shard_pixels(), renderer.shard_count()), "MMLT::init");
+}
+void HipMMLT::render(const uint32 instance, RenderingContext& renderer)
+{
+	const fpt_rendering_context_view v = renderer.view(instance);
+	fpt_context* ctx = renderer.get_hip_context();
+	check(ctx, fpt_mmlt_render(ctx, instance, &v), "MMLT::render");
+	if (instance == 0)
+	{
+		// the per-technique norms and the chains seeded with each technique (the table CMLT::render prints at instance 0, cmlt.cu:1060-1077)
+		const uint32 L = m_options.mlt.bpt.max_path_length, W = L + 2;
+		std::vector<float> norms(size_t(W) * W, 0.0f); std::vector<uint32_t> chains(size_t(W) * W, 0u);
+		fpt_mmlt_stats st;
+		check(ctx, fpt_mmlt_get_st_norms(ctx, norms.data(), chains.data()), "MMLT::render (st norms)");
+		check(ctx, fpt_mmlt_get_stats(ctx, &st), "MMLT::render (stats)");
+		std::fprintf(stderr, "  image brightness: %f\n", st.image_brightness);
+		std::fprintf(stderr, "  st chains\n");
+		for (uint32 t = 2; t <= L + 1; ++t)
+			for (uint32 s = 0; s + t <= L + 1; ++s)
+				std::fprintf(stderr, "    [%u,%u] : %7u, %f\n", s, t, chains[s + t * W], norms[s + t * W]);
+	}
 }
 
 // the integer all-reduce of the light-tracing splat sums (3 x int64 per pixel per pass in flight), then the fold into the frame

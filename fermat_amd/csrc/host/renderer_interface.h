@@ -222,6 +222,19 @@ struct HipPSSMLT final : RendererInterface
 	fpt_pssmlt_options m_options;
 };
 
+// the multiplexed Metropolis renderer (one bidirectional technique per chain: the reference's `-cmlt -charted-swaps 0`, src/renderers/cmlt.h); `-mmlt` on the
+// command line, with HipPSSMLT's options and -mmlt-swaps F.  Prints the (s,t) table of norms and seeded chains at instance 0
+struct HipMMLT final : RendererInterface
+{
+	void init(int argc, char** argv, RenderingContext& renderer) override;
+	void update_scene(RenderingContext& renderer) override;      // as HipPathTracer's
+	void render(const uint32 instance, RenderingContext& renderer) override;
+	void destroy() override { delete this; }
+	static RendererInterface* factory() { return new HipMMLT(); }
+
+	fpt_mmlt_options m_options;
+};
+
 } // namespace fermat
 
 // plugin entry point with the reference's name and meaning (src/renderers/hellopt_plugin.cpp:35-39)

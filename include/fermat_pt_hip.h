@@ -430,8 +430,55 @@ int fpt_pssmlt_debug_eval(fpt_context* ctx, const fpt_rendering_context_view* vi
  *   op 1  seed_cdf + sample_seeds: n values; params {n_seeds}; arrays {value float4 n, cdf uint64 n, seeds uint32 n_seeds}
  *   op 2  accept_reject + resolve on hand-made chains: n chains; params {max_path_length, instance, step, mutation, light_perturbations, eye_perturbations, radius bits,
  *         pdf_norm bits, res_x, res_y}; arrays {light_u, eye_u, new_value float4, path_value float4, path_pdf, rejections, splat int64 3 per pixel (zeroed by the caller),
- *         splat_out (copy of the sums before the resolve), composited float4 per pixel, counts uint64[2]} */
+ *         splat_out (copy of the sums before the resolve), composited float4 per pixel, counts uint64[2]}
+ *   op 3  technique index: params {max_path_length}; arrays {st uint32 n (s | t << 8), index uint32 n (0xFFFFFFFF for a technique outside the table), back uint32 n
+ *         (the technique of that index as s | t << 8)}
+ *   op 4  swap proposal: params {max_path_length, instance, step}; arrays {st uint32 n, chain uint32 n, st_new uint32 n, m_out float n (the number that chose)} */
 int fpt_debug_mlt(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_params, uint32_t n_params, void* const* h_arrays, uint32_t n_arrays);
+
+/* ---- multiplexed Metropolis light transport (`-mmlt`): one bidirectional technique per chain.  The reference's `-cmlt -charted-swaps 0`
+ *      (src/renderers/cmlt.{h,cu}): the part of CMLT that needs no path inversion -----------------------------------------------------------------------------------
+ * A technique is (s light vertices, t eye vertices); with light tracing off t is in [2, L + 1] and s in [0, L + 1 - t]: L (L + 1) / 2 techniques, numbered t-major
+ * (index = sum_{j=2}^{t-1} (L + 2 - j) + s).  One render call: the frame is rescaled; a presampling BPT pass over the pixels stores every sample in the cell
+ * [technique * n_pixels + pixel] of the technique table; the PSSMLT integer CDF over all cells draws n_chains stratified seeds -- stratum i's target is the exact integer
+ * floor(total * (i * 2^24 + m) / (n_chains * 2^24)), m = floor(randfloat(instance, hash32(0x5eed5eed)) * 2^24) ONE offset for all strata, so that every technique starts
+ * within 1 of n_chains * its share of the chains --, seed e starting a chain with technique e / n_pixels from the coordinates of eye path e % n_pixels: the chains start
+ * sorted by technique; st_norm(s, t) = (the CDF's difference across the technique's
+ * block) * 2^-32 / n_pixels and image_brightness the same expression on the total; every chain then takes chain_length steps as PSSMLT's on its OWN technique: the
+ * light sub-path stops at vertex s - 1 (none for s = 0), the eye sub-path at vertex t, one connection or the emission is sampled -- at most
+ * max(s - 1, 0) + (t - 1) + [s > 0] rays per proposal.  mmlt_frequency = F > 0: step l > 0 with l % F == 0 keeps the coordinates and proposes the neighbouring
+ * technique of the same path length instead (the cyclic walk on s of mmlt_swap_kernel, cmlt.cu:496-544, chosen by mutation number dimension (L + 1) * 6 + 1),
+ * accepted with min(1, new / old) and splatted as any other step; the technique is replaced with the value on acceptance.
+ * Deviations: PSSMLT's three (above), the seeds' common offset (PSSMLT jitters every stratum on its own, in float), and the swap's acceptance test takes no st_norms ratio (the reference multiplies the test, not the splats, by
+ * st_norms[new] / st_norms[old], cmlt.cu:375-377): the target is max_comp f_{s,t}(u) on the disjoint union of the techniques and the walk is symmetric.
+ * Not built: charted swaps and path inversion, chains that persist across render calls (`reseeding`, `startup_skips`: every call reseeds), techniques with t <= 1 and
+ * light tracing, single_connection = 1, passes in flight, tile sharding / multi-GPU.
+ * fpt_mmlt_init replaces fpt_pssmlt_init / fpt_bpt_init and refuses what fpt_pssmlt_init refuses, and a technique table of 2^32 cells or more. */
+typedef struct fpt_mmlt_options
+{
+	fpt_pssmlt_options mlt;
+	uint32_t mmlt_frequency;               /* 0: no swaps */
+} fpt_mmlt_options;
+typedef struct fpt_mmlt_stats
+{
+	float image_brightness, pdf_norm;      /* of the last render call */
+	uint32_t chain_length, n_chains;
+	uint64_t accepted, rejected;           /* proposals of the last render call, step 0 and swaps included */
+	uint64_t swaps_proposed, swaps_accepted;
+	uint64_t rays;                         /* rays queued by the chain steps: sub-path and connection rays (the presampling pass is not counted) */
+} fpt_mmlt_stats;
+int fpt_mmlt_init(fpt_context* ctx, const fpt_mmlt_options* opts, const fpt_rendering_context_view* view, const char* h_samples_dir,
+                  const uint32_t* d_pixels, uint32_t n_local_pixels);        /* d_pixels: as fpt_bpt_init's, and must be NULL */
+int fpt_mmlt_render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view);
+int fpt_mmlt_get_stats(fpt_context* ctx, fpt_mmlt_stats* out);
+/* of the last render call: st_norms[s + t * (L + 2)] (float, (L + 2)^2 entries, 0 outside the table) and the number of chains seeded with each technique, indexed alike */
+int fpt_mmlt_get_st_norms(fpt_context* ctx, float* h_st_norms, uint32_t* h_chains);
+/* as fpt_pssmlt_download without the presample; h_st: each chain's technique s | t << 8; h_table: the technique table, float4 x n_techniques x n_pixels */
+int fpt_mmlt_download(fpt_context* ctx, float* h_light_u, float* h_eye_u, float* h_path_value /*float4*/, float* h_path_pdf, uint32_t* h_rejections, uint32_t* h_seeds,
+                      uint32_t* h_st, float* h_table /*float4*/);
+/* as fpt_pssmlt_debug_eval, set i evaluating technique h_st[i] = s | t << 8 alone; h_rays (or NULL) receives the number of rays queued */
+int fpt_mmlt_debug_eval(fpt_context* ctx, const fpt_rendering_context_view* view, uint32_t n, const float* h_light_u, const float* h_eye_u, const uint32_t* h_st,
+                        float* h_value /*float4*/, uint64_t* h_rays);
 
 /* ---- multi-GPU: image tiles sharded over one process per GPU; replaces the single-GPU reference's cudaSetDevice(0) + whole-frame
  *      ownership (src/renderer.cu:600-603).  No data-path collective: each rank renders the pixels handed to fpt_pt_init / fpt_bpt_init

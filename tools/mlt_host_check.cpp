@@ -1,5 +1,5 @@
-// The host-only arithmetic of the Metropolis renderer (fermat_amd/csrc/fpt_mlt_host.h: option checks, chain length, normalisation, the choice of a step's
-// mutation) as a stand-alone CPU program, to be built with -fsanitize=address,undefined:  bash tools/sanitize_mlt_host.sh
+// The host-only arithmetic of the Metropolis renderers (fermat_amd/csrc/fpt_mlt_host.h: option checks, chain length, normalisation, the choice of a step's
+// mutation; for `-mmlt` the technique count and index, the swap proposal and the refusals) as a stand-alone CPU program, to be built with -fsanitize=address,undefined:  bash tools/sanitize_mlt_host.sh
 #include "fpt_bpt_device.h"
 #include "fpt_mlt_host.h"
 #include <cstdio>
@@ -45,6 +45,72 @@ int main()
 	const float ms[] = { 0.0f, 1.0e-45f, 0.25f, 0.49999997f, 0.5f, 0.50000006f, 0.99999994f };
 	for (float m : ms) for (float u : ms) { const float r = mlt_perturbed_u(u, m, 1u, 0.01f); CHECK(r >= 0.0f && r < 1.0f); CHECK(mlt_perturbed_u(u, m, 2u, 0.01f) == m); CHECK(mlt_perturbed_u(u, m, 0u, 0.01f) == u); }
 	for (uint32_t c = 0; c < 4096; ++c) { const float m = mlt_mutation_number(c & 3u, c >> 4, c * 2654435761u, c % 43u); CHECK(m >= 0.0f && m < 1.0f); }
-	std::printf(failures ? "%d check(s) failed\n" : "mlt host helpers: all checks passed\n", failures);
+	// ---- the multiplexed renderer: the technique index is a bijection onto L (L + 1) / 2, t-major, and mlt_tech_st its inverse
+	for (uint32_t L = 1; L <= 15; ++L)
+	{
+		std::vector<uint32_t> seen(mlt_tech_count(L), 0u);
+		CHECK(mlt_tech_count(L) == L * (L + 1) / 2);
+		uint32_t next = 0;
+		for (uint32_t t = 0; t <= L + 3; ++t)
+			for (uint32_t s = 0; s <= L + 3; ++s)
+			{
+				const bool valid = t >= 2 && s + t <= L + 1;
+				CHECK(mlt_tech_valid(s, t, L) == valid);
+				if (!valid) continue;
+				const uint32_t k = mlt_tech_index(s, t, L);
+				CHECK(k == next); ++next;
+				if (k < seen.size()) seen[k]++;
+				CHECK(mlt_tech_st(k, L) == (s | (t << 8)));
+				CHECK(mlt_tech_max_rays(s, t) == (s > 1 ? s - 1 : 0) + (t - 1) + (s > 0 ? 1 : 0));
+				// the swap walk: s + t is kept, t stays >= 2, the two directions undo each other (a symmetric walk on the cycle of k = s + t - 1 techniques)
+				const uint32_t up = mlt_swap_proposal(s, t, 0.75f), down = mlt_swap_proposal(s, t, 0.25f);
+				CHECK((up & 0xFFu) + (up >> 8) == s + t && (down & 0xFFu) + (down >> 8) == s + t && (up >> 8) >= 2 && (down >> 8) >= 2);
+				CHECK(mlt_tech_valid(up & 0xFFu, up >> 8, L) && mlt_tech_valid(down & 0xFFu, down >> 8, L));
+				CHECK(mlt_swap_proposal(up & 0xFFu, up >> 8, 0.25f) == (s | (t << 8)) && mlt_swap_proposal(down & 0xFFu, down >> 8, 0.75f) == (s | (t << 8)));
+				if (s + t == 2) CHECK(up == (s | (t << 8)) && down == up);
+			}
+		CHECK(next == mlt_tech_count(L));
+		for (uint32_t c : seen) CHECK(c == 1u);
+	}
+	CHECK(mlt_swap_proposal(0, 4, 0.5f) == (2u | (2u << 8)) && mlt_swap_proposal(2, 2, 0.50000006f) == (0u | (4u << 8)) && mlt_swap_proposal(1, 3, 0.9f) == (2u | (2u << 8)));
+	CHECK(mlt_swap_dim(6) == 43u);
+	// the seed targets: floor(total * (i 2^24 + m) / (n 2^24)) against the 128-bit quotient, at the ends of every range; rising in i and below the total
+	{
+		const unsigned long long totals[] = { 1ull, 5ull, 0xFFFFFFFFull, 1ull << 42, (1ull << 63) + 12345ull, ~0ull };
+		const uint32_t ns[] = { 1u, 7u, 200u, 65536u, (1u << 24) - 1u }, ms[] = { 0u, 1u, 0x800000u, 0xFFFFFFu };
+		for (unsigned long long total : totals) for (uint32_t n : ns) for (uint32_t m : ms)
+		{
+			const uint32_t is[] = { 0u, n / 2u, n - 1u };
+			unsigned long long prev = 0;
+			for (uint32_t i : is)
+			{
+				const unsigned long long got = mlt_seed_target(total, i, n, m);
+				const unsigned __int128 want = (unsigned __int128)total * ((((unsigned long long)i) << 24) | m) / (((unsigned long long)n) << 24);
+				CHECK(got == (unsigned long long)want && got < total && got >= prev);
+				prev = got;
+			}
+		}
+		CHECK(mlt_muldiv(3, 5, 7) == 2 && mlt_muldiv((1ull << 47) - 1, (1ull << 47) - 1, 1ull << 47) == (1ull << 47) - 2);
+		for (uint32_t inst = 0; inst < 64; ++inst) CHECK(mlt_seed_offset(inst) < (1u << 24));
+		CHECK(mlt_seed_offset(0) != mlt_seed_offset(1));
+	}
+	CHECK(!mlt_is_swap_step(0, 4) && !mlt_is_swap_step(2, 0) && mlt_is_swap_step(2, 4) && !mlt_is_swap_step(2, 3) && mlt_is_swap_step(1, 1));
+	{
+		fpt_mmlt_options mo; std::memset(&mo, 0, sizeof(mo)); mo.mlt = o; mo.mmlt_frequency = 2;
+		CHECK(mmlt_refusal(mo, 1600 * 900, false) == nullptr);
+		auto names = [&](const fpt_mmlt_options& p, uint32_t n_pixels, bool sharded, const char* word)
+		{ const char* w = mmlt_refusal(p, n_pixels, sharded); return w && std::strstr(w, "fpt_mmlt_init") && std::strstr(w, word); };
+		{ fpt_mmlt_options p = mo; p.mlt.bpt.use_vpls = 1; CHECK(names(p, 1024, false, "use_vpls")); }
+		CHECK(names(mo, 1600 * 900, true, "pixels"));
+		{ fpt_mmlt_options p = mo; p.mlt.n_chains = 0; CHECK(names(p, 1024, false, "n_chains")); }
+		{ fpt_mmlt_options p = mo; p.mlt.n_chains = 1u << 24; CHECK(names(p, 1u << 23, false, "n_chains")); }
+		{ fpt_mmlt_options p = mo; p.mlt.n_chains = 300; p.mlt.spp = 1; CHECK(names(p, 256, false, "spp")); }
+		{ fpt_mmlt_options p = mo; p.mlt.n_chains = 1; p.mlt.spp = 0xFFFFFFFFu; CHECK(names(p, 0xFFFFFFu, false, "32 bits")); }
+		{ fpt_mmlt_options p = mo; p.mlt.bpt.max_path_length = 16; CHECK(names(p, 1600 * 900, false, "max_path_length")); }
+		// the technique table: 21 cells per pixel at L = 6, 120 at L = 15; refused from 2^32 cells on
+		{ fpt_mmlt_options p = mo; p.mlt.bpt.max_path_length = 15; CHECK(names(p, 40000u * 1000u, false, "technique table")); CHECK(mmlt_refusal(p, 35791394u, false) == nullptr); CHECK(names(p, 35791395u, false, "32 bits")); }
+		{ fpt_mmlt_options p = mo; CHECK(mmlt_refusal(p, 0xFFFFFFu, false) == nullptr); }
+	}
+	std::printf(failures ? "%d check(s) failed\n" : "mlt host helpers (pssmlt and mmlt): all checks passed\n", failures);
 	return failures ? 1 : 0;
 }

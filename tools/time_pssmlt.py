@@ -1,7 +1,12 @@
-"""Times one render() of the primary-sample-space Metropolis renderer on the water_caustic stand-in (the scene of bench.py --renderer bpt), at the reference's
-defaults (64 K chains, 4 spp) and at 1 M chains.  A timing tool, not a bench line: bench.py measures the flagship workloads and knows nothing of this renderer.
+"""Times one render() of a Metropolis renderer -- the primary-sample-space one (`--renderer pssmlt`, the default) or the multiplexed one (`--renderer mmlt`, one
+(s, t) technique per chain) -- on the water_caustic stand-in (the scene of bench.py --renderer bpt), at the reference's defaults (64 K chains, 4 spp) and at 1 M
+chains.  A timing tool, not a bench line: bench.py measures the flagship workloads and knows nothing of these renderers.
 
-    python tools/time_pssmlt.py [--res 1600 900] [--path-length 9] [--chains 65536 1048576] [--spp 4] [--repeats 3]
+    python tools/time_pssmlt.py [--renderer pssmlt|mmlt] [--mmlt-swaps F] [--res 1600 900] [--path-length 9] [--chains 65536 1048576] [--spp 4] [--repeats 3]
+
+After the timed calls: one call at 2 x spp, from which the time of everything but the chain steps (rescale, presampling pass, seed CDF and seeds, coordinate
+recovery, resolve) is extrapolated as  t(spp) - chain_length(spp) x the time per step,  and one call with the traversal kernels' counters on, which gives the rays
+the traversal fetched per mutation (the presampling pass and null rays included).  `--renderer mmlt` also reports the rays its chain steps queued (its own counter).
 
 Per configuration: one warm-up render call (code objects, allocations), then `--repeats` timed calls of consecutive instances, each timed by the host clock
 around a call that ends in a device synchronise (fpt_pssmlt_render reads its counters back, and synchronize() follows).  Prints one JSON line per configuration:
@@ -29,27 +34,55 @@ def main():
     ap.add_argument("--chains", type=int, nargs="+", default=[64 * 1024, 1024 * 1024])
     ap.add_argument("--spp", type=int, default=4)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--renderer", choices=("pssmlt", "mmlt"), default="pssmlt")
+    ap.add_argument("--mmlt-swaps", type=int, default=0)
     args = ap.parse_args()
+    mmlt = args.renderer == "mmlt"
     W, H = args.res
     L = args.path_length
     s = scene.water_caustic_standin()
     table = np.fromfile(os.path.join(scene.DATA_DIR, "glossy_reflectance.dat"), np.float32)
     for n_chains in args.chains:
-        opts = fa.default_pssmlt_options(L, n_chains=n_chains, spp=args.spp)
-        r = fa.Renderer(s, W, H, fa.default_options(L), table=table, pssmlt_options=opts)
-        r.pssmlt_render(0, sync=True)                                  # warm-up: every shape the timed calls use
-        times = []
-        for i in range(args.repeats):
-            r.synchronize()
-            t0 = time.perf_counter()
-            r.pssmlt_render(1 + i, sync=True)
-            times.append(time.perf_counter() - t0)
-        st = r.pssmlt_stats()
+        def renderer(spp):
+            if mmlt:
+                return fa.Renderer(s, W, H, fa.default_options(L), table=table, mmlt_options=fa.default_mmlt_options(L, mmlt_frequency=args.mmlt_swaps, n_chains=n_chains, spp=spp))
+            return fa.Renderer(s, W, H, fa.default_options(L), table=table, pssmlt_options=fa.default_pssmlt_options(L, n_chains=n_chains, spp=spp))
+
+        def timed(r, first, repeats):
+            render = r.mmlt_render if mmlt else r.pssmlt_render
+            render(0, sync=True)                                           # warm-up: every shape the timed calls use
+            out = []
+            for i in range(repeats):
+                r.synchronize()
+                t0 = time.perf_counter()
+                render(first + i, sync=True)
+                out.append(time.perf_counter() - t0)
+            return out
+        r = renderer(args.spp)
+        times = timed(r, 1, args.repeats)
+        st = r.mmlt_stats() if mmlt else r.pssmlt_stats()
+        # the traversal's own count of the rays it fetched in one more call
+        r.set_counting(True)
+        (r.mmlt_render if mmlt else r.pssmlt_render)(1 + args.repeats, sync=True)
+        closest, shadow = r.trace_counters()
+        r.set_counting(False)
+        traced = int(closest.rays) + int(shadow.rays)
+        r2 = renderer(2 * args.spp)
+        med2 = float(np.median(timed(r2, 1, args.repeats)))
+        st2 = r2.mmlt_stats() if mmlt else r2.pssmlt_stats()
+        r2.close()
         fb = r.framebuffer()[5][:, :3]
         med = float(np.median(times))
         # launches a call enqueues: the presampling pass and chain_length steps, each a BPT wavefront of (L - 1) x 2 light launches + 1 + 3 L + 2 eye launches + the acceptance test
         per_wavefront = 1 + 2 * (L - 1) + 1 + 3 * L + 2
-        print(json.dumps({"tool": "time_pssmlt", "scene": "water_caustic-standin", "triangles": int(s.num_triangles), "resolution": [W, H], "max_path_length": L,
+        step_s = (med2 - med) / max(1, st2["chain_length"] - st["chain_length"])
+        extra = {"renderer": args.renderer, "step_ms": round(step_s * 1e3, 3), "presample_and_seed_s": round(med - st["chain_length"] * step_s, 4),
+                 "traced_rays_per_mutation": round(traced / (st["chain_length"] * n_chains), 3)}
+        if mmlt:
+            n_tech = L * (L + 1) // 2
+            extra.update({"mmlt_swaps": args.mmlt_swaps, "queued_rays_per_mutation": round(st["rays"] / (st["chain_length"] * n_chains), 3), "swaps_proposed": st["swaps_proposed"],
+                          "swaps_accepted": st["swaps_accepted"], "table_cells": n_tech * W * H, "table_MiB": round(n_tech * W * H * 16 / 2 ** 20, 1)})
+        print(json.dumps({**extra, "tool": "time_pssmlt", "scene": "water_caustic-standin", "triangles": int(s.num_triangles), "resolution": [W, H], "max_path_length": L,
                           "n_chains": n_chains, "spp": args.spp, "chain_length": st["chain_length"], "render_s": [round(t, 4) for t in times], "median_s": round(med, 4),
                           "spread_s": round(max(times) - min(times), 4), "launches_per_call_approx": (st["chain_length"] + 1) * per_wavefront + st["chain_length"] + 6,
                           "mutations_per_s_M": round(st["chain_length"] * n_chains / med / 1e6, 2), "msample_per_s": round(args.spp * W * H / med / 1e6, 2),
