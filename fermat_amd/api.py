@@ -105,8 +105,8 @@ def default_pssmlt_options(max_path_length=6, **kw):
 
 
 class MmltOptions(C.Structure):
-    """fpt_mmlt_options: the PSSMLT options plus the swap frequency (CMLTOptions::mmlt_frequency, src/renderers/cmlt.h)"""
-    _fields_ = [("mlt", PssmltOptions), ("mmlt_frequency", C.c_uint32)]
+    """fpt_mmlt_options: the PSSMLT options plus the swap frequency (CMLTOptions::mmlt_frequency, src/renderers/cmlt.h) and the lens-techniques switch"""
+    _fields_ = [("mlt", PssmltOptions), ("mmlt_frequency", C.c_uint32), ("lens_techniques", C.c_uint32)]
 
 
 class MmltStats(C.Structure):
@@ -114,10 +114,10 @@ class MmltStats(C.Structure):
                 ("accepted", C.c_uint64), ("rejected", C.c_uint64), ("swaps_proposed", C.c_uint64), ("swaps_accepted", C.c_uint64), ("rays", C.c_uint64)]
 
 
-def default_mmlt_options(max_path_length=6, mmlt_frequency=0, **kw):
-    """the multiplexed Metropolis renderer (the reference's `-cmlt -charted-swaps 0`): default_pssmlt_options' keywords, and mmlt_frequency = F > 0 for a technique
-    swap at every F-th chain step"""
-    return MmltOptions(default_pssmlt_options(max_path_length, **kw), mmlt_frequency)
+def default_mmlt_options(max_path_length=6, mmlt_frequency=0, lens_techniques=0, **kw):
+    """the multiplexed Metropolis renderer (the reference's `-cmlt -charted-swaps 0`): default_pssmlt_options' keywords, mmlt_frequency = F > 0 for a technique
+    swap at every F-th chain step, and lens_techniques = 1 for the lens connections (s, 1), s in [2, L], beside the others (light tracing is then on)"""
+    return MmltOptions(default_pssmlt_options(max_path_length, **kw), mmlt_frequency, lens_techniques)
 
 
 def tech_word(s, t):
@@ -208,7 +208,8 @@ ENTRY_POINTS = ["fpt_create", "fpt_destroy", "fpt_last_error", "fpt_stream", "fp
                 "fpt_mesh_lights_init_device", "fpt_mesh_lights_update_device", "fpt_rt_set_intersector", "fpt_rt_intersector",
                 "fpt_debug_psf", "fpt_psfpt_debug_set_table_log2", "fpt_debug_bpt", "fpt_debug_frame",
                 "fpt_pssmlt_init", "fpt_pssmlt_render", "fpt_pssmlt_get_stats", "fpt_pssmlt_download", "fpt_pssmlt_debug_eval", "fpt_debug_mlt", "fpt_debug_device_build",
-                "fpt_mmlt_init", "fpt_mmlt_render", "fpt_mmlt_get_stats", "fpt_mmlt_get_st_norms", "fpt_mmlt_download", "fpt_mmlt_debug_eval"]
+                "fpt_mmlt_init", "fpt_mmlt_render", "fpt_mmlt_get_stats", "fpt_mmlt_get_st_norms", "fpt_mmlt_download", "fpt_mmlt_debug_eval",
+                "fpt_mmlt_download_pixels", "fpt_mmlt_debug_eval_pixels", "fpt_debug_bpt_splat_entries"]
 
 # fpt_debug_device_build: the arrays of the last device build, by their `which` (name -> (which, dtype, columns)); rows: n triangles, n - 1 binary nodes or the wide nodes
 LBVH_CELL_DTYPE = np.dtype([("c", "<f4", 7), ("k", "u1", 7), ("k8", "u1"), ("leaf", "u1"), ("count", "u1"), ("spare", "u1", 2)])
@@ -557,6 +558,12 @@ class Renderer:
         self._check(self.L.fpt_bpt_resolve_splats(self.ctx, C.byref(self.view)))
         self.synchronize()
 
+    def bpt_splat_entries(self):
+        """(entries, splatted) of the light-tracing stage's queue after the last bpt_render: all camera connections queued, and those with an unoccluded shadow ray"""
+        n = C.c_uint32(0); v = C.c_uint32(0)
+        self._check(self.L.fpt_debug_bpt_splat_entries(self.ctx, C.byref(n), C.byref(v)))
+        return int(n.value), int(v.value)
+
     def bpt_set_profiling(self, on):
         self._check(self.L.fpt_bpt_set_profiling(self.ctx, C.c_int(1 if on else 0)))
 
@@ -631,22 +638,33 @@ class Renderer:
 
     def mmlt_state(self):
         """what the last mmlt_render left: light_u / eye_u (dims, n_chains), path_value (n_chains, 4), path_pdf, rejections, seeds (cells of the table), st (s | t << 8) per
-        chain, and the technique table (n_techniques, n_pixels, 4)"""
+        chain, and the technique table (n_techniques, n_pixels, 4).  With lens_techniques = 1 the table has the L - 1 lens techniques after the others, and the
+        state also holds table_pixel (L - 1, n_pixels), the pixel of every lens cell's sample, and path_pixel (n_chains), the pixel of every chain's state (0xFFFFFFFF:
+        none / the one of eye coordinates 3 and 4)"""
         L = self._mmlt_L()
         n = int(self.mmlt_options.mlt.n_chains); d = (L + 1) * 3; npx = self.res[0] * self.res[1]
+        lens = int(self.mmlt_options.lens_techniques) != 0
         out = dict(light_u=np.zeros((d, n), np.float32), eye_u=np.zeros((d, n), np.float32), path_value=np.zeros((n, 4), np.float32), path_pdf=np.zeros(n, np.float32),
-                   rejections=np.zeros(n, np.uint32), seeds=np.zeros(n, np.uint32), st=np.zeros(n, np.uint32), table=np.zeros((L * (L + 1) // 2, npx, 4), np.float32))
+                   rejections=np.zeros(n, np.uint32), seeds=np.zeros(n, np.uint32), st=np.zeros(n, np.uint32), table=np.zeros((L * (L + 1) // 2 + (L - 1 if lens else 0), npx, 4), np.float32))
         self._check(self.L.fpt_mmlt_download(self.ctx, *[C.c_void_p(out[k].ctypes.data) for k in ("light_u", "eye_u", "path_value", "path_pdf", "rejections", "seeds", "st", "table")]))
+        if lens:
+            out["table_pixel"] = np.full((L - 1, npx), 0xFFFFFFFF, np.uint32); out["path_pixel"] = np.full(n, 0xFFFFFFFF, np.uint32)
+            self._check(self.L.fpt_mmlt_download_pixels(self.ctx, C.c_void_p(out["table_pixel"].ctypes.data), C.c_void_p(out["path_pixel"].ctypes.data)))
         return out
 
-    def mmlt_eval(self, light_u, eye_u, st, with_rays=False):
+    def mmlt_eval(self, light_u, eye_u, st, with_rays=False, with_pixels=False):
         """the value (n, 4) of n coordinate sets (light_u / eye_u of shape (dims, n)), set i through technique st[i] = s | t << 8 alone, mutation Null; with_rays: also the
-        number of rays the evaluation queued"""
+        number of rays the evaluation queued; with_pixels: (value, rays, pixel), pixel[i] where a t = 1 evaluation landed (0xFFFFFFFF otherwise)"""
         light_u = np.ascontiguousarray(light_u, np.float32); eye_u = np.ascontiguousarray(eye_u, np.float32); st = np.ascontiguousarray(st, np.uint32)
         d = (self._mmlt_L() + 1) * 3
         assert light_u.shape == eye_u.shape and light_u.shape[0] == d and st.shape == (light_u.shape[1],)
         n = light_u.shape[1]
         out = np.zeros((n, 4), np.float32); rays = C.c_uint64(0)
+        if with_pixels:
+            pixel = np.full(n, 0xFFFFFFFF, np.uint32)
+            self._check(self.L.fpt_mmlt_debug_eval_pixels(self.ctx, C.byref(self.view), C.c_uint32(n), C.c_void_p(light_u.ctypes.data), C.c_void_p(eye_u.ctypes.data),
+                                                          C.c_void_p(st.ctypes.data), C.c_void_p(out.ctypes.data), C.byref(rays), C.c_void_p(pixel.ctypes.data)))
+            return out, int(rays.value), pixel
         self._check(self.L.fpt_mmlt_debug_eval(self.ctx, C.byref(self.view), C.c_uint32(n), C.c_void_p(light_u.ctypes.data), C.c_void_p(eye_u.ctypes.data), C.c_void_p(st.ctypes.data),
                                                C.c_void_p(out.ctypes.data), C.byref(rays)))
         return (out, int(rays.value)) if with_rays else out

@@ -40,11 +40,17 @@ struct ValueSink { float4* value; };
 // Technique table sink (the presampling pass of `-mmlt`): the sample of eye path `id` with technique (s, t) is stored in cell[mlt_tech_index(s, t) * n_paths + id]
 // and nothing else is written.  With single_connection = 0 a path has one sample per technique at most: a plain store, free of races for the reason given above
 // sink<MLT> (fpt_bpt.hip).  Set = cell != NULL
-struct TechTable { float4* cell; };
+// With light tracing on (P.light_tracing != 0: the lens techniques (s, 1), s in [2, L], numbered after the others) the pass's light-tracing stage resolves into the
+// table as well: the sample of light path `id` at depth d is stored, when unoccluded, as (c, 1) in cell[mlt_tech_index(d + 1, 1, L, true) * n_paths + id], c the
+// splat BEFORE the multiplication by light_weight, and the pixel it lands on in pixel[(d - 1) * n_paths + id] (the lens block only).  A light path has one vertex per
+// depth at most: plain stores
+struct TechTable { float4* cell; uint32_t* pixel; };
 // Technique-fixed evaluation (the chain steps of `-mmlt`): chain c evaluates technique st[c] = s | t << 8 alone -- its light sub-path stops at vertex s - 1 (none
 // for s = 0), its eye sub-path at vertex t, one connection or the emission is sampled -- and the one sample goes to the ValueSink.  rays, when set, counts the
 // rays queued (sub-path and connection rays; null rays are not counted).  Set = st != NULL; needs ChainCoords and ValueSink
-struct ChainTech { const uint32_t* st; unsigned long long* rays; };
+// A chain whose word says t = 1 (light tracing on) starts no eye sub-path: lens_chain_kernel connects stored vertex s - 1 to the lens, writes the pixel the sample
+// lands on to new_pixel[chain] (0xFFFFFFFF for t >= 2 or when nothing is to be traced) and lens_chain_resolve_kernel puts c * visibility into the ValueSink
+struct ChainTech { const uint32_t* st; unsigned long long* rays; uint32_t* new_pixel; };
 
 struct BptParams
 {
@@ -92,6 +98,10 @@ void launch_bpt_eye_primary(const BptParams& p, hipStream_t s);
 void launch_bpt_eye_vertices(const BptParams& p, uint32_t max_entries, hipStream_t s);
 void launch_bpt_eye_resolve(const BptParams& p, uint32_t max_entries, hipStream_t s);
 void launch_bpt_connect_camera(const BptParams& p, hipStream_t s);
+// the lens techniques of `-mmlt`: the shadow queue connect_camera filled for a TechTable -> the table's lens block; and the chain-mode lens stage (one thread per chain)
+void launch_bpt_lens_table(const BptParams& p, uint32_t max_entries, hipStream_t s);
+void launch_bpt_lens_chain(const BptParams& p, hipStream_t s);
+void launch_bpt_lens_chain_resolve(const BptParams& p, hipStream_t s);
 void launch_bpt_build_flat_list(const BptParams& p, hipStream_t s);     // -sc 1: count, scan, fill
 // shared light vertices: this rank's stored vertices (paths `pixels`, n_passes passes) -> wire records, *out_count += their number; and the inverse
 void launch_bpt_pack_light_vertices(const LightVertexRecord* rec, const uint32_t* counts, const uint32_t* pixels, uint32_t n_local, uint32_t n_paths, uint32_t n_passes,

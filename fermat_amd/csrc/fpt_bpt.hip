@@ -7,6 +7,7 @@
 //   eye_resolve_kernel        solve_occlusion + ConnectionsSink<false>   src/bpt_kernels.h:899-916 ; src/renderers/bpt_impl.h:131-163
 //   connect_camera_kernel     light_tracing_kernel / connect_to_camera   src/bpt_kernels.h:919-1070
 //   splat_kernel, splat_resolve_kernel    ConnectionsSink<true>  src/renderers/bpt_impl.h:141-155
+//   lens_table_kernel, lens_chain_kernel, lens_chain_resolve_kernel    the lens techniques (s, 1) of `-mmlt`: connect_to_camera per table cell / per chain
 //
 // MI355X design:
 //  * the light-vertex store is SoA indexed `path + depth * n_paths` (the reference's kPathOrdering), so a bounce of light
@@ -22,6 +23,8 @@
 //    samples are templates on one bool; `-bpt` launches the `false` instantiation, whose code does not know the other exists.
 //  * the multiplexed Metropolis renderer (`-mmlt`) adds two more views, read by the `true` instantiation alone: TechTable (the presampling pass keeps every sample in
 //    the cell of its (s, t) technique) and ChainTech (a chain evaluates one technique: its sub-paths stop at vertex s - 1 and t, one connection or the emission).
+//    With light tracing on (the lens techniques (s, 1), opt-in) the table also takes the light-tracing stage's samples (connect_camera_kernel<true>, lens_table_kernel)
+//    and a chain on (s, 1) starts no eye sub-path: lens_chain_kernel connects its vertex s - 1 to the lens, one thread per chain.
 #include "fpt_bpt_device.h"
 
 namespace fpt {
@@ -445,6 +448,14 @@ __global__ void __launch_bounds__(BPT_BLOCK) eye_primary_kernel(const BptParams 
 	const uint32_t k = i / P.n_local, li = i - k * P.n_local;
 	const uint32_t idx = P.pixels ? P.pixels[li] : li;
 	const uint32_t px = idx % P.res_x, py = idx / P.res_x;
+	// technique-fixed, t = 1 (a lens connection): the eye sub-path is not started.  Its queue slot gets a null ray, as the light side's for s = 0
+	if (MLT && P.fixed.st && (P.fixed.st[idx] >> 8) == 1u)
+	{
+		write_ray(P.out.rays, i, splat3(0.0f), 0.0f, splat3(0.0f), -1.0f);
+		P.out.weights[i] = make_float4(0, 0, 0, 0); P.out.pixels[i] = k * P.n_paths + idx; P.out.chan[i] = 0; P.out.path_weights[i] = make_float4(0, 0, 0, 0);
+		if (i == 0) *P.out.size = P.n_local * P.n_passes;
+		return;
+	}
 	// chain mode: eye path idx is the chain, its screen position the chain's coordinates 3 and 4 (eye vertex 1); (px, py) is not read
 	const float ux = eye_coord<MLT>(P, k, idx, px, py, 1, 0), uy = eye_coord<MLT>(P, k, idx, px, py, 1, 1);
 	const float dx = ux * 2.f - 1.f, dy = uy * 2.f - 1.f;
@@ -736,8 +747,11 @@ __global__ void __launch_bounds__(BPT_BLOCK) unpack_light_vertices_kernel(const 
 
 // stage B of connect_camera_kernel for one stored vertex of depth >= 1 (connect_to_camera, src/bpt_kernels.h:919-1032): the sample's weight, the pixel it
 // lands on (without the pass offset) and the origin of its shadow ray; false when nothing is to be traced.  `terms`: as in connect
+// `c_out` (the lens techniques of `-mmlt`) receives c, the weight before the multiplication by light_weight; `n_light`, when not 0, is the number of light paths
+// light_weight divides by instead of P.n_paths (a chain step runs n_chains paths and must decide as the presampling pass over n_pixels did)
 struct LensTerms { f3 out; float d2, cos_theta, G, p_s, f_s, ox, oy; f3 f_L; float p_L, pGp, next_pGp, mis_w; };
-__device__ __forceinline__ bool connect_lens(const BptParams& P, const StoredVertex& lv, uint32_t depth, f3& w, float& light_weight, uint32_t& pixel, f3& origin, LensTerms* terms)
+__device__ __forceinline__ bool connect_lens(const BptParams& P, const StoredVertex& lv, uint32_t depth, f3& w, float& light_weight, uint32_t& pixel, f3& origin, LensTerms* terms,
+                                             f3* c_out = nullptr, uint32_t n_light = 0u)
 {
 	float d2;
 	const f3 out = lens_direction(P, lv.position, d2);
@@ -755,8 +769,9 @@ __device__ __forceinline__ bool connect_lens(const BptParams& P, const StoredVer
 		(depth > 1 && !P.opt.indirect_lighting_nee && !P.opt.indirect_lighting_bsdf) ? 1.0f :
 		mis3(pGp / P.light_tracing, next_pGp, lv.pGp_sum);
 	const f3 c = lv.alpha * f_L * f_s * G * mis_w;
-	light_weight = 1.0f / float(P.n_paths);
+	light_weight = 1.0f / float(n_light ? n_light : P.n_paths);
 	w = mk3(c.x * light_weight, c.y * light_weight, c.z * light_weight);
+	if (c_out) *c_out = c;
 	if (terms)
 	{
 		terms->out = out; terms->d2 = d2; terms->cos_theta = cos_theta; terms->G = G; terms->p_s = p_s; terms->f_s = f_s; terms->ox = ox; terms->oy = oy;
@@ -778,6 +793,9 @@ __device__ __forceinline__ bool connect_lens(const BptParams& P, const StoredVer
 // order-independent 2^-32 fixed-point integers, so the queue order is free.  (A thread per path doing everything ran at 23 % lane utilisation
 // (PMC): path lengths differ and most vertices lie outside the frustum; a thread per vertex needs 8x the workgroups, and their queue atomics
 // -- ~90 per microsecond on one counter -- then cost more than the divergence did.)
+// MLT with a TechTable set (the presampling pass of `-mmlt` with the lens techniques): the queue entry carries what lens_table_kernel needs to name the cell -- the
+// weight is c (before light_weight), its fourth component the pixel's bits, and `pixels` holds depth << 24 | the LIGHT PATH
+template <bool MLT>
 __global__ void __launch_bounds__(BPT_BLOCK) connect_camera_kernel(const BptParams P)
 {
 	__shared__ RangeScratch sc;
@@ -816,8 +834,18 @@ __global__ void __launch_bounds__(BPT_BLOCK) connect_camera_kernel(const BptPara
 			StoredVertex lv;
 			load_stored(P, li, depth, lv);
 			uint32_t px = 0;
-			want = connect_lens(P, lv, depth, w, light_weight, px, origin, nullptr);
-			out_pixel = pass_k * P.n_paths + px;
+			if (MLT && P.tech.cell)
+			{
+				f3 c;
+				want = connect_lens(P, lv, depth, w, light_weight, px, origin, nullptr, &c);
+				w = c; light_weight = as_f32(px);
+				out_pixel = (depth << 24) | (li - depth * P.n_store);          // one pass: the store slot is light path + depth * n_store, the path below 2^24 (fpt_bpt_init)
+			}
+			else
+			{
+				want = connect_lens(P, lv, depth, w, light_weight, px, origin, nullptr);
+				out_pixel = pass_k * P.n_paths + px;
+			}
 		}
 		const uint32_t slot = block_range_alloc(P.shadow.size, want ? 1u : 0u, sc);
 		if (want)
@@ -828,6 +856,64 @@ __global__ void __launch_bounds__(BPT_BLOCK) connect_camera_kernel(const BptPara
 		}
 		__syncthreads();          // the scratch of block_range_alloc is reused by the next round
 	}
+}
+
+// ---- the lens techniques (s, 1) of the multiplexed Metropolis renderer ------------------------------------------------------------------------------------------
+// the presampling pass: one thread per entry of the queue connect_camera_kernel<true> filled; an unoccluded sample of light path `id` at depth d is technique
+// (d + 1, 1): (c, 1) into its cell, the pixel into the pixel plane.  A light path has one vertex per depth at most: plain stores, no races
+__global__ void __launch_bounds__(BPT_BLOCK) lens_table_kernel(const BptParams P)
+{
+	const uint32_t e = threadIdx.x + blockIdx.x * blockDim.x;
+	if (e >= *P.shadow.size) return;
+	if (!(P.shadow.hits[e].x < 0.0f)) return;
+	const float4 w = P.shadow.weights[e];
+	const uint32_t word = P.shadow.pixels[e], depth = word >> 24, id = word & 0xFFFFFFu, L = P.opt.max_path_length;
+	if (!mlt_tech_valid(depth + 1u, 1u, L, true) || id >= P.n_paths) return;          // (valid by construction; an index outside the table is dropped, not written)
+	P.tech.cell[size_t(mlt_tech_index(depth + 1u, 1u, L, true)) * P.n_paths + id] = make_float4(w.x, w.y, w.z, 1.0f);
+	P.tech.pixel[size_t(depth - 1u) * P.n_paths + id] = as_u32(w.w);
+}
+// a chain step: one thread per chain.  A chain on (s, 1) connects vertex s - 1 of its light sub-path to the lens -- one vertex per chain, so none of the divergence
+// connect_camera_kernel's LDS list is there for -- and queues the shadow ray, compacted (one queue atomic per workgroup); the entry names the chain
+__global__ void __launch_bounds__(BPT_BLOCK) lens_chain_kernel(const BptParams P)
+{
+	__shared__ RangeScratch sc;
+	const uint32_t chain = threadIdx.x + blockIdx.x * blockDim.x;
+	bool want = false;
+	f3 origin = splat3(0.0f), c = splat3(0.0f);
+	if (chain < P.n_local)
+	{
+		uint32_t fs, ft, px = 0xFFFFFFFFu;
+		fixed_tech(P, chain, fs, ft);
+		if (ft == 1u && fs >= 2u && fs <= P.opt.max_path_length && P.store.counts[chain] >= fs)
+		{
+			StoredVertex lv;
+			load_stored(P, chain + (fs - 1u) * P.n_store, fs - 1u, lv);
+			f3 w; float light_weight; uint32_t pixel = 0;
+			want = connect_lens(P, lv, fs - 1u, w, light_weight, pixel, origin, nullptr, &c, P.res_x * P.res_y);
+			if (want) px = pixel;
+		}
+		if (P.fixed.new_pixel) P.fixed.new_pixel[chain] = px;
+	}
+	const uint32_t slot = block_range_alloc(P.shadow.size, want ? 1u : 0u, sc);
+	if (want)
+	{
+		write_ray(P.shadow.rays, slot, origin, 0.0f, P.eye - origin, 0.9999f);
+		P.shadow.weights[slot] = make_float4(c.x, c.y, c.z, 1.0f);
+		P.shadow.pixels[slot] = chain;
+		count_rays(P, 1u);
+	}
+}
+// its resolve: c * visibility into the chain's value, in the units of the table's cell (not times light_weight).  A t = 1 chain has no other sample: a plain store
+__global__ void __launch_bounds__(BPT_BLOCK) lens_chain_resolve_kernel(const BptParams P)
+{
+	const uint32_t e = threadIdx.x + blockIdx.x * blockDim.x;
+	if (e >= *P.shadow.size) return;
+	const float4 w = P.shadow.weights[e];
+	const float vis = (P.shadow.hits[e].x < 0.0f) ? 1.0f : 0.0f;
+	const uint32_t chain = P.shadow.pixels[e];
+	if (chain >= P.n_local) return;
+	P.value.value[chain] = make_float4(w.x * vis, w.y * vis, w.z * vis, w.w * vis);
+	if (vis == 0.0f && P.fixed.new_pixel) P.fixed.new_pixel[chain] = 0xFFFFFFFFu;          // an occluded sample lands nowhere, as in the table's pixel plane
 }
 
 __device__ __forceinline__ void splat_fixed3(float4 w, float fw, long long q[3]) { q[0] = splat_fixed(w.x * fw); q[1] = splat_fixed(w.y * fw); q[2] = splat_fixed(w.z * fw); }
@@ -1058,8 +1144,10 @@ void launch_bpt_build_flat_list(const BptParams& p, hipStream_t s)
 	hipLaunchKernelGGL(flat_scan_kernel, dim3(1), dim3(BPT_BLOCK), 0, s, p.flat_block_sums, n_blocks, p.flat_meta + 2 * p.n_passes, p.opt.max_path_length == 1);
 	hipLaunchKernelGGL(flat_fill_kernel, dim3(n_blocks), dim3(BPT_BLOCK), 0, s, p);
 }
-void launch_bpt_connect_camera(const BptParams& p, hipStream_t s)
-{ hipLaunchKernelGGL(connect_camera_kernel, grid_for(p.n_local * p.n_passes), dim3(BPT_BLOCK), 0, s, p); }
+void launch_bpt_connect_camera(const BptParams& p, hipStream_t s) { FPT_BPT_LAUNCH(connect_camera_kernel, p.n_local * p.n_passes); }
+void launch_bpt_lens_table(const BptParams& p, uint32_t max_entries, hipStream_t s) { hipLaunchKernelGGL(lens_table_kernel, grid_for(max_entries), dim3(BPT_BLOCK), 0, s, p); }
+void launch_bpt_lens_chain(const BptParams& p, hipStream_t s) { hipLaunchKernelGGL(lens_chain_kernel, grid_for(p.n_local), dim3(BPT_BLOCK), 0, s, p); }
+void launch_bpt_lens_chain_resolve(const BptParams& p, hipStream_t s) { hipLaunchKernelGGL(lens_chain_resolve_kernel, grid_for(p.n_local), dim3(BPT_BLOCK), 0, s, p); }
 void launch_bpt_splat(const BptParams& p, uint32_t max_entries, hipStream_t s) { hipLaunchKernelGGL(splat_kernel, grid_for(max_entries), dim3(BPT_BLOCK), 0, s, p); }
 void launch_bpt_splat_resolve(const BptParams& p, hipStream_t s) { hipLaunchKernelGGL(splat_resolve_kernel, grid_for(p.n_paths * p.n_passes), dim3(BPT_BLOCK), 0, s, p); }
 void launch_bpt_merge_exact(const FrameBufferDev& fb, float4* albedo_d, float4* albedo_s, const BptLog& log, long long* splat, const uint32_t* pixels, uint32_t n_local,

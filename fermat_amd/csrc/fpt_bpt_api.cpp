@@ -287,12 +287,24 @@ struct BptRun
 			cur ^= 1;
 		}
 		// ---- light_tracing (src/bpt_control.h:572-600): this rank's own light paths ----
-		if (b.light_tracing)
+		if (b.light_tracing && P.fixed.st)
+		{
+			// a chain step of `-mmlt` with the lens techniques: the chains on (s, 1) connect their vertex s - 1 to the lens; a launch of its own for the shadow rays (they
+			// could ride in the eye sub-paths' first traversal launch, which for these chains holds null rays: one launch less per step, not measured -- DESIGN 6h)
+			P.shadow.size = b.cnt.queue(L, SHADOW);
+			launch_bpt_lens_chain(P, s);
+			trace(P.shadow.rays, P.shadow.hits, P.shadow.size, true);
+			launch_bpt_lens_chain_resolve(P, s);
+		}
+		else if (b.light_tracing)
 		{
 			P.shadow.size = b.cnt.queue(L, SHADOW);
 			timed_launch(ctx, 3, s, [&] { launch_bpt_connect_camera(P, s); });
 			trace(P.shadow.rays, P.shadow.hits, P.shadow.size, true);
-			launch_bpt_splat(P, uint32_t(std::min<size_t>(size_t(n_launch) * (L > 1 ? L - 1 : 1), 0xFFFFFFFFu)), s);
+			const uint32_t max_splats = uint32_t(std::min<size_t>(size_t(n_launch) * (L > 1 ? L - 1 : 1), 0xFFFFFFFFu));
+			// a technique table keeps the samples apart, in the lens block's cells; the splat sums stay untouched
+			if (P.tech.cell) launch_bpt_lens_table(P, max_splats, s);
+			else launch_bpt_splat(P, max_splats, s);
 			if (prof) st.shadow_light_tracing = read_u32(ctx, P.shadow.size);
 		}
 		if (prof)
@@ -339,6 +351,7 @@ void bpt_sample_paths(fpt_context* ctx, uint32_t instance, const fpt_rendering_c
 	require(b.ready && b.max_batch == 1 && !b.d_pixels && !b.light_pending && b.pending_n == 0, "fpt_pssmlt: the bidirectional state is not the one fpt_pssmlt_init made");
 	require(((value != nullptr) != (tech != nullptr && tech->cell != nullptr)) && (n ? n : b.n_paths) <= std::max(b.n_paths, b.min_paths), "fpt_pssmlt: more paths than the storage holds");
 	require(!fixed || (chain && value && !b.opt.single_connection), "fpt_mmlt: a technique-fixed evaluation needs chain coordinates, a value sink and single_connection = 0");
+	require(!(tech && tech->cell && b.light_tracing) || tech->pixel, "fpt_mmlt: with light tracing on the technique table needs its pixel plane");
 	BptRun run(ctx, instance, 1, view);
 	if (tiled) *tiled = run.P;
 	run.for_value_sink(n ? n : b.n_paths, chain, value, tech, fixed);
@@ -347,6 +360,25 @@ void bpt_sample_paths(fpt_context* ctx, uint32_t instance, const fpt_rendering_c
 }
 }
 extern "C" {
+
+/* probe: the light-tracing stage's queue as the last single-pass render call left it -- its entries and how many of them splat_kernel added (a positive weight, an
+ * unoccluded shadow ray).  Counted on the host */
+int fpt_debug_bpt_splat_entries(fpt_context* ctx, uint32_t* h_entries, uint32_t* h_visible)
+{
+	return guarded(ctx, [&] {
+		flush_deferred(ctx);
+		fpt_context::BptState& b = ctx->bpt;
+		require(b.ready && b.max_batch == 1 && h_entries && h_visible, "fpt_debug_bpt_splat_entries: fpt_bpt_init first, one pass in flight, no null argument");
+		*h_entries = *h_visible = 0u;
+		if (!b.light_tracing || !b.counters.ptr) return;
+		const uint32_t n = std::min<uint32_t>(read_u32(ctx, PassCounters{ b.counters.ptr }.queue(b.opt.max_path_length, BptRun::SHADOW)), uint32_t(std::min<size_t>(b.s_hits.count, b.s_weights.count)));
+		std::vector<float4> hits(n), weights(n);
+		b.s_hits.download(hits.data(), n, ctx->stream); b.s_weights.download(weights.data(), n, ctx->stream);
+		uint32_t visible = 0;
+		for (uint32_t i = 0; i < n; ++i) visible += ((weights[i].x > 0.0f || weights[i].y > 0.0f || weights[i].z > 0.0f) && hits[i].x < 0.0f) ? 1u : 0u;
+		*h_entries = n; *h_visible = visible;
+	});
+}
 
 int fpt_bpt_render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view)
 {

@@ -405,6 +405,9 @@ struct fpt_context
 		fpt::DeviceArray<unsigned long long> mcounts, ends;                // swaps proposed, swaps accepted, rays queued by the chain steps; the CDF at the techniques' block ends
 		std::vector<float> st_norms; std::vector<uint32_t> st_chains;      // (L+2)^2 each, s + t * (L+2)
 		fpt_mmlt_stats mstats{};
+		// its lens techniques (fpt_mmlt_options::lens_techniques): the table's pixel plane ((L - 1) x n_pixels), the pixel of every chain's proposal and current state
+		bool lens = false;
+		fpt::DeviceArray<uint32_t> table_pixel, new_pixel, path_pixel;
 	} mlt;
 	bool profiling = false;
 	int capture_bounce = -1;

@@ -19,6 +19,10 @@ struct MltChains
 	// the multiplexed renderer (`-mmlt`), all unset for `-pssmlt`: the chains' techniques (s | t << 8); on a swap step (swap != 0) the proposal was evaluated with
 	// st_new, which replaces st together with the value on acceptance; mcounts[0] swaps proposed, [1] swaps accepted
 	uint32_t* st; const uint32_t* st_new; unsigned long long* mcounts; uint32_t swap;
+	// the lens techniques of `-mmlt` (both NULL otherwise: the kernel is then the one above): the pixel of the proposed and of the current state; 0xFFFFFFFF = "quantize
+	// eye coordinates 3 and 4", any other value is the pixel itself (a t = 1 state: where its lens connection landed).  path_pixel is committed with the value on
+	// acceptance and kept on rejection.  A proposal that carries a pixel arrives as c (the table's cell) and counts as c * light_weight, light_weight = 1 / (res_x res_y)
+	const uint32_t* new_pixel; uint32_t* path_pixel;
 };
 
 // Largest single value of the seed CDF: a path value above 2^31 counts 2^31 (its integer is 2^63, the largest a uint64 sum can take once)
@@ -28,7 +32,9 @@ static constexpr float kMltSeedClamp = 2147483648.0f;
 size_t mlt_seed_cdf_scratch_bytes(uint32_t n);
 // q[i] = floor(min(max_comp(value[i].xyz), 2^31) * 2^32), 0 for a negative or non-finite value; cdf = the inclusive scan of q (rocPRIM).  Integers: the CDF does not
 // depend on the order of the scan's additions, as the splat sums do not (the reference scans floats, pssmlt.cu:513-532)
-void launch_mlt_seed_cdf(const float4* value, uint32_t n, unsigned long long* q, unsigned long long* cdf, void* scratch, size_t scratch_bytes, hipStream_t s);
+// scaled_from / scale (the lens block of the multiplexed renderer's table): value[i].xyz counts times `scale` for i >= scaled_from
+void launch_mlt_seed_cdf(const float4* value, uint32_t n, unsigned long long* q, unsigned long long* cdf, void* scratch, size_t scratch_bytes, hipStream_t s,
+                         uint32_t scaled_from = 0xFFFFFFFFu, float scale = 1.0f);
 // sample_seeds (pssmlt.cu:327-338) on the integer CDF: r = (i + randfloat(i, 0)) / n_seeds in float, target = uint64(double(r) * double(total)), the seed = the first
 // entry whose CDF exceeds the target, at most the last non-empty entry.  total == 0: nothing is written
 // common_offset >= 0 (the multiplexed renderer): the targets are mlt_seed_target's (fpt_mlt_host.h) -- exact integers, one offset of common_offset * 2^-24 for all strata
@@ -43,11 +49,13 @@ void launch_mlt_resolve(float4* composited, long long* splat, uint32_t n_pixels,
 // ---- the multiplexed renderer (`-mmlt`; src/renderers/cmlt.cu without charted swaps) ----
 // the chains' start: seed cell e = seeds[c] of the technique table gives chain c the technique e / n_paths (st[c] = s | t << 8) and the eye path e % n_paths
 // (path_seeds[c], what launch_mlt_recover_coordinates reads); tech_chains[technique] (zeroed by the caller) counts the chains per technique
-void launch_mmlt_start_chains(const uint32_t* seeds, uint32_t n_chains, uint32_t n_paths, uint32_t L, uint32_t* st, uint32_t* path_seeds, uint32_t* tech_chains, hipStream_t s);
+void launch_mmlt_start_chains(const uint32_t* seeds, uint32_t n_chains, uint32_t n_paths, uint32_t L, uint32_t* st, uint32_t* path_seeds, uint32_t* tech_chains, hipStream_t s,
+                              bool lens = false);          // lens: the table has the lens block; a seed there starts (s, 1) on LIGHT path e % n_paths
 // ends[k] = cdf[(k + 1) * n_paths - 1]: the seed CDF at the end of every technique's block (st_norms are their differences)
 void launch_mmlt_block_ends(const unsigned long long* cdf, uint32_t n_tech, uint32_t n_paths, unsigned long long* ends, hipStream_t s);
 // mmlt_swap_kernel (cmlt.cu:496-544): st_new[c] = mlt_swap_proposal(st[c], mutation number of (instance, step, c, mlt_swap_dim(L)))
-void launch_mmlt_swap(const uint32_t* st, uint32_t* st_new, uint32_t n_chains, uint32_t L, uint32_t instance, uint32_t step, hipStream_t s);
+// lens: mlt_swap_proposal_lens, the ring with the t = 1 stop
+void launch_mmlt_swap(const uint32_t* st, uint32_t* st_new, uint32_t n_chains, uint32_t L, uint32_t instance, uint32_t step, hipStream_t s, bool lens = false);
 // probes (fpt_debug_mlt ops 3 and 4)
 void launch_debug_mmlt_tech(uint32_t n, uint32_t L, const uint32_t* st, uint32_t* index, uint32_t* back, hipStream_t s);
 void launch_debug_mmlt_swap(uint32_t n, uint32_t L, uint32_t instance, uint32_t step, const uint32_t* st, const uint32_t* chain, uint32_t* st_new, float* m_out, hipStream_t s);

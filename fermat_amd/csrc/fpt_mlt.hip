@@ -13,6 +13,8 @@
 //   mmlt_start_chains_kernel            a seed cell of the technique table -> the chain's technique and eye path
 //   mmlt_block_ends_kernel              the seed CDF at the end of every technique's block (st_norms)
 //   mmlt_swap_kernel                    mmlt_swap_kernel                     src/renderers/cmlt.cu:496-544
+// With its lens techniques (s, 1) (fpt_mmlt_options::lens_techniques) the table has a lens block after the others whose cells count times light_weight
+// in the seed CDF, the walk has the t = 1 stop, and accept_reject_kernel keeps a pixel per chain: a t = 1 state lands where its lens connection did.
 #include "fpt_mlt.h"
 #include "fpt_bpt_device.h"
 #include <cstring>
@@ -25,11 +27,13 @@ namespace {
 constexpr int MLT_BLOCK = 256;
 inline dim3 grid_for(uint32_t n) { return dim3((n + MLT_BLOCK - 1) / MLT_BLOCK); }
 
-__global__ void __launch_bounds__(MLT_BLOCK) seed_values_kernel(const float4* __restrict__ value, uint32_t n, unsigned long long* __restrict__ q)
+// the values from `scaled_from` on (the lens block of the multiplexed renderer's table; n for none) count times `scale` (light_weight), component by component
+__global__ void __launch_bounds__(MLT_BLOCK) seed_values_kernel(const float4* __restrict__ value, uint32_t n, unsigned long long* __restrict__ q, uint32_t scaled_from, float scale)
 {
 	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
 	if (i >= n) return;
-	const float4 v = value[i];
+	float4 v = value[i];
+	if (i >= scaled_from) { v.x *= scale; v.y *= scale; v.z *= scale; }
 	const float m = max_comp(mk3(v.x, v.y, v.z));
 	unsigned long long r = 0;
 	if (is_finite(m) && m > 0.0f) r = (unsigned long long)(double(sel_min(m, kMltSeedClamp)) * 4294967296.0);      // exact: a float times 2^32, at most 2^63
@@ -84,11 +88,26 @@ __global__ void __launch_bounds__(MLT_BLOCK) accept_reject_kernel(const MltChain
 		auto new_light = [&](uint32_t d) { const float u = C.light_u[size_t(d) * n + chain]; return light_mut ? mlt_perturbed_u(u, mlt_mutation_number(C.instance, C.step, chain, d), light_mut, C.radius) : u; };
 		auto new_eye = [&](uint32_t d) { const float u = C.eye_u[size_t(d) * n + chain]; return eye_mut ? mlt_perturbed_u(u, mlt_mutation_number(C.instance, C.step, chain, dims + d), eye_mut, C.radius) : u; };
 		// perform the MH acceptance-rejection test
-		const float4 w = C.new_value[chain];
+		float4 w = C.new_value[chain];
+		// the lens techniques: a t = 1 proposal arrives as c, the light-tracing sample BEFORE the multiplication by light_weight = 1 / n_pixels (the table's cell).  What it
+		// adds to a pixel of the frame is c * light_weight, the BPT's splat: that is the state's value from here on -- in the test, in the deposit and in path_value
+		uint32_t new_lens = 0xFFFFFFFFu;
+		if (C.path_pixel)
+		{
+			new_lens = C.new_pixel[chain];
+			if (new_lens != 0xFFFFFFFFu) { const float light_weight = 1.0f / float(C.res_x * C.res_y); w.x *= light_weight; w.y *= light_weight; w.z *= light_weight; }
+		}
 		const float new_pdf = max_comp(mk3(w.x, w.y, w.z));
 		const float old_pdf = C.path_pdf[chain];
-		const uint32_t old_pixel = quantize(C.eye_u[size_t(3) * n + chain], C.res_x) + quantize(C.eye_u[size_t(4) * n + chain], C.res_y) * C.res_x;
-		const uint32_t new_pixel = quantize(new_eye(3), C.res_x) + quantize(new_eye(4), C.res_y) * C.res_x;
+		uint32_t old_pixel = quantize(C.eye_u[size_t(3) * n + chain], C.res_x) + quantize(C.eye_u[size_t(4) * n + chain], C.res_y) * C.res_x;
+		uint32_t new_pixel = quantize(new_eye(3), C.res_x) + quantize(new_eye(4), C.res_y) * C.res_x;
+		// and a t = 1 state lands where its lens connection did, not where eye coordinates 3 and 4 point
+		if (C.path_pixel)
+		{
+			const uint32_t old_lens = C.path_pixel[chain];
+			if (old_lens != 0xFFFFFFFFu) old_pixel = old_lens < C.res_x * C.res_y ? old_lens : 0u;
+			if (new_lens != 0xFFFFFFFFu) new_pixel = new_lens < C.res_x * C.res_y ? new_lens : 0u;
+		}
 		float ar = 1.0f;
 		if (old_pdf) { const float ratio = new_pdf / old_pdf; ar = ratio < 1.0f ? ratio : 1.0f; }          // fminf(1, ratio): 1 for a NaN
 		const float inv_count = float(C.instance + 1);
@@ -110,6 +129,7 @@ __global__ void __launch_bounds__(MLT_BLOCK) accept_reject_kernel(const MltChain
 			C.path_pdf[chain] = new_pdf;
 			// write out the successful st
 			if (C.st && C.swap) C.st[chain] = C.st_new[chain];
+			if (C.path_pixel) C.path_pixel[chain] = new_lens;
 			// copy the successful mutation coordinates
 			if (light_mut) for (uint32_t d = 0; d < dims; ++d) C.light_u[size_t(d) * n + chain] = new_light(d);
 			if (eye_mut) for (uint32_t d = 0; d < dims; ++d) C.eye_u[size_t(d) * n + chain] = new_eye(d);
@@ -152,14 +172,14 @@ __global__ void __launch_bounds__(MLT_BLOCK) mlt_resolve_kernel(float4* __restri
 }
 
 __global__ void __launch_bounds__(MLT_BLOCK) mmlt_start_chains_kernel(const uint32_t* __restrict__ seeds, uint32_t n_chains, uint32_t n_paths, uint32_t L, uint32_t* __restrict__ st,
-                                                                      uint32_t* __restrict__ path_seeds, uint32_t* __restrict__ tech_chains)
+                                                                      uint32_t* __restrict__ path_seeds, uint32_t* __restrict__ tech_chains, bool lens)
 {
 	const uint32_t c = threadIdx.x + blockIdx.x * blockDim.x;
 	if (c >= n_chains) return;
 	const uint32_t e = seeds[c];
 	uint32_t tech = e / n_paths;
-	if (tech >= mlt_tech_count(L)) tech = mlt_tech_count(L) - 1u;          // (a seed is a cell of the table: never taken)
-	st[c] = mlt_tech_st(tech, L);
+	if (tech >= mlt_tech_count(L, lens)) tech = mlt_tech_count(L, lens) - 1u;          // (a seed is a cell of the table: never taken)
+	st[c] = mlt_tech_st(tech, L, lens);
 	path_seeds[c] = e - (e / n_paths) * n_paths;
 	atomicAdd(tech_chains + tech, 1u);
 }
@@ -170,13 +190,14 @@ __global__ void __launch_bounds__(MLT_BLOCK) mmlt_block_ends_kernel(const unsign
 	if (k < n_tech) ends[k] = cdf[size_t(k + 1u) * n_paths - 1u];
 }
 
-__global__ void __launch_bounds__(MLT_BLOCK) mmlt_swap_kernel(const uint32_t* __restrict__ st, uint32_t* __restrict__ st_new, uint32_t n_chains, uint32_t L, uint32_t instance, uint32_t step)
+__global__ void __launch_bounds__(MLT_BLOCK) mmlt_swap_kernel(const uint32_t* __restrict__ st, uint32_t* __restrict__ st_new, uint32_t n_chains, uint32_t L, uint32_t instance, uint32_t step, bool lens)
 {
 	const uint32_t c = threadIdx.x + blockIdx.x * blockDim.x;
 	if (c >= n_chains) return;
 	const uint32_t w = st[c];
 	// generate a candidate (s_new,t_new) pair with s_new + t_new = s + t: perform a random walk on s
-	st_new[c] = mlt_swap_proposal(w & 0xFFu, w >> 8, mlt_mutation_number(instance, step, c, mlt_swap_dim(L)));
+	const float u = mlt_mutation_number(instance, step, c, mlt_swap_dim(L));
+	st_new[c] = lens ? mlt_swap_proposal_lens(w & 0xFFu, w >> 8, u) : mlt_swap_proposal(w & 0xFFu, w >> 8, u);
 }
 
 __global__ void __launch_bounds__(MLT_BLOCK) debug_mmlt_tech_kernel(uint32_t n, uint32_t L, const uint32_t* __restrict__ st, uint32_t* __restrict__ index, uint32_t* __restrict__ back)
@@ -217,9 +238,9 @@ size_t mlt_seed_cdf_scratch_bytes(uint32_t n)
 	const hipError_t e = rocprim::inclusive_scan(nullptr, bytes, static_cast<const unsigned long long*>(nullptr), static_cast<unsigned long long*>(nullptr), size_t(n), rocprim::plus<unsigned long long>());
 	return e == hipSuccess ? (bytes ? bytes : 1) : 0;
 }
-void launch_mlt_seed_cdf(const float4* value, uint32_t n, unsigned long long* q, unsigned long long* cdf, void* scratch, size_t scratch_bytes, hipStream_t s)
+void launch_mlt_seed_cdf(const float4* value, uint32_t n, unsigned long long* q, unsigned long long* cdf, void* scratch, size_t scratch_bytes, hipStream_t s, uint32_t scaled_from, float scale)
 {
-	hipLaunchKernelGGL(seed_values_kernel, grid_for(n), dim3(MLT_BLOCK), 0, s, value, n, q);
+	hipLaunchKernelGGL(seed_values_kernel, grid_for(n), dim3(MLT_BLOCK), 0, s, value, n, q, scaled_from < n ? scaled_from : n, scale);
 	(void)rocprim::inclusive_scan(scratch, scratch_bytes, static_cast<const unsigned long long*>(q), cdf, size_t(n), rocprim::plus<unsigned long long>(), s);
 }
 void launch_mlt_sample_seeds(const unsigned long long* cdf, uint32_t n, uint32_t n_seeds, uint32_t* seeds, hipStream_t s, int common_offset)
@@ -229,12 +250,12 @@ void launch_mlt_recover_coordinates(const BptParams& tiled, const uint32_t* seed
 void launch_mlt_accept_reject(const MltChains& c, hipStream_t s) { hipLaunchKernelGGL(accept_reject_kernel, grid_for(c.n_chains), dim3(MLT_BLOCK), 0, s, c); }
 void launch_mlt_resolve(float4* composited, long long* splat, uint32_t n_pixels, hipStream_t s)
 { hipLaunchKernelGGL(mlt_resolve_kernel, grid_for(n_pixels), dim3(MLT_BLOCK), 0, s, composited, splat, n_pixels); }
-void launch_mmlt_start_chains(const uint32_t* seeds, uint32_t n_chains, uint32_t n_paths, uint32_t L, uint32_t* st, uint32_t* path_seeds, uint32_t* tech_chains, hipStream_t s)
-{ hipLaunchKernelGGL(mmlt_start_chains_kernel, grid_for(n_chains), dim3(MLT_BLOCK), 0, s, seeds, n_chains, n_paths, L, st, path_seeds, tech_chains); }
+void launch_mmlt_start_chains(const uint32_t* seeds, uint32_t n_chains, uint32_t n_paths, uint32_t L, uint32_t* st, uint32_t* path_seeds, uint32_t* tech_chains, hipStream_t s, bool lens)
+{ hipLaunchKernelGGL(mmlt_start_chains_kernel, grid_for(n_chains), dim3(MLT_BLOCK), 0, s, seeds, n_chains, n_paths, L, st, path_seeds, tech_chains, lens); }
 void launch_mmlt_block_ends(const unsigned long long* cdf, uint32_t n_tech, uint32_t n_paths, unsigned long long* ends, hipStream_t s)
 { hipLaunchKernelGGL(mmlt_block_ends_kernel, grid_for(n_tech), dim3(MLT_BLOCK), 0, s, cdf, n_tech, n_paths, ends); }
-void launch_mmlt_swap(const uint32_t* st, uint32_t* st_new, uint32_t n_chains, uint32_t L, uint32_t instance, uint32_t step, hipStream_t s)
-{ hipLaunchKernelGGL(mmlt_swap_kernel, grid_for(n_chains), dim3(MLT_BLOCK), 0, s, st, st_new, n_chains, L, instance, step); }
+void launch_mmlt_swap(const uint32_t* st, uint32_t* st_new, uint32_t n_chains, uint32_t L, uint32_t instance, uint32_t step, hipStream_t s, bool lens)
+{ hipLaunchKernelGGL(mmlt_swap_kernel, grid_for(n_chains), dim3(MLT_BLOCK), 0, s, st, st_new, n_chains, L, instance, step, lens); }
 void launch_debug_mmlt_tech(uint32_t n, uint32_t L, const uint32_t* st, uint32_t* index, uint32_t* back, hipStream_t s)
 { hipLaunchKernelGGL(debug_mmlt_tech_kernel, grid_for(n), dim3(MLT_BLOCK), 0, s, n, L, st, index, back); }
 void launch_debug_mmlt_swap(uint32_t n, uint32_t L, uint32_t instance, uint32_t step, const uint32_t* st, const uint32_t* chain, uint32_t* st_new, float* m_out, hipStream_t s)

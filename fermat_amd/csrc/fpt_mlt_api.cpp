@@ -8,6 +8,7 @@
 // And of the multiplexed renderer (`-mmlt`, fpt_mmlt_*: the reference's `-cmlt -charted-swaps 0`, src/renderers/cmlt.cu): the same wavefront, with the presampling pass
 // sinking into a technique table (TechTable) and every chain step evaluating the chain's one (s, t) technique (ChainTech).  Read-backs per call: the CDF at the
 // techniques' block ends (st_norms and the total), and at the end the counters and the chains seeded per technique.  Every call reseeds; charted swaps are not built.
+// With lens_techniques = 1 the table has the lens block (s, 1), s in [2, L], after the others and a pixel plane beside it; the chains keep the pixel of their state.
 #include "fpt_host.h"
 #include "fpt_mlt.h"
 #include "fpt_mlt_host.h"
@@ -104,11 +105,15 @@ void mmlt_render_impl(fpt_context* ctx, uint32_t instance, const fpt_rendering_c
 	launch_rescale(fb, nullptr, n_pixels, float(instance) / float(instance + 1), s);
 	// the BPT presampling pass: the tiled coordinates, every sample into the cell of its technique
 	zero(m.table, n_cells, s);
+	const bool lens = m.lens;
+	const size_t n_lens_cells = lens ? size_t(L - 1u) * n_pixels : 0;
+	if (n_lens_cells) FPT_HIP_CHECK(hipMemsetAsync(m.table_pixel.ptr, 0xFF, n_lens_cells * sizeof(uint32_t), s));
 	BptParams tiled;
-	const TechTable table = { m.table.ptr };
+	const TechTable table = { m.table.ptr, lens ? m.table_pixel.ptr : nullptr };
 	bpt_sample_paths(ctx, instance, view, 0u, nullptr, nullptr, &tiled, &table, nullptr);
 	// one CDF over all cells: the seeds are single connections, drawn in proportion to their value whatever their technique
-	launch_mlt_seed_cdf(m.table.ptr, n_cells, m.q.ptr, m.cdf.ptr, m.scan_scratch.ptr, m.scan_scratch.count, s);
+	// (a lens cell holds c, the sample before the multiplication by light_weight = 1 / n_pixels; what it adds to the frame, and so what it counts here, is c * light_weight)
+	launch_mlt_seed_cdf(m.table.ptr, n_cells, m.q.ptr, m.cdf.ptr, m.scan_scratch.ptr, m.scan_scratch.count, s, lens ? mlt_tech_count(L) * n_pixels : n_cells, 1.0f / float(n_pixels));
 	launch_mlt_sample_seeds(m.cdf.ptr, n_cells, n_chains, m.seeds.ptr, s, int(mlt_seed_offset(instance)));
 	launch_mmlt_block_ends(m.cdf.ptr, n_tech, n_pixels, m.ends.ptr, s);
 	FPT_HIP_CHECK(hipGetLastError());
@@ -125,12 +130,12 @@ void mmlt_render_impl(fpt_context* ctx, uint32_t instance, const fpt_rendering_c
 	m.st_norms.assign(size_t(W) * W, 0.0f); m.st_chains.assign(size_t(W) * W, 0u);
 	for (uint32_t k = 0; k < n_tech; ++k)
 	{
-		const uint32_t w = mlt_tech_st(k, L);
+		const uint32_t w = mlt_tech_st(k, L, lens);
 		m.st_norms[(w & 0xFFu) + (w >> 8) * W] = mlt_image_brightness(ends[k] - (k ? ends[k - 1] : 0ull), n_pixels);
 	}
 	if (total == 0) return;          // a black frame: no sample to start a chain from, the frame is only rescaled
 	zero(m.tech_chains, n_tech, s);
-	launch_mmlt_start_chains(m.seeds.ptr, n_chains, n_pixels, L, m.st.ptr, m.path_seeds.ptr, m.tech_chains.ptr, s);
+	launch_mmlt_start_chains(m.seeds.ptr, n_chains, n_pixels, L, m.st.ptr, m.path_seeds.ptr, m.tech_chains.ptr, s, lens);
 	// recover the primary coordinates of the selected seed paths
 	launch_mlt_recover_coordinates(tiled, m.path_seeds.ptr, n_chains, m.light_u.ptr, m.eye_u.ptr, s);
 	// initialize the initial path pdfs and the rejection counters to zero
@@ -142,17 +147,23 @@ void mmlt_render_impl(fpt_context* ctx, uint32_t instance, const fpt_rendering_c
 	C.light_perturbations = m.opt.light_perturbations; C.eye_perturbations = m.opt.eye_perturbations; C.radius = m.opt.radius; C.pdf_norm = st.pdf_norm;
 	C.res_x = view->res_x; C.res_y = view->res_y;
 	C.st = m.st.ptr; C.st_new = m.st_new.ptr; C.mcounts = m.mcounts.ptr;
+	if (lens)
+	{
+		// no chain has a state yet: its pixel is committed with the first accepted proposal (step 0 for a seed)
+		FPT_HIP_CHECK(hipMemsetAsync(m.path_pixel.ptr, 0xFF, n_chains * sizeof(uint32_t), s));
+		C.new_pixel = m.new_pixel.ptr; C.path_pixel = m.path_pixel.ptr;
+	}
 	// start the chains
 	for (uint32_t l = 0; l < m.chain_length; ++l)
 	{
 		// a swap step keeps the coordinates and proposes another technique of the same path length; any other step is PSSMLT's on the chain's own technique
 		const bool swap = mlt_is_swap_step(m.mmlt_frequency, l);
 		const uint32_t mutation = swap ? 0u : mlt_mutation_type(m.opt.independent_samples, instance, l);
-		if (swap) launch_mmlt_swap(m.st.ptr, m.st_new.ptr, n_chains, L, instance, l, s);
+		if (swap) launch_mmlt_swap(m.st.ptr, m.st_new.ptr, n_chains, L, instance, l, s, lens);
 		// reset the new path values
 		zero(m.new_value, n_chains, s);
 		const ChainCoords chain = chain_view(m, n_chains, l, mutation);
-		const ChainTech fixed = { swap ? m.st_new.ptr : m.st.ptr, m.mcounts.ptr + 2 };
+		const ChainTech fixed = { swap ? m.st_new.ptr : m.st.ptr, m.mcounts.ptr + 2, lens ? m.new_pixel.ptr : nullptr };
 		bpt_sample_paths(ctx, instance, view, n_chains, &chain, m.new_value.ptr, nullptr, nullptr, &fixed);
 		// and perform the usual acceptance-rejection step
 		C.step = l; C.mutation = mutation; C.swap = swap ? 1u : 0u;
@@ -167,7 +178,7 @@ void mmlt_render_impl(fpt_context* ctx, uint32_t instance, const fpt_rendering_c
 	FPT_HIP_CHECK(hipMemcpyAsync(tech_chains.data(), m.tech_chains.ptr, n_tech * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
 	FPT_HIP_CHECK(hipStreamSynchronize(s));
 	st.accepted = counts[0]; st.rejected = counts[1]; st.swaps_proposed = mcounts[0]; st.swaps_accepted = mcounts[1]; st.rays = mcounts[2];
-	for (uint32_t k = 0; k < n_tech; ++k) { const uint32_t w = mlt_tech_st(k, L); m.st_chains[(w & 0xFFu) + (w >> 8) * W] = tech_chains[k]; }
+	for (uint32_t k = 0; k < n_tech; ++k) { const uint32_t w = mlt_tech_st(k, L, lens); m.st_chains[(w & 0xFFu) + (w >> 8) * W] = tech_chains[k]; }
 }
 
 } // namespace
@@ -317,19 +328,28 @@ int fpt_mmlt_init(fpt_context* ctx, const fpt_mmlt_options* opts, const fpt_rend
 		const uint32_t n_pixels = view->res_x * view->res_y;
 		require(n_pixels > 0, "fpt_mmlt_init: empty frame");
 		if (const char* why = mmlt_refusal(*opts, n_pixels, d_pixels != nullptr)) require(false, why);
-		m.opt = opts->mlt; m.mmlt_frequency = opts->mmlt_frequency;
-		// forced as in PSSMLT: no light tracing (no technique with t <= 1), every connection of the path's own light sub-path: one sample per technique
-		m.opt.bpt.light_tracing = 0.0f; m.opt.bpt.single_connection = 0u;
+		m.opt = opts->mlt; m.mmlt_frequency = opts->mmlt_frequency; m.lens = opts->lens_techniques != 0u;
+		// forced as in PSSMLT: every connection of the path's own light sub-path: one sample per technique; and no light tracing (no technique with t <= 1) unless the
+		// lens techniques are on: then light tracing is ON, so that every technique's MIS weight accounts for the lens connection
+		m.opt.bpt.light_tracing = m.lens ? 1.0f : 0.0f; m.opt.bpt.single_connection = 0u;
 		const uint32_t n_chains = m.opt.n_chains, cap = std::max(n_pixels, n_chains), L = m.opt.bpt.max_path_length;
 		bpt_init(ctx, &m.opt.bpt, view, h_samples_dir, nullptr, 0u, n_chains);
 		m.n_pixels = n_pixels; m.n_chains = n_chains; m.chain_length = mlt_chain_length(m.opt.spp, n_pixels, n_chains);
-		m.n_tech = mlt_tech_count(L);
+		m.n_tech = mlt_tech_count(L, m.lens);
 		const uint32_t n_cells = m.n_tech * n_pixels;          // below 2^32: mmlt_refusal
 		const size_t dims = coord_dims(m);
 		m.table.alloc(n_cells); m.new_value.alloc(cap); m.path_value.alloc(n_chains);
 		m.light_u.alloc(dims * cap); m.eye_u.alloc(dims * cap); m.path_pdf.alloc(n_chains); m.rejections.alloc(n_chains); m.seeds.alloc(n_chains);
 		m.st.alloc(n_chains); m.st_new.alloc(n_chains); m.path_seeds.alloc(n_chains); m.tech_chains.alloc(m.n_tech); m.ends.alloc(m.n_tech);
 		m.q.alloc(n_cells); m.cdf.alloc(n_cells); m.counts.alloc(2); m.mcounts.alloc(3);
+		if (m.lens)
+		{
+			const size_t n_lens_cells = std::max<size_t>(size_t(L - 1u) * n_pixels, 1);
+			m.table_pixel.alloc(n_lens_cells); m.new_pixel.alloc(cap); m.path_pixel.alloc(n_chains);
+			FPT_HIP_CHECK(hipMemsetAsync(m.table_pixel.ptr, 0xFF, n_lens_cells * sizeof(uint32_t), ctx->stream));
+			FPT_HIP_CHECK(hipMemsetAsync(m.new_pixel.ptr, 0xFF, size_t(cap) * sizeof(uint32_t), ctx->stream));
+			FPT_HIP_CHECK(hipMemsetAsync(m.path_pixel.ptr, 0xFF, size_t(n_chains) * sizeof(uint32_t), ctx->stream));
+		}
 		const size_t scratch = mlt_seed_cdf_scratch_bytes(n_cells);
 		require(scratch != 0, "fpt_mmlt_init: the scan's scratch size could not be determined");
 		m.scan_scratch.alloc(scratch);
@@ -385,7 +405,25 @@ int fpt_mmlt_download(fpt_context* ctx, float* h_light_u, float* h_eye_u, float*
 	});
 }
 
+int fpt_mmlt_download_pixels(fpt_context* ctx, uint32_t* h_table_pixel, uint32_t* h_path_pixel)
+{
+	return guarded(ctx, [&] {
+		fpt_context::MltState& m = ctx->mlt;
+		require(m.ready && m.multiplexed, "fpt_mmlt_download_pixels: fpt_mmlt_init has not been called");
+		if (!m.lens) return;
+		hipStream_t s = ctx->stream;
+		const size_t n_lens_cells = size_t(m.opt.bpt.max_path_length - 1u) * m.n_pixels;
+		if (h_table_pixel && n_lens_cells) m.table_pixel.download(h_table_pixel, n_lens_cells, s);
+		if (h_path_pixel) m.path_pixel.download(h_path_pixel, m.n_chains, s);
+		FPT_HIP_CHECK(hipStreamSynchronize(s));
+	});
+}
+
 int fpt_mmlt_debug_eval(fpt_context* ctx, const fpt_rendering_context_view* view, uint32_t n, const float* h_light_u, const float* h_eye_u, const uint32_t* h_st, float* h_value, uint64_t* h_rays)
+{ return fpt_mmlt_debug_eval_pixels(ctx, view, n, h_light_u, h_eye_u, h_st, h_value, h_rays, nullptr); }
+
+int fpt_mmlt_debug_eval_pixels(fpt_context* ctx, const fpt_rendering_context_view* view, uint32_t n, const float* h_light_u, const float* h_eye_u, const uint32_t* h_st, float* h_value, uint64_t* h_rays,
+                               uint32_t* h_pixel)
 {
 	return guarded(ctx, [&] {
 		fpt_context::MltState& m = ctx->mlt;
@@ -393,19 +431,23 @@ int fpt_mmlt_debug_eval(fpt_context* ctx, const fpt_rendering_context_view* view
 		require(view && h_light_u && h_eye_u && h_st && h_value, "fpt_mmlt_debug_eval: null argument");
 		require(n >= 1 && n <= std::max(m.n_pixels, m.n_chains), "fpt_mmlt_debug_eval: n out of range [1, max(n_pixels, n_chains)]");
 		const uint32_t L = m.opt.bpt.max_path_length;
-		for (uint32_t i = 0; i < n; ++i) require(mlt_tech_valid(h_st[i] & 0xFFu, h_st[i] >> 8, L), "fpt_mmlt_debug_eval: a technique outside t in [2, L + 1], s in [0, L + 1 - t]");
+		for (uint32_t i = 0; i < n; ++i)
+			require(mlt_tech_valid(h_st[i] & 0xFFu, h_st[i] >> 8, L, m.lens), m.lens ? "fpt_mmlt_debug_eval: a technique outside t in [2, L + 1], s in [0, L + 1 - t] and t = 1, s in [2, L]"
+			                                                                        : "fpt_mmlt_debug_eval: a technique outside t in [2, L + 1], s in [0, L + 1 - t]");
 		hipStream_t s = ctx->stream;
 		const size_t nu = size_t(coord_dims(m)) * n;
 		// the chains' own coordinates and techniques are kept: the caller's sets are evaluated from scratch arrays
-		DeviceArray<float> lu, eu; DeviceArray<uint32_t> st; DeviceArray<unsigned long long> rays;
+		DeviceArray<float> lu, eu; DeviceArray<uint32_t> st, px; DeviceArray<unsigned long long> rays;
 		lu.upload(h_light_u, nu, s); eu.upload(h_eye_u, nu, s); st.upload(h_st, n, s); rays.alloc(1);
+		if (m.lens) { px.alloc(n); FPT_HIP_CHECK(hipMemsetAsync(px.ptr, 0xFF, size_t(n) * sizeof(uint32_t), s)); }
 		zero(rays, 1, s);
 		zero(m.new_value, n, s);
 		ChainCoords c = chain_view(m, n, 0u, 0u);
 		c.light_u = lu.ptr; c.eye_u = eu.ptr;
-		const ChainTech fixed = { st.ptr, rays.ptr };
+		const ChainTech fixed = { st.ptr, rays.ptr, m.lens ? px.ptr : nullptr };
 		bpt_sample_paths(ctx, 0u, view, n, &c, m.new_value.ptr, nullptr, nullptr, &fixed);          // (with mutation Null nothing reads the instance)
 		m.new_value.download(reinterpret_cast<float4*>(h_value), n, s);
+		if (h_pixel) { if (m.lens) px.download(h_pixel, n, s); else std::fill(h_pixel, h_pixel + n, 0xFFFFFFFFu); }
 		unsigned long long r = 0;
 		FPT_HIP_CHECK(hipMemcpyAsync(&r, rays.ptr, sizeof(r), hipMemcpyDeviceToHost, s));
 		FPT_HIP_CHECK(hipStreamSynchronize(s));

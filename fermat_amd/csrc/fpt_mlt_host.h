@@ -35,13 +35,17 @@ inline uint32_t mlt_mutation_type(float independent_samples, uint32_t instance, 
 
 // ---- the multiplexed renderer (`-mmlt`): one bidirectional technique (s light vertices, t eye vertices) per chain ------------------------------------------
 // With light tracing off the techniques are t in [2, L + 1], s in [0, L + 1 - t]: L (L + 1) / 2 of them, numbered t-major (all techniques of t = 2, s rising, then
-// t = 3, ...): index = sum_{j = 2}^{t - 1} (L + 2 - j) + s.  Shared by the kernels (fpt_bpt.hip, fpt_mlt.hip) and the host
-FPT_HD uint32_t mlt_tech_count(uint32_t L) { return L * (L + 1u) / 2u; }
-FPT_HD bool mlt_tech_valid(uint32_t s, uint32_t t, uint32_t L) { return t >= 2u && t <= L + 1u && s <= L + 1u - t; }
-FPT_HD uint32_t mlt_tech_index(uint32_t s, uint32_t t, uint32_t L) { return (t - 2u) * (L + 2u) - (t * (t - 1u) / 2u - 1u) + s; }
-// the inverse: technique `index` < mlt_tech_count(L) as s | t << 8 (the word a chain keeps)
-FPT_HD uint32_t mlt_tech_st(uint32_t index, uint32_t L)
+// t = 3, ...): index = sum_{j = 2}^{t - 1} (L + 2 - j) + s.  Shared by the kernels (fpt_bpt.hip, fpt_mlt.hip) and the host.
+// `lens` (fpt_mmlt_options::lens_techniques): the lens connections (s, 1), s in [2, L], exist as well -- L - 1 more, numbered AFTER the others with s rising, so that
+// no index above moves: index(s, 1) = L (L + 1) / 2 + (s - 2).  (1, 1) stays out: a light vertex of depth 0 never splats.  L = 1 adds nothing
+FPT_HD uint32_t mlt_tech_count(uint32_t L, bool lens = false) { return L * (L + 1u) / 2u + (lens ? L - 1u : 0u); }
+FPT_HD bool mlt_tech_valid(uint32_t s, uint32_t t, uint32_t L, bool lens = false) { return (t >= 2u && t <= L + 1u && s <= L + 1u - t) || (lens && t == 1u && s >= 2u && s <= L); }
+FPT_HD uint32_t mlt_tech_index(uint32_t s, uint32_t t, uint32_t L, bool lens = false)
+{ return lens && t == 1u ? L * (L + 1u) / 2u + (s - 2u) : (t - 2u) * (L + 2u) - (t * (t - 1u) / 2u - 1u) + s; }
+// the inverse: technique `index` < mlt_tech_count(L, lens) as s | t << 8 (the word a chain keeps)
+FPT_HD uint32_t mlt_tech_st(uint32_t index, uint32_t L, bool lens = false)
 {
+	if (lens && index >= L * (L + 1u) / 2u) return (index - L * (L + 1u) / 2u + 2u) | (1u << 8);
 	uint32_t t = 2u;
 	while (t < L + 1u && index >= L + 2u - t) { index -= L + 2u - t; ++t; }
 	return index | (t << 8);
@@ -52,6 +56,15 @@ FPT_HD uint32_t mlt_swap_proposal(uint32_t s, uint32_t t, float u)
 {
 	const uint32_t s_new = u > 0.5f ? (t > 2u ? s + 1u : 0u) : (s > 0u ? s - 1u : s + t - 2u);
 	return s_new | ((s + t - s_new) << 8);
+}
+// with the lens techniques: the ring of path length k = s + t - 1 >= 2 gains the stop s = k, i.e. (k, 1): u > 1/2 proposes s + 1 (0 from t = 1), otherwise s - 1 (k from
+// s = 0).  k = 1 proposes the chain's own technique ((1, 1) does not exist).  Both directions have probability 1/2 on a cycle: the walk stays symmetric.  Needs t >= 1
+FPT_HD uint32_t mlt_swap_proposal_lens(uint32_t s, uint32_t t, float u)
+{
+	const uint32_t k = s + t - 1u;
+	if (k < 2u) return s | (t << 8);
+	const uint32_t s_new = u > 0.5f ? (t > 1u ? s + 1u : 0u) : (s > 0u ? s - 1u : k);
+	return s_new | ((k + 1u - s_new) << 8);
 }
 // the dimension of mlt_mutation_number that picks the swap's direction: one past the accept/reject number
 FPT_HD uint32_t mlt_swap_dim(uint32_t L) { return (L + 1u) * 6u + 1u; }
@@ -96,8 +109,10 @@ inline const char* mmlt_refusal(const fpt_mmlt_options& o, uint32_t n_pixels, bo
 	if (uint64_t(o.mlt.spp) * n_pixels < o.mlt.n_chains) return "fpt_mmlt_init: spp * n_pixels < n_chains: the chains would have no steps (raise spp or lower n_chains)";
 	if (uint64_t(o.mlt.spp) * n_pixels / o.mlt.n_chains > 0xFFFFFFFFull) return "fpt_mmlt_init: spp * n_pixels / n_chains does not fit 32 bits";
 	if (o.mlt.bpt.max_path_length < 1 || o.mlt.bpt.max_path_length > 15) return "fpt_mmlt_init: max_path_length out of range [1,15]";
-	if (uint64_t(mlt_tech_count(o.mlt.bpt.max_path_length)) * n_pixels > 0xFFFFFFFFull)
-		return "fpt_mmlt_init: the technique table (max_path_length (max_path_length + 1) / 2 cells per pixel) does not fit 32 bits: lower the resolution or max_path_length";
+	if (o.lens_techniques > 1u) return "fpt_mmlt_init: lens_techniques must be 0 or 1";
+	if (uint64_t(mlt_tech_count(o.mlt.bpt.max_path_length, o.lens_techniques != 0u)) * n_pixels > 0xFFFFFFFFull)
+		return o.lens_techniques ? "fpt_mmlt_init: the technique table (max_path_length (max_path_length + 1) / 2 + max_path_length - 1 cells per pixel with lens_techniques = 1) does not fit 32 bits: lower the resolution or max_path_length"
+		                         : "fpt_mmlt_init: the technique table (max_path_length (max_path_length + 1) / 2 cells per pixel) does not fit 32 bits: lower the resolution or max_path_length";
 	return nullptr;
 }
 

@@ -577,9 +577,12 @@ void HipMMLT::init(int argc, char** argv, RenderingContext& renderer)
 {
 	fpt_mmlt_options& p = m_options;
 	parse_pssmlt_options(argc, argv, p.mlt);
-	p.mmlt_frequency = 0;
+	p.mmlt_frequency = 0; p.lens_techniques = 0;
 	for (int i = 0; i + 1 < argc; ++i)
+	{
 		if (std::strcmp(argv[i], "-mmlt-swaps") == 0 || std::strcmp(argv[i], "-mmlt-frequency") == 0) p.mmlt_frequency = uint32(std::atoi(argv[++i]));
+		else if (std::strcmp(argv[i], "-mmlt-lens") == 0) p.lens_techniques = uint32(std::atoi(argv[++i]));
+	}
 	fpt_context* ctx = renderer.get_hip_context();
 	const fpt_rendering_context_view v = renderer.view(0);
 	const SceneArrays& h = renderer.get_host_scene();
@@ -604,6 +607,9 @@ void HipMMLT::render(const uint32 instance, RenderingContext& renderer)
 		for (uint32 t = 2; t <= L + 1; ++t)
 			for (uint32 s = 0; s + t <= L + 1; ++s)
 				std::fprintf(stderr, "    [%u,%u] : %7u, %f\n", s, t, chains[s + t * W], norms[s + t * W]);
+		// the lens connections, in table order after the others
+		for (uint32 s = 2; m_options.lens_techniques && s <= L; ++s)
+			std::fprintf(stderr, "    [%u,%u] : %7u, %f\n", s, 1u, chains[s + 1 * W], norms[s + 1 * W]);
 	}
 }
 

@@ -382,6 +382,9 @@ int64_t* fpt_bpt_splat_buffer(fpt_context* ctx);
 int fpt_bpt_use_splat_buffer(fpt_context* ctx, int64_t* d_splats);       /* caller-owned buffer (3 x int64 per pixel, zeroed) instead of the internal one; NULL restores it */
 int fpt_bpt_set_deferred_splats(fpt_context* ctx, int deferred);
 int fpt_bpt_resolve_splats(fpt_context* ctx, const fpt_rendering_context_view* view);
+/* probe (tests): the light-tracing stage's shadow queue as the last fpt_bpt_render (one pass in flight) left it: the number of its entries and of those that were
+ * splatted (a positive weight and an unoccluded shadow ray) */
+int fpt_debug_bpt_splat_entries(fpt_context* ctx, uint32_t* h_entries, uint32_t* h_visible);
 
 /* ---- primary-sample-space Metropolis light transport (`-pssmlt`, src/renderers/pssmlt.{h,cu}) on the bidirectional kernels ----------------------
  * One render call = PSSMLT::render (pssmlt.cu:541-700): the frame is rescaled by instance / (instance + 1); a presampling BPT pass over the pixels keeps every
@@ -438,26 +441,41 @@ int fpt_debug_mlt(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_params
 
 /* ---- multiplexed Metropolis light transport (`-mmlt`): one bidirectional technique per chain.  The reference's `-cmlt -charted-swaps 0`
  *      (src/renderers/cmlt.{h,cu}): the part of CMLT that needs no path inversion -----------------------------------------------------------------------------------
- * A technique is (s light vertices, t eye vertices); with light tracing off t is in [2, L + 1] and s in [0, L + 1 - t]: L (L + 1) / 2 techniques, numbered t-major
- * (index = sum_{j=2}^{t-1} (L + 2 - j) + s).  One render call: the frame is rescaled; a presampling BPT pass over the pixels stores every sample in the cell
+ * A technique is (s light vertices, t eye vertices).  With lens_techniques = 0 light tracing is off, t is in [2, L + 1] and s in [0, L + 1 - t]: L (L + 1) / 2
+ * techniques, numbered t-major (index = sum_{j=2}^{t-1} (L + 2 - j) + s).  With lens_techniques = 1 the lens connections (s, 1), s in [2, L] -- a light sub-path of s
+ * vertices joined straight to the lens, the BPT's light tracing -- exist beside them: L - 1 more techniques, numbered after the others (index = L (L + 1) / 2 + s - 2),
+ * and the base options' light_tracing is set to 1, so that every technique's MIS weight accounts for the lens connection.  (1, 1) stays out: a light vertex of depth 0
+ * never splats.  One render call: the frame is rescaled; a presampling BPT pass over the pixels stores every sample in the cell
  * [technique * n_pixels + pixel] of the technique table; the PSSMLT integer CDF over all cells draws n_chains stratified seeds -- stratum i's target is the exact integer
  * floor(total * (i * 2^24 + m) / (n_chains * 2^24)), m = floor(randfloat(instance, hash32(0x5eed5eed)) * 2^24) ONE offset for all strata, so that every technique starts
  * within 1 of n_chains * its share of the chains --, seed e starting a chain with technique e / n_pixels from the coordinates of eye path e % n_pixels: the chains start
  * sorted by technique; st_norm(s, t) = (the CDF's difference across the technique's
  * block) * 2^-32 / n_pixels and image_brightness the same expression on the total; every chain then takes chain_length steps as PSSMLT's on its OWN technique: the
  * light sub-path stops at vertex s - 1 (none for s = 0), the eye sub-path at vertex t, one connection or the emission is sampled -- at most
- * max(s - 1, 0) + (t - 1) + [s > 0] rays per proposal.  mmlt_frequency = F > 0: step l > 0 with l % F == 0 keeps the coordinates and proposes the neighbouring
+ * max(s - 1, 0) + (t - 1) + [s > 0] rays per proposal.
+ * The lens techniques: the presampling pass also connects every stored vertex of light path `id` to the lens (the BPT's light-tracing stage); the sample of depth d is
+ * technique (d + 1, 1) and, when its shadow ray is unoccluded, cell [index(d + 1, 1) * n_pixels + id] holds (c, 1), c = alpha f_L f_s G mis_w -- the BPT's splat BEFORE
+ * the multiplication by light_weight = 1 / n_pixels -- and a parallel uint32 plane holds the pixel it lands on (0xFFFFFFFF where there is no sample).  What such a
+ * sample adds to a pixel of the frame is c * light_weight (per component, in float), and that is what it counts for wherever the renderer weighs it: in the seed CDF (so
+ * that the table's total over n_pixels is the frame's mean, and st_norms / image_brightness / pdf_norm keep their expressions), in a chain's acceptance test, in its
+ * deposit and in its path_value; fpt_mmlt_debug_eval and the table return c.  A seed in the lens block starts its technique from the coordinates of LIGHT path e % n_pixels (the eye coordinates of the
+ * same index come along).  A chain on (s, 1) traces no eye sub-path: vertex s - 1 of its light sub-path is connected to the lens, s rays per proposal at most, and
+ * the chain's pixel is the one the connection lands on, kept per chain beside the value (0xFFFFFFFF: the pixel of eye coordinates 3 and 4, as for t >= 2); all eye
+ * coordinates of such a chain are free variables, perturbed and committed like the others.
+ * mmlt_frequency = F > 0: step l > 0 with l % F == 0 keeps the coordinates and proposes the neighbouring
  * technique of the same path length instead (the cyclic walk on s of mmlt_swap_kernel, cmlt.cu:496-544, chosen by mutation number dimension (L + 1) * 6 + 1),
- * accepted with min(1, new / old) and splatted as any other step; the technique is replaced with the value on acceptance.
+ * accepted with min(1, new / old) and splatted as any other step; the technique is replaced with the value on acceptance.  With lens_techniques = 1 the cycle of path
+ * length k = s + t - 1 >= 2 is s in [0, k], s = k being (k, 1); k = 1 proposes the chain's own technique.
  * Deviations: PSSMLT's three (above), the seeds' common offset (PSSMLT jitters every stratum on its own, in float), and the swap's acceptance test takes no st_norms ratio (the reference multiplies the test, not the splats, by
  * st_norms[new] / st_norms[old], cmlt.cu:375-377): the target is max_comp f_{s,t}(u) on the disjoint union of the techniques and the walk is symmetric.
- * Not built: charted swaps and path inversion, chains that persist across render calls (`reseeding`, `startup_skips`: every call reseeds), techniques with t <= 1 and
- * light tracing, single_connection = 1, passes in flight, tile sharding / multi-GPU.
- * fpt_mmlt_init replaces fpt_pssmlt_init / fpt_bpt_init and refuses what fpt_pssmlt_init refuses, and a technique table of 2^32 cells or more. */
+ * Not built: charted swaps and path inversion, chains that persist across render calls (`reseeding`, `startup_skips`: every call reseeds), techniques with t = 0,
+ * single_connection = 1, passes in flight, tile sharding / multi-GPU.
+ * fpt_mmlt_init replaces fpt_pssmlt_init / fpt_bpt_init and refuses what fpt_pssmlt_init refuses, lens_techniques > 1, and a technique table of 2^32 cells or more. */
 typedef struct fpt_mmlt_options
 {
 	fpt_pssmlt_options mlt;
 	uint32_t mmlt_frequency;               /* 0: no swaps */
+	uint32_t lens_techniques;              /* 0: t >= 2 only, light tracing off; 1: the lens connections (s, 1), s in [2, L], as well, light tracing on */
 } fpt_mmlt_options;
 typedef struct fpt_mmlt_stats
 {
@@ -479,6 +497,13 @@ int fpt_mmlt_download(fpt_context* ctx, float* h_light_u, float* h_eye_u, float*
 /* as fpt_pssmlt_debug_eval, set i evaluating technique h_st[i] = s | t << 8 alone; h_rays (or NULL) receives the number of rays queued */
 int fpt_mmlt_debug_eval(fpt_context* ctx, const fpt_rendering_context_view* view, uint32_t n, const float* h_light_u, const float* h_eye_u, const uint32_t* h_st,
                         float* h_value /*float4*/, uint64_t* h_rays);
+/* the lens techniques' planes (any pointer may be NULL): h_table_pixel, uint32 x (L - 1) x n_pixels, [(s - 2) * n_pixels + light path] = the pixel of that cell's
+ * sample (0xFFFFFFFF: none); h_path_pixel, uint32 x n_chains, the pixel of each chain's current state (0xFFFFFFFF: that of eye coordinates 3 and 4).  With
+ * lens_techniques = 0 nothing is written */
+int fpt_mmlt_download_pixels(fpt_context* ctx, uint32_t* h_table_pixel, uint32_t* h_path_pixel);
+/* fpt_mmlt_debug_eval that also returns, in h_pixel (uint32 x n, or NULL), the pixel a t = 1 evaluation lands on (0xFFFFFFFF for t >= 2 or when nothing was connected) */
+int fpt_mmlt_debug_eval_pixels(fpt_context* ctx, const fpt_rendering_context_view* view, uint32_t n, const float* h_light_u, const float* h_eye_u, const uint32_t* h_st,
+                               float* h_value /*float4*/, uint64_t* h_rays, uint32_t* h_pixel);
 
 /* ---- multi-GPU: image tiles sharded over one process per GPU; replaces the single-GPU reference's cudaSetDevice(0) + whole-frame
  *      ownership (src/renderer.cu:600-603).  No data-path collective: each rank renders the pixels handed to fpt_pt_init / fpt_bpt_init

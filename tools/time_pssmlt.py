@@ -2,7 +2,7 @@
 (s, t) technique per chain) -- on the water_caustic stand-in (the scene of bench.py --renderer bpt), at the reference's defaults (64 K chains, 4 spp) and at 1 M
 chains.  A timing tool, not a bench line: bench.py measures the flagship workloads and knows nothing of these renderers.
 
-    python tools/time_pssmlt.py [--renderer pssmlt|mmlt] [--mmlt-swaps F] [--res 1600 900] [--path-length 9] [--chains 65536 1048576] [--spp 4] [--repeats 3]
+    python tools/time_pssmlt.py [--renderer pssmlt|mmlt] [--mmlt-swaps F] [--lens] [--res 1600 900] [--path-length 9] [--chains 65536 1048576] [--spp 4] [--repeats 3]
 
 After the timed calls: one call at 2 x spp, from which the time of everything but the chain steps (rescale, presampling pass, seed CDF and seeds, coordinate
 recovery, resolve) is extrapolated as  t(spp) - chain_length(spp) x the time per step,  and one call with the traversal kernels' counters on, which gives the rays
@@ -36,6 +36,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--renderer", choices=("pssmlt", "mmlt"), default="pssmlt")
     ap.add_argument("--mmlt-swaps", type=int, default=0)
+    ap.add_argument("--lens", action="store_true", help="--renderer mmlt: the lens connections (s, 1) beside the other techniques (light tracing on)")
     args = ap.parse_args()
     mmlt = args.renderer == "mmlt"
     W, H = args.res
@@ -45,7 +46,7 @@ def main():
     for n_chains in args.chains:
         def renderer(spp):
             if mmlt:
-                return fa.Renderer(s, W, H, fa.default_options(L), table=table, mmlt_options=fa.default_mmlt_options(L, mmlt_frequency=args.mmlt_swaps, n_chains=n_chains, spp=spp))
+                return fa.Renderer(s, W, H, fa.default_options(L), table=table, mmlt_options=fa.default_mmlt_options(L, mmlt_frequency=args.mmlt_swaps, lens_techniques=int(args.lens), n_chains=n_chains, spp=spp))
             return fa.Renderer(s, W, H, fa.default_options(L), table=table, pssmlt_options=fa.default_pssmlt_options(L, n_chains=n_chains, spp=spp))
 
         def timed(r, first, repeats):
@@ -79,7 +80,9 @@ def main():
         extra = {"renderer": args.renderer, "step_ms": round(step_s * 1e3, 3), "presample_and_seed_s": round(med - st["chain_length"] * step_s, 4),
                  "traced_rays_per_mutation": round(traced / (st["chain_length"] * n_chains), 3)}
         if mmlt:
-            n_tech = L * (L + 1) // 2
+            n_tech = L * (L + 1) // 2 + (L - 1 if args.lens else 0)
+            norms, _ = r.mmlt_st_norms()          # indexed [t, s]: the share of the norms the lens connections (t = 1) hold
+            extra.update({"lens": int(args.lens), "st_norm_share_t1": round(float(norms[1].sum() / max(float(norms.sum()), 1e-30)), 4)})
             extra.update({"mmlt_swaps": args.mmlt_swaps, "queued_rays_per_mutation": round(st["rays"] / (st["chain_length"] * n_chains), 3), "swaps_proposed": st["swaps_proposed"],
                           "swaps_accepted": st["swaps_accepted"], "table_cells": n_tech * W * H, "table_MiB": round(n_tech * W * H * 16 / 2 ** 20, 1)})
         print(json.dumps({**extra, "tool": "time_pssmlt", "scene": "water_caustic-standin", "triangles": int(s.num_triangles), "resolution": [W, H], "max_path_length": L,
