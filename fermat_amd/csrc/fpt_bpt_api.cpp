@@ -133,7 +133,7 @@ extern "C" {
 int fpt_bpt_init(fpt_context* ctx, const fpt_bpt_options* opts, const fpt_rendering_context_view* view, const char* h_samples_dir,
                  const uint32_t* d_pixels, uint32_t n_local_pixels)
 {
-	return guarded(ctx, [&] { ctx->mlt.ready = false; bpt_init(ctx, opts, view, h_samples_dir, d_pixels, n_local_pixels, 0u); });
+	return guarded(ctx, [&] { ctx->mlt.reset(); bpt_init(ctx, opts, view, h_samples_dir, d_pixels, n_local_pixels, 0u); });
 }
 
 int fpt_bpt_set_profiling(fpt_context* ctx, int on) { return guarded(ctx, [&] { flush_deferred(ctx); ctx->bpt.profiling = on != 0; }); }
@@ -348,10 +348,10 @@ void bpt_sample_paths(fpt_context* ctx, uint32_t instance, const fpt_rendering_c
                       const TechTable* tech, const ChainTech* fixed)
 {
 	fpt_context::BptState& b = ctx->bpt;
-	require(b.ready && b.max_batch == 1 && !b.d_pixels && !b.light_pending && b.pending_n == 0, "fpt_pssmlt: the bidirectional state is not the one fpt_pssmlt_init made");
-	require(((value != nullptr) != (tech != nullptr && tech->cell != nullptr)) && (n ? n : b.n_paths) <= std::max(b.n_paths, b.min_paths), "fpt_pssmlt: more paths than the storage holds");
-	require(!fixed || (chain && value && !b.opt.single_connection), "fpt_mmlt: a technique-fixed evaluation needs chain coordinates, a value sink and single_connection = 0");
-	require(!(tech && tech->cell && b.light_tracing) || tech->pixel, "fpt_mmlt: with light tracing on the technique table needs its pixel plane");
+	require(b.ready && b.max_batch == 1 && !b.d_pixels && !b.light_pending && b.pending_n == 0, "fpt_mlt: the bidirectional state is not the one the Metropolis renderer's init made");
+	require(((value != nullptr) != (tech != nullptr && tech->cell != nullptr)) && (n ? n : b.n_paths) <= std::max(b.n_paths, b.min_paths), "fpt_mlt: more paths than the storage holds");
+	require(!fixed || (chain && value && !b.opt.single_connection), "fpt_mlt: a technique-fixed evaluation needs chain coordinates, a value sink and single_connection = 0");
+	require(!(tech && tech->cell && b.light_tracing) || tech->pixel, "fpt_mlt: with light tracing on the technique table needs its pixel plane");
 	BptRun run(ctx, instance, 1, view);
 	if (tiled) *tiled = run.P;
 	run.for_value_sink(n ? n : b.n_paths, chain, value, tech, fixed);

@@ -385,29 +385,60 @@ struct fpt_context
 		uint32_t light_instance = 0, light_passes = 0;
 		fpt::DeviceArray<fpt::LightVertexWire> lv_send, lv_recv; fpt::DeviceArray<uint32_t> lv_count;
 	} bpt;
-	// primary-sample-space Metropolis renderer (fpt_mlt_api.cpp) on the bidirectional state above
+	// The state of the two Metropolis renderers on the bidirectional state above (fpt_mlt_api.cpp) and its one owner: `-pssmlt` (fpt_pssmlt_init) and `-mmlt`
+	// (fpt_mmlt_init; `lens`: with its lens techniques (s, 1)) are two modes of one state, and one init of either leaves the other nothing.
+	//   1. Agreement.  Whenever `mode` is not None, the arrays, n_pixels, n_chains, chain_length, n_tech, `lens` and the options agree, and ctx->bpt is the state this
+	//      init made: min_paths = n_chains, the forced options (light_tracing = lens, single_connection = 0), one pass in flight.
+	//   2. Invalid during init.  From the first modification to the end of an init `mode` is None.  A throw in between -- a refusal, an allocation -- leaves it None and
+	//      releases every array below; if bpt_init had already run, it clears ctx->bpt.ready as well, so that no bidirectional state with options nobody asked for stays usable.
+	//   3. Nothing left over.  A successful init leaves allocated only what its mode uses: an init starts with reset(), and allocate() walks each_array(), where an array
+	//      the mode does not use has no elements.
+	//   4. Readers check first.  Everything that reads the state checks `mode` first (state_in, fpt_mlt_api.cpp): render, get_stats, get_st_norms, download,
+	//      download_pixels and debug_eval of both families, each answering "<its init> has not been called" in any other mode.
+	//   5. reset() is the only way to invalidate the state: fpt_bpt_init, which replaces the bidirectional state under it, calls it.
 	struct MltState
 	{
-		bool ready = false;
+		enum Mode : uint32_t { None, Pssmlt, Mmlt };
+		Mode mode = None;
+		bool lens = false;                                                 // of Mmlt: fpt_mmlt_options::lens_techniques
 		fpt_pssmlt_options opt{};
 		uint32_t n_pixels = 0, n_chains = 0, chain_length = 0;
-		fpt::DeviceArray<float4> presample, new_value, path_value;       // per pixel; per chain (new_value: max(n_pixels, n_chains), fpt_pssmlt_debug_eval)
-		fpt::DeviceArray<float> light_u, eye_u, path_pdf;                  // (L+1)*3 x max(n_pixels, n_chains); n_chains
+		uint32_t mmlt_frequency = 0, n_tech = 0;                           // of Mmlt; Pssmlt: no swaps, ONE technique: its presampling value per pixel is a table with a single block
+		size_t scan_bytes = 0;                                             // mlt_seed_cdf_scratch_bytes(n_tech * n_pixels)
+		fpt::DeviceArray<float4> table, new_value, path_value;            // the presampling pass's technique table; the proposals' and the chains' values
+		fpt::DeviceArray<float> light_u, eye_u, path_pdf;
 		fpt::DeviceArray<uint32_t> rejections, seeds;
-		fpt::DeviceArray<unsigned long long> q, cdf, counts;               // the seed CDF and its terms (n_pixels); accepted, rejected, + the CDF's total read back
+		fpt::DeviceArray<unsigned long long> q, cdf, counts;               // the seed CDF and its terms; accepted, rejected
 		fpt::DeviceArray<uint8_t> scan_scratch;
-		fpt_pssmlt_stats stats{};
-		// the multiplexed renderer (`-mmlt`, fpt_mmlt_init): one (s, t) technique per chain
-		bool multiplexed = false;
-		uint32_t mmlt_frequency = 0, n_tech = 0;
-		fpt::DeviceArray<float4> table;                                    // the presampling pass's technique table: n_tech x n_pixels cells
-		fpt::DeviceArray<uint32_t> st, st_new, path_seeds, tech_chains;    // per chain: s | t << 8, the swap step's proposal, the seed's eye path; chains seeded per technique
-		fpt::DeviceArray<unsigned long long> mcounts, ends;                // swaps proposed, swaps accepted, rays queued by the chain steps; the CDF at the techniques' block ends
-		std::vector<float> st_norms; std::vector<uint32_t> st_chains;      // (L+2)^2 each, s + t * (L+2)
-		fpt_mmlt_stats mstats{};
-		// its lens techniques (fpt_mmlt_options::lens_techniques): the table's pixel plane ((L - 1) x n_pixels), the pixel of every chain's proposal and current state
-		bool lens = false;
-		fpt::DeviceArray<uint32_t> table_pixel, new_pixel, path_pixel;
+		// Mmlt: per chain s | t << 8, the swap step's proposal, the seed's path; chains seeded per technique; swaps proposed, swaps accepted, rays queued by the chain
+		// steps; the CDF at the techniques' block ends
+		fpt::DeviceArray<uint32_t> st, st_new, path_seeds, tech_chains;
+		fpt::DeviceArray<unsigned long long> mcounts, ends;
+		fpt::DeviceArray<uint32_t> table_pixel, new_pixel, path_pixel;     // lens: the pixel of the lens block's cells, of every chain's proposal and of its current state
+		std::vector<float> st_norms; std::vector<uint32_t> st_chains;      // Mmlt: (L+2)^2 each, s + t * (L+2)
+		fpt_mmlt_stats stats{};                                            // of the last render call; fpt_pssmlt_stats is its leading part
+		uint32_t dims() const { return (opt.bpt.max_path_length + 1u) * 3u; }      // coordinates per chain and side
+		// the list: v(array, its elements in mode `of` for the shape above, the byte it is cleared with).  new_value and the coordinates hold max(n_pixels, n_chains)
+		// entries (debug_eval takes that many sets); the lens block's pixel plane keeps one entry at L = 1, where the block is empty.  The list's order is the order
+		// of allocation, the one the two inits had when they were separate (EXPERIMENTS 6i)
+		template <typename V> void each_array(Mode of, V&& v)
+		{
+			const size_t px = n_pixels, ch = n_chains, cap = px > ch ? px : ch, cells = size_t(n_tech) * px, x = of == Mmlt, l = x && lens, L = opt.bpt.max_path_length;
+			v(table, cells, 0); v(new_value, cap, 0); v(path_value, ch, 0); v(light_u, dims() * cap, 0); v(eye_u, dims() * cap, 0); v(path_pdf, ch, 0); v(rejections, ch, 0); v(seeds, ch, 0);
+			v(st, x * ch, 0); v(st_new, x * ch, 0); v(path_seeds, x * ch, 0); v(tech_chains, x * n_tech, 0); v(ends, x * n_tech, 0);
+			v(q, cells, 0); v(cdf, cells, 0); v(counts, 2, 0); v(mcounts, x * 3, 0);
+			v(table_pixel, l * (L > 1 ? (L - 1) * px : 1), 0xFF); v(new_pixel, l * cap, 0xFF); v(path_pixel, l * ch, 0xFF);
+			v(scan_scratch, scan_bytes, 0);
+		}
+		// the storage of mode `of` for the shape the members describe, cleared on `s` (part of an init: `mode` stays None)
+		void allocate(Mode of, hipStream_t s)
+		{ each_array(of, [&](auto& a, size_t n, int fill) { a.alloc(n); if (n) FPT_HIP_CHECK(hipMemsetAsync(a.ptr, fill, n * sizeof(*a.ptr), s)); }); }
+		void reset()
+		{
+			mode = None; lens = false; opt = fpt_pssmlt_options{}; n_pixels = n_chains = chain_length = mmlt_frequency = n_tech = 0; scan_bytes = 0;
+			each_array(None, [](auto& a, size_t, int) { a.release(); });
+			st_norms.clear(); st_chains.clear(); stats = fpt_mmlt_stats{};
+		}
 	} mlt;
 	bool profiling = false;
 	int capture_bounce = -1;
@@ -466,7 +497,8 @@ namespace fpt { void resize_wavefront(fpt_context* ctx, uint32_t passes, const f
                 void set_batch(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_context_view* view, bool for_psfpt); }
 // fpt_bpt_api.cpp: what fpt_bpt_set_batch allocates per path in flight, with every pixel rendered here
 namespace fpt { uint64_t bpt_bytes_per_path(fpt_context* ctx); }
-// fpt_bpt_api.cpp, for the Metropolis renderer (inside the caller's `guarded`).  bpt_init: fpt_bpt_init's body, storage for at least `min_paths` paths.
+// fpt_bpt_api.cpp, for the Metropolis renderers (inside the caller's `guarded`).  bpt_init: fpt_bpt_init's body, storage for at least `min_paths` paths; the one init of
+// fpt_mlt_api.cpp calls it and, should it throw afterwards, clears ctx->bpt.ready (MltState, invariant 2); fpt_bpt_init itself resets ctx->mlt first (invariant 5).
 // bpt_sample_paths: one bidirectional wavefront (BptRun: light_phase, rest) of `n` light and eye sub-paths -- n = 0: the frame's pixels -- whose samples go to
 // `value` (ValueSink) and whose coordinates come from `chain` (ChainCoords) or, chain == NULL, from the tiled sequence; the frame is not touched.  `tiled`, when
 // given, receives the parameter block of the tiled pass (what launch_mlt_recover_coordinates reads).  `tech` (with value == NULL): the samples go to the technique

@@ -4,19 +4,21 @@
 #pragma once
 #include "fpt_math.h"
 #include "../../include/fermat_pt_hip.h"
+#include <string>
 
 namespace fpt {
 
-// why fpt_pssmlt_init refuses these options (the message names the option), or NULL.  `sharded`: the caller passed a pixel list
-inline const char* mlt_refusal(const fpt_pssmlt_options& o, uint32_t n_pixels, bool sharded)
+// why the init named `who` refuses these options: "<who>: <a reason that names the option>", or empty.  `sharded`: the caller passed a pixel list
+inline std::string mlt_refusal(const fpt_pssmlt_options& o, uint32_t n_pixels, bool sharded, const char* who = "fpt_pssmlt_init")
 {
-	if (o.bpt.use_vpls) return "fpt_pssmlt_init: use_vpls = 1 is not supported (a chain's first light coordinate would have to select a VPL)";
-	if (sharded) return "fpt_pssmlt_init: a tile-sharded context (pixels != NULL) is not supported: a chain splats to any pixel";
-	if (o.n_chains == 0) return "fpt_pssmlt_init: n_chains must be at least 1";
-	if (o.n_chains >= (1u << 24)) return "fpt_pssmlt_init: n_chains must stay below 2^24 (light-vertex ids hold 24-bit path indices)";
-	if (uint64_t(o.spp) * n_pixels < o.n_chains) return "fpt_pssmlt_init: spp * n_pixels < n_chains: the chains would have no steps (raise spp or lower n_chains)";
-	if (uint64_t(o.spp) * n_pixels / o.n_chains > 0xFFFFFFFFull) return "fpt_pssmlt_init: spp * n_pixels / n_chains does not fit 32 bits";
-	return nullptr;
+	const char* why = nullptr;
+	if (o.bpt.use_vpls) why = "use_vpls = 1 is not supported (a chain's first light coordinate would have to select a VPL)";
+	else if (sharded) why = "a tile-sharded context (pixels != NULL) is not supported: a chain splats to any pixel";
+	else if (o.n_chains == 0) why = "n_chains must be at least 1";
+	else if (o.n_chains >= (1u << 24)) why = "n_chains must stay below 2^24 (light-vertex ids hold 24-bit path indices)";
+	else if (uint64_t(o.spp) * n_pixels < o.n_chains) why = "spp * n_pixels < n_chains: the chains would have no steps (raise spp or lower n_chains)";
+	else if (uint64_t(o.spp) * n_pixels / o.n_chains > 0xFFFFFFFFull) why = "spp * n_pixels / n_chains does not fit 32 bits";
+	return why ? std::string(who) + ": " + why : std::string();
 }
 // chain_length = spp * n_pixels / n_chains (pssmlt.cu:560); the product in 64 bits
 inline uint32_t mlt_chain_length(uint32_t spp, uint32_t n_pixels, uint32_t n_chains) { return n_chains ? uint32_t(uint64_t(spp) * n_pixels / n_chains) : 0u; }
@@ -99,21 +101,17 @@ FPT_HD unsigned long long mlt_seed_target(unsigned long long total, uint32_t i, 
 	return (total / d) * num + mlt_muldiv(total % d, num, d);
 }
 // (st_norm of a technique is mlt_image_brightness on the seed CDF's difference across the technique's block of the table)
-// why fpt_mmlt_init refuses these options (the message names the option), or NULL: fpt_pssmlt_init's reasons and a technique table whose cells do not fit 32 bits
-inline const char* mmlt_refusal(const fpt_mmlt_options& o, uint32_t n_pixels, bool sharded)
+// why fpt_mmlt_init refuses these options, or empty: mlt_refusal's reasons, then a path length or a switch out of range and a technique table whose cells do not fit 32 bits
+inline std::string mmlt_refusal(const fpt_mmlt_options& o, uint32_t n_pixels, bool sharded)
 {
-	if (o.mlt.bpt.use_vpls) return "fpt_mmlt_init: use_vpls = 1 is not supported (a chain's first light coordinate would have to select a VPL)";
-	if (sharded) return "fpt_mmlt_init: a tile-sharded context (pixels != NULL) is not supported: a chain splats to any pixel";
-	if (o.mlt.n_chains == 0) return "fpt_mmlt_init: n_chains must be at least 1";
-	if (o.mlt.n_chains >= (1u << 24)) return "fpt_mmlt_init: n_chains must stay below 2^24 (light-vertex ids hold 24-bit path indices)";
-	if (uint64_t(o.mlt.spp) * n_pixels < o.mlt.n_chains) return "fpt_mmlt_init: spp * n_pixels < n_chains: the chains would have no steps (raise spp or lower n_chains)";
-	if (uint64_t(o.mlt.spp) * n_pixels / o.mlt.n_chains > 0xFFFFFFFFull) return "fpt_mmlt_init: spp * n_pixels / n_chains does not fit 32 bits";
+	const std::string common = mlt_refusal(o.mlt, n_pixels, sharded, "fpt_mmlt_init");
+	if (!common.empty()) return common;
 	if (o.mlt.bpt.max_path_length < 1 || o.mlt.bpt.max_path_length > 15) return "fpt_mmlt_init: max_path_length out of range [1,15]";
 	if (o.lens_techniques > 1u) return "fpt_mmlt_init: lens_techniques must be 0 or 1";
 	if (uint64_t(mlt_tech_count(o.mlt.bpt.max_path_length, o.lens_techniques != 0u)) * n_pixels > 0xFFFFFFFFull)
 		return o.lens_techniques ? "fpt_mmlt_init: the technique table (max_path_length (max_path_length + 1) / 2 + max_path_length - 1 cells per pixel with lens_techniques = 1) does not fit 32 bits: lower the resolution or max_path_length"
 		                         : "fpt_mmlt_init: the technique table (max_path_length (max_path_length + 1) / 2 cells per pixel) does not fit 32 bits: lower the resolution or max_path_length";
-	return nullptr;
+	return std::string();
 }
 
 } // namespace fpt

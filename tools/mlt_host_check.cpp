@@ -16,13 +16,15 @@ int main()
 {
 	fpt_pssmlt_options o; std::memset(&o, 0, sizeof(o));
 	o.bpt.max_path_length = 6; o.n_chains = 64 * 1024; o.spp = 4; o.light_perturbations = o.eye_perturbations = 1; o.radius = 0.01f;
-	CHECK(mlt_refusal(o, 1600 * 900, false) == nullptr);
-	{ fpt_pssmlt_options p = o; p.bpt.use_vpls = 1; const char* w = mlt_refusal(p, 1024, false); CHECK(w && std::strstr(w, "use_vpls")); }
-	{ const char* w = mlt_refusal(o, 1600 * 900, true); CHECK(w && std::strstr(w, "pixels")); }
-	{ fpt_pssmlt_options p = o; p.n_chains = 0; const char* w = mlt_refusal(p, 1024, false); CHECK(w && std::strstr(w, "n_chains")); }
-	{ fpt_pssmlt_options p = o; p.n_chains = 1u << 24; const char* w = mlt_refusal(p, 1u << 23, false); CHECK(w && std::strstr(w, "n_chains")); }
-	{ fpt_pssmlt_options p = o; p.n_chains = 300; p.spp = 1; const char* w = mlt_refusal(p, 256, false); CHECK(w && std::strstr(w, "spp")); }
-	{ fpt_pssmlt_options p = o; p.n_chains = 1; p.spp = 0xFFFFFFFFu; const char* w = mlt_refusal(p, 0xFFFFFFu, false); CHECK(w && std::strstr(w, "32 bits")); }
+	CHECK(mlt_refusal(o, 1600 * 900, false).empty());
+	auto refuses = [&](const fpt_pssmlt_options& p, uint32_t n_pixels, bool sharded, const char* word)
+	{ const std::string w = mlt_refusal(p, n_pixels, sharded); return std::strstr(w.c_str(), "fpt_pssmlt_init") && std::strstr(w.c_str(), word); };
+	{ fpt_pssmlt_options p = o; p.bpt.use_vpls = 1; CHECK(refuses(p, 1024, false, "use_vpls")); }
+	{ CHECK(refuses(o, 1600 * 900, true, "pixels")); }
+	{ fpt_pssmlt_options p = o; p.n_chains = 0; CHECK(refuses(p, 1024, false, "n_chains")); }
+	{ fpt_pssmlt_options p = o; p.n_chains = 1u << 24; CHECK(refuses(p, 1u << 23, false, "n_chains")); }
+	{ fpt_pssmlt_options p = o; p.n_chains = 300; p.spp = 1; CHECK(refuses(p, 256, false, "spp")); }
+	{ fpt_pssmlt_options p = o; p.n_chains = 1; p.spp = 0xFFFFFFFFu; CHECK(refuses(p, 0xFFFFFFu, false, "32 bits")); }
 	// products that overflow 32 bits stay exact
 	CHECK(mlt_chain_length(4, 1600 * 900, 64 * 1024) == 87);
 	CHECK(mlt_chain_length(4096, 4096 * 4096 - 1, 1u << 23) == uint32_t(uint64_t(4096) * (4096 * 4096 - 1) >> 23));
@@ -97,9 +99,9 @@ int main()
 	CHECK(!mlt_is_swap_step(0, 4) && !mlt_is_swap_step(2, 0) && mlt_is_swap_step(2, 4) && !mlt_is_swap_step(2, 3) && mlt_is_swap_step(1, 1));
 	{
 		fpt_mmlt_options mo; std::memset(&mo, 0, sizeof(mo)); mo.mlt = o; mo.mmlt_frequency = 2;
-		CHECK(mmlt_refusal(mo, 1600 * 900, false) == nullptr);
+		CHECK(mmlt_refusal(mo, 1600 * 900, false).empty());
 		auto names = [&](const fpt_mmlt_options& p, uint32_t n_pixels, bool sharded, const char* word)
-		{ const char* w = mmlt_refusal(p, n_pixels, sharded); return w && std::strstr(w, "fpt_mmlt_init") && std::strstr(w, word); };
+		{ const std::string w = mmlt_refusal(p, n_pixels, sharded); return std::strstr(w.c_str(), "fpt_mmlt_init") && std::strstr(w.c_str(), word); };
 		{ fpt_mmlt_options p = mo; p.mlt.bpt.use_vpls = 1; CHECK(names(p, 1024, false, "use_vpls")); }
 		CHECK(names(mo, 1600 * 900, true, "pixels"));
 		{ fpt_mmlt_options p = mo; p.mlt.n_chains = 0; CHECK(names(p, 1024, false, "n_chains")); }
@@ -108,8 +110,8 @@ int main()
 		{ fpt_mmlt_options p = mo; p.mlt.n_chains = 1; p.mlt.spp = 0xFFFFFFFFu; CHECK(names(p, 0xFFFFFFu, false, "32 bits")); }
 		{ fpt_mmlt_options p = mo; p.mlt.bpt.max_path_length = 16; CHECK(names(p, 1600 * 900, false, "max_path_length")); }
 		// the technique table: 21 cells per pixel at L = 6, 120 at L = 15; refused from 2^32 cells on
-		{ fpt_mmlt_options p = mo; p.mlt.bpt.max_path_length = 15; CHECK(names(p, 40000u * 1000u, false, "technique table")); CHECK(mmlt_refusal(p, 35791394u, false) == nullptr); CHECK(names(p, 35791395u, false, "32 bits")); }
-		{ fpt_mmlt_options p = mo; CHECK(mmlt_refusal(p, 0xFFFFFFu, false) == nullptr); }
+		{ fpt_mmlt_options p = mo; p.mlt.bpt.max_path_length = 15; CHECK(names(p, 40000u * 1000u, false, "technique table")); CHECK(mmlt_refusal(p, 35791394u, false).empty()); CHECK(names(p, 35791395u, false, "32 bits")); }
+		{ fpt_mmlt_options p = mo; CHECK(mmlt_refusal(p, 0xFFFFFFu, false).empty()); }
 	}
 	std::printf(failures ? "%d check(s) failed\n" : "mlt host helpers (pssmlt and mmlt): all checks passed\n", failures);
 	return failures ? 1 : 0;

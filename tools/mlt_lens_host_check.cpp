@@ -79,9 +79,9 @@ int main()
 		fpt_mmlt_options mo; std::memset(&mo, 0, sizeof(mo));
 		mo.mlt.bpt.max_path_length = 6; mo.mlt.n_chains = 64 * 1024; mo.mlt.spp = 4; mo.mlt.light_perturbations = mo.mlt.eye_perturbations = 1; mo.mlt.radius = 0.01f;
 		mo.mmlt_frequency = 2; mo.lens_techniques = 1;
-		CHECK(mmlt_refusal(mo, 1600 * 900, false) == nullptr);
+		CHECK(mmlt_refusal(mo, 1600 * 900, false).empty());
 		auto names = [&](const fpt_mmlt_options& p, uint32_t n_pixels, bool sharded, const char* word)
-		{ const char* w = mmlt_refusal(p, n_pixels, sharded); return w && std::strstr(w, "fpt_mmlt_init") && std::strstr(w, word); };
+		{ const std::string w = mmlt_refusal(p, n_pixels, sharded); return std::strstr(w.c_str(), "fpt_mmlt_init") && std::strstr(w.c_str(), word); };
 		{ fpt_mmlt_options p = mo; p.mlt.bpt.use_vpls = 1; CHECK(names(p, 1024, false, "use_vpls")); }
 		CHECK(names(mo, 1024, true, "pixels"));
 		{ fpt_mmlt_options p = mo; p.mlt.n_chains = 0; CHECK(names(p, 1024, false, "n_chains")); }
@@ -92,13 +92,13 @@ int main()
 		// L = 15: 120 cells per pixel without, 134 with the lens block -- floor((2^32 - 1) / 134) = 32051994 pixels fit, one more does not; 120 cells still fit there
 		{
 			fpt_mmlt_options p = mo; p.mlt.bpt.max_path_length = 15;
-			CHECK(mmlt_refusal(p, 32051994u, false) == nullptr);
+			CHECK(mmlt_refusal(p, 32051994u, false).empty());
 			CHECK(names(p, 32051995u, false, "technique table") && names(p, 32051995u, false, "32 bits") && names(p, 32051995u, false, "lens_techniques"));
 			p.lens_techniques = 0;
-			CHECK(mmlt_refusal(p, 32051995u, false) == nullptr && mmlt_refusal(p, 35791394u, false) == nullptr && names(p, 35791395u, false, "technique table"));
+			CHECK(mmlt_refusal(p, 32051995u, false).empty() && mmlt_refusal(p, 35791394u, false).empty() && names(p, 35791395u, false, "technique table"));
 		}
 		// L = 1 with the switch on is legal and adds nothing
-		{ fpt_mmlt_options p = mo; p.mlt.bpt.max_path_length = 1; CHECK(mmlt_refusal(p, 1600 * 900, false) == nullptr && mlt_tech_count(1, true) == 1u); }
+		{ fpt_mmlt_options p = mo; p.mlt.bpt.max_path_length = 1; CHECK(mmlt_refusal(p, 1600 * 900, false).empty() && mlt_tech_count(1, true) == 1u); }
 	}
 	std::printf(failures ? "%d check(s) failed\n" : "mlt lens host helpers (mmlt, lens_techniques = 1): all checks passed\n", failures);
 	return failures ? 1 : 0;
