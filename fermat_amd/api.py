@@ -209,7 +209,8 @@ ENTRY_POINTS = ["fpt_create", "fpt_destroy", "fpt_last_error", "fpt_stream", "fp
                 "fpt_debug_psf", "fpt_psfpt_debug_set_table_log2", "fpt_debug_bpt", "fpt_debug_frame",
                 "fpt_pssmlt_init", "fpt_pssmlt_render", "fpt_pssmlt_get_stats", "fpt_pssmlt_download", "fpt_pssmlt_debug_eval", "fpt_debug_mlt", "fpt_debug_device_build",
                 "fpt_mmlt_init", "fpt_mmlt_render", "fpt_mmlt_get_stats", "fpt_mmlt_get_st_norms", "fpt_mmlt_download", "fpt_mmlt_debug_eval",
-                "fpt_mmlt_download_pixels", "fpt_mmlt_debug_eval_pixels", "fpt_debug_bpt_splat_entries"]
+                "fpt_mmlt_download_pixels", "fpt_mmlt_debug_eval_pixels", "fpt_debug_bpt_splat_entries",
+                "fpt_mlt_set_persistence", "fpt_mlt_restart_chains", "fpt_mlt_get_persistence"]
 
 # fpt_debug_device_build: the arrays of the last device build, by their `which` (name -> (which, dtype, columns)); rows: n triangles, n - 1 binary nodes or the wide nodes
 LBVH_CELL_DTYPE = np.dtype([("c", "<f4", 7), ("k", "u1", 7), ("k8", "u1"), ("leaf", "u1"), ("count", "u1"), ("spare", "u1", 2)])
@@ -668,6 +669,22 @@ class Renderer:
         self._check(self.L.fpt_mmlt_debug_eval(self.ctx, C.byref(self.view), C.c_uint32(n), C.c_void_p(light_u.ctypes.data), C.c_void_p(eye_u.ctypes.data), C.c_void_p(st.ctypes.data),
                                                C.c_void_p(out.ctypes.data), C.byref(rays)))
         return (out, int(rays.value)) if with_rays else out
+
+    # -- chains that persist across render calls, either Metropolis renderer (fpt_mlt_set_persistence, include/fermat_pt_hip.h)
+    def mlt_set_persistence(self, reseeding, startup_skips=0):
+        """a render call reseeds when there are no live chains or instance % reseeding == 0 and continues the chains otherwise; the first startup_skips steps of a
+        reseeding call deposit nothing.  Drops live chains"""
+        self._check(self.L.fpt_mlt_set_persistence(self.ctx, C.c_uint32(reseeding), C.c_uint32(startup_skips)))
+
+    def mlt_restart_chains(self):
+        """drops live chains (after an edit the library cannot see: materials or textures changed in place on the device): the next render call reseeds"""
+        self._check(self.L.fpt_mlt_restart_chains(self.ctx))
+
+    def mlt_persistence(self):
+        """dict(reseeding, startup_skips (as clamped), last_call_reseeded, calls_since_reseed)"""
+        v = [C.c_uint32() for _ in range(4)]
+        self._check(self.L.fpt_mlt_get_persistence(self.ctx, *[C.byref(x) for x in v]))
+        return dict(zip(("reseeding", "startup_skips", "last_call_reseeded", "calls_since_reseed"), (int(x.value) for x in v)))
 
     def debug_mlt(self, op, arrays, params=(), n=None):
         """fpt_debug_mlt (layouts: include/fermat_pt_hip.h); arguments and result as debug_bpt's"""

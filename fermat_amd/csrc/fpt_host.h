@@ -394,8 +394,13 @@ struct fpt_context
 	//   3. Nothing left over.  A successful init leaves allocated only what its mode uses: an init starts with reset(), and allocate() walks each_array(), where an array
 	//      the mode does not use has no elements.
 	//   4. Readers check first.  Everything that reads the state checks `mode` first (state_in, fpt_mlt_api.cpp): render, get_stats, get_st_norms, download,
-	//      download_pixels and debug_eval of both families, each answering "<its init> has not been called" in any other mode.
+	//      download_pixels and debug_eval of both families, each answering "<its init> has not been called" in any other mode; fpt_mlt_set_persistence, _restart_chains and
+	//      _get_persistence (any_mode) in either mode.
 	//   5. reset() is the only way to invalidate the state: fpt_bpt_init, which replaces the bidirectional state under it, calls it.
+	//   6. Live chains (fpt_mlt_set_persistence).  `live` implies that the chain arrays (coordinates, path_value, path_pdf, rejections, st, path_pixel) hold the
+	//      state the last render call left, that the table, seeds, st_norms and st_chains are those of the period's reseed, and that period_brightness, period_camera,
+	//      period_res and period_scene describe that reseed.  Only a render call that ran its chain loop sets it; drop_chains() and reset() clear it, and a call that finds the
+	//      scene's generation (a geometry build or refit, an emitter-table replace), the view's camera or its resolution changed treats the chains as not live.
 	struct MltState
 	{
 		enum Mode : uint32_t { None, Pssmlt, Mmlt };
@@ -417,6 +422,12 @@ struct fpt_context
 		fpt::DeviceArray<uint32_t> table_pixel, new_pixel, path_pixel;     // lens: the pixel of the lens block's cells, of every chain's proposal and of its current state
 		std::vector<float> st_norms; std::vector<uint32_t> st_chains;      // Mmlt: (L+2)^2 each, s + t * (L+2)
 		fpt_mmlt_stats stats{};                                            // of the last render call; fpt_pssmlt_stats is its leading part
+		// chains that persist across render calls (invariant 6): a call reseeds when the chains are not live or instance % reseeding == 0; startup_skips is kept clamped
+		uint32_t reseeding = 1, startup_skips = 0, calls_since_reseed = 0;
+		bool live = false, last_call_reseeded = false;
+		float period_brightness = 0.0f;                                    // image_brightness of the period's reseed
+		fpt_camera period_camera{}; uint32_t period_res[2] = { 0, 0 }; uint64_t period_scene = 0;
+		void drop_chains() { live = false; calls_since_reseed = 0; period_brightness = 0.0f; }
 		uint32_t dims() const { return (opt.bpt.max_path_length + 1u) * 3u; }      // coordinates per chain and side
 		// the list: v(array, its elements in mode `of` for the shape above, the byte it is cleared with).  new_value and the coordinates hold max(n_pixels, n_chains)
 		// entries (debug_eval takes that many sets); the lens block's pixel plane keeps one entry at L = 1, where the block is empty.  The list's order is the order
@@ -438,6 +449,7 @@ struct fpt_context
 			mode = None; lens = false; opt = fpt_pssmlt_options{}; n_pixels = n_chains = chain_length = mmlt_frequency = n_tech = 0; scan_bytes = 0;
 			each_array(None, [](auto& a, size_t, int) { a.release(); });
 			st_norms.clear(); st_chains.clear(); stats = fpt_mmlt_stats{};
+			reseeding = 1; startup_skips = 0; last_call_reseeded = false; period_camera = fpt_camera{}; period_res[0] = period_res[1] = 0; period_scene = 0; drop_chains();
 		}
 	} mlt;
 	bool profiling = false;

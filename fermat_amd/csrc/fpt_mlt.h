@@ -23,6 +23,8 @@ struct MltChains
 	// eye coordinates 3 and 4", any other value is the pixel itself (a t = 1 state: where its lens connection landed).  path_pixel is committed with the value on
 	// acceptance and kept on rejection.  A proposal that carries a pixel arrives as c (the table's cell) and counts as c * light_weight, light_weight = 1 / (res_x res_y)
 	const uint32_t* new_pixel; uint32_t* path_pixel;
+	// 0: a skipped step of a reseeding call (startup_skips, cmlt.cu:1110): the acceptance test, the commit, `rejections` and the counters as ever, but nothing is deposited
+	uint32_t accumulate;
 };
 
 // Largest single value of the seed CDF: a path value above 2^31 counts 2^31 (its integer is 2^63, the largest a uint64 sum can take once)

@@ -121,8 +121,9 @@ __global__ void __launch_bounds__(MLT_BLOCK) accept_reject_kernel(const MltChain
 				if (q) atomicAdd(reinterpret_cast<unsigned long long*>(C.splat + size_t(pixel) * 3 + k), (unsigned long long)q);
 			}
 		};
-		if (old_pdf > 0) splat(old_pixel, C.pdf_norm * (1.0f - ar), C.path_value[chain], old_pdf);
-		if (new_pdf > 0) splat(new_pixel, C.pdf_norm * ar, w, new_pdf);
+		// (a skipped step of a reseeding call deposits nothing: MltChains::accumulate)
+		if (C.accumulate && old_pdf > 0) splat(old_pixel, C.pdf_norm * (1.0f - ar), C.path_value[chain], old_pdf);
+		if (C.accumulate && new_pdf > 0) splat(new_pixel, C.pdf_norm * ar, w, new_pdf);
 		if (mlt_mutation_number(C.instance, C.step, chain, dims * 2u) * old_pdf < new_pdf)
 		{
 			C.path_value[chain] = w;

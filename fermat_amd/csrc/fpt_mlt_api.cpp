@@ -8,7 +8,11 @@
 // and every chain step evaluates the whole path; `-mmlt` sinks it into the table by technique (TechTable) and every chain step evaluates the chain's one (s, t) technique
 // (ChainTech); with lens_techniques = 1 the table has the lens block (s, 1), s in [2, L], after the others and a pixel plane beside it, and the chains keep the pixel of their
 // state.  Read-backs per call: the seed CDF at the ends of the table's blocks (st_norms and the total, which the normalisation needs on the host: the reference synchronises
-// there as well, pssmlt.cu:531) and at the end the counters (`-mmlt`: and the chains seeded per technique).  Every call reseeds.
+// there as well, pssmlt.cu:531) and at the end the counters (`-mmlt`: and the chains seeded per technique).
+// By default every call reseeds.  With fpt_mlt_set_persistence(reseeding = R > 1) the chains stay alive (MltState, invariant 6): a call whose instance is no multiple of R and
+// that finds live chains CONTINUES them -- rescale, the chain loop with a real mutation at step 0, resolve, the counters' read-back; no presampling pass, no CDF, no seeds, no
+// read-back before the loop -- under the normalisation of the period's reseed (CMLTOptions::reseeding, cmlt.cu:1013-1016; the reference's PSSMLT has no such option: it gets
+// one here because the render loop is shared).  startup_skips = K: the first K steps of a reseeding call deposit nothing (cmlt.cu:1097,1110).
 // Out of scope: passes in flight, deferral, tile sharding / multi-GPU, use_vpls, charted swaps.
 #include "fpt_host.h"
 #include "fpt_mlt.h"
@@ -25,6 +29,8 @@ void need(bool ok, const char* who, const char* what, const char* more = "") { i
 const char* init_of(Mlt::Mode mode) { return mode == Mlt::Mmlt ? "fpt_mmlt_init" : "fpt_pssmlt_init"; }
 // "readers check first" (MltState): entry point `who` of the family of `mode` gets the state only in that mode
 Mlt& state_in(fpt_context* ctx, Mlt::Mode mode, const char* who) { need(ctx->mlt.mode == mode, who, init_of(mode), " has not been called"); return ctx->mlt; }
+// ... and `who` of both families (fpt_mlt_*) gets it in either mode
+Mlt& any_mode(fpt_context* ctx, const char* who) { need(ctx->mlt.mode != Mlt::None, who, "fpt_pssmlt_init / fpt_mmlt_init", " has not been called"); return ctx->mlt; }
 template <typename A> void zero(A& a, size_t n, hipStream_t s) { if (n) FPT_HIP_CHECK(hipMemsetAsync(a.ptr, 0, n * sizeof(*a.ptr), s)); }
 
 ChainCoords chain_view(Mlt& m, uint32_t n, uint32_t step, uint32_t mutation)
@@ -66,6 +72,14 @@ void init(fpt_context* ctx, const fpt_pssmlt_options& opts, uint32_t mmlt_freque
 	catch (...) { m.reset(); if (bpt_made) ctx->bpt.ready = false; throw; }
 }
 
+// MltState, invariant 6: do the chain arrays hold chains this call may continue?  Not after a geometry build or refit or an emitter-table replace (the scene's generation
+// moved), nor under another camera or resolution than the period's reseed saw (compared bytewise)
+bool chains_live(fpt_context* ctx, const Mlt& m, const fpt_rendering_context_view* view)
+{
+	return m.live && m.period_scene == ctx->scene.value && std::memcmp(&m.period_camera, &view->camera, sizeof(fpt_camera)) == 0 &&
+	       m.period_res[0] == view->res_x && m.period_res[1] == view->res_y;
+}
+
 // one render call of either renderer: PSSMLT::render (pssmlt.cu:541-700); CMLT::render (cmlt.cu:983-1190) without charted swaps
 void render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view, Mlt::Mode mode, const char* who)
 {
@@ -79,56 +93,73 @@ void render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_vie
 	const bool mmlt = mode == Mlt::Mmlt, lens = m.lens;
 	const uint32_t n_pixels = m.n_pixels, n_chains = m.n_chains, L = m.opt.bpt.max_path_length, n_tech = m.n_tech, n_cells = n_tech * n_pixels, W = L + 2u;
 	const FrameBufferDev fb = fb_dev(view->fb);
+	// does this call continue the chains the last one left?  (MltState, invariant 6.)  Whatever happens below, they are live again only once the chain loop has run
+	const bool continuing = !mlt_call_reseeds(instance, m.reseeding, chains_live(ctx, m, view));
+	m.live = false; m.last_call_reseeded = !continuing;
 	// pre-multiply the previous frame for blending
 	launch_rescale(fb, nullptr, n_pixels, float(instance) / float(instance + 1), s);
-	// the BPT presampling pass over the tiled coordinates: `-pssmlt` sums every eye path's samples into the path's cell, `-mmlt` puts every sample into the cell of its technique
-	zero(m.table, n_cells, s);
-	if (lens && L > 1u) FPT_HIP_CHECK(hipMemsetAsync(m.table_pixel.ptr, 0xFF, size_t(L - 1u) * n_pixels * sizeof(uint32_t), s));
-	BptParams tiled;
-	const TechTable table = { m.table.ptr, lens ? m.table_pixel.ptr : nullptr };
-	if (mmlt) bpt_sample_paths(ctx, instance, view, 0u, nullptr, nullptr, &tiled, &table, nullptr);
-	else bpt_sample_paths(ctx, instance, view, 0u, nullptr, m.table.ptr, &tiled);
-	// resample the seeds for our chains to remove startup bias.  One CDF over all cells: `-mmlt`'s seeds are single connections, drawn in proportion to their value whatever
-	// their technique (a lens cell holds c, the sample before the multiplication by light_weight = 1 / n_pixels; what it adds to the frame, and so what it counts here, is
-	// c * light_weight).  `-pssmlt` jitters every stratum on its own; `-mmlt` takes one offset for all strata (mlt_seed_target)
-	launch_mlt_seed_cdf(m.table.ptr, n_cells, m.q.ptr, m.cdf.ptr, m.scan_scratch.ptr, m.scan_scratch.count, s, lens ? mlt_tech_count(L) * n_pixels : n_cells, 1.0f / float(n_pixels));
-	launch_mlt_sample_seeds(m.cdf.ptr, n_cells, n_chains, m.seeds.ptr, s, mmlt ? int(mlt_seed_offset(instance)) : -1);
-	// the CDF at the ends of the techniques' blocks; `-pssmlt`'s one block ends where the CDF does, and is read from there
-	const unsigned long long* d_ends = m.cdf.ptr + (n_cells - 1u);
-	if (mmlt) { launch_mmlt_block_ends(m.cdf.ptr, n_tech, n_pixels, m.ends.ptr, s); d_ends = m.ends.ptr; }
-	FPT_HIP_CHECK(hipGetLastError());
-	std::vector<unsigned long long> ends(n_tech, 0ull);
-	FPT_HIP_CHECK(hipMemcpyAsync(ends.data(), d_ends, n_tech * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-	FPT_HIP_CHECK(hipStreamSynchronize(s));
-	const unsigned long long total = ends[n_tech - 1u];
 	fpt_mmlt_stats& st = m.stats;
-	std::memset(&st, 0, sizeof(st));
-	st.n_chains = n_chains; st.chain_length = m.chain_length;
-	st.image_brightness = mlt_image_brightness(total, n_pixels);
-	st.pdf_norm = mlt_pdf_norm(st.image_brightness, n_pixels, m.chain_length, n_chains);
-	if (mmlt)
+	if (continuing)
 	{
-		// the st_norms: exact, as the CDF is an integer
-		m.st_norms.assign(size_t(W) * W, 0.0f); m.st_chains.assign(size_t(W) * W, 0u);
-		for (uint32_t k = 0; k < n_tech; ++k)
+		// statistics are per call; the brightness, st_norms, st_chains, the table and the seeds stay those of the period's reseed
+		std::memset(&st, 0, sizeof(st));
+		st.n_chains = n_chains; st.chain_length = m.chain_length;
+		st.image_brightness = m.period_brightness;
+		st.pdf_norm = mlt_pdf_norm(st.image_brightness, n_pixels, mlt_accumulated_steps(m.chain_length, m.startup_skips, false), n_chains);
+	}
+	else
+	{
+		m.drop_chains();
+		BptParams tiled;
+		// the BPT presampling pass over the tiled coordinates: `-pssmlt` sums every eye path's samples into the path's cell, `-mmlt` puts every sample into the cell of its technique
+		zero(m.table, n_cells, s);
+		if (lens && L > 1u) FPT_HIP_CHECK(hipMemsetAsync(m.table_pixel.ptr, 0xFF, size_t(L - 1u) * n_pixels * sizeof(uint32_t), s));
+		const TechTable table = { m.table.ptr, lens ? m.table_pixel.ptr : nullptr };
+		if (mmlt) bpt_sample_paths(ctx, instance, view, 0u, nullptr, nullptr, &tiled, &table, nullptr);
+		else bpt_sample_paths(ctx, instance, view, 0u, nullptr, m.table.ptr, &tiled);
+		// resample the seeds for our chains to remove startup bias.  One CDF over all cells: `-mmlt`'s seeds are single connections, drawn in proportion to their value whatever
+		// their technique (a lens cell holds c, the sample before the multiplication by light_weight = 1 / n_pixels; what it adds to the frame, and so what it counts here, is
+		// c * light_weight).  `-pssmlt` jitters every stratum on its own; `-mmlt` takes one offset for all strata (mlt_seed_target)
+		launch_mlt_seed_cdf(m.table.ptr, n_cells, m.q.ptr, m.cdf.ptr, m.scan_scratch.ptr, m.scan_scratch.count, s, lens ? mlt_tech_count(L) * n_pixels : n_cells, 1.0f / float(n_pixels));
+		launch_mlt_sample_seeds(m.cdf.ptr, n_cells, n_chains, m.seeds.ptr, s, mmlt ? int(mlt_seed_offset(instance)) : -1);
+		// the CDF at the ends of the techniques' blocks; `-pssmlt`'s one block ends where the CDF does, and is read from there
+		const unsigned long long* d_ends = m.cdf.ptr + (n_cells - 1u);
+		if (mmlt) { launch_mmlt_block_ends(m.cdf.ptr, n_tech, n_pixels, m.ends.ptr, s); d_ends = m.ends.ptr; }
+		FPT_HIP_CHECK(hipGetLastError());
+		std::vector<unsigned long long> ends(n_tech, 0ull);
+		FPT_HIP_CHECK(hipMemcpyAsync(ends.data(), d_ends, n_tech * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+		FPT_HIP_CHECK(hipStreamSynchronize(s));
+		const unsigned long long total = ends[n_tech - 1u];
+		std::memset(&st, 0, sizeof(st));
+		st.n_chains = n_chains; st.chain_length = m.chain_length;
+		st.image_brightness = mlt_image_brightness(total, n_pixels);
+		// (the steps that deposit: all but the startup_skips of this reseeding call, cmlt.cu:1097)
+		st.pdf_norm = mlt_pdf_norm(st.image_brightness, n_pixels, mlt_accumulated_steps(m.chain_length, m.startup_skips, true), n_chains);
+		if (mmlt)
 		{
-			const uint32_t w = mlt_tech_st(k, L, lens);
-			m.st_norms[(w & 0xFFu) + (w >> 8) * W] = mlt_image_brightness(ends[k] - (k ? ends[k - 1] : 0ull), n_pixels);
+			// the st_norms: exact, as the CDF is an integer
+			m.st_norms.assign(size_t(W) * W, 0.0f); m.st_chains.assign(size_t(W) * W, 0u);
+			for (uint32_t k = 0; k < n_tech; ++k)
+			{
+				const uint32_t w = mlt_tech_st(k, L, lens);
+				m.st_norms[(w & 0xFFu) + (w >> 8) * W] = mlt_image_brightness(ends[k] - (k ? ends[k - 1] : 0ull), n_pixels);
+			}
 		}
+		if (total == 0) return;          // a black frame: no sample to start a chain from, the frame is only rescaled
+		// the path whose coordinates start each chain: `-pssmlt`'s seed itself; `-mmlt`'s seed is a cell, which gives the chain its technique as well
+		const uint32_t* path_seeds = m.seeds.ptr;
+		if (mmlt)
+		{
+			zero(m.tech_chains, n_tech, s);
+			launch_mmlt_start_chains(m.seeds.ptr, n_chains, n_pixels, L, m.st.ptr, m.path_seeds.ptr, m.tech_chains.ptr, s, lens);
+			path_seeds = m.path_seeds.ptr;
+		}
+		// recover the primary coordinates of the selected seed paths
+		launch_mlt_recover_coordinates(tiled, path_seeds, n_chains, m.light_u.ptr, m.eye_u.ptr, s);
+		// initialize the initial path pdfs and the rejection counters to zero
+		zero(m.path_pdf, n_chains, s); zero(m.rejections, n_chains, s);
 	}
-	if (total == 0) return;          // a black frame: no sample to start a chain from, the frame is only rescaled
-	// the path whose coordinates start each chain: `-pssmlt`'s seed itself; `-mmlt`'s seed is a cell, which gives the chain its technique as well
-	const uint32_t* path_seeds = m.seeds.ptr;
-	if (mmlt)
-	{
-		zero(m.tech_chains, n_tech, s);
-		launch_mmlt_start_chains(m.seeds.ptr, n_chains, n_pixels, L, m.st.ptr, m.path_seeds.ptr, m.tech_chains.ptr, s, lens);
-		path_seeds = m.path_seeds.ptr;
-	}
-	// recover the primary coordinates of the selected seed paths
-	launch_mlt_recover_coordinates(tiled, path_seeds, n_chains, m.light_u.ptr, m.eye_u.ptr, s);
-	// initialize the initial path pdfs and the rejection counters to zero
-	zero(m.path_pdf, n_chains, s); zero(m.rejections, n_chains, s); zero(m.counts, 2, s);
+	zero(m.counts, 2, s);
 	MltChains C; std::memset(&C, 0, sizeof(C));
 	C.light_u = m.light_u.ptr; C.eye_u = m.eye_u.ptr; C.new_value = m.new_value.ptr; C.path_value = m.path_value.ptr; C.path_pdf = m.path_pdf.ptr; C.rejections = m.rejections.ptr;
 	C.splat = b.splat_ptr(); C.counts = m.counts.ptr;
@@ -144,8 +175,8 @@ void render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_vie
 	}
 	if (lens)
 	{
-		// no chain has a state yet: its pixel is committed with the first accepted proposal (step 0 for a seed)
-		FPT_HIP_CHECK(hipMemsetAsync(m.path_pixel.ptr, 0xFF, n_chains * sizeof(uint32_t), s));
+		// a reseeding call: no chain has a state yet, its pixel is committed with the first accepted proposal (step 0 for a seed)
+		if (!continuing) FPT_HIP_CHECK(hipMemsetAsync(m.path_pixel.ptr, 0xFF, n_chains * sizeof(uint32_t), s));
 		C.new_pixel = m.new_pixel.ptr; C.path_pixel = m.path_pixel.ptr;
 		fixed.new_pixel = m.new_pixel.ptr;
 	}
@@ -153,9 +184,10 @@ void render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_vie
 	for (uint32_t l = 0; l < m.chain_length; ++l)
 	{
 		// a swap step (`-mmlt` with mmlt_frequency > 0) keeps the coordinates and proposes another technique of the same path length; any other step disables any kind of
-		// mutations at step 0 and enables them later on, `-mmlt` on the chain's own technique
+		// mutations at step 0 and enables them later on, `-mmlt` on the chain's own technique.  Step 0 of a continuing call is a real mutation (cmlt.cu:1107); the swap
+		// steps are counted per call (cmlt.cu:1118)
 		const bool swap = mlt_is_swap_step(m.mmlt_frequency, l);
-		const uint32_t mutation = swap ? 0u : mlt_mutation_type(m.opt.independent_samples, instance, l);
+		const uint32_t mutation = swap ? 0u : mlt_mutation_type(m.opt.independent_samples, instance, l, continuing);
 		if (swap) launch_mmlt_swap(m.st.ptr, m.st_new.ptr, n_chains, L, instance, l, s, lens);
 		// reset the new path values
 		zero(m.new_value, n_chains, s);
@@ -164,22 +196,31 @@ void render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_vie
 		fixed.st = swap ? m.st_new.ptr : m.st.ptr;
 		bpt_sample_paths(ctx, instance, view, n_chains, &chain, m.new_value.ptr, nullptr, nullptr, mmlt ? &fixed : nullptr);
 		// and perform the usual acceptance-rejection step
-		C.step = l; C.mutation = mutation; C.swap = swap ? 1u : 0u;
+		// (the first startup_skips steps of a reseeding call deposit nothing, cmlt.cu:1110; a continuing call's chains are burnt in: every step deposits)
+		C.step = l; C.mutation = mutation; C.swap = swap ? 1u : 0u; C.accumulate = continuing || l >= m.startup_skips ? 1u : 0u;
 		launch_mlt_accept_reject(C, s);
 	}
 	launch_mlt_resolve(fb.ch[FPT_FB_COMPOSITED_C], b.splat_ptr(), n_pixels, s);
 	FPT_HIP_CHECK(hipGetLastError());
 	unsigned long long counts[2] = { 0, 0 }, mcounts[3] = { 0, 0, 0 };
-	std::vector<uint32_t> tech_chains(mmlt ? n_tech : 0u, 0u);
+	std::vector<uint32_t> tech_chains(mmlt && !continuing ? n_tech : 0u, 0u);          // (the chains seeded per technique are the reseed's)
 	FPT_HIP_CHECK(hipMemcpyAsync(counts, m.counts.ptr, sizeof(counts), hipMemcpyDeviceToHost, s));
 	if (mmlt)
 	{
 		FPT_HIP_CHECK(hipMemcpyAsync(mcounts, m.mcounts.ptr, sizeof(mcounts), hipMemcpyDeviceToHost, s));
-		FPT_HIP_CHECK(hipMemcpyAsync(tech_chains.data(), m.tech_chains.ptr, n_tech * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+		if (!tech_chains.empty()) FPT_HIP_CHECK(hipMemcpyAsync(tech_chains.data(), m.tech_chains.ptr, n_tech * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
 	}
 	FPT_HIP_CHECK(hipStreamSynchronize(s));
 	st.accepted = counts[0]; st.rejected = counts[1]; st.swaps_proposed = mcounts[0]; st.swaps_accepted = mcounts[1]; st.rays = mcounts[2];
 	for (size_t k = 0; k < tech_chains.size(); ++k) { const uint32_t w = mlt_tech_st(uint32_t(k), L, lens); m.st_chains[(w & 0xFFu) + (w >> 8) * W] = tech_chains[k]; }
+	// the chains are live (MltState, invariant 6); a reseed opens the period the next calls are checked against
+	if (!continuing)
+	{
+		m.period_brightness = st.image_brightness; m.period_camera = view->camera; m.period_res[0] = view->res_x; m.period_res[1] = view->res_y; m.period_scene = ctx->scene.value;
+		m.calls_since_reseed = 0;
+	}
+	else ++m.calls_since_reseed;
+	m.live = true;
 }
 
 // the state the last render call left (any pointer may be NULL): the chains' arrays and the table; h_st for `-mmlt` alone
@@ -265,6 +306,30 @@ int fpt_pssmlt_render(fpt_context* ctx, uint32_t instance, const fpt_rendering_c
 int fpt_mmlt_render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view)
 { return guarded(ctx, [&] { flush_deferred(ctx); render(ctx, instance, view, Mlt::Mmlt, "fpt_mmlt_render"); }); }
 
+// chains that persist across render calls: the three calls of either Metropolis mode, after the mode's init
+int fpt_mlt_set_persistence(fpt_context* ctx, uint32_t reseeding, uint32_t startup_skips)
+{
+	return guarded(ctx, [&] {
+		Mlt& m = any_mode(ctx, "fpt_mlt_set_persistence");
+		const std::string refusal = mlt_persistence_refusal(reseeding);
+		if (!refusal.empty()) throw std::runtime_error(refusal);
+		m.reseeding = reseeding; m.startup_skips = mlt_clamp_skips(startup_skips, m.chain_length);
+		m.drop_chains();
+	});
+}
+int fpt_mlt_restart_chains(fpt_context* ctx)
+{ return guarded(ctx, [&] { any_mode(ctx, "fpt_mlt_restart_chains").drop_chains(); }); }
+int fpt_mlt_get_persistence(fpt_context* ctx, uint32_t* reseeding, uint32_t* startup_skips, uint32_t* last_call_reseeded, uint32_t* calls_since_reseed)
+{
+	return guarded(ctx, [&] {
+		const Mlt& m = any_mode(ctx, "fpt_mlt_get_persistence");
+		if (reseeding) *reseeding = m.reseeding;
+		if (startup_skips) *startup_skips = m.startup_skips;
+		if (last_call_reseeded) *last_call_reseeded = m.last_call_reseeded ? 1u : 0u;
+		if (calls_since_reseed) *calls_since_reseed = m.calls_since_reseed;
+	});
+}
+
 int fpt_pssmlt_get_stats(fpt_context* ctx, fpt_pssmlt_stats* out)
 {
 	return guarded(ctx, [&] {
@@ -315,8 +380,8 @@ int fpt_mmlt_debug_eval_pixels(fpt_context* ctx, const fpt_rendering_context_vie
 int fpt_debug_mlt(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_params, uint32_t n_params, void* const* h_arrays, uint32_t n_arrays)
 {
 	return guarded(ctx, [&] {
-		static const uint32_t want_params[5] = { 4, 1, 10, 1, 3 }, want_arrays[5] = { 6, 3, 10, 3, 4 };
-		require(op >= 0 && op <= 4, "fpt_debug_mlt: unknown op");
+		static const uint32_t want_params[6] = { 4, 1, 10, 1, 3, 11 }, want_arrays[6] = { 6, 3, 10, 3, 4, 10 };
+		require(op >= 0 && op <= 5, "fpt_debug_mlt: unknown op");
 		require(n_params == want_params[op] && n_arrays == want_arrays[op] && h_arrays && h_params, "fpt_debug_mlt: wrong number of parameters or arrays for this op");
 		flush_deferred(ctx);
 		hipStream_t s = ctx->stream;
@@ -354,7 +419,7 @@ int fpt_debug_mlt(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_params
 			C.radius = as_f32(h_params[6]); C.pdf_norm = as_f32(h_params[7]); C.res_x = h_params[8]; C.res_y = h_params[9];
 			require(n >= 1 && C.max_path_length >= 1 && C.max_path_length <= 15 && C.mutation <= 2u && C.res_x >= 1 && C.res_y >= 1 && uint64_t(C.res_x) * C.res_y < (1ull << 24),
 			        "fpt_debug_mlt: accept/reject: n, max_path_length (1..15), mutation (0..2) or resolution out of range");
-			C.n_chains = n;
+			C.n_chains = n; C.accumulate = op == 5 ? (h_params[10] ? 1u : 0u) : 1u;
 			C.light_u = static_cast<float*>(arr(0)); C.eye_u = static_cast<float*>(arr(1)); C.new_value = static_cast<const float4*>(arr(2)); C.path_value = static_cast<float4*>(arr(3));
 			C.path_pdf = static_cast<float*>(arr(4)); C.rejections = static_cast<uint32_t*>(arr(5)); C.splat = static_cast<long long*>(arr(6)); C.counts = static_cast<unsigned long long*>(arr(9));
 			const size_t cells = size_t(C.res_x) * C.res_y * 3;

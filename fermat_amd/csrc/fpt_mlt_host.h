@@ -35,6 +35,24 @@ inline uint32_t mlt_mutation_type(float independent_samples, uint32_t instance, 
 	return randfloat(step, hash32(instance + 0x9e3779b9u)) < independent_samples ? 2u : 1u;
 }
 
+// ---- chains that persist across render calls (fpt_mlt_set_persistence; CMLTOptions::reseeding / startup_skips, src/renderers/cmlt.h:62-63) ----
+// does render call `instance` reseed?  With no live chains always; otherwise every `reseeding`-th instance (mlt.cu:213-220, cmlt.cu:1013-1016).  reseeding >= 1
+inline bool mlt_call_reseeds(uint32_t instance, uint32_t reseeding, bool live) { return !live || instance % reseeding == 0u; }
+// the mutation of step `step` of a call that CONTINUES live chains: step 0 is a real mutation (cmlt.cu:1107), chosen by the rule of the later steps applied to step 0
+inline uint32_t mlt_mutation_type(float independent_samples, uint32_t instance, uint32_t step, bool continuing)
+{
+	if (step == 0 && continuing) return randfloat(0u, hash32(instance + 0x9e3779b9u)) < independent_samples ? 2u : 1u;
+	return mlt_mutation_type(independent_samples, instance, step);
+}
+// startup_skips as the renderer keeps it: at most chain_length - 1 (cmlt.cu:824), so that a reseeding call accumulates at least one step
+inline uint32_t mlt_clamp_skips(uint32_t startup_skips, uint32_t chain_length) { return chain_length ? (startup_skips < chain_length - 1u ? startup_skips : chain_length - 1u) : 0u; }
+// the steps of a call that deposit: all of a continuing call (a deviation: the reference skips there too), chain_length - startup_skips of a reseeding one
+// (cmlt.cu:1097); what mlt_pdf_norm takes for its chain_length
+inline uint32_t mlt_accumulated_steps(uint32_t chain_length, uint32_t startup_skips, bool reseeds) { return reseeds ? chain_length - mlt_clamp_skips(startup_skips, chain_length) : chain_length; }
+// why fpt_mlt_set_persistence refuses, or empty
+inline std::string mlt_persistence_refusal(uint32_t reseeding)
+{ return reseeding == 0u ? std::string("fpt_mlt_set_persistence: reseeding must be at least 1 (1: every call reseeds)") : std::string(); }
+
 // ---- the multiplexed renderer (`-mmlt`): one bidirectional technique (s light vertices, t eye vertices) per chain ------------------------------------------
 // With light tracing off the techniques are t in [2, L + 1], s in [0, L + 1 - t]: L (L + 1) / 2 of them, numbered t-major (all techniques of t = 2, s rising, then
 // t = 3, ...): index = sum_{j = 2}^{t - 1} (L + 2 - j) + s.  Shared by the kernels (fpt_bpt.hip, fpt_mlt.hip) and the host.

@@ -378,8 +378,11 @@ static void rebuild_emitters(RenderingContext& renderer, const char* who)
 void HipPathTracer::update_scene(RenderingContext& renderer) { rebuild_emitters(renderer, "PathTracer::update_scene"); }
 void HipPSFPT::update_scene(RenderingContext& renderer) { rebuild_emitters(renderer, "PSFPT::update_scene"); }
 void HipBPT::update_scene(RenderingContext& renderer) { rebuild_emitters(renderer, "BPT::update_scene"); }
-void HipPSSMLT::update_scene(RenderingContext& renderer) { rebuild_emitters(renderer, "PSSMLT::update_scene"); }
-void HipMMLT::update_scene(RenderingContext& renderer) { rebuild_emitters(renderer, "MMLT::update_scene"); }
+// the Metropolis renderers' chains belong to the scene as it was (an edit in place is invisible to the library): the next call reseeds
+void HipPSSMLT::update_scene(RenderingContext& renderer)
+{ rebuild_emitters(renderer, "PSSMLT::update_scene"); check(renderer.get_hip_context(), fpt_mlt_restart_chains(renderer.get_hip_context()), "PSSMLT::update_scene"); }
+void HipMMLT::update_scene(RenderingContext& renderer)
+{ rebuild_emitters(renderer, "MMLT::update_scene"); check(renderer.get_hip_context(), fpt_mlt_restart_chains(renderer.get_hip_context()), "MMLT::update_scene"); }
 
 void HipPathTracer::render(const uint32 instance, RenderingContext& renderer)
 {
@@ -556,6 +559,18 @@ static void parse_pssmlt_options(int argc, char** argv, fpt_pssmlt_options& p)
 		else if (is("-independent-samples") || is("-independent") || is("-is")) p.independent_samples = float(std::atof(argv[++i]));
 	}
 }
+// -reseeding R (the reference's -rf as well, CMLTOptions::reseeding) and -startup-skips K: fpt_mlt_set_persistence after the init.  The default stays R = 1, every call
+// reseeds (the reference's CMLT defaults to 8; its PSSMLT has no such option and gets one here because the render loop is shared)
+static void set_mlt_persistence(int argc, char** argv, fpt_context* ctx, const char* who)
+{
+	uint32 reseeding = 1, skips = 0;
+	for (int i = 0; i + 1 < argc; ++i)
+	{
+		if (std::strcmp(argv[i], "-reseeding") == 0 || std::strcmp(argv[i], "-rf") == 0) reseeding = uint32(std::atoi(argv[++i]));
+		else if (std::strcmp(argv[i], "-startup-skips") == 0) skips = uint32(std::atoi(argv[++i]));
+	}
+	if (reseeding != 1 || skips != 0) check(ctx, fpt_mlt_set_persistence(ctx, reseeding, skips), who);
+}
 void HipPSSMLT::init(int argc, char** argv, RenderingContext& renderer)
 {
 	fpt_pssmlt_options& p = m_options;
@@ -565,6 +580,7 @@ void HipPSSMLT::init(int argc, char** argv, RenderingContext& renderer)
 	const SceneArrays& h = renderer.get_host_scene();
 	renderer.init_mesh_lights("mesh_lights.init");     // src/renderers/pssmlt.cu:465
 	check(ctx, fpt_pssmlt_init(ctx, &p, &v, h.samples_dir, renderer.shard_pixels(), renderer.shard_count()), "PSSMLT::init");
+	set_mlt_persistence(argc, argv, ctx, "PSSMLT::init (-reseeding)");
 }
 void HipPSSMLT::render(const uint32 instance, RenderingContext& renderer)
 {
@@ -588,6 +604,7 @@ void HipMMLT::init(int argc, char** argv, RenderingContext& renderer)
 	const SceneArrays& h = renderer.get_host_scene();
 	renderer.init_mesh_lights("mesh_lights.init");     // src/renderers/cmlt.cu:847-852
 	check(ctx, fpt_mmlt_init(ctx, &p, &v, h.samples_dir, renderer.shard_pixels(), renderer.shard_count()), "MMLT::init");
+	set_mlt_persistence(argc, argv, ctx, "MMLT::init (-reseeding)");
 }
 void HipMMLT::render(const uint32 instance, RenderingContext& renderer)
 {

@@ -1,6 +1,6 @@
 // main.cpp — `fermat_hip`, the batch renderer (src/main.cu:98-218) on top of the host mirror.
 //
-//   fermat_hip -i scene.{fa,obj} [-r W H] [-a aspect] [-c camera.txt] [-pt | -bpt | -psfpt | -pssmlt | -mmlt [-mmlt-swaps F] [-mmlt-lens 0|1]] [-passes N] [-o output] [-ref ref.tga]
+//   fermat_hip -i scene.{fa,obj} [-r W H] [-a aspect] [-c camera.txt] [-pt | -bpt | -psfpt | -pssmlt | -mmlt [-mmlt-swaps F] [-mmlt-lens 0|1] [-reseeding R] [-startup-skips K]] [-passes N] [-o output] [-ref ref.tga]
 //              [-benchmark file] [-save-intermediate] [PT flags: -pl/-bounces/-nee/-bsdf/-nee-alg mesh|vpl ...]
 //              [-data dir] [-device id] [-filtered | -shading-mode N]   (kFiltered = EAW-denoised output; the reference toggles it in the viewer)
 //              [-bvh quality|fast|trbvh]   the acceleration structure's build mode (fpt_rt_set_build_mode): host SAH, device radix tree, device Trbvh
@@ -115,7 +115,7 @@ int main(int argc, char** argv)
 	{
 		std::fprintf(stderr, "options:\n  -i scene.obj|scene.fa  specify the input scene\n  -r int int             specify the resolution\n"
 		                     "  -a float               specify the aspect ratio\n  -c camera.txt          specify a camera file\n"
-		                     "  -pt                    use the PT renderer\n  -pssmlt                use the PSSMLT renderer (-chains K [x 1024], -spp N, -perturbations 0|1, -independent-samples p)\n  -mmlt                  use the multiplexed MLT renderer: one (s,t) technique per chain (-pssmlt's options, -mmlt-swaps F, -mmlt-lens 0|1: the lens connections (s,1) and light tracing)\n  -passes int            number of passes - 1\n  -o name                output image name\n"
+		                     "  -pt                    use the PT renderer\n  -pssmlt                use the PSSMLT renderer (-chains K [x 1024], -spp N, -perturbations 0|1, -independent-samples p)\n  -mmlt                  use the multiplexed MLT renderer: one (s,t) technique per chain (-pssmlt's options, -mmlt-swaps F, -mmlt-lens 0|1: the lens connections (s,1) and light tracing)\n  -reseeding R           -pssmlt / -mmlt: keep the chains alive across passes and reseed every R-th (also -rf; default 1: every pass reseeds)\n  -startup-skips K       -pssmlt / -mmlt: the first K steps of a reseeding pass deposit nothing\n  -passes int            number of passes - 1\n  -o name                output image name\n"
 		                     "  -bvh quality|fast|trbvh  build mode of the acceleration structure (host SAH, device radix tree, device Trbvh)\n"
 		                     "  -intersector mt|watertight  triangle intersector the acceleration structure is built for (default mt; watertight: no ray slips between adjacent triangles)\n"
 		                     "  -lights host|device      builder of the emitter tables (host mesh on host threads, device mesh on the device; FPT_LIGHTS_BUILD overrides)\n");

@@ -223,7 +223,7 @@ struct HipPSSMLT final : RendererInterface
 };
 
 // the multiplexed Metropolis renderer (one bidirectional technique per chain: the reference's `-cmlt -charted-swaps 0`, src/renderers/cmlt.h); `-mmlt` on the
-// command line, with HipPSSMLT's options, -mmlt-swaps F and -mmlt-lens 0|1.  Prints the (s,t) table of norms and seeded chains at instance 0
+// command line, with HipPSSMLT's options (-reseeding R and -startup-skips K among them: fpt_mlt_set_persistence), -mmlt-swaps F and -mmlt-lens 0|1.  Prints the (s,t) table of norms and seeded chains at instance 0
 struct HipMMLT final : RendererInterface
 {
 	void init(int argc, char** argv, RenderingContext& renderer) override;

@@ -400,7 +400,8 @@ int fpt_debug_bpt_splat_entries(fpt_context* ctx, uint32_t* h_entries, uint32_t*
  *   2. the seed CDF is the inclusive scan of floor(min(max_comp(value), 2^31) * 2^32) as uint64 (0 for a negative or non-finite value; sums wrap modulo 2^64);
  *      image_brightness = float(double(total) * 2^-32 / n_pixels)
  *   3. the chains' splats are the 2^-32 fixed-point integer sums of the light-tracing splats (above), not float atomics.
- * Not built: the per-(s,t) statistics the reference prints (st_norms), passes in flight, deferral, tile sharding / multi-GPU, use_vpls.
+ * Not built: the per-(s,t) statistics the reference prints (st_norms), passes in flight, deferral, tile sharding / multi-GPU, use_vpls.  Chains that persist across
+ * render calls are opt-in (fpt_mlt_set_persistence, below): by default every call reseeds, as the reference's PSSMLT does.
  * fpt_pssmlt_init replaces fpt_bpt_init (it initialises the bidirectional state itself, sized for max(n_pixels, n_chains) paths) and refuses, with a message that
  * names the option: bpt.use_vpls = 1, a tile-sharded context (d_pixels != NULL), n_chains = 0, spp * n_pixels < n_chains. */
 typedef struct fpt_pssmlt_options
@@ -436,7 +437,9 @@ int fpt_pssmlt_debug_eval(fpt_context* ctx, const fpt_rendering_context_view* vi
  *         splat_out (copy of the sums before the resolve), composited float4 per pixel, counts uint64[2]}
  *   op 3  technique index: params {max_path_length}; arrays {st uint32 n (s | t << 8), index uint32 n (0xFFFFFFFF for a technique outside the table), back uint32 n
  *         (the technique of that index as s | t << 8)}
- *   op 4  swap proposal: params {max_path_length, instance, step}; arrays {st uint32 n, chain uint32 n, st_new uint32 n, m_out float n (the number that chose)} */
+ *   op 4  swap proposal: params {max_path_length, instance, step}; arrays {st uint32 n, chain uint32 n, st_new uint32 n, m_out float n (the number that chose)}
+ *   op 5  op 2 with one more parameter, `accumulate` (params[10]): 0 = a skipped step (startup_skips, below): the test, the commit, the rejection counters and the
+ *         counts as op 2's, nothing deposited */
 int fpt_debug_mlt(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_params, uint32_t n_params, void* const* h_arrays, uint32_t n_arrays);
 
 /* ---- multiplexed Metropolis light transport (`-mmlt`): one bidirectional technique per chain.  The reference's `-cmlt -charted-swaps 0`
@@ -468,8 +471,8 @@ int fpt_debug_mlt(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_params
  * length k = s + t - 1 >= 2 is s in [0, k], s = k being (k, 1); k = 1 proposes the chain's own technique.
  * Deviations: PSSMLT's three (above), the seeds' common offset (PSSMLT jitters every stratum on its own, in float), and the swap's acceptance test takes no st_norms ratio (the reference multiplies the test, not the splats, by
  * st_norms[new] / st_norms[old], cmlt.cu:375-377): the target is max_comp f_{s,t}(u) on the disjoint union of the techniques and the walk is symmetric.
- * Not built: charted swaps and path inversion, chains that persist across render calls (`reseeding`, `startup_skips`: every call reseeds), techniques with t = 0,
- * single_connection = 1, passes in flight, tile sharding / multi-GPU.
+ * Not built: charted swaps and path inversion, techniques with t = 0, single_connection = 1, passes in flight, tile sharding / multi-GPU.  Chains that persist across
+ * render calls (`reseeding`, `startup_skips`) are opt-in: fpt_mlt_set_persistence, below; by default every call reseeds.
  * fpt_mmlt_init replaces fpt_pssmlt_init / fpt_bpt_init and refuses what fpt_pssmlt_init refuses, lens_techniques > 1, and a technique table of 2^32 cells or more. */
 typedef struct fpt_mmlt_options
 {
@@ -489,9 +492,11 @@ int fpt_mmlt_init(fpt_context* ctx, const fpt_mmlt_options* opts, const fpt_rend
                   const uint32_t* d_pixels, uint32_t n_local_pixels);        /* d_pixels: as fpt_bpt_init's, and must be NULL */
 int fpt_mmlt_render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view);
 int fpt_mmlt_get_stats(fpt_context* ctx, fpt_mmlt_stats* out);
-/* of the last render call: st_norms[s + t * (L + 2)] (float, (L + 2)^2 entries, 0 outside the table) and the number of chains seeded with each technique, indexed alike */
+/* of the last RESEEDING render call (with fpt_mlt_set_persistence a continuing call leaves them, the table and the seeds as the period's reseed made them):
+ * st_norms[s + t * (L + 2)] (float, (L + 2)^2 entries, 0 outside the table) and the number of chains seeded with each technique, indexed alike */
 int fpt_mmlt_get_st_norms(fpt_context* ctx, float* h_st_norms, uint32_t* h_chains);
-/* as fpt_pssmlt_download without the presample; h_st: each chain's technique s | t << 8; h_table: the technique table, float4 x n_techniques x n_pixels */
+/* as fpt_pssmlt_download without the presample; h_st: each chain's technique s | t << 8; h_table: the technique table, float4 x n_techniques x n_pixels.  The chains'
+ * arrays are what the last call left; h_seeds and h_table are those of the period's reseed (fpt_mlt_set_persistence) */
 int fpt_mmlt_download(fpt_context* ctx, float* h_light_u, float* h_eye_u, float* h_path_value /*float4*/, float* h_path_pdf, uint32_t* h_rejections, uint32_t* h_seeds,
                       uint32_t* h_st, float* h_table /*float4*/);
 /* as fpt_pssmlt_debug_eval, set i evaluating technique h_st[i] = s | t << 8 alone; h_rays (or NULL) receives the number of rays queued */
@@ -504,6 +509,31 @@ int fpt_mmlt_download_pixels(fpt_context* ctx, uint32_t* h_table_pixel, uint32_t
 /* fpt_mmlt_debug_eval that also returns, in h_pixel (uint32 x n, or NULL), the pixel a t = 1 evaluation lands on (0xFFFFFFFF for t >= 2 or when nothing was connected) */
 int fpt_mmlt_debug_eval_pixels(fpt_context* ctx, const fpt_rendering_context_view* view, uint32_t n, const float* h_light_u, const float* h_eye_u, const uint32_t* h_st,
                                float* h_value /*float4*/, uint64_t* h_rays, uint32_t* h_pixel);
+
+/* ---- chains that persist across render calls, for both Metropolis renderers (CMLTOptions::reseeding = 8 and startup_skips, src/renderers/cmlt.h:62-63; the reference's
+ *      PSSMLT has no such option: it gets one here because the render loop is shared) -------------------------------------------------------------------------------
+ * Default: reseeding = 1, startup_skips = 0 -- every render call reseeds, bit for bit as before these calls existed.  With reseeding = R a render call RESEEDS (the
+ * whole call described above) when the context holds no live chains or instance % R == 0, and otherwise CONTINUES: rescale, chain_length steps from the state the
+ * previous call left (coordinates, value, pdf, technique, pixel, rejection counters), resolve, the counters' read-back -- no presampling pass, no CDF, no seeds and no
+ * host synchronisation before the chain loop.  Of a continuing call: the counters and the rays are the call's own; image_brightness is the period's (its reseed's);
+ * pdf_norm = brightness * n_pixels / (chain_length * n_chains); st_norms, the chains per technique, the table and the seeds stay the reseed's; step 0 is a real mutation
+ * (cmlt.cu:1107) whose type is the later steps' rule at step 0, randfloat(0, hash32(instance + 0x9e3779b9)) < independent_samples ? Independent : Cauchy; swap steps are
+ * l > 0 with l % F == 0 of THIS call (cmlt.cu:1118).  Mutation numbers are a function of (instance, step, chain, dimension): a sequence of calls is bit-reproducible.
+ * startup_skips = K (clamped to chain_length - 1, cmlt.cu:824): steps l < K of a RESEEDING call run the acceptance test in full and deposit nothing (cmlt.cu:1110), and
+ * that call's pdf_norm divides by (chain_length - K) * n_chains (cmlt.cu:1097).  Deviation: the reference skips the first K steps of every call; here a continuing
+ * call, whose chains are burnt in, deposits every step.
+ * Chains are live after a call that ran its chain loop, until: either init or fpt_bpt_init; fpt_mlt_set_persistence or fpt_mlt_restart_chains; a successful
+ * fpt_rt_create_geometry / fpt_rt_refit_geometry, an emitter-table replace (fpt_mesh_lights_init*, fpt_mesh_lights_update* when it rebuilt) or fpt_mesh_invalidate; a
+ * render call whose view's camera or resolution differs bytewise from the period's reseed's; a reseed that finds a black frame (such a period reseeds at every call,
+ * mlt.cu:220).  Materials or textures edited IN PLACE on the device cannot be seen by the library: the host calls fpt_mlt_restart_chains (or fpt_mesh_invalidate) after
+ * such an edit.  fpt_*_debug_eval does not touch the chains, between two calls of a period either.
+ * All three are valid in either Metropolis mode after the mode's init and answer "... has not been called" otherwise. */
+/* reseeding = 0 is refused by name; calling it drops live chains, so the next call reseeds */
+int fpt_mlt_set_persistence(fpt_context* ctx, uint32_t reseeding, uint32_t startup_skips);
+/* drops live chains and changes nothing else */
+int fpt_mlt_restart_chains(fpt_context* ctx);
+/* any pointer may be NULL.  last_call_reseeded: 1 when the last render call reseeded; calls_since_reseed: continuing calls since the period's reseed */
+int fpt_mlt_get_persistence(fpt_context* ctx, uint32_t* reseeding, uint32_t* startup_skips, uint32_t* last_call_reseeded, uint32_t* calls_since_reseed);
 
 /* ---- multi-GPU: image tiles sharded over one process per GPU; replaces the single-GPU reference's cudaSetDevice(0) + whole-frame
  *      ownership (src/renderer.cu:600-603).  No data-path collective: each rank renders the pixels handed to fpt_pt_init / fpt_bpt_init

@@ -3,6 +3,12 @@
 chains.  A timing tool, not a bench line: bench.py measures the flagship workloads and knows nothing of these renderers.
 
     python tools/time_pssmlt.py [--renderer pssmlt|mmlt] [--mmlt-swaps F] [--lens] [--res 1600 900] [--path-length 9] [--chains 65536 1048576] [--spp 4] [--repeats 3]
+                                [--reseeding R [R ...] --startup-skips K]
+
+With `--reseeding` (chains that persist across render calls, fpt_mlt_set_persistence) the tool times PERIODS instead: one context per value of R, all alive, run in
+turn -- a warm-up block of max(R) calls each, then `--repeats` timed blocks of max(R) consecutive instances each, alternating between the settings -- and prints per
+setting the median time per call by position in the period (position 0 reseeds, the others continue), the mutations per second over a whole period and the frame mean
+after 16 calls.
 
 After the timed calls: one call at 2 x spp, from which the time of everything but the chain steps (rescale, presampling pass, seed CDF and seeds, coordinate
 recovery, resolve) is extrapolated as  t(spp) - chain_length(spp) x the time per step,  and one call with the traversal kernels' counters on, which gives the rays
@@ -37,6 +43,8 @@ def main():
     ap.add_argument("--renderer", choices=("pssmlt", "mmlt"), default="pssmlt")
     ap.add_argument("--mmlt-swaps", type=int, default=0)
     ap.add_argument("--lens", action="store_true", help="--renderer mmlt: the lens connections (s, 1) beside the other techniques (light tracing on)")
+    ap.add_argument("--reseeding", type=int, nargs="+", default=None, help="time periods of R calls with persistent chains, one context per value, alternating")
+    ap.add_argument("--startup-skips", type=int, default=0)
     args = ap.parse_args()
     mmlt = args.renderer == "mmlt"
     W, H = args.res
@@ -44,6 +52,10 @@ def main():
     s = scene.water_caustic_standin()
     table = np.fromfile(os.path.join(scene.DATA_DIR, "glossy_reflectance.dat"), np.float32)
     for n_chains in args.chains:
+        if args.reseeding:
+            time_periods(args, s, table, n_chains)
+            continue
+
         def renderer(spp):
             if mmlt:
                 return fa.Renderer(s, W, H, fa.default_options(L), table=table, mmlt_options=fa.default_mmlt_options(L, mmlt_frequency=args.mmlt_swaps, lens_techniques=int(args.lens), n_chains=n_chains, spp=spp))
@@ -91,6 +103,49 @@ def main():
                           "mutations_per_s_M": round(st["chain_length"] * n_chains / med / 1e6, 2), "msample_per_s": round(args.spp * W * H / med / 1e6, 2),
                           "accepted": st["accepted"], "rejected": st["rejected"], "image_brightness": float(st["image_brightness"]),
                           "frame_finite": bool(np.isfinite(fb).all()), "frame_mean": float(fb.mean())}))
+        r.close()
+
+
+def time_periods(args, s, table, n_chains):
+    """--reseeding: per-call times by position in the period, the settings alternating block by block"""
+    mmlt = args.renderer == "mmlt"
+    W, H = args.res
+    L = args.path_length
+    block = max(args.reseeding)
+    runs = []
+    for R in args.reseeding:
+        if mmlt:
+            r = fa.Renderer(s, W, H, fa.default_options(L), table=table, mmlt_options=fa.default_mmlt_options(L, mmlt_frequency=args.mmlt_swaps, lens_techniques=int(args.lens), n_chains=n_chains, spp=args.spp))
+        else:
+            r = fa.Renderer(s, W, H, fa.default_options(L), table=table, pssmlt_options=fa.default_pssmlt_options(L, n_chains=n_chains, spp=args.spp))
+        r.mlt_set_persistence(R, args.startup_skips)
+        runs.append(dict(R=R, r=r, next=0, times=[[] for _ in range(R)], reseeded=[[] for _ in range(R)], mean16=None))
+    for rep in range(args.repeats + 1):          # block 0 warms up: code objects, allocations, and the first period's reseed
+        for run in runs:
+            r = run["r"]; render = r.mmlt_render if mmlt else r.pssmlt_render
+            for _ in range(block):
+                i = run["next"]; run["next"] += 1
+                r.synchronize()
+                t0 = time.perf_counter()
+                render(i, sync=True)
+                dt = time.perf_counter() - t0
+                if rep > 0:
+                    run["times"][i % run["R"]].append(dt); run["reseeded"][i % run["R"]].append(r.mlt_persistence()["last_call_reseeded"])
+                if run["next"] == 16:
+                    run["mean16"] = float(r.framebuffer()[5][:, :3].mean())
+    for run in runs:
+        r = run["r"]; R = run["R"]
+        st = r.mmlt_stats() if mmlt else r.pssmlt_stats()
+        med = [float(np.median(t)) for t in run["times"]]
+        assert all(all(f == int(k == 0) for f in flags) for k, flags in enumerate(run["reseeded"]))
+        fb = r.framebuffer()[5][:, :3]
+        print(json.dumps({"tool": "time_pssmlt", "mode": "periods", "renderer": args.renderer, "scene": "water_caustic-standin", "resolution": [W, H], "max_path_length": L,
+                          "n_chains": n_chains, "spp": args.spp, "chain_length": st["chain_length"], "mmlt_swaps": args.mmlt_swaps if mmlt else None, "lens": int(args.lens) if mmlt else None,
+                          "reseeding": R, "startup_skips": r.mlt_persistence()["startup_skips"], "timed_calls": sum(len(t) for t in run["times"]),
+                          "median_ms_by_position": [round(m * 1e3, 3) for m in med], "reseeding_call_median_ms": round(med[0] * 1e3, 3),
+                          "continuing_call_median_ms": round(float(np.median(np.concatenate(run["times"][1:]))) * 1e3, 3) if R > 1 else None,
+                          "period_ms": round(sum(med) * 1e3, 3), "mutations_per_s_M_over_a_period": round(R * st["chain_length"] * n_chains / sum(med) / 1e6, 2),
+                          "calls": run["next"], "frame_mean_after_16_calls": run["mean16"], "frame_mean": float(fb.mean()), "frame_finite": bool(np.isfinite(fb).all())}))
         r.close()
 
 
