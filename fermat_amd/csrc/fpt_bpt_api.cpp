@@ -16,10 +16,11 @@ using namespace fpt;
 
 namespace {
 
-BptQueue queue_view(fpt_context::BptState& b, int which, uint32_t* size)
+// "readers check first" (BptState, part 4): entry point `who` gets the state only once an init has made it
+BptState& state_of(fpt_context* ctx, const char* who)
 {
-	BptQueue q; q.rays = b.q_rays[which].ptr; q.hits = b.q_hits[which].ptr; q.weights = b.q_weights[which].ptr; q.path_weights = b.q_pw[which].ptr; q.pixels = b.q_pixels[which].ptr; q.chan = b.q_chan[which].ptr; q.size = size;
-	return q;
+	if (!ctx->bpt.ready()) throw std::runtime_error(std::string(who) + ": fpt_bpt_init has not been called");
+	return ctx->bpt;
 }
 
 uint32_t read_u32(fpt_context* ctx, const uint32_t* d)
@@ -30,66 +31,30 @@ uint32_t read_u32(fpt_context* ctx, const uint32_t* d)
 	return v;
 }
 
-BptLog log_view(fpt_context::BptState& b)
-{
-	BptLog g; g.val = b.log_val.ptr; g.chan = b.log_chan.ptr; g.mask = b.log_mask.ptr;
-	g.cap = uint32_t(size_t(b.n_paths) * b.max_batch); g.conn_cells = b.opt.single_connection ? 1u : b.opt.max_path_length;
-	g.mask_words = (b.opt.max_path_length * (1u + g.conn_cells) + 31u) / 32u;
-	return g;
-}
-
 // fold the light-tracing splat sums into the frame (one pass: straight into the frame buffer); a batch: the merge applies, pass by pass and in the
 // sequential order, the albedo planes, the eye paths' cells and the splat sums
 void resolve_splats(fpt_context* ctx, const fpt_rendering_context_view* view)
 {
-	fpt_context::BptState& b = ctx->bpt;
+	BptState& b = ctx->bpt;
+	const BptState::Shape& sh = b.shape;
 	const uint32_t n_passes = b.pending_n > 1 ? b.pending_n : 1u;
 	const FrameBufferDev real = fb_dev(view->fb);
 	if (n_passes > 1)
 	{
-		launch_bpt_merge_exact(real, b.albedo[0].ptr, b.albedo[1].ptr, log_view(b), b.splat_ptr(), b.d_pixels, b.n_local, b.n_paths, b.pending_first, n_passes,
-		                       b.opt.max_path_length, ctx->stream);
+		launch_bpt_merge_exact(real, b.albedo[0].ptr, b.albedo[1].ptr, b.log_view(), b.splat_ptr(), b.d_pixels, sh.n_local, sh.n_paths, b.pending_first, n_passes,
+		                       sh.max_path_length, ctx->stream);
 		// the sums of every pixel of the batch, this rank's or not (all-reduced sums cover the whole frame)
-		FPT_HIP_CHECK(hipMemsetAsync(b.splat_ptr(), 0, size_t(b.n_paths) * n_passes * 3 * sizeof(long long), ctx->stream));
+		FPT_HIP_CHECK(hipMemsetAsync(b.splat_ptr(), 0, size_t(sh.n_paths) * n_passes * 3 * sizeof(long long), ctx->stream));
 	}
 	else
 	{
 		BptParams P; std::memset(&P, 0, sizeof(P));
 		P.fb = real; P.splat = b.splat_ptr(); P.res_x = view->res_x; P.res_y = view->res_y;
-		P.n_paths = b.n_paths; P.n_passes = 1; P.plane_stride = 0u; P.instance = b.pending_first;
+		P.n_paths = sh.n_paths; P.n_passes = 1; P.plane_stride = 0u; P.instance = b.pending_first;
 		launch_bpt_splat_resolve(P, ctx->stream);
 	}
 	b.pending_n = 0;
 	FPT_HIP_CHECK(hipGetLastError());
-}
-
-// The list of the arrays sized by paths in flight: v(array, elements per eye / connection path rendered HERE, elements per light path or pixel of the FRAME); the
-// two differ under tile sharding.  `L`, `sc`: max_path_length, -sc 1; `batched`: the planes and the log exist for passes in flight only
-template <typename V> void each_array(fpt_context::BptState& b, size_t L, size_t sc, size_t batched, V&& v)
-{
-	for (int k = 0; k < 2; ++k) { v(b.q_rays[k], 2, 0); v(b.q_hits[k], 1, 0); v(b.q_weights[k], 1, 0); v(b.q_pw[k], 1, 0); v(b.q_pixels[k], 1, 0); v(b.q_chan[k], 1, 0); }
-	// an eye vertex connects to at most L light vertices; a light path splats at most L-1
-	v(b.s_rays, 2 * L, 0); v(b.s_hits, L, 0); v(b.s_weights, L, 0); v(b.s_pixels, L, 0); v(b.s_chan, L, 0); v(b.conn, 1, 0);
-	v(b.v_pos, 0, L); v(b.v_rec, 0, L); v(b.v_counts, 0, 1);
-	v(b.flat, 0, sc * L);                     // -sc 1: the flat vertex list, at most one entry per store slot
-	v(b.splat, 0, 3);
-	v(b.albedo[0], 0, batched); v(b.albedo[1], 0, batched);
-	// the eye paths' contribution log (BptLog, fpt_bpt.h): per bounce an emission cell + 1 (-sc 1) or L (-sc 0) connection cells, a fill bit per cell
-	const size_t cells = L * (1 + (sc ? 1 : L));
-	v(b.log_val, 0, batched * cells); v(b.log_chan, 0, batched * cells); v(b.log_mask, 0, batched * ((cells + 31) / 32));
-}
-
-// device storage for `passes` passes in flight; clears what the kernels expect zeroed
-void alloc_storage(fpt_context* ctx, uint32_t passes)
-{
-	fpt_context::BptState& b = ctx->bpt;
-	const size_t nl = size_t(std::max(b.n_local, b.min_paths)) * passes, np = size_t(std::max(b.n_paths, b.min_paths)) * passes, L = b.opt.max_path_length;
-	each_array(b, L, b.opt.single_connection ? 1 : 0, passes > 1, [&](auto& a, size_t per_local, size_t per_path) { a.alloc(per_local * nl + per_path * np); });
-	// -sc 1, not per path: per-block counts of the list's scan (4096 elements per block); per-pass bounds
-	if (b.opt.single_connection) { b.flat_block_sums.alloc((np * L + 4095) / 4096 + 1); b.flat_meta.alloc(2 * size_t(passes) + 2); }
-	auto zero = [&](auto& a) { if (a.ptr) FPT_HIP_CHECK(hipMemsetAsync(a.ptr, 0, a.count * sizeof(*a.ptr), ctx->stream)); };
-	zero(b.v_counts); zero(b.splat); zero(b.albedo[0]); zero(b.albedo[1]); zero(b.log_mask);
-	b.max_batch = passes;
 }
 
 } // namespace
@@ -106,25 +71,15 @@ void bpt_init(fpt_context* ctx, const fpt_bpt_options* opts, const fpt_rendering
 		require(!opts->use_vpls || ctx->emitters.n_vpls != 0, "fpt_bpt_init: -use-vpls needs a VPL set");
 		// light_primary_kernel reads vpls[pixel index]: the reference allocates one VPL per light path by construction (src/renderers/bpt.cu:53)
 		require(!opts->use_vpls || size_t(ctx->emitters.n_vpls) >= size_t(view->res_x) * view->res_y, "fpt_bpt_init: -use-vpls needs one VPL per pixel (fpt_mesh_lights_init with n_vpls >= res_x * res_y)");
-		fpt_context::BptState& b = ctx->bpt;
-		b.opt = *opts;
-		b.min_paths = min_paths;
-		b.n_paths = view->res_x * view->res_y;
-		b.n_local = d_pixels ? n_local_pixels : b.n_paths;
-		b.d_pixels = d_pixels;
-		require(b.n_local > 0, "fpt_bpt_init: empty pixel set");
-		// compensate for the amount of light vs eye sub-paths (src/renderers/bpt.cu:75): both equal the pixel count here
-		b.light_tracing = opts->light_tracing * (float(b.n_paths) / float(b.n_paths));
-		const uint32_t L = opts->max_path_length;
-		alloc_storage(ctx, 1);
-		if (ctx->defer_kind == DEFER_BPT) ctx->defer_max = 1;          // storage for one pass: fpt_bpt_set_deferred sizes it again
-		b.counters.alloc(CNT_TOTAL);
+		BptState::Shape shape;
+		shape.n_paths = view->res_x * view->res_y; shape.n_local = d_pixels ? n_local_pixels : shape.n_paths; shape.min_paths = min_paths;
+		shape.passes = 1; shape.max_path_length = opts->max_path_length; shape.single_connection = opts->single_connection != 0;
+		require(shape.n_local > 0, "fpt_bpt_init: empty pixel set");
+		// nothing refuses from here on (BptState, part 1).  The state under a Metropolis state is replaced: that one goes first (MltState, invariant 5)
+		if (ctx->mlt.mode != fpt_context::MltState::None) ctx->mlt.reset();
 		// sampler: (L+1)*2*6 dimensions (src/renderers/bpt.cu:83-87); consumes the context's rand() stream after whatever ran before
-		std::vector<float> shifts;
-		b.seq_dims = (L + 1) * 2 * 6;
-		build_shift_table(256, b.seq_dims, h_samples_dir, ctx->crt_rand, shifts);
-		b.d_shifts.upload(shifts.data(), shifts.size(), ctx->stream);
-		b.ready = true;
+		ctx->bpt.init(*opts, shape, d_pixels, ctx->stream, [&] { std::vector<float> shifts; build_shift_table(256, shape.seq_dims(), h_samples_dir, ctx->crt_rand, shifts); return shifts; });
+		if (ctx->defer_kind == DEFER_BPT) ctx->defer_max = 1;          // storage for one pass: fpt_bpt_set_deferred sizes it again
 }
 } // namespace fpt
 
@@ -133,7 +88,7 @@ extern "C" {
 int fpt_bpt_init(fpt_context* ctx, const fpt_bpt_options* opts, const fpt_rendering_context_view* view, const char* h_samples_dir,
                  const uint32_t* d_pixels, uint32_t n_local_pixels)
 {
-	return guarded(ctx, [&] { ctx->mlt.reset(); bpt_init(ctx, opts, view, h_samples_dir, d_pixels, n_local_pixels, 0u); });
+	return guarded(ctx, [&] { bpt_init(ctx, opts, view, h_samples_dir, d_pixels, n_local_pixels, 0u); });
 }
 
 int fpt_bpt_set_profiling(fpt_context* ctx, int on) { return guarded(ctx, [&] { flush_deferred(ctx); ctx->bpt.profiling = on != 0; }); }
@@ -142,15 +97,14 @@ int64_t* fpt_bpt_splat_buffer(fpt_context* ctx) { return ctx ? reinterpret_cast<
 int fpt_bpt_use_splat_buffer(fpt_context* ctx, int64_t* d_splats) { return guarded(ctx, [&] { ctx->bpt.splat_external = reinterpret_cast<long long*>(d_splats); }); }
 int fpt_bpt_set_deferred_splats(fpt_context* ctx, int deferred) { return guarded(ctx, [&] { flush_deferred(ctx); ctx->bpt.deferred_splats = deferred != 0; }); }
 int fpt_bpt_resolve_splats(fpt_context* ctx, const fpt_rendering_context_view* view)
-{ return guarded(ctx, [&] { flush_deferred(ctx); require(ctx->bpt.ready, "fpt_bpt_resolve_splats: fpt_bpt_init has not been called"); resolve_splats(ctx, view); }); }
+{ return guarded(ctx, [&] { flush_deferred(ctx); state_of(ctx, "fpt_bpt_resolve_splats"); resolve_splats(ctx, view); }); }
 
 int fpt_bpt_download_light_vertices(fpt_context* ctx, float* h_pos, uint32_t* h_input, uint32_t* h_gbuffer, float* h_weights, uint32_t* h_path_id, uint32_t* h_counts)
 {
 	return guarded(ctx, [&] {
-		fpt_context::BptState& b = ctx->bpt;
 		flush_deferred(ctx);
-		require(b.ready, "fpt_bpt_download_light_vertices: fpt_bpt_init has not been called");
-		const size_t nv = size_t(b.n_paths) * b.opt.max_path_length;
+		BptState& b = state_of(ctx, "fpt_bpt_download_light_vertices");
+		const size_t nv = size_t(b.shape.n_paths) * b.shape.max_path_length;
 		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 		std::vector<LightVertexRecord> rec(nv);          // the store is an array of 64-byte records on the device; the caller gets the reference's five arrays
 		if (nv) FPT_HIP_CHECK(hipMemcpy(rec.data(), b.v_rec.ptr, nv * sizeof(LightVertexRecord), hipMemcpyDeviceToHost));
@@ -163,7 +117,7 @@ int fpt_bpt_download_light_vertices(fpt_context* ctx, float* h_pos, uint32_t* h_
 			if (h_weights) std::memcpy(h_weights + 2 * i, &r.weights, 8);
 			if (h_path_id) h_path_id[i] = r.path_id;
 		}
-		if (h_counts) FPT_HIP_CHECK(hipMemcpy(h_counts, b.v_counts.ptr, size_t(b.n_paths) * 4, hipMemcpyDeviceToHost));
+		if (h_counts) FPT_HIP_CHECK(hipMemcpy(h_counts, b.v_counts.ptr, size_t(b.shape.n_paths) * 4, hipMemcpyDeviceToHost));
 	});
 }
 
@@ -174,26 +128,28 @@ struct BptRun
 {
 	// the queues' slots in a bounce group of the counter block (fpt_host.h)
 	enum : uint32_t { LIGHT = CNT_PATH, EYE = CNT_SHADOW_DIR, SHADOW = CNT_SHADOW };
-	fpt_context* ctx; fpt_context::BptState& b; BptParams P; hipStream_t s; uint32_t n_launch, L; bool prof;
+	fpt_context* ctx; BptState& b; BptParams P; hipStream_t s; uint32_t n_launch, L; bool prof;
 	BptRun(fpt_context* c, uint32_t instance, uint32_t n_passes, const fpt_rendering_context_view* view) : ctx(c), b(c->bpt)
 	{
 		const bool batched = n_passes > 1;
-		n_launch = b.n_local * n_passes; s = ctx->stream; L = b.opt.max_path_length; prof = b.profiling;
+		const BptState::Shape& sh = b.shape;
+		n_launch = sh.n_local * n_passes; s = ctx->stream; L = sh.max_path_length; prof = b.profiling;
 		std::memset(&P, 0, sizeof(P));
 		P.store.rec = b.v_rec.ptr; P.store.pos = b.v_pos.ptr; P.store.counts = b.v_counts.ptr;
 		P.conn = b.conn.ptr; P.splat = b.splat_ptr();
 		P.flat = b.flat.ptr; P.flat_meta = b.flat_meta.ptr; P.flat_block_sums = b.flat_block_sums.ptr;
-		P.seq.shifts = b.d_shifts.ptr; P.seq.n_dims = b.seq_dims; P.seq.tile_size = 256;
+		P.seq.shifts = b.d_shifts.ptr; P.seq.n_dims = sh.seq_dims(); P.seq.tile_size = 256;
 		P.mesh = view->mesh; P.textures = view->d_textures; P.table = view->d_glossy_reflectance; P.shade_records = ensure_shade_records(ctx, view, s);
 		P.emitters = emitter_view(ctx, b.opt.use_vpls);
 		const FrameBufferDev real_fb = fb_dev(view->fb);
 		// passes in flight: the terms of the albedo planes' channels go to the planes, every other term to the eye path's cell of the log
 		P.fb = batched ? plane_view(real_fb, b.albedo[0].ptr, b.albedo[1].ptr) : real_fb;
-		if (batched) P.log = log_view(b);
-		P.opt = b.opt; P.pixels = b.d_pixels; P.n_local = b.n_local; P.n_paths = b.n_paths;
+		if (batched) P.log = b.log_view();
+		P.opt = b.opt; P.pixels = b.d_pixels; P.n_local = sh.n_local; P.n_paths = sh.n_paths;
 		P.res_x = view->res_x; P.res_y = view->res_y; P.instance = instance;
-		P.n_passes = n_passes; P.n_store = b.n_paths * n_passes; P.plane_stride = batched ? b.n_paths : 0u;
-		P.light_tracing = b.light_tracing;
+		P.n_passes = n_passes; P.n_store = sh.n_paths * n_passes; P.plane_stride = batched ? sh.n_paths : 0u;
+		// no compensation for the amount of light vs eye sub-paths (src/renderers/bpt.cu:75): both equal the pixel count here
+		P.light_tracing = b.opt.light_tracing;
 		P.eye = mk3(view->camera.eye[0], view->camera.eye[1], view->camera.eye[2]);
 		camera_frame(view->camera, view->aspect, P.U, P.V, P.W);
 		P.W_len = length(P.W);
@@ -230,13 +186,13 @@ struct BptRun
 		// shared light vertices: the store holds the other ranks' vertices of the previous batch -- forget them
 		if (b.shared_lv) FPT_HIP_CHECK(hipMemsetAsync(b.v_counts.ptr, 0, size_t(P.n_store) * sizeof(uint32_t), s));
 		int cur = 0;
-		P.out = queue_view(b, cur, b.cnt.queue(0, LIGHT));
+		P.out = b.queue_view(cur, b.cnt.queue(0, LIGHT));
 		launch_bpt_light_primary(P, s);
 		for (uint32_t bounce = 0; bounce + 1 < L; ++bounce)
 		{
 			P.bounce = bounce;
-			P.in = queue_view(b, cur, b.cnt.queue(bounce, LIGHT));
-			P.out = queue_view(b, cur ^ 1, b.cnt.queue(bounce + 1, LIGHT));
+			P.in = b.queue_view(cur, b.cnt.queue(bounce, LIGHT));
+			P.out = b.queue_view(cur ^ 1, b.cnt.queue(bounce + 1, LIGHT));
 			trace(P.in.rays, P.in.hits, P.in.size, false);
 			timed_launch(ctx, 3, s, [&] { launch_bpt_light_vertices(P, n_launch, s); });
 			if (prof) { st.light_queue[bounce] = read_u32(ctx, P.in.size); if (st.light_queue[bounce]) st.n_bounces_light = bounce + 1; }
@@ -250,14 +206,14 @@ struct BptRun
 		if (b.opt.single_connection) launch_bpt_build_flat_list(P, s);
 		// ---- sample_eye_subpaths (src/bpt_control.h:384-470) ----
 		int cur = 0;
-		P.out = queue_view(b, cur, b.cnt.queue(0, EYE));
+		P.out = b.queue_view(cur, b.cnt.queue(0, EYE));
 		launch_bpt_eye_primary(P, s);
 		BptParams P_prev = P;
 		for (uint32_t bounce = 0; bounce < L; ++bounce)
 		{
 			P.bounce = bounce;
-			P.in = queue_view(b, cur, b.cnt.queue(bounce, EYE));
-			P.out = queue_view(b, cur ^ 1, b.cnt.queue(bounce + 1, EYE));
+			P.in = b.queue_view(cur, b.cnt.queue(bounce, EYE));
+			P.out = b.queue_view(cur ^ 1, b.cnt.queue(bounce + 1, EYE));
 			P.shadow.rays = b.s_rays.ptr; P.shadow.hits = b.s_hits.ptr; P.shadow.weights = b.s_weights.ptr; P.shadow.pixels = b.s_pixels.ptr; P.shadow.chan = b.s_chan.ptr;
 			P.shadow.size = b.cnt.queue(bounce, SHADOW);
 			// the connections of bounce b-1 ride in the launch that finds the hits of bounce b (one traversal launch per bounce instead of two: a
@@ -287,7 +243,7 @@ struct BptRun
 			cur ^= 1;
 		}
 		// ---- light_tracing (src/bpt_control.h:572-600): this rank's own light paths ----
-		if (b.light_tracing && P.fixed.st)
+		if (b.opt.light_tracing && P.fixed.st)
 		{
 			// a chain step of `-mmlt` with the lens techniques: the chains on (s, 1) connect their vertex s - 1 to the lens; a launch of its own for the shadow rays (they
 			// could ride in the eye sub-paths' first traversal launch, which for these chains holds null rays: one launch less per step, not measured -- DESIGN 6h)
@@ -296,7 +252,7 @@ struct BptRun
 			trace(P.shadow.rays, P.shadow.hits, P.shadow.size, true);
 			launch_bpt_lens_chain_resolve(P, s);
 		}
-		else if (b.light_tracing)
+		else if (b.opt.light_tracing)
 		{
 			P.shadow.size = b.cnt.queue(L, SHADOW);
 			timed_launch(ctx, 3, s, [&] { launch_bpt_connect_camera(P, s); });
@@ -309,7 +265,7 @@ struct BptRun
 		}
 		if (prof)
 		{
-			std::vector<uint32_t> counts(size_t(b.n_paths) * P.n_passes);
+			std::vector<uint32_t> counts(size_t(b.shape.n_paths) * P.n_passes);
 			FPT_HIP_CHECK(hipMemcpyAsync(counts.data(), b.v_counts.ptr, counts.size() * 4, hipMemcpyDeviceToHost, s));
 			FPT_HIP_CHECK(hipStreamSynchronize(s));
 			uint64_t total = 0; for (uint32_t c : counts) total += c;
@@ -318,23 +274,22 @@ struct BptRun
 		if (P.value.value || P.tech.cell) { FPT_HIP_CHECK(hipGetLastError()); return; }          // a value sink or a technique table: the frame and the splat sums are the caller's
 		// the frame: light-tracing splats, then (batch) the planes in pass order.  Deferred mode leaves both to fpt_bpt_resolve_splats
 		b.pending_first = P.instance; b.pending_n = P.n_passes;
-		if (!b.deferred_splats || !b.light_tracing) resolve_splats(ctx, view);
+		if (!b.deferred_splats || !b.opt.light_tracing) resolve_splats(ctx, view);
 		FPT_HIP_CHECK(hipGetLastError());
 	}
 };
 
 static void render_impl(fpt_context* ctx, uint32_t instance, uint32_t n_passes, const fpt_rendering_context_view* view)
 {
-	fpt_context::BptState& b = ctx->bpt;
-	require(b.ready, "fpt_bpt_render: fpt_bpt_init has not been called");
+	BptState& b = state_of(ctx, "fpt_bpt_render");
 	require(ctx->tree.valid, "fpt_bpt_render: create_geometry has not been called");
 	require(ctx->emitters.valid, "fpt_bpt_render: fpt_mesh_lights_init has not been called");
-	require(view->res_x * view->res_y == b.n_paths, "fpt_bpt_render: the view's resolution differs from fpt_bpt_init's");
-	require(n_passes >= 1 && n_passes <= b.max_batch, "fpt_bpt_render_batch: more passes than fpt_bpt_set_batch sized the storage for");
+	require(view->res_x * view->res_y == b.shape.n_paths, "fpt_bpt_render: the view's resolution differs from fpt_bpt_init's");
+	require(b.serves(n_passes), "fpt_bpt_render_batch: more passes than fpt_bpt_set_batch sized the storage for");
 	require(b.pending_n == 0, "fpt_bpt_render: the previous batch's splats have not been resolved (fpt_bpt_resolve_splats)");
 	require(!b.light_pending, "fpt_bpt_render: the previous batch waits for fpt_bpt_finish (shared light vertices)");
 	// renderer.multiply_frame(instance / (instance + 1)) over this rank's pixels; a batch scales pass by pass when its planes are merged
-	if (n_passes == 1) launch_rescale(fb_dev(view->fb), b.d_pixels, b.n_local, float(instance) / float(instance + 1), ctx->stream);
+	if (n_passes == 1) launch_rescale(fb_dev(view->fb), b.d_pixels, b.shape.n_local, float(instance) / float(instance + 1), ctx->stream);
 	BptRun run(ctx, instance, n_passes, view);
 	run.light_phase();
 	if (b.shared_lv) { b.light_pending = true; b.light_instance = instance; b.light_passes = n_passes; FPT_HIP_CHECK(hipGetLastError()); return; }
@@ -347,14 +302,14 @@ namespace fpt {
 void bpt_sample_paths(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view, uint32_t n, const ChainCoords* chain, float4* value, BptParams* tiled,
                       const TechTable* tech, const ChainTech* fixed)
 {
-	fpt_context::BptState& b = ctx->bpt;
-	require(b.ready && b.max_batch == 1 && !b.d_pixels && !b.light_pending && b.pending_n == 0, "fpt_mlt: the bidirectional state is not the one the Metropolis renderer's init made");
-	require(((value != nullptr) != (tech != nullptr && tech->cell != nullptr)) && (n ? n : b.n_paths) <= std::max(b.n_paths, b.min_paths), "fpt_mlt: more paths than the storage holds");
+	BptState& b = state_of(ctx, "fpt_mlt");
+	require(b.shape.passes == 1 && !b.d_pixels && !b.light_pending && b.pending_n == 0, "fpt_mlt: the bidirectional state is not the one the Metropolis renderer's init made");
+	require(((value != nullptr) != (tech != nullptr && tech->cell != nullptr)) && b.serves(1, n), "fpt_mlt: more paths than the storage holds");
 	require(!fixed || (chain && value && !b.opt.single_connection), "fpt_mlt: a technique-fixed evaluation needs chain coordinates, a value sink and single_connection = 0");
-	require(!(tech && tech->cell && b.light_tracing) || tech->pixel, "fpt_mlt: with light tracing on the technique table needs its pixel plane");
+	require(!(tech && tech->cell && b.opt.light_tracing) || tech->pixel, "fpt_mlt: with light tracing on the technique table needs its pixel plane");
 	BptRun run(ctx, instance, 1, view);
 	if (tiled) *tiled = run.P;
-	run.for_value_sink(n ? n : b.n_paths, chain, value, tech, fixed);
+	run.for_value_sink(n ? n : b.shape.n_paths, chain, value, tech, fixed);
 	run.light_phase();
 	run.rest(view);
 }
@@ -367,11 +322,11 @@ int fpt_debug_bpt_splat_entries(fpt_context* ctx, uint32_t* h_entries, uint32_t*
 {
 	return guarded(ctx, [&] {
 		flush_deferred(ctx);
-		fpt_context::BptState& b = ctx->bpt;
-		require(b.ready && b.max_batch == 1 && h_entries && h_visible, "fpt_debug_bpt_splat_entries: fpt_bpt_init first, one pass in flight, no null argument");
+		BptState& b = ctx->bpt;
+		require(b.ready() && b.shape.passes == 1 && h_entries && h_visible, "fpt_debug_bpt_splat_entries: fpt_bpt_init first, one pass in flight, no null argument");
 		*h_entries = *h_visible = 0u;
-		if (!b.light_tracing || !b.counters.ptr) return;
-		const uint32_t n = std::min<uint32_t>(read_u32(ctx, PassCounters{ b.counters.ptr }.queue(b.opt.max_path_length, BptRun::SHADOW)), uint32_t(std::min<size_t>(b.s_hits.count, b.s_weights.count)));
+		if (!b.opt.light_tracing) return;
+		const uint32_t n = std::min<uint32_t>(read_u32(ctx, PassCounters{ b.counters.ptr }.queue(b.shape.max_path_length, BptRun::SHADOW)), uint32_t(std::min<size_t>(b.s_hits.count, b.s_weights.count)));
 		std::vector<float4> hits(n), weights(n);
 		b.s_hits.download(hits.data(), n, ctx->stream); b.s_weights.download(weights.data(), n, ctx->stream);
 		uint32_t visible = 0;
@@ -384,9 +339,9 @@ int fpt_bpt_render(fpt_context* ctx, uint32_t instance, const fpt_rendering_cont
 {
 	return guarded(ctx, [&] {
 		require(view != nullptr, "fpt_bpt_render: null view");
-		fpt_context::BptState& b = ctx->bpt;
+		BptState& b = ctx->bpt;
 		// deferred (fpt_bpt_set_deferred) unless the caller steps in between the phases of a pass: splat sums to all-reduce, light vertices to exchange
-		if (ctx->defer_kind != DEFER_BPT || ctx->defer_max <= 1 || b.profiling || b.shared_lv || (b.deferred_splats && b.light_tracing)) { flush_deferred(ctx); render_impl(ctx, instance, 1, view); return; }
+		if (ctx->defer_kind != DEFER_BPT || ctx->defer_max <= 1 || b.profiling || b.shared_lv || (b.deferred_splats && b.opt.light_tracing)) { flush_deferred(ctx); render_impl(ctx, instance, 1, view); return; }
 		defer_pass(ctx, DEFER_BPT, instance, view);
 	});
 }
@@ -394,7 +349,7 @@ int fpt_bpt_render(fpt_context* ctx, uint32_t instance, const fpt_rendering_cont
 int fpt_bpt_set_deferred(fpt_context* ctx, uint32_t max_passes)
 {
 	{ const int st = guarded(ctx, [&] { flush_deferred(ctx); require(max_passes >= 1, "fpt_bpt_set_deferred: max_passes must be >= 1"); }); if (st != 0) return st; }
-	if (max_passes > ctx->bpt.max_batch) { const int st = fpt_bpt_set_batch(ctx, max_passes); if (st != 0) return st; }
+	if (max_passes > std::max(ctx->bpt.shape.passes, 1u)) { const int st = fpt_bpt_set_batch(ctx, max_passes); if (st != 0) return st; }
 	return guarded(ctx, [&] { ctx->defer_max = max_passes; ctx->defer_kind = DEFER_BPT; });
 }
 
@@ -402,15 +357,16 @@ int fpt_bpt_set_deferred(fpt_context* ctx, uint32_t max_passes)
 int fpt_bpt_set_batch(fpt_context* ctx, uint32_t max_passes)
 {
 	return guarded(ctx, [&] {
-		fpt_context::BptState& b = ctx->bpt;
 		flush_deferred(ctx);
-		require(b.ready, "fpt_bpt_set_batch: fpt_bpt_init has not been called");
+		BptState& b = state_of(ctx, "fpt_bpt_set_batch");
 		// virtual path ids and light-vertex slots (virtual id + depth x passes x pixels) are 32-bit words: the bound is memory long before it is this
-		require(max_passes >= 1 && uint64_t(max_passes) * b.n_paths * b.opt.max_path_length < (1ull << 32),
+		require(max_passes >= 1 && uint64_t(max_passes) * b.shape.n_paths * b.shape.max_path_length < (1ull << 32),
 		        "fpt_bpt_set_batch: passes x pixels x max_path_length must stay below 2^32 (light-vertex slots are 32-bit)");
 		require(b.pending_n == 0, "fpt_bpt_set_batch: a batch is waiting for fpt_bpt_resolve_splats");
+		require(!b.light_pending, "fpt_bpt_set_batch: a batch is waiting for fpt_bpt_finish");
 		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		alloc_storage(ctx, max_passes);
+		BptState::Shape shape = b.shape; shape.passes = max_passes;
+		b.resize(shape, ctx->stream);
 		if (ctx->defer_kind == DEFER_BPT && ctx->defer_max > max_passes) ctx->defer_max = max_passes;
 	});
 }
@@ -424,7 +380,7 @@ int fpt_bpt_set_shared_light_vertices(fpt_context* ctx, int on)
 {
 	return guarded(ctx, [&] {
 		flush_deferred(ctx);
-		require(ctx->bpt.ready && !ctx->bpt.light_pending, "fpt_bpt_set_shared_light_vertices: fpt_bpt_init first; no batch may be waiting for fpt_bpt_finish");
+		require(ctx->bpt.ready() && !ctx->bpt.light_pending, "fpt_bpt_set_shared_light_vertices: fpt_bpt_init first; no batch may be waiting for fpt_bpt_finish");
 		ctx->bpt.shared_lv = on != 0;
 	});
 }
@@ -432,27 +388,26 @@ int fpt_bpt_set_shared_light_vertices(fpt_context* ctx, int on)
 namespace fpt {
 uint64_t bpt_bytes_per_path(fpt_context* ctx)
 {
-	fpt_context::BptState& b = ctx->bpt;
-	uint64_t bytes = 0;          // before fpt_bpt_init: the default path length, -sc 0
-	each_array(b, b.opt.max_path_length ? b.opt.max_path_length : 9, b.opt.single_connection ? 1 : 0, 1, [&](auto& a, size_t per_local, size_t per_path) { bytes += (per_local + per_path) * sizeof(*a.ptr); });
-	return bytes;
+	BptState::Shape shape = ctx->bpt.shape;
+	if (!ctx->bpt.ready()) shape.max_path_length = 9;          // before fpt_bpt_init: the default path length, -sc 0
+	shape.passes = 2;                                          // in flight: the planes and the log count
+	return ctx->bpt.bytes_per_path(shape);
 }
 uint32_t bpt_pack_own_vertices(fpt_context* ctx)
 {
-	fpt_context::BptState& b = ctx->bpt;
+	BptState& b = state_of(ctx, "fpt_bpt_export_light_vertices");
 	require(b.light_pending, "no light sub-paths are waiting (fpt_bpt_set_shared_light_vertices, then fpt_bpt_render)");
-	const size_t cap = size_t(b.n_local) * b.light_passes * b.opt.max_path_length;
-	b.lv_send.alloc(std::max<size_t>(b.lv_send.count, cap));
+	b.lv_send.alloc(std::max(b.lv_send.count, size_t(b.shape.n_local) * b.light_passes * b.shape.max_path_length));
 	b.lv_count.alloc(32);
 	FPT_HIP_CHECK(hipMemsetAsync(b.lv_count.ptr, 0, 32 * sizeof(uint32_t), ctx->stream));
-	launch_bpt_pack_light_vertices(b.v_rec.ptr, b.v_counts.ptr, b.d_pixels, b.n_local, b.n_paths, b.light_passes, b.lv_send.ptr, b.lv_count.ptr, ctx->stream);
+	launch_bpt_pack_light_vertices(b.v_rec.ptr, b.v_counts.ptr, b.d_pixels, b.shape.n_local, b.shape.n_paths, b.light_passes, b.lv_send.ptr, b.lv_count.ptr, ctx->stream);
 	return read_u32(ctx, b.lv_count.ptr);
 }
 void bpt_import_vertices(fpt_context* ctx, const LightVertexWire* d_records, uint32_t count)
 {
-	fpt_context::BptState& b = ctx->bpt;
+	BptState& b = state_of(ctx, "fpt_bpt_import_light_vertices");
 	require(b.light_pending, "no light sub-paths are waiting (fpt_bpt_set_shared_light_vertices, then fpt_bpt_render)");
-	if (count) launch_bpt_unpack_light_vertices(d_records, count, b.v_rec.ptr, b.v_pos.ptr, b.v_counts.ptr, b.n_paths * b.light_passes, ctx->stream);
+	if (count) launch_bpt_unpack_light_vertices(d_records, count, b.v_rec.ptr, b.v_pos.ptr, b.v_counts.ptr, b.shape.n_paths * b.light_passes, ctx->stream);
 	FPT_HIP_CHECK(hipGetLastError());
 }
 } // namespace fpt
@@ -472,7 +427,7 @@ int fpt_bpt_import_light_vertices(fpt_context* ctx, const void* d_records, uint3
 int fpt_bpt_finish(fpt_context* ctx, const fpt_rendering_context_view* view)
 {
 	return guarded(ctx, [&] {
-		fpt_context::BptState& b = ctx->bpt;
+		BptState& b = state_of(ctx, "fpt_bpt_finish");
 		require(b.light_pending, "fpt_bpt_finish: no light sub-paths are waiting");
 		BptRun run(ctx, b.light_instance, b.light_passes, view);
 		b.light_pending = false;

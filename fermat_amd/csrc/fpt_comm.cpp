@@ -313,13 +313,13 @@ int fpt_psfpt_exchange_cells(fpt_context* ctx)
 int fpt_bpt_exchange_light_vertices(fpt_context* ctx)
 {
 	return guarded(ctx, [&] {
-		fpt_context::BptState& b = ctx->bpt;
+		BptState& b = ctx->bpt;
 		require(ctx->comm != nullptr, "fpt_bpt_exchange_light_vertices: no communicator (fpt_comm_init / fpt_comm_adopt)");
 		const int W = ctx->comm_world, me = ctx->comm_rank;
 		ncclComm_t comm = static_cast<ncclComm_t>(ctx->comm);
 		hipStream_t s = ctx->stream;
 		const uint32_t mine = bpt_pack_own_vertices(ctx);
-		DeviceArray<uint32_t>& dc = ctx->psf.ex_counts;                   // a few words of scratch shared with the PSFPT exchange
+		DeviceArray<uint32_t>& dc = b.lv_ranks;
 		dc.alloc(std::max<size_t>(dc.count, size_t(W)));
 		std::vector<uint32_t> counts(size_t(W), 0u); counts[size_t(me)] = mine;
 		FPT_HIP_CHECK(hipMemcpyAsync(dc.ptr, counts.data(), size_t(W) * sizeof(uint32_t), hipMemcpyHostToDevice, s));

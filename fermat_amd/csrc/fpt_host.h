@@ -3,6 +3,7 @@
 #include "fpt_kernels.h"
 #include "fpt_bvh.h"
 #include "fpt_bpt.h"
+#include <algorithm>
 #include <memory>
 #include <string>
 #include <utility>
@@ -258,6 +259,130 @@ struct WavefrontStore
 	bool serves(uint32_t passes, bool psf, bool dir) const { return passes >= 1 && passes <= shape.passes && (shape.psf || !psf) && (shape.dir || !dir); }
 };
 
+// The device state of the bidirectional path tracer (fpt_bpt_api.cpp), on which the Metropolis renderers sample as well (MltState, below), and its one owner:
+//   1. Refuse first.  Every refusal of fpt_bpt_init (the range of L, the 24-bit path ids, the emitters, -use-vpls and its VPL count, the empty pixel set) and of
+//      fpt_bpt_set_batch happens before the first write: a refused call leaves this state, and any Metropolis state on it, exactly as it was and usable.
+//   2. Invalid while changing.  `shape` says what every array is sized for, and from the first write of an init or a re-size to the last it is empty: ready() and
+//      serves() are false.  A throw in between (out of memory) leaves NO bidirectional state, and every reader answers "fpt_bpt_init has not been called".  resize() is
+//      the only code that allocates or clears the arrays the shape sizes; it clears what the kernels expect zeroed on the given stream and does not synchronise.
+//   3. An init replaces everything that describes a pass in progress: init() and reset() clear pending_*, light_*, `cnt` and `stats`.  What the caller SET survives an
+//      init: profiling, deferred_splats, shared_lv and splat_external, whose memory the library does not own and does not clear.
+//   4. Readers check first (state_of, fpt_bpt_api.cpp): the render entry points, fpt_bpt_resolve_splats, fpt_bpt_download_light_vertices, fpt_bpt_set_batch,
+//      fpt_bpt_set_shared_light_vertices, bpt_sample_paths, fpt_debug_bpt_splat_entries, and the pack / import / finish calls of the shared light vertices.
+//   5. reset() is the only way to invalidate the state from outside: a Metropolis init that throws after bpt_init calls it (MltState, invariant 2).
+//   6. Each array stands ONCE in each_array().  resize(), bytes_per_path() and reset() walk that list, so what fpt_bytes_per_path_in_flight reports is what is allocated
+//      and an array the shape does not use (the -sc 1 list under -sc 0) is released.
+struct BptState
+{
+	struct Shape
+	{
+		uint32_t n_local = 0, n_paths = 0;                   // eye / connection paths rendered HERE, light paths or pixels of the FRAME: the two differ under tile sharding
+		uint32_t min_paths = 0;                              // the arrays hold at least this many paths per pass (the Metropolis renderers' chains may outnumber the pixels)
+		uint32_t passes = 0, max_path_length = 0;            // passes in flight
+		bool single_connection = false;                      // -sc 1
+		size_t local_paths() const { return size_t(std::max(n_local, min_paths)) * passes; }
+		size_t frame_paths() const { return size_t(std::max(n_paths, min_paths)) * passes; }
+		// the eye paths' contribution log (BptLog, fpt_bpt.h): per bounce an emission cell + 1 (-sc 1) or L (-sc 0) connection cells, a fill bit per cell
+		uint32_t conn_cells() const { return single_connection ? 1u : max_path_length; }
+		uint32_t log_cells() const { return max_path_length * (1u + conn_cells()); }
+		uint32_t seq_dims() const { return (max_path_length + 1u) * 2u * 6u; }      // the sampler's dimensions (src/renderers/bpt.cu:83-87)
+	};
+	Shape shape;
+	fpt_bpt_options opt{};                                   // of the init that made `shape`: max_path_length and single_connection agree with it
+	const uint32_t* d_pixels = nullptr;                      // this rank's pixel list (the caller's memory; NULL = the whole frame)
+	// what the caller set (part 3)
+	bool profiling = false, deferred_splats = false, shared_lv = false;      // shared_lv: the call stops after the light sub-paths until fpt_bpt_finish
+	long long* splat_external = nullptr;
+	// the pass in progress.  pending_*: a batch whose light-tracing splats still wait for fpt_bpt_resolve_splats (deferred mode); light_*: one that waits for
+	// fpt_bpt_finish; cnt: the call in progress's view of `counters` (its light and eye phases may be two calls apart)
+	uint32_t pending_first = 0, pending_n = 0;
+	bool light_pending = false; uint32_t light_instance = 0, light_passes = 0;
+	PassCounters cnt;
+	fpt_bpt_stats stats{};
+	DeviceArray<float4> q_rays[2], q_hits[2], q_weights[2], q_pw[2]; DeviceArray<uint32_t> q_pixels[2]; DeviceArray<uint8_t> q_chan[2];
+	DeviceArray<float4> s_rays, s_hits, s_weights; DeviceArray<uint32_t> s_pixels; DeviceArray<uint8_t> s_chan; DeviceArray<uint2> conn;
+	DeviceArray<float4> v_pos; DeviceArray<LightVertexRecord> v_rec; DeviceArray<uint32_t> v_counts;
+	DeviceArray<uint32_t> flat, flat_meta, flat_block_sums;         // -sc 1: the flat light-vertex list (fpt_bpt.h)
+	DeviceArray<long long> splat;
+	DeviceArray<float4> albedo[2];                                  // passes in flight: the diffuse and the specular albedo's per-pass planes
+	DeviceArray<float4> log_val; DeviceArray<uint32_t> log_chan, log_mask;
+	DeviceArray<uint32_t> counters; DeviceArray<float> d_shifts;
+	// the staging of the light-vertex exchange: own and received wire records, the packed count, the ranks' counts
+	DeviceArray<LightVertexWire> lv_send, lv_recv; DeviceArray<uint32_t> lv_count, lv_ranks;
+
+	// the list: v(array, elements per local path, elements per frame path, elements that are not per path).  The list's order is the order of allocation (EXPERIMENTS
+	// 6i: reordering such a list moved `-pssmlt` by 0.5 ms).  Planes and log exist for passes IN FLIGHT only (passes > 1).  The exchange's staging has no elements here:
+	// a re-size releases it, and the exchange grows it to what the ranks send (bpt_pack_own_vertices, fpt_bpt_exchange_light_vertices)
+	template <typename V> void each_array(const Shape& s, V&& v)
+	{
+		const size_t L = s.max_path_length, sc = s.single_connection, g = s.passes > 1, cells = s.log_cells();
+		for (int k = 0; k < 2; ++k) { v(q_rays[k], 2, 0, 0); v(q_hits[k], 1, 0, 0); v(q_weights[k], 1, 0, 0); v(q_pw[k], 1, 0, 0); v(q_pixels[k], 1, 0, 0); v(q_chan[k], 1, 0, 0); }
+		// an eye vertex connects to at most L light vertices; a light path splats at most L-1
+		v(s_rays, 2 * L, 0, 0); v(s_hits, L, 0, 0); v(s_weights, L, 0, 0); v(s_pixels, L, 0, 0); v(s_chan, L, 0, 0); v(conn, 1, 0, 0);
+		v(v_pos, 0, L, 0); v(v_rec, 0, L, 0); v(v_counts, 0, 1, 0);
+		v(flat, 0, sc * L, 0);                    // -sc 1: the flat vertex list, at most one entry per store slot
+		v(splat, 0, 3, 0);
+		v(albedo[0], 0, g, 0); v(albedo[1], 0, g, 0);
+		v(log_val, 0, g * cells, 0); v(log_chan, 0, g * cells, 0); v(log_mask, 0, g * ((cells + 31) / 32), 0);
+		// -sc 1, not per path: per-block counts of the list's scan (4096 elements per block); per-pass bounds
+		v(flat_block_sums, 0, 0, sc * ((s.frame_paths() * L + 4095) / 4096 + 1)); v(flat_meta, 0, 0, sc * (2 * size_t(s.passes) + 2));
+		v(counters, 0, 0, CNT_TOTAL);
+		v(d_shifts, 0, 0, size_t(256) * 256 * s.seq_dims());      // the Cranley-Patterson shifts of a 256 x 256 tile (build_shift_table)
+		v(lv_send, 0, 0, 0); v(lv_recv, 0, 0, 0); v(lv_count, 0, 0, 0); v(lv_ranks, 0, 0, 0);
+	}
+	// part 2.  `then`: what an init still has to do to the allocated arrays before the state is valid
+	template <typename F> void resize(const Shape& s, hipStream_t stream, F&& then)
+	{
+		shape = Shape{};
+		each_array(s, [&](auto& a, size_t per_local, size_t per_frame, size_t fixed) { a.alloc(per_local * s.local_paths() + per_frame * s.frame_paths() + fixed); });
+		auto zero = [&](auto& a) { if (a.ptr) FPT_HIP_CHECK(hipMemsetAsync(a.ptr, 0, a.count * sizeof(*a.ptr), stream)); };
+		zero(v_counts); zero(splat); zero(albedo[0]); zero(albedo[1]); zero(log_mask);
+		then();
+		shape = s;
+	}
+	void resize(const Shape& s, hipStream_t stream) { resize(s, stream, [] {}); }          // a re-size keeps the shift table it has
+	// parts 2 and 3: what fpt_bpt_init does once nothing can refuse any more.  `shift_table()` builds the sampler's table on the host: after the device arrays are
+	// allocated, as ever -- a host buffer of that size allocated before them moves where they lie (EXPERIMENTS 6k)
+	template <typename F> void init(const fpt_bpt_options& o, const Shape& s, const uint32_t* pixels, hipStream_t stream, F&& shift_table)
+	{
+		shape = Shape{}; forget_pass();
+		opt = o; d_pixels = pixels;
+		resize(s, stream, [&] {
+			const std::vector<float> shifts = shift_table();
+			require(shifts.size() == d_shifts.count, "fpt_bpt_init: the shift table's size differs from the sampler's dimensions");
+			d_shifts.upload(shifts.data(), shifts.size(), stream);
+		});
+	}
+	void forget_pass() { pending_first = pending_n = 0; light_pending = false; light_instance = light_passes = 0; cnt = PassCounters{}; stats = fpt_bpt_stats{}; }
+	void reset()
+	{
+		shape = Shape{}; forget_pass(); opt = fpt_bpt_options{}; d_pixels = nullptr;
+		each_array(shape, [](auto& a, size_t, size_t, size_t) { a.release(); });
+	}
+	// what a path in flight costs: the per-path terms of the list for `s` (the other terms do not grow with the paths)
+	uint64_t bytes_per_path(const Shape& s)
+	{
+		uint64_t b = 0;
+		each_array(s, [&](auto& a, size_t per_local, size_t per_frame, size_t) { b += (per_local + per_frame) * sizeof(*a.ptr); });
+		return b;
+	}
+	bool ready() const { return shape.passes != 0; }
+	// is a render of `n_passes` passes of `paths` light and eye sub-paths each (the Metropolis renderers' chains; 0 = the frame's pixels) covered by what the arrays hold?
+	bool serves(uint32_t n_passes, uint32_t paths = 0) const { return n_passes >= 1 && n_passes <= shape.passes && paths <= std::max(shape.n_paths, shape.min_paths); }
+	long long* splat_ptr() { return splat_external ? splat_external : splat.ptr; }
+	BptQueue queue_view(int which, uint32_t* size)
+	{
+		BptQueue q; q.rays = q_rays[which].ptr; q.hits = q_hits[which].ptr; q.weights = q_weights[which].ptr; q.path_weights = q_pw[which].ptr; q.pixels = q_pixels[which].ptr; q.chan = q_chan[which].ptr; q.size = size;
+		return q;
+	}
+	BptLog log_view()
+	{
+		BptLog g; g.val = log_val.ptr; g.chan = log_chan.ptr; g.mask = log_mask.ptr;
+		g.cap = uint32_t(size_t(shape.n_paths) * shape.passes); g.conn_cells = shape.conn_cells(); g.mask_words = (shape.log_cells() + 31u) / 32u;
+		return g;
+	}
+};
+
 // a table of the path-space filter's cache (fpt_kernels.h PsfDev): `tables` tables of 2^log2 slots each, side by side.  `listed`: pass tables, whose
 // live slots are listed in `touched` (as long as the tables) and counted in `touched_n` (one word per table)
 struct PsfTable
@@ -354,49 +479,19 @@ struct fpt_context
 		fpt::DeviceArray<uint32_t> ex_counts;
 		fpt::PsfTable batch;                        // passes in flight (fpt_psfpt_set_batch): one pass table per pass of the batch, with the lists of their live slots
 	} psf;
-	// bidirectional path tracer
-	struct BptState
-	{
-		bool ready = false, profiling = false, deferred_splats = false;
-		fpt_bpt_options opt{};
-		uint32_t n_local = 0, n_paths = 0;
-		uint32_t min_paths = 0;                              // the arrays hold at least this many paths per pass (the Metropolis renderer's chains may outnumber the pixels)
-		const uint32_t* d_pixels = nullptr;
-		float light_tracing = 0.0f;
-		fpt::DeviceArray<float> d_shifts; uint32_t seq_dims = 0;
-		fpt::DeviceArray<float4> q_rays[2], q_hits[2], q_weights[2], q_pw[2]; fpt::DeviceArray<uint32_t> q_pixels[2]; fpt::DeviceArray<uint8_t> q_chan[2];
-		fpt::DeviceArray<float4> s_rays, s_hits, s_weights; fpt::DeviceArray<uint32_t> s_pixels; fpt::DeviceArray<uint8_t> s_chan; fpt::DeviceArray<uint2> conn;
-		fpt::DeviceArray<float4> v_pos; fpt::DeviceArray<fpt::LightVertexRecord> v_rec;
-		fpt::DeviceArray<uint32_t> v_counts;
-		fpt::DeviceArray<uint32_t> flat, flat_meta, flat_block_sums;      // -sc 1: the flat light-vertex list (fpt_bpt.h)
-		fpt::DeviceArray<long long> splat; long long* splat_external = nullptr;
-		// passes in flight (fpt_bpt_set_batch / fpt_bpt_render_batch): everything above is sized for max_batch passes; albedo = the per-pass
-		// accumulation planes; pending_* = a batch whose light-tracing splats still wait for fpt_bpt_resolve_splats (deferred mode)
-		uint32_t max_batch = 1;
-		fpt::DeviceArray<float4> albedo[2];                  // the diffuse and the specular albedo's per-pass planes
-		fpt::DeviceArray<float4> log_val; fpt::DeviceArray<uint32_t> log_chan, log_mask;      // the eye paths' contribution log (fpt_bpt.h BptLog)
-		uint32_t pending_first = 0, pending_n = 0;
-		long long* splat_ptr() { return splat_external ? splat_external : splat.ptr; }
-		fpt::DeviceArray<uint32_t> counters;
-		fpt::PassCounters cnt;                               // the call in progress's view of `counters` (its light and eye phases may be two calls apart)
-		fpt_bpt_stats stats{};
-		// shared light vertices (fpt_bpt_set_shared_light_vertices): the call stops after the light sub-paths until fpt_bpt_finish
-		bool shared_lv = false, light_pending = false;
-		uint32_t light_instance = 0, light_passes = 0;
-		fpt::DeviceArray<fpt::LightVertexWire> lv_send, lv_recv; fpt::DeviceArray<uint32_t> lv_count;
-	} bpt;
+	fpt::BptState bpt;                                   // the bidirectional path tracer's state and everything that describes it
 	// The state of the two Metropolis renderers on the bidirectional state above (fpt_mlt_api.cpp) and its one owner: `-pssmlt` (fpt_pssmlt_init) and `-mmlt`
 	// (fpt_mmlt_init; `lens`: with its lens techniques (s, 1)) are two modes of one state, and one init of either leaves the other nothing.
 	//   1. Agreement.  Whenever `mode` is not None, the arrays, n_pixels, n_chains, chain_length, n_tech, `lens` and the options agree, and ctx->bpt is the state this
 	//      init made: min_paths = n_chains, the forced options (light_tracing = lens, single_connection = 0), one pass in flight.
 	//   2. Invalid during init.  From the first modification to the end of an init `mode` is None.  A throw in between -- a refusal, an allocation -- leaves it None and
-	//      releases every array below; if bpt_init had already run, it clears ctx->bpt.ready as well, so that no bidirectional state with options nobody asked for stays usable.
+	//      releases every array below; if bpt_init had already run, it resets ctx->bpt as well (BptState::reset), so that no bidirectional state with options nobody asked for stays usable.
 	//   3. Nothing left over.  A successful init leaves allocated only what its mode uses: an init starts with reset(), and allocate() walks each_array(), where an array
 	//      the mode does not use has no elements.
 	//   4. Readers check first.  Everything that reads the state checks `mode` first (state_in, fpt_mlt_api.cpp): render, get_stats, get_st_norms, download,
 	//      download_pixels and debug_eval of both families, each answering "<its init> has not been called" in any other mode; fpt_mlt_set_persistence, _restart_chains and
 	//      _get_persistence (any_mode) in either mode.
-	//   5. reset() is the only way to invalidate the state: fpt_bpt_init, which replaces the bidirectional state under it, calls it.
+	//   5. reset() is the only way to invalidate the state: bpt_init, which replaces the bidirectional state under it, calls it once nothing can refuse any more (BptState, part 1).
 	//   6. Live chains (fpt_mlt_set_persistence).  `live` implies that the chain arrays (coordinates, path_value, path_pdf, rejections, st, path_pixel) hold the
 	//      state the last render call left, that the table, seeds, st_norms and st_chains are those of the period's reseed, and that period_brightness, period_camera,
 	//      period_res and period_scene describe that reseed.  Only a render call that ran its chain loop sets it; drop_chains() and reset() clear it, and a call that finds the
@@ -510,7 +605,7 @@ namespace fpt { void resize_wavefront(fpt_context* ctx, uint32_t passes, const f
 // fpt_bpt_api.cpp: what fpt_bpt_set_batch allocates per path in flight, with every pixel rendered here
 namespace fpt { uint64_t bpt_bytes_per_path(fpt_context* ctx); }
 // fpt_bpt_api.cpp, for the Metropolis renderers (inside the caller's `guarded`).  bpt_init: fpt_bpt_init's body, storage for at least `min_paths` paths; the one init of
-// fpt_mlt_api.cpp calls it and, should it throw afterwards, clears ctx->bpt.ready (MltState, invariant 2); fpt_bpt_init itself resets ctx->mlt first (invariant 5).
+// fpt_mlt_api.cpp calls it and, should it throw afterwards, calls ctx->bpt.reset() (MltState, invariant 2); a call that finds a Metropolis state resets it (invariant 5).
 // bpt_sample_paths: one bidirectional wavefront (BptRun: light_phase, rest) of `n` light and eye sub-paths -- n = 0: the frame's pixels -- whose samples go to
 // `value` (ValueSink) and whose coordinates come from `chain` (ChainCoords) or, chain == NULL, from the tiled sequence; the frame is not touched.  `tiled`, when
 // given, receives the parameter block of the tiled pass (what launch_mlt_recover_coordinates reads).  `tech` (with value == NULL): the samples go to the technique

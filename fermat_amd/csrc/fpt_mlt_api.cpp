@@ -69,7 +69,7 @@ void init(fpt_context* ctx, const fpt_pssmlt_options& opts, uint32_t mmlt_freque
 		m.stats.n_chains = m.n_chains; m.stats.chain_length = m.chain_length;
 		m.mode = mode;
 	}
-	catch (...) { m.reset(); if (bpt_made) ctx->bpt.ready = false; throw; }
+	catch (...) { m.reset(); if (bpt_made) ctx->bpt.reset(); throw; }
 }
 
 // MltState, invariant 6: do the chain arrays hold chains this call may continue?  Not after a geometry build or refit or an emitter-table replace (the scene's generation
@@ -85,7 +85,7 @@ void render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_vie
 {
 	need(view != nullptr, who, "null view");
 	Mlt& m = state_in(ctx, mode, who);
-	fpt_context::BptState& b = ctx->bpt;
+	BptState& b = ctx->bpt;
 	need(ctx->tree.valid, who, "create_geometry has not been called");
 	need(ctx->emitters.valid, who, "fpt_mesh_lights_init has not been called");
 	need(view->res_x * view->res_y == m.n_pixels, who, "the view's resolution differs from ", mode == Mlt::Mmlt ? "fpt_mmlt_init's" : "fpt_pssmlt_init's");
