@@ -210,7 +210,8 @@ ENTRY_POINTS = ["fpt_create", "fpt_destroy", "fpt_last_error", "fpt_stream", "fp
                 "fpt_pssmlt_init", "fpt_pssmlt_render", "fpt_pssmlt_get_stats", "fpt_pssmlt_download", "fpt_pssmlt_debug_eval", "fpt_debug_mlt", "fpt_debug_device_build",
                 "fpt_mmlt_init", "fpt_mmlt_render", "fpt_mmlt_get_stats", "fpt_mmlt_get_st_norms", "fpt_mmlt_download", "fpt_mmlt_debug_eval",
                 "fpt_mmlt_download_pixels", "fpt_mmlt_debug_eval_pixels", "fpt_debug_bpt_splat_entries",
-                "fpt_mlt_set_persistence", "fpt_mlt_restart_chains", "fpt_mlt_get_persistence"]
+                "fpt_mlt_set_persistence", "fpt_mlt_restart_chains", "fpt_mlt_get_persistence",
+                "fpt_mlt_set_chain_shard", "fpt_mlt_get_chain_shard", "fpt_mlt_finish"]
 
 # fpt_debug_device_build: the arrays of the last device build, by their `which` (name -> (which, dtype, columns)); rows: n triangles, n - 1 binary nodes or the wide nodes
 LBVH_CELL_DTYPE = np.dtype([("c", "<f4", 7), ("k", "u1", 7), ("k8", "u1"), ("leaf", "u1"), ("count", "u1"), ("spare", "u1", 2)])
@@ -598,8 +599,9 @@ class Renderer:
         return (self.pssmlt_options.bpt.max_path_length + 1) * 3
 
     def pssmlt_state(self):
-        """what the last pssmlt_render left: light_u / eye_u (dims, n_chains), path_value (n_chains, 4), path_pdf, rejections, seeds (n_chains), presample (n_pixels, 4)"""
-        n = int(self.pssmlt_options.n_chains); d = self._pssmlt_dims(); npx = self.res[0] * self.res[1]
+        """what the last pssmlt_render left: light_u / eye_u (dims, n_chains), path_value (n_chains, 4), path_pdf, rejections, seeds (n_chains), presample (n_pixels, 4).
+        Under a chain shard (mlt_set_chain_shard) n_chains is the shard's n_local: its chains in slot order"""
+        n = self._mlt_n_local(self.pssmlt_options.n_chains); d = self._pssmlt_dims(); npx = self.res[0] * self.res[1]
         out = dict(light_u=np.zeros((d, n), np.float32), eye_u=np.zeros((d, n), np.float32), path_value=np.zeros((n, 4), np.float32), path_pdf=np.zeros(n, np.float32),
                    rejections=np.zeros(n, np.uint32), seeds=np.zeros(n, np.uint32), presample=np.zeros((npx, 4), np.float32))
         self._check(self.L.fpt_pssmlt_download(self.ctx, *[C.c_void_p(out[k].ctypes.data) for k in ("light_u", "eye_u", "path_value", "path_pdf", "rejections", "seeds", "presample")]))
@@ -641,9 +643,9 @@ class Renderer:
         """what the last mmlt_render left: light_u / eye_u (dims, n_chains), path_value (n_chains, 4), path_pdf, rejections, seeds (cells of the table), st (s | t << 8) per
         chain, and the technique table (n_techniques, n_pixels, 4).  With lens_techniques = 1 the table has the L - 1 lens techniques after the others, and the
         state also holds table_pixel (L - 1, n_pixels), the pixel of every lens cell's sample, and path_pixel (n_chains), the pixel of every chain's state (0xFFFFFFFF:
-        none / the one of eye coordinates 3 and 4)"""
+        none / the one of eye coordinates 3 and 4).  Under a chain shard (mlt_set_chain_shard) n_chains is the shard's n_local: its chains in slot order"""
         L = self._mmlt_L()
-        n = int(self.mmlt_options.mlt.n_chains); d = (L + 1) * 3; npx = self.res[0] * self.res[1]
+        n = self._mlt_n_local(self.mmlt_options.mlt.n_chains); d = (L + 1) * 3; npx = self.res[0] * self.res[1]
         lens = int(self.mmlt_options.lens_techniques) != 0
         out = dict(light_u=np.zeros((d, n), np.float32), eye_u=np.zeros((d, n), np.float32), path_value=np.zeros((n, 4), np.float32), path_pdf=np.zeros(n, np.float32),
                    rejections=np.zeros(n, np.uint32), seeds=np.zeros(n, np.uint32), st=np.zeros(n, np.uint32), table=np.zeros((L * (L + 1) // 2 + (L - 1 if lens else 0), npx, 4), np.float32))
@@ -685,6 +687,38 @@ class Renderer:
         v = [C.c_uint32() for _ in range(4)]
         self._check(self.L.fpt_mlt_get_persistence(self.ctx, *[C.byref(x) for x in v]))
         return dict(zip(("reseeding", "startup_skips", "last_call_reseeded", "calls_since_reseed"), (int(x.value) for x in v)))
+
+    # -- chain shards, either Metropolis renderer: the same frame on any number of GPUs (fpt_mlt_set_chain_shard, include/fermat_pt_hip.h)
+    def mlt_set_chain_shard(self, rank, world):
+        """this context runs the global chains rank + i * world, chain rank + i * world in slot i; with world > 1 a render call leaves its sums in the splat buffer and
+        waits for mlt_finish.  Drops live chains; (0, 1) is the renderer without shards"""
+        self._check(self.L.fpt_mlt_set_chain_shard(self.ctx, C.c_uint32(rank), C.c_uint32(world)))
+
+    def mlt_chain_shard(self):
+        """dict(rank, world, n_local, pending)"""
+        v = [C.c_uint32() for _ in range(4)]
+        self._check(self.L.fpt_mlt_get_chain_shard(self.ctx, *[C.byref(x) for x in v]))
+        return dict(zip(("rank", "world", "n_local", "pending"), (int(x.value) for x in v)))
+
+    def _mlt_n_local(self, n_chains):
+        """the chains a download returns: the shard's; without a Metropolis state the options' n_chains, so that the download itself says what is missing"""
+        n = C.c_uint32(0)
+        return int(n.value) if self.L.fpt_mlt_get_chain_shard(self.ctx, None, None, C.byref(n), None) == 0 else int(n_chains)
+
+    def mlt_splat_buffer(self):
+        """keep the chains' splat sums (int64, 3 per pixel, 2^-32 fixed point) in a torch tensor, so that the ranks of a chain shard can sum them between a render call
+        and mlt_finish (torch.distributed.all_reduce, or by hand between contexts on one GPU); returns it.  Call after the init, before the first render call"""
+        self.splats = self.torch.zeros((self.res[0] * self.res[1], 3), dtype=self.torch.int64, device=self.dev)
+        self.torch.cuda.synchronize(self.dev)
+        self._check(self.L.fpt_bpt_use_splat_buffer(self.ctx, C.c_void_p(self.splats.data_ptr())))
+        return self.splats
+
+    def mlt_finish(self, sync=False):
+        """the second half of a shard's render call: sums the ranks' splat sums and counters over the context's communicator (without one the caller has summed the
+        buffers itself) and folds them into the frame"""
+        self._check(self.L.fpt_mlt_finish(self.ctx, C.byref(self.view)))
+        if sync:
+            self.synchronize()
 
     def debug_mlt(self, op, arrays, params=(), n=None):
         """fpt_debug_mlt (layouts: include/fermat_pt_hip.h); arguments and result as debug_bpt's"""

@@ -30,7 +30,16 @@ struct BptLog { float4* val; uint32_t* chan; uint32_t* mask; uint32_t cap, mask_
 // sequence, PerturbedPrimaryCoords (src/bpt_samplers.h:90-155).  light_u / eye_u: (L+1)*3 dimensions each, laid out dim * n_chains + chain (src/bpt_samplers.h:100-103);
 // mutation: 0 Null, 1 Cauchy, 2 Independent, applied where a coordinate is read (fpt_bpt_device.h); a side whose *_perturbations flag is 0 is read as it
 // is.  Set = light_u != NULL.  The path id is the chain; the eye path's screen position is (coordinate 3, coordinate 4) and the lens sample is ignored (pssmlt.cu:391-397)
-struct ChainCoords { const float* light_u; const float* eye_u; uint32_t n_chains, step, mutation, light_perturbations, eye_perturbations; float radius; };
+// Chain shards (fpt_mlt_set_chain_shard): the arrays hold the n_chains chains of ONE rank, local chain c in slot c, and c is global chain
+// chain_first + c * chain_stride -- the id the mutation numbers are a function of.  (0, 1): the local chain is the global one
+// The view keeps its 40 bytes, and BptParams with it its 768 = twelve 64-byte lines of kernel arguments for every bidirectional kernel: the mutation (0..2) and the two
+// flags (0 / 1: whoever fills them normalises) share one word
+struct ChainCoords
+{
+	const float* light_u; const float* eye_u; uint32_t n_chains, step; uint16_t mutation; uint8_t light_perturbations, eye_perturbations; float radius;
+	uint32_t chain_first = 0u, chain_stride = 1u;
+};
+static_assert(sizeof(ChainCoords) == 40, "ChainCoords must keep its size: BptParams is the argument block of every bidirectional kernel");
 // Value sink: every frame contribution of eye path `id` is added to value[id] (all four components) and nothing else is written: no frame cell, no albedo
 // plane, no gbuffer, no log (the sinks of pssmlt.cu:257-304).  Set = value != NULL
 struct ValueSink { float4* value; };
@@ -91,6 +100,8 @@ struct BptParams
 	TechTable tech;
 	ChainTech fixed;
 };
+
+static_assert(sizeof(BptParams) == 768, "the argument block of the bidirectional kernels is twelve 64-byte lines (EXPERIMENTS 6l)");
 
 void launch_bpt_light_primary(const BptParams& p, hipStream_t s);
 void launch_bpt_light_vertices(const BptParams& p, uint32_t max_entries, hipStream_t s);

@@ -45,7 +45,8 @@ __device__ __forceinline__ float chain_coord(const ChainCoords& C, const float* 
 	const float cur = u[size_t(dim) * C.n_chains + chain];
 	const uint32_t mutation = perturb ? C.mutation : 0u;
 	if (mutation == 0u) return cur;
-	return mlt_perturbed_u(cur, mlt_mutation_number(instance, C.step, chain, side_offset + dim), mutation, C.radius);
+	// (the mutation number is the GLOBAL chain's: a rank's shard of the chains draws what the one-GPU run draws for them)
+	return mlt_perturbed_u(cur, mlt_mutation_number(instance, C.step, C.chain_first + chain * C.chain_stride, side_offset + dim), mutation, C.radius);
 }
 __device__ __forceinline__ float chain_light_coord(const BptParams& P, uint32_t chain, uint32_t dim) { return chain_coord(P.chain, P.chain.light_u, P.chain.light_perturbations, 0u, P.instance, chain, dim); }
 __device__ __forceinline__ float chain_eye_coord(const BptParams& P, uint32_t chain, uint32_t dim)

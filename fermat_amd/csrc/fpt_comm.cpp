@@ -266,6 +266,18 @@ int fpt_bpt_allreduce_splats(fpt_context* ctx, uint64_t n_int64)
 	});
 }
 
+} // extern "C"
+// the Metropolis renderers' chain shards (fpt_mlt_finish, fpt_mlt_api.cpp): the splat sums (ncclInt64, the call above on the Metropolis state's buffer) and the
+// call's counters (ncclUint64), summed over the ranks in place.  Integer sums: the result does not depend on the order RCCL adds in
+namespace fpt {
+void comm_allreduce_sum64(fpt_context* ctx, void* d_values, size_t n, bool is_signed, const char* who)
+{
+	require(ctx->comm != nullptr && d_values != nullptr && n > 0, (std::string(who) + ": no communicator or nothing to reduce").c_str());
+	nccl_check(rccl().AllReduce(d_values, d_values, n, is_signed ? ncclInt64 : ncclUint64, ncclSum, static_cast<ncclComm_t>(ctx->comm), ctx->stream), "ncclAllReduce");
+}
+}
+extern "C" {
+
 // PSFPT under tile sharding: every rank hands every other rank the cells its paths touched in the pass in flight (PsfRecord: key, three
 // fixed-point sums, count -- a few thousand per pass on the bench frame, 40 B each) and merges all of them, its own included, into its copy
 // of the global table; fpt_psfpt_finish then blends from equal tables on every rank.  One integer all-reduce tells everybody the counts, one

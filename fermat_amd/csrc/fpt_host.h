@@ -496,6 +496,12 @@ struct fpt_context
 	//      state the last render call left, that the table, seeds, st_norms and st_chains are those of the period's reseed, and that period_brightness, period_camera,
 	//      period_res and period_scene describe that reseed.  Only a render call that ran its chain loop sets it; drop_chains() and reset() clear it, and a call that finds the
 	//      scene's generation (a geometry build or refit, an emitter-table replace), the view's camera or its resolution changed treats the chains as not live.
+	//   7. Chain shards (fpt_mlt_set_chain_shard).  shard_rank < shard_world <= n_chains and shard_n = mlt_shard_count(n_chains, shard_rank, shard_world)
+	//      whenever `mode` is not None; an init leaves (0, 1) and shard_n = n_chains.  The arrays keep the size the init gave them: slots [0, shard_n) of every chain
+	//      array hold this rank's chains, global chain shard_rank + slot * shard_world in `slot`, and the coordinates' stride is shard_n; live chains are chains of the
+	//      shard that is set (a shard change drops them).  `pending` implies shard_world > 1 and that the splat buffer holds the sums of this rank's chains for the
+	//      last render call, not yet folded into the frame: only a render call that returned without a throw sets it, only fpt_mlt_finish and reset() clear it (a
+	//      render call that throws leaves it clear: a render call is refused while it is set), and while it is set the shard cannot change.
 	struct MltState
 	{
 		enum Mode : uint32_t { None, Pssmlt, Mmlt };
@@ -522,6 +528,8 @@ struct fpt_context
 		bool live = false, last_call_reseeded = false;
 		float period_brightness = 0.0f;                                    // image_brightness of the period's reseed
 		fpt_camera period_camera{}; uint32_t period_res[2] = { 0, 0 }; uint64_t period_scene = 0;
+		uint32_t shard_rank = 0, shard_world = 1, shard_n = 0;           // invariant 7
+		bool pending = false;
 		void drop_chains() { live = false; calls_since_reseed = 0; period_brightness = 0.0f; }
 		uint32_t dims() const { return (opt.bpt.max_path_length + 1u) * 3u; }      // coordinates per chain and side
 		// the list: v(array, its elements in mode `of` for the shape above, the byte it is cleared with).  new_value and the coordinates hold max(n_pixels, n_chains)
@@ -545,6 +553,7 @@ struct fpt_context
 			each_array(None, [](auto& a, size_t, int) { a.release(); });
 			st_norms.clear(); st_chains.clear(); stats = fpt_mmlt_stats{};
 			reseeding = 1; startup_skips = 0; last_call_reseeded = false; period_camera = fpt_camera{}; period_res[0] = period_res[1] = 0; period_scene = 0; drop_chains();
+			shard_rank = 0; shard_world = 1; shard_n = 0; pending = false;
 		}
 	} mlt;
 	bool profiling = false;
@@ -595,6 +604,9 @@ namespace fpt { ContribLog lane_log(fpt_context* ctx, uint32_t first); }
 // where the samples of a PT / PSFPT pass go: the frame itself, or (`batched`: passes in flight) the albedo planes and the contribution log of the pixel
 // range that starts at `first` (fpt_api.cpp)
 namespace fpt { void sample_targets(fpt_context* ctx, const FrameBufferDev& real_fb, bool batched, uint32_t first, FrameBufferDev& fb, ContribLog& log); }
+// fpt_comm.cpp, for fpt_mlt_finish (inside the caller's `guarded`): the in-place sum over the ranks of n 64-bit integers on the context's stream, ncclInt64 or ncclUint64;
+// throws "<who>: ..." without a communicator
+namespace fpt { void comm_allreduce_sum64(fpt_context* ctx, void* d_values, size_t n, bool is_signed, const char* who); }
 // BPT, shared light vertices (fpt_bpt_api.cpp): this rank's vertices of the batch in flight -> ctx->bpt.lv_send (returns their number); wire records -> the store
 namespace fpt { uint32_t bpt_pack_own_vertices(fpt_context* ctx); void bpt_import_vertices(fpt_context* ctx, const LightVertexWire* d_records, uint32_t count); }
 

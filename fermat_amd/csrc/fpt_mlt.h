@@ -25,6 +25,9 @@ struct MltChains
 	const uint32_t* new_pixel; uint32_t* path_pixel;
 	// 0: a skipped step of a reseeding call (startup_skips, cmlt.cu:1110): the acceptance test, the commit, `rejections` and the counters as ever, but nothing is deposited
 	uint32_t accumulate;
+	// chain shards (ChainCoords, fpt_bpt.h): slot c of the arrays above is global chain chain_first + c * chain_stride, whose mutation numbers the step draws; n_chains
+	// counts the slots, pdf_norm is the caller's (of ALL ranks' chains).  A block cleared with memset has stride 0: the caller sets (0, 1)
+	uint32_t chain_first = 0u, chain_stride = 1u;
 };
 
 // Largest single value of the seed CDF: a path value above 2^31 counts 2^31 (its integer is 2^63, the largest a uint64 sum can take once)
@@ -40,7 +43,9 @@ void launch_mlt_seed_cdf(const float4* value, uint32_t n, unsigned long long* q,
 // sample_seeds (pssmlt.cu:327-338) on the integer CDF: r = (i + randfloat(i, 0)) / n_seeds in float, target = uint64(double(r) * double(total)), the seed = the first
 // entry whose CDF exceeds the target, at most the last non-empty entry.  total == 0: nothing is written
 // common_offset >= 0 (the multiplexed renderer): the targets are mlt_seed_target's (fpt_mlt_host.h) -- exact integers, one offset of common_offset * 2^-24 for all strata
-void launch_mlt_sample_seeds(const unsigned long long* cdf, uint32_t n, uint32_t n_seeds, uint32_t* seeds, hipStream_t s, int common_offset = -1);
+// chain shards: seeds[i], i < mlt_shard_count(n_seeds, chain_first, chain_stride), is the seed of GLOBAL stratum chain_first + i * chain_stride of the n_seeds
+void launch_mlt_sample_seeds(const unsigned long long* cdf, uint32_t n, uint32_t n_seeds, uint32_t* seeds, hipStream_t s, int common_offset = -1, uint32_t chain_first = 0u,
+                             uint32_t chain_stride = 1u);
 // recover_primary_coordinates (pssmlt.cu:350-407): chain c gets every coordinate light and eye sub-path seeds[c] read in the pass `tiled` describes (its sequence,
 // instance and resolution), through the accessors that pass used.  Eye vertex 0 (the lens) is zeros
 void launch_mlt_recover_coordinates(const BptParams& tiled, const uint32_t* seeds, uint32_t n_chains, float* light_u, float* eye_u, hipStream_t s);
@@ -57,7 +62,9 @@ void launch_mmlt_start_chains(const uint32_t* seeds, uint32_t n_chains, uint32_t
 void launch_mmlt_block_ends(const unsigned long long* cdf, uint32_t n_tech, uint32_t n_paths, unsigned long long* ends, hipStream_t s);
 // mmlt_swap_kernel (cmlt.cu:496-544): st_new[c] = mlt_swap_proposal(st[c], mutation number of (instance, step, c, mlt_swap_dim(L)))
 // lens: mlt_swap_proposal_lens, the ring with the t = 1 stop
-void launch_mmlt_swap(const uint32_t* st, uint32_t* st_new, uint32_t n_chains, uint32_t L, uint32_t instance, uint32_t step, hipStream_t s, bool lens = false);
+// chain shards: slot c draws the number of global chain chain_first + c * chain_stride
+void launch_mmlt_swap(const uint32_t* st, uint32_t* st_new, uint32_t n_chains, uint32_t L, uint32_t instance, uint32_t step, hipStream_t s, bool lens = false, uint32_t chain_first = 0u,
+                      uint32_t chain_stride = 1u);
 // probes (fpt_debug_mlt ops 3 and 4)
 void launch_debug_mmlt_tech(uint32_t n, uint32_t L, const uint32_t* st, uint32_t* index, uint32_t* back, hipStream_t s);
 void launch_debug_mmlt_swap(uint32_t n, uint32_t L, uint32_t instance, uint32_t step, const uint32_t* st, const uint32_t* chain, uint32_t* st_new, float* m_out, hipStream_t s);

@@ -41,9 +41,13 @@ __global__ void __launch_bounds__(MLT_BLOCK) seed_values_kernel(const float4* __
 }
 
 // common_offset < 0: PSSMLT's rule, one jitter per stratum in float; >= 0 (the multiplexed renderer): the exact integer targets of mlt_seed_target with that offset
-__global__ void __launch_bounds__(MLT_BLOCK) sample_seeds_kernel(const unsigned long long* __restrict__ cdf, uint32_t n, uint32_t n_seeds, uint32_t* __restrict__ seeds, int common_offset)
+// chain shards: thread i of n_local finds the seed of GLOBAL stratum seed_id = chain_first + i * chain_stride < n_seeds and keeps it in slot i
+__global__ void __launch_bounds__(MLT_BLOCK) sample_seeds_kernel(const unsigned long long* __restrict__ cdf, uint32_t n, uint32_t n_seeds, uint32_t* __restrict__ seeds, int common_offset,
+                                                                 uint32_t n_local, uint32_t chain_first, uint32_t chain_stride)
 {
-	const uint32_t seed_id = threadIdx.x + blockIdx.x * blockDim.x;
+	const uint32_t slot = threadIdx.x + blockIdx.x * blockDim.x;
+	if (slot >= n_local) return;
+	const uint32_t seed_id = chain_first + slot * chain_stride;
 	if (seed_id >= n_seeds) return;
 	const unsigned long long total = cdf[n - 1];
 	if (total == 0) return;
@@ -58,7 +62,7 @@ __global__ void __launch_bounds__(MLT_BLOCK) sample_seeds_kernel(const unsigned 
 	// the last non-empty entry: the first with cdf >= total
 	lo = 0; hi = n - 1;
 	while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (cdf[mid] >= total) hi = mid; else lo = mid + 1; }
-	seeds[seed_id] = ub < lo ? ub : lo;
+	seeds[slot] = ub < lo ? ub : lo;
 }
 
 __global__ void __launch_bounds__(MLT_BLOCK) recover_coordinates_kernel(const BptParams P, const uint32_t* __restrict__ seeds, uint32_t n_chains, float* __restrict__ light_u, float* __restrict__ eye_u)
@@ -84,9 +88,10 @@ __global__ void __launch_bounds__(MLT_BLOCK) accept_reject_kernel(const MltChain
 	if (chain < C.n_chains)
 	{
 		const uint32_t n = C.n_chains, dims = (C.max_path_length + 1u) * 3u;
+		const uint32_t gid = C.chain_first + chain * C.chain_stride;          // whose mutation numbers this slot draws (chain shards)
 		const uint32_t light_mut = C.light_perturbations ? C.mutation : 0u, eye_mut = C.eye_perturbations ? C.mutation : 0u;
-		auto new_light = [&](uint32_t d) { const float u = C.light_u[size_t(d) * n + chain]; return light_mut ? mlt_perturbed_u(u, mlt_mutation_number(C.instance, C.step, chain, d), light_mut, C.radius) : u; };
-		auto new_eye = [&](uint32_t d) { const float u = C.eye_u[size_t(d) * n + chain]; return eye_mut ? mlt_perturbed_u(u, mlt_mutation_number(C.instance, C.step, chain, dims + d), eye_mut, C.radius) : u; };
+		auto new_light = [&](uint32_t d) { const float u = C.light_u[size_t(d) * n + chain]; return light_mut ? mlt_perturbed_u(u, mlt_mutation_number(C.instance, C.step, gid, d), light_mut, C.radius) : u; };
+		auto new_eye = [&](uint32_t d) { const float u = C.eye_u[size_t(d) * n + chain]; return eye_mut ? mlt_perturbed_u(u, mlt_mutation_number(C.instance, C.step, gid, dims + d), eye_mut, C.radius) : u; };
 		// perform the MH acceptance-rejection test
 		float4 w = C.new_value[chain];
 		// the lens techniques: a t = 1 proposal arrives as c, the light-tracing sample BEFORE the multiplication by light_weight = 1 / n_pixels (the table's cell).  What it
@@ -124,7 +129,7 @@ __global__ void __launch_bounds__(MLT_BLOCK) accept_reject_kernel(const MltChain
 		// (a skipped step of a reseeding call deposits nothing: MltChains::accumulate)
 		if (C.accumulate && old_pdf > 0) splat(old_pixel, C.pdf_norm * (1.0f - ar), C.path_value[chain], old_pdf);
 		if (C.accumulate && new_pdf > 0) splat(new_pixel, C.pdf_norm * ar, w, new_pdf);
-		if (mlt_mutation_number(C.instance, C.step, chain, dims * 2u) * old_pdf < new_pdf)
+		if (mlt_mutation_number(C.instance, C.step, gid, dims * 2u) * old_pdf < new_pdf)
 		{
 			C.path_value[chain] = w;
 			C.path_pdf[chain] = new_pdf;
@@ -191,13 +196,14 @@ __global__ void __launch_bounds__(MLT_BLOCK) mmlt_block_ends_kernel(const unsign
 	if (k < n_tech) ends[k] = cdf[size_t(k + 1u) * n_paths - 1u];
 }
 
-__global__ void __launch_bounds__(MLT_BLOCK) mmlt_swap_kernel(const uint32_t* __restrict__ st, uint32_t* __restrict__ st_new, uint32_t n_chains, uint32_t L, uint32_t instance, uint32_t step, bool lens)
+__global__ void __launch_bounds__(MLT_BLOCK) mmlt_swap_kernel(const uint32_t* __restrict__ st, uint32_t* __restrict__ st_new, uint32_t n_chains, uint32_t L, uint32_t instance, uint32_t step, bool lens,
+                                                              uint32_t chain_first, uint32_t chain_stride)
 {
 	const uint32_t c = threadIdx.x + blockIdx.x * blockDim.x;
 	if (c >= n_chains) return;
 	const uint32_t w = st[c];
 	// generate a candidate (s_new,t_new) pair with s_new + t_new = s + t: perform a random walk on s
-	const float u = mlt_mutation_number(instance, step, c, mlt_swap_dim(L));
+	const float u = mlt_mutation_number(instance, step, chain_first + c * chain_stride, mlt_swap_dim(L));
 	st_new[c] = lens ? mlt_swap_proposal_lens(w & 0xFFu, w >> 8, u) : mlt_swap_proposal(w & 0xFFu, w >> 8, u);
 }
 
@@ -244,8 +250,11 @@ void launch_mlt_seed_cdf(const float4* value, uint32_t n, unsigned long long* q,
 	hipLaunchKernelGGL(seed_values_kernel, grid_for(n), dim3(MLT_BLOCK), 0, s, value, n, q, scaled_from < n ? scaled_from : n, scale);
 	(void)rocprim::inclusive_scan(scratch, scratch_bytes, static_cast<const unsigned long long*>(q), cdf, size_t(n), rocprim::plus<unsigned long long>(), s);
 }
-void launch_mlt_sample_seeds(const unsigned long long* cdf, uint32_t n, uint32_t n_seeds, uint32_t* seeds, hipStream_t s, int common_offset)
-{ hipLaunchKernelGGL(sample_seeds_kernel, grid_for(n_seeds), dim3(MLT_BLOCK), 0, s, cdf, n, n_seeds, seeds, common_offset); }
+void launch_mlt_sample_seeds(const unsigned long long* cdf, uint32_t n, uint32_t n_seeds, uint32_t* seeds, hipStream_t s, int common_offset, uint32_t chain_first, uint32_t chain_stride)
+{
+	const uint32_t n_local = mlt_shard_count(n_seeds, chain_first, chain_stride);
+	if (n_local) hipLaunchKernelGGL(sample_seeds_kernel, grid_for(n_local), dim3(MLT_BLOCK), 0, s, cdf, n, n_seeds, seeds, common_offset, n_local, chain_first, chain_stride);
+}
 void launch_mlt_recover_coordinates(const BptParams& tiled, const uint32_t* seeds, uint32_t n_chains, float* light_u, float* eye_u, hipStream_t s)
 { hipLaunchKernelGGL(recover_coordinates_kernel, grid_for(n_chains), dim3(MLT_BLOCK), 0, s, tiled, seeds, n_chains, light_u, eye_u); }
 void launch_mlt_accept_reject(const MltChains& c, hipStream_t s) { hipLaunchKernelGGL(accept_reject_kernel, grid_for(c.n_chains), dim3(MLT_BLOCK), 0, s, c); }
@@ -255,8 +264,8 @@ void launch_mmlt_start_chains(const uint32_t* seeds, uint32_t n_chains, uint32_t
 { hipLaunchKernelGGL(mmlt_start_chains_kernel, grid_for(n_chains), dim3(MLT_BLOCK), 0, s, seeds, n_chains, n_paths, L, st, path_seeds, tech_chains, lens); }
 void launch_mmlt_block_ends(const unsigned long long* cdf, uint32_t n_tech, uint32_t n_paths, unsigned long long* ends, hipStream_t s)
 { hipLaunchKernelGGL(mmlt_block_ends_kernel, grid_for(n_tech), dim3(MLT_BLOCK), 0, s, cdf, n_tech, n_paths, ends); }
-void launch_mmlt_swap(const uint32_t* st, uint32_t* st_new, uint32_t n_chains, uint32_t L, uint32_t instance, uint32_t step, hipStream_t s, bool lens)
-{ hipLaunchKernelGGL(mmlt_swap_kernel, grid_for(n_chains), dim3(MLT_BLOCK), 0, s, st, st_new, n_chains, L, instance, step, lens); }
+void launch_mmlt_swap(const uint32_t* st, uint32_t* st_new, uint32_t n_chains, uint32_t L, uint32_t instance, uint32_t step, hipStream_t s, bool lens, uint32_t chain_first, uint32_t chain_stride)
+{ hipLaunchKernelGGL(mmlt_swap_kernel, grid_for(n_chains), dim3(MLT_BLOCK), 0, s, st, st_new, n_chains, L, instance, step, lens, chain_first, chain_stride); }
 void launch_debug_mmlt_tech(uint32_t n, uint32_t L, const uint32_t* st, uint32_t* index, uint32_t* back, hipStream_t s)
 { hipLaunchKernelGGL(debug_mmlt_tech_kernel, grid_for(n), dim3(MLT_BLOCK), 0, s, n, L, st, index, back); }
 void launch_debug_mmlt_swap(uint32_t n, uint32_t L, uint32_t instance, uint32_t step, const uint32_t* st, const uint32_t* chain, uint32_t* st_new, float* m_out, hipStream_t s)

@@ -13,7 +13,11 @@
 // that finds live chains CONTINUES them -- rescale, the chain loop with a real mutation at step 0, resolve, the counters' read-back; no presampling pass, no CDF, no seeds, no
 // read-back before the loop -- under the normalisation of the period's reseed (CMLTOptions::reseeding, cmlt.cu:1013-1016; the reference's PSSMLT has no such option: it gets
 // one here because the render loop is shared).  startup_skips = K: the first K steps of a reseeding call deposit nothing (cmlt.cu:1097,1110).
-// Out of scope: passes in flight, deferral, tile sharding / multi-GPU, use_vpls, charted swaps.
+// Multi-GPU is a shard of the CHAINS, not of the pixels (fpt_mlt_set_chain_shard, MltState invariant 7): rank r of W runs the global chains r + i * W in the
+// slots i of its arrays, with the mutation numbers, seeds and normalisation of the global chains; every rank runs the whole presampling pass and holds the same CDF.  A
+// render call of such a shard stops before the resolve and is PENDING; fpt_mlt_finish sums the ranks' integer splat sums and counters (RCCL, or the caller has done it) and
+// resolves: every rank then holds the frame one GPU renders, bit for bit, for any W.
+// Out of scope: passes in flight, deferral, pixel-tile sharding, a sharded presampling pass, use_vpls, charted swaps.
 #include "fpt_host.h"
 #include "fpt_mlt.h"
 #include "fpt_mlt_host.h"
@@ -35,8 +39,9 @@ template <typename A> void zero(A& a, size_t n, hipStream_t s) { if (n) FPT_HIP_
 
 ChainCoords chain_view(Mlt& m, uint32_t n, uint32_t step, uint32_t mutation)
 {
-	ChainCoords c; c.light_u = m.light_u.ptr; c.eye_u = m.eye_u.ptr; c.n_chains = n; c.step = step; c.mutation = mutation;
-	c.light_perturbations = m.opt.light_perturbations; c.eye_perturbations = m.opt.eye_perturbations; c.radius = m.opt.radius;
+	ChainCoords c; c.light_u = m.light_u.ptr; c.eye_u = m.eye_u.ptr; c.n_chains = n; c.step = step; c.mutation = uint16_t(mutation);
+	c.light_perturbations = m.opt.light_perturbations ? 1u : 0u; c.eye_perturbations = m.opt.eye_perturbations ? 1u : 0u; c.radius = m.opt.radius;          // (flags: one byte each)
+	c.chain_first = 0u; c.chain_stride = 1u;          // (debug_eval's sets are nobody's chains; the chain loop names its shard)
 	return c;
 }
 
@@ -67,6 +72,7 @@ void init(fpt_context* ctx, const fpt_pssmlt_options& opts, uint32_t mmlt_freque
 		m.allocate(mode, ctx->stream);
 		if (mode == Mlt::Mmlt) { m.st_norms.assign(size_t(L + 2) * (L + 2), 0.0f); m.st_chains.assign(size_t(L + 2) * (L + 2), 0u); }
 		m.stats.n_chains = m.n_chains; m.stats.chain_length = m.chain_length;
+		m.shard_rank = 0u; m.shard_world = 1u; m.shard_n = m.n_chains;          // invariant 7
 		m.mode = mode;
 	}
 	catch (...) { m.reset(); if (bpt_made) ctx->bpt.reset(); throw; }
@@ -89,9 +95,13 @@ void render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_vie
 	need(ctx->tree.valid, who, "create_geometry has not been called");
 	need(ctx->emitters.valid, who, "fpt_mesh_lights_init has not been called");
 	need(view->res_x * view->res_y == m.n_pixels, who, "the view's resolution differs from ", mode == Mlt::Mmlt ? "fpt_mmlt_init's" : "fpt_pssmlt_init's");
+	{ const std::string refusal = mlt_render_pending_refusal(who, m.pending); if (!refusal.empty()) throw std::runtime_error(refusal); }
 	hipStream_t s = ctx->stream;
 	const bool mmlt = mode == Mlt::Mmlt, lens = m.lens;
 	const uint32_t n_pixels = m.n_pixels, n_chains = m.n_chains, L = m.opt.bpt.max_path_length, n_tech = m.n_tech, n_cells = n_tech * n_pixels, W = L + 2u;
+	// the chain shard (invariant 7): this rank runs n_local chains, slot i being global chain first + i * stride.  n_chains stays the count of ALL ranks' chains: what the
+	// seeds are strata of and what the normalisation divides by.  Everything before the seeds is computed in full on every rank, from the same numbers: identical copies
+	const uint32_t n_local = m.shard_n, first = m.shard_rank, stride = m.shard_world;
 	const FrameBufferDev fb = fb_dev(view->fb);
 	// does this call continue the chains the last one left?  (MltState, invariant 6.)  Whatever happens below, they are live again only once the chain loop has run
 	const bool continuing = !mlt_call_reseeds(instance, m.reseeding, chains_live(ctx, m, view));
@@ -121,7 +131,7 @@ void render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_vie
 		// their technique (a lens cell holds c, the sample before the multiplication by light_weight = 1 / n_pixels; what it adds to the frame, and so what it counts here, is
 		// c * light_weight).  `-pssmlt` jitters every stratum on its own; `-mmlt` takes one offset for all strata (mlt_seed_target)
 		launch_mlt_seed_cdf(m.table.ptr, n_cells, m.q.ptr, m.cdf.ptr, m.scan_scratch.ptr, m.scan_scratch.count, s, lens ? mlt_tech_count(L) * n_pixels : n_cells, 1.0f / float(n_pixels));
-		launch_mlt_sample_seeds(m.cdf.ptr, n_cells, n_chains, m.seeds.ptr, s, mmlt ? int(mlt_seed_offset(instance)) : -1);
+		launch_mlt_sample_seeds(m.cdf.ptr, n_cells, n_chains, m.seeds.ptr, s, mmlt ? int(mlt_seed_offset(instance)) : -1, first, stride);
 		// the CDF at the ends of the techniques' blocks; `-pssmlt`'s one block ends where the CDF does, and is read from there
 		const unsigned long long* d_ends = m.cdf.ptr + (n_cells - 1u);
 		if (mmlt) { launch_mmlt_block_ends(m.cdf.ptr, n_tech, n_pixels, m.ends.ptr, s); d_ends = m.ends.ptr; }
@@ -145,25 +155,25 @@ void render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_vie
 				m.st_norms[(w & 0xFFu) + (w >> 8) * W] = mlt_image_brightness(ends[k] - (k ? ends[k - 1] : 0ull), n_pixels);
 			}
 		}
-		if (total == 0) return;          // a black frame: no sample to start a chain from, the frame is only rescaled
+		if (total == 0) { m.pending = stride > 1u; return; }          // a black frame: no sample to start a chain from, the frame is only rescaled (on every rank: the total is everybody's)
 		// the path whose coordinates start each chain: `-pssmlt`'s seed itself; `-mmlt`'s seed is a cell, which gives the chain its technique as well
 		const uint32_t* path_seeds = m.seeds.ptr;
 		if (mmlt)
 		{
 			zero(m.tech_chains, n_tech, s);
-			launch_mmlt_start_chains(m.seeds.ptr, n_chains, n_pixels, L, m.st.ptr, m.path_seeds.ptr, m.tech_chains.ptr, s, lens);
+			launch_mmlt_start_chains(m.seeds.ptr, n_local, n_pixels, L, m.st.ptr, m.path_seeds.ptr, m.tech_chains.ptr, s, lens);          // (counts this rank's chains)
 			path_seeds = m.path_seeds.ptr;
 		}
 		// recover the primary coordinates of the selected seed paths
-		launch_mlt_recover_coordinates(tiled, path_seeds, n_chains, m.light_u.ptr, m.eye_u.ptr, s);
+		launch_mlt_recover_coordinates(tiled, path_seeds, n_local, m.light_u.ptr, m.eye_u.ptr, s);
 		// initialize the initial path pdfs and the rejection counters to zero
-		zero(m.path_pdf, n_chains, s); zero(m.rejections, n_chains, s);
+		zero(m.path_pdf, n_local, s); zero(m.rejections, n_local, s);
 	}
 	zero(m.counts, 2, s);
 	MltChains C; std::memset(&C, 0, sizeof(C));
 	C.light_u = m.light_u.ptr; C.eye_u = m.eye_u.ptr; C.new_value = m.new_value.ptr; C.path_value = m.path_value.ptr; C.path_pdf = m.path_pdf.ptr; C.rejections = m.rejections.ptr;
 	C.splat = b.splat_ptr(); C.counts = m.counts.ptr;
-	C.n_chains = n_chains; C.max_path_length = L; C.instance = instance;
+	C.n_chains = n_local; C.chain_first = first; C.chain_stride = stride; C.max_path_length = L; C.instance = instance;
 	C.light_perturbations = m.opt.light_perturbations; C.eye_perturbations = m.opt.eye_perturbations; C.radius = m.opt.radius; C.pdf_norm = st.pdf_norm;
 	C.res_x = view->res_x; C.res_y = view->res_y;
 	ChainTech fixed = { nullptr, nullptr, nullptr };
@@ -176,7 +186,7 @@ void render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_vie
 	if (lens)
 	{
 		// a reseeding call: no chain has a state yet, its pixel is committed with the first accepted proposal (step 0 for a seed)
-		if (!continuing) FPT_HIP_CHECK(hipMemsetAsync(m.path_pixel.ptr, 0xFF, n_chains * sizeof(uint32_t), s));
+		if (!continuing) FPT_HIP_CHECK(hipMemsetAsync(m.path_pixel.ptr, 0xFF, n_local * sizeof(uint32_t), s));
 		C.new_pixel = m.new_pixel.ptr; C.path_pixel = m.path_pixel.ptr;
 		fixed.new_pixel = m.new_pixel.ptr;
 	}
@@ -188,19 +198,21 @@ void render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_vie
 		// steps are counted per call (cmlt.cu:1118)
 		const bool swap = mlt_is_swap_step(m.mmlt_frequency, l);
 		const uint32_t mutation = swap ? 0u : mlt_mutation_type(m.opt.independent_samples, instance, l, continuing);
-		if (swap) launch_mmlt_swap(m.st.ptr, m.st_new.ptr, n_chains, L, instance, l, s, lens);
+		if (swap) launch_mmlt_swap(m.st.ptr, m.st_new.ptr, n_local, L, instance, l, s, lens, first, stride);
 		// reset the new path values
-		zero(m.new_value, n_chains, s);
+		zero(m.new_value, n_local, s);
 		// sample a set of bidirectional paths corresponding to our current primary coordinates
-		const ChainCoords chain = chain_view(m, n_chains, l, mutation);
+		ChainCoords chain = chain_view(m, n_local, l, mutation);
+		chain.chain_first = first; chain.chain_stride = stride;
 		fixed.st = swap ? m.st_new.ptr : m.st.ptr;
-		bpt_sample_paths(ctx, instance, view, n_chains, &chain, m.new_value.ptr, nullptr, nullptr, mmlt ? &fixed : nullptr);
+		bpt_sample_paths(ctx, instance, view, n_local, &chain, m.new_value.ptr, nullptr, nullptr, mmlt ? &fixed : nullptr);
 		// and perform the usual acceptance-rejection step
 		// (the first startup_skips steps of a reseeding call deposit nothing, cmlt.cu:1110; a continuing call's chains are burnt in: every step deposits)
 		C.step = l; C.mutation = mutation; C.swap = swap ? 1u : 0u; C.accumulate = continuing || l >= m.startup_skips ? 1u : 0u;
 		launch_mlt_accept_reject(C, s);
 	}
-	launch_mlt_resolve(fb.ch[FPT_FB_COMPOSITED_C], b.splat_ptr(), n_pixels, s);
+	// one rank of several: the sums stay in the splat buffer for fpt_mlt_finish, which adds the other ranks' before it resolves
+	if (stride == 1u) launch_mlt_resolve(fb.ch[FPT_FB_COMPOSITED_C], b.splat_ptr(), n_pixels, s);
 	FPT_HIP_CHECK(hipGetLastError());
 	unsigned long long counts[2] = { 0, 0 }, mcounts[3] = { 0, 0, 0 };
 	std::vector<uint32_t> tech_chains(mmlt && !continuing ? n_tech : 0u, 0u);          // (the chains seeded per technique are the reseed's)
@@ -221,6 +233,41 @@ void render(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_vie
 	}
 	else ++m.calls_since_reseed;
 	m.live = true;
+	m.pending = stride > 1u;
+}
+
+// fpt_mlt_finish: the second half of a shard's render call (MltState, invariant 7)
+void finish(fpt_context* ctx, const fpt_rendering_context_view* view)
+{
+	const char* who = "fpt_mlt_finish";
+	Mlt& m = any_mode(ctx, who);
+	need(view != nullptr, who, "null view");
+	{ const std::string refusal = mlt_finish_refusal(m.pending, m.shard_world, ctx->comm ? uint32_t(ctx->comm_world) : 0u); if (!refusal.empty()) throw std::runtime_error(refusal); }
+	need(view->res_x * view->res_y == m.n_pixels, who, "the view's resolution differs from the init's");
+	BptState& b = ctx->bpt;
+	hipStream_t s = ctx->stream;
+	const bool mmlt = m.mode == Mlt::Mmlt;
+	const uint32_t L = m.opt.bpt.max_path_length, W = L + 2u, n_tech = mmlt ? m.n_tech : 0u;
+	if (ctx->comm)
+	{
+		// the sums of all ranks' chains: integers, so every rank gets the sums one GPU running all the chains has; then, once, the call's counters
+		comm_allreduce_sum64(ctx, b.splat_ptr(), size_t(3) * m.n_pixels, true, who);
+		fpt_mmlt_stats& st = m.stats;
+		// (the chains seeded per technique are the reseed's: a continuing call sends zeros and keeps what the period's finish folded)
+		std::vector<unsigned long long> h(5u + n_tech, 0ull);
+		h[0] = st.accepted; h[1] = st.rejected; h[2] = st.swaps_proposed; h[3] = st.swaps_accepted; h[4] = st.rays;
+		for (uint32_t k = 0; k < n_tech && m.last_call_reseeded; ++k) { const uint32_t w = mlt_tech_st(k, L, m.lens); h[5u + k] = m.st_chains[(w & 0xFFu) + (w >> 8) * W]; }
+		DeviceArray<unsigned long long> d; d.upload(h.data(), h.size(), s);
+		comm_allreduce_sum64(ctx, d.ptr, h.size(), false, who);
+		d.download(h.data(), h.size(), s);
+		FPT_HIP_CHECK(hipStreamSynchronize(s));
+		st.accepted = h[0]; st.rejected = h[1]; st.swaps_proposed = h[2]; st.swaps_accepted = h[3]; st.rays = h[4];
+		for (uint32_t k = 0; k < n_tech && m.last_call_reseeded; ++k) { const uint32_t w = mlt_tech_st(k, L, m.lens); m.st_chains[(w & 0xFFu) + (w >> 8) * W] = uint32_t(h[5u + k]); }
+	}
+	launch_mlt_resolve(fb_dev(view->fb).ch[FPT_FB_COMPOSITED_C], b.splat_ptr(), m.n_pixels, s);
+	FPT_HIP_CHECK(hipGetLastError());
+	FPT_HIP_CHECK(hipStreamSynchronize(s));
+	m.pending = false;
 }
 
 // the state the last render call left (any pointer may be NULL): the chains' arrays and the table; h_st for `-mmlt` alone
@@ -229,7 +276,7 @@ void download(fpt_context* ctx, Mlt::Mode mode, const char* who, float* h_light_
 {
 	Mlt& m = state_in(ctx, mode, who);
 	hipStream_t s = ctx->stream;
-	const size_t n = m.n_chains, nu = size_t(m.dims()) * n;
+	const size_t n = m.shard_n, nu = size_t(m.dims()) * n;          // the shard's chains, in slot order (invariant 7)
 	if (h_light_u) m.light_u.download(h_light_u, nu, s);
 	if (h_eye_u) m.eye_u.download(h_eye_u, nu, s);
 	if (h_path_value) m.path_value.download(reinterpret_cast<float4*>(h_path_value), n, s);
@@ -317,6 +364,29 @@ int fpt_mlt_set_persistence(fpt_context* ctx, uint32_t reseeding, uint32_t start
 		m.drop_chains();
 	});
 }
+// chain shards (MltState, invariant 7): which of the n_chains global chains this context runs
+int fpt_mlt_set_chain_shard(fpt_context* ctx, uint32_t rank, uint32_t world)
+{
+	return guarded(ctx, [&] {
+		Mlt& m = any_mode(ctx, "fpt_mlt_set_chain_shard");
+		const std::string refusal = mlt_shard_refusal(rank, world, m.n_chains, m.pending);
+		if (!refusal.empty()) throw std::runtime_error(refusal);
+		m.shard_rank = rank; m.shard_world = world; m.shard_n = mlt_shard_count(m.n_chains, rank, world);
+		m.drop_chains();
+	});
+}
+int fpt_mlt_get_chain_shard(fpt_context* ctx, uint32_t* rank, uint32_t* world, uint32_t* n_local, uint32_t* pending)
+{
+	return guarded(ctx, [&] {
+		const Mlt& m = any_mode(ctx, "fpt_mlt_get_chain_shard");
+		if (rank) *rank = m.shard_rank;
+		if (world) *world = m.shard_world;
+		if (n_local) *n_local = m.shard_n;
+		if (pending) *pending = m.pending ? 1u : 0u;
+	});
+}
+int fpt_mlt_finish(fpt_context* ctx, const fpt_rendering_context_view* view)
+{ return guarded(ctx, [&] { flush_deferred(ctx); finish(ctx, view); }); }
 int fpt_mlt_restart_chains(fpt_context* ctx)
 { return guarded(ctx, [&] { any_mode(ctx, "fpt_mlt_restart_chains").drop_chains(); }); }
 int fpt_mlt_get_persistence(fpt_context* ctx, uint32_t* reseeding, uint32_t* startup_skips, uint32_t* last_call_reseeded, uint32_t* calls_since_reseed)
@@ -364,7 +434,7 @@ int fpt_mmlt_download_pixels(fpt_context* ctx, uint32_t* h_table_pixel, uint32_t
 		hipStream_t s = ctx->stream;
 		const size_t n_lens_cells = size_t(m.opt.bpt.max_path_length - 1u) * m.n_pixels;
 		if (h_table_pixel && n_lens_cells) m.table_pixel.download(h_table_pixel, n_lens_cells, s);
-		if (h_path_pixel) m.path_pixel.download(h_path_pixel, m.n_chains, s);
+		if (h_path_pixel) m.path_pixel.download(h_path_pixel, m.shard_n, s);
 		FPT_HIP_CHECK(hipStreamSynchronize(s));
 	});
 }
@@ -419,7 +489,7 @@ int fpt_debug_mlt(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_params
 			C.radius = as_f32(h_params[6]); C.pdf_norm = as_f32(h_params[7]); C.res_x = h_params[8]; C.res_y = h_params[9];
 			require(n >= 1 && C.max_path_length >= 1 && C.max_path_length <= 15 && C.mutation <= 2u && C.res_x >= 1 && C.res_y >= 1 && uint64_t(C.res_x) * C.res_y < (1ull << 24),
 			        "fpt_debug_mlt: accept/reject: n, max_path_length (1..15), mutation (0..2) or resolution out of range");
-			C.n_chains = n; C.accumulate = op == 5 ? (h_params[10] ? 1u : 0u) : 1u;
+			C.n_chains = n; C.chain_first = 0u; C.chain_stride = 1u; C.accumulate = op == 5 ? (h_params[10] ? 1u : 0u) : 1u;
 			C.light_u = static_cast<float*>(arr(0)); C.eye_u = static_cast<float*>(arr(1)); C.new_value = static_cast<const float4*>(arr(2)); C.path_value = static_cast<float4*>(arr(3));
 			C.path_pdf = static_cast<float*>(arr(4)); C.rejections = static_cast<uint32_t*>(arr(5)); C.splat = static_cast<long long*>(arr(6)); C.counts = static_cast<unsigned long long*>(arr(9));
 			const size_t cells = size_t(C.res_x) * C.res_y * 3;

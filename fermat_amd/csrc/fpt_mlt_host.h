@@ -53,6 +53,33 @@ inline uint32_t mlt_accumulated_steps(uint32_t chain_length, uint32_t startup_sk
 inline std::string mlt_persistence_refusal(uint32_t reseeding)
 { return reseeding == 0u ? std::string("fpt_mlt_set_persistence: reseeding must be at least 1 (1: every call reseeds)") : std::string(); }
 
+// ---- chain shards (fpt_mlt_set_chain_shard): rank r of W owns the global chains g = r + i * W, i in [0, n_local), and keeps chain g in slot i of every
+// chain array.  Interleaved, not contiguous: `-mmlt` starts its chains sorted by technique and techniques differ in cost, so ranges would give the ranks unequal work
+// the chains of rank `rank`: those g < n_chains with g = rank (mod world); 0 for a rank outside the world
+FPT_HD uint32_t mlt_shard_count(uint32_t n_chains, uint32_t rank, uint32_t world) { return world != 0u && rank < world && rank < n_chains ? (n_chains - rank + world - 1u) / world : 0u; }
+// the global chain in slot `slot` of rank `rank`
+FPT_HD uint32_t mlt_shard_global(uint32_t slot, uint32_t rank, uint32_t world) { return rank + slot * world; }
+// why fpt_mlt_set_chain_shard refuses, or empty.  `pending`: a render call of a shard waits for fpt_mlt_finish
+inline std::string mlt_shard_refusal(uint32_t rank, uint32_t world, uint32_t n_chains, bool pending)
+{
+	const char* why = nullptr;
+	if (world == 0u) why = "world must be at least 1 (1: this context runs every chain)";
+	else if (rank >= world) why = "rank must be below world";
+	else if (world > n_chains) why = "world exceeds n_chains: a rank would own no chain";
+	else if (pending) why = "a render call waits for fpt_mlt_finish: the shard cannot change under its sums";
+	return why ? std::string("fpt_mlt_set_chain_shard: ") + why : std::string();
+}
+// the two refusals of the calls around a pending finish, or empty: a render call (`who`) while one waits; fpt_mlt_finish with none waiting; and fpt_mlt_finish on a
+// communicator of another size than the shard's world (comm_world 0: no communicator, the caller has summed the buffers)
+inline std::string mlt_render_pending_refusal(const char* who, bool pending)
+{ return pending ? std::string(who) + ": the previous render call of this chain shard waits for fpt_mlt_finish" : std::string(); }
+inline std::string mlt_finish_refusal(bool pending, uint32_t shard_world, uint32_t comm_world)
+{
+	if (!pending) return "fpt_mlt_finish: no render call is pending (a shard of world > 1 renders first; with world = 1 the render call resolves itself)";
+	if (comm_world != 0u && comm_world != shard_world) return "fpt_mlt_finish: the communicator's world size differs from the chain shard's world";
+	return std::string();
+}
+
 // ---- the multiplexed renderer (`-mmlt`): one bidirectional technique (s light vertices, t eye vertices) per chain ------------------------------------------
 // With light tracing off the techniques are t in [2, L + 1], s in [0, L + 1 - t]: L (L + 1) / 2 of them, numbered t-major (all techniques of t = 2, s rising, then
 // t = 3, ...): index = sum_{j = 2}^{t - 1} (L + 2 - j) + s.  Shared by the kernels (fpt_bpt.hip, fpt_mlt.hip) and the host.

@@ -571,6 +571,13 @@ static void set_mlt_persistence(int argc, char** argv, fpt_context* ctx, const c
 	}
 	if (reseeding != 1 || skips != 0) check(ctx, fpt_mlt_set_persistence(ctx, reseeding, skips), who);
 }
+// -gpus N: the Metropolis renderers shard their CHAINS over the ranks, not the pixels (fpt_mlt_set_chain_shard): every rank owns the whole frame -- so the inits get no
+// pixel list -- and runs the chains rank + i * N; after every render call fpt_mlt_finish sums the ranks' splat sums and counters over the context's communicator and
+// resolves, which leaves the SAME full frame on every rank, the one of one GPU bit for bit
+static void set_mlt_shard(RenderingContext& renderer, fpt_context* ctx, const char* who)
+{ if (renderer.world_size() > 1) check(ctx, fpt_mlt_set_chain_shard(ctx, uint32(renderer.rank()), uint32(renderer.world_size())), who); }
+static void finish_mlt_shard(RenderingContext& renderer, fpt_context* ctx, const fpt_rendering_context_view& v, const char* who)
+{ if (renderer.world_size() > 1) check(ctx, fpt_mlt_finish(ctx, &v), who); }
 void HipPSSMLT::init(int argc, char** argv, RenderingContext& renderer)
 {
 	fpt_pssmlt_options& p = m_options;
@@ -579,13 +586,15 @@ void HipPSSMLT::init(int argc, char** argv, RenderingContext& renderer)
 	const fpt_rendering_context_view v = renderer.view(0);
 	const SceneArrays& h = renderer.get_host_scene();
 	renderer.init_mesh_lights("mesh_lights.init");     // src/renderers/pssmlt.cu:465
-	check(ctx, fpt_pssmlt_init(ctx, &p, &v, h.samples_dir, renderer.shard_pixels(), renderer.shard_count()), "PSSMLT::init");
+	check(ctx, fpt_pssmlt_init(ctx, &p, &v, h.samples_dir, nullptr, v.res_x * v.res_y), "PSSMLT::init");
 	set_mlt_persistence(argc, argv, ctx, "PSSMLT::init (-reseeding)");
+	set_mlt_shard(renderer, ctx, "PSSMLT::init (-gpus)");
 }
 void HipPSSMLT::render(const uint32 instance, RenderingContext& renderer)
 {
 	const fpt_rendering_context_view v = renderer.view(instance);
 	check(renderer.get_hip_context(), fpt_pssmlt_render(renderer.get_hip_context(), instance, &v), "PSSMLT::render");
+	finish_mlt_shard(renderer, renderer.get_hip_context(), v, "PSSMLT::render (finish)");
 }
 
 // ---- HipMMLT: the reference's `-cmlt -charted-swaps 0` (CMLTOptions, src/renderers/cmlt.h) --------------------------------------------------
@@ -603,15 +612,17 @@ void HipMMLT::init(int argc, char** argv, RenderingContext& renderer)
 	const fpt_rendering_context_view v = renderer.view(0);
 	const SceneArrays& h = renderer.get_host_scene();
 	renderer.init_mesh_lights("mesh_lights.init");     // src/renderers/cmlt.cu:847-852
-	check(ctx, fpt_mmlt_init(ctx, &p, &v, h.samples_dir, renderer.shard_pixels(), renderer.shard_count()), "MMLT::init");
+	check(ctx, fpt_mmlt_init(ctx, &p, &v, h.samples_dir, nullptr, v.res_x * v.res_y), "MMLT::init");
 	set_mlt_persistence(argc, argv, ctx, "MMLT::init (-reseeding)");
+	set_mlt_shard(renderer, ctx, "MMLT::init (-gpus)");
 }
 void HipMMLT::render(const uint32 instance, RenderingContext& renderer)
 {
 	const fpt_rendering_context_view v = renderer.view(instance);
 	fpt_context* ctx = renderer.get_hip_context();
 	check(ctx, fpt_mmlt_render(ctx, instance, &v), "MMLT::render");
-	if (instance == 0)
+	finish_mlt_shard(renderer, ctx, v, "MMLT::render (finish)");          // (and the chains per technique printed below are all ranks')
+	if (instance == 0 && renderer.rank() == 0)
 	{
 		// the per-technique norms and the chains seeded with each technique (the table CMLT::render prints at instance 0, cmlt.cu:1060-1077)
 		const uint32 L = m_options.mlt.bpt.max_path_length, W = L + 2;

@@ -7,7 +7,8 @@
 //              [-intersector mt|watertight]  the triangle intersector the tree is built for (fpt_rt_set_intersector): fpt-MT (default) or the watertight fpt-WT
 //              [-lights host|device]       who builds the emitter tables: the host from the host mesh (default), or the device from the device mesh (the same tables)
 //              [-gpus N]   one process per GPU of this node (forked here), image rows interleaved over the ranks, frame gathered to rank 0
-//                          over RCCL (fpt_gather_framebuffer); -pt and -bpt
+//                          over RCCL (fpt_gather_framebuffer); -pt, -bpt and -psfpt.  -pssmlt and -mmlt shard their chains instead (fpt_mlt_set_chain_shard): every
+//                          rank ends a pass with the same full frame, the one of one GPU bit for bit
 //   fermat_hip -diff a.tga b.tga
 // As in the reference the pass loop runs i = 0..N inclusive (N+1 samples per pixel), the image is written as <output>.tga
 // through to_rgba, and -ref prints the RMSE of the 8-bit image against a reference TGA (diff_image, src/main.cu:63-96).
@@ -180,7 +181,7 @@ int main(int argc, char** argv)
 			renderer.render(i);
 			if (i == n_passes || (save_intermediate && ((i + 1) & i) == 0))
 			{
-				renderer.gather_frame(0);                    // N > 1: every rank's rows travel to rank 0 (collective)
+				renderer.gather_frame(0);                    // N > 1: every rank's rows travel to rank 0 (collective; -pssmlt / -mmlt: rows that are already equal on every rank)
 				if (rank != 0) continue;
 				renderer.download_rgba(rgba.data());
 				if (i == n_passes)

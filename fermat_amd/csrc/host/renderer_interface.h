@@ -209,8 +209,9 @@ struct HipBPT final : RendererInterface
 	void finish_sharded_pass(fpt_context* ctx, const fpt_rendering_context_view& v, uint32 passes_in_flight);
 };
 
-// the primary-sample-space Metropolis renderer behind RendererInterface (PSSMLT, src/renderers/pssmlt.h:101-130); `-pssmlt` on the command line.  One GPU, one
-// render call per pass (no passes in flight): include/fermat_pt_hip.h says what is and is not built
+// the primary-sample-space Metropolis renderer behind RendererInterface (PSSMLT, src/renderers/pssmlt.h:101-130); `-pssmlt` on the command line.  One
+// render call per pass (no passes in flight); under -gpus N the CHAINS are sharded over the ranks (fpt_mlt_set_chain_shard) and every render call ends with
+// fpt_mlt_finish, after which every rank holds the same full frame: include/fermat_pt_hip.h says what is and is not built
 struct HipPSSMLT final : RendererInterface
 {
 	void init(int argc, char** argv, RenderingContext& renderer) override;

@@ -400,7 +400,8 @@ int fpt_debug_bpt_splat_entries(fpt_context* ctx, uint32_t* h_entries, uint32_t*
  *   2. the seed CDF is the inclusive scan of floor(min(max_comp(value), 2^31) * 2^32) as uint64 (0 for a negative or non-finite value; sums wrap modulo 2^64);
  *      image_brightness = float(double(total) * 2^-32 / n_pixels)
  *   3. the chains' splats are the 2^-32 fixed-point integer sums of the light-tracing splats (above), not float atomics.
- * Not built: the per-(s,t) statistics the reference prints (st_norms), passes in flight, deferral, tile sharding / multi-GPU, use_vpls.  Chains that persist across
+ * Not built: the per-(s,t) statistics the reference prints (st_norms), passes in flight, deferral, pixel-tile sharding, use_vpls.  Multi-GPU shards the chains
+ * (fpt_mlt_set_chain_shard, below).  Chains that persist across
  * render calls are opt-in (fpt_mlt_set_persistence, below): by default every call reseeds, as the reference's PSSMLT does.
  * fpt_pssmlt_init replaces fpt_bpt_init (it initialises the bidirectional state itself, sized for max(n_pixels, n_chains) paths) and refuses, with a message that
  * names the option: bpt.use_vpls = 1, a tile-sharded context (d_pixels != NULL), n_chains = 0, spp * n_pixels < n_chains. */
@@ -471,7 +472,8 @@ int fpt_debug_mlt(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_params
  * length k = s + t - 1 >= 2 is s in [0, k], s = k being (k, 1); k = 1 proposes the chain's own technique.
  * Deviations: PSSMLT's three (above), the seeds' common offset (PSSMLT jitters every stratum on its own, in float), and the swap's acceptance test takes no st_norms ratio (the reference multiplies the test, not the splats, by
  * st_norms[new] / st_norms[old], cmlt.cu:375-377): the target is max_comp f_{s,t}(u) on the disjoint union of the techniques and the walk is symmetric.
- * Not built: charted swaps and path inversion, techniques with t = 0, single_connection = 1, passes in flight, tile sharding / multi-GPU.  Chains that persist across
+ * Not built: charted swaps and path inversion, techniques with t = 0, single_connection = 1, passes in flight, pixel-tile sharding.  Multi-GPU shards the chains
+ * (fpt_mlt_set_chain_shard, below).  Chains that persist across
  * render calls (`reseeding`, `startup_skips`) are opt-in: fpt_mlt_set_persistence, below; by default every call reseeds.
  * fpt_mmlt_init replaces fpt_pssmlt_init / fpt_bpt_init and refuses what fpt_pssmlt_init refuses, lens_techniques > 1, and a technique table of 2^32 cells or more. */
 typedef struct fpt_mmlt_options
@@ -534,6 +536,29 @@ int fpt_mlt_set_persistence(fpt_context* ctx, uint32_t reseeding, uint32_t start
 int fpt_mlt_restart_chains(fpt_context* ctx);
 /* any pointer may be NULL.  last_call_reseeded: 1 when the last render call reseeded; calls_since_reseed: continuing calls since the period's reseed */
 int fpt_mlt_get_persistence(fpt_context* ctx, uint32_t* reseeding, uint32_t* startup_skips, uint32_t* last_call_reseeded, uint32_t* calls_since_reseed);
+
+/* ---- chain shards: the Metropolis renderers on several GPUs, the SAME frame bit for bit for any number of ranks ------------------------------------------------------
+ * A chain is independent of every other chain, its mutation numbers are a function of (instance, step, chain, dimension) and its deposits are integer sums: so the
+ * CHAINS are sharded, not the pixels.  fpt_mlt_set_chain_shard(rank r, world W) makes this context run the global chains g = r + i * W, i in [0, n_local),
+ * n_local = (n_chains - r + W - 1) / W -- interleaved, because `-mmlt` starts its chains sorted by technique and techniques differ in cost.  Global chain g lives in
+ * slot i of every chain array; the arrays keep the size the init gave them and the coordinates are laid out dim * n_local + slot.  Every rank runs the whole presampling
+ * pass, the CDF, st_norms and the brightness (deterministic: identical copies, nothing to exchange); slot i takes the seed of global stratum g of n_chains, the mutation
+ * numbers, the acceptance number and the swap direction of global chain g, and pdf_norm divides by the global n_chains.  (0, 1), what an init leaves, is the renderer
+ * without shards, bit for bit.
+ * Valid in either Metropolis mode after the mode's init; drops live chains; an init resets the shard to (0, 1).  Refused by name, before anything is written:
+ * world = 0, rank >= world, world > n_chains, and a change while a finish is pending.
+ * With world > 1 a render call runs as ever over the local chains but stops before the sums are folded into the frame: they stay in the splat buffer (the library's,
+ * or the caller's: fpt_bpt_use_splat_buffer) and the call is PENDING; a second render call while one is pending is refused.  fpt_mlt_finish(view) then, on a context
+ * with a communicator (fpt_comm_init / fpt_comm_adopt, whose world size must be the shard's), all-reduces the sums (int64, 3 * n_pixels) and, once, a small uint64
+ * array of the call's counters (accepted, rejected, swaps proposed, swaps accepted, rays, and after a reseeding call the chains seeded per technique), folds those into
+ * the statistics, and resolves; on a context without one it reduces nothing -- the caller has summed the ranks' buffers itself and written the sum into each -- and
+ * resolves.  After it every rank holds the same full frame, the one a single GPU renders.  Until then (and without a communicator, afterwards too) fpt_*_get_stats and
+ * the chains per technique are the shard's own.  fpt_mlt_finish is refused when nothing is pending: with world = 1 a render call resolves itself, as before.
+ * fpt_*_download, fpt_mmlt_download_pixels' h_path_pixel and the seeds return the shard's n_local chains in slot order; the table is everybody's. */
+int fpt_mlt_set_chain_shard(fpt_context* ctx, uint32_t rank, uint32_t world);
+/* any pointer may be NULL.  n_local: the chains this context runs; pending: 1 while a render call waits for fpt_mlt_finish */
+int fpt_mlt_get_chain_shard(fpt_context* ctx, uint32_t* rank, uint32_t* world, uint32_t* n_local, uint32_t* pending);
+int fpt_mlt_finish(fpt_context* ctx, const fpt_rendering_context_view* view);
 
 /* ---- multi-GPU: image tiles sharded over one process per GPU; replaces the single-GPU reference's cudaSetDevice(0) + whole-frame
  *      ownership (src/renderer.cu:600-603).  No data-path collective: each rank renders the pixels handed to fpt_pt_init / fpt_bpt_init

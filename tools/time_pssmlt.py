@@ -3,12 +3,16 @@
 chains.  A timing tool, not a bench line: bench.py measures the flagship workloads and knows nothing of these renderers.
 
     python tools/time_pssmlt.py [--renderer pssmlt|mmlt] [--mmlt-swaps F] [--lens] [--res 1600 900] [--path-length 9] [--chains 65536 1048576] [--spp 4] [--repeats 3]
-                                [--reseeding R [R ...] --startup-skips K]
+                                [--reseeding R [R ...] --startup-skips K] [--shard R/N]
 
 With `--reseeding` (chains that persist across render calls, fpt_mlt_set_persistence) the tool times PERIODS instead: one context per value of R, all alive, run in
 turn -- a warm-up block of max(R) calls each, then `--repeats` timed blocks of max(R) consecutive instances each, alternating between the settings -- and prints per
 setting the median time per call by position in the period (position 0 reseeds, the others continue), the mutations per second over a whole period and the frame mean
 after 16 calls.
+
+With `--shard R/N` (chain shards, fpt_mlt_set_chain_shard) every context runs rank R's share of the chains of an N-rank run, on this one GPU: a timed call is the
+render call plus fpt_mlt_finish WITHOUT a communicator -- the whole presampling pass, the shard's chain steps and the resolve of the shard's own sums, but no
+all-reduce.  The lines are labelled "emulated": they say what one rank computes, not what N GPUs achieve; the frame they leave is one rank's part of the sums.
 
 After the timed calls: one call at 2 x spp, from which the time of everything but the chain steps (rescale, presampling pass, seed CDF and seeds, coordinate
 recovery, resolve) is extrapolated as  t(spp) - chain_length(spp) x the time per step,  and one call with the traversal kernels' counters on, which gives the rays
@@ -45,7 +49,10 @@ def main():
     ap.add_argument("--lens", action="store_true", help="--renderer mmlt: the lens connections (s, 1) beside the other techniques (light tracing on)")
     ap.add_argument("--reseeding", type=int, nargs="+", default=None, help="time periods of R calls with persistent chains, one context per value, alternating")
     ap.add_argument("--startup-skips", type=int, default=0)
+    ap.add_argument("--shard", default=None, metavar="R/N", help="emulated: time rank R's share of the chains of an N-rank run on this GPU, without the all-reduce")
     args = ap.parse_args()
+    args.shard = tuple(int(x) for x in args.shard.split("/")) if args.shard else None
+    assert args.shard is None or (len(args.shard) == 2 and 0 <= args.shard[0] < args.shard[1]), "--shard R/N needs 0 <= R < N"
     mmlt = args.renderer == "mmlt"
     W, H = args.res
     L = args.path_length
@@ -58,11 +65,14 @@ def main():
 
         def renderer(spp):
             if mmlt:
-                return fa.Renderer(s, W, H, fa.default_options(L), table=table, mmlt_options=fa.default_mmlt_options(L, mmlt_frequency=args.mmlt_swaps, lens_techniques=int(args.lens), n_chains=n_chains, spp=spp))
-            return fa.Renderer(s, W, H, fa.default_options(L), table=table, pssmlt_options=fa.default_pssmlt_options(L, n_chains=n_chains, spp=spp))
+                r = fa.Renderer(s, W, H, fa.default_options(L), table=table, mmlt_options=fa.default_mmlt_options(L, mmlt_frequency=args.mmlt_swaps, lens_techniques=int(args.lens), n_chains=n_chains, spp=spp))
+            else:
+                r = fa.Renderer(s, W, H, fa.default_options(L), table=table, pssmlt_options=fa.default_pssmlt_options(L, n_chains=n_chains, spp=spp))
+            set_shard(r, args)
+            return r
 
         def timed(r, first, repeats):
-            render = r.mmlt_render if mmlt else r.pssmlt_render
+            render = render_call(r, mmlt, args)
             render(0, sync=True)                                           # warm-up: every shape the timed calls use
             out = []
             for i in range(repeats):
@@ -76,7 +86,7 @@ def main():
         st = r.mmlt_stats() if mmlt else r.pssmlt_stats()
         # the traversal's own count of the rays it fetched in one more call
         r.set_counting(True)
-        (r.mmlt_render if mmlt else r.pssmlt_render)(1 + args.repeats, sync=True)
+        render_call(r, mmlt, args)(1 + args.repeats, sync=True)
         closest, shadow = r.trace_counters()
         r.set_counting(False)
         traced = int(closest.rays) + int(shadow.rays)
@@ -97,6 +107,7 @@ def main():
             extra.update({"lens": int(args.lens), "st_norm_share_t1": round(float(norms[1].sum() / max(float(norms.sum()), 1e-30)), 4)})
             extra.update({"mmlt_swaps": args.mmlt_swaps, "queued_rays_per_mutation": round(st["rays"] / (st["chain_length"] * n_chains), 3), "swaps_proposed": st["swaps_proposed"],
                           "swaps_accepted": st["swaps_accepted"], "table_cells": n_tech * W * H, "table_MiB": round(n_tech * W * H * 16 / 2 ** 20, 1)})
+        extra.update(shard_labels(r, args))
         print(json.dumps({**extra, "tool": "time_pssmlt", "scene": "water_caustic-standin", "triangles": int(s.num_triangles), "resolution": [W, H], "max_path_length": L,
                           "n_chains": n_chains, "spp": args.spp, "chain_length": st["chain_length"], "render_s": [round(t, 4) for t in times], "median_s": round(med, 4),
                           "spread_s": round(max(times) - min(times), 4), "launches_per_call_approx": (st["chain_length"] + 1) * per_wavefront + st["chain_length"] + 6,
@@ -104,6 +115,29 @@ def main():
                           "accepted": st["accepted"], "rejected": st["rejected"], "image_brightness": float(st["image_brightness"]),
                           "frame_finite": bool(np.isfinite(fb).all()), "frame_mean": float(fb.mean())}))
         r.close()
+
+
+def set_shard(r, args):
+    if args.shard:
+        r.mlt_set_chain_shard(*args.shard)
+
+
+def render_call(r, mmlt, args):
+    """render(instance, sync): the renderer's call, followed under --shard R/N with N > 1 by mlt_finish (no communicator: the shard's own sums are resolved)"""
+    render = r.mmlt_render if mmlt else r.pssmlt_render
+    if not args.shard or args.shard[1] == 1:
+        return render
+
+    def both(instance, sync=False):
+        render(instance)
+        r.mlt_finish(sync=sync)
+    return both
+
+
+def shard_labels(r, args):
+    if not args.shard:
+        return {}
+    return {"emulated": True, "shard": "%d/%d" % args.shard, "n_local": r.mlt_chain_shard()["n_local"], "allreduce": "not run"}
 
 
 def time_periods(args, s, table, n_chains):
@@ -119,10 +153,11 @@ def time_periods(args, s, table, n_chains):
         else:
             r = fa.Renderer(s, W, H, fa.default_options(L), table=table, pssmlt_options=fa.default_pssmlt_options(L, n_chains=n_chains, spp=args.spp))
         r.mlt_set_persistence(R, args.startup_skips)
+        set_shard(r, args)
         runs.append(dict(R=R, r=r, next=0, times=[[] for _ in range(R)], reseeded=[[] for _ in range(R)], mean16=None))
     for rep in range(args.repeats + 1):          # block 0 warms up: code objects, allocations, and the first period's reseed
         for run in runs:
-            r = run["r"]; render = r.mmlt_render if mmlt else r.pssmlt_render
+            r = run["r"]; render = render_call(r, mmlt, args)
             for _ in range(block):
                 i = run["next"]; run["next"] += 1
                 r.synchronize()
@@ -139,7 +174,7 @@ def time_periods(args, s, table, n_chains):
         med = [float(np.median(t)) for t in run["times"]]
         assert all(all(f == int(k == 0) for f in flags) for k, flags in enumerate(run["reseeded"]))
         fb = r.framebuffer()[5][:, :3]
-        print(json.dumps({"tool": "time_pssmlt", "mode": "periods", "renderer": args.renderer, "scene": "water_caustic-standin", "resolution": [W, H], "max_path_length": L,
+        print(json.dumps({**shard_labels(r, args), "tool": "time_pssmlt", "mode": "periods", "renderer": args.renderer, "scene": "water_caustic-standin", "resolution": [W, H], "max_path_length": L,
                           "n_chains": n_chains, "spp": args.spp, "chain_length": st["chain_length"], "mmlt_swaps": args.mmlt_swaps if mmlt else None, "lens": int(args.lens) if mmlt else None,
                           "reseeding": R, "startup_skips": r.mlt_persistence()["startup_skips"], "timed_calls": sum(len(t) for t in run["times"]),
                           "median_ms_by_position": [round(m * 1e3, 3) for m in med], "reseeding_call_median_ms": round(med[0] * 1e3, 3),
