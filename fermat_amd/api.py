@@ -130,6 +130,11 @@ class EawParams(C.Structure):
                 ("E", C.c_float * 3), ("U", C.c_float * 3), ("V", C.c_float * 3), ("W", C.c_float * 3)]
 
 
+class XblParams(C.Structure):
+    _fields_ = [("phi_normal", C.c_float), ("phi_position", C.c_float), ("phi_color", C.c_float), ("taps", C.c_uint32),
+                ("E", C.c_float * 3), ("U", C.c_float * 3), ("V", C.c_float * 3), ("W", C.c_float * 3)]
+
+
 # ShadingMode (src/renderer_view.h:61-76) and FilterOp (src/filters.h:44-57)
 BUILD_QUALITY, BUILD_FAST, BUILD_TRBVH = 0, 1, 2          # fpt_rt_set_build_mode / Renderer.set_build_mode
 INTERSECTOR_MT, INTERSECTOR_WATERTIGHT = 0, 1             # fpt_rt_set_intersector / Renderer.set_intersector
@@ -211,7 +216,8 @@ ENTRY_POINTS = ["fpt_create", "fpt_destroy", "fpt_last_error", "fpt_stream", "fp
                 "fpt_mmlt_init", "fpt_mmlt_render", "fpt_mmlt_get_stats", "fpt_mmlt_get_st_norms", "fpt_mmlt_download", "fpt_mmlt_debug_eval",
                 "fpt_mmlt_download_pixels", "fpt_mmlt_debug_eval_pixels", "fpt_debug_bpt_splat_entries",
                 "fpt_mlt_set_persistence", "fpt_mlt_restart_chains", "fpt_mlt_get_persistence",
-                "fpt_mlt_set_chain_shard", "fpt_mlt_get_chain_shard", "fpt_mlt_finish"]
+                "fpt_mlt_set_chain_shard", "fpt_mlt_get_chain_shard", "fpt_mlt_finish",
+                "fpt_xbl", "fpt_filter_xbl"]
 
 # fpt_debug_device_build: the arrays of the last device build, by their `which` (name -> (which, dtype, columns)); rows: n triangles, n - 1 binary nodes or the wide nodes
 LBVH_CELL_DTYPE = np.dtype([("c", "<f4", 7), ("k", "u1", 7), ("k8", "u1"), ("leaf", "u1"), ("count", "u1"), ("spare", "u1", 2)])
@@ -950,6 +956,39 @@ class Renderer:
         self._check(self.L.fpt_eaw(self.ctx, C.c_uint32(w), C.c_uint32(h), C.c_void_p(d_dst.data_ptr()), C.c_int(op), C.c_void_p(d_w.data_ptr()) if d_w is not None else None,
                                    C.c_float(w_min), C.c_void_p(d_img.data_ptr()), C.c_void_p(d_geo.data_ptr()), C.c_void_p(d_v.data_ptr()) if d_v is not None else None,
                                    C.byref(p), C.c_uint32(step)))
+        self.synchronize()
+        return d_dst.cpu().numpy()
+
+    def filter_xbl(self, instance):
+        """the XBL driver of RenderingContextImpl::filter (src/renderer.cu:1161-1215) -> FILTERED_C; needs the context's shift table (any Renderer has one)"""
+        self._check(self.L.fpt_filter_xbl(self.ctx, C.byref(self.view), C.c_uint32(instance)))
+        self.synchronize()
+
+    def xbl(self, dst, op, w_img, w_min, img, gb_geo, var, params, taps, filter_radius, step, shifts=None, tile=None):
+        """one XBL step on host arrays (H, W, 4), the twin of eaw(): op = FilterOp bits, params = the 15 floats eaw() takes, taps / filter_radius / step as in
+        fpt_xbl; shifts = (2, tile, tile) or (2, tile * tile) host floats, the planes of dimensions 0 and 1 (None: the context's own table); returns the new dst"""
+        torch = self.torch
+        img = np.ascontiguousarray(img, np.float32); h, w = img.shape[:2]
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(self.dev)  # noqa: E731
+        d_dst, d_img, d_geo = up(dst), up(img), up(gb_geo)
+        d_w = up(w_img) if w_img is not None else None
+        d_v = up(var) if var is not None else None
+        p = XblParams(); flat = np.asarray(params, np.float32)
+        p.phi_normal, p.phi_position, p.phi_color, p.taps = float(flat[0]), float(flat[1]), float(flat[2]), int(taps)
+        p.E = (C.c_float * 3)(*flat[3:6]); p.U = (C.c_float * 3)(*flat[6:9]); p.V = (C.c_float * 3)(*flat[9:12]); p.W = (C.c_float * 3)(*flat[12:15])
+        if shifts is None:
+            ptr, nd, ts = C.c_void_p(), C.c_uint32(), C.c_uint32()
+            self._check(self.L.fpt_sequence_device_view(self.ctx, C.byref(ptr), C.byref(nd), C.byref(ts)))
+            d_s, s_ptr, tile = None, ptr, ts.value
+        else:
+            shifts = np.ascontiguousarray(shifts, np.float32)
+            tile = int(tile) if tile is not None else int(shifts.shape[-1])
+            assert shifts.size == 2 * tile * tile, "shifts: two planes of tile x tile floats"
+            d_s = up(shifts.reshape(-1)); s_ptr = C.c_void_p(d_s.data_ptr())
+        torch.cuda.synchronize(self.dev)
+        self._check(self.L.fpt_xbl(self.ctx, C.c_uint32(w), C.c_uint32(h), C.c_void_p(d_dst.data_ptr()), C.c_uint32(op), C.c_void_p(d_w.data_ptr()) if d_w is not None else None,
+                                   C.c_float(w_min), C.c_void_p(d_img.data_ptr()), C.c_void_p(d_geo.data_ptr()), C.c_void_p(d_v.data_ptr()) if d_v is not None else None,
+                                   C.byref(p), C.c_uint32(filter_radius), C.c_uint32(step), s_ptr, C.c_uint32(tile)))
         self.synchronize()
         return d_dst.cpu().numpy()
 

@@ -482,6 +482,64 @@ int fpt_filter(fpt_context* ctx, const fpt_rendering_context_view* view, uint32_
 	});
 }
 
+static XblParams xbl_params(const fpt_xbl_params& p)
+{
+	XblParams r; r.phi_normal = p.phi_normal; r.phi_position = p.phi_position; r.phi_color = p.phi_color; r.taps = p.taps;
+	r.E = mk3(p.E[0], p.E[1], p.E[2]); r.U = mk3(p.U[0], p.U[1], p.U[2]); r.V = mk3(p.V[0], p.V[1], p.V[2]); r.W = mk3(p.W[0], p.W[1], p.W[2]);
+	return r;
+}
+int fpt_xbl(fpt_context* ctx, uint32_t res_x, uint32_t res_y, float* d_dst, uint32_t op, const float* d_w_img, float w_min, const float* d_img,
+            const float* d_gbuffer_geo, const float* d_var, const fpt_xbl_params* params, uint32_t filter_radius, uint32_t step_size,
+            const float* d_shifts, uint32_t tile_size)
+{
+	return guarded(ctx, [&] { flush_deferred(ctx);
+		xbl_check_args(d_dst, d_img, d_gbuffer_geo, params, d_w_img, op, d_shifts, tile_size);
+		if (res_x == 0 || res_y == 0) return;
+		launch_xbl(reinterpret_cast<float4*>(d_dst), op, reinterpret_cast<const float4*>(d_w_img), w_min, reinterpret_cast<const float4*>(d_img),
+		           reinterpret_cast<const float4*>(d_gbuffer_geo), nullptr, nullptr, 0, d_var, xbl_params(*params), filter_radius, step_size, d_shifts, tile_size, res_x, res_y, ctx->stream);
+		FPT_HIP_CHECK(hipGetLastError());
+	});
+}
+int fpt_filter_xbl(fpt_context* ctx, const fpt_rendering_context_view* view, uint32_t instance)
+{
+	(void)instance;                          // the reference's XBL driver does not use it (its phi_color is 0)
+	return guarded(ctx, [&] { flush_deferred(ctx);
+		require(view->fb.gbuffer_geo != nullptr, "fpt_filter_xbl: the view has no gbuffer");
+		require(ctx->d_shifts.ptr != nullptr && ctx->seq_dims >= 2, "fpt_filter_xbl: the context holds no shift table (fpt_sequence_setup or fpt_pt_init makes one)");
+		const uint32_t W = view->res_x, H = view->res_y;
+		const size_t n = size_t(W) * H;
+		if (n == 0) return;
+		hipStream_t s = ctx->stream;
+		const int layout = xbl_layout_from(std::getenv("FPT_XBL_LAYOUT"));
+		ctx->filter_var.alloc(n);
+		if (layout == 1 || layout == 2) ctx->filter_nrm.alloc(n);
+		if (layout == 1 || layout == 3) ctx->filter_tmp[0].alloc(n);
+		if (layout == 2) ctx->filter_rec.alloc(n * 3);
+		float4* output = reinterpret_cast<float4*>(view->fb.channels[FPT_FB_FILTERED_C]);
+		FPT_HIP_CHECK(hipMemcpyAsync(output, view->fb.channels[FPT_FB_DIRECT_C], n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+		XblParams p;
+		p.phi_normal = 32.0f; p.phi_position = 1.0f; p.phi_color = 0.0f; p.taps = 32u;
+		p.E = mk3(view->camera.eye[0], view->camera.eye[1], view->camera.eye[2]);
+		camera_frame(view->camera, view->aspect, p.U, p.V, p.W);
+		const float4* geo = reinterpret_cast<const float4*>(view->fb.gbuffer_geo);
+		const float4* nrm = (layout == 1 || layout == 2) ? ctx->filter_nrm.ptr : nullptr;
+		if (nrm) launch_unpack_normals(geo, ctx->filter_nrm.ptr, uint32_t(n), s);
+		float4* col = (layout == 1 || layout == 3) ? ctx->filter_tmp[0].ptr : layout == 2 ? ctx->filter_rec.ptr : nullptr;
+		const uint32_t op = FPT_FILTER_OP_DEMODULATE_INPUT | FPT_FILTER_OP_MODULATE_OUTPUT | FPT_FILTER_OP_ADD_MODE;
+		const int pairs[2][2] = { { FPT_FB_DIFFUSE_C, FPT_FB_DIFFUSE_A }, { FPT_FB_SPECULAR_C, FPT_FB_SPECULAR_A } };
+		for (int k = 0; k < 2; ++k)
+		{
+			const float4* input = reinterpret_cast<const float4*>(view->fb.channels[pairs[k][0]]);
+			const float4* weight = reinterpret_cast<const float4*>(view->fb.channels[pairs[k][1]]);
+			launch_filter_variance(input, ctx->filter_var.ptr, 2, W, H, s);
+			if (layout != 0) launch_xbl_prepare(op, weight, 1.0e-4f, input, geo, nrm, col, layout, uint32_t(n), s);
+			// dst += w * xbl(img / w)  (src/renderer.cu:1182-1193)
+			launch_xbl(output, op, weight, 1.0e-4f, input, geo, nrm, col, layout, ctx->filter_var.ptr, p, 21u, 1u, ctx->d_shifts.ptr, ctx->seq_tile, W, H, s);
+		}
+		FPT_HIP_CHECK(hipGetLastError());
+	});
+}
+
 // what one render lane works with: its stream, counters and resolve blocks (lane 0 = the context's), and its range [first, first + n) of the rank's
 // pixel list (`pixels` = that range of the list, NULL = the identity when one lane renders everything)
 struct LaneRefs

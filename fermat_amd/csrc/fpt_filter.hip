@@ -1,7 +1,8 @@
 // fpt_filter.hip — the post-process step after the path tracer (kFiltered shading mode): variance box filter, edge-avoiding
-// à-trous wavelet (EAW) steps and the per-ShadingMode to_rgba.
+// à-trous wavelet (EAW) steps, the stochastic cross-bilateral (XBL) step and the per-ShadingMode to_rgba.
 //
 //   EAW_kernel / EAW_mad_kernel             src/eaw.cu:45-252           (one kernel here, MAD as a template flag, FilterOp bits at run time)
+//   XBL_mad_kernel                          src/xbl.cu:37-199           (xbl_kernel; the driver of src/renderer.cu:1161-1215 is fpt_filter_xbl)
 //   filter_variance_kernel                  src/renderer.cu:366-399
 //   to_rgba_kernel                          src/renderer.cu:83-282
 //   GBufferView unpack                      src/framebuffer.h:92-111 ; contrib/cugar/spherical/mappings_inline.h:162-172
@@ -14,6 +15,14 @@
 // step runs in 0.10-0.13 ms.
 // Launch: 64x4 tiles, one wavefront per 64-pixel row segment => every tap row is one coalesced 1 KB float4 load; the block
 // index is taken XCD-major (blockIdx % 8 selects the XCD) so that vertically adjacent tiles, which share taps, meet in one L2.
+//
+// XBL: one pass of `taps` disk-distributed taps per pixel, each its own scattered address (the blue-noise shift differs from pixel to pixel), so
+// a tap row is NOT a coalesced load: a wavefront's load touches up to 64 cache lines.  Per tap the plain step gathers three float4 (img, w_img, geo)
+// and unpacks a normal (sin/cos + sqrt) and divides by the weight; fpt_filter_xbl may prepare the per-pixel values once per channel instead (XBL_PLANES:
+// colour after the input op + unpacked normal as planes; XBL_RECORD: geo, normal and colour as one 48-byte record, three adjacent float4; XBL_COLOUR: the colour plane
+// alone, two gathers per tap instead of three, the normal still unpacked per tap) -- the same operations on the same operands, so the same bits.  Measured
+// (EXPERIMENTS 6m, 1600x900, ms per fpt_filter_xbl): plain 1.30, planes 1.36, record 1.37, colour 0.81 against 1.52 for the EAW chain: the step's time follows the number
+// of gather instructions per tap, not the arithmetic and not the cache lines, so XBL_COLOUR is the driver's default.  Tiles and the XCD-major tile order as for EAW.
 #include "fpt_kernels.h"
 #include "fpt_shading.h"
 
@@ -131,6 +140,130 @@ __global__ void __launch_bounds__(256) eaw_kernel(float4* __restrict__ dst, uint
 	dst[pc] = make_float4(result.x, result.y, result.z, result.w);
 }
 
+// square_to_unit_disk (contrib/cugar/spherical/mappings_inline.h:56-87) with the project's sincos.  The reference feeds it u, v that are NOT wrapped to
+// [0, 1) (a sum of two numbers of [0, 1)), so a, b reach 3 and so does the radius: DESIGN 9
+__device__ __forceinline__ void unit_disk(float u, float v, float& dx, float& dy)
+{
+	const float a = 2 * u - 1;
+	const float b = 2 * v - 1;
+	float phi, r;
+	if (a > -b)
+	{
+		if (a > b) { r = a;  phi = (kPi / 4) * (b / a); }
+		else       { r = b;  phi = (kPi / 4) * (2 - (a / b)); }
+	}
+	else
+	{
+		if (a < b) { r = -a; phi = (kPi / 4) * (4 + (b / a)); }
+		else       { r = -b; phi = b != 0 ? (kPi / 4) * (6 - (a / b)) : 0; }
+	}
+	float s, c;
+	det_sincos(phi, s, c);
+	dx = r * c; dy = r * s;
+}
+// the reference's stand-in for exp(e), e <= 0: (1 + 0.45 e)^2 inside |e| < 1 and 0 elsewhere (it jumps from 0.3025 to 0 at the cut; a NaN gives 0)
+__device__ __forceinline__ float xbl_weight(float e)
+{
+	float t = 0.0f;
+	if (fabsf(e) < 1.0f) t = 1.0f + 0.45f * e;
+	return t * t;
+}
+__device__ __forceinline__ f4 input_op(uint32_t op, f4 c, f4 w) { return (op & OP_MODULATE_IN) ? c * w : (op & OP_DEMODULATE_IN) ? div4(c, w) : c; }
+
+enum { XBL_PLAIN = 0, XBL_PLANES = 1, XBL_RECORD = 2, XBL_COLOUR = 3 };
+
+// what fpt_filter_xbl may compute once per pixel and channel instead of once per tap: the colour after the input op (`col`, XBL_PLANES) or the record
+// { geo, normal, colour } (`col` = 3 float4 per pixel, XBL_RECORD); nrm = the plane of unpack_normals_kernel
+template <int LAYOUT>
+__global__ void __launch_bounds__(256) xbl_prepare_kernel(uint32_t op, const float4* __restrict__ w_img, float w_min, const float4* __restrict__ img, const float4* __restrict__ geo,
+                                                             const float4* __restrict__ nrm, float4* __restrict__ col, uint32_t n)
+{
+	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
+	if (i >= n) return;
+	const f4 c = input_op(op, to_f4(img[i]), w_img ? clamp_below(w_img[i], w_min) : mk4(1, 1, 1, 1));
+	const float4 c4 = make_float4(c.x, c.y, c.z, c.w);
+	if (LAYOUT == XBL_RECORD) { col[size_t(i) * 3] = geo[i]; col[size_t(i) * 3 + 1] = nrm[i]; col[size_t(i) * 3 + 2] = c4; }
+	else col[i] = c4;
+}
+
+template <int LAYOUT>
+__global__ void __launch_bounds__(256) xbl_kernel(float4* __restrict__ dst, uint32_t op, const float4* __restrict__ w_img, float w_min, const float4* __restrict__ img,
+                                                     const float4* __restrict__ geo, const float4* __restrict__ nrm, const float4* __restrict__ col, const float* __restrict__ var,
+                                                     XblParams prm, uint32_t radius, uint32_t step, const float* __restrict__ shifts, uint32_t tile,
+                                                     uint32_t res_x, uint32_t res_y, uint32_t tiles_x, uint32_t tiles_y)
+{
+	uint32_t tx, ty;
+	tile_of_block(blockIdx.x, tiles_x, tiles_y, tx, ty);
+	const uint32_t x = tx * 64u + (threadIdx.x & 63u), y = ty * 4u + (threadIdx.x >> 6);
+	if (tx >= tiles_x || x >= res_x || y >= res_y) return;
+	const size_t pc = size_t(y) * res_x + x;
+
+	const f4 w_c = w_img ? clamp_below(w_img[pc], w_min) : mk4(1, 1, 1, 1);
+	constexpr bool unpack = LAYOUT == XBL_PLAIN || LAYOUT == XBL_COLOUR;          // the normal comes from the gbuffer word, per tap
+	const f4 col_c = LAYOUT == XBL_PLAIN ? input_op(op, to_f4(img[pc]), w_c) : to_f4(col[LAYOUT == XBL_RECORD ? pc * 3 + 2 : pc]);
+	const float4 geo_c = geo[pc];
+	f4 result = col_c;
+	if (!gb_miss(geo_c))
+	{
+		f3 n_c;
+		if (unpack) n_c = gb_normal(geo_c); else { const float4 t = nrm[pc]; n_c = mk3(t.x, t.y, t.z); }
+		const f3 p_c = mk3(geo_c.x, geo_c.y, geo_c.z);
+		// the eye IS subtracted here (src/xbl.cu:107-109), unlike in the EAW MAD kernel
+		const float pos_radius = 20 * sel_min(length(prm.U) / float(res_x), length(prm.V) / float(res_y)) * dot(p_c - prm.E, prm.W) / dot(prm.W, prm.W);
+		const float variance = var ? var[pc] : 1.0f;
+		const float phi_n = prm.phi_normal * float(step) * float(step);
+		const float phi_p = prm.phi_position / (pos_radius * pos_radius);
+		const float phi_c = prm.phi_color / sel_max(1.0e-3f, variance * variance);
+		const size_t plane = size_t(tile) * tile;
+		const size_t cell = size_t(x & (tile - 1u)) + size_t(y & (tile - 1u)) * tile;
+		const float shift_u = shifts[cell], shift_v = shifts[plane + cell];
+		float sum_w = 0.0f;
+		f3 sum_c = mk3(0, 0, 0);
+		for (uint32_t s = 0; s < prm.taps; ++s)
+		{
+			float xx = 0.0f, yy = 0.0f;                     // tap 0 is the centre, whatever u and v are
+			if (s != 0)
+			{
+				float dx, dy;
+				unit_disk(randfloat(s, 0u) + shift_u, randfloat(s, 1u) + shift_v, dx, dy);          // no wrap to [0, 1): as written
+				xx = dx * float(radius); yy = dy * float(radius);
+			}
+			// int2(float(x) + xx * step): the conversion truncates toward zero, so (-1, 0) is column / row 0 and inside the frame
+			const int px = to_i32_sat(float(x) + xx * float(step)), py = to_i32_sat(float(y) + yy * float(step));
+			if (px < 0 || py < 0 || px >= int(res_x) || py >= int(res_y)) continue;          // skipped, not clamped
+			const size_t pp = size_t(py) * res_x + size_t(px);
+			const float d2 = (xx * xx + yy * yy) / 100.0f;                                       // from the offsets BEFORE the step scales them
+			float4 geo_p; f4 col_p; f3 n_p;
+			if (LAYOUT == XBL_RECORD) { const float4* r = col + pp * 3; geo_p = r[0]; const float4 t = r[1]; n_p = mk3(t.x, t.y, t.z); col_p = to_f4(r[2]); }
+			else
+			{
+				geo_p = geo[pp];
+				if (LAYOUT == XBL_PLANES) { col_p = to_f4(col[pp]); const float4 t = nrm[pp]; n_p = mk3(t.x, t.y, t.z); }
+				else if (LAYOUT == XBL_COLOUR) col_p = to_f4(col[pp]);
+				else col_p = input_op(op, to_f4(img[pp]), w_img ? clamp_below(w_img[pp], w_min) : mk4(1, 1, 1, 1));
+			}
+			if (gb_miss(geo_p)) continue;
+			if (unpack) n_p = gb_normal(geo_p);
+			const float d = dot(n_p, n_c);
+			if (d < 0.9f) continue;
+			const float w_nrm = (1.0f - sel_max(1e-8f, d)) * phi_n;
+			const f3 dc = mk3(col_p.x - col_c.x, col_p.y - col_c.y, col_p.z - col_c.z);
+			const float w_col = dot(dc, dc) * phi_c;
+			const f3 dp = mk3(geo_p.x, geo_p.y, geo_p.z) - p_c;
+			const float w_pos = dot(dp, dp) * phi_p;
+			// myexp(0.0 - d2 - a - b - c): the double literal promotes the sum, myexp's float parameter narrows it
+			const double e = (((0.0 - double(d2)) - double(sel_max(w_pos, 0.0f))) - double(sel_max(w_nrm, 0.0f))) - double(sel_max(w_col, 0.0f));
+			const float w = xbl_weight(float(e));
+			sum_w += w;
+			sum_c = sum_c + w * mk3(col_p.x, col_p.y, col_p.z);
+		}
+		if (sum_w) result = mk4(sum_c.x / sum_w, sum_c.y / sum_w, sum_c.z / sum_w, col_c.w);
+	}
+	f4 r = (op & OP_ADD) ? to_f4(dst[pc]) : mk4(0, 0, 0, 0);
+	r = r + ((op & OP_MODULATE_OUT) ? result * w_c : (op & OP_DEMODULATE_OUT) ? div4(result, w_c) : result);
+	dst[pc] = make_float4(r.x, r.y, r.z, r.w);
+}
+
 __global__ void __launch_bounds__(256) filter_variance_kernel(const float4* __restrict__ img, float* __restrict__ var, uint32_t FW, uint32_t res_x, uint32_t res_y)
 {
 	const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
@@ -208,6 +341,20 @@ void launch_eaw(float4* dst, int op, const float4* w_img, float w_min, const flo
 	if (op < 0) { if (nrm) FPT_EAW_LAUNCH(false, true, 0u); else FPT_EAW_LAUNCH(false, false, 0u); }
 	else        { if (nrm) FPT_EAW_LAUNCH(true, true, uint32_t(op)); else FPT_EAW_LAUNCH(true, false, uint32_t(op)); }
 	#undef FPT_EAW_LAUNCH
+}
+void launch_xbl(float4* dst, uint32_t op, const float4* w_img, float w_min, const float4* img, const float4* geo, const float4* nrm, const float4* col, int layout, const float* var,
+                const XblParams& prm, uint32_t radius, uint32_t step, const float* shifts, uint32_t tile, uint32_t res_x, uint32_t res_y, hipStream_t s)
+{
+	const uint32_t tiles_x = (res_x + 63u) / 64u, tiles_y = (res_y + 3u) / 4u;
+	const uint32_t blocks = ((tiles_x * tiles_y + 7u) / 8u) * 8u;
+	#define FPT_XBL_LAUNCH(L) hipLaunchKernelGGL((xbl_kernel<L>), dim3(blocks), dim3(256), 0, s, dst, op, w_img, w_min, img, geo, nrm, col, var, prm, radius, step, shifts, tile, res_x, res_y, tiles_x, tiles_y)
+	if (layout == XBL_RECORD) FPT_XBL_LAUNCH(XBL_RECORD); else if (layout == XBL_PLANES) FPT_XBL_LAUNCH(XBL_PLANES); else if (layout == XBL_COLOUR) FPT_XBL_LAUNCH(XBL_COLOUR); else FPT_XBL_LAUNCH(XBL_PLAIN);
+	#undef FPT_XBL_LAUNCH
+}
+void launch_xbl_prepare(uint32_t op, const float4* w_img, float w_min, const float4* img, const float4* geo, const float4* nrm, float4* col, int layout, uint32_t n, hipStream_t s)
+{
+	if (layout == XBL_RECORD) hipLaunchKernelGGL((xbl_prepare_kernel<XBL_RECORD>), dim3((n + 255u) / 256u), dim3(256), 0, s, op, w_img, w_min, img, geo, nrm, col, n);
+	else                      hipLaunchKernelGGL((xbl_prepare_kernel<XBL_PLANES>), dim3((n + 255u) / 256u), dim3(256), 0, s, op, w_img, w_min, img, geo, nrm, col, n);
 }
 void launch_unpack_normals(const float4* geo, float4* nrm, uint32_t n, hipStream_t s)
 { hipLaunchKernelGGL(unpack_normals_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, geo, nrm, n); }

@@ -14,6 +14,23 @@
 #include <chrono>
 
 inline void require(bool cond, const char* msg) { if (!cond) throw std::runtime_error(msg); }
+// what fpt_xbl refuses before it launches (host only; tools/xbl_host_check.cpp runs it without a device).  0x0f = the modulate / demodulate bits of FilterOp
+inline void xbl_check_args(const void* dst, const void* img, const void* geo, const void* params, const void* w_img, uint32_t op, const void* shifts, uint32_t tile_size)
+{
+	require(dst && img && geo && params, "fpt_xbl: null buffer");
+	require(shifts != nullptr, "fpt_xbl: d_shifts is NULL");
+	require(tile_size && (tile_size & (tile_size - 1)) == 0, "fpt_xbl: tile_size must be a power of two");
+	require(w_img || !(op & 0x0fu), "fpt_xbl: a modulate or demodulate op needs a weight image");
+	require(dst != img, "fpt_xbl: dst must not alias img");
+}
+// FPT_XBL_LAYOUT = 0 | 1 | 2 | 3 picks what fpt_filter_xbl prepares per channel (launch_xbl, fpt_kernels.h); the frame is the same bit for bit.  Default 3, the fastest
+// measured: EXPERIMENTS 6m
+inline int xbl_layout_from(const char* env)
+{
+	if (!env || !*env) return 3;
+	require(env[0] >= '0' && env[0] <= '3' && env[1] == 0, "FPT_XBL_LAYOUT: expected 0, 1, 2 or 3");
+	return env[0] - '0';
+}
 
 namespace fpt {
 
@@ -460,6 +477,7 @@ struct fpt_context
 	fpt::DeviceArray<uint32_t> d_identity;               // 0 .. n-1: the pixel list the lanes index when the caller passed none
 	hipEvent_t lane_start = nullptr;
 	fpt::DeviceArray<float4> filter_tmp[2], filter_nrm; fpt::DeviceArray<float> filter_var;     // fpt_filter scratch (ping-pong images, variance)
+	fpt::DeviceArray<float4> filter_rec;                                                        // fpt_filter_xbl scratch: 3 float4 per pixel { geo, normal, colour } (layout 2 only)
 	// path-space filtering (PSFPT): hash table of cache cells (its reference queue is the store's)
 	struct PsfState
 	{

@@ -116,6 +116,14 @@ struct EawParams { float phi_normal, phi_position, phi_color; f3 E, U, V, W; };
 void launch_eaw(float4* dst, int op, const float4* w_img, float w_min, const float4* img, const float4* geo, const float4* nrm, const float* var, const EawParams& prm, uint32_t step,
                 uint32_t res_x, uint32_t res_y, hipStream_t s);
 void launch_unpack_normals(const float4* geo, float4* nrm, uint32_t n, hipStream_t s);
+// XBLParams (src/xbl.h): the EAW strengths and camera frame plus the number of taps
+struct XblParams { float phi_normal, phi_position, phi_color; uint32_t taps; f3 E, U, V, W; };
+// one stochastic cross-bilateral step (XBL_mad_kernel, src/xbl.cu:37-199): always the weighted form, op = FilterOp bits; shifts = the planes of dimensions 0 and 1
+// of a shift table of tile x tile cells (tile a power of two).  layout 0: everything from img / w_img / geo, per tap.  layout 1: col = the colour after the input op,
+// nrm = the unpacked normals, both prepared beforehand.  layout 2: col = 3 float4 per pixel { geo, normal, colour }.  layout 3: col as in layout 1, nrm unused (two gathers per tap: geo and col).  The same bits whichever layout
+void launch_xbl(float4* dst, uint32_t op, const float4* w_img, float w_min, const float4* img, const float4* geo, const float4* nrm, const float4* col, int layout, const float* var,
+                const XblParams& prm, uint32_t radius, uint32_t step, const float* shifts, uint32_t tile, uint32_t res_x, uint32_t res_y, hipStream_t s);
+void launch_xbl_prepare(uint32_t op, const float4* w_img, float w_min, const float4* img, const float4* geo, const float4* nrm, float4* col, int layout, uint32_t n, hipStream_t s);
 void launch_filter_variance(const float4* img, float* var, uint32_t FW, uint32_t res_x, uint32_t res_y, hipStream_t s);
 void launch_rgba_mode(const FrameBufferDev& fb, uint32_t mode, uint32_t n, float exposure, float inv_gamma, uint32_t* rgba, hipStream_t s);
 // the frame probe's targets (fpt_debug_frame): what the writers of fpt_device.h / fpt_psf.h take, plus the bounds of the arrays behind them

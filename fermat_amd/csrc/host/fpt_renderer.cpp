@@ -106,6 +106,8 @@ void RenderingContext::init(int argc, char** argv, const SceneArrays& scene)
 		else if (std::strcmp(argv[i], "-a") == 0) m_aspect = float(std::atof(argv[++i]));
 		else if (std::strcmp(argv[i], "-device") == 0) device = std::atoi(argv[++i]);
 		else if (std::strcmp(argv[i], "-filtered") == 0) m_shading_mode = FPT_SHADING_FILTERED;          // the viewer's 'f' key (src/glut_viewer.cu:298)
+		else if (std::strcmp(argv[i], "-filter") == 0)                       // which of the reference's two filters filter() runs (it picks one with an #if, src/renderer.cu:1109,1161)
+			m_filter = parse_filter_option(i + 1 < argc ? argv[++i] : nullptr);
 		else if (std::strcmp(argv[i], "-shading-mode") == 0) m_shading_mode = uint32(std::atoi(argv[++i]));
 		else if (std::strcmp(argv[i], "-bvh") == 0 && i + 1 < argc)          // no counterpart in the reference (OptiX picks its builder): fast / trbvh = built on the device
 		{
@@ -289,7 +291,11 @@ void RenderingContext::render(const uint32 instance)
 	if (m_shading_mode == FPT_SHADING_FILTERED) filter(instance);          // src/renderer.cu:1045-1047 (with -batch only the call that completes a batch sees a new frame; the filter is stateless)
 }
 
-void RenderingContext::filter(const uint32 instance) { check(m_ctx, fpt_filter(m_ctx, &m_view, instance), "filter"); }
+void RenderingContext::filter(const uint32 instance)
+{
+	if (m_filter == 1u) check(m_ctx, fpt_filter_xbl(m_ctx, &m_view, instance), "filter (xbl)");
+	else check(m_ctx, fpt_filter(m_ctx, &m_view, instance), "filter");
+}
 
 void RenderingContext::download_channel(uint32 channel, float* h_out)
 {

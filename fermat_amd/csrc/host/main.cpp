@@ -2,7 +2,8 @@
 //
 //   fermat_hip -i scene.{fa,obj} [-r W H] [-a aspect] [-c camera.txt] [-pt | -bpt | -psfpt | -pssmlt | -mmlt [-mmlt-swaps F] [-mmlt-lens 0|1] [-reseeding R] [-startup-skips K]] [-passes N] [-o output] [-ref ref.tga]
 //              [-benchmark file] [-save-intermediate] [PT flags: -pl/-bounces/-nee/-bsdf/-nee-alg mesh|vpl ...]
-//              [-data dir] [-device id] [-filtered | -shading-mode N]   (kFiltered = EAW-denoised output; the reference toggles it in the viewer)
+//              [-data dir] [-device id] [-filtered | -shading-mode N]   (kFiltered = denoised output; the reference toggles it in the viewer)
+//              [-filter eaw|xbl]           which denoiser -filtered runs: the EAW chain (default) or the cross-bilateral XBL pass (fpt_filter_xbl)
 //              [-bvh quality|fast|trbvh]   the acceleration structure's build mode (fpt_rt_set_build_mode): host SAH, device radix tree, device Trbvh
 //              [-intersector mt|watertight]  the triangle intersector the tree is built for (fpt_rt_set_intersector): fpt-MT (default) or the watertight fpt-WT
 //              [-lights host|device]       who builds the emitter tables: the host from the host mesh (default), or the device from the device mesh (the same tables)

@@ -10,10 +10,20 @@
 #include "../../../include/fermat_host.h"
 #include <cstdio>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
 namespace fermat {
+
+// `-filter eaw|xbl`: which of the reference's two filters filter() runs (0 = EAW, 1 = XBL); anything else is an error that names the option
+inline unsigned parse_filter_option(const char* v)
+{
+	const std::string s = v ? v : "";
+	if (s == "eaw") return 0u;
+	if (s == "xbl") return 1u;
+	throw std::runtime_error("-filter " + s + ": expected eaw or xbl");
+}
 
 typedef uint32_t uint32;
 
@@ -83,7 +93,7 @@ struct RenderingContext
 	struct uint2v { uint32 x, y; };
 	uint2v res() const { uint2v r; r.x = m_res_x; r.y = m_res_y; return r; }
 	fpt_rendering_context_view view(const uint32 instance);               // :1058-1084
-	void filter(const uint32 instance);                                   // EAW denoiser -> FILTERED_C, :1099-1151
+	void filter(const uint32 instance);                                   // the denoiser `-filter eaw|xbl` chose -> FILTERED_C, :1099-1217 (eaw, the default: :1109-1160; xbl: :1161-1215)
 	uint32& get_shading_mode() { return m_shading_mode; }                 // ShadingMode (src/renderer_view.h:61-76), :1373
 	void clear();                                                         // zero the frame buffer, :381-389
 	void multiply_frame(const float scale);                               // :391-401
@@ -134,6 +144,7 @@ struct RenderingContext
 	std::vector<float> m_host_vertices;          // update_model: the host mesh's vertex data once a caller has handed over new ones
 	uint32 m_res_x, m_res_y;
 	uint32 m_shading_mode;               // FPT_SHADING_*; kFiltered makes render() run filter() before to_rgba (:1045-1049)
+	uint32 m_filter = 0;                 // what filter() runs: 0 = fpt_filter (EAW), 1 = fpt_filter_xbl (`-filter xbl`)
 	float m_aspect, m_exposure, m_gamma;
 	std::vector<void*> m_device_allocs;
 	fpt_rendering_context_view m_view;

@@ -629,6 +629,24 @@ int fpt_eaw(fpt_context* ctx, uint32_t res_x, uint32_t res_y, float* d_dst, int 
 /* RenderingContextImpl::filter (src/renderer.cu:1099-1151): FILTERED_C = DIRECT_C + eaw^7(DIFFUSE_C | DIFFUSE_A) + eaw^7(SPECULAR_C | SPECULAR_A);
  * needs the gbuffer of the view; full-frame (under tile sharding gather the input channels first) */
 int fpt_filter(fpt_context* ctx, const fpt_rendering_context_view* view, uint32_t instance);
+/* the second filter of the FilteringModule: one stochastic cross-bilateral (XBL) step per channel in place of seven a-trous steps (src/xbl.{h,cu}).  Opt-in */
+typedef struct fpt_xbl_params { float phi_normal, phi_position, phi_color; uint32_t taps; float E[3], U[3], V[3], W[3]; } fpt_xbl_params;   /* XBLParams, src/xbl.h */
+/* XBL(dst, op, w_img, w_min, img, gb, var, params, filter_radius, step_size, sequence) (src/xbl.cu:57-223): one step on the context's stream, op = FilterOp bits.
+ * Tap s of pixel (x, y) lies at (int)(x + disk(randfloat(s, 0) + shift(x, y, 0), randfloat(s, 1) + shift(x, y, 1)) * filter_radius * step_size), tap 0 at the
+ * centre; shift(x, y, d) = d_shifts[d * tile_size^2 + (x & (tile_size - 1)) + (y & (tile_size - 1)) * tile_size], so d_shifts points at the planes of dimensions
+ * 0 and 1 (tile_size^2 floats each; the head of what fpt_sequence_device_view returns will do).  d_var may be NULL (variance 1); d_w_img may be NULL only when op has
+ * no modulate or demodulate bit.  Refused: d_shifts == NULL, a tile_size that is 0 or not a power of two, dst aliasing img.  taps = 0 (every pixel passes through
+ * the two ops), filter_radius = 0 and step_size = 0 (every tap is the centre) are legal */
+int fpt_xbl(fpt_context* ctx, uint32_t res_x, uint32_t res_y, float* d_dst, uint32_t op, const float* d_w_img, float w_min, const float* d_img,
+            const float* d_gbuffer_geo, const float* d_var, const fpt_xbl_params* params, uint32_t filter_radius, uint32_t step_size,
+            const float* d_shifts, uint32_t tile_size);
+/* the XBL driver the reference keeps behind an #elif in RenderingContextImpl::filter (src/renderer.cu:1161-1215): FILTERED_C = DIRECT_C + xbl(DIFFUSE_C | DIFFUSE_A) +
+ * xbl(SPECULAR_C | SPECULAR_A), each = filter_variance(input, var, 2) + one fpt_xbl(op = DEMODULATE_INPUT | MODULATE_OUTPUT | ADD_MODE, w_min 1e-4, taps 32,
+ * phi_normal 32, phi_position 1, phi_color 0, filter_radius 21, step_size 1) on the context's own shift table; `instance` is unused, as there.  Refused when the context
+ * holds no shift table (fpt_sequence_setup / fpt_pt_init).  Dimensions 0 and 1 of that table are the first two components of samples-0.dat whichever of the two
+ * set-ups made it, provided it was given a samples directory that holds the file (without one they are the set-up's own multi-jittered layer 0).  Needs the gbuffer of
+ * the view; full-frame, like fpt_filter; bit-identical to the two calls it stands for */
+int fpt_filter_xbl(fpt_context* ctx, const fpt_rendering_context_view* view, uint32_t instance);
 
 /* ---- the rest of RenderingContext's frame / table accessors a third-party RendererInterface plugin may call (src/renderer.h:52-228) ---- */
 /* multiply_frame (src/renderer.cu:292-312, :391-401): saves the luminances, scales the six accumulation channels; rescale_frame(i) = multiply_frame(i / (i + 1)) */
