@@ -217,7 +217,8 @@ ENTRY_POINTS = ["fpt_create", "fpt_destroy", "fpt_last_error", "fpt_stream", "fp
                 "fpt_mmlt_download_pixels", "fpt_mmlt_debug_eval_pixels", "fpt_debug_bpt_splat_entries",
                 "fpt_mlt_set_persistence", "fpt_mlt_restart_chains", "fpt_mlt_get_persistence",
                 "fpt_mlt_set_chain_shard", "fpt_mlt_get_chain_shard", "fpt_mlt_finish",
-                "fpt_xbl", "fpt_filter_xbl"]
+                "fpt_xbl", "fpt_filter_xbl",
+                "fpt_debug_set_trace_blocks", "fpt_debug_trace_tickets"]
 
 # fpt_debug_device_build: the arrays of the last device build, by their `which` (name -> (which, dtype, columns)); rows: n triangles, n - 1 binary nodes or the wide nodes
 LBVH_CELL_DTYPE = np.dtype([("c", "<f4", 7), ("k", "u1", 7), ("k8", "u1"), ("leaf", "u1"), ("count", "u1"), ("spare", "u1", 2)])
@@ -1018,6 +1019,17 @@ class Renderer:
         self._check(self.L.fpt_rt_trace_shadow_bits(self.ctx, C.c_uint32(len(rays)), C.c_void_p(d_r.data_ptr()), C.c_void_p(d_b.data_ptr())))
         self.synchronize()
         return d_b.cpu().numpy().view(np.uint32)
+
+    def debug_set_trace_blocks(self, n_blocks):
+        """fpt_debug_set_trace_blocks: every traversal launch of this context runs at most n_blocks 256-thread blocks from now on (0 = the default grid again; a value
+        above the default is refused).  Results do not depend on the grid; a launch of more than 256 * n_blocks rays then draws tickets, steals and refills."""
+        self._check(self.L.fpt_debug_set_trace_blocks(self.ctx, C.c_uint32(n_blocks)))
+
+    def debug_trace_tickets(self):
+        """fpt_debug_trace_tickets: the eight shard counters of the hand-out as the last trace / trace_shadow_bits call left them (uint32[8])"""
+        out = (C.c_uint32 * 8)()
+        self._check(self.L.fpt_debug_trace_tickets(self.ctx, out))
+        return np.array(list(out), np.uint32)
 
     def sequence(self, instance=None):
         if instance is not None:

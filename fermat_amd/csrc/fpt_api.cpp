@@ -195,7 +195,27 @@ int fpt_rt_trace_counted(fpt_context* ctx, uint32_t count, const fpt_ray* d_rays
 		rt_launch(ctx, count, d_rays, d_hits, nullptr, shadow != 0, true);
 		unsigned long long s[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
 		if (count) ctx->d_trace_stats.download(s, 8, ctx->stream);
-		if (h_out) { h_out->rays = count; h_out->nodes_visited = shadow ? s[4] : s[0]; h_out->tris_tested = shadow ? s[5] : s[1]; }
+		// rays: the kernel's own count of the rays its lanes took (one per refill of a lane), not `count`: a ray handed out twice or never shows here
+		if (h_out) { h_out->rays = shadow ? s[6] : s[2]; h_out->nodes_visited = shadow ? s[4] : s[0]; h_out->tris_tested = shadow ? s[5] : s[1]; }
+	});
+}
+// test probes of the hand-out (tests/test_trace_schedule.py).  The cap is read by trace_blocks(), from which every traversal launch sizes its grid; pending passes
+// were deferred under the old cap and are rendered under it
+int fpt_debug_set_trace_blocks(fpt_context* ctx, uint32_t n_blocks)
+{
+	return guarded(ctx, [&] { flush_deferred(ctx);
+		require(n_blocks <= ctx->trace_blocks_default(), "fpt_debug_set_trace_blocks: n_blocks is above the default grid (blocks per CU x CUs); the cap only shrinks the grid");
+		ctx->trace_blocks_cap = n_blocks;
+	});
+}
+// rt_launch's ticket area is the first of the context's counter block: shard k's dispenser at word k * 32 (TICKET_STRIDE / 8, the kernel's TICKET_PAD)
+int fpt_debug_trace_tickets(fpt_context* ctx, uint32_t h_out[8])
+{
+	return guarded(ctx, [&] {
+		require(h_out != nullptr, "fpt_debug_trace_tickets: null output");
+		uint32_t area[TICKET_STRIDE];
+		ctx->d_counters.download(area, TICKET_STRIDE, ctx->stream);
+		for (uint32_t k = 0; k < 8; ++k) h_out[k] = area[CNT_TICKETS + k * (TICKET_STRIDE / 8)];
 	});
 }
 int fpt_rt_bvh_info(fpt_context* ctx, uint32_t* n_nodes, uint32_t* n_leaf_tris, uint32_t* max_depth)

@@ -600,7 +600,10 @@ struct fpt_context
 	fpt::DeviceArray<float4> comm_staging, comm_recv;        // the packed message of this rank / the root's receive buffer
 
 	uint32_t blocks_per_cu = 8;
-	uint32_t trace_blocks() const { return n_cus * blocks_per_cu; }   // persistent grid: blocks_per_cu x 256-thread blocks per CU
+	uint32_t trace_blocks_cap = 0;                                     // fpt_debug_set_trace_blocks: 0 = none, else never above the default
+	uint32_t trace_blocks_default() const { return n_cus * blocks_per_cu; }
+	// persistent grid: blocks_per_cu x 256-thread blocks per CU, unless a test caps it.  Every traversal launch sizes its grid from here
+	uint32_t trace_blocks() const { const uint32_t d = trace_blocks_default(); return (trace_blocks_cap && trace_blocks_cap < d) ? trace_blocks_cap : d; }
 };
 
 // renders the passes fpt_pt_render has deferred (no-op when none are pending); throws on error.  Called by every entry point that reads or writes the

@@ -152,8 +152,17 @@ int fpt_rt_trace(fpt_context* ctx, uint32_t count, const fpt_ray* d_rays, fpt_hi
 int fpt_rt_trace_shadow(fpt_context* ctx, uint32_t count, const fpt_ray* d_rays, fpt_hit* d_hits);
 /* RTContext::trace_shadow(count, MaskedRay*, uint32* binary_hits) (src/rt.h:102, src/rt.cpp:636-659): 1 bit per ray */
 int fpt_rt_trace_shadow_bits(fpt_context* ctx, uint32_t count, const fpt_ray* d_rays, uint32_t* d_bits);
-/* instrumented closest-hit / any-hit launch: same results, also counts nodes popped and triangles tested */
+/* instrumented closest-hit / any-hit launch: same results, also counts nodes popped and triangles tested; `rays` is the kernel's own count of the rays its
+ * lanes took, which equals `count` */
 int fpt_rt_trace_counted(fpt_context* ctx, uint32_t count, const fpt_ray* d_rays, fpt_hit* d_hits, int shadow, fpt_trace_counters* h_out);
+/* probe (tests): a cap on the persistent traversal grid.  Every traversal launch of the context -- the four calls above and the renderers' -- runs at most n_blocks
+ * 256-thread blocks from then on; 0 restores the default (blocks per CU x CUs).  Results never depend on the grid; what changes is the hand-out: a launch of
+ * n rays leaves the path without atomics (one fixed 64-ray batch per wave) once n > 256 n_blocks, so a capped context draws tickets, steals and refills at a
+ * few hundred rays.  Flushes deferred passes first.  A value above the default is refused and leaves the cap as it was: the cap only shrinks the grid. */
+int fpt_debug_set_trace_blocks(fpt_context* ctx, uint32_t n_blocks);
+/* probe (tests): the eight ticket counters of the hand-out as the last fpt_rt_trace* launch of this context left them (all zero after a launch that ran
+ * without atomics).  Valid until the context's next render call, which reuses their words; synchronises the context's stream. */
+int fpt_debug_trace_tickets(fpt_context* ctx, uint32_t h_out[8]);
 int fpt_rt_bvh_info(fpt_context* ctx, uint32_t* n_nodes, uint32_t* n_leaf_tris, uint32_t* max_depth);
 /* what the builder behind create_geometry produced: node occupancy (wide nodes by number of used child slots), depth, the traversal-stack bound
  * of the tree, SAH costs and build times (host threads used) */
