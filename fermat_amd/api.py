@@ -211,7 +211,7 @@ ENTRY_POINTS = ["fpt_create", "fpt_destroy", "fpt_last_error", "fpt_stream", "fp
                 "fpt_multiply_frame", "fpt_clamp_frame", "fpt_sequence_device_view", "fpt_mesh_lights_device_view", "fpt_mesh_invalidate", "fpt_rt_refit_geometry", "fpt_debug_refit_bvh",
                 "fpt_debug_build_emitter_tables", "fpt_clear_gbuffer", "fpt_rt_download_bvh", "fpt_mesh_lights_update", "fpt_rt_set_build_mode",
                 "fpt_mesh_lights_init_device", "fpt_mesh_lights_update_device", "fpt_rt_set_intersector", "fpt_rt_intersector",
-                "fpt_debug_psf", "fpt_psfpt_debug_set_table_log2", "fpt_debug_bpt", "fpt_debug_frame",
+                "fpt_debug_psf", "fpt_psfpt_debug_set_table_log2", "fpt_psfpt_debug_download_refs", "fpt_debug_bpt", "fpt_debug_frame",
                 "fpt_pssmlt_init", "fpt_pssmlt_render", "fpt_pssmlt_get_stats", "fpt_pssmlt_download", "fpt_pssmlt_debug_eval", "fpt_debug_mlt", "fpt_debug_device_build",
                 "fpt_mmlt_init", "fpt_mmlt_render", "fpt_mmlt_get_stats", "fpt_mmlt_get_st_norms", "fpt_mmlt_download", "fpt_mmlt_debug_eval",
                 "fpt_mmlt_download_pixels", "fpt_mmlt_debug_eval_pixels", "fpt_debug_bpt_splat_entries",
@@ -500,6 +500,22 @@ class Renderer:
     def psf_debug_set_table_log2(self, log2_size):
         """tests of the cache under load: 2^log2_size slots (8..24) instead of 2^24; before the first render, psf_set_batch and psf_set_sharded"""
         self._check(self.L.fpt_psfpt_debug_set_table_log2(self.ctx, C.c_uint32(log2_size)))
+
+    def psf_refs(self):
+        """the reference queue of the last rendered pass, read only: per bounce 0..L-1 a dict of n, ref_pixels, ref_cache, ref_wd, ref_wg (in append order, which is
+        not defined) and keys: the key of the slot each cache word names (~0 after a batch or a finished sharded pass, whose pass tables are gone)"""
+        out = []
+        for b in range(int(self.options.max_path_length)):
+            n = C.c_uint32(0)
+            self._check(self.L.fpt_psfpt_debug_download_refs(self.ctx, C.c_uint32(b), None, None, None, None, None, C.c_uint32(0), C.byref(n)))
+            m = n.value
+            d = dict(n=m, ref_pixels=np.zeros(m, np.uint32), ref_cache=np.zeros(m, np.uint32), ref_wd=np.zeros((m, 4), np.float32), ref_wg=np.zeros((m, 4), np.float32),
+                     keys=np.zeros(m, np.uint64))
+            if m:
+                self._check(self.L.fpt_psfpt_debug_download_refs(self.ctx, C.c_uint32(b), *[C.c_void_p(d[k].ctypes.data) for k in ("ref_pixels", "ref_cache", "ref_wd", "ref_wg", "keys")],
+                                                                 C.c_uint32(m), C.byref(n)))
+            out.append(d)
+        return out
 
     def psf_cells(self):
         """occupied cache cells sorted by key: keys, sample counts, 2^-32 fixed-point sums"""

@@ -485,6 +485,7 @@ struct fpt_context
 		fpt_psf_options opt{};
 		fpt::PsfTable table;                        // the global table
 		fpt::DeviceArray<uint32_t> ref_size;        // the reference queue's fill, one word per bounce
+		uint32_t ref_stride = 0, ref_mode = 0;      // the last render's: entries per bounce of the queue, and the table its cache words name (0 global, 1 the shard's pass table, 2 a batch's)
 		float bbox[6] = { 0, 0, 0, 0, 0, 0 };
 		fpt::DeviceArray<fpt::ResolveParams> d_resolve;     // per-bounce blocks read by the MIXED launches with the fused cache-aware resolve
 		std::vector<fpt::ResolveParams> h_resolve;

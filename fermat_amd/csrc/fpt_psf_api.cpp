@@ -116,6 +116,42 @@ int fpt_psfpt_download_cells(fpt_context* ctx, uint64_t* h_keys, uint64_t* h_cou
 	});
 }
 
+int fpt_psfpt_debug_download_refs(fpt_context* ctx, uint32_t bounce, uint32_t* h_pixels, uint32_t* h_cache, float* h_wd, float* h_wg, uint64_t* h_keys,
+                                  uint32_t max_refs, uint32_t* n_refs)
+{
+	return guarded(ctx, [&] {
+		flush_deferred(ctx);
+		fpt_context::PsfState& s = ctx->psf; WavefrontStore& w = ctx->store;
+		require(s.ready, "fpt_psfpt_debug_download_refs: fpt_psfpt_init has not been called");
+		require(bounce < 32, "fpt_psfpt_debug_download_refs: bounce must be below 32");
+		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+		uint32_t n = 0;
+		if (s.rendered) FPT_HIP_CHECK(hipMemcpy(&n, s.ref_size.ptr + bounce, sizeof(uint32_t), hipMemcpyDeviceToHost));
+		const size_t at = size_t(bounce) * s.ref_stride;
+		require(n <= s.ref_stride && at + n <= w.ref_pixels.count, "fpt_psfpt_debug_download_refs: the queue was re-shaped since the last render");
+		if (n_refs) *n_refs = n;
+		const uint32_t m = n < max_refs ? n : max_refs;
+		if (!m) return;
+		if (h_pixels) FPT_HIP_CHECK(hipMemcpy(h_pixels, w.ref_pixels.ptr + at, size_t(m) * 4, hipMemcpyDeviceToHost));
+		if (h_wd) FPT_HIP_CHECK(hipMemcpy(h_wd, w.ref_wd.ptr + at, size_t(m) * 16, hipMemcpyDeviceToHost));
+		if (h_wg) FPT_HIP_CHECK(hipMemcpy(h_wg, w.ref_wg.ptr + at, size_t(m) * 16, hipMemcpyDeviceToHost));
+		if (!h_cache && !h_keys) return;
+		std::vector<uint32_t> cache(m);
+		FPT_HIP_CHECK(hipMemcpy(cache.data(), w.ref_cache.ptr + at, size_t(m) * 4, hipMemcpyDeviceToHost));
+		if (h_cache) std::memcpy(h_cache, cache.data(), size_t(m) * 4);
+		if (!h_keys) return;
+		// the key of the slot a cache word names: read from the global table, or from the shard's pass table while its pass is pending; the pass tables of a
+		// batch and of a finished sharded pass are cleared by then, and their words resolve to the empty mark
+		const PsfTable* t = s.ref_mode == 0 ? &s.table : (s.ref_mode == 1 && s.pending) ? &s.shard : nullptr;
+		for (uint32_t i = 0; i < m; ++i)
+		{
+			const uint32_t slot = cache[i] & 0x1FFFFFFFu;
+			h_keys[i] = ~0ull;
+			if (t && slot < (size_t(1) << t->log2)) FPT_HIP_CHECK(hipMemcpy(h_keys + i, t->keys.ptr + slot, 8, hipMemcpyDeviceToHost));
+		}
+	});
+}
+
 // PSFPT::render for n_passes >= 1 passes in flight (instances instance .. instance + n_passes - 1).  One pass: the reference's sequence.  A batch:
 // the passes of a batch are independent until the blend (nothing on a path reads the cache), so they run as one wavefront like the path tracer's
 // batches, each pass accumulating into its own pass table and its own frame planes; the tables are then folded into the global table IN PASS ORDER,
@@ -156,6 +192,7 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 		require(!ps.sharded || !ps.pending, "fpt_psfpt_render: the previous pass has not been finished (fpt_psfpt_exchange_cells / fpt_psfpt_import_cells, then fpt_psfpt_finish)");
 		// batched: one pass table per pass of the batch (2^log2 slots each, enough for every cell a pass can create), their slot lists, the global table
 		PsfDev psf = psf_dev(ctx, batched ? PSF_BATCHED : ps.sharded ? PSF_SHARDED : PSF_PLAIN);
+		ps.ref_stride = n; ps.ref_mode = batched ? 2u : ps.sharded ? 1u : 0u;
 		psf.bbox_lo = mk3(ps.bbox[0], ps.bbox[1], ps.bbox[2]); psf.bbox_hi = mk3(ps.bbox[3], ps.bbox[4], ps.bbox[5]); psf.instance = instance;
 
 		// the rays are those of the renderer's own queues (fpt_device.h PathQueue / ShadowQueue): the .w words carry PixelInfo / pass offset, the intervals are the queues'

@@ -780,6 +780,12 @@ int fpt_debug_frame(fpt_context* ctx, int op, uint32_t n, const uint32_t* h_para
 /* debug entry (tests of the cache under load): the cache of a context after fpt_psfpt_init and before its first render, fpt_psfpt_set_batch or
  * fpt_psfpt_set_sharded, re-allocated with 2^log2_size slots (8..24) and cleared.  A table that fills up refuses further keys: their vertices stay uncached. */
 int fpt_psfpt_debug_set_table_log2(fpt_context* ctx, uint32_t log2_size);
+/* debug entry, read-only (tests/test_psfpt_truth.py): the reference queue of bounce `bounce` (0..31) as the last rendered pass left it -- *n_refs entries, of which
+ * the first max_refs are copied to the HOST arrays that are not NULL: PixelInfo, the cache word (slot : 29 | comp : 2 | new : 1), the diffuse and the glossy
+ * weight (4 floats each), and the KEY of the slot the cache word names (~0 where that table is gone: after a batch, after fpt_psfpt_finish).  The order of
+ * a bounce's entries is the order of the appends, which is not defined.  Pending deferred passes are rendered first. */
+int fpt_psfpt_debug_download_refs(fpt_context* ctx, uint32_t bounce, uint32_t* h_pixels, uint32_t* h_cache, float* h_wd, float* h_wg, uint64_t* h_keys,
+                                  uint32_t max_refs, uint32_t* n_refs);
 
 /* host-side probe of the acceleration-structure builder behind fpt_rt_create_geometry (no GPU, no context; HOST arrays in, HOST arrays out):
  * *node_words = 32-bit words per node (20: the 80-byte 8-wide compressed node, see fermat_amd/csrc/fpt_bvh.h), records = 48-byte triangle

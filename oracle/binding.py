@@ -228,6 +228,19 @@ class OraclePT:
     def psf_ref_count(self):
         return int(lib().orc_psf_ref_count(self.h))
 
+    def psf_refs(self):
+        """the twin of fermat_amd's Renderer.psf_refs: per bounce n, ref_pixels, ref_cache, ref_wd, ref_wg and the keys of the slots the cache words name"""
+        n = int(lib().orc_psf_get_refs(self.h, None, None, None, None, None, None, C.c_uint32(0)))
+        b = np.zeros(n, np.uint32); a = dict(ref_pixels=np.zeros(n, np.uint32), ref_cache=np.zeros(n, np.uint32), keys=np.zeros(n, np.uint64),
+                                             ref_wd=np.zeros((n, 4), np.float32), ref_wg=np.zeros((n, 4), np.float32))
+        if n:
+            lib().orc_psf_get_refs(self.h, *[C.c_void_p(x.ctypes.data) for x in (b, a["ref_pixels"], a["ref_cache"], a["keys"], a["ref_wd"], a["ref_wg"])], C.c_uint32(n))
+        out = []
+        for k in range(int(self.options.max_path_length)):
+            sel = b == k
+            out.append(dict({key: v[sel] for key, v in a.items()}, n=int(sel.sum())))
+        return out
+
     # -- bidirectional path tracer (oracle/o_bpt.h), sharing this context's scene / BVH / lights / frame buffer
     def bpt_init(self, options, samples_dir):
         self.bpt_options = options

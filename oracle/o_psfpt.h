@@ -72,7 +72,7 @@ struct PsfState
 	std::unordered_map<u64, u32> index;      // key -> slot
 	std::vector<u64> keys;
 	std::vector<Cell> cells;
-	struct Ref { u32 pixel_info, cache; V4 w_d, w_g; };
+	struct Ref { u32 pixel_info, cache; V4 w_d, w_g; u32 bounce; };      // bounce: of the vertex that appended it (orc_psf_get_refs; the blend does not read it)
 	std::vector<Ref> refs;
 
 	// 2^-32 fixed point, round half to even.  DEFINED HERE beyond the range of a 64-bit integer (|v| >= 2^31, which only a firefly_filter above that lets through):

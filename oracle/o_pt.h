@@ -439,7 +439,7 @@ struct PathTracer
 			const V4 w_mod(w.x * maxf(md.x, 1.0e-4f), w.y * maxf(md.y, 1.0e-4f), w.z * maxf(md.z, 1.0e-4f), 0.0f * maxf(md.w, 1.0e-4f));     // modulate(Vector4f(w,0), diffuse)
 			const u32 comp = pi_comp(pixel_info);
 			PsfState::Ref r;
-			r.pixel_info = pixel_info; r.cache = cache_info(new_cache_slot, 3u, 0);
+			r.pixel_info = pixel_info; r.cache = cache_info(new_cache_slot, 3u, 0); r.bounce = in_bounce;
 			r.w_d = (comp & kDiffuseMask) ? w_mod : V4(0, 0, 0, 0);
 			r.w_g = ((comp & kGlossyMask) && in_bounce) ? w_mod : V4(0, 0, 0, 0);
 			psf->refs.push_back(r);

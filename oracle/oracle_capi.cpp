@@ -471,6 +471,21 @@ u32 orc_psf_get_cells(orc_pt* h, u64* keys, u64* counts, long long* sums, u32 ma
 	return n;
 }
 u32 orc_psf_ref_count(orc_pt* h) { return u32(h->psf.refs.size()); }
+// the reference queue of the last pass, in append order: the bounce of the vertex, PixelInfo, the cache word, the key of the slot it names, the two weights
+u32 orc_psf_get_refs(orc_pt* h, u32* bounce, u32* pixels, u32* cache, u64* keys, float* wd, float* wg, u32 max_n)
+{
+	const PsfState& s = h->psf;
+	const u32 n = u32(s.refs.size());
+	if (!bounce) return n;
+	for (u32 i = 0; i < n && i < max_n; ++i)
+	{
+		const PsfState::Ref& r = s.refs[i];
+		bounce[i] = r.bounce; pixels[i] = r.pixel_info; cache[i] = r.cache; keys[i] = ci_valid(r.cache) ? s.keys[ci_slot(r.cache)] : ~0ull;
+		const float d[4] = { r.w_d.x, r.w_d.y, r.w_d.z, r.w_d.w }, g[4] = { r.w_g.x, r.w_g.y, r.w_g.z, r.w_g.w };
+		for (int k = 0; k < 4; ++k) { wd[4 * size_t(i) + k] = d[k]; wg[4 * size_t(i) + k] = g[k]; }
+	}
+	return n;
+}
 // twin of the device probe fpt_debug_psf (include/fermat_pt_hip.h has the layouts): spatial_hash, the cell sums and the cell mean are the oracle's own.  The
 // oracle keeps its cells in a map and has no table; op 1 restates the device's scheme -- multiplicative hash, linear probing with wrap, refusal when full -- one
 // key after the other, so that the table invariants of tests/psf_truth.py are run on the CPU leg too.

@@ -17,10 +17,11 @@ Spelled out, because each is a place to go wrong:
   * LUMINANCE is written by multiply_frame, before the scaling, and only there
   * a merge leaves the albedo planes and the mask words it visited zero, and never reads a cell whose bit is clear
 
-NOT covered: the PSFPT's clamp of an EMISSION.  PSFPTVertexProcessor::accumulate_emissive clamps its sample itself (src/psfpt_vertex_processor.h:351) and then adds it
-as the path tracer's does; on the device that clamp (and the choice between the image and the cache cell) sits in shade_kernel, at the call of accumulate_emissive,
-which the probe does not run.  So `accumulate_emissive` below takes the value as it arrives, for both renderers, and an emission here is what is left after the
-clamp; the clamp itself is seen only by the whole renders of tests/test_psfpt.py, not here.
+The PSFPT's clamp of an EMISSION is not this judge's rule: PSFPTVertexProcessor::accumulate_emissive clamps its sample itself (src/psfpt_vertex_processor.h:351) and
+then adds it as the path tracer's does; on the device that clamp (and the choice between the image and the cache cell) sits in shade_kernel, at the call of
+accumulate_emissive, which the frame probe does not run.  So `accumulate_emissive` below takes the value as it arrives, for both renderers, and an emission here is
+what is left after the clamp.  The clamp and the choice are judged by the replay of a whole pass, tests/psfpt_truth.py (Processor.emissive; its mistakes
+"emission_unclamped" and "emission_to_frame"), which hands this module emissions that are already clamped.
 
 `wrong` names ONE deliberate mistake (WRONG below): the same replay with that mistake built in.  tests/test_frame_truth.py uses them to show that its inputs are
 sharp enough to tell each mistake from the truth."""

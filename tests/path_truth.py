@@ -31,6 +31,9 @@ Reference quirks reproduced on purpose:
   * the shadow origin is shifted back along the UNNORMALISED ray direction (src/pathtracer_core.h:979, 1097)
   * the emissive hit at bounce 0 reads p_prev = 1 from the camera weight's .w and is not MIS-weighted (src/pathtracer_core.h:1133-1135)
 
+The vertex processor is the path tracer's, stated inline; replay_pass(psf=...) swaps in another at the reference's five call sites (tests/psfpt_truth.py: the
+path-space-filtering one), everything else of the pass staying as stated here.
+
 `wrong` names ONE deliberate mistake (WRONG below): the same replay with that mistake built in; tests/test_path_truth.py records which case refuses which."""
 import ctypes
 import ctypes.util
@@ -229,22 +232,27 @@ def as_rays(origin, mask, d, tmax):
     return r
 
 
-def light_record(n, slot, sp, pos, inn, ray_dir, w, l_pos, l_n, l_rad, l_pdf, use_mis, eps, bounce, opts):
-    """the record of vertex ops 7 (include/fermat_pt_hip.h): frame n, ng, t, b; position, in, ray_dir, w; the light point; use_mis, origin_eps, bounce, options"""
+def light_record(n, slot, sp, pos, inn, ray_dir, w, l_pos, l_n, l_rad, l_pdf, use_mis, eps, bounce, opts, psf_mode=None, demod=None):
+    """the record of vertex ops 7 (include/fermat_pt_hip.h): frame n, ng, t, b; position, in, ray_dir, w; the light point; use_mis, origin_eps, bounce, options;
+    psf_mode per element and the demodulating albedo (the PSFPT's weights: tests/psfpt_truth.py decides them)"""
     r = np.zeros((n, 48), F32)
     r[:, 0] = bits_f32(slot)
     r[:, 1:4] = sp[:, 6:9]; r[:, 4:7] = sp[:, 3:6]; r[:, 7:10] = sp[:, 9:12]; r[:, 10:13] = sp[:, 12:15]
     r[:, 13:16] = pos; r[:, 16:19] = inn; r[:, 19:22] = ray_dir; r[:, 22:25] = w
     r[:, 25:28] = l_pos; r[:, 28:31] = l_n; r[:, 31:34] = l_rad; r[:, 34] = l_pdf
     r[:, 35] = bits_f32(1 if use_mis else 0); r[:, 36] = F32(eps); r[:, 37] = bits_f32(bounce); r[:, 38] = bits_f32(opts)
+    if psf_mode is not None:
+        r[:, 39] = bits_f32(psf_mode); r[:, 40:43] = demod
     return r
 
 
-def replay_pass(prov, scn, res_x, res_y, options, instance, shifts, pixels=None, wrong=None):
+def replay_pass(prov, scn, res_x, res_y, options, instance, shifts, pixels=None, wrong=None, psf=None):
     """ONE pass.  scn: anything with camera, materials, material_indices, dir_lights (a fermat_amd.scene.Scene).  options: a mapping of OPTION_NAMES.
     Returns dict(queues: per bounce the expected INPUT queue with its hits, in the order of the pixel list -- origin, mask, dir, tmax, weight (.w = p_prev), pixel_info,
     cone, hits; samples / albedo: per pixel, as frame_truth.render_pass takes them; stats: per bounce (in, directional, mesh, scatter) sizes; counts: the
-    non-vacuity counters; folded: the folded sample table; camera: U, V, W and the primary ray's two samples)"""
+    non-vacuity counters; folded: the folded sample table; camera: U, V, W and the primary ray's two samples)
+    psf: the PSFPT's vertex processor (tests/psfpt_truth.py Processor), called at the reference's five call sites (src/pathtracer_core.h:851-858, 943-984, 1064-1102,
+    1147, 1196-1241); None = the path tracer's own, stated inline.  Its state travels in the queue's "vinfo" entry, which only it reads."""
     assert wrong is None or wrong in WRONG
     o = {k: int(options[k]) for k in OPTION_NAMES}
     assert o["diffuse_scattering"] and o["glossy_scattering"], "the probes sample every component"
@@ -261,6 +269,8 @@ def replay_pass(prov, scn, res_x, res_y, options, instance, shifts, pixels=None,
     mask_dir, mask_mesh = (0x2, 0x1) if wrong == "masks_swapped" else (0x1, 0x2)
 
     q, cam = primary_rays(scn.camera, res_x, res_y, pixels, sampler)
+    if psf is not None:
+        q["vinfo"] = psf.primary(len(pixels))
     samples = {int(p): [] for p in pixels}
     albedo = {}
     queues, stats = [], []
@@ -282,6 +292,8 @@ def replay_pass(prov, scn, res_x, res_y, options, instance, shifts, pixels=None,
             st = [n, 0, 0, 0]
             nq = dict(origin=np.zeros((0, 3), F32), mask=np.zeros(0, U32), dir=np.zeros((0, 3), F32), tmax=np.zeros(0, F32), weight=np.zeros((0, 4), F32),
                       pixel_info=np.zeros(0, U32), cone=np.zeros((0, 2), F32))
+            if psf is not None:
+                nq["vinfo"] = psf.primary(0)
             if m:
                 org, d, t = q["origin"][act], q["dir"][act], hits["t"][act]
                 tri = hits["triId"][act].astype(np.int64)
@@ -319,6 +331,10 @@ def replay_pass(prov, scn, res_x, res_y, options, instance, shifts, pixels=None,
                 cone_radius = q["cone"][act, 0] + F32(1.0) / np.sqrt(q["cone"][act, 1] * prev_G)
                 z = sampler.vertex_samples(pix % res_x, pix // res_x, b)
                 slot = np.arange(m)
+                vx = None
+                if psf is not None:
+                    # preprocess_vertex (:851-858), handed the PREVIOUS vertex's info word from the queue
+                    vx = psf.preprocess(b, pinfo, q["vinfo"][act], sp, pos, inn, cone_radius, w, p_prev, mats["diffuse"][:, 0:3])
 
                 # each sample carries its bounce and its kind; their order within the bounce is frame_truth.pass_order's, not decided here
                 if do_emissive:
@@ -334,14 +350,18 @@ def replay_pass(prov, scn, res_x, res_y, options, instance, shifts, pixels=None,
                     e = eo[:, 2:5]
                     keep = wanted(e)
                     for k in np.nonzero(keep)[0]:
-                        samples[int(pix[k])].append((b, FT.EMISSIVE, int(comp_in[k]), e[k].copy()))
+                        if psf is not None:
+                            psf.emissive(b, int(pix[k]), int(comp_in[k]), q["vinfo"][act][k], e[k].copy(), samples)          # (:1147) the previous vertex's word
+                        else:
+                            samples[int(pix[k])].append((b, FT.EMISSIVE, int(comp_in[k]), e[k].copy()))
                     counts["emissive_kept"] += int(keep.sum())
                     if b >= 1:
                         counts["emissive_mis_partial"] += int((keep & (eo[:, 1] > 0) & (eo[:, 1] < 1)).sum())
 
                 def light_sample(kind, l_pos, l_n, l_rad, l_pdf, use_mis, eps, mask):
                     # the probe's two MIS option bits are both set and the bounce is the true one (it picks w_d / w_g's form): whether MIS applies is `use_mis`, the replay's
-                    lr = light_record(m, slot, sp, pos, inn, d, w, l_pos, l_n, l_rad, l_pdf, use_mis, eps, b, bsdf_opts | 4 | 8)
+                    pm, dm = psf.nee_mode(b, vx) if psf is not None else (None, None)
+                    lr = light_record(m, slot, sp, pos, inn, d, w, l_pos, l_n, l_rad, l_pdf, use_mis, eps, b, bsdf_opts | 4 | 8, pm, dm)
                     lo = np.asarray(prov.vertex(7, lr, mats=mats), F32)
                     w_d, w_g = lo[:, 1:4], lo[:, 4:7]
                     # kept iff max_comp(w_d + w_g) > 0 and all components finite
@@ -357,7 +377,10 @@ def replay_pass(prov, scn, res_x, res_y, options, instance, shifts, pixels=None,
                         occ = np.roll(occ, -1)
                     for j, k in enumerate(keep):
                         if not occ[j]:
-                            samples[int(pix[k])].append((b, kind, int(comp_in[k]), w_d[k].copy(), w_g[k].copy()))
+                            if psf is not None:
+                                psf.nee(b, kind, int(pix[k]), int(comp_in[k]), vx, k, w_d[k].copy(), w_g[k].copy(), samples)          # (:984, 1102)
+                            else:
+                                samples[int(pix[k])].append((b, kind, int(comp_in[k]), w_d[k].copy(), w_g[k].copy()))
                     return len(keep), m - len(keep), int(occ.sum()), int((~occ).sum()), lo
 
                 if do_directional:
@@ -369,7 +392,8 @@ def replay_pass(prov, scn, res_x, res_y, options, instance, shifts, pixels=None,
                     l_rad = (FAR * FAR) * l_col
                     l_pdf = np.full(m, F32(1.0) / F32(len(dir_lights)), F32)
                     if wrong is None:
-                        dr = light_record(m, slot, sp, pos, inn, d, w, l_pos, l_dir, l_rad, l_pdf, False, eps_dir, b, bsdf_opts | 4 | 8); dr[:, 44] = z[:, 2]
+                        pm, dm = psf.nee_mode(b, vx) if psf is not None else (None, None)
+                        dr = light_record(m, slot, sp, pos, inn, d, w, l_pos, l_dir, l_rad, l_pdf, False, eps_dir, b, bsdf_opts | 4 | 8, pm, dm); dr[:, 44] = z[:, 2]
                         d9 = np.asarray(prov.vertex(9, dr, mats=mats), F32)
                     k_, dr_, oc_, vi_, d7 = light_sample(FT.NEE_DIRECTIONAL, l_pos, l_dir, l_rad, l_pdf, wrong == "dir_mis", eps_dir, mask_dir)
                     counts["dir_kept"] += k_; counts["dir_dropped"] += dr_; counts["dir_occluded"] += oc_; counts["dir_visible"] += vi_
@@ -394,6 +418,8 @@ def replay_pass(prov, scn, res_x, res_y, options, instance, shifts, pixels=None,
                     comp = bo[:, 0].astype(np.int64)
                     out, p, p_proj, g = bo[:, 1:4], bo[:, 4], bo[:, 5], bo[:, 6:9]
                     out_w = g * w
+                    if psf is not None:
+                        out_w = psf.scatter_weight(b, vx, comp, g, w, out_w)          # compute_scattering_weights (:1196-1241)
                     # kept iff the component is not absorb, p != 0, max_comp > 0 and all components finite
                     keep = np.nonzero((comp != ABSORPTION) & (p != 0) & wanted(out_w))[0]
                     counts["absorbed"] += int((comp == ABSORPTION).sum())
@@ -410,6 +436,8 @@ def replay_pass(prov, scn, res_x, res_y, options, instance, shifts, pixels=None,
                               weight=np.concatenate([out_w[keep], (p_proj if wrong == "p_prev_proj" else p)[keep, None]], 1).astype(F32),
                               pixel_info=(pix[keep] | (comp[keep] << 27) | (diffuse << 31)).astype(U32),
                               cone=np.stack([cone_radius[keep], np.where(p[keep] > F32(32.0), p[keep], F32(32.0))], -1).astype(F32))      # (cone_radius, max(p, 32))
+                    if psf is not None:
+                        nq["vinfo"] = psf.scatter_info(b, q["vinfo"][act], vx, comp, keep)
                     st[3] = nk
             stats.append(tuple(st))
             q = nq
