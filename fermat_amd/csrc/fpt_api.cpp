@@ -22,6 +22,31 @@ void launch_debug_vertex(int op, uint32_t n, const fpt_rendering_context_view& v
                          uint32_t n_textures, const EmitterView& em, const ShadeRecord* shade_records, const float* rec, uint32_t rec_stride, float* out, hipStream_t s);
 // ... and the path-space-filtering probe's
 void launch_debug_psf(int op, uint32_t n, const PsfDev& psf, uint32_t n_cells, const void* in, void* out0, float* out1, hipStream_t s);
+// fpt_pt_init in two steps, which fpt_psfpt_init runs around its own checks: everything it refuses, writing nothing; then the set-up, which refuses nothing
+void pt_init_check(const fpt_pt_options* opts, const fpt_rendering_context_view* view, const uint32_t* d_pixels, uint32_t n_local_pixels)
+{
+	require(opts && view, "fpt_pt_init: null argument");
+	require(opts->max_path_length >= 1 && opts->max_path_length <= 31, "fpt_pt_init: max_path_length out of range [1,31]");
+	require(opts->nee_type <= 1, "fpt_pt_init: only the mesh and vpl NEE algorithms are implemented");
+	require(uint64_t(view->res_x) * view->res_y < (1ull << 27), "fpt_pt_init: PixelInfo holds 27-bit pixel indices");
+	require((d_pixels ? n_local_pixels : view->res_x * view->res_y) > 0, "fpt_pt_init: empty pixel set");
+}
+void pt_init_apply(fpt_context* ctx, const fpt_pt_options* opts, const fpt_rendering_context_view* view, const char* h_samples_dir, const uint32_t* d_pixels, uint32_t n_local_pixels)
+{
+	ctx->opt = *opts;
+	ctx->n_local = d_pixels ? n_local_pixels : view->res_x * view->res_y;
+	ctx->d_pixels = d_pixels;
+	// queue arena (alloc_queues, src/pathtracer_kernels.h:90-126): two path queues, one shadow queue per light kind
+	resize_wavefront(ctx, 1, view, false);
+	// sampler (PathTracer::init, src/renderers/pathtracer_impl.h:148-150)
+	build_shift_table(256, 6 * (opts->max_path_length + 1), h_samples_dir, ctx->crt_rand, ctx->h_shifts);
+	ctx->seq_dims = 6 * (opts->max_path_length + 1); ctx->seq_tile = 256;
+	ctx->d_shifts.upload(ctx->h_shifts.data(), ctx->h_shifts.size(), ctx->stream);
+	ctx->d_samples.alloc(ctx->h_shifts.size());
+	if (ctx->emitters.valid && ctx->emitters.n_vpls == 0) ctx->opt.nee_type = 0;     // :165-166
+	ctx->defer_max = 1;
+	ctx->pt_ready = true;
+}
 }
 
 namespace {
@@ -351,24 +376,8 @@ int fpt_pt_init(fpt_context* ctx, const fpt_pt_options* opts, const fpt_renderin
                 const uint32_t* d_pixels, uint32_t n_local_pixels)
 {
 	return guarded(ctx, [&] { flush_deferred(ctx);
-		require(opts && view, "fpt_pt_init: null argument");
-		require(opts->max_path_length >= 1 && opts->max_path_length <= 31, "fpt_pt_init: max_path_length out of range [1,31]");
-		require(opts->nee_type <= 1, "fpt_pt_init: only the mesh and vpl NEE algorithms are implemented");
-		require(uint64_t(view->res_x) * view->res_y < (1ull << 27), "fpt_pt_init: PixelInfo holds 27-bit pixel indices");
-		ctx->opt = *opts;
-		ctx->n_local = d_pixels ? n_local_pixels : view->res_x * view->res_y;
-		ctx->d_pixels = d_pixels;
-		require(ctx->n_local > 0, "fpt_pt_init: empty pixel set");
-		// queue arena (alloc_queues, src/pathtracer_kernels.h:90-126): two path queues, one shadow queue per light kind
-		resize_wavefront(ctx, 1, view, false);
-		// sampler (PathTracer::init, src/renderers/pathtracer_impl.h:148-150)
-		build_shift_table(256, 6 * (opts->max_path_length + 1), h_samples_dir, ctx->crt_rand, ctx->h_shifts);
-		ctx->seq_dims = 6 * (opts->max_path_length + 1); ctx->seq_tile = 256;
-		ctx->d_shifts.upload(ctx->h_shifts.data(), ctx->h_shifts.size(), ctx->stream);
-		ctx->d_samples.alloc(ctx->h_shifts.size());
-		if (ctx->emitters.valid && ctx->emitters.n_vpls == 0) ctx->opt.nee_type = 0;     // :165-166
-		ctx->defer_max = 1;
-		ctx->pt_ready = true;
+		pt_init_check(opts, view, d_pixels, n_local_pixels);
+		pt_init_apply(ctx, opts, view, h_samples_dir, d_pixels, n_local_pixels);
 	});
 }
 
@@ -618,11 +627,11 @@ static ContribLog log_from(ContribLog g, uint32_t first)
 	if (g.mask) g.mask += size_t(first) * g.mask_words;
 	return g;
 }
-// ctx->store.resize for this context; the held blocks of the fused resolves, which name its buffers, are forgotten
+// ctx->store.resize for this context; the held blocks of the fused resolves, which name its buffers, and a sharded PSFPT pass that waits in its reference queue are forgotten
 void resize_wavefront(fpt_context* ctx, uint32_t passes, const fpt_rendering_context_view* view, bool for_psfpt)
 {
 	ctx->store.resize(WavefrontStore::Shape{ ctx->n_local, passes, ctx->opt.max_path_length, view->dir_lights_count != 0, for_psfpt }, ctx->stream);
-	ctx->h_fused.clear(); ctx->psf.h_resolve.clear();
+	ctx->h_fused.clear(); ctx->psf.h_resolve.clear(); ctx->psf.forget_pass();
 	for (auto& X : ctx->extra_lanes) X->h_fused.clear();
 }
 // the lane's view of the context's log

@@ -285,8 +285,8 @@ extern "C" {
 int fpt_psfpt_exchange_cells(fpt_context* ctx)
 {
 	return guarded(ctx, [&] {
-		fpt_context::PsfState& ps = ctx->psf;
-		require(ps.sharded && ps.pending, "fpt_psfpt_exchange_cells: no sharded pass is pending (fpt_psfpt_set_sharded, fpt_psfpt_render)");
+		PsfState& ps = ctx->psf;
+		require(ps.pass_pending(), "fpt_psfpt_exchange_cells: no sharded pass is pending (fpt_psfpt_set_sharded, fpt_psfpt_render)");
 		require(ctx->comm != nullptr, "fpt_psfpt_exchange_cells: no communicator (fpt_comm_init / fpt_comm_adopt)");
 		const int W = ctx->comm_world, me = ctx->comm_rank;
 		ncclComm_t comm = static_cast<ncclComm_t>(ctx->comm);

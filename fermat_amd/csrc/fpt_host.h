@@ -23,6 +23,12 @@ inline void xbl_check_args(const void* dst, const void* img, const void* geo, co
 	require(w_img || !(op & 0x0fu), "fpt_xbl: a modulate or demodulate op needs a weight image");
 	require(dst != img, "fpt_xbl: dst must not alias img");
 }
+// what fpt_psfpt_init refuses of the PSF options (host only; tools/psf_owner_host_check.cpp runs it without a device)
+inline void psf_check_options(const fpt_psf_options* psf)
+{
+	require(psf != nullptr, "fpt_psfpt_init: null options");
+	require(psf->psf_temporal_reuse >= 1, "fpt_psfpt_init: psf_temporal_reuse must be >= 1");
+}
 // FPT_XBL_LAYOUT = 0 | 1 | 2 | 3 picks what fpt_filter_xbl prepares per channel (launch_xbl, fpt_kernels.h); the frame is the same bit for bit.  Default 3, the fastest
 // measured: EXPERIMENTS 6m
 inline int xbl_layout_from(const char* env)
@@ -400,24 +406,103 @@ struct BptState
 	}
 };
 
-// a table of the path-space filter's cache (fpt_kernels.h PsfDev): `tables` tables of 2^log2 slots each, side by side.  `listed`: pass tables, whose
-// live slots are listed in `touched` (as long as the tables) and counted in `touched_n` (one word per table)
+// a table of the path-space filter's cache (fpt_kernels.h PsfDev): `tables` tables of 2^log2 slots each, side by side.  Pass tables list their live slots in
+// `touched` (as long as the tables) and count them in `touched_n` (one word per table).  PsfState::resize gives the arrays their sizes and `log2` its value
 struct PsfTable
 {
 	DeviceArray<unsigned long long> keys; DeviceArray<long long> cells; uint32_t log2 = 0;
 	DeviceArray<uint32_t> touched, touched_n;
-	void alloc(uint32_t log2_size, size_t tables = 1, bool listed = false)
-	{
-		const size_t slots = (size_t(1) << log2_size) * tables;
-		log2 = log2_size; keys.alloc(slots); cells.alloc(slots * 4);
-		touched.alloc(listed ? slots : 0); touched_n.alloc(listed ? (tables > 32 ? tables : 32) : 0);
-	}
 	void clear(hipStream_t s)
 	{
-		FPT_HIP_CHECK(hipMemsetAsync(keys.ptr, 0xFF, keys.count * sizeof(unsigned long long), s));
-		FPT_HIP_CHECK(hipMemsetAsync(cells.ptr, 0, cells.count * sizeof(long long), s));
+		if (keys.ptr) FPT_HIP_CHECK(hipMemsetAsync(keys.ptr, 0xFF, keys.count * sizeof(unsigned long long), s));
+		if (cells.ptr) FPT_HIP_CHECK(hipMemsetAsync(cells.ptr, 0, cells.count * sizeof(long long), s));
 		if (touched_n.ptr) FPT_HIP_CHECK(hipMemsetAsync(touched_n.ptr, 0, touched_n.count * sizeof(uint32_t), s));
 	}
+};
+// the slots of a pass table of a batch: 2^b >= (pixels rendered here) x (max_path_length + 1) >= the cells a pass can create, at least 2^10, at most the global table's
+inline uint32_t psf_pass_table_log2(uint32_t n_local, uint32_t max_path_length, uint32_t global_log2)
+{
+	uint32_t b = 10;
+	while ((size_t(1) << b) < size_t(n_local) * (max_path_length + 1) && b < global_log2) ++b;
+	return b;
+}
+
+// The state of the path-space-filtering path tracer (fpt_psf_api.cpp; its queues, log and reference queue are the WavefrontStore's) and its one owner:
+//   1. Refuse first.  Every refusal of fpt_psfpt_init (null options, psf_temporal_reuse < 1: psf_check_options; everything fpt_pt_init refuses: pt_init_check), of
+//      fpt_psfpt_set_batch, fpt_psfpt_set_sharded and fpt_psfpt_debug_set_table_log2 happens before the first write to this state, the PT's set-up, the store or the
+//      context's random stream: a refused call leaves everything as it was and usable.
+//   2. Invalid while changing.  `shape` says what every array is sized for, and from the first write of an init or a re-size to the last it is empty: ready() is false.
+//      A throw in between (out of memory, the bbox read) leaves NO PSF state, and every reader answers "fpt_psfpt_init has not been called".  resize() is the only set-up
+//      code that allocates, releases or clears the tables (a render clears what its pass has to find empty); it clears on the given stream and does not synchronise.
+//   3. An init replaces everything: after it the state is unsharded, has one pass in flight and no pending pass, `rendered` is false, ref_stride and ref_mode are 0 and
+//      h_resolve is forgotten.  Whoever wants a sharded or a batched state calls fpt_psfpt_set_sharded / fpt_psfpt_set_batch after EVERY init.  forget_pass() clears
+//      the pending markers; reset() releases everything.
+//   4. Each array stands ONCE in each_array() with its elements as a function of the shape; an array the shape does not use has none and is released (the shard table,
+//      its list and `records` of an unsharded state; the pass tables of one pass in flight).  The exchange's staging (recv, ex_counts) has no elements there: a
+//      re-size releases it and the exchange grows it to what the ranks send (fpt_psfpt_exchange_cells).
+//   5. Readers check first (state_of, fpt_psf_api.cpp): the render entry points, fpt_psfpt_set_batch, fpt_psfpt_set_sharded, fpt_psfpt_debug_set_table_log2,
+//      fpt_psfpt_download_cells, fpt_psfpt_debug_download_refs; the export / import / exchange / finish calls of a sharded pass ask pass_pending(), false without a state.
+//   6. The store under a pending pass.  resize_wavefront (fpt_api.cpp), the one place the store is re-shaped, calls forget_pass(): a pass whose reference queue is gone
+//      cannot be finished.  fpt_psfpt_finish asks the store serves() before it launches.
+//   Beyond the owner's methods the entry points write only the exchange's staging and d_resolve / h_resolve (upload_if_changed, per render).
+struct PsfState
+{
+	// the global table's slots (0 = no state); the shard's pass table, as large as the global one, its list and `records` exist; passes in flight, from two on with one
+	// pass table of 2^pass_log2 slots each
+	struct Shape { uint32_t table_log2 = 0; bool sharded = false; uint32_t passes = 0, pass_log2 = 0; };
+	Shape shape;
+	fpt_psf_options opt{};
+	bool rendered = false;                              // a pass has run (fpt_psfpt_debug_set_table_log2 re-sizes the table only before)
+	uint32_t ref_stride = 0, ref_mode = 0;              // the last render's: entries per bounce of the queue, and the table its cache words name (0 global, 1 the shard's pass table, 2 a batch's)
+	float bbox[6] = { 0, 0, 0, 0, 0, 0 };
+	bool pending = false; uint32_t pending_instance = 0, pending_bounces = 0;      // sharded: a pass has been rendered and waits for fpt_psfpt_finish
+	PsfTable table, shard, batch;                       // the global table; the shard's pass table; one pass table per pass of a batch
+	DeviceArray<uint32_t> ref_size;                     // the reference queue's fill, one word per bounce
+	DeviceArray<PsfRecord> records, recv; DeviceArray<uint32_t> ex_counts;      // sharded: this rank's records of the pass in flight; the exchange's receive buffer and counts
+	DeviceArray<ResolveParams> d_resolve; std::vector<ResolveParams> h_resolve;      // per-bounce blocks read by the MIXED launches with the fused cache-aware resolve
+
+	// the list: v(array, elements).  Its order is the order of allocation (EXPERIMENTS 6i)
+	template <typename V> void each_array(const Shape& s, V&& v)
+	{
+		const size_t g = s.table_log2 ? size_t(1) << s.table_log2 : 0, sh = s.sharded ? g : 0, b = s.passes > 1 ? (size_t(1) << s.pass_log2) * s.passes : 0;
+		v(table.keys, g); v(table.cells, 4 * g); v(ref_size, g ? 32 : 0);
+		v(shard.keys, sh); v(shard.cells, 4 * sh); v(shard.touched, sh); v(shard.touched_n, sh ? 32 : 0); v(records, sh);
+		v(batch.keys, b); v(batch.cells, 4 * b); v(batch.touched, b); v(batch.touched_n, b ? std::max<size_t>(s.passes, 32) : 0);
+		v(recv, 0); v(ex_counts, 0);
+	}
+	void forget_pass() { pending = false; pending_instance = pending_bounces = 0; }
+	void invalidate() { shape = Shape{}; forget_pass(); }          // part 2: no PSF state from here on, until init() or resize() has made one
+	// part 2.  The pass tables are cleared, so a pass that waits in one is forgotten; the global table keeps its cells unless its size changes (an init starts from no
+	// shape).  `then`: what an init still has to do before the state is valid
+	template <typename F> void resize(const Shape& s, hipStream_t stream, F&& then)
+	{
+		const bool keep_cells = shape.table_log2 == s.table_log2;
+		invalidate(); table.log2 = shard.log2 = batch.log2 = 0;
+		each_array(s, [](auto& a, size_t n) { a.alloc(n); });
+		table.log2 = s.table_log2; shard.log2 = s.sharded ? s.table_log2 : 0; batch.log2 = s.passes > 1 ? s.pass_log2 : 0;
+		if (!keep_cells) table.clear(stream);
+		shard.clear(stream); batch.clear(stream);
+		then();
+		shape = s;
+	}
+	void resize(const Shape& s, hipStream_t stream) { resize(s, stream, [] {}); }
+	// part 3: what fpt_psfpt_init does once nothing can refuse any more and the store is shaped.  `read_bbox(bbox)` reads the scene's box on the host: after the
+	// device arrays are allocated, as ever (EXPERIMENTS 6k)
+	template <typename F> void init(const fpt_psf_options& o, uint32_t table_log2, hipStream_t stream, F&& read_bbox)
+	{
+		invalidate(); opt = o; rendered = false; ref_stride = ref_mode = 0; h_resolve.clear();
+		resize(Shape{ table_log2, false, 1, 0 }, stream, [&] { read_bbox(bbox); });
+	}
+	void reset()
+	{
+		init(fpt_psf_options{}, 0, nullptr, [](float* b) { std::fill(b, b + 6, 0.0f); });          // no table, no elements: every array is released
+		shape = Shape{}; d_resolve.release();
+	}
+	bool ready() const { return shape.table_log2 != 0; }
+	bool pass_pending() const { return shape.sharded && pending; }
+	// the writes of a render: a pass starts; a sharded pass waits for fpt_psfpt_finish
+	void begin_pass(uint32_t stride, uint32_t mode) { rendered = true; ref_stride = stride; ref_mode = mode; }
+	void hold_pass(uint32_t instance, uint32_t bounces) { pending = true; pending_instance = instance; pending_bounces = bounces; }
 };
 } // namespace fpt
 
@@ -478,26 +563,7 @@ struct fpt_context
 	hipEvent_t lane_start = nullptr;
 	fpt::DeviceArray<float4> filter_tmp[2], filter_nrm; fpt::DeviceArray<float> filter_var;     // fpt_filter scratch (ping-pong images, variance)
 	fpt::DeviceArray<float4> filter_rec;                                                        // fpt_filter_xbl scratch: 3 float4 per pixel { geo, normal, colour } (layout 2 only)
-	// path-space filtering (PSFPT): hash table of cache cells (its reference queue is the store's)
-	struct PsfState
-	{
-		bool ready = false, rendered = false;       // rendered: a pass has run (fpt_psfpt_debug_set_table_log2 re-sizes the table only before)
-		fpt_psf_options opt{};
-		fpt::PsfTable table;                        // the global table
-		fpt::DeviceArray<uint32_t> ref_size;        // the reference queue's fill, one word per bounce
-		uint32_t ref_stride = 0, ref_mode = 0;      // the last render's: entries per bounce of the queue, and the table its cache words name (0 global, 1 the shard's pass table, 2 a batch's)
-		float bbox[6] = { 0, 0, 0, 0, 0, 0 };
-		fpt::DeviceArray<fpt::ResolveParams> d_resolve;     // per-bounce blocks read by the MIXED launches with the fused cache-aware resolve
-		std::vector<fpt::ResolveParams> h_resolve;
-		// tile sharding (fpt_psfpt_set_sharded): the pass table with the list of its live slots, this rank's records of the pass in flight and the
-		// receive buffer of the exchange; `pending` = a pass has been rendered and waits for fpt_psfpt_finish
-		bool sharded = false, pending = false;
-		uint32_t pending_instance = 0, pending_bounces = 0;
-		fpt::PsfTable shard;
-		fpt::DeviceArray<fpt::PsfRecord> records, recv;
-		fpt::DeviceArray<uint32_t> ex_counts;
-		fpt::PsfTable batch;                        // passes in flight (fpt_psfpt_set_batch): one pass table per pass of the batch, with the lists of their live slots
-	} psf;
+	fpt::PsfState psf;                                   // the path-space filter's state and everything that describes it (its reference queue is the store's)
 	fpt::BptState bpt;                                   // the bidirectional path tracer's state and everything that describes it
 	// The state of the two Metropolis renderers on the bidirectional state above (fpt_mlt_api.cpp) and its one owner: `-pssmlt` (fpt_pssmlt_init) and `-mmlt`
 	// (fpt_mmlt_init; `lens`: with its lens techniques (s, 1)) are two modes of one state, and one init of either leaves the other nothing.
@@ -632,10 +698,13 @@ namespace fpt { void comm_allreduce_sum64(fpt_context* ctx, void* d_values, size
 // BPT, shared light vertices (fpt_bpt_api.cpp): this rank's vertices of the batch in flight -> ctx->bpt.lv_send (returns their number); wire records -> the store
 namespace fpt { uint32_t bpt_pack_own_vertices(fpt_context* ctx); void bpt_import_vertices(fpt_context* ctx, const LightVertexWire* d_records, uint32_t count); }
 
-// fpt_api.cpp, called inside the caller's `guarded`.  resize_wavefront: ctx->store.resize, and the held blocks of the fused resolves, which name its buffers, are
-// forgotten.  set_batch: fpt_pt_set_batch's body, the shared part of fpt_psfpt_set_batch's
+// fpt_api.cpp, called inside the caller's `guarded`.  resize_wavefront: ctx->store.resize, and the held blocks of the fused resolves, which name its buffers, and a
+// pending PSFPT pass are forgotten.  set_batch: fpt_pt_set_batch's body, the shared part of fpt_psfpt_set_batch's.  pt_init_check / pt_init_apply: fpt_pt_init's two
+// steps -- every refusal, writing nothing; the set-up, refusing nothing -- which fpt_psfpt_init runs around its own checks (PsfState, part 1)
 namespace fpt { void resize_wavefront(fpt_context* ctx, uint32_t passes, const fpt_rendering_context_view* view, bool for_psfpt);
-                void set_batch(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_context_view* view, bool for_psfpt); }
+                void set_batch(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_context_view* view, bool for_psfpt);
+                void pt_init_check(const fpt_pt_options* opts, const fpt_rendering_context_view* view, const uint32_t* d_pixels, uint32_t n_local_pixels);
+                void pt_init_apply(fpt_context* ctx, const fpt_pt_options* opts, const fpt_rendering_context_view* view, const char* h_samples_dir, const uint32_t* d_pixels, uint32_t n_local_pixels); }
 // fpt_bpt_api.cpp: what fpt_bpt_set_batch allocates per path in flight, with every pixel rendered here
 namespace fpt { uint64_t bpt_bytes_per_path(fpt_context* ctx); }
 // fpt_bpt_api.cpp, for the Metropolis renderers (inside the caller's `guarded`).  bpt_init: fpt_bpt_init's body, storage for at least `min_paths` paths; the one init of

@@ -12,12 +12,18 @@ namespace {
 // the cache as the kernels see it.  PLAIN: the one table in keys / cells.  SHARDED: the pass table there, the global table in g_keys / g_cells.  BATCHED: one
 // pass table per pass of the batch there (pass_stride apart), the global table in g_keys / g_cells.  bbox_* and instance are the render's to add
 enum PsfMode { PSF_PLAIN, PSF_SHARDED, PSF_BATCHED };
+// PsfState, part 5
+PsfState& state_of(fpt_context* ctx, const char* who)
+{
+	if (!ctx->psf.ready()) throw std::runtime_error(std::string(who) + ": fpt_psfpt_init has not been called");
+	return ctx->psf;
+}
 PsfDev psf_dev(fpt_context* ctx, PsfMode mode)
 {
-	fpt_context::PsfState& ps = ctx->psf; WavefrontStore& w = ctx->store;
+	PsfState& ps = ctx->psf; WavefrontStore& w = ctx->store;
 	PsfDev psf; std::memset(&psf, 0, sizeof(psf));
 	const PsfTable& t = mode == PSF_BATCHED ? ps.batch : mode == PSF_SHARDED ? ps.shard : ps.table;
-	psf.keys = t.keys.ptr; psf.cells = t.cells.ptr; psf.log2_size = mode == PSF_BATCHED ? t.log2 : ps.table.log2; psf.g_log2_size = ps.table.log2;
+	psf.keys = t.keys.ptr; psf.cells = t.cells.ptr; psf.log2_size = t.log2; psf.g_log2_size = ps.table.log2;
 	if (mode != PSF_PLAIN) { psf.g_keys = ps.table.keys.ptr; psf.g_cells = ps.table.cells.ptr; psf.touched = t.touched.ptr; psf.touched_n = t.touched_n.ptr; }
 	if (mode == PSF_BATCHED) psf.pass_stride = 1u << t.log2;
 	psf.ref_pixels = w.ref_pixels.ptr; psf.ref_cache = w.ref_cache.ptr; psf.ref_wd = w.ref_wd.ptr; psf.ref_wg = w.ref_wg.ptr; psf.ref_size = ps.ref_size.ptr; psf.ref_k = w.ref_k.ptr;
@@ -35,7 +41,7 @@ PsfDev at_bounce(const PsfDev& psf, uint32_t bounce, uint32_t n)
 // psf_blending, update_variances, clamp_frame(100): the tail of PSFPT::render (src/renderers/psfpt_impl.h:275-284, 402-420)
 void finish_pass(fpt_context* ctx, const PsfDev& psf, const FrameBufferDev& fb, uint32_t instance, uint32_t bounces_run)
 {
-	fpt_context::PsfState& ps = ctx->psf;
+	PsfState& ps = ctx->psf;
 	hipStream_t s = ctx->stream;
 	const uint32_t n = ctx->n_local;
 	const float frame_weight = 1.0f / float(instance + 1);
@@ -51,45 +57,42 @@ extern "C" {
 int fpt_psfpt_init(fpt_context* ctx, const fpt_pt_options* opts, const fpt_psf_options* psf, const fpt_rendering_context_view* view,
                    const char* h_samples_dir, const uint32_t* d_pixels, uint32_t n_local_pixels)
 {
-	const int st = fpt_pt_init(ctx, opts, view, h_samples_dir, d_pixels, n_local_pixels);
-	if (st != 0) return st;
-	return guarded(ctx, [&] {
-		require(psf != nullptr, "fpt_psfpt_init: null options");
-		require(psf->psf_temporal_reuse >= 1, "fpt_psfpt_init: psf_temporal_reuse must be >= 1");
-		fpt_context::PsfState& s = ctx->psf;
-		s.opt = *psf;
+	return guarded(ctx, [&] { flush_deferred(ctx);
+		pt_init_check(opts, view, d_pixels, n_local_pixels);
+		psf_check_options(psf);
+		ctx->psf.invalidate();          // PsfState, part 2: the PT's set-up and the store change under the state from here on
+		pt_init_apply(ctx, opts, view, h_samples_dir, d_pixels, n_local_pixels);
 		// the store's extras: per-path vertex info, per-shadow-sample hit records and the reference queue.  PSFRefQueue: n_pixels * (L + 1) entries as in the
 		// reference (:176-181).  A path can open a new cache vertex after every glossy bounce, i.e. own several references; they are kept per bounce (<= 1 per
 		// path and bounce) and blended bounce by bounce, which makes the per-pixel order of the blend the order of creation without any atomics
 		resize_wavefront(ctx, 1, view, true);
 		// cache: the reference allocates 64M cells (HASH_SIZE, src/renderers/psfpt_impl.h:46); a cell is addressed by key, so the table size only
 		// has to exceed the number of live cells: 2^26 for frames beyond a megapixel, 2^24 below
-		s.table.alloc(uint64_t(view->res_x) * view->res_y > (1u << 20) ? 26u : 24u); s.table.clear(ctx->stream);
-		s.ref_size.alloc(32);
-		// m_bbox = renderer.compute_bbox(): over the mesh vertices (src/renderer.cu:1086-1097)
-		std::vector<float> vtx(size_t(view->mesh.num_vertices) * 4);
-		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		if (!vtx.empty()) FPT_HIP_CHECK(hipMemcpy(vtx.data(), view->mesh.vertex_data, vtx.size() * sizeof(float), hipMemcpyDeviceToHost));
-		float lo[3] = { 1.0e30f, 1.0e30f, 1.0e30f }, hi[3] = { -1.0e30f, -1.0e30f, -1.0e30f };
-		for (int i = 0; i < view->mesh.num_vertices; ++i) for (int c = 0; c < 3; ++c)
-		{
-			const float v = vtx[size_t(i) * 4 + c];
-			lo[c] = lo[c] < v ? lo[c] : v; hi[c] = hi[c] > v ? hi[c] : v;
-		}
-		for (int c = 0; c < 3; ++c) { s.bbox[c] = lo[c]; s.bbox[3 + c] = hi[c]; }
-		s.ready = true;
+		ctx->psf.init(*psf, uint64_t(view->res_x) * view->res_y > (1u << 20) ? 26u : 24u, ctx->stream, [&](float* bbox) {
+			// m_bbox = renderer.compute_bbox(): over the mesh vertices (src/renderer.cu:1086-1097)
+			std::vector<float> vtx(size_t(view->mesh.num_vertices) * 4);
+			FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+			if (!vtx.empty()) FPT_HIP_CHECK(hipMemcpy(vtx.data(), view->mesh.vertex_data, vtx.size() * sizeof(float), hipMemcpyDeviceToHost));
+			float lo[3] = { 1.0e30f, 1.0e30f, 1.0e30f }, hi[3] = { -1.0e30f, -1.0e30f, -1.0e30f };
+			for (int i = 0; i < view->mesh.num_vertices; ++i) for (int c = 0; c < 3; ++c)
+			{
+				const float v = vtx[size_t(i) * 4 + c];
+				lo[c] = lo[c] < v ? lo[c] : v; hi[c] = hi[c] > v ? hi[c] : v;
+			}
+			for (int c = 0; c < 3; ++c) { bbox[c] = lo[c]; bbox[3 + c] = hi[c]; }
+		});
 	});
 }
 
 int fpt_psfpt_debug_set_table_log2(fpt_context* ctx, uint32_t log2_size)
 {
 	return guarded(ctx, [&] {
-		fpt_context::PsfState& s = ctx->psf;
-		require(s.ready, "fpt_psfpt_debug_set_table_log2: fpt_psfpt_init has not been called");
-		require(!s.rendered && !s.sharded && ctx->store.shape.passes <= 1, "fpt_psfpt_debug_set_table_log2: call it before the first render, fpt_psfpt_set_batch and fpt_psfpt_set_sharded");
+		PsfState& s = state_of(ctx, "fpt_psfpt_debug_set_table_log2");
+		require(!s.rendered && !s.shape.sharded && s.shape.passes <= 1 && ctx->store.shape.passes <= 1, "fpt_psfpt_debug_set_table_log2: call it before the first render, fpt_psfpt_set_batch and fpt_psfpt_set_sharded");
 		require(log2_size >= 8 && log2_size <= 24, "fpt_psfpt_debug_set_table_log2: log2_size must be 8..24");
 		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		s.table.alloc(log2_size); s.table.clear(ctx->stream);
+		PsfState::Shape shape = s.shape; shape.table_log2 = log2_size;
+		s.resize(shape, ctx->stream);
 		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 	});
 }
@@ -98,8 +101,7 @@ int fpt_psfpt_download_cells(fpt_context* ctx, uint64_t* h_keys, uint64_t* h_cou
 {
 	return guarded(ctx, [&] {
 		flush_deferred(ctx);
-		fpt_context::PsfState& s = ctx->psf;
-		require(s.ready, "fpt_psfpt_download_cells: fpt_psfpt_init has not been called");
+		PsfState& s = state_of(ctx, "fpt_psfpt_download_cells");
 		const size_t n = size_t(1) << s.table.log2;
 		std::vector<unsigned long long> keys(n); std::vector<long long> cells(n * 4);
 		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -121,8 +123,7 @@ int fpt_psfpt_debug_download_refs(fpt_context* ctx, uint32_t bounce, uint32_t* h
 {
 	return guarded(ctx, [&] {
 		flush_deferred(ctx);
-		fpt_context::PsfState& s = ctx->psf; WavefrontStore& w = ctx->store;
-		require(s.ready, "fpt_psfpt_debug_download_refs: fpt_psfpt_init has not been called");
+		PsfState& s = state_of(ctx, "fpt_psfpt_debug_download_refs"); WavefrontStore& w = ctx->store;
 		require(bounce < 32, "fpt_psfpt_debug_download_refs: bounce must be below 32");
 		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 		uint32_t n = 0;
@@ -159,17 +160,17 @@ int fpt_psfpt_debug_download_refs(fpt_context* ctx, uint32_t bounce, uint32_t* h
 // merge_passes applies rescale / planes / variances / clamp_frame pass by pass.  The cache is bit-identical to n sequential calls, the frame to rounding.
 static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, const fpt_rendering_context_view* view)
 {
-		fpt_context::PsfState& ps = ctx->psf;
-		require(ps.ready && ctx->pt_ready, "fpt_psfpt_render: fpt_psfpt_init has not been called");
+		PsfState& ps = state_of(ctx, "fpt_psfpt_render");
+		require(ctx->pt_ready, "fpt_psfpt_render: fpt_psfpt_init has not been called");
 		require(ctx->tree.valid, "fpt_psfpt_render: create_geometry has not been called");
 		require(ctx->emitters.valid, "fpt_psfpt_render: fpt_mesh_lights_init has not been called");
-		ps.rendered = true;
-		const bool batched = n_passes > 1;
-		require(!batched || !ps.sharded, "fpt_psfpt_render_batch: a sharded context renders one pass at a time");
+		const bool batched = n_passes > 1, sharded = ps.shape.sharded;
+		require(!batched || !sharded, "fpt_psfpt_render_batch: a sharded context renders one pass at a time");
+		require(!ps.pass_pending(), "fpt_psfpt_render: the previous pass has not been finished (fpt_psfpt_exchange_cells / fpt_psfpt_import_cells, then fpt_psfpt_finish)");
 		// the store is shared with the plain path tracer: a later fpt_pt_init / fpt_pt_set_batch / fpt_pt_set_deferred re-shapes it without the PSFPT's extras, and a
 		// view with directional lights needs their queue and log cells
 		WavefrontStore& w = ctx->store;
-		require(w.serves(n_passes, true, view->dir_lights_count != 0),
+		require(w.serves(n_passes, true, view->dir_lights_count != 0) && n_passes <= ps.shape.passes,
 		        "fpt_psfpt_render_batch: more passes than fpt_psfpt_set_batch sized the storage for, the storage was re-shaped by fpt_pt_set_batch since, or the view has "
 		        "directional lights and it was sized without them: call fpt_psfpt_set_batch with this view");
 		hipStream_t s = ctx->stream;
@@ -189,10 +190,9 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 		if (batched) { pass.n_slot = ctx->n_local; pass.acc_stride = ctx->n_local; pass.pixels = ctx->d_pixels; }
 		else         { pass.n_slot = view->res_x * view->res_y; pass.acc_stride = pass.n_slot; pass.pixels = nullptr; }
 		SequenceView seq; seq.shifts = ctx->d_shifts.ptr; seq.n_dims = ctx->seq_dims; seq.tile_size = ctx->seq_tile;
-		require(!ps.sharded || !ps.pending, "fpt_psfpt_render: the previous pass has not been finished (fpt_psfpt_exchange_cells / fpt_psfpt_import_cells, then fpt_psfpt_finish)");
 		// batched: one pass table per pass of the batch (2^log2 slots each, enough for every cell a pass can create), their slot lists, the global table
-		PsfDev psf = psf_dev(ctx, batched ? PSF_BATCHED : ps.sharded ? PSF_SHARDED : PSF_PLAIN);
-		ps.ref_stride = n; ps.ref_mode = batched ? 2u : ps.sharded ? 1u : 0u;
+		PsfDev psf = psf_dev(ctx, batched ? PSF_BATCHED : sharded ? PSF_SHARDED : PSF_PLAIN);
+		ps.begin_pass(n, batched ? 2u : sharded ? 1u : 0u);
 		psf.bbox_lo = mk3(ps.bbox[0], ps.bbox[1], ps.bbox[2]); psf.bbox_hi = mk3(ps.bbox[3], ps.bbox[4], ps.bbox[5]); psf.instance = instance;
 
 		// the rays are those of the renderer's own queues (fpt_device.h PathQueue / ShadowQueue): the .w words carry PixelInfo / pass offset, the intervals are the queues'
@@ -271,11 +271,11 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 			std::swap(qa, qb);
 			qin = qa->view(cnt.queue(bounce + 1, CNT_PATH)); qout = qb->view(cnt.queue(bounce + 2, CNT_PATH));
 		}
-		if (ps.sharded)
+		if (sharded)
 		{
 			// this rank's cells of the pass -> records; the frame is completed by fpt_psfpt_finish once every rank's records are in the global table
 			launch_psf_collect(psf, ps.records.ptr, s);
-			ps.pending = true; ps.pending_instance = instance; ps.pending_bounces = bounces_run;
+			ps.hold_pass(instance, bounces_run);
 			FPT_HIP_CHECK(hipGetLastError());
 			return;
 		}
@@ -312,7 +312,7 @@ int fpt_psfpt_render(fpt_context* ctx, uint32_t instance, const fpt_rendering_co
 {
 	return guarded(ctx, [&] {
 		require(view != nullptr, "fpt_psfpt_render: null view");
-		if (ctx->defer_kind != DEFER_PSFPT || ctx->defer_max <= 1 || ctx->psf.sharded) { flush_deferred(ctx); render_psf(ctx, instance, 1, view); return; }
+		if (ctx->defer_kind != DEFER_PSFPT || ctx->defer_max <= 1 || ctx->psf.shape.sharded) { flush_deferred(ctx); render_psf(ctx, instance, 1, view); return; }
 		defer_pass(ctx, DEFER_PSFPT, instance, view);          // fpt_psfpt_set_deferred: consecutive instances of the same view, as fpt_pt_render
 	});
 }
@@ -331,16 +331,12 @@ int fpt_psfpt_set_deferred(fpt_context* ctx, uint32_t max_passes, const fpt_rend
 int fpt_psfpt_set_batch(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_context_view* view)
 {
 	return guarded(ctx, [&] {
-		fpt_context::PsfState& ps = ctx->psf;
-		require(ps.ready, "fpt_psfpt_set_batch: fpt_psfpt_init has not been called");
-		require(!ps.sharded || max_passes == 1, "fpt_psfpt_set_batch: a sharded context renders one pass at a time");
+		PsfState& ps = state_of(ctx, "fpt_psfpt_set_batch");
+		require(!ps.shape.sharded || max_passes == 1, "fpt_psfpt_set_batch: a sharded context renders one pass at a time");
 		set_batch(ctx, max_passes, view, true);
-		if (max_passes > 1)
-		{
-			uint32_t b = 10;
-			while ((size_t(1) << b) < size_t(ctx->n_local) * (ctx->opt.max_path_length + 1) && b < ps.table.log2) ++b;
-			ps.batch.alloc(b, max_passes, true); ps.batch.clear(ctx->stream);
-		}
+		PsfState::Shape shape = ps.shape; shape.passes = max_passes;
+		shape.pass_log2 = max_passes > 1 ? psf_pass_table_log2(ctx->n_local, ctx->opt.max_path_length, shape.table_log2) : 0;
+		ps.resize(shape, ctx->stream);
 		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 	});
 }
@@ -349,21 +345,18 @@ int fpt_psfpt_set_sharded(fpt_context* ctx, int on)
 {
 	return guarded(ctx, [&] {
 		flush_deferred(ctx);
-		fpt_context::PsfState& ps = ctx->psf;
-		require(ps.ready, "fpt_psfpt_set_sharded: fpt_psfpt_init has not been called");
+		PsfState& ps = state_of(ctx, "fpt_psfpt_set_sharded");
 		require(!ps.pending, "fpt_psfpt_set_sharded: a pass is pending");
-		ps.sharded = on != 0;
-		if (!ps.sharded) return;
-		ps.shard.alloc(ps.table.log2, 1, true); ps.shard.clear(ctx->stream);
-		ps.records.alloc(size_t(1) << ps.table.log2);
+		PsfState::Shape shape = ps.shape; shape.sharded = on != 0;
+		ps.resize(shape, ctx->stream);
 	});
 }
 
 int fpt_psfpt_export_cells(fpt_context* ctx, const void** d_records, uint32_t* n_records)
 {
 	return guarded(ctx, [&] {
-		fpt_context::PsfState& ps = ctx->psf;
-		require(ps.sharded && ps.pending, "fpt_psfpt_export_cells: no sharded pass is pending");
+		PsfState& ps = ctx->psf;
+		require(ps.pass_pending(), "fpt_psfpt_export_cells: no sharded pass is pending");
 		require(d_records && n_records, "fpt_psfpt_export_cells: null argument");
 		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 		FPT_HIP_CHECK(hipMemcpy(n_records, ps.shard.touched_n.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -374,8 +367,7 @@ int fpt_psfpt_export_cells(fpt_context* ctx, const void** d_records, uint32_t* n
 int fpt_psfpt_import_cells(fpt_context* ctx, const void* d_records, uint32_t n_records)
 {
 	return guarded(ctx, [&] {
-		fpt_context::PsfState& ps = ctx->psf;
-		require(ps.sharded && ps.pending, "fpt_psfpt_import_cells: no sharded pass is pending");
+		require(ctx->psf.pass_pending(), "fpt_psfpt_import_cells: no sharded pass is pending");
 		require(d_records || n_records == 0, "fpt_psfpt_import_cells: null records");
 		if (!n_records) return;
 		launch_psf_merge(psf_dev(ctx, PSF_SHARDED), static_cast<const PsfRecord*>(d_records), nullptr, n_records, ctx->stream);
@@ -386,14 +378,16 @@ int fpt_psfpt_import_cells(fpt_context* ctx, const void* d_records, uint32_t n_r
 int fpt_psfpt_finish(fpt_context* ctx, const fpt_rendering_context_view* view)
 {
 	return guarded(ctx, [&] {
-		fpt_context::PsfState& ps = ctx->psf;
-		require(ps.sharded && ps.pending, "fpt_psfpt_finish: no sharded pass is pending");
+		PsfState& ps = ctx->psf;
+		require(ps.pass_pending(), "fpt_psfpt_finish: no sharded pass is pending");
+		require(view != nullptr, "fpt_psfpt_finish: null view");
+		require(ctx->store.serves(1, true, view->dir_lights_count != 0), "fpt_psfpt_finish: the storage was re-shaped since the pass was rendered");
 		PsfDev psf = psf_dev(ctx, PSF_SHARDED);
 		psf.instance = ps.pending_instance;
 		finish_pass(ctx, psf, fb_dev(view->fb), ps.pending_instance, ps.pending_bounces);
 		launch_psf_clear_pass(psf, ctx->stream);
 		FPT_HIP_CHECK(hipMemsetAsync(ps.shard.touched_n.ptr, 0, sizeof(uint32_t), ctx->stream));
-		ps.pending = false;
+		ps.forget_pass();
 		FPT_HIP_CHECK(hipGetLastError());
 	});
 }

@@ -302,7 +302,10 @@ typedef struct fpt_psf_options
 	uint32_t psf_temporal_reuse;   /* -temporal-reuse   : the cache is cleared every this many passes (64) */
 	float    firefly_filter;       /* -firefly-filter   : clamp of every accumulated sample (100)        */
 } fpt_psf_options;
-/* PSFPT::init (src/renderers/psfpt_impl.h:184-273) = the path tracer's init + cache and reference-queue storage */
+/* PSFPT::init (src/renderers/psfpt_impl.h:184-273) = the path tracer's init + cache and reference-queue storage.  Every refusal (what fpt_pt_init refuses, null PSF
+ * options, psf_temporal_reuse < 1) comes before the first write: a refused call leaves the PSFPT, the PT's set-up and the random stream as they were.  A successful one
+ * replaces the whole PSF state: an empty cache, NOT sharded, ONE pass in flight, no pass pending -- call fpt_psfpt_set_sharded / fpt_psfpt_set_batch / _set_deferred
+ * after EVERY init that wants them. */
 int fpt_psfpt_init(fpt_context* ctx, const fpt_pt_options* opts, const fpt_psf_options* psf, const fpt_rendering_context_view* view,
                    const char* h_samples_dir, const uint32_t* d_pixels, uint32_t n_local_pixels);
 /* PSFPT::render (:275-284): rescale, path_trace_loop with the PSFPT vertex processor, psf_blending, update_variances, clamp_frame(100) */
@@ -326,11 +329,14 @@ int fpt_psfpt_set_deferred(fpt_context* ctx, uint32_t max_passes, const fpt_rend
  *   fpt_psfpt_exchange_cells : the exchange over the context's RCCL communicator (one all-reduce of the counts, one group of sends / receives)
  *                              and the merge of every rank's records, this rank's included;
  *   fpt_psfpt_export_cells / fpt_psfpt_import_cells : the same by hand (device pointer to this rank's records / merge a list of records), for a
- *                              host that moves the records itself; the own records must be imported too. */
+ *                              host that moves the records itself; the own records must be imported too.
+ * fpt_psfpt_set_sharded(ctx, 0) releases the pass table and the records; fpt_psfpt_init resets the context to unsharded.  Refused while a pass is pending. */
 int fpt_psfpt_set_sharded(fpt_context* ctx, int on);
 int fpt_psfpt_exchange_cells(fpt_context* ctx);
 int fpt_psfpt_export_cells(fpt_context* ctx, const void** d_records, uint32_t* n_records);
 int fpt_psfpt_import_cells(fpt_context* ctx, const void* d_records, uint32_t n_records);
+/* Refused ("no sharded pass is pending") when nothing waits: after fpt_psfpt_init, and after anything that re-shaped the passes-in-flight storage under the pass
+ * (fpt_pt_init, fpt_pt_set_batch, fpt_pt_set_deferred, fpt_psfpt_set_batch), which forgets it: render the pass again. */
 int fpt_psfpt_finish(fpt_context* ctx, const fpt_rendering_context_view* view);
 int fpt_psfpt_download_cells(fpt_context* ctx, uint64_t* h_keys, uint64_t* h_counts, int64_t* h_sums, uint32_t max_cells, uint32_t* n_cells);
 
