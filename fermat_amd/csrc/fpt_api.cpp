@@ -33,6 +33,7 @@ void pt_init_check(const fpt_pt_options* opts, const fpt_rendering_context_view*
 }
 void pt_init_apply(fpt_context* ctx, const fpt_pt_options* opts, const fpt_rendering_context_view* view, const char* h_samples_dir, const uint32_t* d_pixels, uint32_t n_local_pixels)
 {
+	ctx->deferred.off(); ctx->lanes.reset();          // an init leaves no deferral and one lane (DeferredRun, part 1; RenderLanes, part 3)
 	ctx->opt = *opts;
 	ctx->n_local = d_pixels ? n_local_pixels : view->res_x * view->res_y;
 	ctx->d_pixels = d_pixels;
@@ -44,7 +45,6 @@ void pt_init_apply(fpt_context* ctx, const fpt_pt_options* opts, const fpt_rende
 	ctx->d_shifts.upload(ctx->h_shifts.data(), ctx->h_shifts.size(), ctx->stream);
 	ctx->d_samples.alloc(ctx->h_shifts.size());
 	if (ctx->emitters.valid && ctx->emitters.n_vpls == 0) ctx->opt.nee_type = 0;     // :165-166
-	ctx->defer_max = 1;
 	ctx->pt_ready = true;
 }
 }
@@ -74,11 +74,11 @@ int fpt_create(int device_id, fpt_context** out_ctx)
 		c->n_cus = uint32_t(prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256);
 		c->blocks_per_cu = trace_blocks_per_cu();
 		FPT_HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-		c->d_counters.alloc(CNT_TOTAL);
+		c->lanes.adopt(c->stream);
 		c->d_trace_stats.alloc(8);
 		FPT_HIP_CHECK(hipMemsetAsync(c->d_trace_stats.ptr, 0, 8 * sizeof(unsigned long long), c->stream));
-		FPT_HIP_CHECK(hipMemsetAsync(c->d_counters.ptr, 0, CNT_TOTAL * sizeof(uint32_t), c->stream));
-		FPT_HIP_CHECK(hipEventCreate(&c->ev[0])); FPT_HIP_CHECK(hipEventCreate(&c->ev[1]));
+		FPT_HIP_CHECK(hipMemsetAsync(c->lanes.counters0().ptr, 0, CNT_TOTAL * sizeof(uint32_t), c->stream));
+		c->timer.create();
 		FPT_HIP_CHECK(hipStreamSynchronize(c->stream));
 		*out_ctx = c;
 		return 0;
@@ -91,15 +91,10 @@ void fpt_destroy(fpt_context* ctx)
 	if (!ctx) return;
 	(void)hipSetDevice(ctx->device);
 	(void)guarded(ctx, [&] { flush_deferred(ctx); });          // render(instance) calls the library still holds back: the caller believes them rendered
-	if (ctx->stream) { (void)hipStreamSynchronize(ctx->stream); }
+	(void)guarded(ctx, [&] { ctx->lanes.sync_all(); });
 	if (ctx->comm) (void)fpt_comm_destroy(ctx);
-	for (auto& X : ctx->extra_lanes) { if (X->stream) { (void)hipStreamSynchronize(X->stream); (void)hipStreamDestroy(X->stream); } if (X->done) (void)hipEventDestroy(X->done); }
-	if (ctx->lane_start) (void)hipEventDestroy(ctx->lane_start);
-	if (ctx->ev_ref) (void)hipEventDestroy(ctx->ev_ref);
-	for (int i = 0; i < 2; ++i) if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
-	for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
 	hipStream_t s = ctx->stream;
-	delete ctx;
+	delete ctx;          // the lanes and the timer destroy their own streams and events
 	if (s) (void)hipStreamDestroy(s);
 }
 
@@ -193,7 +188,7 @@ static void rt_launch(fpt_context* ctx, uint32_t count, const fpt_ray* d_rays, f
 {
 	require(ctx->tree.valid, "fpt_rt_trace*: create_geometry has not been called");
 	if (count == 0) return;
-	PassCounters cnt{ ctx->d_counters.ptr };
+	PassCounters cnt{ ctx->lanes.counters0().ptr };
 	TraceParams p = trace_params(ctx, cnt);
 	p.rays = reinterpret_cast<const float4*>(d_rays);
 	p.hits = reinterpret_cast<float4*>(d_hits);
@@ -239,7 +234,7 @@ int fpt_debug_trace_tickets(fpt_context* ctx, uint32_t h_out[8])
 	return guarded(ctx, [&] {
 		require(h_out != nullptr, "fpt_debug_trace_tickets: null output");
 		uint32_t area[TICKET_STRIDE];
-		ctx->d_counters.download(area, TICKET_STRIDE, ctx->stream);
+		ctx->lanes.counters0().download(area, TICKET_STRIDE, ctx->stream);
 		for (uint32_t k = 0; k < 8; ++k) h_out[k] = area[CNT_TICKETS + k * (TICKET_STRIDE / 8)];
 	});
 }
@@ -569,13 +564,6 @@ int fpt_filter_xbl(fpt_context* ctx, const fpt_rendering_context_view* view, uin
 	});
 }
 
-// what one render lane works with: its stream, counters and resolve blocks (lane 0 = the context's), and its range [first, first + n) of the rank's
-// pixel list (`pixels` = that range of the list, NULL = the identity when one lane renders everything)
-struct LaneRefs
-{
-	hipStream_t s; uint32_t* cnt; DeviceArray<FusedResolve>* d_fused; std::vector<FusedResolve>* h_fused;
-	uint32_t first, n; const uint32_t* pixels;
-};
 static PathQueue offset_queue(PathQueue q, size_t o) { q.rays += 2 * o; q.hits += o; q.weights += o; if (q.cones) q.cones += o; if (q.vinfo) q.vinfo += o; return q; }
 static ShadowQueue offset_queue(ShadowQueue q, size_t o) { q.rays += 2 * o; q.w_d += o; q.w_g += o; if (q.vinfo) q.vinfo += o; return q; }
 
@@ -631,8 +619,7 @@ static ContribLog log_from(ContribLog g, uint32_t first)
 void resize_wavefront(fpt_context* ctx, uint32_t passes, const fpt_rendering_context_view* view, bool for_psfpt)
 {
 	ctx->store.resize(WavefrontStore::Shape{ ctx->n_local, passes, ctx->opt.max_path_length, view->dir_lights_count != 0, for_psfpt }, ctx->stream);
-	ctx->h_fused.clear(); ctx->psf.h_resolve.clear(); ctx->psf.forget_pass();
-	for (auto& X : ctx->extra_lanes) X->h_fused.clear();
+	ctx->lanes.forget_blocks(); ctx->psf.h_resolve.clear(); ctx->psf.forget_pass();
 }
 // the lane's view of the context's log
 ContribLog lane_log(fpt_context* ctx, uint32_t first)
@@ -652,208 +639,181 @@ void sample_targets(fpt_context* ctx, const FrameBufferDev& real_fb, bool batche
 } // namespace fpt
 extern "C" {
 
-// one wavefront of `n_passes` passes (instances instance .. instance + n_passes - 1) over one lane's pixels.  `batched`: samples go to the per-pass
-// accumulation planes (plane k = pass instance + k; a lane owns columns first .. first + n - 1 of every plane); the caller merges.
-static void render_lane(fpt_context* ctx, const LaneRefs& L, uint32_t instance, uint32_t n_passes, bool batched, const fpt_rendering_context_view* view)
+// fpt_pt_set_capture: the path queue that enters `bounce`, read back as the reference's PTRayQueue entries
+static void read_back_capture(fpt_context* ctx, const PathQueue& qin, uint32_t bounce, hipStream_t s)
 {
+	uint32_t n = 0;
+	FPT_HIP_CHECK(hipMemcpyAsync(&n, qin.size, sizeof(uint32_t), hipMemcpyDeviceToHost, s)); FPT_HIP_CHECK(hipStreamSynchronize(s));
+	ctx->captured_count = n;
+	ctx->cap_rays.resize(n); ctx->cap_hits.resize(n); ctx->cap_weights.resize(size_t(n) * 4); ctx->cap_pixels.resize(n); ctx->cap_cones.resize(size_t(n) * 2);
+	if (!n) return;
+	FPT_HIP_CHECK(hipMemcpy(ctx->cap_rays.data(), qin.rays, size_t(n) * 32, hipMemcpyDeviceToHost));
+	FPT_HIP_CHECK(hipMemcpy(ctx->cap_hits.data(), qin.hits, size_t(n) * 16, hipMemcpyDeviceToHost));
+	FPT_HIP_CHECK(hipMemcpy(ctx->cap_weights.data(), qin.weights, size_t(n) * 16, hipMemcpyDeviceToHost));
+	// the queue's rays carry PixelInfo / the pass offset where a Ray has tmin / tmax (fpt_device.h PathQueue): hand out the reference's PTRayQueue entry
+	for (uint32_t e = 0; e < n; ++e)
 	{
-		hipStream_t s = L.s;
-		const fpt_pt_options& opt = ctx->opt;
-		const FrameBufferDev real_fb = fb_dev(view->fb);
-		PassInfo pass; pass.base_instance = instance; pass.n_passes = n_passes; pass.n_slot = L.n; pass.acc_stride = ctx->n_local; pass.pixels = L.pixels;
-		FrameBufferDev fb; ContribLog log;
-		sample_targets(ctx, real_fb, batched, L.first, fb, log);
-		const uint32_t n_paths = L.n * n_passes;
-		const size_t q_off = size_t(L.first) * ctx->store.shape.passes;          // the lane's share of the queue arrays
-		// persistent traversal grid: no more blocks than the lane's queues can feed (closest-hit + shadow rays <= 2 per path)
-		const uint32_t trace_grid = std::min(ctx->trace_blocks(), std::max(1u, uint32_t((2ull * n_paths + 255ull) / 256ull)));
-		const bool sync_mode = ctx->profiling || ctx->capture_bounce >= 0;
-		float t_ms[5] = { 0, 0, 0, 0, 0 };
+		ctx->cap_pixels[e] = ctx->cap_rays[e].mask_or_tmin;
+		const float tmin = bounce ? QUEUE_SCATTER_TMIN : QUEUE_PRIMARY_TMIN;
+		std::memcpy(&ctx->cap_rays[e].mask_or_tmin, &tmin, 4);
+		ctx->cap_rays[e].tmax = bounce ? QUEUE_SCATTER_TMAX : QUEUE_PRIMARY_TMAX;
+	}
+	FPT_HIP_CHECK(hipMemcpy(ctx->cap_cones.data(), qin.cones, size_t(n) * 8, hipMemcpyDeviceToHost));
+}
 
-		// PathTracer::render (src/renderers/pathtracer_impl.h:197-324); rescale_frame / update_variances (or the merge of the planes) are the caller's
-		FPT_HIP_CHECK(hipMemsetAsync(L.cnt, 0, CNT_TOTAL * sizeof(uint32_t), s));
-		PassCounters cnt{ L.cnt };
+// one wavefront of pass.n_passes passes (instances pass.base_instance ...) over one lane's pixels: pass.n_slot entries from `first` of the rank's pixel list
+// (pass.pixels = that range of the list, NULL = the identity when one lane renders everything).  `batched`: samples go to the per-pass accumulation planes
+// (plane k = pass base_instance + k; a lane owns columns first .. first + n_slot - 1 of every plane); the caller merges.
+static void render_lane(fpt_context* ctx, RenderLanes::Lane& L, uint32_t first, const PassInfo& pass, bool batched, const fpt_rendering_context_view* view)
+{
+	hipStream_t s = L.stream;
+	const fpt_pt_options& opt = ctx->opt;
+	const FrameBufferDev real_fb = fb_dev(view->fb);
+	FrameBufferDev fb; ContribLog log;
+	sample_targets(ctx, real_fb, batched, first, fb, log);
+	const uint32_t n_paths = pass.n_slot * pass.n_passes, isect = ctx->tree.info.intersector;
+	const size_t q_off = size_t(first) * ctx->store.shape.passes;          // the lane's share of the queue arrays
+	// persistent traversal grid: no more blocks than the lane's queues can feed (closest-hit + shadow rays <= 2 per path)
+	const uint32_t trace_grid = std::min(ctx->trace_blocks(), std::max(1u, uint32_t((2ull * n_paths + 255ull) / 256ull)));
+	const bool sync_mode = ctx->timer.sync() || ctx->capture_bounce >= 0;
+	float t_ms[5] = { 0, 0, 0, 0, 0 };
 
-		SequenceView seq; seq.shifts = ctx->d_shifts.ptr; seq.n_dims = ctx->seq_dims; seq.tile_size = ctx->seq_tile;
-		// path queue of bounce b counts in group b; shade_b fills the path queue of group b+1 and the shadow queues of group b
-		WavefrontStore& w = ctx->store;
-		PathQueue qin = offset_queue(w.q_a.view(cnt.queue(0, CNT_PATH)), q_off), qout = offset_queue(w.q_b.view(cnt.queue(1, CNT_PATH)), q_off);
-		ShadowQueue qsd = offset_queue(w.q_shadow_dir.view(cnt.queue(0, CNT_SHADOW_DIR)), w.shape.dir ? q_off : 0), qs = offset_queue(w.q_shadow.view(cnt.queue(0, CNT_SHADOW)), q_off);
-		// The ray-cone plane (PTRayQueue's cone radius + pdf, src/pathtracer_queues.h) is carried for whoever reads it: the path-space filter's hash (fpt_psf_api.cpp)
-		// and fpt_pt_set_capture.  The plain path tracer's vertices do not, and 8 B read + 8 B written per vertex are 4 % of a bandwidth-bound kernel's traffic.
+	// PathTracer::render (src/renderers/pathtracer_impl.h:197-324); rescale_frame / update_variances (or the merge of the planes) are the caller's
+	FPT_HIP_CHECK(hipMemsetAsync(L.counters.ptr, 0, CNT_TOTAL * sizeof(uint32_t), s));
+	PassCounters cnt{ L.counters.ptr };
+
+	SequenceView seq; seq.shifts = ctx->d_shifts.ptr; seq.n_dims = ctx->seq_dims; seq.tile_size = ctx->seq_tile;
+	// path queue of bounce b counts in group b; shade_b fills the path queue of group b+1 and the shadow queues of group b
+	WavefrontStore& w = ctx->store;
+	PathQueue qin = offset_queue(w.q_a.view(cnt.queue(0, CNT_PATH)), q_off), qout = offset_queue(w.q_b.view(cnt.queue(1, CNT_PATH)), q_off);
+	ShadowQueue qsd = offset_queue(w.q_shadow_dir.view(cnt.queue(0, CNT_SHADOW_DIR)), w.shape.dir ? q_off : 0), qs = offset_queue(w.q_shadow.view(cnt.queue(0, CNT_SHADOW)), q_off);
+	// The ray-cone plane (PTRayQueue's cone radius + pdf, src/pathtracer_queues.h) is carried for whoever reads it: the path-space filter's hash (fpt_psf_api.cpp)
+	// and fpt_pt_set_capture.  The plain path tracer's vertices do not, and 8 B read + 8 B written per vertex are 4 % of a bandwidth-bound kernel's traffic.
 #ifndef FPT_KEEP_CONES
-		if (ctx->capture_bounce < 0) qin.cones = qout.cones = nullptr;
+	if (ctx->capture_bounce < 0) qin.cones = qout.cones = nullptr;
 #endif
 
-		launch_primary_rays(primary_params(view, seq, L.pixels, L.n, pass, qin), s);
+	launch_primary_rays(primary_params(view, seq, pass.pixels, pass.n_slot, pass, qin), s);
 
-		ShadeParams sh; std::memset(&sh, 0, sizeof(sh));
-		sh.shadow_dir = qsd; sh.shadow = qs; sh.seq = seq;
-		sh.mesh = view->mesh; sh.textures = view->d_textures; sh.table = view->d_glossy_reflectance; sh.shade_records = ensure_shade_records(ctx, view, s);
-		sh.dir_lights = view->d_dir_lights; sh.n_dir_lights = view->dir_lights_count;
-		sh.emitters = emitter_view(ctx, opt.nee_type == 1);
-		sh.emitters.vpl_points = opt.nee_type == 1 ? ensure_vpl_points(ctx, view, s) : nullptr;
-		sh.fb = fb; sh.log = log; sh.gbuffer = real_fb; sh.opt = opt; sh.res_x = view->res_x; sh.res_y = view->res_y;
-		sh.pass = pass;
+	ShadeParams sh; std::memset(&sh, 0, sizeof(sh));
+	sh.shadow_dir = qsd; sh.shadow = qs; sh.seq = seq;
+	sh.mesh = view->mesh; sh.textures = view->d_textures; sh.table = view->d_glossy_reflectance; sh.shade_records = ensure_shade_records(ctx, view, s);
+	sh.dir_lights = view->d_dir_lights; sh.n_dir_lights = view->dir_lights_count;
+	sh.emitters = emitter_view(ctx, opt.nee_type == 1);
+	sh.emitters.vpl_points = opt.nee_type == 1 ? ensure_vpl_points(ctx, view, s) : nullptr;
+	sh.fb = fb; sh.log = log; sh.gbuffer = real_fb; sh.opt = opt; sh.res_x = view->res_x; sh.res_y = view->res_y;
+	sh.pass = pass;
 
-		// what a fused any-hit launch needs to retire an unoccluded sample, one block per (bounce, light kind).  The blocks hold nothing that
-		// changes from pass to pass (the first instance travels as a kernel argument), so they are uploaded only when a pointer or the batch shape changed
+	// what a fused any-hit launch needs to retire an unoccluded sample, one block per (bounce, light kind).  The blocks hold nothing that
+	// changes from pass to pass (the first instance travels as a kernel argument), so they are uploaded only when a pointer or the batch shape changed
+	std::vector<FusedResolve> blocks(2 * size_t(opt.max_path_length));
+	std::memset(blocks.data(), 0, blocks.size() * sizeof(FusedResolve));
+	PassInfo block_pass = pass; block_pass.base_instance = 0;
+	for (uint32_t b = 0; b < opt.max_path_length; ++b)
+		for (int kind = 0; kind < 2; ++kind)
 		{
-			std::vector<FusedResolve> blocks(2 * size_t(opt.max_path_length));
-			std::memset(blocks.data(), 0, blocks.size() * sizeof(FusedResolve));
-			PassInfo block_pass = pass; block_pass.base_instance = 0;
-			for (uint32_t b = 0; b < opt.max_path_length; ++b)
-				for (int kind = 0; kind < 2; ++kind)
-				{
-					const ShadowQueue& q = kind ? qs : qsd;
-					FusedResolve& f = blocks[2 * size_t(b) + kind];
-					f.w_d = q.w_d; f.w_g = q.w_g; f.fb = fb; f.pass = block_pass; f.bounce = b; f.log = log; f.kind = uint32_t(kind);
-				}
-			upload_if_changed(*L.d_fused, *L.h_fused, blocks, s);
+			const ShadowQueue& q = kind ? qs : qsd;
+			FusedResolve& f = blocks[2 * size_t(b) + kind];
+			f.w_d = q.w_d; f.w_g = q.w_g; f.fb = fb; f.pass = block_pass; f.bounce = b; f.log = log; f.kind = uint32_t(kind);
 		}
-		// a traversal launch that retires the shadow rays of `q` (bounce `bounce`) through their fused resolve block
-		auto shadow_params = [&](const ShadowQueue& q, uint32_t bounce) {
-			TraceParams p = trace_params(ctx, cnt);
-			p.shadow_rays = q.rays; p.shadow_size = q.size; p.fused = L.d_fused->ptr + 2 * size_t(bounce) + (q.w_d == qs.w_d ? 1 : 0); p.base_instance = instance;
-			return p;
-		};
+	upload_if_changed(L.d_fused, L.h_fused, blocks, s);
+	// a traversal launch that retires the shadow rays of `q` (bounce `bounce`) through their fused resolve block
+	auto shadow_params = [&](const ShadowQueue& q, uint32_t bounce) {
+		TraceParams p = trace_params(ctx, cnt);
+		p.shadow_rays = q.rays; p.shadow_size = q.size; p.fused = L.d_fused.ptr + 2 * size_t(bounce) + (q.w_d == qs.w_d ? 1 : 0); p.base_instance = pass.base_instance;
+		return p;
+	};
+	// ... and the launch itself, into the log when passes are in flight, into the frame otherwise; `mixed`: together with the closest-hit trace of p.rays
+	auto trace_shadows = [&](int bucket, const TraceParams& p, bool mixed) {
+		timed_launch(ctx, bucket, s, [&] {
+			if (mixed) { if (batched) launch_trace_mixed_log(p, isect, ctx->counting, trace_grid, s); else launch_trace_mixed(p, isect, ctx->counting, trace_grid, s); }
+			else       { if (batched) launch_trace_shadow_log(p, isect, ctx->counting, trace_grid, s); else launch_trace_shadow(p, isect, true, ctx->counting, trace_grid, s); }
+		}, t_ms);
+	};
 
-		fpt_pt_stats& st = ctx->stats;
-		if (sync_mode) { std::memset(&st, 0, sizeof(st)); }
-		ctx->captured_count = 0;
+	fpt_pt_stats& st = ctx->stats;
+	if (sync_mode) { std::memset(&st, 0, sizeof(st)); }
+	ctx->captured_count = 0;
 
-		// closest-hit trace of the primary rays (RTContext::trace); later bounces are traced by the MIXED launch at the end of
-		// the previous iteration, together with that bounce's shadow rays
+	// closest-hit trace of the primary rays (RTContext::trace); later bounces are traced by the MIXED launch at the end of
+	// the previous iteration, together with that bounce's shadow rays
+	TraceParams tp = trace_params(ctx, cnt);
+	tp.rays = qin.rays; tp.hits = qin.hits; tp.count_ptr = qin.size;
+	timed_launch(ctx, 0, s, [&] { launch_trace_closest_queue(tp, isect, true, ctx->counting, trace_grid, s); }, t_ms);
+	for (uint32_t bounce = 0; bounce < opt.max_path_length; ++bounce)
+	{
+		sh.bounce = bounce;
+		per_bounce_options(sh, opt, ctx->emitters.n_vpls);
+
+		if (sync_mode)
 		{
-			TraceParams tp = trace_params(ctx, cnt);
-			tp.rays = qin.rays; tp.hits = qin.hits; tp.count_ptr = qin.size;
-			timed_launch(ctx, 0, s, [&] { launch_trace_closest_queue(tp, ctx->tree.info.intersector, true, ctx->counting, trace_grid, s); }, t_ms);
+			uint32_t in_size = 0;
+			FPT_HIP_CHECK(hipMemcpyAsync(&in_size, qin.size, sizeof(uint32_t), hipMemcpyDeviceToHost, s)); FPT_HIP_CHECK(hipStreamSynchronize(s));
+			st.in_size[bounce] = in_size; st.n_bounces = bounce + 1; st.shade_events += in_size; st.rays_traced += in_size;
+			if (in_size == 0) { st.n_bounces = bounce; break; }
 		}
-		for (uint32_t bounce = 0; bounce < opt.max_path_length; ++bounce)
-		{
-			sh.bounce = bounce;
-			per_bounce_options(sh, opt, ctx->emitters.n_vpls);
+		if (ctx->capture_bounce == int(bounce)) read_back_capture(ctx, qin, bounce, s);
+		// this bounce's output counters are fresh words zeroed by the per-pass memset
+		qout.size = cnt.queue(bounce + 1, CNT_PATH); qsd.size = cnt.queue(bounce, CNT_SHADOW_DIR); qs.size = cnt.queue(bounce, CNT_SHADOW);
+		sh.in = qin; sh.scatter = qout; sh.shadow_dir = qsd; sh.shadow = qs;
+		timed_launch(ctx, 3, s, [&] { launch_shade(sh, n_paths, s); }, t_ms);
 
-			if (sync_mode)
-			{
-				uint32_t in_size = 0;
-				FPT_HIP_CHECK(hipMemcpyAsync(&in_size, qin.size, sizeof(uint32_t), hipMemcpyDeviceToHost, s)); FPT_HIP_CHECK(hipStreamSynchronize(s));
-				st.in_size[bounce] = in_size; st.n_bounces = bounce + 1; st.shade_events += in_size; st.rays_traced += in_size;
-				if (in_size == 0) { st.n_bounces = bounce; break; }
-			}
-			if (ctx->capture_bounce == int(bounce))
-			{
-				uint32_t n = 0;
-				FPT_HIP_CHECK(hipMemcpyAsync(&n, qin.size, sizeof(uint32_t), hipMemcpyDeviceToHost, s)); FPT_HIP_CHECK(hipStreamSynchronize(s));
-				ctx->captured_count = n;
-				ctx->cap_rays.resize(n); ctx->cap_hits.resize(n); ctx->cap_weights.resize(size_t(n) * 4); ctx->cap_pixels.resize(n); ctx->cap_cones.resize(size_t(n) * 2);
-				if (n)
-				{
-					FPT_HIP_CHECK(hipMemcpy(ctx->cap_rays.data(), qin.rays, size_t(n) * 32, hipMemcpyDeviceToHost));
-					FPT_HIP_CHECK(hipMemcpy(ctx->cap_hits.data(), qin.hits, size_t(n) * 16, hipMemcpyDeviceToHost));
-					FPT_HIP_CHECK(hipMemcpy(ctx->cap_weights.data(), qin.weights, size_t(n) * 16, hipMemcpyDeviceToHost));
-					// the queue's rays carry PixelInfo / the pass offset where a Ray has tmin / tmax (fpt_device.h PathQueue): hand out the reference's PTRayQueue entry
-					for (uint32_t e = 0; e < n; ++e)
-					{
-						ctx->cap_pixels[e] = ctx->cap_rays[e].mask_or_tmin;
-						const float tmin = bounce ? QUEUE_SCATTER_TMIN : QUEUE_PRIMARY_TMIN;
-						std::memcpy(&ctx->cap_rays[e].mask_or_tmin, &tmin, 4);
-						ctx->cap_rays[e].tmax = bounce ? QUEUE_SCATTER_TMAX : QUEUE_PRIMARY_TMAX;
-					}
-					FPT_HIP_CHECK(hipMemcpy(ctx->cap_cones.data(), qin.cones, size_t(n) * 8, hipMemcpyDeviceToHost));
-				}
-			}
-			// this bounce's output counters are fresh words zeroed by the per-pass memset
-			qout.size = cnt.queue(bounce + 1, CNT_PATH); qsd.size = cnt.queue(bounce, CNT_SHADOW_DIR); qs.size = cnt.queue(bounce, CNT_SHADOW);
-			sh.in = qin; sh.scatter = qout; sh.shadow_dir = qsd; sh.shadow = qs;
-			timed_launch(ctx, 3, s, [&] { launch_shade(sh, n_paths, s); }, t_ms);
-
-			// directional-light samples are resolved first (their own queue), then the mesh-light samples of the same bounce
-			if (view->dir_lights_count)
-			{
-				const TraceParams sp = shadow_params(qsd, bounce);
-				timed_launch(ctx, 2, s, [&] { if (batched) launch_trace_shadow_log(sp, ctx->tree.info.intersector, ctx->counting, trace_grid, s); else launch_trace_shadow(sp, ctx->tree.info.intersector, true, ctx->counting, trace_grid, s); }, t_ms);
-			}
-			if (bounce + 1 < opt.max_path_length)
-			{
-				// ONE launch: closest-hit trace of the scattered rays (= bounce+1's RTContext::trace) + any-hit trace of this bounce's
-				// shadow rays fused with solve_occlusion (RTContext::trace_shadow + solve_occlusion)
-				TraceParams mp = shadow_params(qs, bounce);
-				mp.rays = qout.rays; mp.hits = qout.hits; mp.count_ptr = qout.size;
-				timed_launch(ctx, 1, s, [&] { if (batched) launch_trace_mixed_log(mp, ctx->tree.info.intersector, ctx->counting, trace_grid, s); else launch_trace_mixed(mp, ctx->tree.info.intersector, ctx->counting, trace_grid, s); }, t_ms);
-			}
-			else if (sh.do_nee)
-			{
-				const TraceParams sp = shadow_params(qs, bounce);
-				timed_launch(ctx, 2, s, [&] { if (batched) launch_trace_shadow_log(sp, ctx->tree.info.intersector, ctx->counting, trace_grid, s); else launch_trace_shadow(sp, ctx->tree.info.intersector, true, ctx->counting, trace_grid, s); }, t_ms);
-			}
-			if (sync_mode)
-			{
-				uint32_t sz[2] = { 0, 0 };
-				FPT_HIP_CHECK(hipMemcpyAsync(sz, qsd.size, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-				FPT_HIP_CHECK(hipMemcpyAsync(sz + 1, qs.size, sizeof(uint32_t), hipMemcpyDeviceToHost, s)); FPT_HIP_CHECK(hipStreamSynchronize(s));
-				st.shadow_dir_size[bounce] = sz[0]; st.shadow_size[bounce] = sz[1]; st.shadow_rays_traced += sz[0] + sz[1];
-			}
-			std::swap(qin, qout);
-		}
-		FPT_HIP_CHECK(hipGetLastError());
-		if (ctx->profiling)
+		// directional-light samples are resolved first (their own queue), then the mesh-light samples of the same bounce
+		if (view->dir_lights_count) trace_shadows(2, shadow_params(qsd, bounce), false);
+		if (bounce + 1 < opt.max_path_length)
 		{
-			st.primary_rt_ms = t_ms[0]; st.path_rt_ms = t_ms[1]; st.shadow_rt_ms = t_ms[2]; st.path_shade_ms = t_ms[3]; st.shadow_shade_ms = 0.0f;
+			// ONE launch: closest-hit trace of the scattered rays (= bounce+1's RTContext::trace) + any-hit trace of this bounce's
+			// shadow rays fused with solve_occlusion (RTContext::trace_shadow + solve_occlusion)
+			TraceParams mp = shadow_params(qs, bounce);
+			mp.rays = qout.rays; mp.hits = qout.hits; mp.count_ptr = qout.size;
+			trace_shadows(1, mp, true);
 		}
+		else if (sh.do_nee) trace_shadows(2, shadow_params(qs, bounce), false);
+		if (sync_mode)
+		{
+			uint32_t sz[2] = { 0, 0 };
+			FPT_HIP_CHECK(hipMemcpyAsync(sz, qsd.size, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+			FPT_HIP_CHECK(hipMemcpyAsync(sz + 1, qs.size, sizeof(uint32_t), hipMemcpyDeviceToHost, s)); FPT_HIP_CHECK(hipStreamSynchronize(s));
+			st.shadow_dir_size[bounce] = sz[0]; st.shadow_size[bounce] = sz[1]; st.shadow_rays_traced += sz[0] + sz[1];
+		}
+		std::swap(qin, qout);
 	}
+	FPT_HIP_CHECK(hipGetLastError());
+	if (ctx->timer.sync()) { st.primary_rt_ms = t_ms[0]; st.path_rt_ms = t_ms[1]; st.shadow_rt_ms = t_ms[2]; st.path_shade_ms = t_ms[3]; st.shadow_shade_ms = 0.0f; }
 }
 
 static void render_passes_impl(fpt_context* ctx, uint32_t instance, uint32_t n_passes, const fpt_rendering_context_view* view)
 {
+	require(ctx->pt_ready, "fpt_pt_render: fpt_pt_init has not been called");
+	require(ctx->store.serves(n_passes, false, view->dir_lights_count != 0),
+	        "fpt_pt_render_batch: n_passes exceeds the batch capacity set by fpt_pt_set_batch (or the view has directional lights and the storage was sized without them): call fpt_pt_set_batch with this view");
+	require(ctx->tree.valid, "fpt_pt_render: create_geometry has not been called");
+	require(ctx->emitters.valid, "fpt_pt_render: fpt_mesh_lights_init has not been called");
+	hipStream_t s = ctx->stream;
+	const FrameBufferDev real_fb = fb_dev(view->fb);
+	const bool batched = n_passes > 1;       // batched mode accumulates into per-pass planes and merges them in order at the end
+	// the lanes: contiguous ranges of the rank's pixel list, each with its own launch chain on its own stream
+	RenderLanes& R = ctx->lanes;
+	const RenderLanes::Split sp = RenderLanes::split(R.count(), ctx->n_local, ctx->timer.sync() || ctx->capture_bounce >= 0, ctx->d_pixels != nullptr);
+	const uint32_t* list = sp.identity ? R.identity.ptr : ctx->d_pixels;
+	if (ctx->opt.nee_type == 1) (void)ensure_vpl_points(ctx, view, s);          // on the context's stream, before the lanes branch off it
+	(void)ensure_shade_records(ctx, view, s);
+	if (sp.n > 1) FPT_HIP_CHECK(hipEventRecord(R.start, s));
+	for (uint32_t j = 0; j < sp.n; ++j)
 	{
-		require(ctx->pt_ready, "fpt_pt_render: fpt_pt_init has not been called");
-		require(ctx->store.serves(n_passes, false, view->dir_lights_count != 0),
-		        "fpt_pt_render_batch: n_passes exceeds the batch capacity set by fpt_pt_set_batch (or the view has directional lights and the storage was sized without them): call fpt_pt_set_batch with this view");
-		require(ctx->tree.valid, "fpt_pt_render: create_geometry has not been called");
-		require(ctx->emitters.valid, "fpt_pt_render: fpt_mesh_lights_init has not been called");
-		hipStream_t s = ctx->stream;
-		const FrameBufferDev real_fb = fb_dev(view->fb);
-		const bool batched = n_passes > 1;       // batched mode accumulates into per-pass planes and merges them in order at the end
-		const bool sync_mode = ctx->profiling || ctx->capture_bounce >= 0;
-		// the lanes: contiguous ranges of the rank's pixel list, each with its own launch chain on its own stream
-		uint32_t n_lanes = sync_mode ? 1u : 1u + uint32_t(ctx->extra_lanes.size());
-		while (n_lanes > 1 && ctx->n_local / n_lanes < 4096u) --n_lanes;
-		if (!ctx->d_pixels && ctx->d_identity.count != ctx->n_local) n_lanes = 1;
-		const uint32_t* list = ctx->d_pixels ? ctx->d_pixels : (n_lanes > 1 ? ctx->d_identity.ptr : nullptr);
-		if (ctx->opt.nee_type == 1) (void)ensure_vpl_points(ctx, view, s);          // on the context's stream, before the lanes branch off it
-		(void)ensure_shade_records(ctx, view, s);
-		if (n_lanes > 1) FPT_HIP_CHECK(hipEventRecord(ctx->lane_start, s));
-		for (uint32_t j = 0; j < n_lanes; ++j)
-		{
-			const uint32_t p0 = uint32_t(uint64_t(ctx->n_local) * j / n_lanes), p1 = uint32_t(uint64_t(ctx->n_local) * (j + 1) / n_lanes);
-			LaneRefs L;
-			if (j == 0) L = LaneRefs{ s, ctx->d_counters.ptr, &ctx->d_fused, &ctx->h_fused, p0, p1 - p0, list };
-			else
-			{
-				fpt_context::PtLane& X = *ctx->extra_lanes[j - 1];
-				FPT_HIP_CHECK(hipStreamWaitEvent(X.stream, ctx->lane_start, 0));      // after everything queued on the context's stream so far
-				L = LaneRefs{ X.stream, X.counters.ptr, &X.d_fused, &X.h_fused, p0, p1 - p0, list + p0 };
-			}
-			PassInfo pass; pass.base_instance = instance; pass.n_passes = n_passes; pass.n_slot = L.n; pass.acc_stride = ctx->n_local; pass.pixels = L.pixels;
-			if (!batched)
-			{
-				// RenderingContextImpl::render's bracket around the renderer (src/renderer.cu:1036-1066), per lane: every pixel sees rescale -> samples -> variances
-				launch_rescale(real_fb, L.pixels, L.n, float(instance) / float(instance + 1), L.s);
-				render_lane(ctx, L, instance, 1, false, view);
-				launch_variance(real_fb, L.pixels, L.n, instance + 1, L.s);
-			}
-			else
-			{
-				render_lane(ctx, L, instance, n_passes, true, view);
-				launch_merge_passes_exact(real_fb, ctx->store.albedo[0].ptr + p0, ctx->store.albedo[1].ptr + p0,
-				                          lane_log(ctx, p0), L.pixels, L.n, pass, L.s);
-			}
-			if (j > 0) FPT_HIP_CHECK(hipEventRecord(ctx->extra_lanes[j - 1]->done, L.s));
-		}
-		for (uint32_t j = 1; j < n_lanes; ++j) FPT_HIP_CHECK(hipStreamWaitEvent(s, ctx->extra_lanes[j - 1]->done, 0));
-		FPT_HIP_CHECK(hipGetLastError());
+		RenderLanes::Lane& L = R.lane(j);
+		const uint32_t p0 = sp.at(j);
+		if (j > 0) FPT_HIP_CHECK(hipStreamWaitEvent(L.stream, R.start, 0));      // after everything queued on the context's stream so far
+		PassInfo pass; pass.base_instance = instance; pass.n_passes = n_passes; pass.n_slot = sp.at(j + 1) - p0; pass.acc_stride = ctx->n_local; pass.pixels = list ? list + p0 : nullptr;
+		// one pass: RenderingContextImpl::render's bracket around the renderer (src/renderer.cu:1036-1066), per lane: every pixel sees rescale -> samples -> variances
+		if (!batched) launch_rescale(real_fb, pass.pixels, pass.n_slot, float(instance) / float(instance + 1), L.stream);
+		render_lane(ctx, L, p0, pass, batched, view);
+		if (!batched) launch_variance(real_fb, pass.pixels, pass.n_slot, instance + 1, L.stream);
+		else launch_merge_passes_exact(real_fb, ctx->store.albedo[0].ptr + p0, ctx->store.albedo[1].ptr + p0, lane_log(ctx, p0), pass.pixels, pass.n_slot, pass, L.stream);
+		if (j > 0) FPT_HIP_CHECK(hipEventRecord(L.done, L.stream));
 	}
+	for (uint32_t j = 1; j < sp.n; ++j) FPT_HIP_CHECK(hipStreamWaitEvent(s, R.lane(j).done, 0));
+	FPT_HIP_CHECK(hipGetLastError());
 }
 
 } // extern "C"
@@ -867,30 +827,24 @@ static void gbuffer_fill(fpt_context* ctx, const fpt_framebuffer_view& fb, size_
 void clear_gbuffer(fpt_context* ctx, const fpt_rendering_context_view* view)
 {
 	// pending passes write the gbuffer when they are rendered (the last one of a batch does): a clear that follows k of them is carried out where it falls in that sequence
-	if (ctx->defer_n == 0) { gbuffer_fill(ctx, view->fb, size_t(view->res_x) * view->res_y); return; }
-	ctx->defer_clear_at = ctx->defer_n; ctx->defer_clear_fb = view->fb; ctx->defer_clear_pixels = view->res_x * view->res_y;
+	if (!ctx->deferred.note_clear(view->fb, view->res_x * view->res_y)) gbuffer_fill(ctx, view->fb, size_t(view->res_x) * view->res_y);
 }
 void flush_deferred(fpt_context* ctx)
 {
-	if (ctx->defer_n == 0) return;
-	const uint32_t first = ctx->defer_first, n = ctx->defer_n;
-	ctx->defer_n = 0;
-	const uint32_t clear_at = ctx->defer_clear_at; ctx->defer_clear_at = 0;
-	// a recorded clear: before the batch when a later pass of the batch rewrites the gbuffer (only the last pass's hits and the last clear before it survive n sequential
-	// {clear, render} calls), after the batch when the clear was the last thing the caller did
-	if (clear_at && clear_at < n) gbuffer_fill(ctx, ctx->defer_clear_fb, ctx->defer_clear_pixels);
-	if (ctx->defer_kind == DEFER_PSFPT)    psf_render_passes(ctx, first, n, &ctx->defer_view);
-	else if (ctx->defer_kind == DEFER_BPT) bpt_render_passes(ctx, first, n, &ctx->defer_view);
-	else                                   render_passes_impl(ctx, first, n, &ctx->defer_view);
-	if (clear_at == n) gbuffer_fill(ctx, ctx->defer_clear_fb, ctx->defer_clear_pixels);
+	DeferredRun& D = ctx->deferred;
+	if (D.n == 0) return;
+	const DeferredRun::Batch b = D.take();          // DeferredRun, parts 3 and 4
+	if (b.clear_before) gbuffer_fill(ctx, D.clear_fb, D.clear_pixels);
+	if (D.kind == DEFER_PSFPT)    psf_render_passes(ctx, b.first, b.n, &D.view);
+	else if (D.kind == DEFER_BPT) bpt_render_passes(ctx, b.first, b.n, &D.view);
+	else                          render_passes_impl(ctx, b.first, b.n, &D.view);
+	if (b.clear_after) gbuffer_fill(ctx, D.clear_fb, D.clear_pixels);
 }
-void defer_pass(fpt_context* ctx, uint32_t kind, uint32_t instance, const fpt_rendering_context_view* view)
+// render(instance) of the renderer that defers() (the caller has asked): anything but the next instance of the same view renders what is pending first
+void defer_pass(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view)
 {
-	// anything but the next instance of the same renderer and view renders what is pending first
-	if (ctx->defer_n && (kind != ctx->defer_kind || instance != ctx->defer_first + ctx->defer_n || std::memcmp(view, &ctx->defer_view, sizeof(*view)) != 0)) flush_deferred(ctx);
-	if (ctx->defer_n == 0) { ctx->defer_first = instance; ctx->defer_view = *view; }
-	ctx->defer_n++;
-	if (ctx->defer_n >= ctx->defer_max) flush_deferred(ctx);
+	if (ctx->deferred.breaks_run(instance, *view)) flush_deferred(ctx);
+	if (ctx->deferred.add(instance, *view)) flush_deferred(ctx);
 }
 // sizes the store for max_passes passes in flight (the PSFPT's has its extras and a fourth kind of log cell: its blends)
 void set_batch(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_context_view* view, bool for_psfpt)
@@ -899,11 +853,11 @@ void set_batch(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_contex
 	require(ctx->pt_ready, "fpt_pt_set_batch: fpt_pt_init has not been called");
 	require(max_passes >= 1, "fpt_pt_set_batch: max_passes must be >= 1");
 	require(uint64_t(ctx->n_local) * max_passes < (1ull << 32), "fpt_pt_set_batch: passes x (pixels rendered here) must stay below 2^32 paths in flight");
-	FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-	for (auto& X : ctx->extra_lanes) FPT_HIP_CHECK(hipStreamSynchronize(X->stream));
+	ctx->lanes.sync_all();
+	// DeferredRun, part 1: what the store serves from here on -- the PT either way, the PSFPT only with its extras
+	ctx->deferred.limit(DEFER_PT, max_passes); ctx->deferred.limit(DEFER_PSFPT, for_psfpt ? max_passes : 0u);
 	resize_wavefront(ctx, max_passes, view, for_psfpt);
 	FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-	if (ctx->defer_kind != DEFER_BPT && ctx->defer_max > max_passes) ctx->defer_max = max_passes;      // a smaller batch than the deferral was sized for
 }
 } // namespace fpt
 extern "C" {
@@ -912,8 +866,8 @@ int fpt_pt_render(fpt_context* ctx, uint32_t instance, const fpt_rendering_conte
 {
 	return guarded(ctx, [&] {
 		require(view != nullptr, "fpt_pt_render: null view");
-		if (ctx->defer_kind != DEFER_PT || ctx->defer_max <= 1 || ctx->profiling || ctx->capture_bounce >= 0) { flush_deferred(ctx); render_passes_impl(ctx, instance, 1, view); return; }
-		defer_pass(ctx, DEFER_PT, instance, view);
+		if (!ctx->deferred.defers(DEFER_PT) || ctx->timer.sync() || ctx->capture_bounce >= 0) { flush_deferred(ctx); render_passes_impl(ctx, instance, 1, view); return; }
+		defer_pass(ctx, instance, view);
 	});
 }
 int fpt_pt_render_batch(fpt_context* ctx, uint32_t first_instance, uint32_t n_passes, const fpt_rendering_context_view* view)
@@ -924,7 +878,7 @@ int fpt_pt_set_deferred(fpt_context* ctx, uint32_t max_passes, const fpt_renderi
 		flush_deferred(ctx);
 		require(max_passes >= 1, "fpt_pt_set_deferred: max_passes must be >= 1");
 		if (max_passes > ctx->store.shape.passes) set_batch(ctx, max_passes, view, false);
-		ctx->defer_max = max_passes; ctx->defer_kind = DEFER_PT;
+		ctx->deferred.set(DEFER_PT, max_passes);
 	});
 }
 int fpt_pt_flush(fpt_context* ctx) { return guarded(ctx, [&] { flush_deferred(ctx); }); }
@@ -955,54 +909,27 @@ int fpt_pt_get_stats(fpt_context* ctx, fpt_pt_stats* h_out)
 { return guarded(ctx, [&] { flush_deferred(ctx); require(h_out != nullptr, "fpt_pt_get_stats: null output"); FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream)); *h_out = ctx->stats; }); }
 int fpt_pt_set_profiling(fpt_context* ctx, int level)
 {
-	return guarded(ctx, [&] { flush_deferred(ctx);
-		ctx->profiling = (level == 1);
-		ctx->profiling_level = level;
-		if (level == 2 && ctx->ev_pool.empty())
-		{
-			ctx->ev_pool.resize(16384);
-			for (hipEvent_t& e : ctx->ev_pool) FPT_HIP_CHECK(hipEventCreate(&e));
-		}
-		ctx->ev_cursor = 0; ctx->timed_launches.clear();
-		if (level == 2)
-		{
-			// the common time base of the render lanes' events
-			if (!ctx->ev_ref) FPT_HIP_CHECK(hipEventCreate(&ctx->ev_ref));
-			FPT_HIP_CHECK(hipEventRecord(ctx->ev_ref, ctx->stream));
-		}
-	});
-}
+	return guarded(ctx, [&] { flush_deferred(ctx); ctx->timer.enable(level, ctx->stream); }); }
 int fpt_pt_collect_timings(fpt_context* ctx, float* h_ms, uint32_t* h_launches)
 {
 	return guarded(ctx, [&] { flush_deferred(ctx);
-		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		for (auto& X : ctx->extra_lanes) FPT_HIP_CHECK(hipStreamSynchronize(X->stream));
-		for (int b = 0; b < 5; ++b) { h_ms[b] = 0.0f; h_launches[b] = 0; ctx->last_union_ms[b] = 0.0f; }
+		ctx->lanes.sync_all();
+		LaunchTimer& T = ctx->timer;
+		for (int b = 0; b < 5; ++b) { h_ms[b] = 0.0f; h_launches[b] = 0; }
 		std::vector<std::pair<float, float>> iv[5];
-		for (const fpt_context::TimedLaunch& t : ctx->timed_launches)
+		for (const LaunchTimer::Timed& t : T.launches)
 		{
-			float ms = 0.0f;
-			FPT_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_pool[t.e0], ctx->ev_pool[t.e1]));
+			float ms = 0.0f, t0 = 0.0f;
+			FPT_HIP_CHECK(hipEventElapsedTime(&ms, T.pool[t.e0], T.pool[t.e1]));
 			h_ms[t.bucket] += ms; h_launches[t.bucket]++;
-			if (ctx->ev_ref)
-			{
-				float t0 = 0.0f;
-				FPT_HIP_CHECK(hipEventElapsedTime(&t0, ctx->ev_ref, ctx->ev_pool[t.e0]));
-				iv[t.bucket].push_back(std::make_pair(t0, t0 + ms));
-			}
+			FPT_HIP_CHECK(hipEventElapsedTime(&t0, T.ref, T.pool[t.e0]));
+			iv[t.bucket].push_back(std::make_pair(t0, t0 + ms));
 		}
 		// per bucket, the time during which at least one of its launches was running: with several render lanes launches overlap, and
-		// the sum of their durations is no longer the time the chip spent on them
-		iv[4].clear();                                    // slot 4: all traversal launches together (buckets 0, 1, 2)
+		// the sum of their durations is no longer the time the chip spent on them.  Slot 4: all traversal launches together (buckets 0, 1, 2)
 		for (int b = 0; b < 3; ++b) iv[4].insert(iv[4].end(), iv[b].begin(), iv[b].end());
-		for (int b = 0; b < 5; ++b)
-		{
-			std::sort(iv[b].begin(), iv[b].end());
-			float end = -1.0e30f, total = 0.0f;
-			for (const auto& x : iv[b]) { if (x.first > end) { total += x.second - x.first; end = x.second; } else if (x.second > end) { total += x.second - end; end = x.second; } }
-			ctx->last_union_ms[b] = total;
-		}
-		ctx->ev_cursor = 0; ctx->timed_launches.clear();
+		for (int b = 0; b < 5; ++b) T.last_union_ms[b] = merged_length(std::move(iv[b]));
+		T.start_over();
 	});
 }
 // level-2 read-out, launch by launch (in issue order): bucket and duration of up to `cap` launches since the last collect; does not reset anything
@@ -1012,43 +939,27 @@ int fpt_pt_launch_list(fpt_context* ctx, uint32_t cap, int* h_bucket, float* h_m
 		require(cap == 0 || (h_bucket && h_ms), "fpt_pt_launch_list: null output array");
 		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 		uint32_t n = 0;
-		for (const fpt_context::TimedLaunch& t : ctx->timed_launches)
+		const LaunchTimer& T = ctx->timer;
+		for (const LaunchTimer::Timed& t : T.launches)
 		{
 			if (n >= cap) break;
 			float ms = 0.0f;
-			FPT_HIP_CHECK(hipEventSynchronize(ctx->ev_pool[t.e1]));          // a launch of an extra render lane sits on that lane's stream, not on ctx->stream
-			FPT_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_pool[t.e0], ctx->ev_pool[t.e1]));
+			FPT_HIP_CHECK(hipEventSynchronize(T.pool[t.e1]));          // a launch of an extra render lane sits on that lane's stream, not on ctx->stream
+			FPT_HIP_CHECK(hipEventElapsedTime(&ms, T.pool[t.e0], T.pool[t.e1]));
 			h_bucket[n] = t.bucket; h_ms[n] = ms; ++n;
 		}
 		if (h_count) *h_count = n;
 	});
 }
 int fpt_pt_last_union_ms(fpt_context* ctx, float* h_ms)
-{ return guarded(ctx, [&] { for (int b = 0; b < 5; ++b) h_ms[b] = ctx->last_union_ms[b]; }); }
-int fpt_pt_lane_count(fpt_context* ctx) { return ctx ? int(1 + ctx->extra_lanes.size()) : 0; }
+{ return guarded(ctx, [&] { for (int b = 0; b < 5; ++b) h_ms[b] = ctx->timer.last_union_ms[b]; }); }
+int fpt_pt_lane_count(fpt_context* ctx) { return ctx ? int(ctx->lanes.count()) : 0; }
 int fpt_pt_set_lanes(fpt_context* ctx, uint32_t n_lanes)
 {
 	return guarded(ctx, [&] { flush_deferred(ctx);
 		require(ctx->pt_ready, "fpt_pt_set_lanes: fpt_pt_init has not been called");
 		require(n_lanes >= 1 && n_lanes <= 16, "fpt_pt_set_lanes: 1..16 lanes");
-		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		for (auto& X : ctx->extra_lanes) { if (X->stream) { (void)hipStreamSynchronize(X->stream); (void)hipStreamDestroy(X->stream); } if (X->done) (void)hipEventDestroy(X->done); }
-		ctx->extra_lanes.clear();
-		if (!ctx->lane_start) FPT_HIP_CHECK(hipEventCreateWithFlags(&ctx->lane_start, hipEventDisableTiming));
-		for (uint32_t j = 1; j < n_lanes; ++j)
-		{
-			std::unique_ptr<fpt_context::PtLane> X(new fpt_context::PtLane());
-			FPT_HIP_CHECK(hipStreamCreateWithFlags(&X->stream, hipStreamNonBlocking));
-			FPT_HIP_CHECK(hipEventCreateWithFlags(&X->done, hipEventDisableTiming));
-			X->counters.alloc(CNT_TOTAL);
-			ctx->extra_lanes.push_back(std::move(X));
-		}
-		if (n_lanes > 1 && !ctx->d_pixels && ctx->d_identity.count != ctx->n_local)
-		{
-			std::vector<uint32_t> id(ctx->n_local);
-			for (uint32_t i = 0; i < ctx->n_local; ++i) id[i] = i;
-			ctx->d_identity.upload(id.data(), id.size(), ctx->stream);
-		}
+		ctx->lanes.set(n_lanes, ctx->n_local, ctx->d_pixels != nullptr);
 	});
 }
 int fpt_pt_set_counting(fpt_context* ctx, int enabled)

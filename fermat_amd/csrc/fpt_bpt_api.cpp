@@ -78,8 +78,8 @@ void bpt_init(fpt_context* ctx, const fpt_bpt_options* opts, const fpt_rendering
 		// nothing refuses from here on (BptState, part 1).  The state under a Metropolis state is replaced: that one goes first (MltState, invariant 5)
 		if (ctx->mlt.mode != fpt_context::MltState::None) ctx->mlt.reset();
 		// sampler: (L+1)*2*6 dimensions (src/renderers/bpt.cu:83-87); consumes the context's rand() stream after whatever ran before
+		ctx->deferred.limit(DEFER_BPT, 1);          // storage for one pass: fpt_bpt_set_deferred sizes it again (DeferredRun, part 1)
 		ctx->bpt.init(*opts, shape, d_pixels, ctx->stream, [&] { std::vector<float> shifts; build_shift_table(256, shape.seq_dims(), h_samples_dir, ctx->crt_rand, shifts); return shifts; });
-		if (ctx->defer_kind == DEFER_BPT) ctx->defer_max = 1;          // storage for one pass: fpt_bpt_set_deferred sizes it again
 }
 } // namespace fpt
 
@@ -341,8 +341,8 @@ int fpt_bpt_render(fpt_context* ctx, uint32_t instance, const fpt_rendering_cont
 		require(view != nullptr, "fpt_bpt_render: null view");
 		BptState& b = ctx->bpt;
 		// deferred (fpt_bpt_set_deferred) unless the caller steps in between the phases of a pass: splat sums to all-reduce, light vertices to exchange
-		if (ctx->defer_kind != DEFER_BPT || ctx->defer_max <= 1 || b.profiling || b.shared_lv || (b.deferred_splats && b.opt.light_tracing)) { flush_deferred(ctx); render_impl(ctx, instance, 1, view); return; }
-		defer_pass(ctx, DEFER_BPT, instance, view);
+		if (!ctx->deferred.defers(DEFER_BPT) || b.profiling || b.shared_lv || (b.deferred_splats && b.opt.light_tracing)) { flush_deferred(ctx); render_impl(ctx, instance, 1, view); return; }
+		defer_pass(ctx, instance, view);
 	});
 }
 /* deferred fpt_bpt_render: as fpt_pt_set_deferred (the BPT's passes in flight are bit-identical to sequential passes) */
@@ -350,7 +350,7 @@ int fpt_bpt_set_deferred(fpt_context* ctx, uint32_t max_passes)
 {
 	{ const int st = guarded(ctx, [&] { flush_deferred(ctx); require(max_passes >= 1, "fpt_bpt_set_deferred: max_passes must be >= 1"); }); if (st != 0) return st; }
 	if (max_passes > std::max(ctx->bpt.shape.passes, 1u)) { const int st = fpt_bpt_set_batch(ctx, max_passes); if (st != 0) return st; }
-	return guarded(ctx, [&] { ctx->defer_max = max_passes; ctx->defer_kind = DEFER_BPT; });
+	return guarded(ctx, [&] { ctx->deferred.set(DEFER_BPT, max_passes); });
 }
 
 /* passes in flight: instance .. instance + n_passes - 1 as ONE wavefront (storage from fpt_bpt_set_batch) */
@@ -365,9 +365,9 @@ int fpt_bpt_set_batch(fpt_context* ctx, uint32_t max_passes)
 		require(b.pending_n == 0, "fpt_bpt_set_batch: a batch is waiting for fpt_bpt_resolve_splats");
 		require(!b.light_pending, "fpt_bpt_set_batch: a batch is waiting for fpt_bpt_finish");
 		FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+		ctx->deferred.limit(DEFER_BPT, max_passes);
 		BptState::Shape shape = b.shape; shape.passes = max_passes;
 		b.resize(shape, ctx->stream);
-		if (ctx->defer_kind == DEFER_BPT && ctx->defer_max > max_passes) ctx->defer_max = max_passes;
 	});
 }
 int fpt_bpt_render_batch(fpt_context* ctx, uint32_t first_instance, uint32_t n_passes, const fpt_rendering_context_view* view)

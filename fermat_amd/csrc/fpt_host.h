@@ -504,6 +504,160 @@ struct PsfState
 	void begin_pass(uint32_t stride, uint32_t mode) { rendered = true; ref_stride = stride; ref_mode = mode; }
 	void hold_pass(uint32_t instance, uint32_t bounces) { pending = true; pending_instance = instance; pending_bounces = bounces; }
 };
+
+// Render lanes (fpt_pt_set_lanes): the rank's pixel list is cut into contiguous ranges and every range is rendered by its own chain of launches on its own HIP
+// stream, so that the drain of one lane's traversal launch (it cannot end before its longest ray) overlaps the other lanes' kernels.  A pixel belongs to one lane,
+// and everything that touches a pixel stays in that lane's stream order: frames are bit-identical for any number of lanes.  The lanes share the store's arrays
+// (disjoint ranges).  Their one owner:
+//   1. One kind of lane.  A lane is a stream, the event that marks its chain done, a counter block, the resolve blocks of its fused any-hit launches and the host
+//      copy of what the device holds of them.  Lane 0 always exists and runs on the context's stream, which it does not own (adopt(), from fpt_create, before
+//      every other allocation); it needs no `done`.  Every other lane owns its stream and event and destroys them itself.
+//   2. set(n) is all or nothing.  The new lanes (stream, event, counters, in that order, lane by lane) and the identity list are made aside and swapped in when
+//      nothing can throw any more: a throw leaves the lanes as they were and leaks nothing.  It synchronises every lane first.
+//   3. The identity list (0 .. n_local - 1, what the lanes index when the caller passed no pixel list) covers n_local whenever more than one lane is set without a
+//      caller's list.  set() builds it; reset() -- fpt_pt_init, which may change n_local -- releases it and leaves one lane, so count() always tells how many
+//      lanes a render without profiling or capture may use.
+//   4. split() is the one rule that says how many lanes run and which range each takes: pure, no state.
+//   5. Readers outside the PT's loop (rt_launch, fpt_debug_trace_tickets, the PSFPT's loop) take lane 0's counter block through counters0().
+struct RenderLanes
+{
+	struct Lane
+	{
+		hipStream_t stream = nullptr; hipEvent_t done = nullptr; bool owns_stream = false;
+		DeviceArray<uint32_t> counters;                      // ticket dispensers + queue sizes, zeroed per pass
+		DeviceArray<FusedResolve> d_fused;                   // per-(bounce, light kind) blocks read by the fused any-hit launches
+		std::vector<FusedResolve> h_fused;                   // what d_fused holds (re-uploaded only when it changes)
+		~Lane() { if (owns_stream && stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); } if (done) (void)hipEventDestroy(done); }
+		Lane() = default; Lane(const Lane&) = delete; Lane& operator=(const Lane&) = delete;
+	};
+	std::vector<std::unique_ptr<Lane>> lanes;
+	DeviceArray<uint32_t> identity;
+	hipEvent_t start = nullptr;                          // recorded on lane 0's stream before the other lanes branch off it
+	RenderLanes() { lanes.push_back(std::make_unique<Lane>()); }
+	~RenderLanes() { lanes.clear(); if (start) (void)hipEventDestroy(start); }
+	uint32_t count() const { return uint32_t(lanes.size()); }
+	Lane& lane(uint32_t j) { return *lanes[j]; }
+	DeviceArray<uint32_t>& counters0() { return lanes[0]->counters; }
+	void adopt(hipStream_t s) { lanes[0]->stream = s; lanes[0]->counters.alloc(CNT_TOTAL); }
+	void sync_all() { for (auto& X : lanes) FPT_HIP_CHECK(hipStreamSynchronize(X->stream)); }
+	void forget_blocks() { for (auto& X : lanes) X->h_fused.clear(); }          // the store they name was re-shaped
+	// part 4.  One lane in sync mode (profiling level 1, capture); fewer lanes until each has at least 4096 pixels; lane j of n takes [at(j), at(j + 1)) of the
+	// rank's pixel list, at(j) = n_local * j / n in 64 bits.  `identity`: the lanes index the identity list (more than one runs and the caller passed no list)
+	struct Split
+	{
+		uint32_t n = 1, n_local = 0; bool identity = false;
+		uint32_t at(uint32_t j) const { return uint32_t(uint64_t(n_local) * j / n); }
+	};
+	static Split split(uint32_t configured, uint32_t n_local, bool sync_mode, bool has_list)
+	{
+		Split sp; sp.n_local = n_local; sp.n = sync_mode ? 1u : configured;
+		while (sp.n > 1 && n_local / sp.n < 4096u) --sp.n;
+		sp.identity = sp.n > 1 && !has_list;
+		return sp;
+	}
+	// part 2
+	void set(uint32_t n, uint32_t n_local, bool has_list)
+	{
+		sync_all();
+		if (!start) FPT_HIP_CHECK(hipEventCreateWithFlags(&start, hipEventDisableTiming));          // kept whatever follows: it belongs to no lane
+		std::vector<std::unique_ptr<Lane>> next(1);
+		DeviceArray<uint32_t> next_identity;
+		const bool new_identity = n > 1 && !has_list && identity.count != n_local;
+		for (uint32_t j = 1; j < n; ++j)
+		{
+			next.push_back(std::make_unique<Lane>());
+			Lane& X = *next.back(); X.owns_stream = true;
+			FPT_HIP_CHECK(hipStreamCreateWithFlags(&X.stream, hipStreamNonBlocking));
+			FPT_HIP_CHECK(hipEventCreateWithFlags(&X.done, hipEventDisableTiming));
+			X.counters.alloc(CNT_TOTAL);
+		}
+		std::vector<uint32_t> id(new_identity ? n_local : 0u);
+		for (uint32_t i = 0; i < id.size(); ++i) id[i] = i;
+		if (new_identity) next_identity.upload(id.data(), id.size(), lanes[0]->stream);
+		next[0] = std::move(lanes[0]);          // nothing throws from here on
+		lanes.swap(next);
+		if (new_identity) identity.swap(next_identity);
+	}
+	void reset() { if (count() > 1) { sync_all(); lanes.resize(1); } identity.release(); }
+};
+
+// Deferred render calls (fpt_pt_set_deferred, fpt_psfpt_set_deferred, fpt_bpt_set_deferred): consecutive render(instance) calls of ONE renderer (`kind`) and one view
+// are collected and rendered as one batch -- bit-identical to rendering them one by one -- when `max` of them are pending or when anything is about to look at the
+// frame, change the set-up or synchronise (flush_deferred, fpt_api.cpp).  The run's one owner:
+//   1. The storage invariant.  A deferral of kind K with maximum M > 1 implies that K's storage (the store for the PT; the store with the PSFPT's extras and the
+//      pass tables for the PSFPT; BptState for the BPT) serves M passes.  set() is called by the three set_deferred entry points after they sized that storage; every
+//      other code that re-sizes storage says what K's storage serves from now on through limit(K, passes) -- 0: nothing -- or off(): set_batch (both the PT's and the
+//      PSFPT's kind), fpt_bpt_set_batch, pt_init_apply, bpt_init.  A deferral whose maximum falls to 1 defers nothing: render(instance) goes straight to the
+//      renderer, which checks its own storage and refuses in the call that asked.
+//   2. A run is consecutive instances [first, first + n) of `view` (compared as bytes), n < max between calls: a render that breaks_run() has the pending run
+//      rendered first, and add() says when the run is full.  The two are separate calls so that a flush which throws leaves the new pass out.
+//   3. A clear of the gbuffer among pending passes (note_clear) is carried out where it falls in the one-by-one sequence: a pass overwrites the gbuffer and a clear
+//      empties it, so of n {clear, render} calls only the last pass's hits and a clear after it survive.  take() says: before the batch when a later pass of the
+//      batch rewrites the gbuffer, after it when the clear was the last thing the caller did.
+//   4. take() empties the run BEFORE it is rendered: a batch that throws is not tried again.  limit() and off() are called with nothing pending (their callers flush first).
+enum : uint32_t { DEFER_PT = 0, DEFER_PSFPT = 1, DEFER_BPT = 2 };
+struct DeferredRun
+{
+	uint32_t max = 1, kind = DEFER_PT, first = 0, n = 0;
+	fpt_rendering_context_view view{};
+	uint32_t clear_at = 0;                               // the number of pending passes the recorded clear FOLLOWS (0 = none recorded)
+	fpt_framebuffer_view clear_fb{}; uint32_t clear_pixels = 0;
+	struct Batch { uint32_t first = 0, n = 0; bool clear_before = false, clear_after = false; };
+	bool defers(uint32_t k) const { return kind == k && max > 1; }
+	bool breaks_run(uint32_t instance, const fpt_rendering_context_view& v) const { return n && (instance != first + n || std::memcmp(&v, &view, sizeof(v)) != 0); }
+	bool add(uint32_t instance, const fpt_rendering_context_view& v) { if (n == 0) { first = instance; view = v; } return ++n >= max; }          // true: the run is full
+	// false: nothing is pending, clear now
+	bool note_clear(const fpt_framebuffer_view& fb, uint32_t pixels) { if (n) { clear_at = n; clear_fb = fb; clear_pixels = pixels; } return n != 0; }
+	Batch take() { const Batch b{ first, n, clear_at && clear_at < n, clear_at && clear_at == n }; n = 0; clear_at = 0; return b; }
+	void set(uint32_t k, uint32_t m) { kind = k; max = m; }
+	void limit(uint32_t k, uint32_t passes) { if (k == kind && max > passes) max = passes ? passes : 1u; }
+	void off() { max = 1; }
+};
+
+// the merged length of [t0, t1) intervals: the time during which at least one of them was running
+inline float merged_length(std::vector<std::pair<float, float>> iv)
+{
+	std::sort(iv.begin(), iv.end());
+	float end = -1.0e30f, total = 0.0f;
+	for (const auto& x : iv) { if (x.first > end) { total += x.second - x.first; end = x.second; } else if (x.second > end) { total += x.second - end; end = x.second; } }
+	return total;
+}
+// Launch timing (fpt_pt_set_profiling) and its one owner.  Level 1: a launch whose caller passes `t_ms` (the PT's stats) is timed synchronously between the two
+// events of `sync_ev`.  Level 2: events from `pool` are recorded around the launch on its stream and read back once, after the timed region
+// (fpt_pt_collect_timings, fpt_pt_launch_list), so measuring costs no host synchronisation; `ref`, recorded when level 2 is switched on, is the common time base of
+// the lanes' events.
+//   1. enable(2) makes the pool and `ref` all or nothing: a create that throws leaves no pool and the level as it was, and the next call tries again.
+//   2. `launches` lists the launches timed since the last collect, in issue order; `cursor` is the next free event.  enable() and collect start both over.
+//   3. timed_launch (below) falls through to an untimed launch when the pool is exhausted.
+//   4. last_union_ms: per bucket, the time during which at least one launch of the bucket was running at the last collect; slot 4: buckets 0, 1 and 2 together.
+struct LaunchTimer
+{
+	enum : uint32_t { POOL = 16384 };
+	struct Timed { int bucket; uint32_t e0, e1; };
+	int level = 0;
+	hipEvent_t sync_ev[2] = { nullptr, nullptr }, ref = nullptr;
+	std::vector<hipEvent_t> pool; uint32_t cursor = 0;
+	std::vector<Timed> launches;
+	float last_union_ms[5] = { 0, 0, 0, 0, 0 };
+	bool sync() const { return level == 1; }
+	LaunchTimer() = default; LaunchTimer(const LaunchTimer&) = delete; LaunchTimer& operator=(const LaunchTimer&) = delete;
+	~LaunchTimer() { destroy(pool); for (hipEvent_t e : { sync_ev[0], sync_ev[1], ref }) if (e) (void)hipEventDestroy(e); }
+	static void destroy(std::vector<hipEvent_t>& events) { for (hipEvent_t e : events) if (e) (void)hipEventDestroy(e); events.clear(); }
+	void create() { FPT_HIP_CHECK(hipEventCreate(&sync_ev[0])); FPT_HIP_CHECK(hipEventCreate(&sync_ev[1])); }          // fpt_create
+	void start_over() { cursor = 0; launches.clear(); }
+	void enable(int lvl, hipStream_t s)
+	{
+		if (lvl == 2 && pool.empty())
+		{
+			std::vector<hipEvent_t> next(POOL + 1, nullptr);          // the pool's events, then `ref`
+			try { for (hipEvent_t& e : next) FPT_HIP_CHECK(hipEventCreate(&e)); } catch (...) { destroy(next); throw; }
+			ref = next.back(); next.pop_back();
+			pool.swap(next);
+		}
+		level = lvl; start_over();
+		if (lvl == 2) FPT_HIP_CHECK(hipEventRecord(ref, s));
+	}
+};
 } // namespace fpt
 
 struct fpt_context
@@ -515,7 +669,6 @@ struct fpt_context
 
 	// RT sub-boundary
 	fpt::AccelTree tree;                                // the acceleration structure and everything that describes it
-	fpt::DeviceArray<uint32_t> d_counters;              // ticket dispensers + queue sizes, zeroed per pass
 	fpt::DeviceArray<unsigned long long> d_trace_stats;
 
 	// sequence
@@ -538,29 +691,9 @@ struct fpt_context
 	bool pt_ready = false;
 	uint32_t n_local = 0;
 	const uint32_t* d_pixels = nullptr;
-	fpt::DeviceArray<fpt::FusedResolve> d_fused;        // per-(bounce, light kind) blocks read by the fused any-hit launches
-	std::vector<fpt::FusedResolve> h_fused;             // what d_fused holds (re-uploaded only when it changes)
 	fpt::WavefrontStore store;                           // queues, albedo planes, contribution log, reference queue: everything sized by paths in flight
-	// deferred fpt_pt_render (fpt_pt_set_deferred): consecutive render(instance) calls are collected and rendered as one batch -- bit-identical to
-	// rendering them one by one -- when defer_max of them are pending or when anything is about to look at the frame (fpt_pt_flush, fpt_synchronize, ...)
-	uint32_t defer_max = 1, defer_first = 0, defer_n = 0;
-	uint32_t defer_kind = 0;                             // whose render() is deferred: 0 the PT's (fpt_pt_set_deferred), 1 the PSFPT's (fpt_psfpt_set_deferred), 2 the BPT's (fpt_bpt_set_deferred)
-	fpt_rendering_context_view defer_view{};
-	uint32_t defer_clear_at = 0;                         // fpt_clear_gbuffer while passes are pending: the number of pending passes the clear FOLLOWS (0 = none recorded)
-	fpt_framebuffer_view defer_clear_fb{}; uint32_t defer_clear_pixels = 0;
-	// Render lanes (fpt_pt_set_lanes): the rank's pixel list is cut into n_lanes contiguous ranges and every range is rendered by its own chain of
-	// launches on its own HIP stream, so that the drain of one lane's traversal launch (it cannot end before its longest ray) overlaps the other
-	// lanes' kernels.  A pixel belongs to one lane, and everything that touches a pixel stays in that lane's stream order: frames are bit-identical
-	// for any number of lanes.  Lane 0 is the context's own stream and counters; the lanes share the queue arrays (disjoint ranges).
-	struct PtLane
-	{
-		hipStream_t stream = nullptr; hipEvent_t done = nullptr;
-		fpt::DeviceArray<uint32_t> counters;
-		fpt::DeviceArray<fpt::FusedResolve> d_fused; std::vector<fpt::FusedResolve> h_fused;
-	};
-	std::vector<std::unique_ptr<PtLane>> extra_lanes;
-	fpt::DeviceArray<uint32_t> d_identity;               // 0 .. n-1: the pixel list the lanes index when the caller passed none
-	hipEvent_t lane_start = nullptr;
+	fpt::RenderLanes lanes;                              // the PT's render lanes; lane 0 holds the counter block every renderer's single-stream launches use
+	fpt::DeferredRun deferred;                           // the render(instance) calls the library holds back
 	fpt::DeviceArray<float4> filter_tmp[2], filter_nrm; fpt::DeviceArray<float> filter_var;     // fpt_filter scratch (ping-pong images, variance)
 	fpt::DeviceArray<float4> filter_rec;                                                        // fpt_filter_xbl scratch: 3 float4 per pixel { geo, normal, colour } (layout 2 only)
 	fpt::PsfState psf;                                   // the path-space filter's state and everything that describes it (its reference queue is the store's)
@@ -641,21 +774,11 @@ struct fpt_context
 			shard_rank = 0; shard_world = 1; shard_n = 0; pending = false;
 		}
 	} mlt;
-	bool profiling = false;
 	int capture_bounce = -1;
 	uint32_t captured_count = 0;
 	std::vector<fpt_ray> cap_rays; std::vector<fpt_hit> cap_hits; std::vector<float> cap_weights; std::vector<uint32_t> cap_pixels; std::vector<float> cap_cones;
 	fpt_pt_stats stats{};
-	hipEvent_t ev[2] = { nullptr, nullptr };
-	// asynchronous per-launch timing (profiling level 2): events are recorded on the stream and read back once, after the
-	// timed region, so measuring costs no host synchronisation
-	struct TimedLaunch { int bucket; uint32_t e0, e1; };
-	hipEvent_t ev_ref = nullptr;                         // recorded when level-2 profiling is switched on: the common time base of the lanes' events
-	float last_union_ms[5] = { 0, 0, 0, 0, 0 };          // per bucket: time during which at least one launch of the bucket was running (last collect)
-	std::vector<hipEvent_t> ev_pool;
-	std::vector<TimedLaunch> timed_launches;
-	uint32_t ev_cursor = 0;
-	int profiling_level = 0;
+	fpt::LaunchTimer timer;                              // fpt_pt_set_profiling: level, events, the launches timed since the last collect
 	bool counting = false;
 
 	// multi-GPU (fpt_comm.cpp): the RCCL communicator of this rank (ncclComm_t), device copies of the ranks' pixel lists, message staging
@@ -676,10 +799,9 @@ struct fpt_context
 // renders the passes fpt_pt_render has deferred (no-op when none are pending); throws on error.  Called by every entry point that reads or writes the
 // frame, changes the renderer's set-up or synchronises
 namespace fpt {
-enum : uint32_t { DEFER_PT = 0, DEFER_PSFPT = 1, DEFER_BPT = 2 };
 void flush_deferred(fpt_context* ctx);
-// render(instance) of renderer `kind` in deferred mode: joins the pending run of consecutive instances of the same view, or starts a new one
-void defer_pass(fpt_context* ctx, uint32_t kind, uint32_t instance, const fpt_rendering_context_view* view);
+// render(instance) of the renderer whose calls ctx->deferred defers(): joins the pending run of consecutive instances of the same view, or starts a new one
+void defer_pass(fpt_context* ctx, uint32_t instance, const fpt_rendering_context_view* view);
 void psf_render_passes(fpt_context* ctx, uint32_t first, uint32_t n, const fpt_rendering_context_view* view);
 void bpt_render_passes(fpt_context* ctx, uint32_t first, uint32_t n, const fpt_rendering_context_view* view);
 }
@@ -754,22 +876,23 @@ namespace fpt { bool build_acceleration_device(fpt_context* ctx, uint32_t tri_co
 template <typename F>
 inline void timed_launch(fpt_context* ctx, int bucket, hipStream_t s, F&& launch, float* t_ms = nullptr)
 {
-	if (ctx->profiling_level == 2 && ctx->ev_cursor + 2 <= ctx->ev_pool.size())
+	fpt::LaunchTimer& T = ctx->timer;
+	if (T.level == 2 && T.cursor + 2 <= T.pool.size())
 	{
-		const uint32_t e0 = ctx->ev_cursor, e1 = ctx->ev_cursor + 1; ctx->ev_cursor += 2;
-		FPT_HIP_CHECK(hipEventRecord(ctx->ev_pool[e0], s));
+		const uint32_t e0 = T.cursor, e1 = T.cursor + 1; T.cursor += 2;
+		FPT_HIP_CHECK(hipEventRecord(T.pool[e0], s));
 		launch();
-		FPT_HIP_CHECK(hipEventRecord(ctx->ev_pool[e1], s));
-		ctx->timed_launches.push_back(fpt_context::TimedLaunch{ bucket, e0, e1 });
+		FPT_HIP_CHECK(hipEventRecord(T.pool[e1], s));
+		T.launches.push_back(fpt::LaunchTimer::Timed{ bucket, e0, e1 });
 		return;
 	}
-	const bool sync_timed = t_ms && ctx->profiling;
-	if (sync_timed) FPT_HIP_CHECK(hipEventRecord(ctx->ev[0], s));
+	const bool sync_timed = t_ms && T.sync();
+	if (sync_timed) FPT_HIP_CHECK(hipEventRecord(T.sync_ev[0], s));
 	launch();
 	if (sync_timed)
 	{
-		FPT_HIP_CHECK(hipEventRecord(ctx->ev[1], s)); FPT_HIP_CHECK(hipEventSynchronize(ctx->ev[1]));
-		float ms = 0; FPT_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1])); t_ms[bucket] += ms;
+		FPT_HIP_CHECK(hipEventRecord(T.sync_ev[1], s)); FPT_HIP_CHECK(hipEventSynchronize(T.sync_ev[1]));
+		float ms = 0; FPT_HIP_CHECK(hipEventElapsedTime(&ms, T.sync_ev[0], T.sync_ev[1])); t_ms[bucket] += ms;
 	}
 }
 

@@ -180,8 +180,8 @@ static void render_psf(fpt_context* ctx, uint32_t instance, uint32_t n_passes, c
 		sample_targets(ctx, real_fb, batched, 0, fb, log);
 		const uint32_t n = ctx->n_local * n_passes;          // paths of the launch chain
 		if (!batched) launch_rescale(fb, ctx->d_pixels, n, float(instance) / float(instance + 1), s);
-		FPT_HIP_CHECK(hipMemsetAsync(ctx->d_counters.ptr, 0, CNT_TOTAL * sizeof(uint32_t), s));
-		PassCounters cnt{ ctx->d_counters.ptr };
+		PassCounters cnt{ ctx->lanes.counters0().ptr };
+		FPT_HIP_CHECK(hipMemsetAsync(cnt.base, 0, CNT_TOTAL * sizeof(uint32_t), s));
 		auto reset_cache = [&] { ps.table.clear(s); };          // initialize the shading cache (src/renderers/psfpt_impl.h:385-387)
 		if (!batched && (instance % ps.opt.psf_temporal_reuse) == 0) reset_cache();
 		FPT_HIP_CHECK(hipMemsetAsync(ps.ref_size.ptr, 0, 32 * sizeof(uint32_t), s));
@@ -312,8 +312,8 @@ int fpt_psfpt_render(fpt_context* ctx, uint32_t instance, const fpt_rendering_co
 {
 	return guarded(ctx, [&] {
 		require(view != nullptr, "fpt_psfpt_render: null view");
-		if (ctx->defer_kind != DEFER_PSFPT || ctx->defer_max <= 1 || ctx->psf.shape.sharded) { flush_deferred(ctx); render_psf(ctx, instance, 1, view); return; }
-		defer_pass(ctx, DEFER_PSFPT, instance, view);          // fpt_psfpt_set_deferred: consecutive instances of the same view, as fpt_pt_render
+		if (!ctx->deferred.defers(DEFER_PSFPT) || ctx->psf.shape.sharded) { flush_deferred(ctx); render_psf(ctx, instance, 1, view); return; }
+		defer_pass(ctx, instance, view);          // fpt_psfpt_set_deferred: consecutive instances of the same view, as fpt_pt_render
 	});
 }
 int fpt_psfpt_render_batch(fpt_context* ctx, uint32_t first_instance, uint32_t n_passes, const fpt_rendering_context_view* view)
@@ -323,7 +323,7 @@ int fpt_psfpt_set_deferred(fpt_context* ctx, uint32_t max_passes, const fpt_rend
 {
 	{ const int st = guarded(ctx, [&] { flush_deferred(ctx); require(max_passes >= 1, "fpt_psfpt_set_deferred: max_passes must be >= 1"); }); if (st != 0) return st; }
 	if (!ctx->store.serves(max_passes, true, view && view->dir_lights_count)) { const int st = fpt_psfpt_set_batch(ctx, max_passes, view); if (st != 0) return st; }
-	return guarded(ctx, [&] { ctx->defer_max = max_passes; ctx->defer_kind = DEFER_PSFPT; });
+	return guarded(ctx, [&] { ctx->deferred.set(DEFER_PSFPT, max_passes); });
 }
 
 // storage for `max_passes` passes in flight: the store with the PSFPT's extras, and one pass table per pass of 2^b slots, 2^b >= (pixels rendered here) x (max_path_length + 1) >= the cells a pass can create, so a pass

@@ -235,7 +235,9 @@ int fpt_pt_render(fpt_context* ctx, uint32_t instance, const fpt_rendering_conte
  * contiguous ranges; fpt_pt_render / fpt_pt_render_batch then run one launch chain per range, each on its own HIP stream, so that the drain of one
  * lane's traversal launch (a launch cannot end before its longest ray) overlaps the other lanes' kernels.  Everything that touches a pixel stays in
  * one lane's stream order, so frames are BIT-IDENTICAL for any number of lanes -- fpt_pt_render with lanes is still the reference's exact
- * arithmetic.  The call returns with the context's stream waiting (asynchronously) for every lane: callers keep ordering their own work on fpt_stream(). */
+ * arithmetic.  The call returns with the context's stream waiting (asynchronously) for every lane: callers keep ordering their own work on fpt_stream().
+ * fpt_pt_init (and fpt_psfpt_init) leaves ONE lane, as it leaves no deferral: call fpt_pt_set_lanes after every init.  The call is all or nothing: a failure
+ * leaves the lanes as they were. */
 int fpt_pt_set_lanes(fpt_context* ctx, uint32_t n_lanes /* 1..16; 1 = off */);
 int fpt_pt_set_batch(fpt_context* ctx, uint32_t max_passes, const fpt_rendering_context_view* view);
 /* What passes in flight cost, so that a host can size them to the device it runs on (VERDICT r3 weak #9 / ADVICE r3): free and total bytes of the context's
