@@ -218,7 +218,7 @@ ENTRY_POINTS = ["fpt_create", "fpt_destroy", "fpt_last_error", "fpt_stream", "fp
                 "fpt_mlt_set_persistence", "fpt_mlt_restart_chains", "fpt_mlt_get_persistence",
                 "fpt_mlt_set_chain_shard", "fpt_mlt_get_chain_shard", "fpt_mlt_finish",
                 "fpt_xbl", "fpt_filter_xbl",
-                "fpt_debug_set_trace_blocks", "fpt_debug_trace_tickets"]
+                "fpt_debug_set_trace_blocks", "fpt_debug_trace_tickets", "fpt_debug_trace_hit_list"]
 
 # fpt_debug_device_build: the arrays of the last device build, by their `which` (name -> (which, dtype, columns)); rows: n triangles, n - 1 binary nodes or the wide nodes
 LBVH_CELL_DTYPE = np.dtype([("c", "<f4", 7), ("k", "u1", 7), ("k8", "u1"), ("leaf", "u1"), ("count", "u1"), ("spare", "u1", 2)])
@@ -233,7 +233,7 @@ def kernel_source_hash():
     import hashlib
     d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
     h = hashlib.sha256()
-    for name in ("fpt_trace.hip", "fpt_trace_kernel.inc", "fpt_trace_wt.hip", "fpt_device.h", "fpt_kernels.h", "fpt_math.h", "fpt_shading.h", "fpt_psf.h", "fpt_bvh.h", "fpt_bvh.cpp", "fpt_build.hip", "fpt_build_lbvh.hip",
+    for name in ("fpt_trace.hip", "fpt_trace_kernel.inc", "fpt_trace_wt.hip", "fpt_trace_dense.hip", "fpt_pt.hip", "fpt_device.h", "fpt_kernels.h", "fpt_math.h", "fpt_shading.h", "fpt_psf.h", "fpt_bvh.h", "fpt_bvh.cpp", "fpt_build.hip", "fpt_build_lbvh.hip",
                  "fpt_cw8_slots.h", "Makefile", "fpt_bpt.h", "fpt_bpt_device.h", "fpt_bpt.hip", "fpt_mlt.h", "fpt_mlt.hip", "fpt_mlt_host.h", "fpt_mlt_api.cpp"):
         with open(os.path.join(d, name), "rb") as f:
             h.update(name.encode()); h.update(f.read())
@@ -1046,6 +1046,26 @@ class Renderer:
         out = (C.c_uint32 * 8)()
         self._check(self.L.fpt_debug_trace_tickets(self.ctx, out))
         return np.array(list(out), np.uint32)
+
+    def debug_trace_hit_list(self, rays, capacity=None):
+        """fpt_debug_trace_hit_list: the hit-listing traversal launch of the passes in flight on `rays` (taken as a path queue's scattered rays: interval (1e-3, 1e8)).
+        Returns dict(list=HIT_DTYPE[capacity], src=uint32[capacity], cursor, waves, chunk); entries at and beyond `cursor` are as this call initialised them
+        (t = 0, triId = 0, src = 0xFFFFFFFF), so a store past the list's end shows.  capacity None = the smallest the library accepts, count + waves x chunk."""
+        torch = self.torch
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        cursor, waves, chunk = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        if capacity is None:          # the query form of the call: no arrays, capacity 0 -> waves and chunk of a launch of this many rays, nothing launched
+            self._check(self.L.fpt_debug_trace_hit_list(self.ctx, C.c_uint32(len(rays)), None, None, None, C.c_uint32(0), C.byref(cursor), C.byref(waves), C.byref(chunk)))
+            capacity = len(rays) + waves.value * chunk.value
+        d_r = torch.from_numpy(rays.view(np.float32).reshape(-1).copy()).to(self.dev) if len(rays) else torch.zeros(8, dtype=torch.float32, device=self.dev)
+        d_l = torch.zeros(max(capacity, 1) * 4, dtype=torch.float32, device=self.dev)
+        d_s = torch.full((max(capacity, 1),), -1, dtype=torch.int32, device=self.dev)
+        torch.cuda.synchronize(self.dev)
+        self._check(self.L.fpt_debug_trace_hit_list(self.ctx, C.c_uint32(len(rays)), C.c_void_p(d_r.data_ptr()), C.c_void_p(d_l.data_ptr()), C.c_void_p(d_s.data_ptr()),
+                                                    C.c_uint32(capacity), C.byref(cursor), C.byref(waves), C.byref(chunk)))
+        self.synchronize()
+        return dict(list=d_l.cpu().numpy().view(HIT_DTYPE).reshape(-1)[:capacity], src=d_s.cpu().numpy().view(np.uint32)[:capacity],
+                    cursor=int(cursor.value), waves=int(waves.value), chunk=int(chunk.value))
 
     def sequence(self, instance=None):
         if instance is not None:

@@ -238,6 +238,33 @@ int fpt_debug_trace_tickets(fpt_context* ctx, uint32_t h_out[8])
 		for (uint32_t k = 0; k < 8; ++k) h_out[k] = area[CNT_TICKETS + k * (TICKET_STRIDE / 8)];
 	});
 }
+// test probe of the hit list (tests/test_hit_list.py): launch_trace_mixed_log_dense on the caller's rays with an empty shadow queue, on lane 0's counter block
+int fpt_debug_trace_hit_list(fpt_context* ctx, uint32_t count, const fpt_ray* d_rays, fpt_hit* d_list, uint32_t* d_src, uint32_t capacity, uint32_t* h_cursor, uint32_t* h_waves, uint32_t* h_chunk)
+{
+	return guarded(ctx, [&] { flush_deferred(ctx);
+		require(ctx->tree.valid, "fpt_debug_trace_hit_list: create_geometry has not been called");
+		const uint32_t blocks = std::max(1u, std::min(ctx->trace_blocks(), uint32_t((uint64_t(count) + 255u) / 256u)));
+		const uint32_t chunk = trace_hit_list_slack(1) / 4u;          // a block is four waves
+		if (h_waves) *h_waves = 4u * blocks;
+		if (h_chunk) *h_chunk = chunk;
+		if (d_list == nullptr && d_src == nullptr && capacity == 0) { if (h_cursor) *h_cursor = 0; return; }          // the query form: a caller sizes its arrays from waves x chunk
+		require(d_list != nullptr && d_src != nullptr && h_cursor != nullptr, "fpt_debug_trace_hit_list: null output");
+		require(uint64_t(capacity) >= uint64_t(count) + trace_hit_list_slack(blocks), "fpt_debug_trace_hit_list: capacity is below count + waves x chunk");
+		*h_cursor = 0;
+		if (count == 0) return;
+		require(d_rays != nullptr, "fpt_debug_trace_hit_list: null rays");
+		hipStream_t s = ctx->stream;
+		FPT_HIP_CHECK(hipMemsetAsync(ctx->lanes.counters0().ptr, 0, CNT_TOTAL * sizeof(uint32_t), s));
+		PassCounters cnt{ ctx->lanes.counters0().ptr };
+		TraceParams p = trace_params(ctx, cnt);
+		p.rays = reinterpret_cast<const float4*>(d_rays); p.count = count;
+		p.shadow_size = cnt.queue(0, CNT_SHADOW);          // zero: no shadow rays, so the launch reads neither p.shadow_rays nor p.fused
+		p.hits = reinterpret_cast<float4*>(d_list); p.hit_src = d_src; p.hit_cursor = cnt.queue(1, CNT_HITS); p.hit_capacity = capacity;
+		launch_trace_mixed_log_dense(p, ctx->tree.info.intersector, false, blocks, s);
+		FPT_HIP_CHECK(hipGetLastError());
+		FPT_HIP_CHECK(hipMemcpyAsync(h_cursor, p.hit_cursor, sizeof(uint32_t), hipMemcpyDeviceToHost, s)); FPT_HIP_CHECK(hipStreamSynchronize(s));
+	});
+}
 int fpt_rt_bvh_info(fpt_context* ctx, uint32_t* n_nodes, uint32_t* n_leaf_tris, uint32_t* max_depth)
 {
 	return guarded(ctx, [&] {
@@ -616,10 +643,36 @@ static ContribLog log_from(ContribLog g, uint32_t first)
 	return g;
 }
 // ctx->store.resize for this context; the held blocks of the fused resolves, which name its buffers, and a sharded PSFPT pass that waits in its reference queue are forgotten
-void resize_wavefront(fpt_context* ctx, uint32_t passes, const fpt_rendering_context_view* view, bool for_psfpt)
+// The hit list of a render lane (MODE_MIXED_LOG_DENSE) holds one entry per path of the lane + what the waves of its traversal grid can leave unused of their last
+// chunks (trace_hit_list_slack) + one shading block, past which no thread of the shading launch reads.  A lane's grid is render_lane's: no more blocks than its queues
+// can feed, 2 rays per path, and never more than the persistent grid.
+static uint32_t lane_trace_grid(const fpt_context* ctx, uint64_t n_paths, bool capped)
+{ return uint32_t(std::min<uint64_t>(capped ? ctx->trace_blocks() : ctx->trace_blocks_default(), std::max<uint64_t>(1, (2 * n_paths + 255) / 256))); }
+static size_t lane_list_slack(const fpt_context* ctx, uint64_t n_paths) { return size_t(trace_hit_list_slack(lane_trace_grid(ctx, n_paths, false))) + SHADE_BLOCK; }
+// ... and of the lanes the context is CONFIGURED for, each with `passes` passes of its pixels in flight: what render_passes_impl adds up lane by lane.  A render with
+// fewer lanes (profiling level 1 and captures run one) or fewer passes needs no more: a grid is min(persistent grid, its rays / 256), which is monotone and subadditive.
+// fpt_pt_set_lanes re-sizes the store when this changes (reshape_hit_lists)
+static size_t hit_list_slack(const fpt_context* ctx, uint32_t passes)
 {
-	ctx->store.resize(WavefrontStore::Shape{ ctx->n_local, passes, ctx->opt.max_path_length, view->dir_lights_count != 0, for_psfpt }, ctx->stream);
+	if (passes <= 1) return 0;
+	const RenderLanes::Split sp = RenderLanes::split(ctx->lanes.count(), ctx->n_local, false, ctx->d_pixels != nullptr);
+	size_t slack = 0;
+	for (uint32_t j = 0; j < sp.n; ++j) slack += lane_list_slack(ctx, uint64_t(sp.at(j + 1) - sp.at(j)) * passes);
+	return slack;
+}
+static void resize_store(fpt_context* ctx, WavefrontStore::Shape shape)
+{
+	shape.list_slack = hit_list_slack(ctx, shape.passes);
+	ctx->store.resize(shape, ctx->stream);
 	ctx->lanes.forget_blocks(); ctx->psf.h_resolve.clear(); ctx->psf.forget_pass();
+}
+void resize_wavefront(fpt_context* ctx, uint32_t passes, const fpt_rendering_context_view* view, bool for_psfpt)
+{ resize_store(ctx, WavefrontStore::Shape{ ctx->n_local, passes, ctx->opt.max_path_length, view->dir_lights_count != 0, for_psfpt }); }
+// after the number of lanes changed: the same shape with the slack of the new lanes (the arrays whose size did not change are kept, DeviceArray::alloc)
+static void reshape_hit_lists(fpt_context* ctx)
+{
+	const WavefrontStore::Shape& s = ctx->store.shape;
+	if (s.passes > 1 && hit_list_slack(ctx, s.passes) != s.list_slack) { resize_store(ctx, s); FPT_HIP_CHECK(hipStreamSynchronize(ctx->stream)); }
 }
 // the lane's view of the context's log
 ContribLog lane_log(fpt_context* ctx, uint32_t first)
@@ -664,7 +717,8 @@ static void read_back_capture(fpt_context* ctx, const PathQueue& qin, uint32_t b
 // one wavefront of pass.n_passes passes (instances pass.base_instance ...) over one lane's pixels: pass.n_slot entries from `first` of the rank's pixel list
 // (pass.pixels = that range of the list, NULL = the identity when one lane renders everything).  `batched`: samples go to the per-pass accumulation planes
 // (plane k = pass base_instance + k; a lane owns columns first .. first + n_slot - 1 of every plane); the caller merges.
-static void render_lane(fpt_context* ctx, RenderLanes::Lane& L, uint32_t first, const PassInfo& pass, bool batched, const fpt_rendering_context_view* view)
+// `list_off`: the hit-list slack of the lanes before this one (passes in flight: the lane's hit records and source indices start at its share of the queue arrays + list_off)
+static void render_lane(fpt_context* ctx, RenderLanes::Lane& L, uint32_t first, size_t list_off, const PassInfo& pass, bool batched, const fpt_rendering_context_view* view)
 {
 	hipStream_t s = L.stream;
 	const fpt_pt_options& opt = ctx->opt;
@@ -692,6 +746,20 @@ static void render_lane(fpt_context* ctx, RenderLanes::Lane& L, uint32_t first, 
 #ifndef FPT_KEEP_CONES
 	if (ctx->capture_bounce < 0) qin.cones = qout.cones = nullptr;
 #endif
+	// Passes in flight, bounces >= 1: the traversal kernel lists the HITS of the scattered rays (MODE_MIXED_LOG_DENSE) and the shading kernel runs one thread per hit, not
+	// one per ray: a miss ends the path and no thread is started for it.  The list is in the order the rays finish, which differs from run to run; the frame does not
+	// depend on it (every contribution goes to the path's own cell of the log).  A capture reads a hit record per queue entry and keeps the older launch.
+	const bool dense = batched && ctx->capture_bounce < 0;
+	const uint32_t list_capacity = dense ? uint32_t(std::min<uint64_t>(uint64_t(n_paths) + lane_list_slack(ctx, n_paths), 0xFFFFFFFFull)) : 0u;
+	uint32_t* const list_src = dense ? w.hit_src() + q_off + list_off : nullptr;
+	if (dense)
+	{
+		require(q_off + list_off + list_capacity <= w.hit_list_entries(), "fpt_pt_render_batch: the hit list's storage is smaller than this lane's share (call fpt_pt_set_batch again)");
+		require(trace_hit_list_slack(trace_grid) + SHADE_BLOCK <= list_capacity - n_paths, "fpt_pt_render_batch: the traversal grid outgrew the hit list's slack");
+		qin.hits += list_off; qout.hits += list_off;
+	}
+	const uint32_t* in_hit_src = nullptr;          // of the queue `qin` as the next shading launch reads it: NULL = a hit record per entry
+	uint32_t* in_entries = nullptr;                // ... and the list's length
 
 	launch_primary_rays(primary_params(view, seq, pass.pixels, pass.n_slot, pass, qin), s);
 
@@ -756,7 +824,11 @@ static void render_lane(fpt_context* ctx, RenderLanes::Lane& L, uint32_t first, 
 		// this bounce's output counters are fresh words zeroed by the per-pass memset
 		qout.size = cnt.queue(bounce + 1, CNT_PATH); qsd.size = cnt.queue(bounce, CNT_SHADOW_DIR); qs.size = cnt.queue(bounce, CNT_SHADOW);
 		sh.in = qin; sh.scatter = qout; sh.shadow_dir = qsd; sh.shadow = qs;
-		timed_launch(ctx, 3, s, [&] { launch_shade(sh, n_paths, s); }, t_ms);
+		sh.in_hit_src = in_hit_src;
+		if (in_hit_src) sh.in.size = in_entries;          // one thread per list entry (the hits and the waves' filler); qin.size stays the number of rays
+		// (a list is at most capacity - SHADE_BLOCK entries long, so no thread of the launch's last block indexes past the capacity)
+		timed_launch(ctx, 3, s, [&] { launch_shade(sh, in_hit_src ? list_capacity - SHADE_BLOCK : n_paths, s); }, t_ms);
+		in_hit_src = nullptr; in_entries = nullptr;
 
 		// directional-light samples are resolved first (their own queue), then the mesh-light samples of the same bounce
 		if (view->dir_lights_count) trace_shadows(2, shadow_params(qsd, bounce), false);
@@ -766,7 +838,14 @@ static void render_lane(fpt_context* ctx, RenderLanes::Lane& L, uint32_t first, 
 			// shadow rays fused with solve_occlusion (RTContext::trace_shadow + solve_occlusion)
 			TraceParams mp = shadow_params(qs, bounce);
 			mp.rays = qout.rays; mp.hits = qout.hits; mp.count_ptr = qout.size;
-			trace_shadows(1, mp, true);
+			if (dense)
+			{
+				// the list's cursor is a fresh word of the counter block, zeroed by the per-pass memset like the queue sizes
+				mp.hit_src = list_src; mp.hit_cursor = cnt.queue(bounce + 1, CNT_HITS); mp.hit_capacity = list_capacity;
+				timed_launch(ctx, 1, s, [&] { launch_trace_mixed_log_dense(mp, isect, ctx->counting, trace_grid, s); }, t_ms);
+				in_hit_src = list_src; in_entries = mp.hit_cursor;
+			}
+			else trace_shadows(1, mp, true);
 		}
 		else if (sh.do_nee) trace_shadows(2, shadow_params(qs, bounce), false);
 		if (sync_mode)
@@ -799,6 +878,7 @@ static void render_passes_impl(fpt_context* ctx, uint32_t instance, uint32_t n_p
 	if (ctx->opt.nee_type == 1) (void)ensure_vpl_points(ctx, view, s);          // on the context's stream, before the lanes branch off it
 	(void)ensure_shade_records(ctx, view, s);
 	if (sp.n > 1) FPT_HIP_CHECK(hipEventRecord(R.start, s));
+	size_t list_off = 0;          // the hit-list slack of the lanes so far
 	for (uint32_t j = 0; j < sp.n; ++j)
 	{
 		RenderLanes::Lane& L = R.lane(j);
@@ -807,7 +887,8 @@ static void render_passes_impl(fpt_context* ctx, uint32_t instance, uint32_t n_p
 		PassInfo pass; pass.base_instance = instance; pass.n_passes = n_passes; pass.n_slot = sp.at(j + 1) - p0; pass.acc_stride = ctx->n_local; pass.pixels = list ? list + p0 : nullptr;
 		// one pass: RenderingContextImpl::render's bracket around the renderer (src/renderer.cu:1036-1066), per lane: every pixel sees rescale -> samples -> variances
 		if (!batched) launch_rescale(real_fb, pass.pixels, pass.n_slot, float(instance) / float(instance + 1), L.stream);
-		render_lane(ctx, L, p0, pass, batched, view);
+		render_lane(ctx, L, p0, list_off, pass, batched, view);
+		if (batched) list_off += lane_list_slack(ctx, uint64_t(pass.n_slot) * n_passes);
 		if (!batched) launch_variance(real_fb, pass.pixels, pass.n_slot, instance + 1, L.stream);
 		else launch_merge_passes_exact(real_fb, ctx->store.albedo[0].ptr + p0, ctx->store.albedo[1].ptr + p0, lane_log(ctx, p0), pass.pixels, pass.n_slot, pass, L.stream);
 		if (j > 0) FPT_HIP_CHECK(hipEventRecord(L.done, L.stream));
@@ -960,6 +1041,7 @@ int fpt_pt_set_lanes(fpt_context* ctx, uint32_t n_lanes)
 		require(ctx->pt_ready, "fpt_pt_set_lanes: fpt_pt_init has not been called");
 		require(n_lanes >= 1 && n_lanes <= 16, "fpt_pt_set_lanes: 1..16 lanes");
 		ctx->lanes.set(n_lanes, ctx->n_local, ctx->d_pixels != nullptr);
+		reshape_hit_lists(ctx);          // the hit lists' slack is sized for the configured lanes
 	});
 }
 int fpt_pt_set_counting(fpt_context* ctx, int enabled)

@@ -216,6 +216,12 @@ struct TraceParams
 	const uint32_t* shadow_size;
 	const struct FusedResolve* fused;
 	uint32_t        base_instance; // first pass of the call: overrides fused->pass.base_instance, so that the blocks behind `fused` do not change from call to call
+	// MODE_MIXED_LOG_DENSE (fpt_trace_kernel.inc): `hits` is then the LIST of the closest-hit rays' hits, hit_src[slot] the queue index of the ray whose hit sits in
+	// hits[slot], hit_cursor the device counter the waves draw their chunks of slots from (zeroed before the launch; its final value is the list's length, filler included)
+	// and hit_capacity the number of entries both arrays hold: no store goes to a slot at or beyond it.  (At the END of the block: the older kernels' argument offsets stay.)
+	uint32_t*       hit_src;
+	uint32_t*       hit_cursor;
+	uint32_t        hit_capacity;
 };
 struct FusedResolve { const float4* w_d; const float4* w_g; FrameBufferDev fb; PassInfo pass; uint32_t bounce; ContribLog log; uint32_t kind; };      // (PixelInfo and the pass offset ride in the shadow entry: ShadowQueue)
 
@@ -268,6 +274,10 @@ void launch_trace_shadow_queue(const TraceParams& p, uint32_t intersector, bool 
 void launch_trace_mixed(const TraceParams& p, uint32_t intersector, bool counted, uint32_t n_blocks, hipStream_t stream);
 void launch_trace_mixed_log(const TraceParams& p, uint32_t intersector, bool counted, uint32_t n_blocks, hipStream_t stream);    // launch_trace_mixed / launch_trace_shadow(fused) for the path tracer's passes in flight: the shadow
 void launch_trace_shadow_log(const TraceParams& p, uint32_t intersector, bool counted, uint32_t n_blocks, hipStream_t stream);   // rays' samples are in the log already (dir.w = path index), an unoccluded one sets its bit
+// launch_trace_mixed_log whose closest-hit rays leave the list of their hits (p.hits, p.hit_src, p.hit_cursor, p.hit_capacity) instead of a record per ray.  The list needs room for
+// every hit plus trace_hit_list_slack(n_blocks) entries: what the waves of the grid can leave unused of their last chunks
+void launch_trace_mixed_log_dense(const TraceParams& p, uint32_t intersector, bool counted, uint32_t n_blocks, hipStream_t stream);
+uint32_t trace_hit_list_slack(uint32_t n_blocks);
 void launch_trace_mixed_psf(const TraceParams& p, uint32_t intersector, bool counted, uint32_t n_blocks, hipStream_t stream);   // p.fused = a ResolveParams block (fpt_kernels.h)
 void launch_trace_mixed_hits(const TraceParams& p, uint32_t intersector, float4* shadow_hits, bool counted, uint32_t n_blocks, hipStream_t stream);   // closest-hit rays -> p.hits, the any-hit rays of p.shadow_rays -> shadow_hits (written, not resolved)
 // fpt_build.hip: the device-side refit of the 8-wide tree (fpt_rt_refit_geometry); d_scan = {bits of |scene|max, error bits}, boxes = 6 floats each

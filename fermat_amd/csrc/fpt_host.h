@@ -163,17 +163,18 @@ struct ShadowStorage
 
 // The per-pass counter block (uint32 words), one layout for the three renderers and the RT boundary's launches.  [CNT_TICKETS, CNT_QUEUES): one
 // ticket area of TICKET_STRIDE words per traversal launch (8 shard dispensers, 128 B apart); then CNT_GROUPS groups of CNT_PER_BOUNCE words, one per
-// bounce, each with three queue-size slots on their own 128-byte lines: PT / PSFPT path queue, directional and mesh-light shadow queues; BPT light
-// sub-paths, eye sub-paths, connection rays.  Every queue of every bounce counts in a fresh word, so ONE memset per pass replaces the reference's two
+// bounce, each with four slots on their own 128-byte lines: PT / PSFPT path queue, directional and mesh-light shadow queues (BPT: light sub-paths, eye
+// sub-paths, connection rays), and the cursor of the hit list that replaces the hit records of the bounce's path queue (CNT_HITS: the path tracer's passes in
+// flight, fpt_trace_kernel.inc MODE_MIXED_LOG_DENSE).  Every queue of every bounce counts in a fresh word, so ONE memset per pass replaces the reference's two
 // cudaMemsets per bounce (src/pathtracer_kernels.h:348-350).  Worst cases, L = max_path_length:
 //   PT    (L <= 31): primary trace + per bounce <= 2 (directional shadow, MIXED or mesh-light shadow; none of the latter at the last bounce) <= 2L = 62
 //                    launches; path queues of bounces 0..L: L + 1 = 32 groups
 //   PSFPT (L <= 31): primary trace + per bounce <= 3 (directional shadow, MIXED or shadow + closest; the last bounce traces nothing) <= 1 + 3(L-1) = 91
 //                    launches; L + 1 = 32 groups
 //   BPT   (L <= 15): L - 1 light traces, L eye traces, the last bounce's connections, light tracing = 2L + 1 = 31 launches; bounces 0..L: L + 1 = 16 groups
-enum : uint32_t { TICKET_STRIDE = 8 * 32, CNT_MAX_LAUNCHES = 96, CNT_GROUPS = 34, CNT_PER_BOUNCE = 96,
+enum : uint32_t { TICKET_STRIDE = 8 * 32, CNT_MAX_LAUNCHES = 96, CNT_GROUPS = 34, CNT_PER_BOUNCE = 128,
                   CNT_TICKETS = 0, CNT_QUEUES = TICKET_STRIDE * CNT_MAX_LAUNCHES, CNT_TOTAL = CNT_QUEUES + CNT_PER_BOUNCE * CNT_GROUPS,
-                  CNT_PATH = 0, CNT_SHADOW_DIR = 32, CNT_SHADOW = 64 };          // the slots of a bounce group
+                  CNT_PATH = 0, CNT_SHADOW_DIR = 32, CNT_SHADOW = 64, CNT_HITS = 96 };          // the slots of a bounce group
 
 // one pass's view of a counter block: ticket areas handed out in launch order, queue-size words by (bounce, slot)
 struct PassCounters
@@ -241,6 +242,8 @@ struct WavefrontStore
 	{
 		uint32_t pixels = 0, passes = 0, max_path_length = 0;      // pixels rendered here, passes in flight, bounces a path can log
 		bool dir = false, psf = false;                           // the directional lights' queue and cells exist; the PSFPT's extras exist (cache-info words, shadow hit records, blend cells, reference queue)
+		size_t list_slack = 0;                                   // entries the hit lists of the configured render lanes together hold beyond one per path (hit_list_slack, fpt_api.cpp): 36 B each,
+		                                                         // not counted by bytes_per_path -- a constant of the persistent grid for large batches, but 8 entries per path below 262 144 paths per lane
 		size_t paths() const { return size_t(pixels) * passes; }
 		uint32_t mask_words() const { return uint32_t(((psf ? 4u : 3u) * max_path_length + 31u) / 32u); }      // one fill bit per cell: emission, two light kinds (+ the PSFPT's blend)
 	};
@@ -252,13 +255,21 @@ struct WavefrontStore
 	DeviceArray<float4> log_emissive, log_nee[2], log_blend; DeviceArray<uint32_t> log_mask;
 	DeviceArray<uint32_t> ref_pixels, ref_cache, ref_k; DeviceArray<float4> ref_wd, ref_wg;      // the PSFPT's reference queue: <= 1 entry per path and bounce 0..L
 
-	// the list: v(array, elements per path in flight, elements it keeps when that is zero).  Planes and log exist for passes IN FLIGHT only (passes > 1); a
-	// view without directional lights keeps one entry of their queue, so that the kernels' parameters hold valid pointers
+	// the list: v(array, elements per path in flight, elements it keeps when that is zero[, elements beyond those per path]).  Planes and log exist for passes IN
+	// FLIGHT only (passes > 1); a view without directional lights keeps one entry of their queue, so that the kernels' parameters hold valid pointers.
+	// The hit list of the path tracer's passes in flight (bounces >= 1; fpt_trace_kernel.inc MODE_MIXED_LOG_DENSE) adds no array and nothing per path.  Its records
+	// take the place of the path queue's hit records, one per path + the slack the traversal waves can leave unused.  Its source indices -- one uint32 per record --
+	// live in the mesh-light shadow queue's w_g plane, which that route never touches (its light samples go to the log at shade time, ShadowQueue): 16 B per path hold
+	// four indices, so the plane grows by the slack's indices alone (hit_src()).  One-pass renders use the plane as w_g again; nothing in it outlives a call.
+	// What the slack costs, and what bytes_per_path() therefore does NOT report (part 2 holds for the per-path terms only): an entry of slack is 16 B in EACH path queue's hit
+	// array + 4 B of index = 36 B, and a lane's slack is (waves of its traversal grid) x 256 + 256 entries, its grid min(persistent grid, 2 rays per path / 256) blocks of four
+	// waves.  With the persistent grid of 2048 blocks (256 CUs x 8) that is 2.1 M entries = 75.5 MB per lane whatever the batch, from 262 144 paths per lane on; below that it is
+	// 8 entries = 288 B per path, as much as +40 % on a small batch.  Sized for the lanes that are configured: fpt_pt_set_lanes re-sizes it.
 	template <typename V> void each_array(const Shape& s, V&& v)
 	{
 		const size_t L = s.max_path_length, d = s.dir, x = s.psf, g = s.passes > 1;
-		for (QueueStorage* q : { &q_a, &q_b }) { v(q->rays, 2, 0); v(q->hits, 1, 0); v(q->weights, 1, 0); v(q->cones, 1, 0); v(q->vinfo, x, 0); }
-		v(q_shadow.rays, 2, 0); v(q_shadow.w_d, 1, 0); v(q_shadow.w_g, 1, 0); v(q_shadow.vinfo, x, 0); v(q_shadow.hits, x, 0);
+		for (QueueStorage* q : { &q_a, &q_b }) { v(q->rays, 2, 0); v(q->hits, 1, 0, g * s.list_slack); v(q->weights, 1, 0); v(q->cones, 1, 0); v(q->vinfo, x, 0); }
+		v(q_shadow.rays, 2, 0); v(q_shadow.w_d, 1, 0); v(q_shadow.w_g, 1, 0, g * ((s.list_slack + 3) / 4)); v(q_shadow.vinfo, x, 0); v(q_shadow.hits, x, 0);
 		v(q_shadow_dir.rays, 2 * d, 2); v(q_shadow_dir.w_d, d, 1); v(q_shadow_dir.w_g, d, 1); v(q_shadow_dir.vinfo, x * d, x); v(q_shadow_dir.hits, x * d, x);
 		v(albedo[0], g, 0); v(albedo[1], g, 0);
 		v(log_emissive, g * L, 0); v(log_nee[0], g * d * 2 * L, 0); v(log_nee[1], g * 2 * L, 0); v(log_blend, g * x * 3 * L, 0); v(log_mask, g * s.mask_words(), 0);
@@ -267,7 +278,7 @@ struct WavefrontStore
 	void resize(const Shape& s, hipStream_t stream)
 	{
 		shape = Shape{};                                         // a throw on the way (out of memory) leaves a store that serves nobody
-		each_array(s, [&](auto& a, size_t per_path, size_t floor) { a.alloc(per_path ? per_path * s.paths() : floor); });
+		each_array(s, [&](auto& a, size_t per_path, size_t floor, size_t beyond = 0) { a.alloc(per_path ? per_path * s.paths() + beyond : floor); });
 		for (DeviceArray<float4>& a : albedo) if (a.ptr) FPT_HIP_CHECK(hipMemsetAsync(a.ptr, 0, a.count * sizeof(float4), stream));
 		if (log_mask.ptr) FPT_HIP_CHECK(hipMemsetAsync(log_mask.ptr, 0, log_mask.count * sizeof(uint32_t), stream));
 		shape = s;
@@ -275,9 +286,12 @@ struct WavefrontStore
 	uint64_t bytes_per_path(const Shape& s)
 	{
 		uint64_t b = 0;
-		each_array(s, [&](auto& a, size_t per_path, size_t) { b += per_path * sizeof(*a.ptr); });
+		each_array(s, [&](auto& a, size_t per_path, size_t, size_t = 0) { b += per_path * sizeof(*a.ptr); });
 		return b;
 	}
+	// the hit list's source indices and how many entries the list can hold (records: either path queue's hit array; indices: four per float4 of the plane)
+	uint32_t* hit_src() { return reinterpret_cast<uint32_t*>(q_shadow.w_g.ptr); }
+	size_t hit_list_entries() const { return shape.passes > 1 ? std::min(std::min(q_a.hits.count, q_b.hits.count), q_shadow.w_g.count * 4) : 0; }
 	// is a render of `passes` passes, by the PSFPT or the PT, of a view with or without directional lights covered by what the arrays are sized for?
 	bool serves(uint32_t passes, bool psf, bool dir) const { return passes >= 1 && passes <= shape.passes && (shape.psf || !psf) && (shape.dir || !dir); }
 };

@@ -72,6 +72,9 @@ struct ShadeParams
 	ContribLog log;              // plain PT, passes in flight: where the paths' frame-buffer contributions go (fpt_device.h)
 	uint32_t write_gbuffer;
 	PsfDev psf;                  // used by the PSF instantiation only
+	// The path tracer's passes in flight, bounces >= 1: in.hits is the LIST of the hits the traversal kernel left (MODE_MIXED_LOG_DENSE, fpt_trace_kernel.inc), *in.size its
+	// length, and in_hit_src[i] the entry of in.rays / in.weights whose ray made hit i.  NULL = the identity: every other route.  (Last in the block: the offsets above stay.)
+	const uint32_t* in_hit_src;
 };
 
 struct ResolveParams

@@ -290,11 +290,13 @@ void shade_kernel(const ShadeParams P)
 	__shared__ float4 park[3][SHADE_BLOCK];
 	uint32_t prev_vinfo = 0xFFFFFFFFu, vinfo = 0xFFFFFFFFu;
 	int psf_mode = 0; f3 mat_diffuse = splat3(1.0f);
-	// One thread per queue entry.  A miss ends the path (no sky lighting, src/pathtracer_core.h:1249-1252) and its lane idles through the kernel -- a third
-	// of the bounce-1 entries of the bench frame.  Shading only the hits was measured twice and dropped: listing the hits of a 2048-entry
+	// One thread per queue entry.  A miss ends the path (no sky lighting, src/pathtracer_core.h:1249-1252) and its lane idles through the kernel: a third of the
+	// bounce-1 entries of rounds 1-3's open box, but 110 of the 4 911 488 entries of bounces >= 1 on the bathroom2 stand-in, a closed room (tools/miss_share.py,
+	// EXPERIMENTS B6).  Shading only the hits by a pass of its own was measured three times and dropped: listing the hits of a 2048-entry
 	// tile in LDS at the head of every block made the kernel 30 % slower (0.504 vs 0.389 ms per step: sixteen loads and two barriers in front of a
 	// 13-us block); a separate compaction kernel + an index list broke even (0.380 vs 0.389, 0.365 vs 0.365: what the fuller waves save, the extra pass
-	// over the hit records and the gathered loads cost).
+	// over the hit records and the gathered loads cost) and loses on the bathroom2 stand-in (0.623 vs 0.591, the pass not counted).  With passes in flight the
+	// entries of bounces >= 1 ARE a list of hits, which the traversal kernel leaves as its rays retire (P.in_hit_src; fpt_trace_kernel.inc MODE_MIXED_LOG_DENSE).
 	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
 	const uint32_t n_in = *P.in.size;
 	if (blockIdx.x * blockDim.x >= n_in) return;                       // whole block beyond the queue: uniform exit
@@ -318,10 +320,12 @@ void shade_kernel(const ShadeParams P)
 
 	if (active)
 	{
-		const float4 ro = P.in.rays[2 * size_t(i)], rd4 = P.in.rays[2 * size_t(i) + 1];
-		const float4 w4 = P.in.weights[i];
+		// the entry's ray and throughput: entry i's own, or (a LIST of hits, ShadeParams::in_hit_src) those of the queue entry whose ray made hit i
+		const uint32_t src = (!PSF && P.in_hit_src) ? P.in_hit_src[i] : i;
+		const float4 ro = P.in.rays[2 * size_t(src)], rd4 = P.in.rays[2 * size_t(src) + 1];
+		const float4 w4 = P.in.weights[src];
 		pixel_info = as_u32(ro.w);                                                        // PathQueue: origin | PixelInfo, dir | pass offset
-		const float2 cone = P.in.cones ? P.in.cones[i] : make_float2(0.0f, 1.0f);      // (no cone plane: the plain path tracer, whose vertices never read it)
+		const float2 cone = P.in.cones ? P.in.cones[src] : make_float2(0.0f, 1.0f);    // (no cone plane: the plain path tracer, whose vertices never read it)
 		slot = decode_slot(P.pass, pixel_info, P.pass.n_passes > 1 ? as_u32(rd4.w) : 0u);
 		pixel = slot.pixel;
 		const uint32_t instance = P.pass.base_instance + slot.k;

@@ -29,9 +29,14 @@
 //     block per refill writes the hit records, the any-hit results and the fused resolves of all the lanes that finished since the last one: inside the burst the
 //     whole wave entered those blocks -- 200 VALU + 130 SALU instructions and, for an unoccluded shadow ray, five dependent memory waits -- whenever ONE lane
 //     finished, which is nearly every iteration (round 8: -7 % traversal time; tests/test_trace_retire_isa.py keeps the burst free of other memory traffic).
+//   * the path tracer's passes in flight, bounces >= 1 (MODE_MIXED_LOG_DENSE, instantiated in fpt_trace_dense.hip): that retire block writes no record per closest-hit ray
+//     but appends the HITS to a list -- slot = the wave's output cursor + the lane's rank among the finishing hit lanes (one ballot), chunks of 256 slots from one device
+//     counter, record to hits[slot], the ray's queue index to hit_src[slot], nothing for a miss -- and the shading kernel runs one thread per list entry.  The list is in the
+//     order the rays finish, which differs from run to run; the frame does not depend on it (a path's contributions go to its own cells of the log).  It
+//     reorders every later queue by completion, which is what it is worth on the bench scene: the next bounce's traversal -11 %, the shading kernel's gathers +0.08 ms.
 // No MFMA: a pointer chase, not a contraction.
-// The kernel's text lives in fpt_trace_kernel.inc and is instantiated twice: here with fpt-MT (trace_kernel, the default) and in fpt_trace_wt.hip with the opt-in watertight
-// intersector fpt-WT (trace_kernel_wt) for trees whose records hold the vertices.  The launch functions below take the tree's intersector and pick the kernel.
+// The kernel's text lives in fpt_trace_kernel.inc and is instantiated three times: here with fpt-MT (trace_kernel, the default), in fpt_trace_wt.hip with the opt-in watertight
+// intersector fpt-WT (trace_kernel_wt) for trees whose records hold the vertices, and in fpt_trace_dense.hip for the hit-listing mode alone, with either.  The launch functions below take the tree's intersector and pick the kernel.
 #include "fpt_device.h"
 #include "fpt_bvh.h"
 #include "fpt_psf.h"

@@ -1,5 +1,6 @@
-// fpt_trace_kernel.inc -- the traversal kernel's text, shared by the two translation units that instantiate it: fpt_trace.hip (the default intersector fpt-MT, kernel
-// trace_kernel) and fpt_trace_wt.hip (the watertight intersector fpt-WT, kernel trace_kernel_wt).  Included once per file, inside namespace fpt, after fpt_device.h,
+// fpt_trace_kernel.inc -- the traversal kernel's text, shared by the translation units that instantiate it: fpt_trace.hip (the default intersector fpt-MT, kernel
+// trace_kernel), fpt_trace_wt.hip (the watertight intersector fpt-WT, kernel trace_kernel_wt) and fpt_trace_dense.hip (MODE_MIXED_LOG_DENSE alone, with either intersector:
+// there twice, each copy in a namespace of its own).  Included once per namespace, inside namespace fpt, after fpt_device.h,
 // fpt_bvh.h and fpt_psf.h, with three macros set: FPT_TRACE_KERNEL (the kernel's name), FPT_TRACE_KERNEL_WAVES (its launch bound, waves per SIMD) and
 // FPT_TRACE_INTERSECTOR (IntersectMT or IntersectWT below).  The design notes are at the head of fpt_trace.hip.
 #if !defined(FPT_TRACE_KERNEL) || !defined(FPT_TRACE_KERNEL_WAVES) || !defined(FPT_TRACE_INTERSECTOR)
@@ -25,6 +26,12 @@
 #ifndef FPT_CHUNK_MAX
 #define FPT_CHUNK_MAX 256          // rays a wave draws per ticket: the last chunk a wave holds is the imbalance at the end of a launch.  Measured, Msample/s in the
 #endif                             // driver's form / at 64 in flight: 1024 -> 1455 / 1678, 512 -> 1495 / 1710, 256 -> 1530 / 1723, 128 -> 1532 / 1704, 64 -> 1481 / 1637
+#ifndef FPT_HIT_CHUNK
+#define FPT_HIT_CHUNK 256          // MODE_MIXED_LOG_DENSE: slots of the hit list a wave draws per atomic (a multiple of 64: a chunk is whole shading waves).  The tail a wave leaves unused
+#endif                             // is filler the shading kernel skips, waves x chunk / 2 entries per launch on average.  Measured at 64 in flight, three runs each, Msample/s (traversal / shading
+                                   // ms per step): 64 -> 662.2-664.0 (1.384-1.388 / 0.709-0.720), 128 -> 674.0-675.4 (1.369-1.373 / 0.690-0.698), 256 -> 680.1-683.3 (1.366-1.370 / 0.669-0.677):
+                                   // the larger the chunk, the longer the runs of list entries that come from one wave's tickets of consecutive rays, and the nearer the shading kernel's gathers
+static_assert(FPT_HIT_CHUNK >= 64 && FPT_HIT_CHUNK % 64 == 0, "FPT_HIT_CHUNK: one fresh chunk must take a whole retire (up to 64 hits), and a chunk is whole shading waves");
 static constexpr int TRACE_BLOCK = 256;
 static constexpr int LDS_STACK   = FPT_LDS_STACK;        // levels x 256 threads x 4 B of LDS per block
 static constexpr int OVF_STACK   = 48 - FPT_LDS_STACK;   // scratch overflow: 48 entries in all (fpt_rt_create_geometry checks the tree's stack bound against it)
@@ -33,19 +40,25 @@ static constexpr uint32_t TICKET_SHARDS = 8;             // one ticket counter p
 static constexpr uint32_t TICKET_PAD    = 32;            // counters sit 128 B apart: atomics on one cache line serialise chip-wide
 
 enum TraceMode { MODE_CLOSEST = 0, MODE_ANY = 1, MODE_ANY_FUSED = 2, MODE_MIXED = 3, MODE_MIXED_PSF = 4, MODE_MIXED_HITS = 5, MODE_CLOSEST_QP = 6, MODE_CLOSEST_QS = 7, MODE_ANY_Q = 8,
-                 MODE_MIXED_LOG = 9, MODE_ANY_LOG = 10 };
+                 MODE_MIXED_LOG = 9, MODE_ANY_LOG = 10, MODE_MIXED_LOG_DENSE = 11 };
 // *_QP / *_QS / ANY_Q (round 5): the rays of a renderer's own queues (fpt_device.h PathQueue / ShadowQueue), whose .w words carry PixelInfo and the pass offset instead of
 // tmin / tmax: primary rays (0, 1e34), scattered rays (1e-3, 1e8), shadow rays (mask, 0.9999).  MIXED, MIXED_PSF and ANY_FUSED read such queues too.
 // MIXED_LOG / ANY_LOG: MIXED / ANY_FUSED for the path tracer's passes in flight.  The shading kernel has already written the sample into its cell of the contribution log
 // (fpt_pt.hip write_shadow_entry) and the shadow ray's dir.w carries the path index pidx of that cell instead of PixelInfo: an unoccluded ray retires by setting the cell's
 // mask bit and nothing else -- no load, no cell store, no wait.  The numbers of the older modes stay: tests/test_trace_retire_isa.py names them.
-constexpr bool closest_from_queue(int m) { return m == MODE_MIXED || m == MODE_MIXED_PSF || m == MODE_MIXED_LOG || m == MODE_CLOSEST_QP || m == MODE_CLOSEST_QS; }
-constexpr bool any_from_queue(int m) { return m == MODE_ANY_FUSED || m == MODE_MIXED || m == MODE_MIXED_PSF || m == MODE_ANY_Q || m == MODE_MIXED_LOG || m == MODE_ANY_LOG; }
-constexpr bool any_to_log(int m) { return m == MODE_MIXED_LOG || m == MODE_ANY_LOG; }
+// MIXED_LOG_DENSE: MIXED_LOG whose closest-hit rays leave a LIST OF HITS instead of a record per ray (the path tracer's passes in flight, bounces >= 1: a miss ends the path,
+// and the shading kernel has nothing to do for it).  A finishing hit lane takes the next slot of the wave's output chunk -- the chunks come from ONE device counter,
+// P.hit_cursor, FPT_HIT_CHUNK slots per draw -- and writes its record to P.hits[slot] and the ray's queue index to P.hit_src[slot]; a miss writes nothing.  The order of the
+// list is the order in which rays finish and differs from run to run; the frame does not depend on it (DESIGN.md 6b).  What a wave leaves unused of its last chunk it fills
+// with miss records at its exit, so the list's length is the counter's final value.  Every store to the list is guarded by P.hit_capacity.
+constexpr bool closest_from_queue(int m) { return m == MODE_MIXED || m == MODE_MIXED_PSF || m == MODE_MIXED_LOG || m == MODE_MIXED_LOG_DENSE || m == MODE_CLOSEST_QP || m == MODE_CLOSEST_QS; }
+constexpr bool any_from_queue(int m) { return m == MODE_ANY_FUSED || m == MODE_MIXED || m == MODE_MIXED_PSF || m == MODE_ANY_Q || m == MODE_MIXED_LOG || m == MODE_MIXED_LOG_DENSE || m == MODE_ANY_LOG; }
+constexpr bool any_to_log(int m) { return m == MODE_MIXED_LOG || m == MODE_MIXED_LOG_DENSE || m == MODE_ANY_LOG; }
+constexpr bool hits_listed(int m) { return m == MODE_MIXED_LOG_DENSE; }
 constexpr bool any_only_from_shadow_queue(int m) { return m == MODE_ANY_FUSED || m == MODE_ANY_LOG; }
 // MIXED_PSF: MIXED with the path-space-filtering resolve (`fused` points to a ResolveParams); MIXED_HITS: the any-hit rays' results are WRITTEN
 // (`fused` points to their float4 Hit array) instead of resolved -- the bidirectional path tracer's connections, which its own kernel adds in order
-constexpr bool mode_is_mixed(int m) { return m == MODE_MIXED || m == MODE_MIXED_PSF || m == MODE_MIXED_HITS || m == MODE_MIXED_LOG; }
+constexpr bool mode_is_mixed(int m) { return m == MODE_MIXED || m == MODE_MIXED_PSF || m == MODE_MIXED_HITS || m == MODE_MIXED_LOG || m == MODE_MIXED_LOG_DENSE; }
 
 struct LaneRay
 {
@@ -228,6 +241,9 @@ __device__ __forceinline__ uint2 pop_entry(uint2 (*lds_stack)[256], const uint2*
 	return v;
 }
 
+// the number of set bits of a wave-uniform mask below this lane (v_mbcnt_lo / _hi: no per-lane mask in registers)
+__device__ __forceinline__ uint32_t lanes_below(unsigned long long mask) { return __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0u)); }
+
 template <int MODE, bool COUNTED>
 __global__ __launch_bounds__(TRACE_BLOCK, FPT_TRACE_KERNEL_WAVES)
 void FPT_TRACE_KERNEL(const TraceParams P)
@@ -287,6 +303,7 @@ void FPT_TRACE_KERNEL(const TraceParams P)
 	int32_t  best_id = -1;
 	bool     occluded = false;
 	unsigned long long cnt[6] = { 0, 0, 0, 0, 0, 0 };      // COUNTED: {nodes, tris, rays} for closest, then for any-hit rays
+	uint32_t o_next = 0, o_end = 0;         // wave-uniform (hits_listed): the unused slots of the wave's chunk of the hit list
 
 	for (;;)
 	{
@@ -294,6 +311,33 @@ void FPT_TRACE_KERNEL(const TraceParams P)
 		//      the tickets are dry: when the wave is empty), so this block runs once per refill with 16-64 live lanes -- inside the burst it ran for the one to three
 		//      lanes that finish in an iteration, with the whole wave waiting.  It comes before the refill, which reuses the lane's registers, and before the exit test
 		//      below, so the last rays of a wave are written too.  One writer per cell holds as before: a path has at most one sample of a kind per launch ----
+		if (hits_listed(MODE))
+		{
+			// the hit list: slot = the wave's cursor + the lane's rank among the finishing hit lanes.  A retire holds at most 64 hits and a chunk at least 64 slots, so the
+			// hits that do not fit into what is left of the chunk go to the head of ONE new chunk; cursor and chunk end stay wave-uniform (scalar registers)
+			const bool list_hit = sp < 0 && !any && best_id >= 0;
+			const unsigned long long listed = __ballot(list_hit);
+			if (listed)
+			{
+				const uint32_t n_hit = uint32_t(__popcll(listed)), left = o_end - o_next;
+				uint32_t fresh = 0;
+				if (n_hit > left)
+				{
+					if (lane == 0) fresh = atomicAdd(P.hit_cursor, uint32_t(FPT_HIT_CHUNK));
+					fresh = uint32_t(__builtin_amdgcn_readfirstlane(int(fresh)));
+				}
+				const uint32_t rank = lanes_below(listed);
+				const uint32_t slot = rank < left ? o_next + rank : fresh + (rank - left);
+				if (list_hit && slot < P.hit_capacity)
+				{
+					const float u = 1.0f - best_bu - best_bv;        // weight of vertex 0, as below
+					P.hits[slot] = make_float4(best_t, as_f32(uint32_t(best_id)), round_through_half(u), round_through_half(best_bu));
+					P.hit_src[slot] = ray_index;
+				}
+				if (n_hit > left) { o_next = fresh + (n_hit - left); o_end = fresh + uint32_t(FPT_HIT_CHUNK); }
+				else o_next += n_hit;
+			}
+		}
 		if (sp < 0)
 		{
 			if (any)
@@ -330,7 +374,7 @@ void FPT_TRACE_KERNEL(const TraceParams P)
 					if (P.bits && occluded) atomicOr(P.bits + (ray_index >> 5), 1u << (ray_index & 31u));
 				}
 			}
-			else
+			else if (!hits_listed(MODE))
 			{
 				float4 h = make_float4(-1.0f, as_f32(0xFFFFFFFFu), 0.0f, 0.0f);
 				if (best_id >= 0)
@@ -372,7 +416,9 @@ void FPT_TRACE_KERNEL(const TraceParams P)
 			if (!dry)
 			{
 				const uint32_t avail = c_end - c_next;
-				const uint32_t rank = __popcll(idle & ((1ull << lane) - 1ull));
+				// (hits_listed: by v_mbcnt, like the list's own rank.  The mask (1 << lane) - 1 is loop-invariant and the compiler keeps it in two VGPRs for the whole kernel: with the
+				//  watertight intersector those two are what stands between the listing mode and seven waves per SIMD.  The older modes keep their instructions)
+				const uint32_t rank = hits_listed(MODE) ? lanes_below(idle) : uint32_t(__popcll(idle & ((1ull << lane) - 1ull)));
 				if (!have && rank < avail)
 				{
 					const uint32_t i = c_next + rank;
@@ -495,6 +541,12 @@ void FPT_TRACE_KERNEL(const TraceParams P)
 			if (n_busy == 0) break;
 			if (!dry && (64 - n_busy) >= REFILL_MIN) break;
 		}
+	}
+	if (hits_listed(MODE))
+	{
+		// what the wave drew and did not use: today's miss record, which the shading kernel skips as it skips every miss
+		for (uint32_t slot = o_next + lane; slot < o_end; slot += 64u)
+			if (slot < P.hit_capacity) { P.hits[slot] = make_float4(-1.0f, as_f32(0xFFFFFFFFu), 0.0f, 0.0f); P.hit_src[slot] = 0u; }
 	}
 	if (COUNTED)
 	{

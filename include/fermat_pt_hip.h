@@ -163,6 +163,13 @@ int fpt_debug_set_trace_blocks(fpt_context* ctx, uint32_t n_blocks);
 /* probe (tests): the eight ticket counters of the hand-out as the last fpt_rt_trace* launch of this context left them (all zero after a launch that ran
  * without atomics).  Valid until the context's next render call, which reuses their words; synchronises the context's stream. */
 int fpt_debug_trace_tickets(fpt_context* ctx, uint32_t h_out[8]);
+/* probe (tests): the traversal launch of the path tracer's passes in flight that LISTS the hits of its closest-hit rays, on `count` rays taken as
+ * scattered rays of a path queue -- the interval is the queue's (1e-3, 1e8), whatever the rays' .w words hold -- and no shadow rays.  d_list (fpt_hit) and d_src
+ * (uint32) hold `capacity` entries each: entry s of the list is a hit and d_src[s] the index of the ray that made it, or filler (t = -1, triId = -1, d_src = 0) where a
+ * wave left a slot of its last chunk unused; a miss leaves no entry.  *h_cursor = the list's length (filler included), *h_waves = the waves of the launch, *h_chunk =
+ * the slots a wave draws at a time.  The query form -- d_list = d_src = NULL, capacity = 0 -- sets *h_waves and *h_chunk for a launch of `count` rays and launches
+ * nothing: a caller sizes its arrays from them.  Otherwise refused, before anything is launched, unless capacity >= count + waves x chunk.  Synchronises the context's stream. */
+int fpt_debug_trace_hit_list(fpt_context* ctx, uint32_t count, const fpt_ray* d_rays, fpt_hit* d_list, uint32_t* d_src, uint32_t capacity, uint32_t* h_cursor, uint32_t* h_waves, uint32_t* h_chunk);
 int fpt_rt_bvh_info(fpt_context* ctx, uint32_t* n_nodes, uint32_t* n_leaf_tris, uint32_t* max_depth);
 /* what the builder behind create_geometry produced: node occupancy (wide nodes by number of used child slots), depth, the traversal-stack bound
  * of the tree, SAH costs and build times (host threads used) */

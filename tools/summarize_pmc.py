@@ -37,7 +37,8 @@ def launches(sub):
 
 
 def is_timed_trace(kn):
-    return "trace_kernel<" in kn and "false>" in kn
+    # trace_kernel / trace_kernel_wt (fpt_trace.hip, fpt_trace_wt.hip) and the hit-listing trace_kernel_dense / trace_kernel_dense_wt (fpt_trace_dense.hip)
+    return any(n in kn for n in ("trace_kernel<", "trace_kernel_wt<", "trace_kernel_dense<", "trace_kernel_dense_wt<")) and "false>" in kn
 
 
 fetch, write, valu = launches("fetch"), launches("write"), launches("valu")
